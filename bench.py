@@ -17,6 +17,17 @@ there (WORLD_SIZE is set) and each process is one rank; ``--gpus`` must then agr
 Scaling modes.  Default: weak (``--tasks`` per GPU).  ``--global-tasks G``: strong (G tasks split over the ranks: the C4
 shape is ``--global-tasks 512 --gpus 8`` = 64 tasks per rank).
 
+Plain and full runs.  A plain run sets up, warms up, times ``--steps`` steps and prints the line (with the roofline of the
+inner fit, from events recorded inside those steps).  ``--full`` adds everything else, measured after the timed steps: the
+run-to-convergence loop, parity against the float64 oracle, the two CPU baselines, the meta-test protocol and the other
+BASELINE.json configurations as side objects; ``--no-parity``, ``--no-cpu-baseline``, ``--no-meta-test``,
+``--converge-steps`` and ``--side-configs`` narrow a full run down.
+
+``--dump-outputs DIR`` writes what the last timed step computed (rank 0): ``loss`` (per-task f_out / N_q, what meta_step
+returns), ``phi`` (the fitted GP parameters it returns), ``W`` (the feature-map weight after the Adam step) and ``W_grad``
+(the outer gradient the step's backward left on W), as float32 ``DIR/<name>.npy``.  Inputs are seeded, so the same
+arguments give the same inputs on every run.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -49,7 +60,7 @@ def parse(argv=None):
     ap.add_argument("--kernel", default="rbf", choices=["rbf", "matern"])
     ap.add_argument("--regression", action="store_true",
                     help="standardised real labels and the numeric-label initialisation (noise 0.01: fs_mol/utils/gp_utils.py:17, "
-                         "fs_mol/models/adaptive_dkt.py:112-119) instead of +-1 classification labels; the line then also reports "
+                         "fs_mol/models/adaptive_dkt.py:112-119) instead of +-1 classification labels; with --full the line also reports "
                          "which fraction of the tasks took the float64 path for ill-conditioned tasks")
     ap.add_argument("--converge", action="store_true", help="headline loop runs the inner fit to convergence instead of a fixed I")
     ap.add_argument("--converge-steps", type=int, default=5, help="steps of the second, run-to-convergence timed loop (0: skip)")
@@ -64,14 +75,39 @@ def parse(argv=None):
     ap.add_argument("--side-configs", choices=("auto", "on", "off"), default="auto",
                     help="the other BASELINE.json configurations as side objects of the line, measured AFTER the headline loop like `converged` / "
                          "`meta_test`: c1 (64 x 32 x 64), t512 (512 tasks/GPU), c5 (8 x 1024 x 512), c3 (default GNN+ECFP+fc model, 16-shot) and c3 at "
-                         "the reference's CLI shape (support 64 / query 256).  auto: only on the default C2 command, one GPU")
+                         "the reference's CLI shape (support 64 / query 256); only with --full.  auto: only on the default C2 command, one GPU")
     ap.add_argument("--gemm-tuning", choices=("off", "shipped"), default="shipped",
                     help="algorithm choice of the two library GEMMs of the theta = W feature map (adkf_ift_amd/gemm_tuning.py): "
                          "hipBLASLt's heuristic, or the recorded choice for these shapes (same float32 arithmetic)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / collective rehearsal without a GPU: ranks rendezvous (gloo), all-reduce a dummy gradient, "
                          "time barriers and print a line with value null (tests/test_bench_launcher.py)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beyond the headline figure, after the timed steps: converged loop, parity, CPU "
+                         "baselines, meta_test, side configurations (a plain run leaves all of them out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as float32 DIR/<name>.npy (loss, phi, W, W_grad)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES_PER_ARRAY = 16 << 20   # four arrays: at most 64 MB in all
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Each array as out_dir/<name>.npy in float32.  An array above DUMP_BYTES_PER_ARRAY is replaced by a fixed sample of its
+    elements (sorted flat indices from a generator seeded with 0: the same for every run of the same shape)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        cap = DUMP_BYTES_PER_ARRAY // a.itemsize
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def _free_port() -> int:
@@ -181,6 +217,9 @@ def main():
         raise SystemExit(f"--global-tasks {args.global_tasks} does not divide over {world} ranks")
     if args.dry_run:
         return dry_run(args, rank, world)
+    if not args.full:   # a plain run: only what the headline figure needs
+        args.converge_steps, args.side_configs = 0, "off"
+        args.no_parity = args.no_cpu_baseline = args.no_meta_test = True
 
     import torch
     import torch.distributed as dist
@@ -240,13 +279,13 @@ def main():
             self.features.planes_from(self.opt)  # the optimiser's launch also writes the bfloat16 planes of the new W (no split launch)
 
         def timed_loop(self, cfg_, steps, warmup, events=None, backend=None, dist_=False):
-            for _ in range(warmup):
-                meta_step(self.features, [self.W], self.opt, self.y_s, self.y_q, cfg_, distributed=dist_, backend=backend)
+            for _ in range(warmup):   # (self.last is kept from here on, so the timed steps see the allocator as warmed up)
+                self.last = meta_step(self.features, [self.W], self.opt, self.y_s, self.y_q, cfg_, distributed=dist_, backend=backend)
             sync()
             t0 = time.perf_counter()
             for k in range(steps):
-                meta_step(self.features, [self.W], self.opt, self.y_s, self.y_q, cfg_, distributed=dist_, backend=backend,
-                          fit_events=events[k] if events else None)
+                self.last = meta_step(self.features, [self.W], self.opt, self.y_s, self.y_q, cfg_, distributed=dist_, backend=backend,
+                                      fit_events=events[k] if events else None)
             t_host = time.perf_counter() - t0   # when the host finished ENQUEUEING the steps (== dt would mean host-bound)
             sync()
             dt = time.perf_counter() - t0
@@ -281,6 +320,10 @@ def main():
     ev = make_events(args.steps) if not args.graph else None
     dt, t_host = timed_loop(cfg, args.steps, args.warmup, ev)
     fit_ms = sum(a.elapsed_time(b_) for a, b_ in ev) / len(ev) if ev else None
+    if args.dump_outputs and rank == 0:   # before anything below steps W again
+        loss, phi = wl.last
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().cpu().numpy(), "phi": phi.detach().cpu().numpy(),
+                                         "W": W.detach().cpu().numpy(), "W_grad": W.grad.cpu().numpy()})
 
     # ---- SURVEY 8d "also report run-to-convergence": a second, short timed loop with the fit run to its stopping rules ----
     converged = None
