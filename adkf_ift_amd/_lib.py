@@ -15,6 +15,8 @@ KERNEL_MATERN52 = 1
 IGNORE_GRAD_CORRECTION = 1
 IGNORE_DIRECT_GRAD = 2
 INFO_OUTER_BASE = 100000
+PM_LATENT = 1     # adkf_predict_marginal: var without the observation noise
+PM_MAXIMIZE = 2   # ... ei for maximisation
 
 ERRORS = {-1: "bad argument", -2: "unsupported size (see adkf_max_points)", -3: "workspace too small",
           -4: "HIP launch failed"}
@@ -56,6 +58,8 @@ SIGNATURES = {
                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_predict": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adkf_predict_marginal": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_outer_nll_value_grad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_ift_hypergrad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1,6 +1,9 @@
 """The Bayesian-optimisation caller of the same GP op: ``create_gp`` + the GP-EI loop of
 bayes_opt/bo_utils.py:342-455, on the HIP library.  The GP is fitted on the queried points, Expected Improvement is
-evaluated for EVERY candidate with one ``adkf_predict`` call (the reference loops over candidates one by one).
+evaluated for EVERY candidate with one ``adkf_predict`` call (the reference loops over candidates one by one).  Candidate
+pools beyond ``adkf_max_points()`` rows - or any pool with ``streaming=True`` - go through ``adkf_predict_marginal``, the
+streaming marginal prediction (no size cap, workspace independent of the pool size); ``run_gp_ei_bo(streaming=True)`` then
+gets EI straight from that one call.
 
 Only the Matern-5/2 branch exists here (the Tanimoto kernel of the reference's fingerprint baseline is not a
 distance-based kernel and is out of the library's scope).
@@ -43,10 +46,38 @@ def create_gp(train_x: torch.Tensor, train_y: torch.Tensor, kernel_type: str, de
     return likelihood, model, mll
 
 
+def _support_batch(model: ExactGPLayer, mll: ExactMarginalLogLikelihood):
+    Z = model.train_inputs[0].detach().float().contiguous()
+    y = model.train_targets.detach().float().contiguous()
+    b = gp_ops.GPBatch(Z[None], y[None], mll.priors_row(Z.device), model.kernel_id)
+    phi = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])[None]
+    return b, phi
+
+
 @torch.no_grad()
-def latent_posterior(model: ExactGPLayer, mll: ExactMarginalLogLikelihood, X: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+def streaming_posterior(model: ExactGPLayer, mll: ExactMarginalLogLikelihood, X: torch.Tensor, best_f: Optional[float] = None,
+                        maximize: bool = False):
+    """(mean, latent variance, EI or None) at every row of X in ONE ``adkf_predict_marginal`` call, for pools of any size."""
+    b, phi = _support_batch(model, mll)
+    X = X.detach().float().contiguous()
+    q_off = torch.tensor([0, X.shape[0]], dtype=torch.int64, device=X.device)
+    bf = None if best_f is None else torch.full((1,), float(best_f), dtype=torch.float32, device=X.device)
+    mean, var, ei, info = gp_ops.predict_marginal(b, phi, X, q_off, latent=True, best_f=bf, maximize=maximize)
+    gp_ops.check_info(info, "BO posterior")
+    return mean, var.clamp_min(1e-12), ei
+
+
+@torch.no_grad()
+def latent_posterior(model: ExactGPLayer, mll: ExactMarginalLogLikelihood, X: torch.Tensor,
+                     streaming: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Mean and variance of the LATENT function at X (``model.posterior(X)`` without observation noise, which is what
-    BoTorch's analytic acquisition functions read)."""
+    BoTorch's analytic acquisition functions read).  ``streaming``: True - ``adkf_predict_marginal``; False - ``adkf_predict``
+    (the joint path, at most ``adkf_max_points()`` rows); None - streaming only when X has more rows than that."""
+    if streaming is None:
+        streaming = X.shape[0] > gp_ops._lib.load().adkf_max_points()
+    if streaming:
+        mean, var, _ = streaming_posterior(model, mll, X)
+        return mean, var
     Z = model.train_inputs[0].detach().float().contiguous()
     y = model.train_targets.detach().float().contiguous()
     b = gp_ops.GPBatch(Z[None], y[None], mll.priors_row(Z.device), model.kernel_id, Z_q=X.detach().float().contiguous()[None])
@@ -69,9 +100,10 @@ def expected_improvement(mean: torch.Tensor, var: torch.Tensor, best_f: float, m
 
 def run_gp_ei_bo(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
                  kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
-                 rng: Optional[np.random.Generator] = None) -> List[int]:
+                 rng: Optional[np.random.Generator] = None, streaming: bool = False) -> List[int]:
     """bo_utils.py:342-397 (minimisation; points sorted by ascending y).  Returns the BO record: the best initial index
-    followed by the queried indices in the order the reference appends them."""
+    followed by the queried indices in the order the reference appends them.  ``streaming``: EI of the whole pool from one
+    ``adkf_predict_marginal`` call (no pool-size cap)."""
     rng = rng or np.random.default_rng()
     n = x_all.shape[0]
     y_all = (y_all - y_all.mean()) / y_all.std()
@@ -82,8 +114,11 @@ def run_gp_ei_bo(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int,
         best = yq.min().item()
         likelihood, model, mll = create_gp(xq, yq, kernel_type, device, noise_init, noise_prior)
         fit_gpytorch_scipy(mll)
-        mean, var = latent_posterior(model, mll, x_all)
-        acq = expected_improvement(mean, var, best, maximize=False).cpu()
+        if streaming:
+            acq = streaming_posterior(model, mll, x_all, best_f=best, maximize=False)[2].cpu()
+        else:
+            mean, var = latent_posterior(model, mll, x_all)
+            acq = expected_improvement(mean, var, best, maximize=False).cpu()
         acq[queried] = -float("inf")
         nonzero = int((acq > 0).sum())
         free = lambda taken: [i for i in range(n) if i not in taken]

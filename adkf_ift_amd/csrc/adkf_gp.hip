@@ -17,6 +17,7 @@
 #include "large_fused.h"
 #include "gemm_x3.h"
 #include "dense_x3.h"
+#include "predict_stream.h"
 #if ADKF_VARIANT_DZ   // A/B experiment only (measured slower than the two ProbDZ launches: see its header)
 #include "../../tools/variants/dz.h"
 #endif
@@ -137,6 +138,30 @@ Workspace carve(void* base, int T, int ns, int nq, int d) {
     }
     w.bytes = off;
     return w;
+}
+
+// adkf_predict_marginal borrows regions of a support-only workspace that prediction does not read - [P, W_ss] and, beyond 128
+// points, the blocked sweep's scratch [lg_Dinv, lg_F] - for its row-tile slots.  Both spans are checked here against every
+// buffer prediction reads (a reorder of carve() that broke that makes the span unusable instead of silently overwritten).
+struct SlotRegion { float* base; size_t floats; };
+void pm_slot_regions(const Workspace& w, int T, int ns, SlotRegion (&r)[2]) {
+    const size_t Tz = (size_t)T;
+    r[0] = {w.P, (size_t)(w.Wss - w.P) + Tz * ns * ns};
+    r[1] = {w.lg_Dinv, w.lg_Dinv ? (size_t)(w.lg_F - w.lg_Dinv) + Tz * LB * w.vld : 0};
+    const char* rd[][2] = {   // [begin, end) of what the prediction kernels and k_refine64 (level 0) read or keep
+        {reinterpret_cast<const char*>(w.mean), reinterpret_cast<const char*>(w.D2ss)},   // (mean [T, d] is carved first, D2ss right after)
+        {reinterpret_cast<const char*>(w.D2ss), reinterpret_cast<const char*>(w.D2ss + Tz * ns * ns)},
+        {reinterpret_cast<const char*>(w.Ainv), reinterpret_cast<const char*>(w.Ainv + Tz * ns * ns)},
+        {reinterpret_cast<const char*>(w.vecs), reinterpret_cast<const char*>(w.vecs + Tz * NVEC * w.vld)},
+        {reinterpret_cast<const char*>(w.scal), reinterpret_cast<const char*>(w.scal + Tz * NSCAL)},
+        {reinterpret_cast<const char*>(w.lg_fit), reinterpret_cast<const char*>(w.lg_fit ? w.lg_fit + Tz : nullptr)},
+        {reinterpret_cast<const char*>(w.w64), reinterpret_cast<const char*>(w.w64 ? w.w64 + 2 * Tz * w.w64_stride : nullptr)}};
+    for (SlotRegion& q : r) {
+        if (!q.base || q.floats == 0) { q = {nullptr, 0}; continue; }
+        const char *b0 = reinterpret_cast<const char*>(q.base), *b1 = reinterpret_cast<const char*>(q.base + q.floats);
+        for (const auto& x : rd)
+            if (x[0] && x[0] < b1 && b0 < x[1]) { q = {nullptr, 0}; break; }
+    }
 }
 
 Workspace carve_for(const adkf_batch_t* b, void* ws) {
@@ -1046,6 +1071,96 @@ int adkf_predict(const adkf_batch_t* b, const float* phi, float* mean, float* va
         if (rc) return rc;
     }
     return predict_core(b, w, mean, var, cov, info, st);
+}
+
+int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
+                          const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
+    int rc = check_batch(b, false);
+    if (rc) return rc;
+    if (b->nq_max != 0 || b->Z_q || b->y_q || is_ard(b)) return ADKF_E_BADARG;   // the support set only; ARD is out of scope
+    if (!phi || !q_off || !info || !ws || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
+    if (ei && !best_f) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
+    Workspace w = carve_for(b, ws);
+    if (ws_bytes < w.bytes) return ADKF_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = stage_dist(b, w, false, st);
+    if (rc) return rc;
+    if (b->flags & ADKF_BATCH_REUSE_INNER) {
+        hipMemsetAsync(info, 0, sizeof(int32_t) * (size_t)b->T, st);
+    } else {
+        InnerArgs ia = inner_args(b, w, const_cast<float*>(phi), info);
+        rc = launch_inner(ia, w, st);
+        if (rc) return rc;
+    }
+    // flagged tasks: float64 A^-1 and alpha (a no-op re-evaluation after a fit that already ran it; needed after DEFER_REFINE)
+    launch_refine(make_tv(b, w, false), b, w, false, 0, nullptr, info, st);
+    LAUNCH_OK();
+    if (rows == 0) return 0;
+
+    const int T = b->T, ns = b->ns_max;
+    PmArgs pa{};
+    pa.Zq = Zq; pa.Zs = b->Z_s; pa.mean_s = w.mean; pa.q_off = q_off; pa.rows = rows;
+    pa.n_s = b->n_s; pa.ns_ld = ns; pa.d = b->d; pa.kind = b->kernel; pa.T = T;
+    pa.Ainv = w.Ainv; pa.D2ss = w.D2ss; pa.y_s = b->y_s; pa.scal = w.scal; pa.best_f = best_f;
+    pa.mean = mean; pa.var = var; pa.ei = ei;
+    pa.info = info;
+    pa.refine_thresh = refine32_threshold(); pa.r64_thresh = w.w64 ? r64_threshold() : INFINITY;
+    pa.latent = (flags & ADKF_PM_LATENT) ? 1 : 0; pa.maximize = (flags & ADKF_PM_MAXIMIZE) ? 1 : 0;
+    pa.vec = ((b->d & 3) == 0 && aligned16(Zq) && aligned16(b->Z_s)) ? 1 : 0;
+    const int ns_pad = ceil_div(ns, PM_TM) * PM_TM;
+    pa.buf_ld = ns_pad + 4;
+    constexpr int static_lds = (2 * PM_TM * LD_MN + 2 * PM_TM + 4 * PM_TM) * (int)sizeof(float);
+    constexpr int dyn_max = PM_LDS_BYTES - static_lds;
+    static const bool optin = [] {
+        bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_predict_marginal<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_max) == hipSuccess;
+        ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_predict_marginal<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_max) == hipSuccess;
+        return ok;
+    }();
+    if (!optin) (void)hipGetLastError();
+    // upper bound of the tile count (the true one depends on q_off, which lives on the device)
+    const int64_t tiles = rows / PM_TM + T;
+    // global row-tile slots: [P, W_ss] and, beyond 128 points, the blocked path's scratch [lg_Dinv, lg_F] - neither is read by prediction
+    // a workgroup's row tiles: K (plain); K, C and the vector A^-1 y (refined)
+    auto tile_floats = [&](bool refine) { return refine ? (size_t)2 * PM_TM * pa.buf_ld + ns_pad : (size_t)PM_TM * pa.buf_ld; };
+    auto set_slots = [&](bool refine) {
+        pa.slot_floats = tile_floats(refine);
+        SlotRegion r[2];
+        pm_slot_regions(w, T, ns, r);
+        for (int q = 0; q < 2; ++q) { pa.slots[q] = r[q].base; pa.slot_count[q] = (int)std::min<size_t>(r[q].floats / pa.slot_floats, 1 << 20); }
+        return (int64_t)pa.slot_count[0] + pa.slot_count[1];
+    };
+    // every output row starts at 0: rows outside every task's range and those of skipped tasks (n_s == 0, info != 0) stay so
+    hipMemsetAsync(mean, 0, sizeof(float) * (size_t)rows, st);
+    if (var) hipMemsetAsync(var, 0, sizeof(float) * (size_t)rows, st);
+    if (ei) hipMemsetAsync(ei, 0, sizeof(float) * (size_t)rows, st);
+    auto launch = [&](auto kern, bool refine) {
+        const size_t dyn = tile_floats(refine) * sizeof(float);
+        if (optin && dyn <= (size_t)dyn_max) {
+            int per_cu = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern.lds, PM_NT, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+            const int grid = (int)std::min<int64_t>(tiles, (int64_t)num_cus() * per_cu);
+            kern.lds<<<grid, PM_NT, dyn, st>>>(pa);
+        } else {
+            const int64_t slots = set_slots(refine);
+            if (slots < 1) return ADKF_E_WORKSPACE;
+            const int grid = (int)std::min<int64_t>(tiles, std::min<int64_t>(slots, (int64_t)num_cus() * 8));
+            kern.global<<<grid, PM_NT, 0, st>>>(pa);
+        }
+        return 0;
+    };
+    struct Plain { decltype(&k_predict_marginal<false, false>) lds = &k_predict_marginal<false, false>, global = &k_predict_marginal<false, true>; };
+    struct Refined { decltype(&k_predict_marginal<true, false>) lds = &k_predict_marginal<true, false>, global = &k_predict_marginal<true, true>; };
+    if ((rc = launch(Plain{}, false))) return rc;
+    if ((rc = launch(Refined{}, true))) return rc;
+    if (w.w64) {
+        Pm64Args p64{pa, w.w64, w.w64_stride};
+        const int gx = (int)std::min<int64_t>(64, (rows + PM64_NT / 64 - 1) / (PM64_NT / 64));
+        k_predict_marginal64<<<dim3(gx, T), PM64_NT, 0, st>>>(p64);
+    }
+    LAUNCH_OK();
+    return 0;
 }
 
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

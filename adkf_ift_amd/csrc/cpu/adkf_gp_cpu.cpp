@@ -516,6 +516,57 @@ int adkf_predict(const adkf_batch_t* b, const float* phi, float* mean, float* va
     return 0;
 }
 
+int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
+                          const float* best_f, float* mean, float* var, float* ei, int32_t* info, void*, size_t, void*) {
+    if (int rc = check(b, false)) return rc;
+    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !q_off || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
+    if (ei && !best_f) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
+    const int d = b->d;
+    // rows outside every task's range and those of tasks with n_s == 0 or info != 0 stay 0 (as on the GPU)
+    if (rows > 0) {
+        std::fill(mean, mean + rows, 0.f);
+        if (var) std::fill(var, var + rows, 0.f);
+        if (ei) std::fill(ei, ei + rows, 0.f);
+    }
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        const int n = std::min(ns_of(b, t), b->ns_max);
+        info[t] = 0;
+        if (n <= 0) continue;
+        const float* Zs = b->Z_s + (size_t)t * b->ns_max * d;
+        const double p[3] = {phi[t * 3], phi[t * 3 + 1], phi[t * 3 + 2]};
+        Inner in = inner_stage(sqdist(Zs, n, Zs, n, d), b->y_s + (size_t)t * b->ns_max, n, p, b->priors + t * 4, b->kernel, false, false);
+        info[t] = in.info;
+        int64_t lo = std::min(std::max<int64_t>(q_off[t], 0), rows), hi = std::min(std::max<int64_t>(q_off[t + 1], lo), rows);
+        const double il2 = 1.0 / (in.l * in.l);
+        std::vector<double> k(n), c(n);
+        for (int64_t r = lo; r < hi; ++r) {
+            if (in.info) break;
+            const Mat D = sqdist(Zq + (size_t)r * d, 1, Zs, n, d);
+            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); k[j] = in.s * k0; }
+            double mu = 0.0, q = 0.0;
+            for (int j = 0; j < n; ++j) {
+                double cj = 0.0;
+                for (int i = 0; i < n; ++i) cj += k[i] * in.Ainv[(size_t)i * n + j];
+                mu += cj * (double)b->y_s[(size_t)t * b->ns_max + j];
+                q += cj * k[j];
+            }
+            const double vl = in.s - q;
+            mean[r] = (float)mu;
+            if (var) var[r] = (float)((flags & ADKF_PM_LATENT) ? vl : vl + in.noise);
+            if (ei) {
+                const double sg = std::sqrt(std::max(vl, 1e-12)), bf = best_f[t];
+                const double u = ((flags & ADKF_PM_MAXIMIZE) ? (mu - bf) : (bf - mu)) / sg;
+                ei[r] = (float)(sg * (u * 0.5 * std::erfc(-u / std::sqrt(2.0)) + std::exp(-0.5 * u * u) / std::sqrt(2.0 * M_PI)));
+            }
+        }
+    }
+    return 0;
+}
+
 static int outer_common(const adkf_batch_t* b, const float* phi, int flags, bool with_hessian, float* f_out, float* g_phi, float* dZ_s, float* dZ_q,
                         float* v_out, float* H_out, int32_t* info) {
     const int d = b->d;

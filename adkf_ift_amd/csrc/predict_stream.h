@@ -1,0 +1,375 @@
+// Streaming marginal prediction (adkf_predict_marginal): mean, variance and Expected Improvement of PACKED query rows against
+// a fitted support set, for query sets of any size, in a workspace that does not depend on the number of rows.
+//
+// Work items are (task, 64-row query tile); a persistent grid walks them in order, every workgroup finding the task of its
+// tile from the row offsets q_off[T + 1] (clamped to [0, rows): bad offsets cannot make it read or write out of bounds).
+// Per tile, for each 64-column panel of the support set:
+//     D^2 = |q|^2 + |s|^2 - 2 q.s on the FP32 MFMA, the query rows centred with the support column mean (as ProbDist), the row
+//           norms summed while the operands are staged;
+//     K   = os kappa(D^2 / l^2)                              -> a [64, ns] row tile in LDS (or a global slot, see below)
+// then C = K A^-1 panel by panel (A^-1 rows through L2), reduced on the fly to mean_i = sum_j C_ij y_j and
+// var_i = os - sum_j C_ij K_ij (as k_predict), EI in the epilogue, 4 to 12 bytes written per row.  Nothing of size rows x ns
+// ever goes to HBM.
+//
+// Tasks that ProbCres / ProbCfix refine in adkf_predict - more than 128 points, or (s + noise) max diag(A^-1) above the float32
+// refinement threshold - take REFINE = true: the same one step C' = C + R A^-1 with R = K - C A (A generated from D2ss), applied
+// to the two reductions directly:
+//     C' y = C y + R (A^-1 y)        and        sum_j C'_ij K_ij = sum_j C_ij K_ij + sum_k R_ik C_ik
+// (the second because (R A^-1) K_i^T = R (A^-1 K_i^T) = R C_i^T for the symmetric A^-1; the correction terms are of the size of
+// the residual, so this reassociation changes them by a relative eps32 only).  That keeps C as one more row tile and A^-1 y as
+// a vector, and saves ProbCfix's product.  The two kinds of task run in two launches of the same kernel (each skips the other's
+// tasks), so the common one needs one row tile of LDS only.  Row tiles that do not fit in LDS (beyond 512 points plain, 256
+// refined) live in per-workgroup slots carved from workspace regions prediction does not read (adkf_gp.hip: pm_slot_regions);
+// the grid is then as large as the number of slots - correct, not tuned.
+//
+// Per 64-column support panel the 64 x d query tile is streamed (and its norms summed) again: ns / 64 times per tile.  At
+// ns <= 64 that is once; beyond, it is the price of not holding a [64, d] tile (512 KB at d = 2048) in LDS.
+//
+// Rows that belong to no task's range, and the rows of tasks with n_s == 0 or info != 0, are written as 0 (the host zeroes the
+// outputs first; the kernels skip such tasks).
+//
+// Tasks flagged for the float64 path (refine64.h) are skipped here; k_predict_marginal64 evaluates their rows in float64 from the features,
+// against the float64 A^-1 and alpha k_refine64 left in the workspace.
+//
+// Deterministic: no atomics; a row's result depends on its task's data and its own features only.
+#pragma once
+#include "refine64.h"
+
+namespace adkf {
+
+constexpr int PM_TM = 64;                   // query rows per tile (and support columns per panel)
+constexpr int PM_NT = 256;
+constexpr int PM_LDS_BYTES = 160 * 1024;
+
+struct PmArgs {
+    const float *Zq, *Zs, *mean_s;          // packed query rows [rows, d]; support [T, ns_ld, d]; support column means [T, d]
+    const int64_t* q_off; int64_t rows;
+    const int32_t* n_s; int ns_ld, d, kind, T;
+    const float *Ainv, *D2ss, *y_s, *scal;
+    const float* best_f;
+    float *mean, *var, *ei;
+    float* slots[2]; int slot_count[2];     // global row-tile slots (GLOBAL instances): two regions, slot_floats each
+    size_t slot_floats;
+    const int32_t* info;                    // tasks with info != 0 (failed factorisation) are skipped: their rows stay 0
+    float refine_thresh, r64_thresh;        // r64_thresh: +inf when the workspace has no float64 region
+    int latent, maximize, vec;
+    int buf_ld;                             // leading dimension of a row tile
+};
+
+__device__ __forceinline__ int pm_ns(const PmArgs& a, int t) {
+    const int n = a.n_s ? a.n_s[t] : a.ns_ld;
+    return n < 0 ? 0 : (n > a.ns_ld ? a.ns_ld : n);
+}
+__device__ __forceinline__ void pm_range(const PmArgs& a, int t, int64_t& lo, int64_t& hi) {
+    lo = a.q_off[t]; hi = a.q_off[t + 1];
+    lo = lo < 0 ? 0 : (lo > a.rows ? a.rows : lo);
+    hi = hi < lo ? lo : (hi > a.rows ? a.rows : hi);
+}
+// which of the three evaluations owns task t: 0 plain, 1 refined C (the gate of ProbCres / ProbCfix), 2 float64; -1 nobody
+__device__ __forceinline__ int pm_kind_of(const PmArgs& a, int t) {
+    if (a.info[t] != 0 || pm_ns(a, t) <= 0) return -1;
+    const float* sc = a.scal + (size_t)t * NSCAL;
+    if (sc[S_PIVR_A] > a.r64_thresh) return 2;
+    return (a.ns_ld > 128 || sc[S_CONDA] > a.refine_thresh) ? 1 : 0;
+}
+
+// acc[2][2] (this wave's 32 x 32 quarter of a 64 x 64 panel) = sum_k A(i, k) B(j, k), both operands K-contiguous, staged
+// through LDS in GK-wide chunks: fa4(i, k, v) / fb4(j, k, v) fill four consecutive k (zero outside their ranges).  SQ: the
+// sums of squares of the staged rows of A and B are accumulated in sqa / sqb (ProbDist's norms).
+template <bool SQ, class FA, class FB>
+__device__ __forceinline__ void pm_mm(f32x4 (&acc)[2][2], int K, float* As, float* Bs, FA fa4, FB fb4, float (&sqa)[2], float (&sqb)[2]) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wr = wv >> 1, wc = wv & 1, fi = lane & 15, fk = lane >> 4;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    float ra[2][4], rb[2][4];
+    auto fetch = [&](int k0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int ps = 0; ps < 2; ++ps) {
+            const int r = (tid >> 3) + ps * 32, k = k0 + (tid & 7) * 4;
+            fa4(r, k, ra[ps]);
+            fb4(r, k, rb[ps]);
+        }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < K; k0 += GK) {
+#pragma unroll
+        for (int ps = 0; ps < 2; ++ps)
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+                const int r = (tid >> 3) + ps * 32;
+                As[r * LD_MN + (tid & 7) * 4 + x] = ra[ps][x];
+                Bs[r * LD_MN + (tid & 7) * 4 + x] = rb[ps][x];
+                if constexpr (SQ) { sqa[ps] = fmaf(ra[ps][x], ra[ps][x], sqa[ps]); sqb[ps] = fmaf(rb[ps][x], rb[ps][x], sqb[ps]); }
+            }
+        __syncthreads();
+        if (k0 + GK < K) fetch(k0 + GK);   // next chunk's loads fly while this one is multiplied
+#pragma unroll
+        for (int s = 0; s < GK / 4; ++s) {
+            float af[2], bf[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) af[i] = As[(wr * 32 + i * 16 + fi) * LD_MN + 4 * s + fk];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bf[j] = Bs[(wc * 32 + j * 16 + fi) * LD_MN + 4 * s + fk];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], bf[j], acc[i][j], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+}
+
+// the element (row, column) of a 64 x 64 panel that acc[i][j][r] holds (C/D map of the 16 x 16 MFMA)
+__device__ __forceinline__ int pm_row(int i, int r) { const int lane = threadIdx.x & 63, wr = (threadIdx.x >> 6) >> 1; return wr * 32 + i * 16 + (lane >> 4) * 4 + r; }
+__device__ __forceinline__ int pm_col(int j) { const int lane = threadIdx.x & 63, wc = (threadIdx.x >> 6) & 1; return wc * 32 + j * 16 + (lane & 15); }
+
+// four consecutive entries of a K-contiguous row (zero beyond k_end); vec: 16-byte loads are legal
+__device__ __forceinline__ void pm_ld4(const float* row, int k, int k_end, bool vec, float (&v)[4]) {
+    if (vec && k + 3 < k_end) { const float4 q = *reinterpret_cast<const float4*>(row + k); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; return; }
+#pragma unroll
+    for (int x = 0; x < 4; ++x) v[x] = k + x < k_end ? row[k + x] : 0.f;
+}
+
+// EI from the latent variance: sigma (u Phi(u) + phi(u)), u = +-(best_f - mean) / sigma; Phi through erfc (tails keep their digits)
+__device__ __forceinline__ float pm_ei(float mean, float var_latent, float best, int maximize) {
+    const float sigma = sqrtf(fmaxf(var_latent, 1e-12f));
+    const float u = (maximize ? (mean - best) : (best - mean)) / sigma;
+    const float cdf = 0.5f * erfcf(-u * 0.70710678118654752f);
+    const float pdf = 0.3989422804014327f * expf(-0.5f * u * u);
+    return sigma * fmaf(u, cdf, pdf);
+}
+
+template <bool REFINE, bool GLOBAL>
+__global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float pm_lds[];
+    __shared__ float As[PM_TM * LD_MN], Bs[PM_TM * LD_MN];
+    __shared__ float rowsq[2][PM_TM];
+    __shared__ float red[2][2][PM_TM];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wc = wv & 1;
+    const int ld = a.buf_ld;
+    float *Kb, *Cb = nullptr, *wv_s = nullptr;   // row tiles K, C; A^-1 y (REFINE)
+    int grid = gridDim.x;
+    if (GLOBAL) {
+        const int s = blockIdx.x;
+        Kb = s < a.slot_count[0] ? a.slots[0] + (size_t)s * a.slot_floats : a.slots[1] + (size_t)(s - a.slot_count[0]) * a.slot_floats;
+    } else {
+        Kb = pm_lds;
+    }
+    if (REFINE) { Cb = Kb + (size_t)PM_TM * ld; wv_s = Cb + (size_t)PM_TM * ld; }
+    const int64_t d = a.d;
+    // persistent walk over the tiles of all tasks, in order: (t, first tile of t) is a cursor that only moves forward
+    int t = 0;
+    int64_t tile0 = 0;
+    for (int64_t g = blockIdx.x;; g += grid) {
+        int64_t lo, hi;
+        for (;;) {
+            if (t >= a.T) return;
+            pm_range(a, t, lo, hi);
+            const int64_t nt = (hi - lo + PM_TM - 1) / PM_TM;
+            const bool mine = pm_kind_of(a, t) == (REFINE ? 1 : 0);
+            if (g < tile0 + nt && mine) break;
+            // next task: the first tile index >= its first tile that this workgroup owns
+            tile0 += nt; ++t;
+            if (g < tile0) g = tile0 + (((int64_t)blockIdx.x - tile0) % grid + grid) % grid;
+        }
+        const int64_t r0 = lo + (g - tile0) * PM_TM;
+        const int m = (int)(hi - r0 < PM_TM ? hi - r0 : PM_TM);
+        const int n = pm_ns(a, t);
+        const float* sc = a.scal + (size_t)t * NSCAL;
+        const float os = sc[S_OS], noise = sc[S_NOISE], il2 = 1.f / (sc[S_LS] * sc[S_LS]);
+        const int kind = a.kind;
+        const float* Zs = a.Zs + (size_t)t * a.ns_ld * d;
+        const float* mu = a.mean_s + (size_t)t * d;
+        const float* Ai = a.Ainv + (size_t)t * a.ns_ld * a.ns_ld;
+        const float* ys = a.y_s + (size_t)t * a.ns_ld;
+        const int np = (n + PM_TM - 1) / PM_TM;   // support panels
+        const int nk = np * PM_TM;                // K extent of the products over the support set (zero-padded)
+        f32x4 acc[2][2];
+        // ---- K row tile
+        for (int p = 0; p < np; ++p) {
+            const int j0 = p * PM_TM;
+            float sqa[2] = {0.f, 0.f}, sqb[2] = {0.f, 0.f};
+            pm_mm<true>(acc, a.d, As, Bs,
+                [&](int i, int k, float (&v)[4]) {
+                    if (i >= m) { v[0] = v[1] = v[2] = v[3] = 0.f; return; }
+                    float z[4], c[4];
+                    pm_ld4(a.Zq + (size_t)(r0 + i) * d, k, a.d, a.vec, z); pm_ld4(mu, k, a.d, a.vec, c);
+#pragma unroll
+                    for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
+                },
+                [&](int j, int k, float (&v)[4]) {
+                    if (j0 + j >= n) { v[0] = v[1] = v[2] = v[3] = 0.f; return; }
+                    float z[4], c[4];
+                    pm_ld4(Zs + (size_t)(j0 + j) * d, k, a.d, a.vec, z); pm_ld4(mu, k, a.d, a.vec, c);
+#pragma unroll
+                    for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
+                }, sqa, sqb);
+#pragma unroll
+            for (int ps = 0; ps < 2; ++ps) {   // the eight threads that staged a row are eight adjacent lanes
+                float x = sqa[ps], y = sqb[ps];
+                x += dpp_f<DPP_XOR1>(x); x += dpp_f<DPP_XOR2>(x); x += dpp_f<DPP_HALF_MIRROR>(x);
+                y += dpp_f<DPP_XOR1>(y); y += dpp_f<DPP_XOR2>(y); y += dpp_f<DPP_HALF_MIRROR>(y);
+                if ((tid & 7) == 0) { rowsq[0][(tid >> 3) + ps * 32] = x; rowsq[1][(tid >> 3) + ps * 32] = y; }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ii = pm_row(i, r), jj = pm_col(j);
+                        const float d2 = fmaxf(rowsq[0][ii] + rowsq[1][jj] - 2.f * acc[i][j][r], 0.f);
+                        Kb[(size_t)ii * ld + j0 + jj] = (ii < m && j0 + jj < n) ? os * kappa0(kind, d2 * il2) : 0.f;
+                    }
+            __syncthreads();
+        }
+        float s1[2][4], s2[2][4];   // per-lane partial sums of the rows this lane holds: C y and C K
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { s1[i][r] = 0.f; s2[i][r] = 0.f; }
+        float dummy[2];
+        auto opK = [&](const float* B) { return [=](int i, int k, float (&v)[4]) {
+#pragma unroll
+            for (int x = 0; x < 4; ++x) v[x] = B[(size_t)i * ld + k + x];
+        }; };
+        // ---- C = K A^-1 (A^-1 symmetric: row j of A^-1 is column j, contiguous in k)
+        for (int p = 0; p < np; ++p) {
+            const int j0 = p * PM_TM;
+            pm_mm<false>(acc, nk, As, Bs, opK(Kb),
+                [&](int j, int k, float (&v)[4]) {
+                    if (j0 + j >= n) { v[0] = v[1] = v[2] = v[3] = 0.f; return; }
+                    pm_ld4(Ai + (size_t)(j0 + j) * a.ns_ld, k, n, false, v);
+                }, dummy, dummy);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ii = pm_row(i, r), jj = j0 + pm_col(j);
+                        if (REFINE) Cb[(size_t)ii * ld + jj] = acc[i][j][r];
+                        if (jj < n) { s1[i][r] = fmaf(acc[i][j][r], ys[jj], s1[i][r]); s2[i][r] = fmaf(acc[i][j][r], Kb[(size_t)ii * ld + jj], s2[i][r]); }
+                    }
+        }
+        if (REFINE) {
+            // A^-1 y (rows of A^-1, fixed order), then R = K - C A panel by panel, folded into the two sums
+            for (int j = tid; j < nk; j += PM_NT) {
+                float w = 0.f;
+                if (j < n) for (int k = 0; k < n; ++k) w = fmaf(Ai[(size_t)j * a.ns_ld + k], ys[k], w);
+                wv_s[j] = w;
+            }
+            __syncthreads();
+            const float* Dss = a.D2ss + (size_t)t * a.ns_ld * a.ns_ld;
+            float c1[2][4], c2[2][4];   // the correction terms, summed apart from the main terms and added last
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { c1[i][r] = 0.f; c2[i][r] = 0.f; }
+            for (int p = 0; p < np; ++p) {
+                const int j0 = p * PM_TM;
+                pm_mm<false>(acc, nk, As, Bs, opK(Cb),
+                    [&](int j, int k, float (&v)[4]) {
+                        const int jj = j0 + j;
+#pragma unroll
+                        for (int x = 0; x < 4; ++x)
+                            v[x] = (jj < n && k + x < n) ? os * kappa0(kind, Dss[(size_t)jj * a.ns_ld + k + x] * il2) + (k + x == jj ? noise : 0.f) : 0.f;
+                    }, dummy, dummy);
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int ii = pm_row(i, r), jj = j0 + pm_col(j);
+                            if (jj < n) {
+                                const float res = Kb[(size_t)ii * ld + jj] - acc[i][j][r];
+                                c1[i][r] = fmaf(res, wv_s[jj], c1[i][r]); c2[i][r] = fmaf(res, Cb[(size_t)ii * ld + jj], c2[i][r]);
+                            }
+                        }
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { s1[i][r] += c1[i][r]; s2[i][r] += c2[i][r]; }
+        }
+        // ---- row reductions: the 16 lanes of a row group, then the two column waves, in a fixed order
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float x = s1[i][r], y = s2[i][r];
+                x += dpp_f<DPP_XOR1>(x); x += dpp_f<DPP_XOR2>(x); x += dpp_f<DPP_HALF_MIRROR>(x); x += dpp_f<DPP_MIRROR>(x);
+                y += dpp_f<DPP_XOR1>(y); y += dpp_f<DPP_XOR2>(y); y += dpp_f<DPP_HALF_MIRROR>(y); y += dpp_f<DPP_MIRROR>(y);
+                if ((lane & 15) == 0) { red[wc][0][pm_row(i, r)] = x; red[wc][1][pm_row(i, r)] = y; }
+            }
+        __syncthreads();
+        if (tid < m) {
+            const size_t row = (size_t)(r0 + tid);
+            const float mean = red[0][0][tid] + red[1][0][tid];
+            const float vl = os - (red[0][1][tid] + red[1][1][tid]);
+            a.mean[row] = mean;
+            if (a.var) a.var[row] = a.latent ? vl : vl + noise;
+            if (a.ei) a.ei[row] = pm_ei(mean, vl, a.best_f[t], a.maximize);
+        }
+        __syncthreads();   // red / rowsq / the row tiles are rewritten by the next tile
+    }
+}
+
+// ---- the float64 evaluation of the rows of flagged tasks: one wave per row, difference-form distances from the features,
+// k_refine64's float64 A^-1 (region A1) and the kernel row parked in LDS
+constexpr int PM64_NT = 256;
+struct Pm64Args { PmArgs p; const double* w64; size_t w64_stride; };
+
+__global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(Pm64Args a64) {
+    const PmArgs& a = a64.p;
+    __shared__ double kr[PM64_NT / 64][R64_MAXN];
+    const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (pm_kind_of(a, t) != 2) return;   // (uniform)
+    const int n = pm_ns(a, t), ld = a.ns_ld;
+    if (n <= 0 || n > R64_MAXN) return;
+    int64_t lo, hi;
+    pm_range(a, t, lo, hi);
+    const float* sc = a.scal + (size_t)t * NSCAL;
+    const double os = sc[S_OS], noise = sc[S_NOISE], ls = sc[S_LS], il2 = 1.0 / (ls * ls);
+    const double* A1 = a64.w64 + (size_t)t * a64.w64_stride;   // float64 A^-1 [ld, ld]
+    const float* Zs = a.Zs + (size_t)t * ld * a.d;
+    const float* ys = a.y_s + (size_t)t * ld;
+    double* k = kr[wv];
+    for (int64_t r = lo + (int64_t)blockIdx.x * (PM64_NT / 64) + wv; r < hi; r += (int64_t)gridDim.x * (PM64_NT / 64)) {
+        const float* zq = a.Zq + (size_t)r * a.d;
+        for (int j = lane; j < n; j += 64) {
+            const float* zs = Zs + (size_t)j * a.d;
+            double s = 0.0;
+            for (int c = 0; c < a.d; ++c) { const double e = (double)zq[c] - (double)zs[c]; s += e * e; }
+            const double u = s * il2;
+            double kv;
+            if (a.kind == ADKF_KERNEL_RBF) kv = exp(-0.5 * u);
+            else { const double rr = sqrt(u); kv = (1.0 + 2.23606797749979 * rr + (5.0 / 3.0) * u) * exp(-2.23606797749979 * rr); }
+            k[j] = os * kv;
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        double s1 = 0.0, s2 = 0.0;
+        for (int j = lane; j < n; j += 64) {
+            double c = 0.0;
+            for (int q = 0; q < n; ++q) c += k[q] * A1[(size_t)q * ld + j];
+            s1 += c * (double)ys[j];
+            s2 += c * k[j];
+        }
+        for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+        if (lane == 0) {
+            const float mean = (float)s1, vl = (float)(os - s2);
+            a.mean[r] = mean;
+            if (a.var) a.var[r] = a.latent ? vl : (float)(os - s2 + noise);
+            if (a.ei) a.ei[r] = pm_ei(mean, vl, a.best_f[t], a.maximize);
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    }
+}
+
+}  // namespace adkf

@@ -140,9 +140,12 @@ def run_on_batches(model, batches: List[DKTBatch], batch_labels: List[torch.Tens
 
 
 @torch.no_grad()
-def meta_test(model, mb: MetaBatch, max_evals: int = 200, gtol: float = 1e-5, ftol: float = 2.22e-9, want_var: bool = False):
+def meta_test(model, mb: MetaBatch, max_evals: int = 200, gtol: float = 1e-5, ftol: float = 2.22e-9, want_var: bool = False,
+              streaming: bool = False):
     """All tasks at once.  Returns (predictions [T, Nq_max], variance or None, phi* [T, 3], n_evals [T]); padded query
-    slots hold 0.  Classification predictions are already passed through the sigmoid."""
+    slots hold 0.  Classification predictions are already passed through the sigmoid.  ``streaming``: fit on a support-only
+    batch and predict the packed query rows with ``gp_ops.predict_marginal`` (no padding to the largest query set, no size
+    cap); same layout out."""
     from . import gp_ops
 
     cfg = model.config
@@ -152,14 +155,23 @@ def meta_test(model, mb: MetaBatch, max_evals: int = 200, gtol: float = 1e-5, ft
     y_s, _ = mb.labels(cfg.use_numeric_labels)
     dev = Z_s.device
     priors = torch.empty(mb.num_tasks, 4, dtype=torch.float32, device=dev)
+    if streaming and cfg.use_ard:
+        raise ValueError("meta_test(streaming=True) does not support ARD kernels")
     b = gp_ops.GPBatch(Z_s.float().contiguous(), y_s.to(dev).float().contiguous(), priors, cfg.gp_kernel,
-                       Z_q=Z_q.float().contiguous(), n_s=mb.n_s, n_q=mb.n_q, ard=cfg.use_ard)
+                       Z_q=None if streaming else Z_q.float().contiguous(), n_s=mb.n_s, n_q=None if streaming else mb.n_q,
+                       ard=cfg.use_ard)
     phi0, _ = gp_ops.init_params_batch(b, cfg.use_numeric_labels, cfg.use_lengthscale_prior)
     b.flags = gp_ops.REUSE_DIST | gp_ops.DEFER_REFINE     # (the prediction redoes ill-conditioned tasks in float64 itself)
     phi, _, _, n_evals, info = gp_ops.fit(b, phi0, max_evals, gtol, ftol)
     gp_ops.check_info(info, "meta-test inner fit")
     b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
-    mean, var, _, info = gp_ops.predict(b, phi, want_var=want_var)
+    if streaming:
+        Zq_p, q_off = gp_ops.pack_rows(Z_q.float(), mb.n_q)
+        mean_p, var_p, _, info = gp_ops.predict_marginal(b, phi, Zq_p, q_off, want_var=want_var)
+        mean = gp_ops.unpack_rows(mean_p, q_off, Z_q.shape[1])
+        var = gp_ops.unpack_rows(var_p, q_off, Z_q.shape[1]) if want_var else None
+    else:
+        mean, var, _, info = gp_ops.predict(b, phi, want_var=want_var)
     gp_ops.check_info(info, "meta-test prediction")
     if was_training:
         model.train()
@@ -168,16 +180,16 @@ def meta_test(model, mb: MetaBatch, max_evals: int = 200, gtol: float = 1e-5, ft
 
 
 def evaluate_tasks(model, tasks: Sequence[DKTBatch], names: Optional[Sequence[str]] = None, tasks_per_call: int = 64,
-                   max_evals: int = 200) -> Dict[str, object]:
+                   max_evals: int = 200, streaming: bool = False) -> Dict[str, object]:
     """``evaluate_adkt_model`` for tasks that are already in memory: per-task metric records, ``tasks_per_call`` tasks
-    per library call (one disconnected graph each)."""
+    per library call (one disconnected graph each).  ``streaming`` is passed to ``meta_test``."""
     names = list(names) if names is not None else [f"task{i}" for i in range(len(tasks))]
     dev = model.device
     out: Dict[str, object] = {}
     for lo in range(0, len(tasks), tasks_per_call):
         chunk = tasks[lo:lo + tasks_per_call]
         mb = collate_meta_batch(chunk).to(dev)
-        preds, _, _, _ = meta_test(model, mb, max_evals=max_evals)
+        preds, _, _, _ = meta_test(model, mb, max_evals=max_evals, streaming=streaming)
         preds = preds.cpu().numpy()
         for k, task in enumerate(chunk):
             nq = task.num_query_samples

@@ -271,6 +271,71 @@ def predict(b: GPBatch, phi: torch.Tensor, want_var=True, want_cov=False):
     return mean, var, cov, info
 
 
+def pack_rows(Z_q: torch.Tensor, n_q: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Padded query rows ``Z_q [T, Nq, d]`` (true sizes ``n_q [T]``, default all ``Nq``) -> packed ``Zq [rows, d]`` and the row
+    offsets ``q_off [T + 1]`` (int64: task t owns rows ``q_off[t]:q_off[t+1]``), on ``Z_q``'s device.  Pure torch; runs on
+    CPU tensors too."""
+    if Z_q.dim() != 3:
+        raise ValueError("Z_q must be [T, N_q, d]")
+    T, nq, d = Z_q.shape
+    if n_q is None:
+        n = torch.full((T,), nq, dtype=torch.int64, device=Z_q.device)
+    else:
+        n = n_q.to(device=Z_q.device, dtype=torch.int64).reshape(T).clamp(0, nq)
+    q_off = torch.zeros(T + 1, dtype=torch.int64, device=Z_q.device)
+    q_off[1:] = torch.cumsum(n, 0)
+    mask = torch.arange(nq, device=Z_q.device)[None, :] < n[:, None]
+    return Z_q[mask].reshape(-1, d).contiguous(), q_off
+
+
+def unpack_rows(x: torch.Tensor, q_off: torch.Tensor, nq: int) -> torch.Tensor:
+    """Per-row results ``x [rows]`` -> ``[T, nq]`` (zeros in the padding): the inverse of ``pack_rows`` for outputs."""
+    T = q_off.numel() - 1
+    n = (q_off[1:] - q_off[:-1]).to(x.device)
+    out = torch.zeros(T, nq, dtype=x.dtype, device=x.device)
+    mask = torch.arange(nq, device=x.device)[None, :] < n[:, None]
+    out[mask] = x
+    return out
+
+
+def predict_marginal(b: GPBatch, phi: torch.Tensor, Zq: torch.Tensor, q_off: torch.Tensor, latent: bool = False,
+                     best_f: Optional[torch.Tensor] = None, maximize: bool = False, want_var: bool = True):
+    """Marginal posterior of packed query rows (``pack_rows``) against the support set of ``b`` (which carries no query set):
+    returns (mean [rows], var [rows] or None, ei [rows] or None, info [T]).  ``var`` includes the observation noise unless
+    ``latent``; ``ei`` (only with ``best_f [T]``) is Expected Improvement on the latent variance, for minimisation unless
+    ``maximize``.  No size cap and a workspace independent of the number of rows (include/adkf_gp.h)."""
+    lib = _lib.load()
+    if b.nq != 0:
+        raise ValueError("predict_marginal takes a support-only batch (no Z_q / y_q): the query rows come packed in Zq")
+    if b.ard:
+        raise ValueError("predict_marginal does not support ARD batches")
+    phi = b.check_phi(phi)
+    Zq = _f32(Zq, "Zq")
+    if Zq.dim() != 2 or Zq.shape[1] != b.d:
+        raise ValueError(f"Zq must be [rows, d] = [rows, {b.d}], got {tuple(Zq.shape)}")
+    if not q_off.is_cuda or q_off.dtype != torch.int64 or q_off.numel() != b.T + 1:
+        raise ValueError(f"q_off must be int64 [T + 1] = [{b.T + 1}] on the GPU")
+    q_off = q_off.contiguous()
+    if best_f is not None:
+        best_f = _f32(best_f, "best_f").reshape(-1)
+        if best_f.numel() != b.T:
+            raise ValueError(f"best_f must have T = {b.T} entries")
+    for name, t in (("Zq", Zq), ("q_off", q_off), ("best_f", best_f)):
+        if t is not None and t.device != b.device:
+            raise ValueError(f"{name} lives on {t.device}, the batch on {b.device}")
+    rows = Zq.shape[0]
+    mean = _new(b, rows)
+    var = _new(b, rows) if want_var else None
+    ei = _new(b, rows) if best_f is not None else None
+    info = _new(b, b.T, dtype=torch.int32)
+    flags = (_lib.PM_LATENT if latent else 0) | (_lib.PM_MAXIMIZE if maximize else 0)
+    ws, nb = b.workspace()
+    cb = b.c_struct()
+    _lib.check(lib.adkf_predict_marginal(C.byref(cb), _ptr(phi), flags, _ptr(Zq), _ptr(q_off), rows, _ptr(best_f), _ptr(mean),
+                                         _ptr(var), _ptr(ei), _ptr(info), _ptr(ws), nb, _stream(b.device)), "adkf_predict_marginal")
+    return mean, var, ei, info
+
+
 def double_path_tasks(b: GPBatch) -> torch.Tensor:
     """[T] int32: 1 where the last ``ift_hypergrad`` / ``outer_nll_value_grad`` on this batch sent the task through the float64
     path (ill-conditioned tasks, csrc/refine64.h).  Diagnostic."""

@@ -171,6 +171,21 @@ int adkf_fit(const adkf_batch_t* b, float* phi, const adkf_fit_options_t* opt, f
 int adkf_predict(const adkf_batch_t* b, const float* phi, float* mean, float* var, float* cov, int32_t* info,
                  void* ws, size_t ws_bytes, void* stream);
 
+/* Streaming marginal prediction: the predictive mean, variance and Expected Improvement of query rows of ANY number, in a
+ * workspace of exactly adkf_workspace_bytes(T, ns_max, 0, d) bytes whatever `rows` is (csrc/predict_stream.h).
+ *   b      the support set only: nq_max == 0, Z_q == y_q == NULL (ADKF_E_BADARG otherwise, and for ARD batches);
+ *          REUSE_INNER after adkf_fit on the same batch and workspace (with or without DEFER_REFINE) reuses A^-1, alpha and
+ *          the scalars, otherwise they are evaluated at phi as adkf_predict does; REUSE_DIST covers D2ss;
+ *   Zq     packed query rows [rows, d]; task t owns rows [q_off[t], q_off[t+1]) (q_off: [T+1] int64, device); every range
+ *          is clamped to [0, rows);
+ *   mean   [rows]; var [rows] (nullable) includes the noise unless ADKF_PM_LATENT; ei [rows] (nullable, needs best_f [T]):
+ *          Expected Improvement sigma (u Phi(u) + phi(u)) on the LATENT variance, u = (best_f - mean) / sigma for
+ *          minimisation, (mean - best_f) / sigma with ADKF_PM_MAXIMIZE; info [T] as adkf_predict.  Rows that belong to no
+ *          task's range, and the rows of tasks with n_s == 0 or info != 0, are written as 0. */
+#define ADKF_PM_LATENT 1   /* var without the observation noise: the latent f, what BoTorch's analytic EI reads */
+#define ADKF_PM_MAXIMIZE 2 /* ei for maximisation (default: minimisation, as bayes_opt.run_gp_ei_bo) */
+int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows, const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream);
+
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

@@ -1,0 +1,129 @@
+#!/usr/bin/env python
+"""Streaming marginal prediction (adkf_predict_marginal) against the joint path (adkf_predict(want_var=True)) where the latter
+accepts the shape.  Both are timed on the same work: from the features, with the fit's A^-1, alpha and scalars reused
+(REUSE_INNER only), so each computes its own distances.  One JSON line per shape: rows/s, GB/s (query features read once plus
+the outputs), the FLOP/s each path EXECUTES (its own count, below) with the marginal path's fractions of the FP32-matrix-pipe
+bound (155 TFLOP/s) and of the HBM bound (6.29 TB/s), and the workspace bytes.  The last line runs the
+tools/bench_meta_test.py shape through meta_test(streaming=True) and streaming=False.
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test]"""
+import argparse, json, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+from adkf_ift_amd import _lib, gp_ops
+
+FP32_MFMA = 155e12
+HBM = 6.29e12
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    for _ in range(reps):
+        fn()
+    ev[1].record()
+    torch.cuda.synchronize()
+    return ev[0].elapsed_time(ev[1]) / 1e3 / reps
+
+
+def _refined(b):
+    """[T] bool: tasks that take the refined-C step (more than 128 points, or S_CONDA above 3: problems.h ProbCres's gate); the
+    scalars sit in the support-only workspace after W_ss (carve() order of adkf_gp.hip)."""
+    ws, _ = b.workspace()
+    al = lambda nfloat: (nfloat * 4 + 255) // 256 * 256
+    off = al(b.T * b.d) + 4 * al(b.T * b.ns * b.ns) + al(b.T * 16 * b.ns)
+    sc = ws[off:off + b.T * 64 * 4].view(torch.float32).view(b.T, 64).cpu()
+    return (sc[:, 47] > 3.0) | (b.ns > 128)
+
+
+def flops_marginal(T, ns, d, rows, n_refined_rows):
+    # support distances (upper tiles of the symmetric block) + per row: distances 2 ns d, C = K A^-1 2 ns^2, refined rows R 2 ns^2
+    t = -(-ns // 64)
+    return T * 64 * 64 * d * t * (t + 1) + rows * (2.0 * ns * d + 2.0 * ns * ns) + n_refined_rows * 2.0 * ns * ns
+
+
+def flops_joint(T, ns, nq, d, n_refined_tasks):
+    # adkf_predict: the support, query-support and query-query distance blocks (symmetric ones: upper tiles), C, and for
+    # refined tasks ProbCres + ProbCfix
+    ts, tq = -(-ns // 64), -(-nq // 64)
+    return (T * 64 * 64 * d * (ts * (ts + 1) + tq * (tq + 1)) + T * 2.0 * nq * ns * d + T * 2.0 * nq * ns * ns
+            + n_refined_tasks * 4.0 * nq * ns * ns)
+
+
+def shape(T, ns, d, rows_per_task, reps, dev):
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    b = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "rbf")
+    phi0, _ = gp_ops.init_params_batch(b, True, True)
+    b.flags = gp_ops.REUSE_DIST
+    phi, _, _, _, info = gp_ops.fit(b, phi0, 200)
+    gp_ops.check_info(info)
+    refined = _refined(b)
+    b.flags = gp_ops.REUSE_INNER
+    rows = T * rows_per_task
+    Zq = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):   # (a [rows, d] @ W product at once would need a second copy of the pool)
+        Zq[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    q_off = torch.arange(T + 1, device=dev, dtype=torch.int64) * rows_per_task
+    best = torch.zeros(T, device=dev)
+    lib = _lib.load()
+    rec = {"shape": f"T={T} ns={ns} d={d} rows/task={rows_per_task}", "rows": rows, "refined_tasks": int(refined.sum()),
+           "workspace_bytes": int(lib.adkf_workspace_bytes(T, ns, 0, d))}
+    byte_row = 4.0 * d + 12.0
+    dt = timed(lambda: gp_ops.predict_marginal(b, phi, Zq, q_off, best_f=best), reps)
+    fl = flops_marginal(T, ns, d, rows, int(refined.sum()) * rows_per_task)
+    rec.update({"marginal_s": dt, "marginal_rows_per_s": rows / dt, "marginal_GB_per_s": rows * byte_row / dt / 1e9,
+                "marginal_TFLOP_per_s": fl / dt / 1e12, "marginal_frac_fp32_mfma_bound": fl / dt / FP32_MFMA,
+                "marginal_frac_hbm_bound": rows * byte_row / dt / HBM})
+    if rows_per_task <= lib.adkf_max_points():
+        # the same fitted parameters on a batch with the padded query set: A^-1, alpha and the scalars written into ITS workspace
+        # by a fit from phi* (which stays put: converged), then timed with REUSE_INNER only - its distance stage runs
+        bj = gp_ops.GPBatch(Zs, ys, b.priors, "rbf", Z_q=Zq.view(T, rows_per_task, d), y_q=torch.zeros(T, rows_per_task, device=dev))
+        phij, _, _, _, info = gp_ops.fit(bj, phi, 200)
+        gp_ops.check_info(info)
+        rec["joint_fit_phi_max_abs_change"] = float((phij - phi).abs().max())
+        bj.flags = gp_ops.REUSE_INNER
+        dtj = timed(lambda: gp_ops.predict(bj, phij, want_var=True), reps)
+        flj = flops_joint(T, ns, rows_per_task, d, int(refined.sum()))
+        rec.update({"adkf_predict_s": dtj, "adkf_predict_rows_per_s": rows / dtj, "adkf_predict_TFLOP_per_s": flj / dtj / 1e12,
+                    "adkf_predict_workspace_bytes": int(lib.adkf_workspace_bytes(T, ns, rows_per_task, d)),
+                    "speedup_vs_adkf_predict": dtj / dt})
+    print(json.dumps(rec), flush=True)
+
+
+def meta_test_shape(dev):
+    from adkf_ift_amd import evaluate as E
+    from adkf_ift_amd.models import ADKTModel, ADKTModelConfig
+    from adkf_ift_amd.synthetic import meta_test_tasks
+    tasks, sizes = meta_test_tasks(157, 64)
+    model = ADKTModel(ADKTModelConfig()).to(dev)
+    out = {"shape": f"meta-test protocol: 157 tasks, support 64, query sizes {int(sizes.min())}..{int(sizes.max())}, 16 tasks per call"}
+    for streaming in (False, True):
+        E.evaluate_tasks(model, tasks[:4], tasks_per_call=4, streaming=streaming)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        E.evaluate_tasks(model, tasks, tasks_per_call=16, streaming=streaming)
+        torch.cuda.synchronize()
+        out["streaming_walltime_s" if streaming else "padded_walltime_s"] = time.perf_counter() - t0
+    print(json.dumps(out), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--skip-meta-test", action="store_true")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    shape(16, 128, 2048, 4096, a.reps, dev)
+    shape(16, 128, 2048, 65536, a.reps, dev)
+    shape(1, 256, 512, 1000000, a.reps, dev)
+    if not a.skip_meta_test:
+        meta_test_shape(dev)
+
+
+if __name__ == "__main__":
+    main()
