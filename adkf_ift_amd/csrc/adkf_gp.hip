@@ -18,16 +18,8 @@
 #include "gemm_x3.h"
 #include "dense_x3.h"
 #include "predict_stream.h"
-#if ADKF_VARIANT_DZ   // A/B experiment only (measured slower than the two ProbDZ launches: see its header)
-#include "../../tools/variants/dz.h"
-#endif
 
 using namespace adkf;
-
-#if ADKF_EVAL_STAMP
-extern "C" __device__ unsigned long long adkf_eval_stamps[16] = {};
-extern "C" int adkf_read_eval_stamps(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(adkf_eval_stamps), sizeof(unsigned long long) * 16); }
-#endif
 
 namespace {
 
@@ -39,11 +31,10 @@ inline size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 inline int grid_for(int T, int tiles) { return ((T + 7) / 8) * 8 * tiles; }
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-// Output-tile edge of the batched GEMMs.  The 128 x 128 variant (gemm.h) halves the operand traffic but leaves one
-// wave per SIMD: measured slower at every stage of C2 (ProbDist 33 -> 49 us, ProbP 22 -> 32 us, profiles/ notes in
-// DESIGN.md), so 64 x 64 (four co-resident workgroups per CU) is used throughout.
-inline int tile_edge(int, int) { return GT; }
-inline int tiles_of(int M, int N) { const int e = tile_edge(M, N); return ceil_div(M, e) * ceil_div(N, e); }
+// Output tiles of the batched GEMMs: 64 x 64 (GT, four co-resident workgroups per CU) throughout.  The 128 x 128 tile halves the
+// operand traffic but leaves one wave per SIMD: measured slower at every stage of C2 (ProbDist 33 -> 49 us, ProbP 22 -> 32 us,
+// profiles/ notes in DESIGN.md).
+inline int tiles_of(int M, int N) { return ceil_div(M, GT) * ceil_div(N, GT); }
 
 // Which problems run on the BF16 matrix pipe (gemm_x3.h: FP32 products out of three-way split operands).  ADKF_X3=0 (read once) sends
 // them back to the FP32-input MFMA kernel for A/B runs.
@@ -67,7 +58,7 @@ inline bool x3_for(int d) { return x3_enabled() && d >= GK; }
 
 template <class P>
 void launch_gemm(const P& p, int T, int M, int N, hipStream_t st, bool x3 = false) {
-    const int tm = ceil_div(M, GT), tn = ceil_div(N, GT);   // (k_bgemm<P, GTL> is not instantiated: see tile_edge)
+    const int tm = ceil_div(M, GT), tn = ceil_div(N, GT);
     if constexpr (use_x3<P>::value) {
         if (x3 && x3_enabled()) { k_bgemm3<P, GT, 256><<<((T + 7) / 8) * 8 * tm * tn, 256, 0, st>>>(p, T, tm, tn); return; }
     }
@@ -313,7 +304,7 @@ void lg_sweep(const LgMat& m0, hipStream_t st) {
             m.Dinv = dinv[step & 1];
             ProbLgPanel pp; pp.m = m; pp.step = step;
             k_bgemm<ProbLgPanel><<<grid_for(m.T, 2 * tn), 256, 0, st>>>(pp, m.T, 2, tn);
-            LgStepArgs sa{m, dinv[(step + 1) & 1], m.cnt, step, tn, npair, step + 1 < nb ? 1 : 0, LGF_STAGGER, LGF_PRIO};
+            LgStepArgs sa{m, dinv[(step + 1) & 1], m.cnt, step, tn, npair, step + 1 < nb ? 1 : 0};
             k_lg_update_sweep<<<grid_for(m.T, npair), LGF_NT, 0, st>>>(sa);
         }
         return;
@@ -445,17 +436,6 @@ bool refine64_lds_optin() {
     return ok;
 }
 
-// ADKF_R64_STOP (read once; diagnostics, tools/history/r64_phases.sh): the float64 path leaves after that phase - results are then garbage
-int r64_stop() {
-    static const int stop = [] {
-        const char* e = getenv("ADKF_R64_STOP");
-        const int v = e ? atoi(e) : 0;
-        if (v != 0) fprintf(stderr, "libadkf_gp: ADKF_R64_STOP=%d is set - the float64 path leaves after that phase and its RESULTS ARE GARBAGE (phase-timing diagnostics only)\n", v);
-        return v;
-    }();
-    return stop;
-}
-
 Refine64Args refine_args(const TaskView& tv, const adkf_batch_t* b, const Workspace& w, bool with_hessian, int level, float* f_out,
                          int32_t* info, float* f_in, float* g_in, float* gnorm, size_t& lds_bytes) {
     const bool lds_inv = refine64_lds_optin();   // (beyond R64_LDS_POINTS the diagonal blocks of the blocked inverse live there)
@@ -464,7 +444,7 @@ Refine64Args refine_args(const TaskView& tv, const adkf_batch_t* b, const Worksp
     lds_bytes = lds_inv ? sizeof(double) * (size_t)R64_LDS_POINTS * R64_LDS_POINTS : 0;
     return Refine64Args{tv, b->Z_s, b->Z_q, b->d, b->y_s, b->y_q, b->priors, w.Ainv, with_hessian ? w.P : nullptr, level >= 1 ? w.C : nullptr,
                         level >= 2 ? w.S : nullptr, w.vecs, w.scal, f_out, info, f_in, g_in, gnorm, w.w64, w.w64_stride, r64_threshold(), b->T,
-                        with_hessian ? 1 : 0, level, lds_inv ? 1 : 0, r64_stop()};
+                        with_hessian ? 1 : 0, level, lds_inv ? 1 : 0};
 }
 
 // Ill-conditioned tasks redo the factorisation-type stages in float64 (refine64.h); everybody else leaves the kernel after
@@ -482,9 +462,7 @@ void launch_refine(const TaskView& tv, const adkf_batch_t* b, const Workspace& w
 // (read once) keeps the sixteen-launch pipeline for A/B measurements.
 bool use_fused_outer(int ns, int nq) {
     static const bool enabled = [] { const char* e = getenv("ADKF_FUSED_OUTER"); return !e || atoi(e) != 0; }();
-    // ADKF_FUSED_OUTER_MIN (read once, experiments): smallest max(support, query) that takes the one-kernel stage; default 1 - round 5
-    // sends the small shapes (C1, 16 / 32 / 64-shot tasks) through the ragged instance too: one launch instead of sixteen
-    static const int min_pts = [] { const char* e = getenv("ADKF_FUSED_OUTER_MIN"); return e ? atoi(e) : 1; }();
+    // (the small shapes - C1, 16 / 32 / 64-shot tasks - go through the ragged instance too: one launch instead of sixteen)
     static const bool optin = [] {
         bool ok = true;
         for (const void* f : {reinterpret_cast<const void*>(&k_hyper<true, 0>), reinterpret_cast<const void*>(&k_hyper<true, 1>),
@@ -494,7 +472,7 @@ bool use_fused_outer(int ns, int nq) {
     }();
     if (!optin) (void)hipGetLastError();
     const int hi = ns > nq ? ns : nq;
-    return enabled && optin && hi >= min_pts && hi <= HY_N;
+    return enabled && optin && hi >= 1 && hi <= HY_N;
 }
 
 int launch_outer_factor(const OuterArgs& a, const Workspace& w, int nq, hipStream_t st) {
@@ -610,19 +588,10 @@ int outer_pipeline(const adkf_batch_t* b, const Workspace& w, const float* phi, 
         ProbDZ<false> pzs; pzs.tv = tv; pzs.Wss = w.Wss; pzs.Wqs = w.Wqs; pzs.Wqq = w.Wqq; pzs.Zs = b->Z_s; pzs.Zq = b->Z_q; pzs.dZ = dZ_s; pzs.d = d;
         ProbDZ<true> pzq; pzq.tv = tv; pzq.Wss = w.Wss; pzq.Wqs = w.Wqs; pzq.Wqq = w.Wqq; pzq.Zs = b->Z_s; pzq.Zq = b->Z_q; pzq.dZ = dZ_q; pzq.d = d;
         // (both cotangents in ONE launch through gemm.h's select() hook, with the two functors behind a run-time switch, was
-        // measured at 139.8 us against 62.6 + 56.4 for the two launches: dropped)
-#if ADKF_VARIANT_DZ
-        static const bool dz_optin = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dz), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                         (int)DZ_LDS_BYTES) == hipSuccess;
-        if (dz_optin && ns == HY_N && nq == HY_N && !b->n_s && !b->n_q && tv.vec && (d % HY_N) == 0) {
-            DzArgs da{w.Wss, w.Wqs, w.Wqq, b->Z_s, b->Z_q, dZ_s, dZ_q, d, T};
-            k_dz<<<grid_for(T, 1), HY_NT, DZ_LDS_BYTES, st>>>(da);
-        } else
-#endif
-        {
-            if (dZ_s) launch_gemm(pzs, T, ns, d, st, x3_for(d));
-            if (dZ_q) launch_gemm(pzq, T, nq, d, st, x3_for(d));
-        }
+        // measured at 139.8 us against 62.6 + 56.4 for the two launches: dropped; so was one workgroup per task with both operands in
+        // LDS, k_dz in tools/variants/dz.h at 4c3bc9b: 135 us inside the step)
+        if (dZ_s) launch_gemm(pzs, T, ns, d, st, x3_for(d));
+        if (dZ_q) launch_gemm(pzq, T, nq, d, st, x3_for(d));
     }
     if (w.w64) {
         // flagged (ill-conditioned) tasks, ONE launch at the very end: the factorisation-type stages (A^-1, alpha, P, the Hessian, C,
@@ -630,7 +599,7 @@ int outer_pipeline(const adkf_batch_t* b, const Workspace& w, const float* phi, 
         size_t lds_bytes;
         const Refine64Args ra = refine_args(tv, b, w, with_hessian, 2, f_out, info, nullptr, nullptr, nullptr, lds_bytes);
         Cot64Args ca{tv, b->Z_s, b->Z_q, dZ_s, dZ_q, d, w.vecs, w.scal, w.w64, w.w64_stride, r64_threshold(), T,
-                     with_hessian ? 1 : 0, flags, dirscale, corrscale, g_phi_out, v_out, H_out, lds_bytes ? 1 : 0, r64_stop()};
+                     with_hessian ? 1 : 0, flags, dirscale, corrscale, g_phi_out, v_out, H_out, lds_bytes ? 1 : 0};
         k_tail64<<<T, R64_NT, lds_bytes, st>>>(ra, ca);
     }
     LAUNCH_OK();
@@ -1558,20 +1527,7 @@ int adkf_dense_weight_grad(const float* g, int32_t ldg, const float* x, int32_t 
     if (tiles * splits > 0x7fffffffLL) return ADKF_E_SIZE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     Dense3TnArgs a{g, ldg, x, ldx, static_cast<float*>(scratch), M, N, K, rps};
-    // ADKF_DENSE_TN_DEPTH (read once): 0 / unset = k_dense3_tn; 2 or 4 = k_dense3_tnd<2 | 4> (deeper prefetch, XCD-aware order; -2 / -4:
-    // dispatch order).  Bit-identical partial sums.  Measured (tools/x3_stream_bench.hip, tools/r05_stream_prof.sh): alone on the chip
-    // with its operands resident in the 256 MB MALL 73 -> 60 us at the C2 feature map, INSIDE the C2 step (operands from HBM) 66.9 / 68.4 /
-    // 69.5 / 67.0 us for tn / tnd<4> / tnd<4> in dispatch order / tnd<2>: no gain where it is used, so the default stays k_dense3_tn.
-    static const int tn_depth = [] { const char* e = getenv("ADKF_DENSE_TN_DEPTH"); return e ? atoi(e) : 0; }();
-    const int depth = tn_depth < 0 ? -tn_depth : tn_depth;
-    if (depth == 2 || depth == 4) {
-        static const bool optin_d = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dense3_tnd<2>), hipFuncAttributeMaxDynamicSharedMemorySize, D3_LDS_BYTES) == hipSuccess &&
-                                    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dense3_tnd<4>), hipFuncAttributeMaxDynamicSharedMemorySize, D3_LDS_BYTES) == hipSuccess;
-        if (!optin_d) { g_last_hip_error = hipErrorInvalidValue; (void)hipGetLastError(); return ADKF_E_LAUNCH; }
-        const int sp = tn_depth < 0 ? -splits : splits;
-        if (depth == 2) k_dense3_tnd<2><<<(unsigned)(tiles * splits), D3_NT, D3_LDS_BYTES, st>>>(a, (int)tiles, sp);
-        else k_dense3_tnd<4><<<(unsigned)(tiles * splits), D3_NT, D3_LDS_BYTES, st>>>(a, (int)tiles, sp);
-    } else k_dense3_tn<<<dim3((unsigned)tiles, (unsigned)splits), D3_NT, D3_LDS_BYTES, st>>>(a);
+    k_dense3_tn<<<dim3((unsigned)tiles, (unsigned)splits), D3_NT, D3_LDS_BYTES, st>>>(a);
     const size_t n = (size_t)N * (size_t)K;
     k_dense3_reduce<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(static_cast<const float*>(scratch), dw, n, splits);
     LAUNCH_OK();

@@ -12,7 +12,7 @@
 // Measured and not kept: a PERSISTENT form (one workgroup per CU walking its tiles with one pipeline over all their chunks, the next
 // tile's first chunks staged under the last ones of the current tile): 73.5 against 73.7 us at 65 536 x 256 x 256, 2.65 against 2.50 - 2.57 ms
 // at 56 554 x 3 072 x 1 408 - the short-K shape is bound by its 134 MB of HBM traffic plus the products, not by the tile boundaries.
-// What bounds it (tools/x3_gemm_bench.hip with -DD3_ABLATE builds, 56 554 x 3 072 x 1 408: 2.50 ms): without the MFMAs 1.86 ms, without the
+// What bounds it (ablation builds of tools/x3_gemm_bench.hip at 4c3bc9b, 56 554 x 3 072 x 1 408: 2.50 ms): without the MFMAs 1.86 ms, without the
 // operand loads after the first chunk 2.38, without the stores 2.42, with none of the three 0.73 - the operand traffic out of L2 (40 KB per
 // tile and chunk: 18.7 GB per call, ~10 TB/s while nothing else runs; 3.7 GB of it from beyond L2, rocprofv3 FETCH_SIZE) takes as long as
 // the products, and the two only partly overlap.  A second register set (loads three chunks ahead) changed nothing (2.54 ms); larger
@@ -22,15 +22,6 @@
 
 namespace adkf {
 
-#ifndef D3_PINGPONG
-#define D3_PINGPONG 1
-#endif
-#ifndef D3_ABLATE   // diagnostics (tools/x3_gemm_bench.hip): 1 no operand loads after the first chunk, 2 no stores of the result, 4 no MFMAs
-#define D3_ABLATE 0
-#endif
-#ifndef D3_EAGER_A
-#define D3_EAGER_A 0
-#endif
 constexpr int D3_TM = 128, D3_TN = 128, D3_NT = 512, D3_PLANE = D3_TM * X3_RS;
 constexpr int D3_LDS_BYTES = 2 * 2 * 3 * D3_PLANE * (int)sizeof(unsigned short);   // two buffers x (A, B) x three planes: 122 880
 
@@ -132,21 +123,6 @@ __global__ __launch_bounds__(D3_NT) void k_dense3(Dense3Args a) {
             b1[j] = *reinterpret_cast<const bf16x8*>(Bb + D3_PLANE + j * 16 * X3_RS);
             b2[j] = *reinterpret_cast<const bf16x8*>(Bb + 2 * D3_PLANE + j * 16 * X3_RS);
         }
-#if D3_EAGER_A
-        bf16x8 a0[MI], a1[MI], a2[MI];
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-            a0[i] = *reinterpret_cast<const bf16x8*>(Ab + i * 16 * X3_RS);
-            a1[i] = *reinterpret_cast<const bf16x8*>(Ab + D3_PLANE + i * 16 * X3_RS);
-            a2[i] = *reinterpret_cast<const bf16x8*>(Ab + 2 * D3_PLANE + i * 16 * X3_RS);
-        }
-#define ADKF_D3_TERM(dst_, aq_, bq_)                                                                      \
-    _Pragma("unroll") for (int i = 0; i < MI; ++i) _Pragma("unroll") for (int j = 0; j < MJ; ++j)       \
-        dst_[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq_[i], bq_[j], dst_[i][j], 0, 0, 0);
-        ADKF_D3_TERM(small, a2, b0) ADKF_D3_TERM(small, a1, b1) ADKF_D3_TERM(small, a0, b2)
-        ADKF_D3_TERM(small, a1, b0) ADKF_D3_TERM(small, a0, b1) ADKF_D3_TERM(acc, a0, b0)
-        (void)ax;
-#else
 #define ADKF_D3_LOADA(q_) _Pragma("unroll") for (int i = 0; i < MI; ++i) ax[i] = *reinterpret_cast<const bf16x8*>(Ab + (q_) * D3_PLANE + i * 16 * X3_RS);
 #define ADKF_D3_TERM(dst_, bq_)                                                                           \
     _Pragma("unroll") for (int i = 0; i < MI; ++i) _Pragma("unroll") for (int j = 0; j < MJ; ++j)       \
@@ -154,8 +130,6 @@ __global__ __launch_bounds__(D3_NT) void k_dense3(Dense3Args a) {
         ADKF_D3_LOADA(2) ADKF_D3_TERM(small, b0)                               // x2 y0
         ADKF_D3_LOADA(1) ADKF_D3_TERM(small, b1) ADKF_D3_TERM(small, b0)       // x1 y1, x1 y0
         ADKF_D3_LOADA(0) ADKF_D3_TERM(small, b2) ADKF_D3_TERM(small, b1) ADKF_D3_TERM(acc, b0)   // x0 y2, x0 y1, x0 y0
-#undef ADKF_D3_LOADA
-#endif
 #undef ADKF_D3_TERM
 #undef ADKF_D3_LOADA
     };
@@ -165,15 +139,15 @@ __global__ __launch_bounds__(D3_NT) void k_dense3(Dense3Args a) {
     stage(0);
     if (nc > 1) fetch(GK);
     __syncthreads();
-    const bool stage_first = D3_PINGPONG ? wv < 4 : true;   // the two waves of a SIMD (wv, wv + 4) take the halves of an iteration in opposite order
+    const bool stage_first = wv < 4;   // the two waves of a SIMD (wv, wv + 4) take the halves of an iteration in opposite order
     for (int c = 0; c < nc; ++c) {
         const int cur = c & 1;
         if (stage_first) {
-            if (c + 1 < nc) { stage(cur ^ 1); if (c + 2 < nc && !(D3_ABLATE & 1)) fetch((c + 2) * GK); }
-            if (!(D3_ABLATE & 4)) multiply(cur);
+            if (c + 1 < nc) { stage(cur ^ 1); if (c + 2 < nc) fetch((c + 2) * GK); }
+            multiply(cur);
         } else {
-            if (!(D3_ABLATE & 4)) multiply(cur);
-            if (c + 1 < nc) { stage(cur ^ 1); if (c + 2 < nc && !(D3_ABLATE & 1)) fetch((c + 2) * GK); }
+            multiply(cur);
+            if (c + 1 < nc) { stage(cur ^ 1); if (c + 2 < nc) fetch((c + 2) * GK); }
         }
         __syncthreads();
     }
@@ -185,7 +159,6 @@ __global__ __launch_bounds__(D3_NT) void k_dense3(Dense3Args a) {
         for (int j = 0; j < MJ; ++j) {
             const int gi0 = m0 + wr * 64 + i * 16 + fk * 4, gj = n0 + wc * 32 + j * 16 + fi;
             if (gj >= a.N) continue;
-            if ((D3_ABLATE & 2) && acc[i][j][0] != 123.456f) continue;
             const float bv = a.bias ? a.bias[gj] : 0.f;
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -313,21 +286,14 @@ __global__ __launch_bounds__(D3_NT) void k_dense3_tn(Dense3TnArgs a) {
 // third of the matrix-pipe rate.  Both have ONE chunk of operand loads in flight per lane (16 - 32 KB per CU, 4 - 8 MB over the chip,
 // where ~16 MB are needed to cover a 2 us trip to HBM at full rate): with eight chunks per tile, or every chunk's operands coming from
 // HBM, each chunk pays most of a memory round trip (8 x 2 us + epilogue = the 18.5 us a workgroup takes).
+// Measured and not kept: a streaming form of the weight gradient (k_dense3_tnd in dense_x3.h at 4c3bc9b: two or four chunks of loads in
+// flight, an XCD-aware workgroup order, bit-identical partial sums).  Alone on the chip, its operands resident in the 256 MB MALL, it took
+// 60 against 73 us at the C2 feature map; INSIDE the C2 step (operands from HBM) 68.4 / 67.0 us for four / two chunks against k_dense3_tn's
+// 66.9 - no gain where it is used.
 //
-#ifndef D3TN_ORDER
-#define D3TN_ORDER 0
-#endif
-#ifndef D3SK_ORDER
-#define D3SK_ORDER 2
-#endif
-#ifndef D3S_ABLATE   // diagnostics (tools/x3_stream_bench.hip): 1 no operand loads behind the prologue, 2 no stores of the result, 4 no MFMAs, 8 no LDS stores of the staging
-#define D3S_ABLATE 0
-#endif
-// d3_multiply: the product of one staged chunk (both kernels below; the same instruction order as k_dense3's).
-// SWAP: the MFMA takes the B fragment as its first operand, i.e. computes the transposed 16 x 16 block - the same products summed in the same
-// order, but a lane then holds FOUR CONSECUTIVE COLUMNS of one output row (row = lane & 15, columns 4 (lane >> 4) + reg): one 16-byte store
-// instead of four 4-byte ones.
-template <bool SWAP = false>
+// d3_multiply: the product of one staged chunk in the same instruction order as k_dense3's, with the B fragment as the MFMA's first
+// operand, i.e. the transposed 16 x 16 block - the same products summed in the same order, but a lane then holds FOUR CONSECUTIVE COLUMNS
+// of one output row (row = lane & 15, columns 4 (lane >> 4) + reg): one 16-byte store instead of four 4-byte ones.
 __device__ __forceinline__ void d3_multiply(const unsigned short* Ab, const unsigned short* Bb, f32x4 (&acc)[4][2], f32x4 (&small)[4][2]) {
     constexpr int MI = 4, MJ = 2;
     bf16x8 b0[MJ], b1[MJ], b2[MJ], ax[MI];
@@ -340,9 +306,7 @@ __device__ __forceinline__ void d3_multiply(const unsigned short* Ab, const unsi
 #define ADKF_D3_LOADA(q_) _Pragma("unroll") for (int i = 0; i < MI; ++i) ax[i] = *reinterpret_cast<const bf16x8*>(Ab + (q_) * D3_PLANE + i * 16 * X3_RS);
 #define ADKF_D3_TERM(dst_, bq_)                                                                           \
     _Pragma("unroll") for (int i = 0; i < MI; ++i) _Pragma("unroll") for (int j = 0; j < MJ; ++j)       \
-        dst_[i][j] = SWAP ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq_[j], ax[i], dst_[i][j], 0, 0, 0)  \
-                          : __builtin_amdgcn_mfma_f32_16x16x32_bf16(ax[i], bq_[j], dst_[i][j], 0, 0, 0);
-    if (D3S_ABLATE & 4) return;
+        dst_[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq_[j], ax[i], dst_[i][j], 0, 0, 0);
     ADKF_D3_LOADA(2) ADKF_D3_TERM(small, b0)
     ADKF_D3_LOADA(1) ADKF_D3_TERM(small, b1) ADKF_D3_TERM(small, b0)
     ADKF_D3_LOADA(0) ADKF_D3_TERM(small, b2) ADKF_D3_TERM(small, b1) ADKF_D3_TERM(acc, b0)
@@ -384,7 +348,6 @@ __global__ __launch_bounds__(D3_NT) void k_dense3_sk(Dense3Args a) {
         rb2 = *reinterpret_cast<const uint4*>(bp + 2 * a.b_plane + c * GK);
     };
     auto stage = [&](int buf, int c) __attribute__((always_inline)) {
-        if (D3S_ABLATE & 8) return;
         uint32_t p0[4], p1[4], p2[4];
         x3_split2(ra[c][0].x, ra[c][0].y, p0[0], p1[0], p2[0]); x3_split2(ra[c][0].z, ra[c][0].w, p0[1], p1[1], p2[1]);
         x3_split2(ra[c][1].x, ra[c][1].y, p0[2], p1[2], p2[2]); x3_split2(ra[c][1].z, ra[c][1].w, p0[3], p1[3], p2[3]);
@@ -408,9 +371,8 @@ __global__ __launch_bounds__(D3_NT) void k_dense3_sk(Dense3Args a) {
     stage(0, 0);
     fetch_b(bp, 1);
     __syncthreads();
-    // (measured at 65 536 x 256 x 256, tools/x3_stream_bench.hip: k_dense3's ping-pong order 61.7 us, everybody staging first 59.6, everybody
-    // multiplying first 58.0 - with the operand loads long in flight there is no load latency left for a partner wave to cover)
-    const bool stage_first = D3SK_ORDER == 0 ? wv < 4 : D3SK_ORDER == 1;   // 0: ping-pong, 1: everybody stages first, 2: everybody multiplies first
+    // Every wave multiplies first, then stages (measured at 65 536 x 256 x 256: k_dense3's ping-pong order 61.7 us, everybody staging first
+    // 59.6, everybody multiplying first 58.0 - with the operand loads long in flight there is no load latency left for a partner wave to cover)
     const bool c_vec = !(a.ldc & 3) && !(reinterpret_cast<uintptr_t>(a.C) & 15);   // 16-byte stores of the result
     int p = 0;
     for (;;) {   // one output tile (mt, nt) per trip
@@ -425,7 +387,7 @@ __global__ __launch_bounds__(D3_NT) void k_dense3_sk(Dense3Args a) {
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int j = 0; j < MJ; ++j) { acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; small[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-        if (refill && !(D3S_ABLATE & 1)) fetch_a(ap2, 0);   // (chunk 0 was staged for this tile in the previous trip)
+        if (refill) fetch_a(ap2, 0);   // (chunk 0 was staged for this tile in the previous trip)
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const int c1 = (c + 1) % NC, c2 = (c + 2) % NC;
@@ -433,15 +395,13 @@ __global__ __launch_bounds__(D3_NT) void k_dense3_sk(Dense3Args a) {
             auto advance = [&]() __attribute__((always_inline)) {
                 if (have_next) {
                     stage(p ^ 1, c1);
-                    if (!(D3S_ABLATE & 1)) {
-                        if (refill && c1 != 0) fetch_a(ap2, c1);
-                        if (c + 2 < NC) fetch_b(bp, c2);
-                        else if (have2) fetch_b(bp2, c2);
-                    }
+                    if (refill && c1 != 0) fetch_a(ap2, c1);
+                    if (c + 2 < NC) fetch_b(bp, c2);
+                    else if (have2) fetch_b(bp2, c2);
                 }
             };
-            if (stage_first) { advance(); d3_multiply<true>(As + p * 3 * D3_PLANE + frag_a, Bs + p * 3 * D3_PLANE + frag_b, acc, small); }
-            else { d3_multiply<true>(As + p * 3 * D3_PLANE + frag_a, Bs + p * 3 * D3_PLANE + frag_b, acc, small); advance(); }
+            d3_multiply(As + p * 3 * D3_PLANE + frag_a, Bs + p * 3 * D3_PLANE + frag_b, acc, small);
+            advance();
             __syncthreads();
             p ^= 1;
         }
@@ -456,7 +416,6 @@ __global__ __launch_bounds__(D3_NT) void k_dense3_sk(Dense3Args a) {
             for (int j = 0; j < MJ; ++j) {
                 const int gj0 = n0 + wc * 32 + j * 16 + fk * 4;
                 if (gj0 >= a.N) continue;
-                if ((D3S_ABLATE & 2) && acc[i][j][0] != 123.456f) continue;
                 float o[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) o[r] = (acc[i][j][r] + small[i][j][r]) + ((a.bias && gj0 + r < a.N) ? a.bias[gj0 + r] : 0.f);
@@ -470,105 +429,6 @@ __global__ __launch_bounds__(D3_NT) void k_dense3_sk(Dense3Args a) {
         if (!have2) break;
         mt = mt2; nt = nt2; bp = bp2;
     }
-}
-
-// k_dense3_tnd<DEPTH>: k_dense3_tn with DEPTH chunks of operand loads in flight per lane (register sets used round robin; the chunk loop
-// is unrolled DEPTH times so that the sets are static), and an XCD-aware order of the workgroups: the output tiles of one row range
-// land on ONE XCD next to each other in time, so the second reader of an operand half finds it in that XCD's L2.  Products, chunk
-// order and row ranges are k_dense3_tn's: bit-identical partial sums.
-template <int DEPTH>
-__global__ __launch_bounds__(D3_NT) void k_dense3_tnd(Dense3TnArgs a, int tiles, int splits) {
-    constexpr int MI = 4, MJ = 2;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int wr = wv >> 2, wc = wv & 3;
-    const int fi = lane & 15, fk = lane >> 4;
-    const int tiles_k = (a.K + D3_TN - 1) / D3_TN;
-    // workgroup id -> (tile, row range): ids b, b + 8, b + 16, ... share an XCD (round-robin dispatch); a multiple-of-8 prefix of the
-    // grid is renumbered XCD-major so that consecutive logical indices - the tiles of one row range - share an XCD
-    const bool remap = splits > 0;   // (splits < 0: dispatch order, for A/B runs)
-    if (splits < 0) splits = -splits;
-    const int total = tiles * splits, per = total >> 3, b = blockIdx.x;
-    const int logical = (remap && b < 8 * per) ? (b & 7) * per + (b >> 3) : b;
-    const int tile = logical % tiles, split = logical / tiles;
-    const int n0 = (tile / tiles_k) * D3_TM, k0 = (tile % tiles_k) * D3_TN;
-    const int r_begin = split * a.rows_per_split, r_end = min(a.M, r_begin + a.rows_per_split);
-    unsigned short* const As = d3_lds;
-    unsigned short* const Bs = d3_lds + 2 * 3 * D3_PLANE;
-    const int sc = tid & 127, srun = (tid >> 7) * 8;
-    const float* gp = a.G + (n0 + sc < a.N ? n0 + sc : 0);
-    const float* xp = a.X + (k0 + sc < a.K ? k0 + sc : 0);
-    const int sdst = sc * X3_RS + srun;
-    const int frag_a = (wr * 64 + fi) * X3_RS + 8 * fk, frag_b = (wc * 32 + fi) * X3_RS + 8 * fk;
-
-    float rg[DEPTH][8], rx[DEPTH][8];
-    auto fetch = [&](int set, int row0) __attribute__((always_inline)) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int r = row0 + srun + q;
-            const int rc = r < r_end ? r : r_end - 1;
-            const float g = gp[(size_t)rc * a.ldg], x = xp[(size_t)rc * a.ldx];
-            rg[set][q] = r < r_end ? g : 0.f; rx[set][q] = r < r_end ? x : 0.f;
-        }
-    };
-    auto stage = [&](int buf, int set) __attribute__((always_inline)) {
-        if (D3S_ABLATE & 8) return;
-        uint32_t p0[4], p1[4], p2[4];
-#pragma unroll
-        for (int h = 0; h < 4; ++h) x3_split2(rg[set][2 * h], rg[set][2 * h + 1], p0[h], p1[h], p2[h]);
-        unsigned short* da = As + buf * 3 * D3_PLANE + sdst;
-        *reinterpret_cast<uint4*>(da) = make_uint4(p0[0], p0[1], p0[2], p0[3]);
-        *reinterpret_cast<uint4*>(da + D3_PLANE) = make_uint4(p1[0], p1[1], p1[2], p1[3]);
-        *reinterpret_cast<uint4*>(da + 2 * D3_PLANE) = make_uint4(p2[0], p2[1], p2[2], p2[3]);
-#pragma unroll
-        for (int h = 0; h < 4; ++h) x3_split2(rx[set][2 * h], rx[set][2 * h + 1], p0[h], p1[h], p2[h]);
-        unsigned short* db = Bs + buf * 3 * D3_PLANE + sdst;
-        *reinterpret_cast<uint4*>(db) = make_uint4(p0[0], p0[1], p0[2], p0[3]);
-        *reinterpret_cast<uint4*>(db + D3_PLANE) = make_uint4(p1[0], p1[1], p1[2], p1[3]);
-        *reinterpret_cast<uint4*>(db + 2 * D3_PLANE) = make_uint4(p2[0], p2[1], p2[2], p2[3]);
-    };
-
-    f32x4 acc[MI][MJ], small[MI][MJ];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < MJ; ++j) { acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; small[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-
-    const int nc = r_end > r_begin ? (r_end - r_begin + GK - 1) / GK : 0;
-    if (nc > 0) {
-        // chunk q travels in set q % DEPTH; chunks 1 .. DEPTH are in flight when the loop starts
-#pragma unroll
-        for (int q = 0; q < DEPTH; ++q) if (q < nc) fetch(q, r_begin + q * GK);
-        stage(0, 0);
-        if (DEPTH < nc) fetch(0, r_begin + DEPTH * GK);
-        __syncthreads();
-        const bool stage_first = D3TN_ORDER == 0 ? wv < 4 : D3TN_ORDER == 1;   // as D3SK_ORDER
-        for (int c0 = 0; c0 < nc; c0 += DEPTH) {
-#pragma unroll
-            for (int u = 0; u < DEPTH; ++u) {
-                const int c = c0 + u;
-                if (c < nc) {   // (uniform over the workgroup: the barrier below is reached by everybody or nobody)
-                    const int cur = (DEPTH & 1) ? (c & 1) : (u & 1), set1 = (u + 1) % DEPTH;
-                    auto advance = [&]() __attribute__((always_inline)) {
-                        if (c + 1 < nc) { stage(cur ^ 1, set1); if (c + 1 + DEPTH < nc && !(D3S_ABLATE & 1)) fetch(set1, r_begin + (c + 1 + DEPTH) * GK); }
-                    };
-                    if (stage_first) { advance(); d3_multiply(As + cur * 3 * D3_PLANE + frag_a, Bs + cur * 3 * D3_PLANE + frag_b, acc, small); }
-                    else { d3_multiply(As + cur * 3 * D3_PLANE + frag_a, Bs + cur * 3 * D3_PLANE + frag_b, acc, small); advance(); }
-                    __syncthreads();
-                }
-            }
-        }
-    }
-    float* out = a.part + (size_t)split * a.N * a.K;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < MJ; ++j) {
-            const int gi0 = n0 + wr * 64 + i * 16 + fk * 4, gj = k0 + wc * 32 + j * 16 + fi;
-            if (gj >= a.K) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (gi0 + r < a.N) out[(size_t)(gi0 + r) * a.K + gj] = acc[i][j][r] + small[i][j][r];
-        }
 }
 
 // dW = part[0] + part[1] + ... in that order

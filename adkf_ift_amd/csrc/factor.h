@@ -20,7 +20,7 @@
 // Rows/cols >= n are padded with the identity; sweeping them is a no-op that leaves -1 on the diagonal.
 //
 // Scheduling.  The chain  update(next pivot rows) -> D^-1 -> F -> LDS  is the critical path (every block step
-// waits for it; measured ~0.4 us against ~0.23 us of bulk FMAs per step, tools/history/chain_bench.hip), so:
+// waits for it; measured ~0.4 us against ~0.23 us of bulk FMAs per step, tools/history/chain_bench.hip at 4c3bc9b), so:
 //   * a thread's RB rows are G = RB/CB groups of B rows that lie NMAX/G apart, and consecutive logical block
 //     rows live in DIFFERENT waves: the ownership of the chain rotates over the waves from step to step;
 //   * (measured and rejected: sending the NEXT diagonal block from its holder before step q's update and letting every
@@ -33,28 +33,13 @@
 //     (vector slots are triple-buffered so the old vectors are still there).
 #pragma once
 #include <limits.h>
-#ifndef ADKF_STAMP
-#define ADKF_STAMP 0  // diagnostic build only (tools/history/sweep_bench.hip): s_memtime stamps of one block step into sm.stamp[]
-#endif
-#if ADKF_STAMP
-#define ADKF_TS(slot) do { if (q_stamp == ADKF_STAMP && (threadIdx.x & 63) == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); sm.stamp[(threadIdx.x >> 6) * 16 + (slot)] = t_; } } while (0)
-#else
-#define ADKF_TS(slot) do {} while (0)
-#endif
-#ifndef ADKF_ABLATE
-#define ADKF_ABLATE 0  // timing-only ablation switches for tools/history/sweep_bench.hip (1: no inverse, 2: no readlane, 4: no F, 8: no deferral)
-#endif
 
 #include "device_utils.h"
 
 namespace adkf {
 
+// (128 points x 512 threads take the matrix-pipe sweep of factor_m.h instead)
 template <int NMAX, int NT> struct SweepCfg;
-#ifndef ADKF_CFG128_RB
-#define ADKF_CFG128_RB 8
-#define ADKF_CFG128_CB 4
-#endif
-template <> struct SweepCfg<128, 512> { static constexpr int RB = ADKF_CFG128_RB, CB = ADKF_CFG128_CB; };
 template <> struct SweepCfg<64, 256> { static constexpr int RB = 4, CB = 4; };
 template <> struct SweepCfg<32, 256> { static constexpr int RB = 2, CB = 2; };
 template <> struct SweepCfg<16, 256> { static constexpr int RB = 1, CB = 1; };
@@ -69,9 +54,6 @@ struct SweepSmemBlk {
     alignas(16) float vec_out[NMAX];      // A^-1 * vec_in
     float red[8 * (NT / 64)];
     int redi[NT / 64];
-#if ADKF_STAMP
-    unsigned long long stamp[(NT / 64) * 16];
-#endif
     static constexpr int SCRATCH_FLOATS = 3 * B * NMAX;
     __device__ __forceinline__ float* scratch() { return &cross[0][0][0]; }   // free for the caller between two sweeps
 };
@@ -86,11 +68,7 @@ __device__ __forceinline__ float fast_rcp(float p) {
 // closed-form 2 x 2 inverses and one Schur complement - two dependent reciprocals instead of four.
 __device__ __forceinline__ void inv2(float a, float b, float c, float& ia, float& ib, float& ic, float& det) {
     det = fmaf(a, c, -b * b);
-#ifdef ADKF_RAW_RCP
-    const float r = __builtin_amdgcn_rcpf(det);
-#else
     const float r = fast_rcp(det);
-#endif
     ia = c * r; ib = -b * r; ic = a * r;
 }
 template <int B> struct InvSpd;
@@ -161,25 +139,17 @@ struct SweepBlk {
     __device__ static __forceinline__ void publish(float (&m)[RB][CB], int bl, int slot, Smem& sm) {
         constexpr int RO = GI * CB;
         const int q = GI * NBR + bl;
-        const int q_stamp = q - 1; (void)q_stamp;
         const int plane = ((bl / NW) * NBC + q) & 63;  // lane, in the owning wave, of the thread (bl, bc = q) that holds D
         float D[B][B];
 #pragma unroll
         for (int a = 0; a < B; ++a)
 #pragma unroll
             for (int b = 0; b <= a; ++b) {
-#if ADKF_ABLATE & 2
-                D[a][b] = m[RO + a][b] + (a == b ? 1.f : 0.f);
-#elif ADKF_ABLATE & 128
-                D[a][b] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m[RO + a][b]), plane));
-#else
                 // ds_bpermute: the ten transfers pipeline through the LDS crossbar behind one wait; ten v_readlane
                 // (SGPR round trips with their hazard waits) measured ~390 cycles on this critical path
                 D[a][b] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(plane << 2, __builtin_bit_cast(int, m[RO + a][b])));
-#endif
                 D[b][a] = D[a][b];
             }
-        ADKF_TS(3);
         // private copies of C and F (registers are plentiful: at most 32 matrix elements per lane)
         if (br() == bl) {
             const int j0 = bc() * CB;
@@ -199,12 +169,7 @@ struct SweepBlk {
             for (int a = 0; a < B; ++a)
 #pragma unroll
                 for (int c = 0; c < CB; ++c) sm.cross[slot][a][j0 + c] = C[a][c];  // C is final: its stores fly under the inverse
-#if ADKF_ABLATE & 1
-            for (int a = 0; a < B; ++a) piv[a] = D[a][a];
-#else
             InvSpd<B>::run(D, piv);
-#endif
-            ADKF_TS(4);
             if (bc() == q) {
 #pragma unroll
                 for (int a = 0; a < B; ++a) sm.pivs[q * B + a] = piv[a];
@@ -213,20 +178,15 @@ struct SweepBlk {
             for (int a = 0; a < B; ++a)
 #pragma unroll
                 for (int c = 0; c < CB; ++c) {
-#if ADKF_ABLATE & 4
-                    F[a][c] = C[a][c] * D[a][a];
-#else
                     float s = 0.f;
 #pragma unroll
                     for (int b = 0; b < B; ++b) s = fmaf(D[a][b], C[b][c], s);
                     F[a][c] = s;
-#endif
                 }
 #pragma unroll
             for (int a = 0; a < B; ++a)
 #pragma unroll
                 for (int c = 0; c < CB; ++c) sm.fvec[slot][a][j0 + c] = F[a][c];
-            ADKF_TS(6);
         }
     }
 
@@ -251,11 +211,6 @@ struct SweepBlk {
             for (int a = 0; a < B; ++a) apply_pivot<R0, R1>(m, slot, a, sm);
         }
     }
-    // (for the ablation harness tools/history/sweep_bench.hip)
-    __device__ static __forceinline__ void step(float (&m)[RB][CB], int q, Smem& sm) {
-        apply_step<0, RB>(m, q % 3, sm);
-    }
-
     // The critical path of one block step, run by the wave that owns the NEXT pivot block qn = NGI * NBR + nbl:
     // fetch only what the chain needs from step q's vectors (C for its columns, F for the next pivot rows), bring
     // those rows up to date, invert and publish - all at raised priority.  The rest of this wave's step-q update
@@ -263,14 +218,9 @@ struct SweepBlk {
     template <int NGI>
     __device__ static __forceinline__ void chain(float (&m)[RB][CB], int nbl, int q, Smem& sm) {
         constexpr int N0 = NGI * CB, N1 = NGI * CB + CB;
-        const int q_stamp = q; (void)q_stamp;
-        ADKF_TS(0);
-        if (!(ADKF_ABLATE & 32)) __builtin_amdgcn_s_setprio(3);
-        ADKF_TS(1);
+        __builtin_amdgcn_s_setprio(3);
         apply_step<N0, N1>(m, q % 3, sm);
-        ADKF_TS(2);
         publish<NGI>(m, nbl, (q + 1) % 3, sm);
-        ADKF_TS(7);
         __builtin_amdgcn_s_setprio(0);
     }
 
@@ -289,20 +239,13 @@ struct SweepBlk {
                     if (!last_of_group) chain<GI>(m, bl + 1, q, sm);
                     else if constexpr (GI + 1 < G) chain<GI + 1>(m, 0, q, sm);
                 } else {
-                    const int q_stamp = q; (void)q_stamp;
-                    ADKF_TS(0);
-#ifdef ADKF_BULK_SLEEP
-                    __builtin_amdgcn_s_sleep(ADKF_BULK_SLEEP);  // let the chain owner's LDS reads and issue slots go first
-#endif
                     if (q > 0 && wave == owner_wave(bl)) {
                         // this wave ran the chain for block q during the previous step and postponed the rest of that
                         // step's update (everything but its pivot rows GI*CB..): do it now, off the critical path
                         apply_step<0, GI * CB>(m, (q + 2) % 3, sm);  // slot of step q - 1
                         apply_step<GI * CB + CB, RB>(m, (q + 2) % 3, sm);
                     }
-                    ADKF_TS(8);
                     apply_step<0, RB>(m, q % 3, sm);
-                    ADKF_TS(10);
                 }
             }
             phase<GI + 1>(m, nq, sm);
@@ -375,26 +318,12 @@ struct SweepBlk {
     }
 };
 
-// The names the kernels use.  128 points x 512 threads takes the wave-owned variant of factor_w.h (ADKF_SWEEP_W=0 keeps
-// the blocked one for A/B measurements); the smaller sizes use the blocked sweep above.
+// The names the kernels use: the blocked sweep above for 16, 32 and 64 points; factor_m.h specialises 128 points x 512 threads.
 template <int NMAX, int NT> struct SweepSmem : SweepSmemBlk<NMAX, NT> {};
 template <int NMAX, int NT> struct Sweep : SweepBlk<NMAX, NT> {};
 
 }  // namespace adkf
 
-// 128 points x 512 threads: rank-4 updates on the matrix pipe (factor_m.h) - the only variant the shipped library compiles.  The
-// A/B builds of tools/ (-DADKF_SWEEP_M=0: the VALU variant, -DADKF_SWEEP_M=0 -DADKF_SWEEP_W=0: the blocked sweep above at 128
-// points, -DADKF_SWEEP_M=2: the sixteen-pivot experiment, measured slower) take their sweeps from tools/variants/.
-#ifndef ADKF_SWEEP_M
-#define ADKF_SWEEP_M 1
-#endif
-#ifndef ADKF_SWEEP_W
-#define ADKF_SWEEP_W 1
-#endif
-#if ADKF_SWEEP_M == 2
-#include "../../tools/variants/factor_m16.h"   // A/B experiment only (measured slower); not part of the shipped library
-#elif ADKF_SWEEP_M
+// 128 points x 512 threads: rank-4 updates on the matrix pipe.  (Measured and replaced: the VALU sweep of round 2,
+// tools/variants/factor_w.h at 4c3bc9b; slower: sixteen-pivot block steps, tools/variants/factor_m16.h at 4c3bc9b.)
 #include "factor_m.h"
-#elif ADKF_SWEEP_W
-#include "../../tools/variants/factor_w.h"     // A/B experiment only (the VALU sweep of round 2)
-#endif

@@ -1,7 +1,7 @@
 // Sweep<128, 512> on the matrix pipe: the symmetric sweep of factor.h with the rank-4 update of every block step issued as
 // v_mfma_f32_16x16x4_f32 (exact fp32: bit-for-bit a k-ordered fmaf chain), the chain of a block step cut down to the 4 x 4
-// inverse alone, and the updates of a step running one step BEHIND its hand-off (included at the end of factor.h; factor_w.h
-// keeps the VALU variant for A/B runs, ADKF_SWEEP_M=0).
+// inverse alone, and the updates of a step running one step BEHIND its hand-off (included at the end of factor.h; the VALU
+// variant it replaced is tools/variants/factor_w.h at 4c3bc9b).
 //
 // Layout.  Wave w (0..7), lane l: p = l & 15, g = l >> 4.  The wave owns the 16 matrix rows 16 w .. 16 w + 15 as eight
 // 16 x 16 accumulator tiles; tile x covers the columns 16 x .. 16 x + 15.  In the MFMA's C/D map lane l, register y of
@@ -23,7 +23,7 @@
 //     by whoever needs it, ONE value per lane (the MFMA's A operand A[m = p][k = g] = -F[g][16 w + p]).
 // A consumer's B operand of tile x - B[k = g][n = p] = C[g][16 x + p] - is one conflict-free ds_read_b32.
 //
-// Schedule.  tools/handoff_bench.hip and the ablation builds of tools/sweepm_bench.hip priced a block step in which every
+// Schedule.  tools/handoff_bench.hip and the ablation builds of tools/sweepm_bench.hip (at 4c3bc9b) priced a block step in which every
 // wave fetches, updates its eight tiles and then publishes: barrier + LDS round trip + operands ~500 cycles, eight MFMAs per
 // wave ~590 (the SIMD's matrix pipe: 16 x 32), piece + LDS write latency ~170, the inversion ~320 - in SERIES, ~1600 per step.
 // Only ONE tile per wave is on the critical path of the next hand-off (tile wq' of the next block: it yields the wave's piece
@@ -39,31 +39,20 @@
 // order they were issued, and the LDS serves reads in the order they arrive: whatever the other waves put in front of the
 // chain wave's three critical reads and its one critical MFMA is what the hand-off waits for.  Only the next owner is on the
 // chain - the others' pieces are not needed before the next barrier, i.e. they have the inversion's ~190 cycles of slack - so
-// every wave but the chain wave sleeps 128 cycles behind the barrier (ADKF_M_SLEEP): 37.2 k -> 35.0 k cycles per sweep; with
-// only the chain wave's SIMD partner (wave + 4) sleeping 35.6 k, i.e. most of it is the partner's early MFMAs.
+// every wave but the chain wave sleeps 128 cycles behind the barrier: 37.2 k -> 35.0 k cycles per sweep; with only the chain
+// wave's SIMD partner (wave + 4) sleeping 35.6 k, i.e. most of it is the partner's early MFMAs.
 #pragma once
-#ifndef ADKF_M_ABLATE
-#define ADKF_M_ABLATE 0   // timing-only ablations for tools/sweepm_bench.hip (2: no inversion, 8: no MFMA at all, 16: one B read instead of eight, 32: no owner work at all, 64: no pieces)
-#endif
-#ifndef ADKF_M_EARLY
-#define ADKF_M_EARLY 2    // how many of the previous step's seven MFMAs issue before the A operand of the new step is formed
-#endif
-#ifndef ADKF_M_A128
-#define ADKF_M_A128 1     // 1: the A operand from two 16-byte LDS reads and four FMAs (36.2 k cycles per sweep); 0: from two dword reads, the row swaps of gfx950 and four DPP FMAs (37.9 k: the swap sequence with its hazard waits is on the hand-off chain)
-#endif
-#ifndef ADKF_M_SLEEP
-#define ADKF_M_SLEEP 2    // s_sleep argument (x 64 cycles) of the waves that are NOT on the hand-off chain, right behind the barrier: 37.2 k -> 35.0 k cycles per sweep (1: 37.0 k, 3: 35.8 k)
-#endif
-#ifndef ADKF_M_SLEEP_MODE
-#define ADKF_M_SLEEP_MODE 0   // who sleeps.  0: every wave but the chain wave (35.0 k); 1: only the chain wave's SIMD partner, wave + 4 (35.6 k: most of the gain is there); 2: everybody but the chain wave, behind its LDS reads instead of in front of them (37.0 k: no gain)
-#endif
-#ifndef ADKF_M_MID
-#define ADKF_M_MID 1      // ... and between the critical MFMA and the piece that is read out of its result (they cover its latency)
-#endif
 
 namespace adkf {
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
+
+// s_sleep argument (x 64 cycles) of the waves that are NOT on the hand-off chain, right behind the barrier: 37.2 k ->
+// 35.0 k cycles per sweep (1: 37.0 k, 3: 35.8 k; behind the reads instead of in front of them: 37.0 k, no gain)
+constexpr int MSWEEP_SLEEP = 2;
+// how many of the previous step's seven MFMAs issue before the A operand of the new step is formed, and how many between the
+// critical MFMA and the piece that is read out of its result (they cover its latency)
+constexpr int MSWEEP_EARLY = 2, MSWEEP_MID = 1;
 
 template <> struct SweepSmem<128, 512> {
     static constexpr int NSLOT = 2;
@@ -74,23 +63,9 @@ template <> struct SweepSmem<128, 512> {
     alignas(16) float vec_out[128];
     float red[8 * 8];
     int redi[8];
-#if ADKF_STAMP
-    unsigned long long stamp[8 * 16];
-#endif
     static constexpr int SCRATCH_FLOATS = NSLOT * 128 * 4;
     __device__ __forceinline__ float* scratch() { return &ct[0][0][0]; }   // free for the caller between two sweeps
 };
-
-#if ADKF_STAMP   // diagnostic build (tools/sweepm_bench.hip -DADKF_STAMP=<step> -DADKF_STAMP_SITE=<k>): s_memtime after the barrier of block
-                 // step <step> and at ONE further site k per build - a stamp has to wait for its own result (lgkmcnt), which drains
-                 // the wave's LDS queue and moves everything behind it, so two sites in one build would not be independent
-#ifndef ADKF_STAMP_SITE
-#define ADKF_STAMP_SITE 1
-#endif
-#define ADKF_MTS(slot_) do { if ((slot_ == 0 || slot_ == ADKF_STAMP_SITE) && s_stamp == ADKF_STAMP && (threadIdx.x & 63) == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); sm.stamp[(threadIdx.x >> 6) * 16 + (slot_)] = t_; } } while (0)
-#else
-#define ADKF_MTS(slot_) do {} while (0)
-#endif
 
 template <> struct Sweep<128, 512> {
     using Smem = SweepSmem<128, 512>;
@@ -111,28 +86,22 @@ template <> struct Sweep<128, 512> {
     // source (hipcc does not fold a mov_dpp into the FMA), with the uniform coefficient g = r - 1 on the pivot lane and -d_aP r on
     // the others formed as ONE fma(-r, y, z) whose y and z are selected while the reciprocal is in flight.  This is the serial
     // core of every block step (all 128 pivots pass through it), so it is one hand-scheduled instruction stream: the dependent
-    // chain of a pivot is mov_dpp -> rcp -> (Newton: 2 fma) -> fma -> fmac_dpp, the next pivot's column is updated first, and
+    // chain of a pivot is mov_dpp -> rcp -> fma -> fmac_dpp, the next pivot's column is updated first, and
     // the "VALU write -> DPP read of the same VGPR" wait states (2) are always covered by the two instructions in between -
-    // no s_nop but the leading one (which covers whatever the compiler placed last).
-#ifndef ADKF_M_NEWTON
-#define ADKF_M_NEWTON 0   // 1: one Newton step on the pivot reciprocals (v_rcp_f32 is 1 ulp; the inverses and log-determinants of tools/sweepm_bench.hip are the same to three digits either way, the step costs 50 cycles per block step)
-#endif
-#if !ADKF_M_NEWTON
-#define ADKF_MGJ_NEWTON(pv)
-#else
-#define ADKF_MGJ_NEWTON(pv) "v_fma_f32 %[e], -" pv ", %[r], 1.0\n\tv_fma_f32 %[r], %[e], %[r], %[r]\n\t"
-#endif
+    // no s_nop but the leading one (which covers whatever the compiler placed last).  (No Newton step on the reciprocals:
+    // v_rcp_f32 is 1 ulp, the inverses and log-determinants came out the same to three digits with one, which costs 50 cycles
+    // per block step.)
 #define ADKF_MGJ_STEP(P, dP, dA, dB, dC, pv, mk) \
         "v_mov_b32_dpp " pv ", " dP " quad_perm:[" #P "," #P "," #P "," #P "] row_mask:0xf bank_mask:0xf\n\t" \
         "v_rcp_f32_e32 %[r], " pv "\n\t" \
         "v_cndmask_b32_e64 %[y], " dP ", -1.0, " mk "\n\t" \
         "v_cndmask_b32_e64 %[z], 0, -1.0, " mk "\n\t" \
-        ADKF_MGJ_NEWTON(pv) \
         "v_fma_f32 %[g], -%[r], %[y], %[z]\n\t" \
         "v_fmac_f32_dpp " dA ", " dA ", %[g] quad_perm:[" #P "," #P "," #P "," #P "] row_mask:0xf bank_mask:0xf\n\t" \
         "v_fmac_f32_dpp " dB ", " dB ", %[g] quad_perm:[" #P "," #P "," #P "," #P "] row_mask:0xf bank_mask:0xf\n\t" \
         "v_fmac_f32_dpp " dC ", " dC ", %[g] quad_perm:[" #P "," #P "," #P "," #P "] row_mask:0xf bank_mask:0xf\n\t" \
         "v_cndmask_b32_e64 " dP ", %[g], %[r], " mk "\n\t"
+    // (`e` is an unused scratch operand, kept because the kernels' register assignment depends on it)
     __device__ static __forceinline__ void gj4(float (&D)[4], float (&piv)[4]) {
         float r, e, y, z, g;
         const unsigned long long m0 = 0x1111111111111111ull, m1 = 0x2222222222222222ull, m2 = 0x4444444444444444ull, m3 = 0x8888888888888888ull;
@@ -155,7 +124,7 @@ template <> struct Sweep<128, 512> {
     struct Addr {
         int b;         // B operand of tile x: ct[.][16 x + p][g]  (+ 64 x)
         int bd;        // the same for this wave's own columns 16 w + p: carries the pivot-row values of the A operand
-        int dq;        // dinv[.][g][p & 3]
+        int dq;        // dinv[.][g][p & 3]: read by nobody, but without it hipcc assigns the registers of the kernels around the sweep differently
         int piece;     // ct[.][16 w + 4 g + y][p & 3]  (+ 4 y)
         __device__ __forceinline__ void init() {
             const int lane = threadIdx.x & 63, p = lane & 15, g = lane >> 4, w = wave();
@@ -168,9 +137,7 @@ template <> struct Sweep<128, 512> {
 
     template <int X>
     __device__ static __forceinline__ void mfma(f32x4_t (&acc)[8], float a, float b) {
-#if !(ADKF_M_ABLATE & 8)
         acc[X] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[X], 0, 0, 0);
-#endif
     }
     // the I-th (0..6) tile of the previous step's update in a step whose critical tile is WN and whose predecessor's was K = WN - 1:
     // every tile but K, starting with WN (the critical MFMA accumulates on top of it)
@@ -183,33 +150,11 @@ template <> struct Sweep<128, 512> {
         }
     }
 
-    // A[m = p][k = g] = -F[g][16 w + p] = -sum_k' dinv[g][k'] C[k'][16 w + p] from one dword of D^-1 per lane (lane (g, p)
-    // holds dinv[g][p & 3]: the row is rebuilt by quad broadcasts) and the B operand of the wave's own columns, which carries
-    // C[g][16 w + p]: the other three lane groups' values come by the row swaps of gfx950 (v_permlane16/32_swap) instead of a
-    // 16-byte LDS read.  (In assembly: given the builtins, hipcc took the two results of a swap for equal and dropped one; the
-    // s_nop cover the VALU write -> permlane swap read wait states the compiler cannot see in here, the last one the VALU
-    // write -> MFMA operand read.)
-    __device__ static __forceinline__ float a_operand(float dq, float bd) {
-        float c0, c1, c2, c3, av;
-        asm volatile("v_mov_b32 %[c0], %[b0]\n\tv_mov_b32 %[c1], %[b0]\n\ts_nop 1\n\t"
-                     "v_permlane16_swap_b32 %[c0], %[c1]\n\ts_nop 1\n\t"          // c0 = [r0 r0 r2 r2], c1 = [r1 r1 r3 r3]
-                     "v_mov_b32 %[c2], %[c0]\n\tv_mov_b32 %[c3], %[c1]\n\ts_nop 1\n\t"
-                     "v_permlane32_swap_b32 %[c0], %[c2]\n\t"                      // C[0][.] everywhere, C[2][.] everywhere
-                     "v_permlane32_swap_b32 %[c1], %[c3]\n\ts_nop 1"
-                     : [c0] "=&v"(c0), [c1] "=&v"(c1), [c2] "=&v"(c2), [c3] "=&v"(c3) : [b0] "v"(bd));
-        asm volatile("v_mul_f32_dpp %[t], -%[d], %[c0] quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf\n\t"
-                     "v_fmac_f32_dpp %[t], -%[d], %[c1] quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf\n\t"
-                     "v_fmac_f32_dpp %[t], -%[d], %[c2] quad_perm:[2,2,2,2] row_mask:0xf bank_mask:0xf\n\t"
-                     "v_fmac_f32_dpp %[t], -%[d], %[c3] quad_perm:[3,3,3,3] row_mask:0xf bank_mask:0xf\n\ts_nop 1"
-                     : [t] "=&v"(av) : [d] "v"(dq), [c0] "v"(c0), [c1] "v"(c1), [c2] "v"(c2), [c3] "v"(c3));
-        return av;
-    }
-
     // This wave's 16 columns of the pivot rows of block (gn, WN), out of tile WN (see the header), into slot SW.
     template <int WN, int SW>
     __device__ static __forceinline__ void piece(const f32x4_t (&acc)[8], const Addr& ad, int gn, Smem& sm) {
         const int lane = threadIdx.x & 63, p = lane & 15, g = lane >> 4, a = p & 3;
-        if ((p >> 2) == gn && !(ADKF_M_ABLATE & 64)) {
+        if ((p >> 2) == gn) {
             f32x4_t v = acc[WN];
             if (wave() == WN && g == gn) {   // C := D - I at the pivot columns (M_PP := D - 2I is additive and nobody reads M_PP again: run() applies it at the end)
                 v.x -= (a == 0) ? 1.f : 0.f; v.y -= (a == 1) ? 1.f : 0.f; v.z -= (a == 2) ? 1.f : 0.f; v.w -= (a == 3) ? 1.f : 0.f;
@@ -238,70 +183,49 @@ template <> struct Sweep<128, 512> {
     // Block step s = 8 gq + K (see the header).  `prev`: the operands of step s - 1 (zeros in the very first step); on return
     // the operands of this step, whose update has reached tile WN only.
     template <int K>
-    __device__ static __forceinline__ void step(f32x4_t (&acc)[8], Ops& prev, const Addr& ad, int gq, Smem& sm, int s_stamp = -1) {
-        (void)s_stamp;
+    __device__ static __forceinline__ void step(f32x4_t (&acc)[8], Ops& prev, const Addr& ad, int gq, Smem& sm) {
         constexpr int SLOT = K & 1, WN = (K + 1) & 7;
         const int w = wave();
         const int gn = gq + (K == 7 ? 1 : 0);
         const bool has_next = gn < 4;
-        const bool is_chain = has_next && w == WN && !(ADKF_M_ABLATE & 32);
-        ADKF_MTS(0);
+        const bool is_chain = has_next && w == WN;
         if (is_chain) __builtin_amdgcn_s_setprio(3);
-#if ADKF_M_SLEEP && ADKF_M_SLEEP_MODE == 0
-        else __builtin_amdgcn_s_sleep(ADKF_M_SLEEP);
-#elif ADKF_M_SLEEP && ADKF_M_SLEEP_MODE == 1
-        else if (w == ((WN + 4) & 7)) __builtin_amdgcn_s_sleep(ADKF_M_SLEEP);
-#endif
+        else __builtin_amdgcn_s_sleep(MSWEEP_SLEEP);
         // the operands of the hand-off chain first: D^-1, the wave's own columns, the critical tile's B; then the other seven
         const float* ctr = &sm.ct[SLOT][0][0];
-#if ADKF_M_A128
         const float4 dv4 = *reinterpret_cast<const float4*>(&sm.dinv[SLOT][(threadIdx.x & 63) >> 4][0]);
         const float4 cr4 = *reinterpret_cast<const float4*>(ctr + (ad.bd & ~3));
-#else
-        const float dq = (&sm.dinv[SLOT][0][0])[ad.dq];
-        const float bd = ctr[ad.bd];
-#endif
         Ops cur;
         cur.b[WN] = ctr[ad.b + 64 * WN];
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int x = 0; x < 8; ++x)
-            if (x != WN) cur.b[x] = (ADKF_M_ABLATE & 16) ? cur.b[WN] * (1.f + x) : ctr[ad.b + 64 * x];
+            if (x != WN) cur.b[x] = ctr[ad.b + 64 * x];
         __builtin_amdgcn_sched_barrier(0);   // all ten reads in flight; the matrix pipe gets the previous step's update meanwhile
-#if ADKF_M_SLEEP && ADKF_M_SLEEP_MODE == 2
-        if (!is_chain) __builtin_amdgcn_s_sleep(ADKF_M_SLEEP);
+        bulk<WN, 0, MSWEEP_EARLY>(acc, prev);
         __builtin_amdgcn_sched_barrier(0);
-#endif
-        bulk<WN, 0, ADKF_M_EARLY>(acc, prev);
-        __builtin_amdgcn_sched_barrier(0);
-#if ADKF_M_A128
+        // A[m = p][k = g] = -F[g][16 w + p] = -sum_k' dinv[g][k'] C[k'][16 w + p] from two 16-byte LDS reads and four FMAs
+        // (36.2 k cycles per sweep; from two dword reads, the row swaps of gfx950 and four DPP FMAs 37.9 k: the swap sequence
+        // with its hazard waits is on the hand-off chain)
         cur.a = -fmaf(dv4.x, cr4.x, fmaf(dv4.y, cr4.y, fmaf(dv4.z, cr4.z, dv4.w * cr4.w)));
-#else
-        cur.a = a_operand(dq, bd);
-#endif
-        ADKF_MTS(1);
         mfma<WN>(acc, cur.a, cur.b[WN]);     // this step's update of the tile the next hand-off comes out of
         __builtin_amdgcn_sched_barrier(0);
-        bulk<WN, ADKF_M_EARLY, ADKF_M_EARLY + ADKF_M_MID>(acc, prev);
+        bulk<WN, MSWEEP_EARLY, MSWEEP_EARLY + MSWEEP_MID>(acc, prev);
         __builtin_amdgcn_sched_barrier(0);
         if (has_next) {
             piece<WN, SLOT ^ 1>(acc, ad, gn, sm);
-            ADKF_MTS(2);
             if (is_chain) {
                 float D[4] = {acc[WN].x, acc[WN].y, acc[WN].z, acc[WN].w}, piv[4] = {1.f, 1.f, 1.f, 1.f};
-                if (!(ADKF_M_ABLATE & 2)) gj4(D, piv);
-                ADKF_MTS(4);
+                gj4(D, piv);
                 publish_dinv<WN, SLOT ^ 1>(D, piv, gn, sm);
-                ADKF_MTS(5);
                 __builtin_amdgcn_s_setprio(0);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        bulk<WN, ADKF_M_EARLY + ADKF_M_MID, 7>(acc, prev);   // the rest issues under the latency of the LDS stores above
+        bulk<WN, MSWEEP_EARLY + MSWEEP_MID, 7>(acc, prev);   // the rest issues under the latency of the LDS stores above
         // (no scheduling fence here: hipcc sinks two of them behind the barrier, in front of the next step's LDS reads, and the
         // sweep is 3 % FASTER that way than with all of them held in front of it - 37.3 k against 38.9 k cycles)
         prev = cur;
-        ADKF_MTS(6);
     }
 
     // In: m = this thread's block of the SPD matrix (identity-padded beyond n).  Out: m = -(A^-1) on the leading n x n part;
@@ -326,14 +250,14 @@ template <> struct Sweep<128, 512> {
                 publish_dinv<0, 0>(D, piv, 0, sm);
             }
             for (int gq = 0; gq < 4; ++gq) {
-                __syncthreads(); step<0>(acc, prev, ad, gq, sm, 8 * gq + 0);
-                __syncthreads(); step<1>(acc, prev, ad, gq, sm, 8 * gq + 1);
-                __syncthreads(); step<2>(acc, prev, ad, gq, sm, 8 * gq + 2);
-                __syncthreads(); step<3>(acc, prev, ad, gq, sm, 8 * gq + 3);
-                __syncthreads(); step<4>(acc, prev, ad, gq, sm, 8 * gq + 4);
-                __syncthreads(); step<5>(acc, prev, ad, gq, sm, 8 * gq + 5);
-                __syncthreads(); step<6>(acc, prev, ad, gq, sm, 8 * gq + 6);
-                __syncthreads(); step<7>(acc, prev, ad, gq, sm, 8 * gq + 7);
+                __syncthreads(); step<0>(acc, prev, ad, gq, sm);
+                __syncthreads(); step<1>(acc, prev, ad, gq, sm);
+                __syncthreads(); step<2>(acc, prev, ad, gq, sm);
+                __syncthreads(); step<3>(acc, prev, ad, gq, sm);
+                __syncthreads(); step<4>(acc, prev, ad, gq, sm);
+                __syncthreads(); step<5>(acc, prev, ad, gq, sm);
+                __syncthreads(); step<6>(acc, prev, ad, gq, sm);
+                __syncthreads(); step<7>(acc, prev, ad, gq, sm);
             }
             bulk<1, 0, 7>(acc, prev);   // the last step's update: tile 0 has it (its "critical" tile), tiles 1..7 get it here
             // M_PP := D - 2I of every block, deferred: inside the loop the accumulators are written by nothing but MFMAs

@@ -12,7 +12,7 @@
 //
 // Tile size: the 128 x 128 tile halves the L2 -> CU operand traffic of the 64 x 64 one, but with 256 threads it leaves
 // one wave per SIMD and nothing to cover the stage/barrier phases: measured 1.4-1.8x SLOWER on every C2 stage, so the
-// host (adkf_gp.hip::tile_edge) always picks 64; the variant stays for experiments with more waves per tile.
+// library instantiates the 64 x 64 tile (GT) only.
 // Also measured without gain: a double-buffered LDS tile with one barrier per chunk (1.530 -> 1.549 ms per C2 step:
 // the second buffer halves the workgroups per CU, which costs more than the removed barrier).
 //
@@ -45,21 +45,11 @@
 
 namespace adkf {
 
-constexpr int GT = 64;        // default tile edge
-constexpr int GTL = 128;      // large tile edge
+constexpr int GT = 64;        // tile edge
 constexpr int GK = 32;        // k chunk
 constexpr int LD_MN = GK + 2; // [mn][k] layout, K-contiguous operands
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#ifndef ADKF_GEMM_ABLATE   // diagnostics (tools/gemm_bench.hip): 1 no fragment reads, 2 no barriers, 4 no operand loads after the first chunk, 8 no epilogue
-#define ADKF_GEMM_ABLATE 0
-#endif
-#if (ADKF_GEMM_ABLATE & 2)
-#define ADKF_GEMM_SYNC() __builtin_amdgcn_sched_barrier(0)
-#else
-#define ADKF_GEMM_SYNC() __syncthreads()
-#endif
 
 template <class P, class = void> struct has_skip : std::false_type {};
 template <class P> struct has_skip<P, std::void_t<decltype(&P::skip)>> : std::true_type {};
@@ -245,10 +235,6 @@ __global__ __launch_bounds__(256) void k_bgemm(P p, int T, int tiles_m, int tile
 #pragma unroll
         for (int s = 0; s < GK / 4; ++s) {
             float af[MI], bf[MI];
-#if (ADKF_GEMM_ABLATE & 1)   // tools/gemm_bench.hip: no fragment reads
-#pragma unroll
-            for (int i = 0; i < MI; ++i) { af[i] = (float)(lane + s + i); bf[i] = (float)(lane - s - i); }
-#else
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
                 const int r = wr * WT + i * 16 + fi;
@@ -259,7 +245,6 @@ __global__ __launch_bounds__(256) void k_bgemm(P p, int T, int tiles_m, int tile
                 const int c = wc * WT + j * 16 + fi;
                 bf[j] = P::B_KCONTIG ? Bs[c * LD_MN + 4 * s + fk] : Bs[(4 * s + fk) * LD_K + c];
             }
-#endif
 #pragma unroll
             for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -295,14 +280,13 @@ __global__ __launch_bounds__(256) void k_bgemm(P p, int T, int tiles_m, int tile
             for (int c = 0; c < DEEP; ++c) {
                 gemm_stage_raw<P, true, TM, P::A_NRAW, 0>(p, As, qa[c], m0, c * GK, sqa);
                 gemm_stage_raw<P, false, TM, P::B_NRAW, 0>(p, Bs, qb[c], n0, c * GK, sqb);
-                ADKF_GEMM_SYNC();
+                __syncthreads();
                 multiply_chunk();
-                ADKF_GEMM_SYNC();
+                __syncthreads();
             }
         }
     }
-#ifndef ADKF_GEMM_NO_RAW
-    if (deep) {} else   // diagnostics: -DADKF_GEMM_NO_RAW sends every tile through the checked path (tools/history/ab_lib.py)
+    if (deep) {} else
     if constexpr (has_raw<P>::value) {
         fast = p.vec && m0 + TM <= M && n0 + TM <= N && K > 0 && (K % GK) == 0 && p.raw_ok();
         if (fast) {
@@ -312,18 +296,17 @@ __global__ __launch_bounds__(256) void k_bgemm(P p, int T, int tiles_m, int tile
             for (int k0 = 0; k0 < K; k0 += GK) {
                 gemm_stage_raw<P, true, TM, P::A_NRAW, SQA>(p, As, qa, m0, k0, sqa);
                 gemm_stage_raw<P, false, TM, P::B_NRAW, SQB>(p, Bs, qb, n0, k0, sqb);
-                ADKF_GEMM_SYNC();
-                if (k0 + GK < K && !(ADKF_GEMM_ABLATE & 4)) {
+                __syncthreads();
+                if (k0 + GK < K) {
                     gemm_fetch_raw<P, true, TM, P::A_NRAW>(p, qa, m0, k0 + GK);
                     gemm_fetch_raw<P, false, TM, P::B_NRAW>(p, qb, n0, k0 + GK);
                 }
                 __builtin_amdgcn_sched_barrier(0);   // the loads above are in flight before the first MFMA issues
                 multiply_chunk();
-                ADKF_GEMM_SYNC();
+                __syncthreads();
             }
         }
     }
-#endif
     if (!fast && !deep) {
         float ra[GPT], rb[GPT];
         gemm_fetch<P, true, TM>(p, ra, m0, 0, M, K);
@@ -377,9 +360,6 @@ __global__ __launch_bounds__(256) void k_bgemm(P p, int T, int tiles_m, int tile
         for (int j = 0; j < MI; ++j) {
             const int gi0 = m0 + wr * WT + i * 16 + fk * 4;
             const int gj = n0 + wc * WT + j * 16 + fi;
-#if (ADKF_GEMM_ABLATE & 8)   // no epilogue (the accumulators stay alive through a store that never happens)
-            if (acc[i][j][0] != 123.456f) continue;
-#endif
             if constexpr (has_pre<P>::value) {
                 if (deep) {   // (a deep tile lies fully inside the task)
                     const float v4[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};

@@ -35,9 +35,6 @@ namespace adkf {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int X3_RS = 40;   // LDS row stride in bfloat16 (80 bytes)
-#ifndef ADKF_X3_ABLATE   // diagnostics (tools/x3_bench.hip): 1 no MFMAs, 2 no splitting arithmetic, 4 no operand loads after the first chunk, 8 no epilogue, 16 no LDS fragment reads
-#define ADKF_X3_ABLATE 0
-#endif
 
 // two floats -> their three bfloat16 pieces, packed pairwise (low half: a, high half: b).  Round to nearest at every cut (v_cvt_pk_bf16_f32):
 // the pieces still sum to the float exactly (the remainders have 16, then 8 significant bits), and - unlike cutting by truncation,
@@ -50,9 +47,6 @@ __device__ __forceinline__ uint32_t x3_pack(float a, float b) {
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
 }
 __device__ __forceinline__ void x3_split2(float a, float b, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-#if (ADKF_X3_ABLATE & 2)
-    p0 = __float_as_uint(a); p1 = __float_as_uint(b); p2 = p0 ^ p1; return;
-#endif
     p0 = x3_pack(a, b);
     const float ra = a - __uint_as_float(p0 << 16), rb = b - __uint_as_float(p0 & 0xffff0000u);   // exact
     p1 = x3_pack(ra, rb);
@@ -219,20 +213,7 @@ __global__ __launch_bounds__(NT) void k_bgemm3(P p, int T, int tiles_m, int tile
         if (p.skip(m0, n0)) K = 0;
     }
     auto multiply_chunk = [&]() __attribute__((always_inline)) {
-#if (ADKF_X3_ABLATE & 1)
-        return;
-#endif
         bf16x8 af[MI][3], bf[MJ][3];
-#if (ADKF_X3_ABLATE & 16)
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) af[i][q] = __builtin_bit_cast(bf16x8, make_uint4(lane + i, lane + q, i, q));
-#pragma unroll
-        for (int j = 0; j < MJ; ++j)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) bf[j][q] = __builtin_bit_cast(bf16x8, make_uint4(lane + j, lane - q, j, q));
-#else
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -243,7 +224,6 @@ __global__ __launch_bounds__(NT) void k_bgemm3(P p, int T, int tiles_m, int tile
 #pragma unroll
             for (int q = 0; q < 3; ++q)
                 bf[j][q] = *reinterpret_cast<const bf16x8*>(Bs + q * C::PLANE + (wc * WTC + j * 16 + fi) * X3_RS + 8 * fk);
-#endif
         // each term runs over all tiles, so that consecutive MFMAs never share an accumulator; smallest first
 #define ADKF_X3_TERM(dst_, qa_, qb_)                                                                                            \
     _Pragma("unroll") for (int i = 0; i < MI; ++i) _Pragma("unroll") for (int j = 0; j < MJ; ++j)                             \
@@ -280,7 +260,7 @@ __global__ __launch_bounds__(NT) void k_bgemm3(P p, int T, int tiles_m, int tile
                 if constexpr (P::B_KCONTIG) x3_stage_raw<P, false, TM, NT, P::B_NRAW, SQB>(p, Bs, qb, n0, k0, sqb);
                 else x3_stage<false, TM, NT, 0>(Bs, cb, sqb);
                 __syncthreads();
-                if (k0 + GK < K && !(ADKF_X3_ABLATE & 4)) fetch(k0 + GK);
+                if (k0 + GK < K) fetch(k0 + GK);
                 __builtin_amdgcn_sched_barrier(0);   // the loads above are in flight before the first MFMA issues
                 multiply_chunk();
                 __syncthreads();
@@ -343,9 +323,6 @@ __global__ __launch_bounds__(NT) void k_bgemm3(P p, int T, int tiles_m, int tile
         for (int j = 0; j < MJ; ++j) {
             const int gi0 = m0 + wr * WTR + i * 16 + fk * 4;
             const int gj = n0 + wc * WTC + j * 16 + fi;
-#if (ADKF_X3_ABLATE & 8)
-            if (acc[i][j][0] != 123.456f) continue;
-#endif
             if constexpr (has_epi4<P>::value) {
                 if (gi0 + 3 < M && gj < N) {
                     const float v4[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};

@@ -65,20 +65,9 @@ struct HyperArgs {
 };
 
 // ---- the kernel function through its exponential factor (the same expressions as kappa3, device_utils.h) -------------------
-#ifndef ADKF_HY_FAST_EXP
-#define ADKF_HY_FAST_EXP 0   // 1: ONE v_exp_f32 of a pre-scaled argument (what k_inner's search evaluations use, inner.h) instead of libm's expf.
-                             // Experiment switch only (tools/r05_fastexp_ab.sh): REJECTED on parity - the golden Matern case gp_N128_Nq128_d256_k1_r1_s0
-                             // goes from 1.9e-5 to 1.1e-4 on v (tolerance 1e-4): the outer stage needs the libm factor
-#endif
-#if ADKF_HY_FAST_EXP
-// absolute error of the factor <= 2^-24 |arg| e^-|arg| <= 2.2e-8 (the rounding of the pre-scaled argument) + 1 ulp of the hardware exp2:
-// below the float32 rounding of the matrix entries the factor goes into
-__device__ __forceinline__ float hy_ex(int kind, float u) {
-    return kind == 0 ? __builtin_amdgcn_exp2f(u * -0.72134752044448170368f) : __builtin_amdgcn_exp2f(__builtin_amdgcn_sqrtf(u) * -3.2259784787f);
-}
-#else
+// The factor is libm's expf.  ONE v_exp_f32 of a pre-scaled argument (what k_inner's search evaluations use, inner.h) was tried and
+// REJECTED on parity: the golden Matern case gp_N128_Nq128_d256_k1_r1_s0 goes from 1.9e-5 to 1.1e-4 on v (tolerance 1e-4).
 __device__ __forceinline__ float hy_ex(int kind, float u) { return kind == 0 ? expf(-0.5f * u) : expf(-SQRT5 * sqrtf(u)); }
-#endif
 __device__ __forceinline__ float hy_k0(int kind, float u, float ex) { return kind == 0 ? ex : (1.f + SQRT5 * sqrtf(u) + (5.f / 3.f) * u) * ex; }
 __device__ __forceinline__ float hy_ex_of_k0(int kind, float u, float k0) { return kind == 0 ? k0 : k0 / (1.f + SQRT5 * sqrtf(u) + (5.f / 3.f) * u); }
 __device__ __forceinline__ void hy_k3(int kind, float u, float ex, float& k0, float& k1, float& k2) {
@@ -404,7 +393,6 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
     auto afun = [=](float d2, int r, int c) { const float u = d2 * il2; return os * hy_k0(kind, u, hy_ex(kind, u)) + (r == c ? noise : 0.f); };
 
     // ================================================ outer stage ==========================================================
-    ADKF_SST(0);
     {
         float4 va[8], vk[8];
         hy_fetch<FULL>(va, Ai, lds, n);
@@ -426,11 +414,9 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
         hy_load<false>(X, HY_LDK, Dqs, lds, m, n, false, k0fun);
     }
     __syncthreads();
-    ADKF_SST(1);
     f32x4_t acc[8];
     hy_zero(acc);
     hy_gemm<false, false>(acc, Y, HY_LDK, X, HY_LDK, kn);     // (C^T / s)[i][j] = sum_k A^-1[i][k] kappa_qs[j][k]
-    ADKF_SST(2);
     if (refine) {   // uniform over the workgroup; none at C2
         // R^T = K_sq - A C^T,  C^T += A^-1 R^T   (ProbCres / ProbCfix; alpha likewise: k_alpha_refine)
         __syncthreads();
@@ -490,10 +476,8 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
             if (i < m) vb[V_MU * vld + i] = s;
         }
     }
-    ADKF_SST(3);
     hy_zero(acc);
     hy_gemm<false, false>(acc, Y, HY_LDM, X, HY_LDK, kn);      // (C K_sq / s)[i][j] = sum_k C[i][k] kappa_qs[j][k]
-    ADKF_SST(4);
     float mm[8][4];
     {
         float dv[8][4];
@@ -516,9 +500,7 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
         }
     }
     __syncthreads();                                           // vec_in complete; everybody is done with X and Y
-    ADKF_SST(5);
     SW::run(mm, m, sm);                                        // mm = -(S^-1)
-    ADKF_SST(6);
     float logdet;
     const int info = SW::finish(m, sm, logdet);
     const float pivr = pivot_ratio<HY_NT>(sm.pivs, m, sm.red);
@@ -538,7 +520,6 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
         if (a.reset_info) a.info[t] = info != 0 ? 100000 + info : 0;
         else if (info != 0 && a.info[t] == 0) a.info[t] = 100000 + info;
     }
-    ADKF_SST(7);
     // W_qq and its reductions from the registers; S^-1 into X (the K_qs image is spent) for the next product
     float r8[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // qq0 qq1 qq2 | oc0 oc1 | ma0 ma1 ma2 | (spare)
     // a vector's entries at this lane's rows / columns of the accumulator layout; fetched from LDS where a pass starts, not kept in
@@ -585,13 +566,10 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
             HY_FENCE();
         }
     }
-    ADKF_SST(8);
     hy_colsum<false>(Y, HY_LDM, nullptr, 0, m, ev, scratch, cte, nullptr);   // C^T e   (barriers inside: X is complete after them)
     if (tid < n) vb[V_CTE * vld + tid] = cte[tid];
-    ADKF_SST(9);
     hy_zero(acc);
     hy_gemm<false, true>(acc, X, HY_LDK, Y, HY_LDM, km);       // (S^-1 C)[i][j] = sum_k S^-1[i][k] C[k][j]
-    ADKF_SST(10);
     {
         float* Wo = a.Wqs + (size_t)t * ldq * lds;
         float e_i[4], e_j[8], al_i[4], al_j[8], cte_i[4], cte_j[8];
@@ -623,13 +601,11 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
             HY_FENCE();
         }
     }
-    ADKF_SST(11);
     __syncthreads();                                           // everybody has read S^-1
     hy_store_t(acc, X, HY_LDK);                                // (Omega C)^T row-major
     __syncthreads();
     hy_zero(acc);
     hy_gemm<true, false>(acc, Y, HY_LDM, X, HY_LDK, km);       // M_A[i][j] = sum_k C[k][i] (Omega C)[k][j]
-    ADKF_SST(12);
     float* Wss_o = a.Wss + (size_t)t * lds * lds;
     {
         float al_i[4], al_j[8], cte_i[4], cte_j[8];
@@ -668,7 +644,6 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
             HY_FENCE();
         }
     }
-    ADKF_SST(13);
     hy_sum<9>(r8, scratch, dsum);                              // (barriers inside: everybody is done with X and Y)
     // grad_phi f_out (solve_v_task): the three pieces of each component nearly cancel - float64 from the row totals on
     const float d1n = sc[S_D1N], d1s = sc[S_D1S], d1l = sc[S_D1L];
@@ -681,7 +656,6 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
         if (a.g_phi_out) { a.g_phi_out[t * 3 + 0] = g0; a.g_phi_out[t * 3 + 1] = g1; a.g_phi_out[t * 3 + 2] = g2; }
     }
     __syncthreads();                                           // (dsum is read; the Hessian stage reuses it)
-    ADKF_SST(14);
 
     // ================================================ Hessian, v, mixed partial ==============================================
     float cn = 0.f, cs = 0.f, cl = 0.f;
@@ -689,14 +663,11 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
         hy_load<FULL>(Y, HY_LDK, Ai, lds, n, n, vec, ident);
         hy_store_t(acc, X, HY_LDK);                            // G (symmetric): from the registers of the epilogue above
         __syncthreads();
-        ADKF_SST(15);
         hy_colsum<true>(X, HY_LDK, Y, HY_LDK, n, al, scratch, be, ga);        // beta = G alpha, gamma = A^-1 alpha
         hy_colsum<false>(Y, HY_LDK, nullptr, 0, n, be, scratch, de, nullptr);   // delta = A^-1 beta
         if (tid < n) { vb[V_BETA * vld + tid] = be[tid]; vb[V_GAMMA * vld + tid] = ga[tid]; vb[V_DELTA * vld + tid] = de[tid]; }
-        ADKF_SST(16);
         hy_zero(acc);
         hy_gemm<false, false>(acc, Y, HY_LDK, X, HY_LDK, kn);  // P[i][j] = sum_k A^-1[i][k] G[j][k]
-        ADKF_SST(17);
         float h9[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // trA2, trPA, trPP, trAinvKll, aKlla, ag, bg, bd, ab
         {
             float al_i[4], al_j[8];
@@ -720,7 +691,6 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
                 HY_FENCE();
             }
         }
-        ADKF_SST(18);
         __syncthreads();                                       // everybody has read G
         hy_store_t(acc, X, HY_LDK);                            // X[j][i] = P[i][j]: P^T row-major
         __syncthreads();
@@ -735,7 +705,6 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
             HY_FENCE();
         }
         if (tid < n) { h9[5] = al[tid] * ga[tid]; h9[6] = be[tid] * ga[tid]; h9[7] = be[tid] * de[tid]; h9[8] = al[tid] * be[tid]; }
-        ADKF_SST(19);
         hy_sum<9>(h9, scratch, dsum);
         if (tid == 0) {
 #pragma unroll
@@ -772,7 +741,6 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
             wv[tid] = wval;
             if (tid < n) vb[V_W * vld + tid] = wval;
         }
-        ADKF_SST(20);
         if (a.corrscale != 0.f) {
             // X[k][i] <- B'[i][k] = (cn - cs noise) A^-1[i][k] + cs [i == k] + cl P[i][k]   (X holds P^T; A^-1 is symmetric)
             const float ca = cn - cs * noise;
@@ -789,10 +757,8 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
                 *reinterpret_cast<float4*>(X + r * HY_LDK + c4) = xv;
             }
             __syncthreads();                                   // (w is visible too)
-            ADKF_SST(21);
             hy_zero(acc);
             hy_gemm<true, false>(acc, X, HY_LDK, Y, HY_LDK, kn);   // ((A^-1 B_v) A^-1)[i][j] = sum_k B'[i][k] A^-1[j][k]
-            ADKF_SST(22);
             float dv[8][4], ess[8][4], wss[8][4];
             hy_dist<FULL, true>(dv, Dss, lds, n, n);
             if (FULL) { hy_sym_load(ess, st_ss); hy_sym_load(wss, Wss_o); }
@@ -826,8 +792,6 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
         if (a.v_out) { a.v_out[t * 3 + 0] = 0.f; a.v_out[t * 3 + 1] = 0.f; a.v_out[t * 3 + 2] = 0.f; }
         if (a.H_out) for (int q = 0; q < 9; ++q) a.H_out[t * 9 + q] = 0.f;
     }
-    ADKF_SST(23);
-    ADKF_SST(24);
 }
 
 }  // namespace adkf

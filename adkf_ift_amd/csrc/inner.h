@@ -8,16 +8,6 @@
 #pragma once
 #include "factor.h"
 
-#ifndef ADKF_EVAL_STAMP
-#define ADKF_EVAL_STAMP 0   // diagnostic build only (tools/history/eval_phases.py): s_memtime at the phase boundaries of one evaluation
-#endif
-#if ADKF_EVAL_STAMP
-extern "C" __device__ unsigned long long adkf_eval_stamps[16];
-#define ADKF_ES(slot) do { if (blockIdx.x == 8 && threadIdx.x == ADKF_EVAL_STAMP - 1 && adkf_stamp_on) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); adkf_eval_stamps[slot] = t_; } } while (0)
-#else
-#define ADKF_ES(slot) do {} while (0)
-#endif
-
 namespace adkf {
 
 struct InnerArgs {
@@ -158,10 +148,6 @@ struct InnerEval {
             asm volatile("" : "+v"(j0), "+v"(i0));
         }
         auto row_of = [&](int r) { return LOW ? i0 + (r << 4) : SW::row(r); };
-#if ADKF_EVAL_STAMP
-        const bool adkf_stamp_on = fast;   // the search evaluations (the final one uses libm expf)
-#endif
-        ADKF_ES(0);
         const float noise = tr[0], os = tr[1], ls = tr[2];   // softplus of x, computed once per trial point (FitShared)
         const float il2 = 1.f / (ls * ls), gl = -2.f / ls;
         if (fast) {
@@ -219,14 +205,9 @@ struct InnerEval {
                 if (!LOW) cache[(r * CB + c) * NT + tid] = k1u;   // lane-private slots, conflict-free
             }
         }
-        ADKF_ES(1);
         __syncthreads();  // previous readers of sm (cross/vec_out) are done
-        ADKF_ES(10);
         SW::run(m, n, sm);
-        ADKF_ES(2);
         SW::solve(m, sm.vec_in, sm.vec_out);  // alpha = A^-1 y
-        ADKF_ES(3);
-        ADKF_ES(4);
         // tr(Ainv G), a^T G a, tr(Ainv), a^T a, y^T a, log|A|, number of non-positive pivots: ONE block reduction
         float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         float ai[RB], aj[CB];
@@ -277,15 +258,12 @@ struct InnerEval {
             acc[5] = logf(p);
             acc[6] = (p > 0.f) ? 0.f : 1.f;
         }
-        ADKF_ES(5);
         block_sum<7, NT>(acc, sm.red);
-        ADKF_ES(6);
         float logdet = acc[5];
         int info = 0;
         if (acc[6] > 0.f) info = SW::finish(n, sm, logdet);   // rare: locate the first non-positive pivot (uniform branch)
         if (tid >= 64) { f = 0.f; return info; }   // the scalar epilogue is consumed by lane 0 only: one wave computes it
         inner_finalize_wave(n, x, pri, logdet, acc, f, g, extra);
-        ADKF_ES(7);
         if (info != 0 || !(f == f)) {
             f = INFINITY;
             return info != 0 ? info : n + 1;

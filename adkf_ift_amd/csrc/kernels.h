@@ -227,13 +227,6 @@ __global__ __launch_bounds__(NT) void k_median(const float* D2ss, const int32_t*
     }
 }
 
-#if ADKF_STAMP_SMALL   // tools/small_bench.hip: s_memtime of the phases of the per-task kernels (workgroup 3, thread 0)
-__device__ unsigned long long g_small_stamps[32];
-#define ADKF_SST(k_) do { if (blockIdx.x == 3 && threadIdx.x == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); g_small_stamps[k_] = t_; } } while (0)
-#else
-#define ADKF_SST(k_) do {} while (0)
-#endif
-
 // ---- Stage C: beta = G alpha, gamma = Ainv alpha, delta = Ainv beta, traces, 3x3 Hessian ------------------
 // (oracle/closed_form.py::inner_stage, want_hessian branch)
 struct HessArgs { TaskView tv; const float* Ainv; const float* P; const float* D2ss; const float* y_s; const float* priors; float* scal; float* vecs; int T; };
@@ -280,7 +273,6 @@ __global__ __launch_bounds__(SMALL_NT) void k_hess(HessArgs a) {
     float* ga = a.vecs + ((size_t)t * NVEC + V_GAMMA) * a.tv.vld;
     float* de = a.vecs + ((size_t)t * NVEC + V_DELTA) * a.tv.vld;
     const int kind = a.tv.kind;
-    ADKF_SST(0);
     // wave per row: beta_i = sum_j G_ij alpha_j ; gamma_i = sum_j Ainv_ij alpha_j
     // (RF rows in flight per wave in both mat-vec passes: a row at a time is a chain of L2 round trips; RF = 8 makes each
     // pass ONE round of loads at 128 points)
@@ -315,7 +307,6 @@ __global__ __launch_bounds__(SMALL_NT) void k_hess(HessArgs a) {
     }
     __threadfence_block();
     __syncthreads();
-    ADKF_SST(1);
     for (int i0 = wv; i0 < n; i0 += RF * NW) {
         float sd[RF];
 #pragma unroll
@@ -337,7 +328,6 @@ __global__ __launch_bounds__(SMALL_NT) void k_hess(HessArgs a) {
     }
     __threadfence_block();
     __syncthreads();
-    ADKF_SST(2);
     // elementwise traces, by 32 x 32 tiles: thread (ty, tx) of tile (ib, jb) owns element (i, j) = (32 ib + ty, 32 jb + tx); the
     // partner P_ji of tr(P P) comes from tile (jb, ib), loaded row-wise as well and turned through LDS (read straight from
     // memory it is a column walk: 64 cache lines per wave instruction, the whole phase was 26 k cycles, 12 us).  At most
@@ -380,9 +370,7 @@ __global__ __launch_bounds__(SMALL_NT) void k_hess(HessArgs a) {
     }
     if (tid < n) { acc[5] = al[tid] * ga[tid]; acc[6] = be[tid] * ga[tid]; acc[7] = be[tid] * de[tid]; acc[8] = al[tid] * be[tid]; }
     for (int i = tid + NT; i < n; i += NT) { acc[5] += al[i] * ga[i]; acc[6] += be[i] * ga[i]; acc[7] += be[i] * de[i]; acc[8] += al[i] * be[i]; }
-    ADKF_SST(3);
     block_sum<9, NT>(acc, red);
-    ADKF_SST(4);
     if (tid == 0) hess_assemble(sc, a.priors + t * 4, n, acc);
 }
 
@@ -441,7 +429,6 @@ __global__ __launch_bounds__(NT) void k_outer_factor(OuterArgs a) {
     const int j0 = SW::bc() * CB;
     if (tid < NMAX) sm.vec_in[tid] = 0.f;
     __syncthreads();
-    ADKF_SST(0);
     // this thread's block of S (exactly symmetric by construction), identity-padded: the loads are issued first and
     // land while the residual below is formed
     float mm[RB][CB];
@@ -479,16 +466,12 @@ __global__ __launch_bounds__(NT) void k_outer_factor(OuterArgs a) {
         }
     }
     __syncthreads();
-    ADKF_SST(1);
     SW::run(mm, m, sm);
-    ADKF_SST(2);
     float logdet;
     const int info = SW::finish(m, sm, logdet);
     const float pivr = pivot_ratio<NT>(sm.pivs, m, sm.red);
-    ADKF_SST(3);
     if (tid == 0) a.scal[(size_t)t * NSCAL + S_PIVR_S] = pivr;
     SW::solve(mm, sm.vec_in, sm.vec_out);  // e = S^-1 r
-    ADKF_SST(4);
     float q[1] = {0.f};
     if (tid < m) {
         const float e = sm.vec_out[tid], r = sm.vec_in[tid];
@@ -497,7 +480,6 @@ __global__ __launch_bounds__(NT) void k_outer_factor(OuterArgs a) {
         q[0] = r * e;
     }
     block_sum<1, NT>(q, sm.red);
-    ADKF_SST(5);
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
         const int i = SW::row(r);
@@ -506,7 +488,6 @@ __global__ __launch_bounds__(NT) void k_outer_factor(OuterArgs a) {
         for (int c = 0; c < CB; ++c) neg[c] = -mm[r][c];
         store_segment<CB>(Si + (size_t)i * a.tv.nq_ld, j0, m, i < m, s_vec, neg);
     }
-    ADKF_SST(6);
     // Cte_j = sum_i C_ij e_i  (thread per column: coalesced; the rows are split over PARTS thread groups so that every
     // thread works and a column is PARTS short chains of loads instead of one long one: 12 -> 4 dependent round trips
     // at 128 x 128)
@@ -550,7 +531,6 @@ __global__ __launch_bounds__(NT) void k_outer_factor(OuterArgs a) {
             }
         }
     }
-    ADKF_SST(7);
     if (tid == 0) {
         const float f = 0.5f * q[0] + 0.5f * logdet + 0.5f * (float)m * LOG_2PI;
         a.scal[(size_t)t * NSCAL + S_FOUT] = f;

@@ -5,7 +5,7 @@
 // of dimension >= 64: pivot ratios below 10), wrong by 1e-3 .. 1e-2 on dL/dZ, grad_phi f_out and v for regression tasks
 // with noise ~0.01 on clustered low-dimensional features (cond 1e3 .. 5e3), where the reference - GPyTorch: Cholesky +
 // triangular solves, fs_mol/models/adaptive_dkt.py:183-191 - stays at 1e-5 .. 1e-4.  A CPU emulation of the precision
-// choices (tools/history/emulate_precision.py, 180 random tasks) shows what it takes to reach 1e-4 everywhere: A^-1, alpha, the
+// choices (tools/history/emulate_precision.py at 4c3bc9b, 180 random tasks) shows what it takes to reach 1e-4 everywhere: A^-1, alpha, the
 // Hessian traces, C = K_qs A^-1, Sigma_q, Sigma_q^-1 and e COMPUTED in float64 and only then rounded to float32 for the
 // cotangent algebra (an explicit inverse ROUNDED to float32 is accurate entry by entry, which is what the element-wise
 // products with kappa' need; the float32 arithmetic that produced it was the problem).  Mixed-precision refinement of
@@ -42,7 +42,7 @@ struct Refine64Args {
     float* vecs; float* scal; float* f_out; int32_t* info;
     float *f_in, *g_in, *gnorm;        // optional: the refined inner value / raw gradient / max |gradient| (adkf_fit, adkf_mll_value_grad)
     double* w64; size_t w64_stride;    // [T][stride] doubles
-    float thresh; int T, want_hess, want_outer, lds_inverse, stop;   // lds_inverse: the launch carries R64_LDS_POINTS^2 doubles of dynamic LDS (the in-LDS inverse and the staged B operands of the products); want_outer: 0 = inner quantities only, 1 = + C and mu (prediction), 2 = + S, S^-1, e, f_out
+    float thresh; int T, want_hess, want_outer, lds_inverse;   // lds_inverse: the launch carries R64_LDS_POINTS^2 doubles of dynamic LDS (the in-LDS inverse and the staged B operands of the products); want_outer: 0 = inner quantities only, 1 = + C and mu (prediction), 2 = + S, S^-1, e, f_out
 };
 
 // doubles per task: [A1 A2 A3 | B1 B2 | S1 S2 | 8 vectors | DDss DDqs DDqq | spare]
@@ -202,7 +202,7 @@ __device__ __forceinline__ void r64_mv_cols(int N, int K, FT ft, FX fx, FE fe, d
 // Squared distances of a flagged task in float64, straight from the float32 features.  The GEMM form of the float32 stage
 // (|x|^2 + |y|^2 - 2 x.y) carries eps32 |x|^2 into every entry: nothing for the benchmark shapes, but for clustered
 // low-dimensional features (the flagged tasks) it was the LAST float32 input of the float64 path and the whole remaining error
-// of it (tools/history/diag_stress.py: dL/dZ_s 1.9e-4 -> 1.7e-6 on the one stress task that stayed above 1e-4).  In float64 the same
+// of it (tools/history/diag_stress.py at 4c3bc9b: dL/dZ_s 1.9e-4 -> 1.7e-6 on the one stress task that stayed above 1e-4).  In float64 the same
 // form carries eps64 |x|^2 - nothing - and runs on the matrix pipe (r64_mm); `same`: X == Y, the diagonal is exactly zero.
 // nx / ny: scratch for the squared row norms (nx + ny doubles).
 __device__ void r64_distances(const float* X, const float* Y, int nx, int ny, int d, double* out, int ldo, double* sx, double* sy, bool same, double* stage = nullptr) {
@@ -287,8 +287,8 @@ __device__ __forceinline__ void r64_sum_n(double (&v)[NV], double* red) {
 // 4 x 8 block of rows 4 ri .. 4 ri + 3 and columns 8 cj .. 8 cj + 7; per step the owners publish pivot row and pivot column to LDS (two
 // buffers in turn: one barrier per step), everybody reads its 8 row entries and its 4 column entries and makes 32 FMAs.  The in-LDS
 // version below ran every step as 32 dependent read-modify-writes per thread with per-element branches and index stepping - 4.6 us per
-// step, 600 us per inverse, 57 % of the float64 path (tools/history/r64_phases.sh).  A first register version with one row strip of 32 columns
-// per thread still took 1.55 us per step: every thread read 33 doubles per step, 128 KB through the CU's LDS port (tools/history/r64_inv_bench.hip);
+// step, 600 us per inverse, 57 % of the float64 path (tools/history/r64_phases.sh at 4c3bc9b).  A first register version with one row strip of 32 columns
+// per thread still took 1.55 us per step: every thread read 33 doubles per step, 128 KB through the CU's LDS port (tools/history/r64_inv_bench.hip at 4c3bc9b);
 // the 4 x 8 block reads 13.  The position of the pivot inside a thread's block must be a compile-time constant (a run-time register
 // index would put the block into scratch memory), hence the steps of a chunk of 32 pivots as a template pack.
 // `buf`: 640 doubles of LDS, 16-byte aligned (two row / column buffers and the pivots).
@@ -367,9 +367,9 @@ __device__ int r64_inverse_reg(double* M, int n, int ld, double& logdet, double*
     return bad;
 }
 
-__device__ int r64_inverse(double* M, int n, int ld, double& logdet, double* colv, double* rowv, double* lds = nullptr, bool in_registers = true) {
+__device__ int r64_inverse(double* M, int n, int ld, double& logdet, double* colv, double* rowv, double* lds = nullptr) {
     const int tid = threadIdx.x;
-    if (in_registers && n <= R64_LDS_POINTS && rowv == colv + R64_MAXN) return r64_inverse_reg(M, n, ld, logdet, colv);   // (colv, rowv: one 2 x 1024 array)
+    if (n <= R64_LDS_POINTS && rowv == colv + R64_MAXN) return r64_inverse_reg(M, n, ld, logdet, colv);   // (colv, rowv: one 2 x 1024 array)
     // up to 128 points the matrix makes its n steps in LDS (`lds`: n * n doubles of dynamic shared memory, 128 KB at n = 128):
     // in global memory every step is 32 dependent read-modify-writes per thread at L2 latency - 1.3 ms per inverse, measured
     double* W = M;
@@ -464,8 +464,6 @@ __global__ void k_double_path_tasks(const float* scal, int ld, int ldq, float th
     flagged[t] = (ra > thresh || rs > thresh) ? 1 : 0;
 }
 
-#define R64_STOP(k_) do { if (a.stop == (k_)) return; } while (0)   // uniform over the workgroup
-
 extern __shared__ double r64_lds[];                     // R64_LDS_POINTS^2 doubles when the batch has at most that many points, else nothing
 
 // The body of k_refine64 for the task of this workgroup (all threads call; returns early - uniformly - for unflagged tasks).
@@ -515,7 +513,6 @@ __device__ __forceinline__ void refine64_task(const Refine64Args& a) {
         r64_distances(Zq, Zq, m, m, a.d, DDqq, ldq, gjc, gjr, true, stage);
     }
     __syncthreads();
-    R64_STOP(1);   // distances
     const float* ys = a.y_s + (size_t)t * ld;
     float* vb = a.vecs + (size_t)t * NVEC * vld;
 
@@ -529,15 +526,13 @@ __device__ __forceinline__ void refine64_task(const Refine64Args& a) {
     }
     double logdetA;
     double* scr = W + r64_scratch_offset(ld, ldq);
-    const int badA = n <= R64_LDS_POINTS ? r64_inverse(A1, n, ld, logdetA, gjc, gjr, a.lds_inverse ? r64_lds : nullptr, a.stop != -1)
+    const int badA = n <= R64_LDS_POINTS ? r64_inverse(A1, n, ld, logdetA, gjc, gjr, a.lds_inverse ? r64_lds : nullptr)
                                          : r64_inverse_blocked(A1, n, ld, logdetA, gjc, gjr, a.lds_inverse ? r64_lds : nullptr, scr);
-    R64_STOP(2);   // + A, A^-1
     float* Ai32 = a.Ainv + (size_t)t * ld * ld;
     for (int e = tid; e < n * n; e += R64_NT) { const int i = e / n, j = e % n; Ai32[(size_t)i * ld + j] = (float)A1[(size_t)i * ld + j]; }
     r64_mv_cols(n, n, [=](int k, int i) { return A1[(size_t)k * ld + i]; }, [=](int k) { return (double)ys[k]; },
                 [=](int i, double v) { v_al[i] = v; vb[V_ALPHA * vld + i] = (float)v; }, gjc);   // (A^-1 is symmetric)
 
-    R64_STOP(3);   // + copy-out, alpha
     // ---- inner scalars and the 3 x 3 Hessian (oracle/closed_form.py::inner_stage)
     {
         for (int e = tid; e < n * n; e += R64_NT) {   // G = dK/dl
@@ -556,7 +551,6 @@ __device__ __forceinline__ void refine64_task(const Refine64Args& a) {
                    [=](int i, int j, double v) { A3[(size_t)i * ld + j] = v; }, stage);   // P = A^-1 G
         }
         __syncthreads();
-        R64_STOP(4);   // + G, three mat-vecs, P = A^-1 G
         double trAinv = 0, trAinvG = 0, aGa = 0, trA2 = 0, trPA = 0, trPP = 0, trAinvKll = 0, aKlla = 0;
         for (int e = tid; e < n * n; e += R64_NT) {
             const int i = e / n, j = e % n;
@@ -630,7 +624,6 @@ __device__ __forceinline__ void refine64_task(const Refine64Args& a) {
         }
     }
     __syncthreads();
-    R64_STOP(5);   // + traces, reductions, Hessian
     if (m <= 0) return;
 
     // ---- outer: C, mu, r, S, S^-1, e, f_out, C^T e   (oracle/closed_form.py::outer_stage)
@@ -658,7 +651,6 @@ __device__ __forceinline__ void refine64_task(const Refine64Args& a) {
         return;
     }
     __syncthreads();
-    R64_STOP(6);   // + K_qs, C, mu
     r64_mm(m, m, n, [=](int i, int k) { return B2[(size_t)i * ld + k]; }, [=](int k, int j) { return B1[(size_t)j * ld + k]; },
            [=](int i, int j, double v) {                                            // Sigma_q = K_qq + noise I - C K_sq, the lower triangle mirrored
                if (j > i) return;
@@ -669,9 +661,8 @@ __device__ __forceinline__ void refine64_task(const Refine64Args& a) {
                S1[(size_t)i * ldq + j] = sv; S1[(size_t)j * ldq + i] = sv;
            }, stage);
     double logdetS;
-    const int badS = m <= R64_LDS_POINTS ? r64_inverse(S1, m, ldq, logdetS, gjc, gjr, a.lds_inverse ? r64_lds : nullptr, a.stop != -1)
+    const int badS = m <= R64_LDS_POINTS ? r64_inverse(S1, m, ldq, logdetS, gjc, gjr, a.lds_inverse ? r64_lds : nullptr)
                                          : r64_inverse_blocked(S1, m, ldq, logdetS, gjc, gjr, a.lds_inverse ? r64_lds : nullptr, scr);
-    R64_STOP(7);   // + S, S^-1
     if (a.S) {
         float* S32 = a.S + (size_t)t * ldq * ldq;
         for (int e = tid; e < m * m; e += R64_NT) { const int i = e / m, j = e % m; S32[(size_t)i * ldq + j] = (float)S1[(size_t)i * ldq + j]; }
@@ -699,7 +690,7 @@ __global__ __launch_bounds__(R64_NT) void k_refine64(Refine64Args a) { refine64_
 //
 // With A^-1, C, Sigma_q^-1 and e computed in float64 the remaining error of flagged tasks (cond 2e3 .. 5e3) sat in the float32
 // products and reductions downstream: Omega C, C^T (Omega C), (A^-1 B_v) A^-1 and the sums behind grad_phi f_out - 1.2x .. 2.3x the
-// tolerance on v and dL/dZ for 4 of 180 stress tasks, none when the emulation runs them in float64 (tools/history/emulate_precision.py,
+// tolerance on v and dL/dZ for 4 of 180 stress tasks, none when the emulation runs them in float64 (tools/history/emulate_precision.py at 4c3bc9b,
 // configuration "all64w").  This kernel redoes exactly that algebra from the float64 matrices k_refine64 left in the workspace
 // region - W_ss (direct and mixed part), W_qs, W_qq, grad_phi f_out, v, w - and then dL/dZ itself, in the difference form
 //     dZs_i = sum_k 4 Wss_ik (z_i - z_k) + sum_q 2 Wqs_qi (z_i - zq_q),   dZq_i = sum_k 2 Wqs_ik (zq_i - z_k) + sum_q 4 Wqq_iq (zq_i - zq_q)
@@ -713,7 +704,6 @@ struct Cot64Args {
     double* w64; size_t w64_stride; float thresh; int T, with_hessian, flags; float dirscale, corrscale; float *g_phi_out, *v_out;
     float* H_out;   // [T, 9] or null: the float64 path's Hessian (k_refine64 leaves it in the scalars) for the caller
     int lds_stage;  // the launch carries R64_LDS_POINTS^2 doubles of dynamic LDS: the products stage their B operands there
-    int stop;       // diagnostics (ADKF_R64_STOP, tools/history/r64_phases.sh): leave after phase `stop` (0: run everything)
 };
 
 __device__ __forceinline__ void cotangent64_task(const Cot64Args& a) {
@@ -761,7 +751,6 @@ __device__ __forceinline__ void cotangent64_task(const Cot64Args& a) {
                 [=](int j, double v) { v_cte[j] = v; }, mvbuf);                                                      // C^T e
     r64_mm(m, n, m, [=](int i, int k) { return S1[(size_t)i * ldq + k]; }, [=](int k, int j) { return B2[(size_t)k * ld + j]; },
            [=](int i, int j, double v) { B1[(size_t)i * ld + j] = 0.5 * (v - v_e[i] * v_cte[j]); }, stage);   // Omega C = (S^-1 C - e (C^T e)^T) / 2
-    R64_STOP(9);   // (8 = all of refine64_task) + C^T e, Omega C
     double oc0 = 0, oc1 = 0, ma0 = 0, ma1 = 0, ma2 = 0, qq0 = 0, qq1 = 0, qq2 = 0;
     {   // M_A = C^T (Omega C) + sym(C^T e alpha^T)   (the three reductions ride in the product's epilogue)
         double* pm0 = &ma0; double* pm1 = &ma1; double* pm2 = &ma2;
@@ -775,7 +764,6 @@ __device__ __forceinline__ void cotangent64_task(const Cot64Args& a) {
                    *pm1 += MA * k0; *pm2 += MA * os * k1 * u * gl;
                }, stage);
     }                                               // (barrier inside) Omega C has been read by everybody: it turns into W_qs in place
-    R64_STOP(10);  // + M_A
     for (int e = tid; e < m * n; e += R64_NT) {     // M_B -> W_qs
         const int i = e / n, j = e % n;
         const double MB = -2.0 * B1[(size_t)i * ld + j] - v_e[i] * v_al[j];
@@ -823,7 +811,6 @@ __device__ __forceinline__ void cotangent64_task(const Cot64Args& a) {
         sc[S_CN] = (float)coef[0]; sc[S_CS] = (float)coef[1]; sc[S_CL] = (float)coef[2];
     }
     __syncthreads();
-    R64_STOP(11);  // + W_qs, W_qq, reductions, v
     const double cn = coef[0], cs = coef[1], cl = coef[2];
     if (a.with_hessian) {
         for (int i = tid; i < n; i += R64_NT) {
@@ -856,7 +843,6 @@ __device__ __forceinline__ void cotangent64_task(const Cot64Args& a) {
         for (int e = tid; e < n * n; e += R64_NT) wss_of(e / n, e % n, 0.0);
         __syncthreads();
     }
-    R64_STOP(12);  // + W_ss with the mixed part
     // ---- dL/dZ in the difference form, from the float64 weights
     const int d = a.d;
     const float* Zs = a.Zs + (size_t)t * ld * d;
@@ -868,7 +854,6 @@ __device__ __forceinline__ void cotangent64_task(const Cot64Args& a) {
     r64_mv_cols(n, n, [=](int k, int i) { return A2[(size_t)k * ld + i]; }, [](int) { return 1.0; }, [=](int i, double v) { rs_ss[i] = v; }, mvbuf);   // (W_ss, W_qq: symmetric)
     r64_mv(m, n, [=](int i, int k) { return B1[(size_t)i * ld + k]; }, [](int) { return 1.0; }, [=](int i, double v) { rs_qs_row[i] = v; });
     r64_mv_cols(m, m, [=](int k, int i) { return S2[(size_t)k * ldq + i]; }, [](int) { return 1.0; }, [=](int i, double v) { rs_qq[i] = v; }, mvbuf);
-    R64_STOP(13);  // + row / column sums of the weights
     if (a.dZs) {
         float* out = a.dZs + (size_t)t * ld * d;
         // dZs_i = 4 (rs_ss_i z_i - sum_k Wss_ik z_k) + 2 (cs_qs_i z_i - sum_q Wqs_qi zq_q): one product over k = [support | query]
@@ -891,7 +876,6 @@ __device__ __forceinline__ void cotangent64_task(const Cot64Args& a) {
 __global__ __launch_bounds__(R64_NT) void k_tail64(Refine64Args ra, Cot64Args ca) {
     refine64_task(ra);
     __syncthreads();
-    if (ra.stop > 0 && ra.stop <= 8) return;
     cotangent64_task(ca);
 }
 

@@ -1,5 +1,4 @@
-// Timing of the batched distance GEMM (csrc/gemm.h + ProbDistMulti) at the C2 shape, with the ablation switches of gemm.h
-// (-DADKF_GEMM_ABLATE=bits).  Not part of the library.
+// Timing of the batched distance GEMM (csrc/gemm.h + ProbDistMulti) at the C2 shape.  Not part of the library.
 //   hipcc -O3 --offload-arch=gfx950 -std=c++17 -I adkf_ift_amd/csrc tools/gemm_bench.hip -o tools/gemm_bench
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -35,7 +34,7 @@ int main() {
         hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1);
         const double flop = 2.0 * T * 10 * 64 * 64 * d;
-        printf("ablate=%d  %.2f us per launch  %.1f TFLOP/s\n", (int)ADKF_GEMM_ABLATE, ms * 1000 / 20, flop / (ms / 20 * 1e-3) / 1e12);
+        printf("%.2f us per launch  %.1f TFLOP/s\n", ms * 1000 / 20, flop / (ms / 20 * 1e-3) / 1e12);
     }
     std::vector<float> out(16);
     hipMemcpy(out.data(), Dqs, 64, hipMemcpyDeviceToHost);

@@ -1,5 +1,5 @@
 // Timing of one block step of the blocked sweep (csrc/large.h: k_lg_diag, ProbLgPanel, ProbLgUpdate) at the C5 shape (8 tasks of
-// 1024 points), each launch on its own, with the ablation switches of gemm.h (-DADKF_GEMM_ABLATE=bits).  Not part of the library.
+// 1024 points), each launch on its own.  Not part of the library.
 //   hipcc -O3 --offload-arch=gfx950 -std=c++17 -I adkf_ift_amd/csrc tools/lg_bench.hip -o tools/lg_bench
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -51,7 +51,7 @@ int main(int argc, char** argv) {
             hipEventRecord(e1);
             hipEventSynchronize(e1);
             float ms; hipEventElapsedTime(&ms, e0, e1);
-            if (rep) printf("mode=%d ablate=%d T=%d n=%d %s  %.2f us per launch\n", mode, (int)ADKF_GEMM_ABLATE, T, n, which == 0 ? "diag  " : which == 1 ? "panel " : "update", ms * 1000 / reps);
+            if (rep) printf("mode=%d T=%d n=%d %s  %.2f us per launch\n", mode, T, n, which == 0 ? "diag  " : which == 1 ? "panel " : "update", ms * 1000 / reps);
         }
     return 0;
 }

@@ -6,7 +6,8 @@ profiles/r03_bench_kernel_stats.csv, r03_k_inner_pmc.json (FETCH_SIZE / WRITE_SI
     python tools/make_pmc_json.py r04 [commit]        (round 4: tools/round4_profiles.sh; k_inner AND k_hyper, profiles/r04_*)
     python tools/make_pmc_json.py c5 [commit]         (round 4: tools/r04_c5_pmc.sh; traffic of one blocked fit by dispatch order)
     python tools/make_pmc_json.py r05 <commit>        (round 5: tools/r05_round_end.sh, ON the GPU box: summaries into gpurun_out/r05_*; the
-                                                       raw rocprofv3 directories are deleted there)"""
+                                                       raw rocprofv3 directories are deleted there)
+The profiling scripts named here are no longer in the tree; they are in git history (e.g. tools/history/ at 4c3bc9b)."""
 import csv
 import glob
 import json

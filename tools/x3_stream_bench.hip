@@ -1,6 +1,6 @@
 // The streaming forms of csrc/dense_x3.h against the forms they replace, at the C2 stand-in feature map's shape by default:
 //   forward   k_dense3 (one chunk of loads in flight)  vs  k_dense3_sk<K / 32> (persistent, a row tile's whole K extent in registers)
-//   gradient  k_dense3_tn                              vs  k_dense3_tnd<2 | 3 | 4> (deeper prefetch, XCD-aware order)
+// and the time of the weight gradient k_dense3_tn on the same operands.
 // Time per launch (HIP events, 20 launches, third repetition), and a bit-for-bit comparison of the results (same products, same order).
 // Not part of the library.
 //   hipcc -O3 --offload-arch=gfx950 -std=c++17 -I adkf_ift_amd/csrc tools/x3_stream_bench.hip -o tools/x3_stream_bench
@@ -46,8 +46,7 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&C0, (size_t)M * N * 4)); CK(hipMalloc(&C1, (size_t)M * N * 4)); CK(hipMalloc(&Wp, hW.size() * 2 * 3));
     CK(hipMemcpy(A, hA.data(), hA.size() * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(W, hW.data(), hW.size() * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(G, hG.data(), hG.size() * 4, hipMemcpyHostToDevice));
-    if (!optin(&k_dense3) || !optin(&k_dense3_sk<2>) || !optin(&k_dense3_sk<4>) || !optin(&k_dense3_sk<8>) || !optin(&k_dense3_tn) ||
-        !optin(&k_dense3_tnd<2>) || !optin(&k_dense3_tnd<3>) || !optin(&k_dense3_tnd<4>)) { printf("LDS opt-in refused\n"); return 1; }
+    if (!optin(&k_dense3) || !optin(&k_dense3_sk<2>) || !optin(&k_dense3_sk<4>) || !optin(&k_dense3_sk<8>) || !optin(&k_dense3_tn)) { printf("LDS opt-in refused\n"); return 1; }
     hipDeviceProp_t prop; CK(hipGetDeviceProperties(&prop, 0));
     const int cus = prop.multiProcessorCount;
     k_split3<<<(unsigned)(((size_t)N * K / 2 + 255) / 256), 256>>>(W, Wp, (size_t)N * K / 2, (size_t)N * K);
@@ -98,28 +97,11 @@ int main(int argc, char** argv) {
     int rps = (int)((M + sp - 1) / sp);
     rps = (rps + GK - 1) / GK * GK;
     const int splits = (M + rps - 1) / rps;
-    float *P0, *P1;
-    const size_t pn = (size_t)splits * N * K;
-    CK(hipMalloc(&P0, pn * 4)); CK(hipMalloc(&P1, pn * 4));
-    Dense3TnArgs t0{G, N, A, K, P0, M, N, K, rps}, t1 = t0;
-    t1.part = P1;
+    float* P0;
+    CK(hipMalloc(&P0, (size_t)splits * N * K * 4));
+    Dense3TnArgs t0{G, N, A, K, P0, M, N, K, rps};
     const float tt_old = time_us([&]() { k_dense3_tn<<<dim3(tiles, splits), D3_NT, D3_LDS_BYTES>>>(t0); });
     printf("gradient k_dense3_tn       %8.2f us  %6.1f TFLOP/s  (%d tiles x %d row ranges of %d) (%s)\n", tt_old, flop / (tt_old * 1e-6) / 1e12, tiles, splits, rps,
            hipGetErrorString(hipGetLastError()));
-    std::vector<float> q0(pn), q1(pn);
-    CK(hipMemcpy(q0.data(), P0, pn * 4, hipMemcpyDeviceToHost));
-    for (int depth = 2; depth <= 4; ++depth) {
-        CK(hipMemset(P1, 0x7f, pn * 4));
-        auto launch = [&]() {
-            if (depth == 2) k_dense3_tnd<2><<<tiles * splits, D3_NT, D3_LDS_BYTES>>>(t1, tiles, splits);
-            else if (depth == 3) k_dense3_tnd<3><<<tiles * splits, D3_NT, D3_LDS_BYTES>>>(t1, tiles, splits);
-            else k_dense3_tnd<4><<<tiles * splits, D3_NT, D3_LDS_BYTES>>>(t1, tiles, splits);
-        };
-        const float tt = time_us(launch);
-        CK(hipDeviceSynchronize());
-        CK(hipMemcpy(q1.data(), P1, pn * 4, hipMemcpyDeviceToHost));
-        printf("gradient k_dense3_tnd<%d>   %8.2f us  %6.1f TFLOP/s  bit-identical to k_dense3_tn: %s (%s)\n", depth, tt, flop / (tt * 1e-6) / 1e12,
-               memcmp(q0.data(), q1.data(), pn * 4) == 0 ? "yes" : "NO", hipGetErrorString(hipGetLastError()));
-    }
     return 0;
 }
