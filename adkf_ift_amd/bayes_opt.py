@@ -49,7 +49,7 @@ def create_gp(train_x: torch.Tensor, train_y: torch.Tensor, kernel_type: str, de
 def _support_batch(model: ExactGPLayer, mll: ExactMarginalLogLikelihood):
     Z = model.train_inputs[0].detach().float().contiguous()
     y = model.train_targets.detach().float().contiguous()
-    b = gp_ops.GPBatch(Z[None], y[None], mll.priors_row(Z.device), model.kernel_id)
+    b = gp_ops.GPBatch(Z[None], y[None], mll.priors_row(Z.device), model.kernel_id, ard=model.ard)
     phi = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])[None]
     return b, phi
 
@@ -80,7 +80,8 @@ def latent_posterior(model: ExactGPLayer, mll: ExactMarginalLogLikelihood, X: to
         return mean, var
     Z = model.train_inputs[0].detach().float().contiguous()
     y = model.train_targets.detach().float().contiguous()
-    b = gp_ops.GPBatch(Z[None], y[None], mll.priors_row(Z.device), model.kernel_id, Z_q=X.detach().float().contiguous()[None])
+    b = gp_ops.GPBatch(Z[None], y[None], mll.priors_row(Z.device), model.kernel_id, Z_q=X.detach().float().contiguous()[None],
+                       ard=model.ard)
     phi = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])[None]
     mean, var, _, info = gp_ops.predict(b, phi, want_var=True)
     gp_ops.check_info(info, "BO posterior")

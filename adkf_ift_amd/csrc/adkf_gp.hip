@@ -134,8 +134,10 @@ Workspace carve(void* base, int T, int ns, int nq, int d) {
 // adkf_predict_marginal borrows regions of a support-only workspace that prediction does not read - [P, W_ss] and, beyond 128
 // points, the blocked sweep's scratch [lg_Dinv, lg_F] - for its row-tile slots.  Both spans are checked here against every
 // buffer prediction reads (a reorder of carve() that broke that makes the span unusable instead of silently overwritten).
+// also_read: further buffers the kernels read (adkf_predict_marginal_ard: the ARD region's mu, il, l and Zt_s, carved after
+// the base carve).
 struct SlotRegion { float* base; size_t floats; };
-void pm_slot_regions(const Workspace& w, int T, int ns, SlotRegion (&r)[2]) {
+void pm_slot_regions(const Workspace& w, int T, int ns, SlotRegion (&r)[2], const SlotRegion* also_read = nullptr, int n_also = 0) {
     const size_t Tz = (size_t)T;
     r[0] = {w.P, (size_t)(w.Wss - w.P) + Tz * ns * ns};
     r[1] = {w.lg_Dinv, w.lg_Dinv ? (size_t)(w.lg_F - w.lg_Dinv) + Tz * LB * w.vld : 0};
@@ -152,6 +154,10 @@ void pm_slot_regions(const Workspace& w, int T, int ns, SlotRegion (&r)[2]) {
         const char *b0 = reinterpret_cast<const char*>(q.base), *b1 = reinterpret_cast<const char*>(q.base + q.floats);
         for (const auto& x : rd)
             if (x[0] && x[0] < b1 && b0 < x[1]) { q = {nullptr, 0}; break; }
+        for (int k = 0; k < n_also && q.base; ++k) {
+            const char *x0 = reinterpret_cast<const char*>(also_read[k].base), *x1 = reinterpret_cast<const char*>(also_read[k].base + also_read[k].floats);
+            if (x0 && x0 < b1 && b0 < x1) q = {nullptr, 0};
+        }
     }
 }
 
@@ -674,9 +680,9 @@ void ard_dz_support(ArdCtx& c, const float* W, float* out, const int32_t* n_over
     launch_gemm(pz, c.T, c.ns, c.d, c.st, x3_for(c.d));
 }
 
-// One evaluation of f_in and its gradient in the h raw parameters at x [T, h]; leaves Zt_s, D2ss, Ainv, alpha, the
-// scalars, G = d f_in / d Z~, S1 and gt for x in the workspace.
-int ard_eval(ArdCtx& c, const float* x, float* f, float* g, int32_t* info3) {
+// The inner quantities at x [T, h]: l, Zt_s, D2ss, Ainv, alpha and the scalars in the workspace (the first half of
+// ard_eval; adkf_predict_marginal_ard runs it alone, so the fit and the prediction produce A^-1 by the same launches).
+int ard_inner(ArdCtx& c, const float* x, int32_t* info3) {
     hipStream_t st = c.st;
     k_ard_params<<<dim3(ceil_div(c.d, 256), c.T), 256, 0, st>>>(c.v, x);
     k_ard_scale<<<dim3(ceil_div(c.ns, 4), c.T), 256, 0, st>>>(c.v, c.b->Z_s, c.a.Zt_s, c.b->n_s, c.ns);
@@ -684,7 +690,14 @@ int ard_eval(ArdCtx& c, const float* x, float* f, float* g, int32_t* info3) {
     if (rc) return rc;
     InnerArgs ia = inner_args(&c.bt, c.w, c.a.phi3, info3);
     ia.f_out = c.a.f3; ia.g_out = c.a.g3;
-    rc = launch_inner(ia, c.w, st);
+    return launch_inner(ia, c.w, st);
+}
+
+// One evaluation of f_in and its gradient in the h raw parameters at x [T, h]; leaves Zt_s, D2ss, Ainv, alpha, the
+// scalars, G = d f_in / d Z~, S1 and gt for x in the workspace.
+int ard_eval(ArdCtx& c, const float* x, float* f, float* g, int32_t* info3) {
+    hipStream_t st = c.st;
+    int rc = ard_inner(c, x, info3);
     if (rc) return rc;
     TaskView tv = make_tv(&c.bt, c.w, false);
     const int win_tiles = std::max(1, std::min(64, c.ns * c.ns / 2048));
@@ -858,6 +871,83 @@ int ard_ift(const adkf_batch_t* b, const float* phi, int flags, bool with_hessia
     if (dZ_q) {
         ArdDzFin fq{c.v, c.a.Gd_q, nullptr, nullptr, nullptr, 0.f, dZ_q, b->n_q, c.nq};
         k_ard_dz_fin<<<dim3(ceil_div(c.d, 256), c.nq, c.T), 256, 0, st>>>(fq);
+    }
+    LAUNCH_OK();
+    return 0;
+}
+
+// The streaming launches of adkf_predict_marginal(_ard), once the inner quantities of the support-only batch b are in w.
+// ARD: b is the scaled batch (Z_s = Zt_s), mean_s the support column means mu, ard the query scaling, also_read the ARD buffers
+// the kernels read (kept out of the row-tile slots).
+template <bool ARD>
+int pm_launch(const adkf_batch_t* b, const Workspace& w, const float* mean_s, const PmArd* ard, const SlotRegion* also_read, int n_also,
+              int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows, const float* best_f, float* mean, float* var, float* ei,
+              int32_t* info, hipStream_t st) {
+    const int T = b->T, ns = b->ns_max;
+    PmArgs pa{};
+    pa.Zq = Zq; pa.Zs = b->Z_s; pa.mean_s = mean_s; pa.q_off = q_off; pa.rows = rows;
+    pa.n_s = b->n_s; pa.ns_ld = ns; pa.d = b->d; pa.kind = b->kernel; pa.T = T;
+    pa.Ainv = w.Ainv; pa.D2ss = w.D2ss; pa.y_s = b->y_s; pa.scal = w.scal; pa.best_f = best_f;
+    pa.mean = mean; pa.var = var; pa.ei = ei;
+    pa.info = info;
+    pa.refine_thresh = refine32_threshold(); pa.r64_thresh = w.w64 ? r64_threshold() : INFINITY;
+    pa.latent = (flags & ADKF_PM_LATENT) ? 1 : 0; pa.maximize = (flags & ADKF_PM_MAXIMIZE) ? 1 : 0;
+    pa.vec = ((b->d & 3) == 0 && aligned16(Zq) && aligned16(b->Z_s)) ? 1 : 0;
+    const int ns_pad = ceil_div(ns, PM_TM) * PM_TM;
+    pa.buf_ld = ns_pad + 4;
+    constexpr int static_lds = (2 * PM_TM * LD_MN + 2 * PM_TM + 4 * PM_TM) * (int)sizeof(float);
+    constexpr int dyn_max = PM_LDS_BYTES - static_lds;
+    static const bool optin = [] {
+        bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_predict_marginal<false, false, ARD>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_max) == hipSuccess;
+        ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_predict_marginal<true, false, ARD>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_max) == hipSuccess;
+        return ok;
+    }();
+    if (!optin) (void)hipGetLastError();
+    // upper bound of the tile count (the true one depends on q_off, which lives on the device)
+    const int64_t tiles = rows / PM_TM + T;
+    // global row-tile slots: [P, W_ss] and, beyond 128 points, the blocked path's scratch [lg_Dinv, lg_F] - neither is read by prediction
+    // a workgroup's row tiles: K (plain); K, C and the vector A^-1 y (refined)
+    auto tile_floats = [&](bool refine) { return refine ? (size_t)2 * PM_TM * pa.buf_ld + ns_pad : (size_t)PM_TM * pa.buf_ld; };
+    auto set_slots = [&](bool refine) {
+        pa.slot_floats = tile_floats(refine);
+        SlotRegion r[2];
+        pm_slot_regions(w, T, ns, r, also_read, n_also);
+        for (int q = 0; q < 2; ++q) { pa.slots[q] = r[q].base; pa.slot_count[q] = (int)std::min<size_t>(r[q].floats / pa.slot_floats, 1 << 20); }
+        return (int64_t)pa.slot_count[0] + pa.slot_count[1];
+    };
+    auto args = [&] {
+        if constexpr (ARD) return PmArdArgs{pa, *ard};
+        else return pa;
+    };
+    // every output row starts at 0: rows outside every task's range and those of skipped tasks (n_s == 0, info != 0) stay so
+    hipMemsetAsync(mean, 0, sizeof(float) * (size_t)rows, st);
+    if (var) hipMemsetAsync(var, 0, sizeof(float) * (size_t)rows, st);
+    if (ei) hipMemsetAsync(ei, 0, sizeof(float) * (size_t)rows, st);
+    auto launch = [&](auto kern, bool refine) {
+        const size_t dyn = tile_floats(refine) * sizeof(float);
+        if (optin && dyn <= (size_t)dyn_max) {
+            int per_cu = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern.lds, PM_NT, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+            const int grid = (int)std::min<int64_t>(tiles, (int64_t)num_cus() * per_cu);
+            kern.lds<<<grid, PM_NT, dyn, st>>>(args());
+        } else {
+            const int64_t slots = set_slots(refine);
+            if (slots < 1) return ADKF_E_WORKSPACE;
+            const int grid = (int)std::min<int64_t>(tiles, std::min<int64_t>(slots, (int64_t)num_cus() * 8));
+            kern.global<<<grid, PM_NT, 0, st>>>(args());
+        }
+        return 0;
+    };
+    struct Plain { decltype(&k_predict_marginal<false, false, ARD>) lds = &k_predict_marginal<false, false, ARD>, global = &k_predict_marginal<false, true, ARD>; };
+    struct Refined { decltype(&k_predict_marginal<true, false, ARD>) lds = &k_predict_marginal<true, false, ARD>, global = &k_predict_marginal<true, true, ARD>; };
+    int rc;
+    if ((rc = launch(Plain{}, false))) return rc;
+    if ((rc = launch(Refined{}, true))) return rc;
+    if (w.w64) {
+        Pm64Args p64{pa, w.w64, w.w64_stride};
+        const int gx = (int)std::min<int64_t>(64, (rows + PM64_NT / 64 - 1) / (PM64_NT / 64));
+        if constexpr (ARD) k_predict_marginal64<true><<<dim3(gx, T), PM64_NT, 0, st>>>(Pm64ArdArgs{p64, *ard});
+        else k_predict_marginal64<false><<<dim3(gx, T), PM64_NT, 0, st>>>(p64);
     }
     LAUNCH_OK();
     return 0;
@@ -1046,7 +1136,7 @@ int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags
                           const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
     int rc = check_batch(b, false);
     if (rc) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q || is_ard(b)) return ADKF_E_BADARG;   // the support set only; ARD is out of scope
+    if (b->nq_max != 0 || b->Z_q || b->y_q || is_ard(b)) return ADKF_E_BADARG;   // the support set only; ARD: adkf_predict_marginal_ard
     if (!phi || !q_off || !info || !ws || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
     if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
     if (ei && !best_f) return ADKF_E_BADARG;
@@ -1067,69 +1157,38 @@ int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags
     launch_refine(make_tv(b, w, false), b, w, false, 0, nullptr, info, st);
     LAUNCH_OK();
     if (rows == 0) return 0;
+    return pm_launch<false>(b, w, w.mean, nullptr, nullptr, 0, flags, Zq, q_off, rows, best_f, mean, var, ei, info, st);
+}
 
-    const int T = b->T, ns = b->ns_max;
-    PmArgs pa{};
-    pa.Zq = Zq; pa.Zs = b->Z_s; pa.mean_s = w.mean; pa.q_off = q_off; pa.rows = rows;
-    pa.n_s = b->n_s; pa.ns_ld = ns; pa.d = b->d; pa.kind = b->kernel; pa.T = T;
-    pa.Ainv = w.Ainv; pa.D2ss = w.D2ss; pa.y_s = b->y_s; pa.scal = w.scal; pa.best_f = best_f;
-    pa.mean = mean; pa.var = var; pa.ei = ei;
-    pa.info = info;
-    pa.refine_thresh = refine32_threshold(); pa.r64_thresh = w.w64 ? r64_threshold() : INFINITY;
-    pa.latent = (flags & ADKF_PM_LATENT) ? 1 : 0; pa.maximize = (flags & ADKF_PM_MAXIMIZE) ? 1 : 0;
-    pa.vec = ((b->d & 3) == 0 && aligned16(Zq) && aligned16(b->Z_s)) ? 1 : 0;
-    const int ns_pad = ceil_div(ns, PM_TM) * PM_TM;
-    pa.buf_ld = ns_pad + 4;
-    constexpr int static_lds = (2 * PM_TM * LD_MN + 2 * PM_TM + 4 * PM_TM) * (int)sizeof(float);
-    constexpr int dyn_max = PM_LDS_BYTES - static_lds;
-    static const bool optin = [] {
-        bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_predict_marginal<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_max) == hipSuccess;
-        ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_predict_marginal<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_max) == hipSuccess;
-        return ok;
-    }();
-    if (!optin) (void)hipGetLastError();
-    // upper bound of the tile count (the true one depends on q_off, which lives on the device)
-    const int64_t tiles = rows / PM_TM + T;
-    // global row-tile slots: [P, W_ss] and, beyond 128 points, the blocked path's scratch [lg_Dinv, lg_F] - neither is read by prediction
-    // a workgroup's row tiles: K (plain); K, C and the vector A^-1 y (refined)
-    auto tile_floats = [&](bool refine) { return refine ? (size_t)2 * PM_TM * pa.buf_ld + ns_pad : (size_t)PM_TM * pa.buf_ld; };
-    auto set_slots = [&](bool refine) {
-        pa.slot_floats = tile_floats(refine);
-        SlotRegion r[2];
-        pm_slot_regions(w, T, ns, r);
-        for (int q = 0; q < 2; ++q) { pa.slots[q] = r[q].base; pa.slot_count[q] = (int)std::min<size_t>(r[q].floats / pa.slot_floats, 1 << 20); }
-        return (int64_t)pa.slot_count[0] + pa.slot_count[1];
-    };
-    // every output row starts at 0: rows outside every task's range and those of skipped tasks (n_s == 0, info != 0) stay so
-    hipMemsetAsync(mean, 0, sizeof(float) * (size_t)rows, st);
-    if (var) hipMemsetAsync(var, 0, sizeof(float) * (size_t)rows, st);
-    if (ei) hipMemsetAsync(ei, 0, sizeof(float) * (size_t)rows, st);
-    auto launch = [&](auto kern, bool refine) {
-        const size_t dyn = tile_floats(refine) * sizeof(float);
-        if (optin && dyn <= (size_t)dyn_max) {
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern.lds, PM_NT, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
-            const int grid = (int)std::min<int64_t>(tiles, (int64_t)num_cus() * per_cu);
-            kern.lds<<<grid, PM_NT, dyn, st>>>(pa);
-        } else {
-            const int64_t slots = set_slots(refine);
-            if (slots < 1) return ADKF_E_WORKSPACE;
-            const int grid = (int)std::min<int64_t>(tiles, std::min<int64_t>(slots, (int64_t)num_cus() * 8));
-            kern.global<<<grid, PM_NT, 0, st>>>(pa);
-        }
-        return 0;
-    };
-    struct Plain { decltype(&k_predict_marginal<false, false>) lds = &k_predict_marginal<false, false>, global = &k_predict_marginal<false, true>; };
-    struct Refined { decltype(&k_predict_marginal<true, false>) lds = &k_predict_marginal<true, false>, global = &k_predict_marginal<true, true>; };
-    if ((rc = launch(Plain{}, false))) return rc;
-    if ((rc = launch(Refined{}, true))) return rc;
-    if (w.w64) {
-        Pm64Args p64{pa, w.w64, w.w64_stride};
-        const int gx = (int)std::min<int64_t>(64, (rows + PM64_NT / 64 - 1) / (PM64_NT / 64));
-        k_predict_marginal64<<<dim3(gx, T), PM64_NT, 0, st>>>(p64);
+int adkf_predict_marginal_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
+                              const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
+    int rc = check_batch(b, false);
+    if (rc) return rc;
+    if (b->nq_max != 0 || b->Z_q || b->y_q || !is_ard(b)) return ADKF_E_BADARG;   // ARD, the support set only
+    if (!phi || !q_off || !info || !ws || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
+    if (ei && !best_f) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
+    ArdCtx c;
+    rc = ard_setup(b, ws, ws_bytes, static_cast<hipStream_t>(stream), c);   // (checks the workspace size before it launches anything)
+    if (rc) return rc;
+    hipStream_t st = c.st;
+    if (b->flags & ADKF_BATCH_REUSE_INNER) {   // the fit's state: mu, Zt_s, D2ss, A^-1, alpha, the scalars (ard_fit ends with an evaluation at phi*)
+        k_ard_params<<<dim3(ceil_div(c.d, 256), c.T), 256, 0, st>>>(c.v, phi);
+        hipMemsetAsync(info, 0, sizeof(int32_t) * (size_t)c.T, st);
+    } else {
+        rc = ard_inner(c, phi, info);
+        if (rc) return rc;
     }
+    // flagged tasks: float64 A^-1 and alpha of the scaled batch (ard_fit does not run it)
+    launch_refine(make_tv(&c.bt, c.w, false), &c.bt, c.w, false, 0, nullptr, info, st);
     LAUNCH_OK();
-    return 0;
+    if (rows == 0) return 0;
+    const size_t td = (size_t)c.T * c.d;
+    k_pm_ard_il<<<(unsigned)((td + 255) / 256), 256, 0, st>>>(c.a.ell, c.a.c, (int64_t)td);   // ArdWs::c: not read by prediction otherwise
+    const PmArd ard{c.a.c, c.a.ell};
+    const SlotRegion rd[] = {{c.a.mu, td}, {c.a.ell, td}, {c.a.c, td}, {c.a.Zt_s, td * c.ns}};
+    return pm_launch<true>(&c.bt, c.w, c.a.mu, &ard, rd, 4, flags, Zq, q_off, rows, best_f, mean, var, ei, info, st);
 }
 
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

@@ -2,7 +2,9 @@
 // testing without a GPU"; section 8(d)(ii): the second CPU baseline, so that GPU-vs-CPU is not only GPU vs slow Python).
 //
 // Same C ABI, HOST pointers: adkf_batch_t, priors, phi layouts, info codes and flags exactly as in the header; `ws` /
-// `ws_bytes` / `stream` are accepted and ignored (adkf_workspace_bytes returns 0 here).  Non-ARD batches of any size.
+// `ws_bytes` / `stream` are accepted and ignored (adkf_workspace_bytes returns 0 here).  Non-ARD batches of any size; the one
+// exception is adkf_predict_marginal_ard, which centres and scales the features by the per-dimension lengthscales and runs
+// the isotropic code at unit lengthscale (csrc/ard.h).
 // Plain loops, OpenMP over the tasks of a batch, float64 arithmetic inside and float32 at the boundary - a Cholesky-based
 // restatement of the same staged closed-form algebra the HIP kernels run (stage names as in DESIGN.md section 3 and
 // oracle/closed_form.py): kernel matrices from difference-form squared distances, A = L L^T, A^-1, the analytic 3 x 3 Hessian,
@@ -38,12 +40,13 @@ inline void kappa(int kind, double u, double& k0, double& k1, double& k2) {
 }
 
 // D2[i][j] = |x_i - y_j|^2 (difference form: exact zero on the diagonal of a matrix with itself)
-Mat sqdist(const float* X, int n, const float* Y, int m, int d) {
+template <class F>
+Mat sqdist(const F* X, int n, const F* Y, int m, int d) {
     Mat D((size_t)n * m);
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < m; ++j) {
             double s = 0.0;
-            const float *x = X + (size_t)i * d, *y = Y + (size_t)j * d;
+            const F *x = X + (size_t)i * d, *y = Y + (size_t)j * d;
             for (int k = 0; k < d; ++k) { const double t = (double)x[k] - (double)y[k]; s += t * t; }
             D[(size_t)i * m + j] = s;
         }
@@ -344,6 +347,30 @@ int check(const adkf_batch_t* b, bool need_q) {
     return 0;
 }
 inline int ns_of(const adkf_batch_t* b, int t) { return b->n_s ? b->n_s[t] : b->ns_max; }
+
+// adkf_predict_marginal(_ard): mean, variance and EI of row r from its squared distances D [n] to the support set of a task
+void pm_row(const Inner& in, int kind, const double* D, const float* y, int flags, const float* best_f, int t, int64_t r, float* mean,
+            float* var, float* ei) {
+    const int n = in.n;
+    const double il2 = 1.0 / (in.l * in.l);
+    std::vector<double> k(n);
+    for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(kind, D[j] * il2, k0, k1, k2); k[j] = in.s * k0; }
+    double mu = 0.0, q = 0.0;
+    for (int j = 0; j < n; ++j) {
+        double cj = 0.0;
+        for (int i = 0; i < n; ++i) cj += k[i] * in.Ainv[(size_t)i * n + j];
+        mu += cj * (double)y[j];
+        q += cj * k[j];
+    }
+    const double vl = in.s - q;
+    mean[r] = (float)mu;
+    if (var) var[r] = (float)((flags & ADKF_PM_LATENT) ? vl : vl + in.noise);
+    if (ei) {
+        const double sg = std::sqrt(std::max(vl, 1e-12)), bf = best_f[t];
+        const double u = ((flags & ADKF_PM_MAXIMIZE) ? (mu - bf) : (bf - mu)) / sg;
+        ei[r] = (float)(sg * (u * 0.5 * std::erfc(-u / std::sqrt(2.0)) + std::exp(-0.5 * u * u) / std::sqrt(2.0 * M_PI)));
+    }
+}
 inline int nq_of(const adkf_batch_t* b, int t) { return b->n_q ? b->n_q[t] : b->nq_max; }
 
 // The quasi-Newton driver of csrc/inner.h (Bfgs + fit_advance), in float64.
@@ -541,27 +568,56 @@ int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags
         Inner in = inner_stage(sqdist(Zs, n, Zs, n, d), b->y_s + (size_t)t * b->ns_max, n, p, b->priors + t * 4, b->kernel, false, false);
         info[t] = in.info;
         int64_t lo = std::min(std::max<int64_t>(q_off[t], 0), rows), hi = std::min(std::max<int64_t>(q_off[t + 1], lo), rows);
-        const double il2 = 1.0 / (in.l * in.l);
-        std::vector<double> k(n), c(n);
         for (int64_t r = lo; r < hi; ++r) {
             if (in.info) break;
             const Mat D = sqdist(Zq + (size_t)r * d, 1, Zs, n, d);
-            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); k[j] = in.s * k0; }
-            double mu = 0.0, q = 0.0;
-            for (int j = 0; j < n; ++j) {
-                double cj = 0.0;
-                for (int i = 0; i < n; ++i) cj += k[i] * in.Ainv[(size_t)i * n + j];
-                mu += cj * (double)b->y_s[(size_t)t * b->ns_max + j];
-                q += cj * k[j];
-            }
-            const double vl = in.s - q;
-            mean[r] = (float)mu;
-            if (var) var[r] = (float)((flags & ADKF_PM_LATENT) ? vl : vl + in.noise);
-            if (ei) {
-                const double sg = std::sqrt(std::max(vl, 1e-12)), bf = best_f[t];
-                const double u = ((flags & ADKF_PM_MAXIMIZE) ? (mu - bf) : (bf - mu)) / sg;
-                ei[r] = (float)(sg * (u * 0.5 * std::erfc(-u / std::sqrt(2.0)) + std::exp(-0.5 * u * u) / std::sqrt(2.0 * M_PI)));
-            }
+            pm_row(in, b->kernel, D.data(), b->y_s + (size_t)t * b->ns_max, flags, best_f, t, r, mean, var, ei);
+        }
+    }
+    return 0;
+}
+
+// ARD: z~ = (z - mu) / l with mu the support column mean and l = softplus(raw_lengthscale) per dimension, then the code above at
+// unit lengthscale (phi3 = (raw_noise, raw_outputscale, softplus^-1(1)), no lengthscale prior), as csrc/ard.h does
+int adkf_predict_marginal_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
+                              const float* best_f, float* mean, float* var, float* ei, int32_t* info, void*, size_t, void*) {
+    if (!b || b->T <= 0 || b->ns_max <= 0 || b->nq_max < 0 || b->d <= 0 || !b->Z_s) return ADKF_E_BADARG;
+    if (b->kernel != ADKF_KERNEL_RBF && b->kernel != ADKF_KERNEL_MATERN52) return ADKF_E_BADARG;
+    if (!(b->flags & ADKF_BATCH_ARD) || b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !q_off || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
+    if (ei && !best_f) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
+    const int d = b->d, h = 2 + d;
+    const double raw_one = std::log(std::expm1(1.0));
+    if (rows > 0) {
+        std::fill(mean, mean + rows, 0.f);
+        if (var) std::fill(var, var + rows, 0.f);
+        if (ei) std::fill(ei, ei + rows, 0.f);
+    }
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        const int n = std::min(ns_of(b, t), b->ns_max);
+        info[t] = 0;
+        if (n <= 0) continue;
+        const float* Zs = b->Z_s + (size_t)t * b->ns_max * d;
+        const float* x = phi + (size_t)t * h;
+        std::vector<double> mu(d, 0.0), l(d);
+        for (int i = 0; i < n; ++i) for (int k = 0; k < d; ++k) mu[k] += Zs[(size_t)i * d + k];
+        for (int k = 0; k < d; ++k) { mu[k] /= n; l[k] = softplus(x[2 + k]); }
+        Mat Zt((size_t)n * d);
+        for (int i = 0; i < n; ++i) for (int k = 0; k < d; ++k) Zt[(size_t)i * d + k] = ((double)Zs[(size_t)i * d + k] - mu[k]) / l[k];
+        const double p[3] = {x[0], x[1], raw_one};
+        const float pri[4] = {b->priors[t * 4], b->priors[t * 4 + 1], 0.f, -1.f};
+        Inner in = inner_stage(sqdist(Zt.data(), n, Zt.data(), n, d), b->y_s + (size_t)t * b->ns_max, n, p, pri, b->kernel, false, false);
+        info[t] = in.info;
+        int64_t lo = std::min(std::max<int64_t>(q_off[t], 0), rows), hi = std::min(std::max<int64_t>(q_off[t + 1], lo), rows);
+        std::vector<double> zt(d);
+        for (int64_t r = lo; r < hi; ++r) {
+            if (in.info) break;
+            for (int k = 0; k < d; ++k) zt[k] = ((double)Zq[(size_t)r * d + k] - mu[k]) / l[k];
+            const Mat D = sqdist(zt.data(), 1, Zt.data(), n, d);
+            pm_row(in, b->kernel, D.data(), b->y_s + (size_t)t * b->ns_max, flags, best_f, t, r, mean, var, ei);
         }
     }
     return 0;

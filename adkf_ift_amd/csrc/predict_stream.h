@@ -31,8 +31,16 @@
 // Tasks flagged for the float64 path (refine64.h) are skipped here; k_predict_marginal64 evaluates their rows in float64 from the features,
 // against the float64 A^-1 and alpha k_refine64 left in the workspace.
 //
+// ARD batches (adkf_predict_marginal_ard) run the same kernels on the scaled features z~ = (z - mu) / l of ard.h at unit
+// lengthscale (ARD = true): the support rows are ard.h's Zt_s, centred and scaled already; the query rows cannot be scaled into a
+// buffer (their number is unbounded), so they are scaled while they are staged, (z - mu) * il with il = 1 / l computed once per
+// call (k_pm_ard_il).  k_predict_marginal64<true> scales with k_ard_scale's float32 expression (z - mu) / l before promoting to
+// float64, so a flagged task's rows see the features ARD adkf_predict would give them.
+//
 // Deterministic: no atomics; a row's result depends on its task's data and its own features only.
 #pragma once
+#include <type_traits>
+
 #include "refine64.h"
 
 namespace adkf {
@@ -55,6 +63,19 @@ struct PmArgs {
     int latent, maximize, vec;
     int buf_ld;                             // leading dimension of a row tile
 };
+
+// the ARD instances: PmArgs::Zs is Zt_s, PmArgs::mean_s the support column means mu of ard.h
+struct PmArd { const float *il, *ell; };   // [T, d] each: 1 / l and l
+struct PmArdArgs { PmArgs p; PmArd r; };
+template <bool ARD> using PmArgsOf = std::conditional_t<ARD, PmArdArgs, PmArgs>;
+__device__ __forceinline__ const PmArgs& pm_base(const PmArgs& a) { return a; }
+__device__ __forceinline__ const PmArgs& pm_base(const PmArdArgs& a) { return a.p; }
+
+// il = 1 / l, so that the staging loop of the ARD instances multiplies instead of divides
+__global__ __launch_bounds__(256) void k_pm_ard_il(const float* ell, float* il, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) il[i] = 1.f / ell[i];
+}
 
 __device__ __forceinline__ int pm_ns(const PmArgs& a, int t) {
     const int n = a.n_s ? a.n_s[t] : a.ns_ld;
@@ -141,8 +162,9 @@ __device__ __forceinline__ float pm_ei(float mean, float var_latent, float best,
     return sigma * fmaf(u, cdf, pdf);
 }
 
-template <bool REFINE, bool GLOBAL>
-__global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgs a) {
+template <bool REFINE, bool GLOBAL, bool ARD = false>
+__global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD> args) {
+    const PmArgs& a = pm_base(args);
     extern __shared__ __attribute__((aligned(16))) float pm_lds[];
     __shared__ float As[PM_TM * LD_MN], Bs[PM_TM * LD_MN];
     __shared__ float rowsq[2][PM_TM];
@@ -182,6 +204,8 @@ __global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgs a) {
         const int kind = a.kind;
         const float* Zs = a.Zs + (size_t)t * a.ns_ld * d;
         const float* mu = a.mean_s + (size_t)t * d;
+        const float* il = nullptr;
+        if constexpr (ARD) il = args.r.il + (size_t)t * d;
         const float* Ai = a.Ainv + (size_t)t * a.ns_ld * a.ns_ld;
         const float* ys = a.y_s + (size_t)t * a.ns_ld;
         const int np = (n + PM_TM - 1) / PM_TM;   // support panels
@@ -196,15 +220,26 @@ __global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgs a) {
                     if (i >= m) { v[0] = v[1] = v[2] = v[3] = 0.f; return; }
                     float z[4], c[4];
                     pm_ld4(a.Zq + (size_t)(r0 + i) * d, k, a.d, a.vec, z); pm_ld4(mu, k, a.d, a.vec, c);
+                    if constexpr (ARD) {
+                        float s[4];
+                        pm_ld4(il, k, a.d, a.vec, s);
 #pragma unroll
-                    for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
+                        for (int x = 0; x < 4; ++x) v[x] = (z[x] - c[x]) * s[x];
+                    } else {
+#pragma unroll
+                        for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
+                    }
                 },
                 [&](int j, int k, float (&v)[4]) {
                     if (j0 + j >= n) { v[0] = v[1] = v[2] = v[3] = 0.f; return; }
-                    float z[4], c[4];
-                    pm_ld4(Zs + (size_t)(j0 + j) * d, k, a.d, a.vec, z); pm_ld4(mu, k, a.d, a.vec, c);
+                    if constexpr (ARD) {   // Zt_s: centred and scaled already
+                        pm_ld4(Zs + (size_t)(j0 + j) * d, k, a.d, a.vec, v);
+                    } else {
+                        float z[4], c[4];
+                        pm_ld4(Zs + (size_t)(j0 + j) * d, k, a.d, a.vec, z); pm_ld4(mu, k, a.d, a.vec, c);
 #pragma unroll
-                    for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
+                        for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
+                    }
                 }, sqa, sqb);
 #pragma unroll
             for (int ps = 0; ps < 2; ++ps) {   // the eight threads that staged a row are eight adjacent lanes
@@ -323,8 +358,13 @@ __global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgs a) {
 // k_refine64's float64 A^-1 (region A1) and the kernel row parked in LDS
 constexpr int PM64_NT = 256;
 struct Pm64Args { PmArgs p; const double* w64; size_t w64_stride; };
+struct Pm64ArdArgs { Pm64Args q; PmArd r; };
+__device__ __forceinline__ const Pm64Args& pm_base(const Pm64Args& a) { return a; }
+__device__ __forceinline__ const Pm64Args& pm_base(const Pm64ArdArgs& a) { return a.q; }
 
-__global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(Pm64Args a64) {
+template <bool ARD = false>
+__global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(std::conditional_t<ARD, Pm64ArdArgs, Pm64Args> args) {
+    const Pm64Args& a64 = pm_base(args);
     const PmArgs& a = a64.p;
     __shared__ double kr[PM64_NT / 64][R64_MAXN];
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -344,7 +384,12 @@ __global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(Pm64Args a64) {
         for (int j = lane; j < n; j += 64) {
             const float* zs = Zs + (size_t)j * a.d;
             double s = 0.0;
-            for (int c = 0; c < a.d; ++c) { const double e = (double)zq[c] - (double)zs[c]; s += e * e; }
+            if constexpr (ARD) {   // the query element scaled as k_ard_scale scales it; zs is Zt_s
+                const float *mu = a.mean_s + (size_t)t * a.d, *el = args.r.ell + (size_t)t * a.d;
+                for (int c = 0; c < a.d; ++c) { const double e = (double)((zq[c] - mu[c]) / el[c]) - (double)zs[c]; s += e * e; }
+            } else {
+                for (int c = 0; c < a.d; ++c) { const double e = (double)zq[c] - (double)zs[c]; s += e * e; }
+            }
             const double u = s * il2;
             double kv;
             if (a.kind == ADKF_KERNEL_RBF) kv = exp(-0.5 * u);

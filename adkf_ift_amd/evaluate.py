@@ -142,7 +142,7 @@ def run_on_batches(model, batches: List[DKTBatch], batch_labels: List[torch.Tens
 @torch.no_grad()
 def meta_test(model, mb: MetaBatch, max_evals: int = 200, gtol: float = 1e-5, ftol: float = 2.22e-9, want_var: bool = False,
               streaming: bool = False):
-    """All tasks at once.  Returns (predictions [T, Nq_max], variance or None, phi* [T, 3], n_evals [T]); padded query
+    """All tasks at once.  Returns (predictions [T, Nq_max], variance or None, phi* [T, h], n_evals [T]); padded query
     slots hold 0.  Classification predictions are already passed through the sigmoid.  ``streaming``: fit on a support-only
     batch and predict the packed query rows with ``gp_ops.predict_marginal`` (no padding to the largest query set, no size
     cap); same layout out."""
@@ -155,8 +155,6 @@ def meta_test(model, mb: MetaBatch, max_evals: int = 200, gtol: float = 1e-5, ft
     y_s, _ = mb.labels(cfg.use_numeric_labels)
     dev = Z_s.device
     priors = torch.empty(mb.num_tasks, 4, dtype=torch.float32, device=dev)
-    if streaming and cfg.use_ard:
-        raise ValueError("meta_test(streaming=True) does not support ARD kernels")
     b = gp_ops.GPBatch(Z_s.float().contiguous(), y_s.to(dev).float().contiguous(), priors, cfg.gp_kernel,
                        Z_q=None if streaming else Z_q.float().contiguous(), n_s=mb.n_s, n_q=None if streaming else mb.n_q,
                        ard=cfg.use_ard)

@@ -303,12 +303,11 @@ def predict_marginal(b: GPBatch, phi: torch.Tensor, Zq: torch.Tensor, q_off: tor
     """Marginal posterior of packed query rows (``pack_rows``) against the support set of ``b`` (which carries no query set):
     returns (mean [rows], var [rows] or None, ei [rows] or None, info [T]).  ``var`` includes the observation noise unless
     ``latent``; ``ei`` (only with ``best_f [T]``) is Expected Improvement on the latent variance, for minimisation unless
-    ``maximize``.  No size cap and a workspace independent of the number of rows (include/adkf_gp.h)."""
+    ``maximize``.  No size cap and a workspace independent of the number of rows (include/adkf_gp.h).  ARD batches (``phi``
+    [T, 2 + d]) go through ``adkf_predict_marginal_ard``."""
     lib = _lib.load()
     if b.nq != 0:
         raise ValueError("predict_marginal takes a support-only batch (no Z_q / y_q): the query rows come packed in Zq")
-    if b.ard:
-        raise ValueError("predict_marginal does not support ARD batches")
     phi = b.check_phi(phi)
     Zq = _f32(Zq, "Zq")
     if Zq.dim() != 2 or Zq.shape[1] != b.d:
@@ -331,8 +330,9 @@ def predict_marginal(b: GPBatch, phi: torch.Tensor, Zq: torch.Tensor, q_off: tor
     flags = (_lib.PM_LATENT if latent else 0) | (_lib.PM_MAXIMIZE if maximize else 0)
     ws, nb = b.workspace()
     cb = b.c_struct()
-    _lib.check(lib.adkf_predict_marginal(C.byref(cb), _ptr(phi), flags, _ptr(Zq), _ptr(q_off), rows, _ptr(best_f), _ptr(mean),
-                                         _ptr(var), _ptr(ei), _ptr(info), _ptr(ws), nb, _stream(b.device)), "adkf_predict_marginal")
+    name = "adkf_predict_marginal_ard" if b.ard else "adkf_predict_marginal"
+    _lib.check(getattr(lib, name)(C.byref(cb), _ptr(phi), flags, _ptr(Zq), _ptr(q_off), rows, _ptr(best_f), _ptr(mean), _ptr(var),
+                                  _ptr(ei), _ptr(info), _ptr(ws), nb, _stream(b.device)), name)
     return mean, var, ei, info
 
 

@@ -173,7 +173,8 @@ int adkf_predict(const adkf_batch_t* b, const float* phi, float* mean, float* va
 
 /* Streaming marginal prediction: the predictive mean, variance and Expected Improvement of query rows of ANY number, in a
  * workspace of exactly adkf_workspace_bytes(T, ns_max, 0, d) bytes whatever `rows` is (csrc/predict_stream.h).
- *   b      the support set only: nq_max == 0, Z_q == y_q == NULL (ADKF_E_BADARG otherwise, and for ARD batches);
+ *   b      the support set only: nq_max == 0, Z_q == y_q == NULL (ADKF_E_BADARG otherwise, and for ARD batches, which
+ *          go to adkf_predict_marginal_ard below);
  *          REUSE_INNER after adkf_fit on the same batch and workspace (with or without DEFER_REFINE) reuses A^-1, alpha and
  *          the scalars, otherwise they are evaluated at phi as adkf_predict does; REUSE_DIST covers D2ss;
  *   Zq     packed query rows [rows, d]; task t owns rows [q_off[t], q_off[t+1]) (q_off: [T+1] int64, device); every range
@@ -185,6 +186,18 @@ int adkf_predict(const adkf_batch_t* b, const float* phi, float* mean, float* va
 #define ADKF_PM_LATENT 1   /* var without the observation noise: the latent f, what BoTorch's analytic EI reads */
 #define ADKF_PM_MAXIMIZE 2 /* ei for maximisation (default: minimisation, as bayes_opt.run_gp_ei_bo) */
 int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows, const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream);
+
+/* The same for ARD batches (one lengthscale per feature dimension); exactly the parameters of adkf_predict_marginal.
+ *   b      must carry ADKF_BATCH_ARD and be support-only (nq_max == 0, Z_q == y_q == NULL); anything else is ADKF_E_BADARG,
+ *          as are a missing Zq with rows > 0, ei without best_f and flag bits other than ADKF_PM_LATENT | ADKF_PM_MAXIMIZE.
+ *          Every argument is checked before anything is launched;
+ *   phi    [T, 2 + d] in the ARD layout (raw_noise, raw_outputscale, raw_lengthscale[0..d));
+ *   ws     exactly adkf_workspace_bytes_ard(T, ns_max, 0, d) bytes whatever `rows` is (less: ADKF_E_WORKSPACE);
+ *          REUSE_INNER after an ARD adkf_fit on the same batch and workspace reuses the fit's state (mu, the scaled support
+ *          features, D2ss, A^-1, alpha, the scalars - the state ARD adkf_predict reuses); otherwise the call evaluates at phi.
+ *          REUSE_DIST is ignored, as for every ARD call.
+ * Outputs, zeroed rows and info as adkf_predict_marginal; info as ARD adkf_predict reports it. */
+int adkf_predict_marginal_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows, const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream);
 
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */

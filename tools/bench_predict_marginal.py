@@ -5,7 +5,11 @@ accepts the shape.  Both are timed on the same work: from the features, with the
 the outputs), the FLOP/s each path EXECUTES (its own count, below) with the marginal path's fractions of the FP32-matrix-pipe
 bound (155 TFLOP/s) and of the HBM bound (6.29 TB/s), and the workspace bytes.  The last line runs the
 tools/bench_meta_test.py shape through meta_test(streaming=True) and streaming=False.
-Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test]"""
+--ard: the same shapes with ARD batches (adkf_predict_marginal_ard) at a per-dimension phi - the median-heuristic lengthscale
+with a seeded +-30 % spread, evaluated once, then timed with REUSE_INNER - against isotropic streaming at the median lengthscale,
+the two timed alternately in this process (median of --reps single calls each), and ARD adkf_predict(want_var=True) where its
+workspace allows the shape.
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -95,6 +99,64 @@ def shape(T, ns, d, rows_per_task, reps, dev):
     print(json.dumps(rec), flush=True)
 
 
+def once(fn):
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    fn()
+    ev[1].record()
+    torch.cuda.synchronize()
+    return ev[0].elapsed_time(ev[1]) / 1e3
+
+
+def shape_ard(T, ns, d, rows_per_task, reps, dev):
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    ba = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "rbf", ard=True)
+    phi0, l0 = gp_ops.init_params_batch(ba, True, True)
+    gs = torch.Generator().manual_seed(1)
+    spread = 1.0 + 0.3 * (2.0 * torch.rand(T, d, generator=gs, dtype=torch.float64) - 1.0)
+    phi = phi0.clone()
+    phi[:, 2:] = torch.log(torch.expm1(l0.double().cpu()[:, None] * spread)).float().to(dev)
+    bi = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "rbf")
+    phii, _ = gp_ops.init_params_batch(bi, True, True)   # (noise, outputscale, the median lengthscale)
+    rows = T * rows_per_task
+    Zq = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):
+        Zq[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    q_off = torch.arange(T + 1, device=dev, dtype=torch.int64) * rows_per_task
+    best = torch.zeros(T, device=dev)
+    lib = _lib.load()
+    fa = lambda: gp_ops.predict_marginal(ba, phi, Zq, q_off, best_f=best)
+    fi = lambda: gp_ops.predict_marginal(bi, phii, Zq, q_off, best_f=best)
+    for b, f in ((ba, fa), (bi, fi)):   # evaluate at phi once; the timed calls reuse it
+        b.flags = 0
+        f()
+        b.flags = gp_ops.REUSE_INNER
+    torch.cuda.synchronize()
+    ta, ti = [], []
+    for _ in range(reps):
+        ta.append(once(fa))
+        ti.append(once(fi))
+    dt, dti = float(np.median(ta)), float(np.median(ti))
+    rec = {"shape": f"ARD T={T} ns={ns} d={d} rows/task={rows_per_task}", "rows": rows, "refined_tasks_ard": int(_refined(ba).sum()),
+           "refined_tasks_isotropic": int(_refined(bi).sum()), "workspace_bytes_ard": int(lib.adkf_workspace_bytes_ard(T, ns, 0, d)),
+           "workspace_bytes_isotropic": int(lib.adkf_workspace_bytes(T, ns, 0, d)),
+           "ard_s": dt, "isotropic_s": dti, "ard_over_isotropic": dt / dti, "ard_rows_per_s": rows / dt,
+           "ard_s_all": ta, "isotropic_s_all": ti}
+    if rows_per_task <= lib.adkf_max_points():
+        bj = gp_ops.GPBatch(Zs, ys, ba.priors, "rbf", Z_q=Zq.view(T, rows_per_task, d), y_q=torch.zeros(T, rows_per_task, device=dev),
+                            ard=True)
+        _, _, _, info = gp_ops.predict(bj, phi, want_var=True)   # the inner quantities at phi into ITS workspace
+        gp_ops.check_info(info)
+        bj.flags = gp_ops.REUSE_INNER
+        dtj = timed(lambda: gp_ops.predict(bj, phi, want_var=True), reps)
+        rec.update({"ard_adkf_predict_s": dtj, "ard_adkf_predict_workspace_bytes": int(lib.adkf_workspace_bytes_ard(T, ns, rows_per_task, d)),
+                    "speedup_vs_ard_adkf_predict": dtj / dt})
+    print(json.dumps(rec), flush=True)
+
+
 def meta_test_shape(dev):
     from adkf_ift_amd import evaluate as E
     from adkf_ift_amd.models import ADKTModel, ADKTModelConfig
@@ -116,12 +178,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--skip-meta-test", action="store_true")
+    ap.add_argument("--ard", action="store_true", help="ARD batches against isotropic streaming (no meta-test line)")
+    ap.add_argument("--skip-large", action="store_true", help="leave out the 1 x 256 x 512 shape with 1M rows")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    shape(16, 128, 2048, 4096, a.reps, dev)
-    shape(16, 128, 2048, 65536, a.reps, dev)
-    shape(1, 256, 512, 1000000, a.reps, dev)
-    if not a.skip_meta_test:
+    run = shape_ard if a.ard else shape
+    run(16, 128, 2048, 4096, a.reps, dev)
+    run(16, 128, 2048, 65536, a.reps, dev)
+    if not a.skip_large:
+        run(1, 256, 512, 1000000, a.reps, dev)
+    if not a.skip_meta_test and not a.ard:
         meta_test_shape(dev)
 
 
