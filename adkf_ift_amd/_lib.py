@@ -17,6 +17,8 @@ IGNORE_DIRECT_GRAD = 2
 INFO_OUTER_BASE = 100000
 PM_LATENT = 1     # adkf_predict_marginal: var without the observation noise
 PM_MAXIMIZE = 2   # ... ei for maximisation
+PM_SCORE_MEAN = 4  # adkf_predict_pool: rank by the posterior mean instead of ei
+POOL_TOPK_MAX = 64
 
 ERRORS = {-1: "bad argument", -2: "unsupported size (see adkf_max_points)", -3: "workspace too small",
           -4: "HIP launch failed"}
@@ -62,6 +64,10 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_predict_marginal_ard": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adkf_predict_pool_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "adkf_predict_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_outer_nll_value_grad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_ift_hypergrad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

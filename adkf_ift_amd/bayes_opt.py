@@ -3,7 +3,8 @@ bayes_opt/bo_utils.py:342-455, on the HIP library.  The GP is fitted on the quer
 evaluated for EVERY candidate with one ``adkf_predict`` call (the reference loops over candidates one by one).  Candidate
 pools beyond ``adkf_max_points()`` rows - or any pool with ``streaming=True`` - go through ``adkf_predict_marginal``, the
 streaming marginal prediction (no size cap, workspace independent of the pool size); ``run_gp_ei_bo(streaming=True)`` then
-gets EI straight from that one call.
+gets EI straight from that one call.  ``run_gp_ei_bo_batched`` runs many replicates of that loop over the same pool at once: one
+batched fit and one ``adkf_predict_pool`` call per iteration, which returns each replicate's best candidates itself.
 
 Only the Matern-5/2 branch exists here (the Tanimoto kernel of the reference's fingerprint baseline is not a
 distance-based kernel and is out of the library's scope).
@@ -133,3 +134,60 @@ def run_gp_ei_bo(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int,
         queried = list(set(queried + pick))
         record.extend(pick[::-1])
     return record
+
+
+@torch.no_grad()
+def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
+                         kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
+                         rngs: List[np.random.Generator]) -> List[List[int]]:
+    """``len(rngs)`` replicates of ``run_gp_ei_bo`` over the same pool at once; returns their records.  Per iteration the
+    replicates' queried sets form ONE batch (initial parameters and priors as ``create_gp`` makes them for each), fitted by ONE
+    ``gp_ops.fit`` with ``fit_gpytorch_scipy``'s options and scored by ONE ``gp_ops.predict_pool`` call that excludes each
+    replicate's queried points and returns its ``query_batch_size`` best candidates: no EI vector ever exists.  Every replicate
+    draws from its own generator in the order the sequential loop does."""
+    R, n = len(rngs), x_all.shape[0]
+    y_all = (y_all - y_all.mean()) / y_all.std()
+    X = x_all.detach().float().contiguous()
+    queried = [rng.choice(np.arange(init_from, n), size=num_init_points, replace=False).tolist() for rng in rngs]
+    records = [[min(q)] for q in queried]
+
+    def free(taken):
+        taken = set(taken)
+        return [i for i in range(n) if i not in taken]
+
+    for _ in range(num_bo_iters):
+        sizes = [len(q) for q in queried]
+        ns = max(sizes)
+        Zs = torch.zeros(R, ns, X.shape[1], dtype=torch.float32, device=X.device)
+        ys = torch.zeros(R, ns, dtype=torch.float32, device=X.device)
+        pri, phi0, best = [], [], []
+        for r, q in enumerate(queried):
+            xq, yq = x_all[q], y_all[q]
+            best.append(yq.min().item())
+            _, model, mll = create_gp(xq, yq, kernel_type, device, noise_init, noise_prior)
+            Zs[r, :sizes[r]] = model.train_inputs[0].detach().float()
+            ys[r, :sizes[r]] = model.train_targets.detach().float()
+            pri.append(mll.priors_row(X.device))
+            phi0.append(torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])[None])
+        n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
+        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=model.ard)
+        phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
+        gp_ops.check_info(info, "run_gp_ei_bo_batched fit")
+        b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+        out = gp_ops.predict_pool(b, phi, X, latent=True, best_f=torch.tensor(best, dtype=torch.float32, device=X.device),
+                                  maximize=False, want_mean=False, want_var=False, want_ei=False, topk=query_batch_size,
+                                  exclude=queried)
+        gp_ops.check_info(out["info"], "BO posterior")
+        top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
+        for r, rng in enumerate(rngs):
+            nonzero = int((top_val[r] > 0).sum())   # of the query_batch_size best: all that the branches below distinguish
+            if nonzero == 0:
+                pick = rng.choice(free(queried[r]), size=query_batch_size, replace=False).tolist()
+            elif nonzero < query_batch_size:
+                pick = top_idx[r, :nonzero].tolist()
+                pick += rng.choice(free(queried[r] + pick), size=query_batch_size - nonzero, replace=False).tolist()
+            else:
+                pick = top_idx[r].tolist()
+            queried[r] = list(set(queried[r] + pick))
+            records[r].extend(pick[::-1])
+    return records

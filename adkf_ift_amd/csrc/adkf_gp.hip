@@ -879,10 +879,15 @@ int ard_ift(const adkf_batch_t* b, const float* phi, int flags, bool with_hessia
 // The streaming launches of adkf_predict_marginal(_ard), once the inner quantities of the support-only batch b are in w.
 // ARD: b is the scaled batch (Z_s = Zt_s), mean_s the support column means mu, ard the query scaling, also_read the ARD buffers
 // the kernels read (kept out of the row-tile slots).
-template <bool ARD>
+// POOL (adkf_predict_pool): Zq is the shared pool, mean / var / ei are [T, rows] and nullable, *pool carries the selection
+// (its grid[] is filled here) and top_idx / top_val receive it.
+constexpr int PM_POOL_LISTS = 4096;   // cap of the candidate lists of a call (the scratch size must not depend on the device)
+inline int pm_pool_chunks_max(int T) { return std::max(1, PM_POOL_LISTS / T); }
+
+template <bool ARD, bool POOL = false>
 int pm_launch(const adkf_batch_t* b, const Workspace& w, const float* mean_s, const PmArd* ard, const SlotRegion* also_read, int n_also,
               int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows, const float* best_f, float* mean, float* var, float* ei,
-              int32_t* info, hipStream_t st) {
+              int32_t* info, hipStream_t st, PmPool* pool = nullptr, int64_t* top_idx = nullptr, float* top_val = nullptr) {
     const int T = b->T, ns = b->ns_max;
     PmArgs pa{};
     pa.Zq = Zq; pa.Zs = b->Z_s; pa.mean_s = mean_s; pa.q_off = q_off; pa.rows = rows;
@@ -898,13 +903,13 @@ int pm_launch(const adkf_batch_t* b, const Workspace& w, const float* mean_s, co
     constexpr int static_lds = (2 * PM_TM * LD_MN + 2 * PM_TM + 4 * PM_TM) * (int)sizeof(float);
     constexpr int dyn_max = PM_LDS_BYTES - static_lds;
     static const bool optin = [] {
-        bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_predict_marginal<false, false, ARD>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_max) == hipSuccess;
-        ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_predict_marginal<true, false, ARD>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_max) == hipSuccess;
+        bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_predict_marginal<false, false, ARD, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_max) == hipSuccess;
+        ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_predict_marginal<true, false, ARD, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn_max) == hipSuccess;
         return ok;
     }();
     if (!optin) (void)hipGetLastError();
-    // upper bound of the tile count (the true one depends on q_off, which lives on the device)
-    const int64_t tiles = rows / PM_TM + T;
+    // upper bound of the tile count (the true one depends on q_off, which lives on the device); POOL: the number of items
+    const int64_t tiles = POOL ? ((rows + PM_TM - 1) / PM_TM) * T : rows / PM_TM + T;
     // global row-tile slots: [P, W_ss] and, beyond 128 points, the blocked path's scratch [lg_Dinv, lg_F] - neither is read by prediction
     // a workgroup's row tiles: K (plain); K, C and the vector A^-1 y (refined)
     auto tile_floats = [&](bool refine) { return refine ? (size_t)2 * PM_TM * pa.buf_ld + ns_pad : (size_t)PM_TM * pa.buf_ld; };
@@ -916,44 +921,110 @@ int pm_launch(const adkf_batch_t* b, const Workspace& w, const float* mean_s, co
         return (int64_t)pa.slot_count[0] + pa.slot_count[1];
     };
     auto args = [&] {
-        if constexpr (ARD) return PmArdArgs{pa, *ard};
+        if constexpr (ARD && POOL) return PmArdPoolArgs{pa, *ard, *pool};
+        else if constexpr (POOL) return PmPoolArgs{pa, *pool};
+        else if constexpr (ARD) return PmArdArgs{pa, *ard};
         else return pa;
     };
     // every output row starts at 0: rows outside every task's range and those of skipped tasks (n_s == 0, info != 0) stay so
-    hipMemsetAsync(mean, 0, sizeof(float) * (size_t)rows, st);
-    if (var) hipMemsetAsync(var, 0, sizeof(float) * (size_t)rows, st);
-    if (ei) hipMemsetAsync(ei, 0, sizeof(float) * (size_t)rows, st);
+    const size_t out_n = POOL ? (size_t)rows * T : (size_t)rows;
+    if (mean && out_n) hipMemsetAsync(mean, 0, sizeof(float) * out_n, st);
+    if (var && out_n) hipMemsetAsync(var, 0, sizeof(float) * out_n, st);
+    if (ei && out_n) hipMemsetAsync(ei, 0, sizeof(float) * out_n, st);
+    if constexpr (POOL) {   // every list starts empty: one that no workgroup writes holds nothing
+        if (pool->k > 0) hipMemsetAsync(pool->cand_idx, 0xff, sizeof(int64_t) * (size_t)T * pool->chunks_max * pool->k, st);
+        pool->grid[0] = pool->grid[1] = pool->grid[2] = 0;
+    }
     auto launch = [&](auto kern, bool refine) {
         const size_t dyn = tile_floats(refine) * sizeof(float);
         if (optin && dyn <= (size_t)dyn_max) {
             int per_cu = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern.lds, PM_NT, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
             const int grid = (int)std::min<int64_t>(tiles, (int64_t)num_cus() * per_cu);
+            if constexpr (POOL) pool->grid[refine ? 1 : 0] = grid;
             kern.lds<<<grid, PM_NT, dyn, st>>>(args());
         } else {
             const int64_t slots = set_slots(refine);
             if (slots < 1) return ADKF_E_WORKSPACE;
             const int grid = (int)std::min<int64_t>(tiles, std::min<int64_t>(slots, (int64_t)num_cus() * 8));
+            if constexpr (POOL) pool->grid[refine ? 1 : 0] = grid;
             kern.global<<<grid, PM_NT, 0, st>>>(args());
         }
         return 0;
     };
-    struct Plain { decltype(&k_predict_marginal<false, false, ARD>) lds = &k_predict_marginal<false, false, ARD>, global = &k_predict_marginal<false, true, ARD>; };
-    struct Refined { decltype(&k_predict_marginal<true, false, ARD>) lds = &k_predict_marginal<true, false, ARD>, global = &k_predict_marginal<true, true, ARD>; };
+    struct Plain { decltype(&k_predict_marginal<false, false, ARD, POOL>) lds = &k_predict_marginal<false, false, ARD, POOL>, global = &k_predict_marginal<false, true, ARD, POOL>; };
+    struct Refined { decltype(&k_predict_marginal<true, false, ARD, POOL>) lds = &k_predict_marginal<true, false, ARD, POOL>, global = &k_predict_marginal<true, true, ARD, POOL>; };
     int rc;
-    if ((rc = launch(Plain{}, false))) return rc;
-    if ((rc = launch(Refined{}, true))) return rc;
-    if (w.w64) {
-        Pm64Args p64{pa, w.w64, w.w64_stride};
-        const int gx = (int)std::min<int64_t>(64, (rows + PM64_NT / 64 - 1) / (PM64_NT / 64));
-        if constexpr (ARD) k_predict_marginal64<true><<<dim3(gx, T), PM64_NT, 0, st>>>(Pm64ArdArgs{p64, *ard});
-        else k_predict_marginal64<false><<<dim3(gx, T), PM64_NT, 0, st>>>(p64);
+    if (rows > 0) {
+        if ((rc = launch(Plain{}, false))) return rc;
+        if ((rc = launch(Refined{}, true))) return rc;
     }
+    if (w.w64 && rows > 0) {
+        Pm64Args p64{pa, w.w64, w.w64_stride};
+        int gx = (int)std::min<int64_t>(64, (rows + PM64_NT / 64 - 1) / (PM64_NT / 64));
+        if constexpr (POOL) {
+            gx = std::min(gx, pool->chunks_max);
+            pool->grid[2] = gx;
+            if constexpr (ARD) k_predict_marginal64<true, true><<<dim3(gx, T), PM64_NT, 0, st>>>(Pm64ArdPoolArgs{p64, *ard, *pool});
+            else k_predict_marginal64<false, true><<<dim3(gx, T), PM64_NT, 0, st>>>(Pm64PoolArgs{p64, *pool});
+        } else {
+            if constexpr (ARD) k_predict_marginal64<true><<<dim3(gx, T), PM64_NT, 0, st>>>(Pm64ArdArgs{p64, *ard});
+            else k_predict_marginal64<false><<<dim3(gx, T), PM64_NT, 0, st>>>(p64);
+        }
+    }
+    if constexpr (POOL)
+        if (pool->k > 0) k_pool_topk<<<T, 64, 0, st>>>(PmTopkArgs{pa, *pool, top_idx, top_val, rows > 0 ? 1 : 0});
     LAUNCH_OK();
     return 0;
 }
 
 inline bool is_ard(const adkf_batch_t* b) { return (b->flags & ADKF_BATCH_ARD) != 0; }
+
+// What adkf_predict_marginal and adkf_predict_pool do before the streaming launches: the inner quantities of the support-only
+// batch b into its workspace (or the fit's, with REUSE_INNER), and the float64 A^-1 and alpha of flagged tasks.
+int pm_prepare(const adkf_batch_t* b, const float* phi, int32_t* info, void* ws, size_t ws_bytes, hipStream_t st, Workspace& w) {
+    w = carve_for(b, ws);
+    if (ws_bytes < w.bytes) return ADKF_E_WORKSPACE;
+    int rc = stage_dist(b, w, false, st);
+    if (rc) return rc;
+    if (b->flags & ADKF_BATCH_REUSE_INNER) {
+        hipMemsetAsync(info, 0, sizeof(int32_t) * (size_t)b->T, st);
+    } else {
+        InnerArgs ia = inner_args(b, w, const_cast<float*>(phi), info);
+        rc = launch_inner(ia, w, st);
+        if (rc) return rc;
+    }
+    // flagged tasks: float64 A^-1 and alpha (a no-op re-evaluation after a fit that already ran it; needed after DEFER_REFINE)
+    launch_refine(make_tv(b, w, false), b, w, false, 0, nullptr, info, st);
+    LAUNCH_OK();
+    return 0;
+}
+
+// The same for ARD batches (adkf_predict_marginal_ard, adkf_predict_pool): c.bt is the scaled batch the streaming kernels run on.
+int pm_prepare_ard(const adkf_batch_t* b, const float* phi, int32_t* info, void* ws, size_t ws_bytes, void* stream, ArdCtx& c) {
+    int rc = ard_setup(b, ws, ws_bytes, static_cast<hipStream_t>(stream), c);   // (checks the workspace size before it launches anything)
+    if (rc) return rc;
+    if (b->flags & ADKF_BATCH_REUSE_INNER) {   // the fit's state: mu, Zt_s, D2ss, A^-1, alpha, the scalars (ard_fit ends with an evaluation at phi*)
+        k_ard_params<<<dim3(ceil_div(c.d, 256), c.T), 256, 0, c.st>>>(c.v, phi);
+        hipMemsetAsync(info, 0, sizeof(int32_t) * (size_t)c.T, c.st);
+    } else {
+        rc = ard_inner(c, phi, info);
+        if (rc) return rc;
+    }
+    // flagged tasks: float64 A^-1 and alpha of the scaled batch (ard_fit does not run it)
+    launch_refine(make_tv(&c.bt, c.w, false), &c.bt, c.w, false, 0, nullptr, info, c.st);
+    LAUNCH_OK();
+    return 0;
+}
+
+// ... and the query scaling of the ARD instances: 1 / l into ArdWs::c (not read by prediction otherwise); rd: the ARD buffers the
+// kernels read
+PmArd pm_ard_scaling(const ArdCtx& c, SlotRegion (&rd)[4]) {
+    const size_t td = (size_t)c.T * c.d;
+    k_pm_ard_il<<<(unsigned)((td + 255) / 256), 256, 0, c.st>>>(c.a.ell, c.a.c, (int64_t)td);
+    rd[0] = {c.a.mu, td}; rd[1] = {c.a.ell, td}; rd[2] = {c.a.c, td}; rd[3] = {c.a.Zt_s, td * c.ns};
+    return PmArd{c.a.c, c.a.ell};
+}
 
 }  // namespace
 
@@ -1141,21 +1212,10 @@ int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags
     if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
     if (ei && !best_f) return ADKF_E_BADARG;
     if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
-    Workspace w = carve_for(b, ws);
-    if (ws_bytes < w.bytes) return ADKF_E_WORKSPACE;
+    Workspace w;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = stage_dist(b, w, false, st);
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, st, w);
     if (rc) return rc;
-    if (b->flags & ADKF_BATCH_REUSE_INNER) {
-        hipMemsetAsync(info, 0, sizeof(int32_t) * (size_t)b->T, st);
-    } else {
-        InnerArgs ia = inner_args(b, w, const_cast<float*>(phi), info);
-        rc = launch_inner(ia, w, st);
-        if (rc) return rc;
-    }
-    // flagged tasks: float64 A^-1 and alpha (a no-op re-evaluation after a fit that already ran it; needed after DEFER_REFINE)
-    launch_refine(make_tv(b, w, false), b, w, false, 0, nullptr, info, st);
-    LAUNCH_OK();
     if (rows == 0) return 0;
     return pm_launch<false>(b, w, w.mean, nullptr, nullptr, 0, flags, Zq, q_off, rows, best_f, mean, var, ei, info, st);
 }
@@ -1170,25 +1230,56 @@ int adkf_predict_marginal_ard(const adkf_batch_t* b, const float* phi, int32_t f
     if (ei && !best_f) return ADKF_E_BADARG;
     if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
     ArdCtx c;
-    rc = ard_setup(b, ws, ws_bytes, static_cast<hipStream_t>(stream), c);   // (checks the workspace size before it launches anything)
+    rc = pm_prepare_ard(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
-    hipStream_t st = c.st;
-    if (b->flags & ADKF_BATCH_REUSE_INNER) {   // the fit's state: mu, Zt_s, D2ss, A^-1, alpha, the scalars (ard_fit ends with an evaluation at phi*)
-        k_ard_params<<<dim3(ceil_div(c.d, 256), c.T), 256, 0, st>>>(c.v, phi);
-        hipMemsetAsync(info, 0, sizeof(int32_t) * (size_t)c.T, st);
-    } else {
-        rc = ard_inner(c, phi, info);
-        if (rc) return rc;
-    }
-    // flagged tasks: float64 A^-1 and alpha of the scaled batch (ard_fit does not run it)
-    launch_refine(make_tv(&c.bt, c.w, false), &c.bt, c.w, false, 0, nullptr, info, st);
-    LAUNCH_OK();
     if (rows == 0) return 0;
-    const size_t td = (size_t)c.T * c.d;
-    k_pm_ard_il<<<(unsigned)((td + 255) / 256), 256, 0, st>>>(c.a.ell, c.a.c, (int64_t)td);   // ArdWs::c: not read by prediction otherwise
-    const PmArd ard{c.a.c, c.a.ell};
-    const SlotRegion rd[] = {{c.a.mu, td}, {c.a.ell, td}, {c.a.c, td}, {c.a.Zt_s, td * c.ns}};
-    return pm_launch<true>(&c.bt, c.w, c.a.mu, &ard, rd, 4, flags, Zq, q_off, rows, best_f, mean, var, ei, info, st);
+    SlotRegion rd[4];
+    const PmArd ard = pm_ard_scaling(c, rd);
+    return pm_launch<true>(&c.bt, c.w, c.a.mu, &ard, rd, 4, flags, Zq, q_off, rows, best_f, mean, var, ei, info, c.st);
+}
+
+size_t adkf_predict_pool_scratch_bytes(int32_t T, int32_t k) {
+    if (T <= 0 || k <= 0 || k > ADKF_POOL_TOPK_MAX) return 0;
+    return (size_t)T * pm_pool_chunks_max(T) * k * (sizeof(int64_t) + sizeof(float));
+}
+
+int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
+                      const int64_t* excl_idx, const int64_t* excl_off, float* mean, float* var, float* ei, int32_t k, int64_t* top_idx,
+                      float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_batch(b, false);
+    if (rc) return rc;
+    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;   // the support set only
+    if (!phi || !info || !ws || !b->y_s || !b->priors || rows < 0 || k < 0) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN)) return ADKF_E_BADARG;
+    const bool by_mean = (flags & ADKF_PM_SCORE_MEAN) != 0;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if ((ei || (k > 0 && !by_mean)) && !best_f) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (!mean && !var && !ei && k == 0) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    const size_t need = adkf_predict_pool_scratch_bytes(b->T, k);
+    if (scratch_bytes < need) return ADKF_E_WORKSPACE;
+    if (need > 0 && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 7u))) return ADKF_E_BADARG;
+    PmPool pool{};
+    pool.excl_idx = excl_off ? excl_idx : nullptr; pool.excl_off = excl_off;
+    pool.k = k; pool.chunks_max = pm_pool_chunks_max(b->T); pool.score_mean = by_mean ? 1 : 0;
+    pool.cand_idx = static_cast<int64_t*>(scratch);
+    pool.cand_val = reinterpret_cast<float*>(pool.cand_idx + (size_t)b->T * pool.chunks_max * k);
+    const int32_t pm_flags = flags & (ADKF_PM_LATENT | ADKF_PM_MAXIMIZE);
+    if (is_ard(b)) {
+        ArdCtx c;
+        rc = pm_prepare_ard(b, phi, info, ws, ws_bytes, stream, c);
+        if (rc) return rc;
+        SlotRegion rd[4];
+        const PmArd ard = pm_ard_scaling(c, rd);
+        return pm_launch<true, true>(&c.bt, c.w, c.a.mu, &ard, rd, 4, pm_flags, X, nullptr, rows, best_f, mean, var, ei, info, c.st, &pool, top_idx, top_val);
+    }
+    Workspace w;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, st, w);
+    if (rc) return rc;
+    return pm_launch<false, true>(b, w, w.mean, nullptr, nullptr, 0, pm_flags, X, nullptr, rows, best_f, mean, var, ei, info, st, &pool, top_idx, top_val);
 }
 
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

@@ -623,6 +623,77 @@ int adkf_predict_marginal_ard(const adkf_batch_t* b, const float* phi, int32_t f
     return 0;
 }
 
+size_t adkf_predict_pool_scratch_bytes(int32_t, int32_t) { return 0; }
+
+// One pool for every task (include/adkf_gp.h).  The selection ranks the float32 values the call returns (or would return), under
+// the total order "larger score first, equal scores by ascending row".
+int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
+                      const int64_t* excl_idx, const int64_t* excl_off, float* mean, float* var, float* ei, int32_t k, int64_t* top_idx,
+                      float* top_val, int32_t* info, void*, size_t, void*, size_t, void*) {
+    if (!b || b->T <= 0 || b->ns_max <= 0 || b->nq_max < 0 || b->d <= 0 || !b->Z_s) return ADKF_E_BADARG;
+    if (b->kernel != ADKF_KERNEL_RBF && b->kernel != ADKF_KERNEL_MATERN52) return ADKF_E_BADARG;
+    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !info || !b->y_s || !b->priors || rows < 0 || k < 0) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN)) return ADKF_E_BADARG;
+    const bool by_mean = (flags & ADKF_PM_SCORE_MEAN) != 0, ard = (b->flags & ADKF_BATCH_ARD) != 0;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if ((ei || (k > 0 && !by_mean)) && !best_f) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (!mean && !var && !ei && k == 0) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    const int d = b->d, h = ard ? 2 + d : 3;
+    const double raw_one = std::log(std::expm1(1.0));
+    const float ninf = -std::numeric_limits<float>::infinity();
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        const int n = std::min(ns_of(b, t), b->ns_max);
+        const size_t o = (size_t)t * (size_t)rows;
+        info[t] = 0;
+        if (mean) std::fill(mean + o, mean + o + rows, 0.f);
+        if (var) std::fill(var + o, var + o + rows, 0.f);
+        if (ei) std::fill(ei + o, ei + o + rows, 0.f);
+        for (int q = 0; q < k; ++q) { top_idx[(size_t)t * k + q] = -1; top_val[(size_t)t * k + q] = ninf; }
+        if (n <= 0) continue;
+        const float* Zs = b->Z_s + (size_t)t * b->ns_max * d;
+        const float* x = phi + (size_t)t * h;
+        std::vector<double> mu(d, 0.0), l(d, 1.0);
+        Mat Zt((size_t)n * d);   // the support rows the distances are taken to: as they are, or centred and scaled (ARD)
+        if (ard) {
+            for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) mu[c] += Zs[(size_t)i * d + c];
+            for (int c = 0; c < d; ++c) { mu[c] /= n; l[c] = softplus(x[2 + c]); }
+        }
+        for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) Zt[(size_t)i * d + c] = ((double)Zs[(size_t)i * d + c] - mu[c]) / l[c];
+        const double p[3] = {x[0], x[1], ard ? raw_one : (double)x[2]};
+        const float pri[4] = {b->priors[t * 4], b->priors[t * 4 + 1], ard ? 0.f : b->priors[t * 4 + 2], ard ? -1.f : b->priors[t * 4 + 3]};
+        Inner in = inner_stage(sqdist(Zt.data(), n, Zt.data(), n, d), b->y_s + (size_t)t * b->ns_max, n, p, pri, b->kernel, false, false);
+        info[t] = in.info;
+        if (in.info) continue;
+        std::vector<float> score(k > 0 ? (size_t)rows : 0);
+        std::vector<double> zt(d);
+        for (int64_t r = 0; r < rows; ++r) {
+            for (int c = 0; c < d; ++c) zt[c] = ((double)X[(size_t)r * d + c] - mu[c]) / l[c];
+            const Mat D = sqdist(zt.data(), 1, Zt.data(), n, d);
+            float m1, v1, e1 = 0.f;
+            const bool want_e = ei || (k > 0 && !by_mean);
+            pm_row(in, b->kernel, D.data(), b->y_s + (size_t)t * b->ns_max, flags, best_f, t, 0, &m1, &v1, want_e ? &e1 : nullptr);
+            if (mean) mean[o + r] = m1;
+            if (var) var[o + r] = v1;
+            if (ei) ei[o + r] = e1;
+            if (k > 0) score[r] = by_mean ? ((flags & ADKF_PM_MAXIMIZE) ? m1 : -m1) : e1;
+        }
+        if (k <= 0) continue;
+        std::vector<int64_t> cand;
+        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
+        for (int64_t r = 0; r < rows; ++r)
+            if (score[r] == score[r] && !(xb && std::binary_search(xb, xe, r))) cand.push_back(r);
+        const size_t kk = std::min<size_t>(k, cand.size());
+        std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return score[a] > score[c] || (score[a] == score[c] && a < c); });
+        for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)t * k + q] = cand[q]; top_val[(size_t)t * k + q] = score[cand[q]]; }
+    }
+    return 0;
+}
+
 static int outer_common(const adkf_batch_t* b, const float* phi, int flags, bool with_hessian, float* f_out, float* g_phi, float* dZ_s, float* dZ_q,
                         float* v_out, float* H_out, int32_t* info) {
     const int d = b->d;

@@ -37,6 +37,21 @@
 // call (k_pm_ard_il).  k_predict_marginal64<true> scales with k_ard_scale's float32 expression (z - mu) / l before promoting to
 // float64, so a flagged task's rows see the features ARD adkf_predict would give them.
 //
+// Shared pool (adkf_predict_pool, POOL = true): every task scores the SAME rows X [rows, d].  An item is (task, pool tile);
+// the row source is X + r * d for every task and the destination t * rows + r.  Every workgroup counts the tasks of its
+// launch's kind and spreads the grid over them: workgroup w serves the (w % n)-th such task and walks the tiles w / n,
+// w / n + C, ... with C = min(grid / n, chunks_max) chunks per task, so the items of one pool tile for different tasks are
+// neighbours in time (the tile comes from HBM once) and a workgroup serves one task per walk; with more tasks than workgroups
+// it serves several, one after the other.  Nothing depends on that placement but speed.  The arithmetic of an item is the
+// packed call's, bit for bit.
+//
+// Selection (k > 0): the first wave, which holds the tile's 64 scores in the epilogue, keeps the best 64 (score, row) pairs
+// of its walk in registers, one per lane, sorted under the total order "larger score first, equal scores by ascending row"
+// (pm_list_merge: a threshold test against the k-th entry first, a binary search of the task's exclusion list for the rows that
+// pass it, then one shift per accepted row).  At the end of the walk the first k go to the scratch list of (task, chunk) with
+// ordinary stores; k_pool_topk, one wave per task after the three walks, merges the task's C lists under the same order.  The
+// answer is unique, so it does not depend on the grid.  NaN scores are never selected.
+//
 // Deterministic: no atomics; a row's result depends on its task's data and its own features only.
 #pragma once
 #include <type_traits>
@@ -67,9 +82,21 @@ struct PmArgs {
 // the ARD instances: PmArgs::Zs is Zt_s, PmArgs::mean_s the support column means mu of ard.h
 struct PmArd { const float *il, *ell; };   // [T, d] each: 1 / l and l
 struct PmArdArgs { PmArgs p; PmArd r; };
-template <bool ARD> using PmArgsOf = std::conditional_t<ARD, PmArdArgs, PmArgs>;
+// the shared-pool instances (POOL): PmArgs::Zq is the pool X, q_off unused, mean / var / ei [T, rows] and each nullable
+struct PmPool {
+    const int64_t *excl_idx, *excl_off;     // nullable: task t may not select rows excl_idx[excl_off[t] .. excl_off[t + 1]), ascending
+    int64_t* cand_idx; float* cand_val;     // scratch lists [T, chunks_max, k]
+    int k, chunks_max, score_mean;
+    int grid[3];                            // the grids of the three walks (k_pool_topk derives the chunks per task from them)
+};
+struct PmPoolArgs { PmArgs p; PmPool s; };
+struct PmArdPoolArgs { PmArgs p; PmArd r; PmPool s; };
+template <bool ARD, bool POOL = false>
+using PmArgsOf = std::conditional_t<POOL, std::conditional_t<ARD, PmArdPoolArgs, PmPoolArgs>, std::conditional_t<ARD, PmArdArgs, PmArgs>>;
 __device__ __forceinline__ const PmArgs& pm_base(const PmArgs& a) { return a; }
 __device__ __forceinline__ const PmArgs& pm_base(const PmArdArgs& a) { return a.p; }
+__device__ __forceinline__ const PmArgs& pm_base(const PmPoolArgs& a) { return a.p; }
+__device__ __forceinline__ const PmArgs& pm_base(const PmArdPoolArgs& a) { return a.p; }
 
 // il = 1 / l, so that the staging loop of the ARD instances multiplies instead of divides
 __global__ __launch_bounds__(256) void k_pm_ard_il(const float* ell, float* il, int64_t n) {
@@ -162,8 +189,60 @@ __device__ __forceinline__ float pm_ei(float mean, float var_latent, float best,
     return sigma * fmaf(u, cdf, pdf);
 }
 
-template <bool REFINE, bool GLOBAL, bool ARD = false>
-__global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD> args) {
+// ---- shared-pool selection
+constexpr int PM_TOPK_MAX = 64;             // one list entry per lane
+
+// (s, r) comes before the list entry (v, i) in the total order; empty entries (i < 0) come last
+__device__ __forceinline__ bool pm_beats(float s, long long r, float v, long long i) { return i < 0 || s > v || (s == v && r < i); }
+
+__device__ __forceinline__ bool pm_excluded(const PmPool& s, int t, long long r) {
+    if (!s.excl_idx) return false;
+    int64_t lo = s.excl_off[t], hi = s.excl_off[t + 1];
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        const int64_t v = s.excl_idx[mid];
+        if (v == r) return true;
+        if (v < r) lo = mid + 1; else hi = mid;
+    }
+    return false;
+}
+
+// One wave: (lv, li) is the sorted list, entry `lane` in each lane; every lane offers one candidate (s, r) if `valid`.
+// Candidates that do not beat the k-th entry, NaN scores and rows for which excl(r) holds are dropped; the rest are inserted one
+// by one (wave-uniform control flow).
+template <class EX>
+__device__ __forceinline__ void pm_list_merge(float& lv, long long& li, int k, float s, long long r, bool valid, EX excl) {
+    const int lane = threadIdx.x & 63;
+    bool pass = valid && s == s && pm_beats(s, r, __shfl(lv, k - 1), __shfl(li, k - 1));
+    if (pass) pass = !excl(r);
+    unsigned long long mask = __ballot(pass);
+    while (mask) {
+        const int l = __ffsll(mask) - 1;
+        mask &= mask - 1;
+        const float cs = __shfl(s, l);
+        const long long cr = __shfl(r, l);
+        if (!pm_beats(cs, cr, __shfl(lv, k - 1), __shfl(li, k - 1))) continue;   // the threshold has moved since the test above
+        const int pos = __popcll(__ballot(!pm_beats(cs, cr, lv, li)));            // the entries that stay ahead are a prefix
+        const float uv = __shfl_up(lv, 1);
+        const long long ui = __shfl_up(li, 1);
+        if (lane == pos) { lv = cs; li = cr; }
+        else if (lane > pos) { lv = uv; li = ui; }
+    }
+}
+
+// the chunks per task of a walk of `grid` workgroups over n tasks
+__device__ __forceinline__ int pm_pool_chunks(int grid, int n, int chunks_max) {
+    const int c = n > 0 ? grid / n : 0;
+    return c < 1 ? 1 : (c > chunks_max ? chunks_max : c);
+}
+__device__ __forceinline__ int pm_count_kind(const PmArgs& a, int kind) {
+    int n = 0;
+    for (int u = 0; u < a.T; ++u) n += pm_kind_of(a, u) == kind ? 1 : 0;
+    return n;
+}
+
+template <bool REFINE, bool GLOBAL, bool ARD = false, bool POOL = false>
+__global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD, POOL> args) {
     const PmArgs& a = pm_base(args);
     extern __shared__ __attribute__((aligned(16))) float pm_lds[];
     __shared__ float As[PM_TM * LD_MN], Bs[PM_TM * LD_MN];
@@ -184,19 +263,52 @@ __global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD> args) 
     // persistent walk over the tiles of all tasks, in order: (t, first tile of t) is a cursor that only moves forward
     int t = 0;
     int64_t tile0 = 0;
+    // POOL: the walk of this workgroup (see the top of the file); pt < 0 before the first task
+    [[maybe_unused]] int pn = 0, pC = 1, pchunk = 0, pj = 0, pt = -1;
+    [[maybe_unused]] int64_t ptile = 0, pntiles = 0;
+    [[maybe_unused]] float lv = -INFINITY;
+    [[maybe_unused]] long long li = -1;
+    if constexpr (POOL) {
+        pn = pm_count_kind(a, REFINE ? 1 : 0);
+        if (pn == 0) return;
+        pC = pm_pool_chunks(grid, pn, args.s.chunks_max);
+        pchunk = blockIdx.x / pn; pj = blockIdx.x % pn;
+        if (pchunk >= pC) return;
+        pntiles = (a.rows + PM_TM - 1) / PM_TM;
+    }
     for (int64_t g = blockIdx.x;; g += grid) {
-        int64_t lo, hi;
-        for (;;) {
-            if (t >= a.T) return;
-            pm_range(a, t, lo, hi);
-            const int64_t nt = (hi - lo + PM_TM - 1) / PM_TM;
-            const bool mine = pm_kind_of(a, t) == (REFINE ? 1 : 0);
-            if (g < tile0 + nt && mine) break;
-            // next task: the first tile index >= its first tile that this workgroup owns
-            tile0 += nt; ++t;
-            if (g < tile0) g = tile0 + (((int64_t)blockIdx.x - tile0) % grid + grid) % grid;
+        int64_t lo, hi, r0;
+        if constexpr (POOL) {
+            lo = 0; hi = a.rows;
+            while (pt < 0 || ptile >= pntiles) {   // the next task of this walk
+                if (pt >= 0) {
+                    if (args.s.k > 0 && tid < args.s.k) {
+                        const size_t e = ((size_t)pt * args.s.chunks_max + pchunk) * args.s.k + tid;
+                        args.s.cand_idx[e] = li; args.s.cand_val[e] = lv;
+                    }
+                    pj += grid;
+                }
+                if (pj >= pn) return;
+                int seen = 0;
+                for (pt = 0; pt < a.T; ++pt)
+                    if (pm_kind_of(a, pt) == (REFINE ? 1 : 0) && seen++ == pj) break;
+                if (pt >= a.T) return;   // (cannot happen: pj < pn)
+                ptile = pchunk; lv = -INFINITY; li = -1;
+            }
+            t = pt; r0 = ptile * PM_TM; ptile += pC;
+        } else {
+            for (;;) {
+                if (t >= a.T) return;
+                pm_range(a, t, lo, hi);
+                const int64_t nt = (hi - lo + PM_TM - 1) / PM_TM;
+                const bool mine = pm_kind_of(a, t) == (REFINE ? 1 : 0);
+                if (g < tile0 + nt && mine) break;
+                // next task: the first tile index >= its first tile that this workgroup owns
+                tile0 += nt; ++t;
+                if (g < tile0) g = tile0 + (((int64_t)blockIdx.x - tile0) % grid + grid) % grid;
+            }
+            r0 = lo + (g - tile0) * PM_TM;
         }
-        const int64_t r0 = lo + (g - tile0) * PM_TM;
         const int m = (int)(hi - r0 < PM_TM ? hi - r0 : PM_TM);
         const int n = pm_ns(a, t);
         const float* sc = a.scal + (size_t)t * NSCAL;
@@ -342,14 +454,26 @@ __global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD> args) 
                 if ((lane & 15) == 0) { red[wc][0][pm_row(i, r)] = x; red[wc][1][pm_row(i, r)] = y; }
             }
         __syncthreads();
+        [[maybe_unused]] float score = 0.f;
         if (tid < m) {
-            const size_t row = (size_t)(r0 + tid);
+            const size_t row = POOL ? (size_t)t * (size_t)a.rows + (size_t)(r0 + tid) : (size_t)(r0 + tid);
             const float mean = red[0][0][tid] + red[1][0][tid];
             const float vl = os - (red[0][1][tid] + red[1][1][tid]);
-            a.mean[row] = mean;
+            if (!POOL || a.mean) a.mean[row] = mean;
             if (a.var) a.var[row] = a.latent ? vl : vl + noise;
-            if (a.ei) a.ei[row] = pm_ei(mean, vl, a.best_f[t], a.maximize);
+            if constexpr (POOL) {
+                const bool by_mean = args.s.score_mean != 0;
+                float e = 0.f;
+                if (a.ei || (args.s.k > 0 && !by_mean)) e = pm_ei(mean, vl, a.best_f[t], a.maximize);
+                if (a.ei) a.ei[row] = e;
+                score = by_mean ? (a.maximize ? mean : -mean) : e;
+            } else {
+                if (a.ei) a.ei[row] = pm_ei(mean, vl, a.best_f[t], a.maximize);
+            }
         }
+        if constexpr (POOL)
+            if (args.s.k > 0 && wv == 0)
+                pm_list_merge(lv, li, args.s.k, score, (long long)(r0 + tid), tid < m, [&](long long r) { return pm_excluded(args.s, t, r); });
         __syncthreads();   // red / rowsq / the row tiles are rewritten by the next tile
     }
 }
@@ -361,18 +485,28 @@ struct Pm64Args { PmArgs p; const double* w64; size_t w64_stride; };
 struct Pm64ArdArgs { Pm64Args q; PmArd r; };
 __device__ __forceinline__ const Pm64Args& pm_base(const Pm64Args& a) { return a; }
 __device__ __forceinline__ const Pm64Args& pm_base(const Pm64ArdArgs& a) { return a.q; }
+// POOL: grid (chunks, T); workgroup (c, t) walks the pool rows c * 4 + wave, stride chunks * 4, and writes the list of (t, c)
+struct Pm64PoolArgs { Pm64Args q; PmPool s; };
+struct Pm64ArdPoolArgs { Pm64Args q; PmArd r; PmPool s; };
+__device__ __forceinline__ const Pm64Args& pm_base(const Pm64PoolArgs& a) { return a.q; }
+__device__ __forceinline__ const Pm64Args& pm_base(const Pm64ArdPoolArgs& a) { return a.q; }
+template <bool ARD, bool POOL>
+using Pm64ArgsOf = std::conditional_t<POOL, std::conditional_t<ARD, Pm64ArdPoolArgs, Pm64PoolArgs>, std::conditional_t<ARD, Pm64ArdArgs, Pm64Args>>;
 
-template <bool ARD = false>
-__global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(std::conditional_t<ARD, Pm64ArdArgs, Pm64Args> args) {
+template <bool ARD = false, bool POOL = false>
+__global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(Pm64ArgsOf<ARD, POOL> args) {
     const Pm64Args& a64 = pm_base(args);
     const PmArgs& a = a64.p;
     __shared__ double kr[PM64_NT / 64][R64_MAXN];
+    [[maybe_unused]] float lv = -INFINITY;   // POOL: every wave keeps a list of the rows it evaluates; merged at the end
+    [[maybe_unused]] long long li = -1;
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (pm_kind_of(a, t) != 2) return;   // (uniform)
     const int n = pm_ns(a, t), ld = a.ns_ld;
     if (n <= 0 || n > R64_MAXN) return;
     int64_t lo, hi;
-    pm_range(a, t, lo, hi);
+    if constexpr (POOL) { lo = 0; hi = a.rows; }
+    else pm_range(a, t, lo, hi);
     const float* sc = a.scal + (size_t)t * NSCAL;
     const double os = sc[S_OS], noise = sc[S_NOISE], ls = sc[S_LS], il2 = 1.0 / (ls * ls);
     const double* A1 = a64.w64 + (size_t)t * a64.w64_stride;   // float64 A^-1 [ld, ld]
@@ -406,15 +540,67 @@ __global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(std::conditional
             s2 += c * k[j];
         }
         for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+        [[maybe_unused]] float score = 0.f;
         if (lane == 0) {
             const float mean = (float)s1, vl = (float)(os - s2);
-            a.mean[r] = mean;
-            if (a.var) a.var[r] = a.latent ? vl : (float)(os - s2 + noise);
-            if (a.ei) a.ei[r] = pm_ei(mean, vl, a.best_f[t], a.maximize);
+            const size_t row = POOL ? (size_t)t * (size_t)a.rows + (size_t)r : (size_t)r;
+            if (!POOL || a.mean) a.mean[row] = mean;
+            if (a.var) a.var[row] = a.latent ? vl : (float)(os - s2 + noise);
+            if constexpr (POOL) {
+                const bool by_mean = args.s.score_mean != 0;
+                float e = 0.f;
+                if (a.ei || (args.s.k > 0 && !by_mean)) e = pm_ei(mean, vl, a.best_f[t], a.maximize);
+                if (a.ei) a.ei[row] = e;
+                score = by_mean ? (a.maximize ? mean : -mean) : e;
+            } else {
+                if (a.ei) a.ei[row] = pm_ei(mean, vl, a.best_f[t], a.maximize);
+            }
         }
+        if constexpr (POOL)
+            if (args.s.k > 0) pm_list_merge(lv, li, args.s.k, score, (long long)r, lane == 0, [&](long long q) { return pm_excluded(args.s, t, q); });
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
+    if constexpr (POOL) {
+        if (args.s.k <= 0) return;   // (uniform)
+        __shared__ float mv[PM64_NT / 64 - 1][64];
+        __shared__ long long mi[PM64_NT / 64 - 1][64];
+        if (wv > 0) { mv[wv - 1][lane] = lv; mi[wv - 1][lane] = li; }
+        __syncthreads();
+        if (wv == 0) {
+            for (int w = 0; w < PM64_NT / 64 - 1; ++w)
+                pm_list_merge(lv, li, args.s.k, mv[w][lane], mi[w][lane], mi[w][lane] >= 0, [](long long) { return false; });
+            if (lane < args.s.k) {
+                const size_t e = ((size_t)t * args.s.chunks_max + blockIdx.x) * args.s.k + lane;
+                args.s.cand_idx[e] = li; args.s.cand_val[e] = lv;
+            }
+        }
+    }
+}
+
+// ---- the last phase of the selection: one wave per task merges the task's lists and writes top_idx / top_val [T, k]
+// (skipped tasks, and every task when no walk ran: -1 / -inf)
+struct PmTopkArgs { PmArgs p; PmPool s; int64_t* top_idx; float* top_val; int walked; };
+__global__ __launch_bounds__(64) void k_pool_topk(PmTopkArgs args) {
+    const PmArgs& a = args.p;
+    const PmPool& s = args.s;
+    const int t = blockIdx.x, lane = threadIdx.x, k = s.k;
+    const int kind = args.walked ? pm_kind_of(a, t) : -1;
+    int C = 0;
+    if (kind == 2) C = s.grid[2];
+    else if (kind >= 0) C = pm_pool_chunks(s.grid[kind], pm_count_kind(a, kind), s.chunks_max);
+    float lv = -INFINITY;
+    long long li = -1;
+    const size_t base = (size_t)t * s.chunks_max * k;
+    const int total = C * k;
+    for (int e0 = 0; e0 < total; e0 += 64) {
+        const int e = e0 + lane;
+        const bool in = e < total;
+        const long long r = in ? (long long)s.cand_idx[base + e] : -1;
+        const float v = in ? s.cand_val[base + e] : 0.f;
+        pm_list_merge(lv, li, k, v, r, r >= 0, [](long long) { return false; });
+    }
+    if (lane < k) { args.top_idx[(size_t)t * k + lane] = li; args.top_val[(size_t)t * k + lane] = li >= 0 ? lv : -INFINITY; }
 }
 
 }  // namespace adkf

@@ -177,6 +177,33 @@ def meta_test(model, mb: MetaBatch, max_evals: int = 200, gtol: float = 1e-5, ft
     return preds, var, phi, n_evals
 
 
+@torch.no_grad()
+def screen(model, mb: MetaBatch, X_features: torch.Tensor, k: int, maximize: bool = True, max_evals: int = 200):
+    """Virtual screening: every task of ``mb`` is fitted on its support set, then ranks the SAME library ``X_features [rows, d]``
+    (rows in the model's feature space) by posterior mean in one ``gp_ops.predict_pool`` call.  Returns (top_idx [T, k] int64,
+    top_val [T, k], phi*): each task's ``k`` (at most 64) best rows, best first (largest mean with ``maximize``, smallest
+    without; ``top_val`` is +mean / -mean accordingly).  Nothing of size T x rows is allocated."""
+    from . import gp_ops
+
+    cfg = model.config
+    was_training = model.training
+    model.eval()
+    Z_s, _ = meta_features(model, mb)
+    y_s, _ = mb.labels(cfg.use_numeric_labels)
+    priors = torch.empty(mb.num_tasks, 4, dtype=torch.float32, device=Z_s.device)
+    b = gp_ops.GPBatch(Z_s.float().contiguous(), y_s.to(Z_s.device).float().contiguous(), priors, cfg.gp_kernel, n_s=mb.n_s, ard=cfg.use_ard)
+    phi0, _ = gp_ops.init_params_batch(b, cfg.use_numeric_labels, cfg.use_lengthscale_prior)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.DEFER_REFINE
+    phi, _, _, _, info = gp_ops.fit(b, phi0, max_evals)
+    gp_ops.check_info(info, "screening inner fit")
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    out = gp_ops.predict_pool(b, phi, X_features, maximize=maximize, score="mean", want_mean=False, want_var=False, topk=k)
+    gp_ops.check_info(out["info"], "screening prediction")
+    if was_training:
+        model.train()
+    return out["top_idx"], out["top_val"], phi
+
+
 def evaluate_tasks(model, tasks: Sequence[DKTBatch], names: Optional[Sequence[str]] = None, tasks_per_call: int = 64,
                    max_evals: int = 200, streaming: bool = False) -> Dict[str, object]:
     """``evaluate_adkt_model`` for tasks that are already in memory: per-task metric records, ``tasks_per_call`` tasks

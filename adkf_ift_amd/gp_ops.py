@@ -336,6 +336,89 @@ def predict_marginal(b: GPBatch, phi: torch.Tensor, Zq: torch.Tensor, q_off: tor
     return mean, var, ei, info
 
 
+def pack_exclude(exclude, T: int, rows: int, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The exclusion lists of ``predict_pool`` in the library's layout: ``(excl_idx, excl_off)``, both int64, task t's rows in
+    ``excl_idx[excl_off[t]:excl_off[t + 1]]`` sorted ascending, without duplicates or entries outside ``[0, rows)``.
+    ``exclude``: None, a list of T index tensors / lists / None, or an ``(excl_idx, excl_off)`` pair (normalised in the same
+    way).  Pure torch; runs on CPU tensors too."""
+    if exclude is None:
+        exclude = [None] * T
+    elif (isinstance(exclude, tuple) and len(exclude) == 2 and torch.is_tensor(exclude[1]) and exclude[1].numel() == T + 1
+          and torch.is_tensor(exclude[0]) and exclude[0].dim() == 1):
+        idx, off = exclude[0], [int(o) for o in exclude[1].tolist()]
+        exclude = [idx[off[t]:off[t + 1]] for t in range(T)]
+    if len(exclude) != T:
+        raise ValueError(f"exclude must hold one index list per task: T = {T}, got {len(exclude)}")
+    parts = []
+    for e in exclude:
+        e = torch.empty(0, dtype=torch.int64) if e is None else torch.as_tensor(e).to(torch.int64).reshape(-1)
+        if device is not None:
+            e = e.to(device)
+        parts.append(torch.unique(e[(e >= 0) & (e < rows)]))   # (sorted)
+    dev = device if device is not None else (parts[0].device if parts else "cpu")
+    off = torch.zeros(T + 1, dtype=torch.int64, device=dev)
+    if parts:
+        off[1:] = torch.cumsum(torch.tensor([q.numel() for q in parts], dtype=torch.int64, device=dev), 0)
+    idx = torch.cat([q.to(dev) for q in parts]) if parts else torch.empty(0, dtype=torch.int64, device=dev)
+    return idx.contiguous(), off
+
+
+def predict_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, latent: bool = False, best_f: Optional[torch.Tensor] = None,
+                 maximize: bool = False, score: str = "ei", want_mean: bool = True, want_var: bool = True,
+                 want_ei: Optional[bool] = None, topk: int = 0, exclude=None):
+    """Every task of the support-only batch ``b`` scores the SAME pool ``X [rows, d]`` in one ``adkf_predict_pool`` call.
+    Returns ``dict(mean, var, ei, top_idx, top_val, info)``: the per-row outputs asked for as ``[T, rows]`` tensors (None
+    otherwise; ``want_ei`` defaults to "``best_f`` given"), ``top_idx [T, topk]`` (int64) / ``top_val [T, topk]`` - each task's
+    ``topk`` (at most 64) rows of largest score, descending, equal scores by ascending row, -1 / -inf where fewer are eligible -
+    and ``info [T]``.  ``score``: ``"ei"`` (needs ``best_f``) or ``"mean"`` (+mean with ``maximize``, -mean without).
+    ``exclude``: rows a task may not select (``pack_exclude``).  With no per-row output and ``topk > 0`` nothing of size
+    T x rows is allocated or written."""
+    lib = _lib.load()
+    if b.nq != 0:
+        raise ValueError("predict_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    if score not in ("ei", "mean"):
+        raise ValueError(f"score must be 'ei' or 'mean', got {score!r}")
+    topk = int(topk)
+    if topk < 0 or topk > _lib.POOL_TOPK_MAX:
+        raise ValueError(f"topk must be in [0, {_lib.POOL_TOPK_MAX}], got {topk}")
+    phi = b.check_phi(phi)
+    X = _f32(X, "X")
+    if X.dim() != 2 or X.shape[1] != b.d:
+        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    if best_f is not None:
+        best_f = _f32(best_f, "best_f").reshape(-1)
+        if best_f.numel() != b.T:
+            raise ValueError(f"best_f must have T = {b.T} entries")
+    if want_ei is None:
+        want_ei = best_f is not None
+    if (want_ei or (topk > 0 and score == "ei")) and best_f is None:
+        raise ValueError("ei and ranking by ei need best_f [T]")
+    if not (want_mean or want_var or want_ei or topk > 0):
+        raise ValueError("no output asked for")
+    rows = X.shape[0]
+    excl_idx = excl_off = None
+    if exclude is not None and topk > 0:
+        excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
+    for name, t in (("X", X), ("best_f", best_f)):
+        if t is not None and t.device != b.device:
+            raise ValueError(f"{name} lives on {t.device}, the batch on {b.device}")
+    mean = _new(b, b.T, rows) if want_mean else None
+    var = _new(b, b.T, rows) if want_var else None
+    ei = _new(b, b.T, rows) if want_ei else None
+    top_idx = _new(b, b.T, topk, dtype=torch.int64) if topk > 0 else None
+    top_val = _new(b, b.T, topk) if topk > 0 else None
+    info = _new(b, b.T, dtype=torch.int32)
+    sb = int(lib.adkf_predict_pool_scratch_bytes(b.T, topk))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device) if sb else None
+    flags = (_lib.PM_LATENT if latent else 0) | (_lib.PM_MAXIMIZE if maximize else 0) | (_lib.PM_SCORE_MEAN if score == "mean" else 0)
+    ws, nb = b.workspace()
+    cb = b.c_struct()
+    _lib.check(lib.adkf_predict_pool(C.byref(cb), _ptr(phi), flags, _ptr(X), rows, _ptr(best_f), _ptr(excl_idx), _ptr(excl_off),
+                                     _ptr(mean), _ptr(var), _ptr(ei), topk, _ptr(top_idx), _ptr(top_val), _ptr(info), _ptr(ws), nb,
+                                     _ptr(scratch), sb, _stream(b.device)), "adkf_predict_pool")
+    return dict(mean=mean, var=var, ei=ei, top_idx=top_idx, top_val=top_val, info=info)
+
+
 def double_path_tasks(b: GPBatch) -> torch.Tensor:
     """[T] int32: 1 where the last ``ift_hypergrad`` / ``outer_nll_value_grad`` on this batch sent the task through the float64
     path (ill-conditioned tasks, csrc/refine64.h).  Diagnostic."""

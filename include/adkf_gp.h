@@ -199,6 +199,35 @@ int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags
  * Outputs, zeroed rows and info as adkf_predict_marginal; info as ARD adkf_predict reports it. */
 int adkf_predict_marginal_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows, const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream);
 
+/* Shared-pool prediction: every task of the batch scores the SAME rows X [rows, d], and the call can return each task's best k
+ * rows itself, so that nothing of size T x rows has to exist unless the caller asks for it (Bayesian-optimisation replicates
+ * over one candidate pool, virtual screening).
+ *   b      support-only as for adkf_predict_marginal; with ADKF_BATCH_ARD in b->flags the call behaves as
+ *          adkf_predict_marginal_ard (phi [T, 2 + d], ws of adkf_workspace_bytes_ard(T, ns_max, 0, d) bytes), without it as
+ *          adkf_predict_marginal (adkf_workspace_bytes(T, ns_max, 0, d)).  REUSE_DIST / REUSE_INNER mean what they mean there.
+ *          The workspace size depends neither on rows nor on k.
+ *   flags  ADKF_PM_LATENT, ADKF_PM_MAXIMIZE, ADKF_PM_SCORE_MEAN; any other bit is ADKF_E_BADARG.
+ *   mean, var, ei   each nullable, [T, rows] row-major (task t, row r at t * rows + r); the values of the packed call: var
+ *          includes the noise unless ADKF_PM_LATENT, ei (needs best_f [T]) is on the latent variance.  With all three NULL the
+ *          kernels write nothing per row.
+ *   k, top_idx, top_val   k == 0: no selection.  Otherwise ([T, k] each) the score of row r for task t is its ei value, or with
+ *          ADKF_PM_SCORE_MEAN +mean under ADKF_PM_MAXIMIZE and -mean without; top_idx[t, 0..k) are the k eligible rows of largest
+ *          score in descending score, equal scores in ascending row index (a total order: the answer is unique and independent of
+ *          the grid), top_val their scores.  A row is eligible unless it is listed in excl_idx[excl_off[t] .. excl_off[t + 1])
+ *          (nullable; int64, each task's range sorted ascending) or its score is NaN.  With fewer than k eligible rows the tail is
+ *          top_idx = -1, top_val = -inf.
+ *   Tasks with n_s == 0 or info != 0: their [rows] slices are 0 (as the packed call zeroes such rows), their selection -1 / -inf.
+ *   scratch   adkf_predict_pool_scratch_bytes(T, k) bytes, 8-byte aligned: the candidate lists of the selection.  It depends
+ *          on T and k only (at most 3 MB), never on rows; 0 for k == 0.  Nothing for the caller to initialise.
+ * Rejected before anything is launched, ADKF_E_BADARG unless noted: a batch with a query set; rows < 0; rows > 0 without X; ei
+ * without best_f; k > 0 ranking by ei without best_f; k < 0; k > 0 without top_idx or top_val; no output at all (mean, var, ei
+ * NULL and k == 0); excl_idx without excl_off; k > ADKF_POOL_TOPK_MAX (ADKF_E_SIZE); a scratch or a workspace that is too small
+ * (ADKF_E_WORKSPACE). */
+#define ADKF_PM_SCORE_MEAN 4 /* adkf_predict_pool only: rank by the posterior mean instead of ei (no best_f needed) */
+#define ADKF_POOL_TOPK_MAX 64
+size_t adkf_predict_pool_scratch_bytes(int32_t T, int32_t k);
+int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, float* mean, float* var, float* ei, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

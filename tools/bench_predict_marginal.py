@@ -9,7 +9,13 @@ tools/bench_meta_test.py shape through meta_test(streaming=True) and streaming=F
 with a seeded +-30 % spread, evaluated once, then timed with REUSE_INNER - against isotropic streaming at the median lengthscale,
 the two timed alternately in this process (median of --reps single calls each), and ARD adkf_predict(want_var=True) where its
 workspace allows the shape.
-Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large]"""
+--pool: shared-pool prediction (adkf_predict_pool) at T=16 ns=128 d=256, one pool of 262 144 rows, Matern, REUSE_INNER, EI:
+(i) predict_pool writing mean, var and ei, (ii) predict_pool returning the 16 best rows per task and nothing per row, against
+what the packed call offers for the same results: (iii) predict_marginal on the pool replicated T times, (iv) the same followed
+by torch.topk over the [T, rows] view.  The four are timed alternately in this process (median of --reps single calls each) and
+reported with the device memory each needs for the pool, the outputs and the scratch.  A second line times
+run_gp_ei_bo_batched with 16 replicates against 16 sequential run_gp_ei_bo(streaming=True) runs (--skip-bo leaves it out).
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -157,6 +163,76 @@ def shape_ard(T, ns, d, rows_per_task, reps, dev):
     print(json.dumps(rec), flush=True)
 
 
+def shape_pool(T, ns, d, rows, k, reps, dev):
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    b = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern")
+    phi0, _ = gp_ops.init_params_batch(b, True, True)
+    b.flags = gp_ops.REUSE_DIST
+    phi, _, _, _, info = gp_ops.fit(b, phi0, 200)
+    gp_ops.check_info(info)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    X = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):
+        X[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    best = ys.median(1).values.contiguous()
+    Xrep = X.repeat(T, 1)   # what the packed layout needs: every task its own copy of the pool
+    q_off = torch.arange(T + 1, device=dev, dtype=torch.int64) * rows
+    f1 = lambda: gp_ops.predict_pool(b, phi, X, best_f=best)
+    f2 = lambda: gp_ops.predict_pool(b, phi, X, best_f=best, want_mean=False, want_var=False, want_ei=False, topk=k)
+    f3 = lambda: gp_ops.predict_marginal(b, phi, Xrep, q_off, best_f=best)
+    f4 = lambda: torch.topk(gp_ops.predict_marginal(b, phi, Xrep, q_off, best_f=best)[2].view(T, rows), k, dim=1)
+    o1, o2, o3, o4 = f1(), f2(), f3(), f4()
+    torch.cuda.synchronize()
+    same_rows = all(torch.equal(o1[n].view(-1), o3[j]) for j, n in enumerate(("mean", "var", "ei")))
+    same_top = torch.equal(o2["top_val"], o4.values)   # (torch.topk does not promise an order among equal values: compare the values)
+    ts = [[], [], [], []]
+    for _ in range(reps):
+        for q, f in enumerate((f1, f2, f3, f4)):
+            ts[q].append(once(f))
+    m = [float(np.median(x)) for x in ts]
+    lib = _lib.load()
+    pool_b, out_b = 4 * rows * d, 3 * 4 * T * rows
+    rec = {"shape": f"pool T={T} ns={ns} d={d} rows={rows} k={k} matern REUSE_INNER EI", "refined_tasks": int(_refined(b).sum()),
+           "workspace_bytes": int(lib.adkf_workspace_bytes(T, ns, 0, d)),
+           "i_pool_rows_s": m[0], "ii_pool_topk_s": m[1], "iii_packed_replicated_s": m[2], "iv_packed_replicated_topk_s": m[3],
+           "i_over_iii": m[0] / m[2], "ii_over_iv": m[1] / m[3], "task_rows_per_s_i": T * rows / m[0], "task_rows_per_s_ii": T * rows / m[1],
+           "i_bytes": pool_b + out_b, "ii_bytes": pool_b + int(lib.adkf_predict_pool_scratch_bytes(T, k)) + T * k * 12,
+           "iii_bytes": T * pool_b + out_b, "iv_bytes": T * pool_b + out_b + T * k * 12,
+           "pool_equals_packed_bitwise": bool(same_rows), "topk_values_equal": bool(same_top), "all_s": ts}
+    print(json.dumps(rec), flush=True)
+
+
+def bo_shape(R, dev, loops=10):
+    from adkf_ift_amd import bayes_opt as BO
+    g = torch.Generator().manual_seed(3)
+    X = torch.randn(10000, 6, generator=g)
+    y = ((X - 0.3) ** 2).sum(1)
+    order = torch.argsort(y)
+    X, y = X[order].to(dev), y[order].to(dev)
+    kw = dict(num_init_points=6, query_batch_size=2, num_bo_iters=3, kernel_type="matern", device=dev, init_from=5000, noise_init=0.01,
+              noise_prior=True)
+    batched = lambda: BO.run_gp_ei_bo_batched(X, y, rngs=[np.random.default_rng(s) for s in range(R)], **kw)
+    sequential = lambda: [BO.run_gp_ei_bo(X, y, rng=np.random.default_rng(s), streaming=True, **kw) for s in range(R)]
+    out = {"shape": f"GP-EI BO: {R} replicates, pool 10000 x 6, 6 initial points, 3 iterations of 2 queries; wall time of {loops} runs"}
+    BO.run_gp_ei_bo_batched(X, y, rngs=[np.random.default_rng(99)], **kw)   # warm-up of both paths
+    BO.run_gp_ei_bo(X, y, rng=np.random.default_rng(99), streaming=True, **kw)
+    for name, f in (("batched", batched), ("sequential", sequential), ("batched_2", batched), ("sequential_2", sequential)):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(loops):
+            rec = f()
+        torch.cuda.synchronize()
+        out[name + "_walltime_s"] = time.perf_counter() - t0
+        out.setdefault("records", {})[name] = rec
+    out["records_equal"] = out["records"]["batched"] == out["records"]["sequential"]
+    del out["records"]
+    out["speedup"] = min(out["sequential_walltime_s"], out["sequential_2_walltime_s"]) / min(out["batched_walltime_s"], out["batched_2_walltime_s"])
+    print(json.dumps(out), flush=True)
+
+
 def meta_test_shape(dev):
     from adkf_ift_amd import evaluate as E
     from adkf_ift_amd.models import ADKTModel, ADKTModelConfig
@@ -180,8 +256,15 @@ def main():
     ap.add_argument("--skip-meta-test", action="store_true")
     ap.add_argument("--ard", action="store_true", help="ARD batches against isotropic streaming (no meta-test line)")
     ap.add_argument("--skip-large", action="store_true", help="leave out the 1 x 256 x 512 shape with 1M rows")
+    ap.add_argument("--pool", action="store_true", help="shared-pool prediction against the packed call on a replicated pool, and the batched BO loop")
+    ap.add_argument("--skip-bo", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.pool:
+        shape_pool(16, 128, 256, 262144, 16, a.reps, dev)
+        if not a.skip_bo:
+            bo_shape(16, dev)
+        return
     run = shape_ard if a.ard else shape
     run(16, 128, 2048, 4096, a.reps, dev)
     run(16, 128, 2048, 65536, a.reps, dev)
