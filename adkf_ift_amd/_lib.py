@@ -19,6 +19,8 @@ PM_LATENT = 1     # adkf_predict_marginal: var without the observation noise
 PM_MAXIMIZE = 2   # ... ei for maximisation
 PM_SCORE_MEAN = 4  # adkf_predict_pool: rank by the posterior mean instead of ei
 POOL_TOPK_MAX = 64
+TS_SAMPLES_MAX = 64      # adkf_thompson_pool: posterior draws per task
+TS_FEATURES_MAX = 4096   # ... random Fourier features (a multiple of 64, at least 64)
 
 ERRORS = {-1: "bad argument", -2: "unsupported size (see adkf_max_points)", -3: "workspace too small",
           -4: "HIP launch failed"}
@@ -68,6 +70,10 @@ SIGNATURES = {
     "adkf_predict_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adkf_thompson_pool_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "adkf_thompson_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_outer_nll_value_grad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_ift_hypergrad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -4,7 +4,7 @@
 // Same C ABI, HOST pointers: adkf_batch_t, priors, phi layouts, info codes and flags exactly as in the header; `ws` /
 // `ws_bytes` / `stream` are accepted and ignored (adkf_workspace_bytes returns 0 here).  Non-ARD batches of any size; the one
 // exception is adkf_predict_marginal_ard, which centres and scales the features by the per-dimension lengthscales and runs
-// the isotropic code at unit lengthscale (csrc/ard.h).
+// the isotropic code at unit lengthscale (csrc/ard.h).  adkf_thompson_pool refuses ARD batches, as the library does.
 // Plain loops, OpenMP over the tasks of a batch, float64 arithmetic inside and float32 at the boundary - a Cholesky-based
 // restatement of the same staged closed-form algebra the HIP kernels run (stage names as in DESIGN.md section 3 and
 // oracle/closed_form.py): kernel matrices from difference-form squared distances, A = L L^T, A^-1, the analytic 3 x 3 Hessian,
@@ -690,6 +690,87 @@ int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, co
         const size_t kk = std::min<size_t>(k, cand.size());
         std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return score[a] > score[c] || (score[a] == score[c] && a < c); });
         for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)t * k + q] = cand[q]; top_val[(size_t)t * k + q] = score[cand[q]]; }
+    }
+    return 0;
+}
+
+size_t adkf_thompson_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { return 0; }
+
+// Thompson sampling over a shared pool (include/adkf_gp.h): the pathwise posterior draws in float64, rounded to float32 at the
+// boundary; the selection ranks those float32 values under "larger score first, equal scores by ascending row".
+int adkf_thompson_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega,
+                       const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx,
+                       const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void*, size_t, void*, size_t,
+                       void*) {
+    if (int rc = check(b, false)) return rc;   // (refuses ARD batches)
+    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!omega || !phase || !w || !eps || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
+    if (m < 64 || m > ADKF_TS_FEATURES_MAX || (m & 63)) return ADKF_E_SIZE;
+    const int d = b->d, ld = b->ns_max;
+    const float ninf = -std::numeric_limits<float>::infinity();
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        const int n = std::min(ns_of(b, t), ld);
+        info[t] = 0;
+        for (int q = 0; q < S; ++q) { sel_idx[(size_t)t * S + q] = -1; sel_val[(size_t)t * S + q] = ninf; }
+        if (paths && rows > 0) std::fill(paths + (size_t)t * S * rows, paths + (size_t)(t + 1) * S * rows, 0.f);
+        if (n <= 0) continue;
+        const float* Zs = b->Z_s + (size_t)t * ld * d;
+        const float* ys = b->y_s + (size_t)t * ld;
+        const double p[3] = {phi[t * 3], phi[t * 3 + 1], phi[t * 3 + 2]};
+        Inner in = inner_stage(sqdist(Zs, n, Zs, n, d), ys, n, p, b->priors + t * 4, b->kernel, false, false);
+        info[t] = in.info;
+        if (in.info) continue;
+        std::vector<double> mu(d, 0.0);
+        for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) mu[c] += Zs[(size_t)i * d + c];
+        for (int c = 0; c < d; ++c) mu[c] /= n;
+        const double amp = std::sqrt(2.0 * in.s / m), sigma = std::sqrt(in.noise), il2 = 1.0 / (in.l * in.l);
+        std::vector<double> ft(m);
+        auto features = [&](const float* x) {   // phi_j(x), j < m
+            for (int j = 0; j < m; ++j) {
+                double a = 0.0;
+                const float* om = omega + (size_t)j * d;
+                for (int c = 0; c < d; ++c) a += (double)om[c] * ((double)x[c] - mu[c]);
+                ft[j] = amp * std::cos(a / in.l + (double)phase[j]);
+            }
+        };
+        auto prior = [&](int q) { double g = 0.0; const float* wq = w + ((size_t)t * S + q) * m; for (int j = 0; j < m; ++j) g += (double)wq[j] * ft[j]; return g; };
+        // r = y - g(Z_s) - sqrt(noise) eps, v = A^-1 r: V [S, n]
+        Mat R((size_t)S * n), V((size_t)S * n);
+        for (int i = 0; i < n; ++i) {
+            features(Zs + (size_t)i * d);
+            for (int q = 0; q < S; ++q) R[(size_t)q * n + i] = (double)ys[i] - prior(q) - sigma * (double)eps[((size_t)t * S + q) * ld + i];
+        }
+        for (int q = 0; q < S; ++q)
+            for (int i = 0; i < n; ++i) {
+                double v = 0.0;
+                for (int k = 0; k < n; ++k) v += in.Ainv[(size_t)i * n + k] * R[(size_t)q * n + k];
+                V[(size_t)q * n + i] = v;
+            }
+        std::vector<float> bv(S, ninf);
+        std::vector<int64_t> bi(S, -1);
+        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
+        std::vector<double> k(n);
+        for (int64_t r = 0; r < rows; ++r) {
+            const float* x = X + (size_t)r * d;
+            features(x);
+            const Mat D = sqdist(x, 1, Zs, n, d);
+            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); k[j] = in.s * k0; }
+            const bool excluded = xb && std::binary_search(xb, xe, r);
+            for (int q = 0; q < S; ++q) {
+                double f = prior(q);
+                for (int j = 0; j < n; ++j) f += k[j] * V[(size_t)q * n + j];
+                const float ff = (float)f, sc = (flags & ADKF_PM_MAXIMIZE) ? ff : -ff;
+                if (paths) paths[((size_t)t * S + q) * rows + r] = ff;
+                if (sc == sc && !excluded && (bi[q] < 0 || sc > bv[q])) { bv[q] = sc; bi[q] = r; }   // (rows ascend: a tie keeps the lower index)
+            }
+        }
+        for (int q = 0; q < S; ++q) { sel_idx[(size_t)t * S + q] = bi[q]; sel_val[(size_t)t * S + q] = bi[q] >= 0 ? bv[q] : ninf; }
     }
     return 0;
 }

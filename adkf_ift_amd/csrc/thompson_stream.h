@@ -1,0 +1,407 @@
+// Thompson sampling over a shared pool (adkf_thompson_pool): S pathwise posterior draws per task (Matheron's rule on a
+// random-Fourier-feature prior draw), each reduced on the fly to its best eligible pool row.  One pass over the pool, work per
+// (task, 64-row pool tile), a scratch that does not depend on the number of rows.
+//
+// With (noise, s, l) the task's hyper-parameters, mu its support column mean, (omega [m, d], phase [m]) the caller's basis at unit
+// lengthscale, w [T, S, m] and eps [T, S, ns] the caller's standard normal draws, sample q of task t is
+//     phi_j(x) = sqrt(2 s / m) cos(omega_j . (x - mu) / l + phase_j)         g(x) = sum_j w[t, q, j] phi_j(x)
+//     r_i = y_i - g(z_i) - sqrt(noise) eps[t, q, i]                           v = A^-1 r
+//     f(x) = g(x) + sum_i k(x, z_i) v_i
+// Four phases, ordered by launch boundaries (no atomics anywhere; every sum has a fixed order, so the result is reproducible to
+// the bit and a task's numbers do not depend on the grid or on the other tasks of the batch):
+//   k_ts_resid   per (task, support row): the m features of the row (one per thread, the feature row of omega streamed), then
+//                g for the S samples (one wave per sample, butterfly sum) and r into V [T, S, ns];
+//   k_ts_solve   per (task, sample): v = A^-1 r, then ONE refinement step v += A^-1 (r - A v) with A regenerated from D2ss (as
+//                ProbCres does), in place in V.  That step is why this call has no plain / refined distinction (pm_kind_of);
+//   k_ts_stream  per (task, pool tile), a persistent grid placed over tasks and tiles exactly as the POOL instances of
+//                predict_stream.h: per 64-feature chunk P = (X - mu) Omega^T on the FP32 MFMA (pm_mm, the operand staging of the
+//                distance product), sqrt(2 s / m) cos(P / l + phase) on the vector ALU into an LDS panel, F += panel W^T on the
+//                MFMA; then per 64-column support panel the K panel exactly as k_predict_marginal computes it (centred D^2 with the
+//                norms summed while staging, then kappa) and F += K_panel V_panel^T.  Only K v is needed, not K A^-1: no [64, ns] row
+//                tile is kept, so any ns runs through this one instance with 53 KB of static LDS.  The X Omega^T product is
+//                computed per task (NOT shared across tasks): the centred form keeps the argument of the cosine at the size of
+//                (x - mu) / l.  Epilogue: the [64, S] tile goes through LDS, optionally to `paths`, and lane q of the first wave
+//                keeps sample q's best (score, row) of the walk under the total order of pm_beats, with the exclusion test of
+//                pm_excluded; at the end of the walk one pair per (task, chunk, sample) goes to scratch with ordinary stores;
+//   k_ts_merge   one wave per task: lane q reduces the chunks' pairs of sample q under the same order.
+// Tasks flagged for the float64 path (refine64.h: their K v cancels beyond float32) take the <true> instances of the first two
+// kernels - the features and r in float64, v from k_refine64's float64 A^-1 - and k_ts_stream64 (one wave per pool row, modelled
+// on k_predict_marginal64) instead of k_ts_stream.  The cosine there is cosf of the argument reduced to [-pi, pi] in float64.
+#pragma once
+#include <type_traits>
+
+#include "predict_stream.h"
+
+namespace adkf {
+
+constexpr int TS_LDP = PM_TM + 4;      // leading dimension of the two LDS panels of k_ts_stream
+constexpr int TS_M_MAX = 4096;         // ADKF_TS_FEATURES_MAX
+constexpr int TS_S_MAX = 64;           // ADKF_TS_SAMPLES_MAX: one sample per lane
+constexpr int TS_NS_MAX = 4096;        // the largest support set of the library
+
+struct TsArgs {
+    PmArgs p;                           // Zq: the pool X; q_off, best_f, mean / var / ei, the slots unused
+    PmPool s;                           // the exclusion lists; cand_* [T, chunks_max, S]; k = S; grid[0]: k_ts_stream, grid[2]: k_ts_stream64
+    const float *omega, *phase, *w, *eps;   // [m, d], [m], [T, S, m], [T, S, ns_ld]
+    int m, S, vec_om;                   // vec_om: 16-byte loads of the rows of omega are legal
+    float* V;                           // [T, S, ns_ld]: r, then v (float32 tasks)
+    double* V64;                        // the same for flagged tasks (null without a float64 region)
+    const double* w64; size_t w64_stride;
+    float* paths;                       // nullable [T, S, rows]
+    int64_t* sel_idx; float* sel_val;   // [T, S]
+    int walked;                         // rows > 0
+};
+
+// does the float32 (F64 = false) or the float64 (true) instance own task t
+template <bool F64>
+__device__ __forceinline__ bool ts_mine(const PmArgs& a, int t) {
+    const int kind = pm_kind_of(a, t);
+    return F64 ? kind == 2 : (kind == 0 || kind == 1);
+}
+__device__ __forceinline__ int ts_count32(const PmArgs& a) {
+    int n = 0;
+    for (int u = 0; u < a.T; ++u) n += ts_mine<false>(a, u) ? 1 : 0;
+    return n;
+}
+
+__device__ __forceinline__ float ts_cos(float x) { return cosf(x); }
+__device__ __forceinline__ double ts_cos(double x) {   // reduced in float64, evaluated in float32
+    x -= 6.283185307179586 * rint(x * 0.15915494309189535);
+    return (double)cosf((float)x);
+}
+
+// ---- r = y - g(Z_s) - sqrt(noise) eps, per (task, support row): grid (ns_ld, T)
+template <bool F64>
+__global__ __launch_bounds__(256) void k_ts_resid(TsArgs args) {
+    using R = std::conditional_t<F64, double, float>;
+    const PmArgs& a = args.p;
+    __shared__ R cs[TS_M_MAX];
+    const int t = blockIdx.y, i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (!ts_mine<F64>(a, t)) return;   // (uniform)
+    if (i >= pm_ns(a, t)) return;
+    const float* sc = a.scal + (size_t)t * NSCAL;
+    const R il = (R)1 / (R)sc[S_LS], amp = sqrt((R)2 * (R)sc[S_OS] / (R)args.m), sigma = sqrt((R)sc[S_NOISE]);
+    const float* z = a.Zs + ((size_t)t * a.ns_ld + i) * a.d;
+    const float* mu = a.mean_s + (size_t)t * a.d;
+    for (int j = tid; j < args.m; j += 256) {
+        const float* om = args.omega + (size_t)j * a.d;
+        R s = 0;
+        for (int c = 0; c < a.d; ++c) {
+            if constexpr (F64) s = fma((double)om[c], (double)z[c] - (double)mu[c], s);
+            else s = fmaf(om[c], z[c] - mu[c], s);
+        }
+        cs[j] = amp * ts_cos(s * il + (R)args.phase[j]);
+    }
+    __syncthreads();
+    for (int q = wv; q < args.S; q += 4) {
+        const float* wq = args.w + ((size_t)t * args.S + q) * args.m;
+        R g = 0;
+        for (int j = lane; j < args.m; j += 64) g += (R)wq[j] * cs[j];
+        for (int o = 32; o > 0; o >>= 1) g += __shfl_xor(g, o);
+        if (lane == 0) {
+            const size_t e = ((size_t)t * args.S + q) * a.ns_ld + i;
+            const R r = (R)a.y_s[(size_t)t * a.ns_ld + i] - g - sigma * (R)args.eps[e];
+            if constexpr (F64) args.V64[e] = r; else args.V[e] = r;
+        }
+    }
+}
+
+// ---- v = A^-1 r (+ one refinement step in float32), per (task, sample), in place: grid (S, T)
+template <bool F64>
+__global__ __launch_bounds__(256) void k_ts_solve(TsArgs args) {
+    const PmArgs& a = args.p;
+    const int t = blockIdx.y, q = blockIdx.x, tid = threadIdx.x;
+    if (!ts_mine<F64>(a, t)) return;   // (uniform)
+    const int n = pm_ns(a, t), ld = a.ns_ld;
+    const size_t base = ((size_t)t * args.S + q) * ld;
+    if constexpr (F64) {
+        __shared__ double rs[R64_MAXN];
+        if (n > R64_MAXN) return;
+        const double* A1 = args.w64 + (size_t)t * args.w64_stride;   // float64 A^-1 [ld, ld] (symmetric)
+        for (int i = tid; i < n; i += 256) rs[i] = args.V64[base + i];
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) {
+            double s = 0.0;
+            for (int k = 0; k < n; ++k) s += A1[(size_t)k * ld + i] * rs[k];
+            args.V64[base + i] = s;
+        }
+    } else {
+        __shared__ float rs[TS_NS_MAX], vs[TS_NS_MAX], es[TS_NS_MAX];
+        const float* sc = a.scal + (size_t)t * NSCAL;
+        const float os = sc[S_OS], noise = sc[S_NOISE], il2 = 1.f / (sc[S_LS] * sc[S_LS]);
+        const float* Ai = a.Ainv + (size_t)t * ld * ld;    // symmetric: column i is row i
+        const float* Dss = a.D2ss + (size_t)t * ld * ld;
+        for (int i = tid; i < n; i += 256) rs[i] = args.V[base + i];
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) {
+            float s = 0.f;
+            for (int k = 0; k < n; ++k) s = fmaf(Ai[(size_t)k * ld + i], rs[k], s);
+            vs[i] = s;
+        }
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) {
+            float s = 0.f;
+            for (int k = 0; k < n; ++k) s = fmaf(os * kappa0(a.kind, Dss[(size_t)k * ld + i] * il2) + (k == i ? noise : 0.f), vs[k], s);
+            es[i] = rs[i] - s;
+        }
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) {
+            float s = 0.f;
+            for (int k = 0; k < n; ++k) s = fmaf(Ai[(size_t)k * ld + i], es[k], s);
+            args.V[base + i] = vs[i] + s;
+        }
+    }
+}
+
+// F (this wave's 32 x 32 quarter of the [64 rows, 64 samples] tile) += A B^T for two LDS panels [64, 64] (leading dimension
+// TS_LDP, K-contiguous).  Column blocks at or beyond S hold zeros and are skipped (wave-uniform).
+__device__ __forceinline__ void ts_mm(f32x4 (&F)[2][2], const float* A, const float* B, int S) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wr = wv >> 1, wc = wv & 1, fi = lane & 15, fk = lane >> 4;
+#pragma unroll
+    for (int s = 0; s < PM_TM / 4; ++s) {
+        float af[2], bf[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) af[i] = A[(wr * 32 + i * 16 + fi) * TS_LDP + 4 * s + fk];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) bf[j] = B[(wc * 32 + j * 16 + fi) * TS_LDP + 4 * s + fk];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            if (wc * 32 + j * 16 < S) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) F[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], bf[j], F[i][j], 0, 0, 0);
+            }
+    }
+}
+
+// B panel: Bp[s][k] = src[(t S + s) ld + k0 + k] for s < S and k0 + k < k_end, else 0
+__device__ __forceinline__ void ts_stage(float* Bp, const float* src, size_t ld, int S, int k0, int k_end) {
+    for (int e = threadIdx.x; e < PM_TM * PM_TM; e += PM_NT) {
+        const int s = e >> 6, k = e & 63;
+        Bp[s * TS_LDP + k] = (s < S && k0 + k < k_end) ? src[(size_t)s * ld + k0 + k] : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgs args) {
+    const PmArgs& a = args.p;
+    __shared__ float As[PM_TM * LD_MN], Bs[PM_TM * LD_MN];
+    __shared__ float Pp[PM_TM * TS_LDP], Bp[PM_TM * TS_LDP];   // the A panel (features or K) and the B panel (W or V)
+    __shared__ float rowsq[2][PM_TM];
+    const int tid = threadIdx.x, wv = tid >> 6;
+    const int grid = gridDim.x, S = args.S;
+    const int64_t d = a.d;
+    // the walk of this workgroup: as the POOL instances of k_predict_marginal
+    const int pn = ts_count32(a);
+    if (pn == 0) return;
+    const int pC = pm_pool_chunks(grid, pn, args.s.chunks_max), pchunk = blockIdx.x / pn;
+    int pj = blockIdx.x % pn, pt = -1;
+    if (pchunk >= pC) return;
+    const int64_t pntiles = (a.rows + PM_TM - 1) / PM_TM;
+    int64_t ptile = 0;
+    float lv = -INFINITY;   // first wave, lane q: the best (score, row) of sample q in this walk
+    long long li = -1;
+    for (;;) {
+        while (pt < 0 || ptile >= pntiles) {   // the next task of this walk
+            if (pt >= 0) {
+                if (tid < S) {
+                    const size_t e = ((size_t)pt * args.s.chunks_max + pchunk) * S + tid;
+                    args.s.cand_idx[e] = li; args.s.cand_val[e] = lv;
+                }
+                pj += grid;
+            }
+            if (pj >= pn) return;
+            int seen = 0;
+            for (pt = 0; pt < a.T; ++pt)
+                if (ts_mine<false>(a, pt) && seen++ == pj) break;
+            if (pt >= a.T) return;   // (cannot happen: pj < pn)
+            ptile = pchunk; lv = -INFINITY; li = -1;
+        }
+        const int t = pt;
+        const int64_t r0 = ptile * PM_TM;
+        ptile += pC;
+        const int mr = (int)(a.rows - r0 < PM_TM ? a.rows - r0 : PM_TM);
+        const int n = pm_ns(a, t);
+        const float* sc = a.scal + (size_t)t * NSCAL;
+        const float os = sc[S_OS], il = 1.f / sc[S_LS], il2 = 1.f / (sc[S_LS] * sc[S_LS]), amp = sqrtf(2.f * os / (float)args.m);
+        const int kind = a.kind;
+        const float* Zs = a.Zs + (size_t)t * a.ns_ld * d;
+        const float* mu = a.mean_s + (size_t)t * d;
+        const int np = (n + PM_TM - 1) / PM_TM;
+        f32x4 acc[2][2], F[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) F[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        auto fx = [&](int i, int k, float (&v)[4]) {   // the centred pool rows of the tile
+            if (i >= mr) { v[0] = v[1] = v[2] = v[3] = 0.f; return; }
+            float z[4], c[4];
+            pm_ld4(a.Zq + (size_t)(r0 + i) * d, k, a.d, a.vec, z); pm_ld4(mu, k, a.d, a.vec, c);
+#pragma unroll
+            for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
+        };
+        float dummy[2];
+        // ---- feature part: F = sqrt(2 s / m) cos((X - mu) Omega^T / l + phase) W^T
+        for (int j0 = 0; j0 < args.m; j0 += PM_TM) {
+            pm_mm<false>(acc, a.d, As, Bs, fx,
+                [&](int j, int k, float (&v)[4]) { pm_ld4(args.omega + (size_t)(j0 + j) * d, k, a.d, args.vec_om, v); }, dummy, dummy);
+            ts_stage(Bp, args.w + (size_t)t * S * args.m, args.m, S, j0, args.m);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int jj = pm_col(j);
+                const float ph = args.phase[j0 + jj];
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ii = pm_row(i, r);
+                        Pp[ii * TS_LDP + jj] = ii < mr ? amp * ts_cos(fmaf(acc[i][j][r], il, ph)) : 0.f;
+                    }
+            }
+            __syncthreads();
+            ts_mm(F, Pp, Bp, S);
+            __syncthreads();
+        }
+        // ---- update part: F += K V^T, the K panel as k_predict_marginal computes it
+        for (int p = 0; p < np; ++p) {
+            const int j0 = p * PM_TM;
+            float sqa[2] = {0.f, 0.f}, sqb[2] = {0.f, 0.f};
+            pm_mm<true>(acc, a.d, As, Bs, fx,
+                [&](int j, int k, float (&v)[4]) {
+                    if (j0 + j >= n) { v[0] = v[1] = v[2] = v[3] = 0.f; return; }
+                    float z[4], c[4];
+                    pm_ld4(Zs + (size_t)(j0 + j) * d, k, a.d, a.vec, z); pm_ld4(mu, k, a.d, a.vec, c);
+#pragma unroll
+                    for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
+                }, sqa, sqb);
+#pragma unroll
+            for (int ps = 0; ps < 2; ++ps) {   // the eight threads that staged a row are eight adjacent lanes
+                float x = sqa[ps], y = sqb[ps];
+                x += dpp_f<DPP_XOR1>(x); x += dpp_f<DPP_XOR2>(x); x += dpp_f<DPP_HALF_MIRROR>(x);
+                y += dpp_f<DPP_XOR1>(y); y += dpp_f<DPP_XOR2>(y); y += dpp_f<DPP_HALF_MIRROR>(y);
+                if ((tid & 7) == 0) { rowsq[0][(tid >> 3) + ps * 32] = x; rowsq[1][(tid >> 3) + ps * 32] = y; }
+            }
+            ts_stage(Bp, args.V + (size_t)t * S * a.ns_ld, a.ns_ld, S, j0, n);
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ii = pm_row(i, r), jj = pm_col(j);
+                        const float d2 = fmaxf(rowsq[0][ii] + rowsq[1][jj] - 2.f * acc[i][j][r], 0.f);
+                        Pp[ii * TS_LDP + jj] = (ii < mr && j0 + jj < n) ? os * kappa0(kind, d2 * il2) : 0.f;
+                    }
+            __syncthreads();
+            ts_mm(F, Pp, Bp, S);
+            __syncthreads();
+        }
+        // ---- epilogue: the tile as [sample][row] through LDS
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Pp[pm_col(j) * TS_LDP + pm_row(i, r)] = F[i][j][r];
+        __syncthreads();
+        if (args.paths)
+            for (int e = tid; e < S * PM_TM; e += PM_NT) {
+                const int q = e >> 6, r = e & 63;
+                if (r < mr) args.paths[((size_t)t * S + q) * (size_t)a.rows + (size_t)(r0 + r)] = Pp[q * TS_LDP + r];
+            }
+        if (wv == 0 && tid < S)
+            for (int r = 0; r < mr; ++r) {
+                const float f = Pp[tid * TS_LDP + r], s = a.maximize ? f : -f;
+                const long long row = r0 + r;
+                if (s == s && pm_beats(s, row, lv, li) && !pm_excluded(args.s, t, row)) { lv = s; li = row; }
+            }
+        __syncthreads();   // the panels are rewritten by the next tile
+    }
+}
+
+// ---- flagged tasks: one wave per pool row in float64, grid (chunks, T); workgroup (c, t) walks the rows c * 4 + wave, stride
+// chunks * 4; lane q carries sample q
+__global__ __launch_bounds__(PM64_NT) void k_ts_stream64(TsArgs args) {
+    const PmArgs& a = args.p;
+    __shared__ double kr[PM64_NT / 64][R64_MAXN];
+    __shared__ float mv[PM64_NT / 64 - 1][64];
+    __shared__ long long mi[PM64_NT / 64 - 1][64];
+    const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, S = args.S, m = args.m;
+    if (!ts_mine<true>(a, t)) return;   // (uniform)
+    const int n = pm_ns(a, t), ld = a.ns_ld;
+    if (n <= 0 || n > R64_MAXN) return;
+    const float* sc = a.scal + (size_t)t * NSCAL;
+    const double os = sc[S_OS], ls = sc[S_LS], il = 1.0 / ls, il2 = il * il, amp = sqrt(2.0 * os / (double)m);
+    const float* Zs = a.Zs + (size_t)t * ld * a.d;
+    const float* mu = a.mean_s + (size_t)t * a.d;
+    const int ql = lane < S ? lane : S - 1;   // (lanes beyond S compute sample S - 1 again and store nothing)
+    const float* wq = args.w + ((size_t)t * S + ql) * m;
+    const double* vq = args.V64 + ((size_t)t * S + ql) * ld;
+    double* k = kr[wv];
+    float lv = -INFINITY;
+    long long li = -1;
+    for (int64_t r = (int64_t)blockIdx.x * (PM64_NT / 64) + wv; r < a.rows; r += (int64_t)gridDim.x * (PM64_NT / 64)) {
+        const float* zq = a.Zq + (size_t)r * a.d;
+        for (int j = lane; j < n; j += 64) {
+            const float* zs = Zs + (size_t)j * a.d;
+            double s = 0.0;
+            for (int c = 0; c < a.d; ++c) { const double e = (double)zq[c] - (double)zs[c]; s += e * e; }
+            const double u = s * il2;
+            double kv;
+            if (a.kind == ADKF_KERNEL_RBF) kv = exp(-0.5 * u);
+            else { const double rr = sqrt(u); kv = (1.0 + 2.23606797749979 * rr + (5.0 / 3.0) * u) * exp(-2.23606797749979 * rr); }
+            k[j] = os * kv;
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        double f = 0.0;
+        for (int j0 = 0; j0 < m; j0 += 64) {   // (m is a multiple of 64) one feature per lane, then every lane adds its sample's 64 terms
+            const float* om = args.omega + (size_t)(j0 + lane) * a.d;
+            double s = 0.0;
+            for (int c = 0; c < a.d; ++c) s = fma((double)om[c], (double)zq[c] - (double)mu[c], s);
+            const double cv = amp * ts_cos(s * il + (double)args.phase[j0 + lane]);
+            for (int jj = 0; jj < 64; ++jj) f = fma((double)wq[j0 + jj], __shfl(cv, jj), f);
+        }
+        double u = 0.0;
+        for (int j = 0; j < n; ++j) u = fma(k[j], vq[j], u);
+        f += u;
+        if (lane < S) {
+            const float ff = (float)f, s = a.maximize ? ff : -ff;
+            if (args.paths) args.paths[((size_t)t * S + lane) * (size_t)a.rows + (size_t)r] = ff;
+            if (s == s && pm_beats(s, (long long)r, lv, li) && !pm_excluded(args.s, t, (long long)r)) { lv = s; li = r; }
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    }
+    if (wv > 0) { mv[wv - 1][lane] = lv; mi[wv - 1][lane] = li; }
+    __syncthreads();
+    if (wv == 0 && lane < S) {
+        for (int w = 0; w < PM64_NT / 64 - 1; ++w)
+            if (mi[w][lane] >= 0 && pm_beats(mv[w][lane], mi[w][lane], lv, li)) { lv = mv[w][lane]; li = mi[w][lane]; }
+        const size_t e = ((size_t)t * args.s.chunks_max + blockIdx.x) * S + lane;
+        args.s.cand_idx[e] = li; args.s.cand_val[e] = lv;
+    }
+}
+
+// ---- one wave per task: lane q reduces the pairs of sample q over the task's chunks (skipped tasks, and every task when no
+// walk ran: -1 / -inf)
+__global__ __launch_bounds__(64) void k_ts_merge(TsArgs args) {
+    const PmArgs& a = args.p;
+    const int t = blockIdx.x, lane = threadIdx.x, S = args.S;
+    const int kind = args.walked ? pm_kind_of(a, t) : -1;
+    int C = 0;
+    if (kind == 2) C = args.s.grid[2];
+    else if (kind >= 0) C = pm_pool_chunks(args.s.grid[0], ts_count32(a), args.s.chunks_max);
+    if (lane >= S) return;
+    float lv = -INFINITY;
+    long long li = -1;
+    for (int c = 0; c < C; ++c) {
+        const size_t e = ((size_t)t * args.s.chunks_max + c) * S + lane;
+        const long long r = args.s.cand_idx[e];
+        const float v = args.s.cand_val[e];
+        if (r >= 0 && pm_beats(v, r, lv, li)) { lv = v; li = r; }
+    }
+    args.sel_idx[(size_t)t * S + lane] = li;
+    args.sel_val[(size_t)t * S + lane] = li >= 0 ? lv : -INFINITY;
+}
+
+}  // namespace adkf

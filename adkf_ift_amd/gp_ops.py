@@ -419,6 +419,92 @@ def predict_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, latent: bool
     return dict(mean=mean, var=var, ei=ei, top_idx=top_idx, top_val=top_val, info=info)
 
 
+def rff_basis(kernel, d: int, m: int, generator: Optional[torch.Generator] = None, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A random-Fourier basis ``(omega [m, d], phase [m])`` of ``kernel`` AT UNIT LENGTHSCALE, as ``thompson_pool`` takes it:
+    ``(1/m) sum_j 2 cos(omega_j.x + phase_j) cos(omega_j.y + phase_j)`` estimates ``kappa(|x - y|)``.  RBF: the rows of ``omega``
+    are N(0, I); Matern-5/2: multivariate Student-t with 5 degrees of freedom, ``z / sqrt(g / 5)`` with ``g ~ chi^2_5`` per row;
+    ``phase`` is uniform on [0, 2 pi).  Drawn in float64 on the generator's device (the CPU without one), returned as float32 on
+    ``device``.  Pure torch; runs without a GPU."""
+    import math
+
+    kind = kernel_id(kernel)
+    d, m = int(d), int(m)
+    if d < 1 or m < 1:
+        raise ValueError(f"rff_basis needs d >= 1 and m >= 1, got d = {d}, m = {m}")
+    gdev = generator.device if generator is not None else torch.device("cpu")
+    omega = torch.randn(m, d, dtype=torch.float64, generator=generator, device=gdev)
+    if kind == KERNEL_MATERN52:
+        chi2 = (torch.randn(m, 5, dtype=torch.float64, generator=generator, device=gdev) ** 2).sum(1, keepdim=True)
+        omega = omega / torch.sqrt(chi2 / 5.0)
+    phase = torch.rand(m, dtype=torch.float64, generator=generator, device=gdev) * (2.0 * math.pi)
+    omega, phase = omega.float(), phase.float().clamp_(max=6.2831850)   # (float32 rounding must not reach 2 pi)
+    if device is not None:
+        omega, phase = omega.to(device), phase.to(device)
+    return omega.contiguous(), phase.contiguous()
+
+
+def thompson_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: torch.Tensor, phase: torch.Tensor, n_samples: int,
+                  generator: Optional[torch.Generator] = None, w: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
+                  maximize: bool = False, exclude=None, want_paths: bool = False):
+    """Thompson sampling over the shared pool ``X [rows, d]`` in one ``adkf_thompson_pool`` call: every task of the support-only
+    batch ``b`` draws ``n_samples`` (at most 64) pathwise posterior functions on the basis ``(omega [m, d], phase [m])``
+    (``rff_basis``; m a multiple of 64, at most 4096), and each function picks its best eligible row.  Returns
+    ``dict(sel_idx [T, S] int64, sel_val [T, S], paths [T, S, rows] or None, info [T], w [T, S, m], eps [T, S, ns])``:
+    ``sel_val`` is the score of the pick, +f with ``maximize`` and -f without; -1 / -inf where no row is eligible.  ``w`` / ``eps``
+    are the standard normal draws: given, or drawn here from ``generator`` (on its device) and returned.  ``exclude``: rows a task
+    may not select (``pack_exclude``).  ARD batches are not supported."""
+    lib = _lib.load()
+    if b.nq != 0:
+        raise ValueError("thompson_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    if b.ard:
+        raise ValueError("thompson_pool does not support ARD batches")
+    S = int(n_samples)
+    if S < 1 or S > _lib.TS_SAMPLES_MAX:
+        raise ValueError(f"n_samples must be in [1, {_lib.TS_SAMPLES_MAX}], got {S}")
+    phi = b.check_phi(phi)
+    X = _f32(X, "X")
+    if X.dim() != 2 or X.shape[1] != b.d:
+        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    omega, phase = _f32(omega, "omega"), _f32(phase, "phase")
+    if omega.dim() != 2 or omega.shape[1] != b.d:
+        raise ValueError(f"omega must be [m, d] = [m, {b.d}], got {tuple(omega.shape)}")
+    m = omega.shape[0]
+    if m < 64 or m > _lib.TS_FEATURES_MAX or m % 64:
+        raise ValueError(f"the number of features must be a multiple of 64 in [64, {_lib.TS_FEATURES_MAX}], got {m}")
+    if tuple(phase.shape) != (m,):
+        raise ValueError(f"phase must be [m] = [{m}], got {tuple(phase.shape)}")
+
+    def draw(t, shape, name):
+        if t is None:
+            gdev = generator.device if generator is not None else b.device
+            return torch.randn(*shape, dtype=torch.float32, generator=generator, device=gdev).to(b.device).contiguous()
+        t = _f32(t, name)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {list(shape)}, got {tuple(t.shape)}")
+        return t
+
+    w = draw(w, (b.T, S, m), "w")
+    eps = draw(eps, (b.T, S, b.ns), "eps")
+    rows = X.shape[0]
+    excl_idx = excl_off = None
+    if exclude is not None:
+        excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
+    for name, t in (("X", X), ("omega", omega), ("phase", phase), ("w", w), ("eps", eps)):
+        if t.device != b.device:
+            raise ValueError(f"{name} lives on {t.device}, the batch on {b.device}")
+    paths = _new(b, b.T, S, rows) if want_paths else None
+    sel_idx, sel_val = _new(b, b.T, S, dtype=torch.int64), _new(b, b.T, S)
+    info = _new(b, b.T, dtype=torch.int32)
+    sb = int(lib.adkf_thompson_pool_scratch_bytes(b.T, b.ns, S, m))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device)
+    ws, nb = b.workspace()
+    cb = b.c_struct()
+    _lib.check(lib.adkf_thompson_pool(C.byref(cb), _ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, _ptr(X), rows, _ptr(omega), _ptr(phase),
+                                      m, _ptr(w), _ptr(eps), S, _ptr(excl_idx), _ptr(excl_off), _ptr(paths), _ptr(sel_idx), _ptr(sel_val),
+                                      _ptr(info), _ptr(ws), nb, _ptr(scratch), sb, _stream(b.device)), "adkf_thompson_pool")
+    return dict(sel_idx=sel_idx, sel_val=sel_val, paths=paths, info=info, w=w, eps=eps)
+
+
 def double_path_tasks(b: GPBatch) -> torch.Tensor:
     """[T] int32: 1 where the last ``ift_hypergrad`` / ``outer_nll_value_grad`` on this batch sent the task through the float64
     path (ill-conditioned tasks, csrc/refine64.h).  Diagnostic."""

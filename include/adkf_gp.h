@@ -228,6 +228,47 @@ int adkf_predict_marginal_ard(const adkf_batch_t* b, const float* phi, int32_t f
 size_t adkf_predict_pool_scratch_bytes(int32_t T, int32_t k);
 int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, float* mean, float* var, float* ei, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Thompson sampling over a shared pool from pathwise posterior draws (csrc/thompson_stream.h): every task of the batch draws S
+ * functions from its posterior (Matheron's rule on a random-Fourier-feature prior draw; Wilson et al. 2020), and each function
+ * picks its own best row of the SAME pool X [rows, d].  The S picks of a task are a diverse batch by construction, no best_f is
+ * involved and no tail probability is evaluated.  One pass over the pool; nothing of size rows is kept unless `paths` is given.
+ * No reference-side counterpart: the reference has analytic EI only.
+ *   The quantity.  With (noise, s, l) from phi[t] under the library's transforms, mu the support column mean of task t, k the
+ *          batch's kernel and A = K_ss + noise I, sample q < S of task t is
+ *              phi_j(x) = sqrt(2 s / m) cos(omega_j . (x - mu) / l + phase_j)    (j < m),    g(x) = sum_j w[t, q, j] phi_j(x),
+ *              r_i = y_i - g(z_i) - sqrt(noise) eps[t, q, i]    (i < n_s[t]),    v = A^-1 r,
+ *              f(x) = g(x) + sum_i k(x, z_i) v_i,
+ *          and score(x) = +f(x) with ADKF_PM_MAXIMIZE, -f(x) without.  Given the arrays below f is a deterministic function; its
+ *          mean over standard normal w, eps is exactly the posterior mean K A^-1 y, whatever m is.
+ *   The caller supplies all randomness: omega [m, d] and phase [m], a random-Fourier basis of the kernel AT UNIT LENGTHSCALE shared
+ *          by all tasks (RBF: rows N(0, I); Matern-5/2: multivariate Student-t with 5 degrees of freedom; phase uniform on
+ *          [0, 2 pi)); w [T, S, m] and eps [T, S, ns_max] standard normal (entries at i >= n_s[t] are ignored).
+ *   b      support-only as for adkf_predict_pool, workspace of adkf_workspace_bytes(T, ns_max, 0, d) bytes; REUSE_DIST / REUSE_INNER
+ *          mean what they mean there (the inner quantities at phi, or the fit's, plus the float64 A^-1 of flagged tasks).  ARD
+ *          batches are refused (ADKF_E_BADARG): the follow-up, as streaming prediction did isotropic first.
+ *   flags  ADKF_PM_MAXIMIZE only.
+ *   sel_idx, sel_val   [T, S]: sel_idx[t, q] is the eligible pool row of largest score of sample q, equal scores going to the
+ *          lowest row index (the total order of adkf_predict_pool: the answer is unique and independent of the grid), sel_val its
+ *          score.  A row is eligible unless it is listed in excl_idx[excl_off[t] .. excl_off[t + 1]) (nullable; as
+ *          adkf_predict_pool) or its score is NaN.  With no eligible row: -1 / -inf.
+ *   paths  nullable, [T, S, rows] with element (t, q, r) at (t S + q) rows + r: the values f (not the scores), for tests and
+ *          diagnostics.  With paths == NULL the call writes T S pairs and nothing per row.
+ *   Tasks with n_s == 0 or info != 0: -1 / -inf in every sample, zeros in paths.
+ *   scratch   adkf_thompson_pool_scratch_bytes(T, ns_max, S, m) bytes, 8-byte aligned: v [T, S, ns_max] (and its float64 twin for
+ *          flagged tasks up to 1024 points) and the per-chunk candidate pairs.  A function of (T, ns_max, S, m) only, never of
+ *          rows.  Nothing for the caller to initialise.
+ * Asynchronous on `stream`, no allocation, no synchronisation, capturable.  No atomics: the result is reproducible to the bit, and
+ * a task's paths and selection depend on that task's data, its w / eps slices, the basis and the pool only - not on the other
+ * tasks of the batch.
+ * Rejected before anything is launched, ADKF_E_BADARG unless noted: a batch with a query set; an ARD batch; any flag bit other
+ * than ADKF_PM_MAXIMIZE; rows < 0; rows > 0 without X; a missing omega, phase, w, eps, sel_idx, sel_val, info or ws; excl_idx
+ * without excl_off; S < 1 or S > ADKF_TS_SAMPLES_MAX (ADKF_E_SIZE); m < 64, m > ADKF_TS_FEATURES_MAX or m not a multiple of 64
+ * (ADKF_E_SIZE); a workspace or a scratch that is too small (ADKF_E_WORKSPACE); a scratch that is not 8-byte aligned. */
+#define ADKF_TS_SAMPLES_MAX 64
+#define ADKF_TS_FEATURES_MAX 4096
+size_t adkf_thompson_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t S, int32_t m);
+int adkf_thompson_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega, const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx, const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

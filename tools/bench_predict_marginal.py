@@ -15,7 +15,12 @@ what the packed call offers for the same results: (iii) predict_marginal on the 
 by torch.topk over the [T, rows] view.  The four are timed alternately in this process (median of --reps single calls each) and
 reported with the device memory each needs for the pool, the outputs and the scratch.  A second line times
 run_gp_ei_bo_batched with 16 replicates against 16 sequential run_gp_ei_bo(streaming=True) runs (--skip-bo leaves it out).
-Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo]"""
+--thompson: Thompson sampling over the same pool (adkf_thompson_pool, S = 16 samples, m = 1024 features, paths = NULL) timed
+alternately with variant (ii) above in this process (median of --reps single calls each; use --reps 9).  S conditioned picks cost S
+passes of (ii) with the library as it stands, so the line carries thompson_s < S * ii_pool_topk_s as "beats_S_passes", the matrix
+FLOP the call executes per (task, row) - 2 d m (X Omega^T, computed per task) + 2 m S + 2 d ns + 2 ns S - and its fraction of the
+FP32-matrix bound.  --out FILE also writes the line to FILE.
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson] [--out FILE]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -41,11 +46,7 @@ def timed(fn, reps):
 def _refined(b):
     """[T] bool: tasks that take the refined-C step (more than 128 points, or S_CONDA above 3: problems.h ProbCres's gate); the
     scalars sit in the support-only workspace after W_ss (carve() order of adkf_gp.hip)."""
-    ws, _ = b.workspace()
-    al = lambda nfloat: (nfloat * 4 + 255) // 256 * 256
-    off = al(b.T * b.d) + 4 * al(b.T * b.ns * b.ns) + al(b.T * 16 * b.ns)
-    sc = ws[off:off + b.T * 64 * 4].view(torch.float32).view(b.T, 64).cpu()
-    return (sc[:, 47] > 3.0) | (b.ns > 128)
+    return (_scal(b)[:, 47] > 3.0) | (b.ns > 128)
 
 
 def flops_marginal(T, ns, d, rows, n_refined_rows):
@@ -205,6 +206,62 @@ def shape_pool(T, ns, d, rows, k, reps, dev):
     print(json.dumps(rec), flush=True)
 
 
+def shape_thompson(T, ns, d, rows, S, m, reps, dev, out_path=None):
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    b = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern")
+    phi0, _ = gp_ops.init_params_batch(b, True, True)
+    b.flags = gp_ops.REUSE_DIST
+    phi, _, _, _, info = gp_ops.fit(b, phi0, 200)
+    gp_ops.check_info(info)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    X = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):
+        X[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    best = ys.median(1).values.contiguous()
+    gc = torch.Generator().manual_seed(1)
+    omega, phase = gp_ops.rff_basis("matern", d, m, generator=gc, device=dev)
+    w, eps = torch.randn(T, S, m, generator=gc).to(dev), torch.randn(T, S, ns, generator=gc).to(dev)
+    f_ts = lambda: gp_ops.thompson_pool(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w, eps=eps)
+    f_ii = lambda: gp_ops.predict_pool(b, phi, X, best_f=best, want_mean=False, want_var=False, want_ei=False, topk=16)
+    o1, o2 = f_ts(), f_ts()
+    f_ii()
+    torch.cuda.synchronize()
+    gp_ops.check_info(o1["info"])
+    ts = [[], []]
+    for _ in range(reps):
+        ts[0].append(once(f_ts))
+        ts[1].append(once(f_ii))
+    t_ts, t_ii = float(np.median(ts[0])), float(np.median(ts[1]))
+    lib = _lib.load()
+    fl = T * rows * (2.0 * d * m + 2.0 * m * S + 2.0 * d * ns + 2.0 * ns * S)
+    fl_ii = T * rows * (2.0 * d * ns + 2.0 * ns * ns)
+    rec = {"shape": f"thompson T={T} ns={ns} d={d} rows={rows} S={S} m={m} matern REUSE_INNER paths=NULL", "design": "X Omega^T per task (not shared)",
+           "float64_tasks": int((_scal(b)[:, 45] > 30.0).sum()), "workspace_bytes": int(lib.adkf_workspace_bytes(T, ns, 0, d)),
+           "scratch_bytes": int(lib.adkf_thompson_pool_scratch_bytes(T, ns, S, m)),
+           "thompson_s": t_ts, "ii_pool_topk_s": t_ii, "thompson_over_ii": t_ts / t_ii, "S_times_ii_s": S * t_ii, "beats_S_passes": bool(t_ts < S * t_ii),
+           "matrix_flop_over_ii": fl / fl_ii, "thompson_TFLOP_per_s": fl / t_ts / 1e12, "thompson_frac_fp32_mfma_bound": fl / t_ts / 157.3e12,
+           "cosines_per_s": T * rows * float(m) / t_ts, "distinct_picks_per_task_min": int(min(len(set(r)) for r in o1["sel_idx"].cpu().tolist())),
+           "repeat_is_bit_equal": bool(torch.equal(o1["sel_idx"], o2["sel_idx"]) and torch.equal(o1["sel_val"], o2["sel_val"])), "all_s": ts}
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    return rec
+
+
+def _scal(b):
+    """The per-task scalars [T, 64] of a support-only workspace (carve() order of adkf_gp.hip; slot 45 is the pivot ratio that flags
+    a task for the float64 path above 30)."""
+    ws, _ = b.workspace()
+    al = lambda nfloat: (nfloat * 4 + 255) // 256 * 256
+    off = al(b.T * b.d) + 4 * al(b.T * b.ns * b.ns) + al(b.T * 16 * b.ns)
+    return ws[off:off + b.T * 64 * 4].view(torch.float32).view(b.T, 64).cpu()
+
+
 def bo_shape(R, dev, loops=10):
     from adkf_ift_amd import bayes_opt as BO
     g = torch.Generator().manual_seed(3)
@@ -258,8 +315,13 @@ def main():
     ap.add_argument("--skip-large", action="store_true", help="leave out the 1 x 256 x 512 shape with 1M rows")
     ap.add_argument("--pool", action="store_true", help="shared-pool prediction against the packed call on a replicated pool, and the batched BO loop")
     ap.add_argument("--skip-bo", action="store_true")
+    ap.add_argument("--thompson", action="store_true", help="adkf_thompson_pool against variant (ii) of --pool, timed alternately")
+    ap.add_argument("--out", default=None, help="--thompson: also write the JSON line to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.thompson:
+        rec = shape_thompson(16, 128, 256, 262144, 16, 1024, a.reps, dev, a.out)
+        sys.exit(0 if rec["beats_S_passes"] else 1)
     if a.pool:
         shape_pool(16, 128, 256, 262144, 16, a.reps, dev)
         if not a.skip_bo:
