@@ -877,30 +877,113 @@ int ard_ift(const adkf_batch_t* b, const float* phi, int flags, bool with_hessia
     return 0;
 }
 
-// The streaming launches of adkf_predict_marginal(_ard), once the inner quantities of the support-only batch b are in w.
-// ARD: b is the scaled batch (Z_s = Zt_s), mean_s the support column means mu, ard the query scaling, also_read the ARD buffers
-// the kernels read (kept out of the row-tile slots).
-// POOL (adkf_predict_pool): Zq is the shared pool, mean / var / ei are [T, rows] and nullable, *pool carries the selection
-// (its grid[] is filled here) and top_idx / top_val receive it.
+inline bool is_ard(const adkf_batch_t* b) { return (b->flags & ADKF_BATCH_ARD) != 0; }
+
 constexpr int PM_POOL_LISTS = 4096;   // cap of the candidate lists of a call (the scratch size must not depend on the device)
 inline int pm_pool_chunks_max(int T) { return std::max(1, PM_POOL_LISTS / T); }
+// the workgroups per task of the float64 kernels: four rows per workgroup and pass
+inline int pm64_grid(int64_t rows) { return (int)std::min<int64_t>(64, (rows + PM64_WAVES - 1) / PM64_WAVES); }
 
-template <bool ARD, bool POOL = false>
-int pm_launch(const adkf_batch_t* b, const Workspace& w, const float* mean_s, const PmArd* ard, const SlotRegion* also_read, int n_also,
-              int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows, const float* best_f, float* mean, float* var, float* ei,
-              int32_t* info, hipStream_t st, PmPool* pool = nullptr, int64_t* top_idx = nullptr, float* top_val = nullptr) {
-    const int T = b->T, ns = b->ns_max;
+// What the streaming kernels of adkf_predict_marginal(_ard), adkf_predict_pool and adkf_thompson_pool run on, once pm_prepare has
+// put the inner quantities of the support-only batch into the workspace.
+struct PmCtx {
+    adkf_batch_t b;             // the batch the kernels see; ARD: the scaled batch (Z_s = Zt_s)
+    Workspace w;
+    const float* mean_s;        // the support column means
+    bool ard;
+    PmArd r;                    // ARD: the query scaling
+    SlotRegion also_read[4];    // ARD: the buffers of the ARD region the kernels read (kept out of the row-tile slots)
+    int n_also;
+    hipStream_t st;
+};
+
+// The inner quantities of b into its workspace (or the fit's, with REUSE_INNER) and the float64 A^-1 and alpha of flagged tasks.  ARD:
+// PmCtx::r names the query scaling, whose 1 / l pm_launch writes into ArdWs::c (not read by prediction otherwise).
+int pm_prepare(const adkf_batch_t* b, const float* phi, int32_t* info, void* ws, size_t ws_bytes, void* stream, PmCtx& c) {
+    c.st = static_cast<hipStream_t>(stream);
+    c.ard = is_ard(b);
+    c.r = PmArd{};
+    c.n_also = 0;
+    int rc;
+    if (c.ard) {
+        ArdCtx ac;
+        rc = ard_setup(b, ws, ws_bytes, c.st, ac);   // (checks the workspace size before it launches anything)
+        if (rc) return rc;
+        if (b->flags & ADKF_BATCH_REUSE_INNER) {   // the fit's state: mu, Zt_s, D2ss, A^-1, alpha, the scalars (ard_fit ends with an evaluation at phi*)
+            k_ard_params<<<dim3(ceil_div(ac.d, 256), ac.T), 256, 0, c.st>>>(ac.v, phi);
+            hipMemsetAsync(info, 0, sizeof(int32_t) * (size_t)ac.T, c.st);
+        } else {
+            rc = ard_inner(ac, phi, info);
+            if (rc) return rc;
+        }
+        const size_t td = (size_t)ac.T * ac.d;
+        c.b = ac.bt; c.w = ac.w; c.mean_s = ac.a.mu;
+        c.r = PmArd{ac.a.c, ac.a.ell};
+        c.also_read[0] = {ac.a.mu, td}; c.also_read[1] = {ac.a.ell, td}; c.also_read[2] = {ac.a.c, td}; c.also_read[3] = {ac.a.Zt_s, td * ac.ns};
+        c.n_also = 4;
+    } else {
+        c.w = carve_for(b, ws);
+        if (ws_bytes < c.w.bytes) return ADKF_E_WORKSPACE;
+        rc = stage_dist(b, c.w, false, c.st);
+        if (rc) return rc;
+        if (b->flags & ADKF_BATCH_REUSE_INNER) {
+            hipMemsetAsync(info, 0, sizeof(int32_t) * (size_t)b->T, c.st);
+        } else {
+            InnerArgs ia = inner_args(b, c.w, const_cast<float*>(phi), info);
+            rc = launch_inner(ia, c.w, c.st);
+            if (rc) return rc;
+        }
+        c.b = *b; c.mean_s = c.w.mean;
+    }
+    // flagged tasks: float64 A^-1 and alpha (a no-op re-evaluation after a fit that already ran it; needed after DEFER_REFINE, and
+    // ard_fit does not run it)
+    launch_refine(make_tv(&c.b, c.w, false), &c.b, c.w, false, 0, nullptr, info, c.st);
+    LAUNCH_OK();
+    return 0;
+}
+
+// The kernel arguments that do not depend on the call's outputs; Zq [rows, d]: the packed query rows or the shared pool.
+PmArgs pm_args(const PmCtx& c, int32_t flags, const float* Zq, int64_t rows, const int32_t* info) {
+    const adkf_batch_t& b = c.b;
     PmArgs pa{};
-    pa.Zq = Zq; pa.Zs = b->Z_s; pa.mean_s = mean_s; pa.q_off = q_off; pa.rows = rows;
-    pa.n_s = b->n_s; pa.ns_ld = ns; pa.d = b->d; pa.kind = b->kernel; pa.T = T;
-    pa.Ainv = w.Ainv; pa.D2ss = w.D2ss; pa.y_s = b->y_s; pa.scal = w.scal; pa.best_f = best_f;
-    pa.mean = mean; pa.var = var; pa.ei = ei;
+    pa.Zq = Zq; pa.Zs = b.Z_s; pa.mean_s = c.mean_s; pa.rows = rows;
+    pa.n_s = b.n_s; pa.ns_ld = b.ns_max; pa.d = b.d; pa.kind = b.kernel; pa.T = b.T;
+    pa.Ainv = c.w.Ainv; pa.D2ss = c.w.D2ss; pa.y_s = b.y_s; pa.scal = c.w.scal;
     pa.info = info;
-    pa.refine_thresh = refine32_threshold(); pa.r64_thresh = w.w64 ? r64_threshold() : INFINITY;
+    pa.refine_thresh = refine32_threshold(); pa.r64_thresh = c.w.w64 ? r64_threshold() : INFINITY;
     pa.latent = (flags & ADKF_PM_LATENT) ? 1 : 0; pa.maximize = (flags & ADKF_PM_MAXIMIZE) ? 1 : 0;
-    pa.vec = ((b->d & 3) == 0 && aligned16(Zq) && aligned16(b->Z_s)) ? 1 : 0;
-    const int ns_pad = ceil_div(ns, PM_TM) * PM_TM;
-    pa.buf_ld = ns_pad + 4;
+    pa.vec = ((b.d & 3) == 0 && aligned16(Zq) && aligned16(b.Z_s)) ? 1 : 0;
+    pa.buf_ld = ceil_div(b.ns_max, PM_TM) * PM_TM + 4;
+    pa.w64 = c.w.w64; pa.w64_stride = c.w.w64_stride;
+    return pa;
+}
+
+// The rows and outputs of a prediction call.  POOL (adkf_predict_pool): Zq is the shared pool, q_off unused, mean / var / ei are
+// [T, rows] and nullable, *pool carries the selection (its grid[] is filled by pm_launch).
+struct PmCall {
+    int32_t flags;
+    const float* Zq; const int64_t* q_off; int64_t rows;
+    const float* best_f;
+    float *mean, *var, *ei;
+    int32_t* info;
+    PmPool* pool;
+};
+
+// The streaming launches of a prepared call.
+template <bool ARD, bool POOL = false>
+int pm_launch(const PmCtx& c, const PmCall& io) {
+    const Workspace& w = c.w;
+    hipStream_t st = c.st;
+    PmPool* pool = io.pool;
+    const int T = c.b.T, ns = c.b.ns_max;
+    const int64_t rows = io.rows;
+    if constexpr (ARD) {   // the query scaling: il = 1 / l, into ArdWs::c
+        const size_t td = (size_t)T * c.b.d;
+        k_pm_ard_il<<<(unsigned)((td + 255) / 256), 256, 0, st>>>(c.r.ell, const_cast<float*>(c.r.il), (int64_t)td);
+    }
+    PmArgs pa = pm_args(c, io.flags, io.Zq, rows, io.info);
+    pa.q_off = io.q_off; pa.best_f = io.best_f; pa.mean = io.mean; pa.var = io.var; pa.ei = io.ei;
+    const int ns_pad = pa.buf_ld - 4;
     constexpr int static_lds = (2 * PM_TM * LD_MN + 2 * PM_TM + 4 * PM_TM) * (int)sizeof(float);
     constexpr int dyn_max = PM_LDS_BYTES - static_lds;
     static const bool optin = [] {
@@ -917,114 +1000,80 @@ int pm_launch(const adkf_batch_t* b, const Workspace& w, const float* mean_s, co
     auto set_slots = [&](bool refine) {
         pa.slot_floats = tile_floats(refine);
         SlotRegion r[2];
-        pm_slot_regions(w, T, ns, r, also_read, n_also);
+        pm_slot_regions(w, T, ns, r, c.also_read, c.n_also);
         for (int q = 0; q < 2; ++q) { pa.slots[q] = r[q].base; pa.slot_count[q] = (int)std::min<size_t>(r[q].floats / pa.slot_floats, 1 << 20); }
         return (int64_t)pa.slot_count[0] + pa.slot_count[1];
     };
     auto args = [&] {
-        if constexpr (ARD && POOL) return PmArdPoolArgs{pa, *ard, *pool};
-        else if constexpr (POOL) return PmPoolArgs{pa, *pool};
-        else if constexpr (ARD) return PmArdArgs{pa, *ard};
-        else return pa;
+        PmArgsOf<ARD, POOL> k{};
+        k.p = pa;
+        if constexpr (ARD) k.r = c.r;
+        if constexpr (POOL) k.s = *pool;
+        return k;
     };
     // every output row starts at 0: rows outside every task's range and those of skipped tasks (n_s == 0, info != 0) stay so
     const size_t out_n = POOL ? (size_t)rows * T : (size_t)rows;
-    if (mean && out_n) hipMemsetAsync(mean, 0, sizeof(float) * out_n, st);
-    if (var && out_n) hipMemsetAsync(var, 0, sizeof(float) * out_n, st);
-    if (ei && out_n) hipMemsetAsync(ei, 0, sizeof(float) * out_n, st);
+    if (io.mean && out_n) hipMemsetAsync(io.mean, 0, sizeof(float) * out_n, st);
+    if (io.var && out_n) hipMemsetAsync(io.var, 0, sizeof(float) * out_n, st);
+    if (io.ei && out_n) hipMemsetAsync(io.ei, 0, sizeof(float) * out_n, st);
     if constexpr (POOL) {   // every list starts empty: one that no workgroup writes holds nothing
         if (pool->k > 0) hipMemsetAsync(pool->cand_idx, 0xff, sizeof(int64_t) * (size_t)T * pool->chunks_max * pool->k, st);
         pool->grid[0] = pool->grid[1] = pool->grid[2] = 0;
+        pool->walked = rows > 0 ? 1 : 0;
     }
-    auto launch = [&](auto kern, bool refine) {
-        const size_t dyn = tile_floats(refine) * sizeof(float);
+    auto launch = [&](auto refine_c) {
+        constexpr bool REFINE = decltype(refine_c)::value;
+        const size_t dyn = tile_floats(REFINE) * sizeof(float);
         if (optin && dyn <= (size_t)dyn_max) {
             int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern.lds, PM_NT, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_predict_marginal<REFINE, false, ARD, POOL>, PM_NT, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
             const int grid = (int)std::min<int64_t>(tiles, (int64_t)num_cus() * per_cu);
-            if constexpr (POOL) pool->grid[refine ? 1 : 0] = grid;
-            kern.lds<<<grid, PM_NT, dyn, st>>>(args());
+            if constexpr (POOL) pool->grid[REFINE ? 1 : 0] = grid;
+            k_predict_marginal<REFINE, false, ARD, POOL><<<grid, PM_NT, dyn, st>>>(args());
         } else {
-            const int64_t slots = set_slots(refine);
+            const int64_t slots = set_slots(REFINE);
             if (slots < 1) return ADKF_E_WORKSPACE;
             const int grid = (int)std::min<int64_t>(tiles, std::min<int64_t>(slots, (int64_t)num_cus() * 8));
-            if constexpr (POOL) pool->grid[refine ? 1 : 0] = grid;
-            kern.global<<<grid, PM_NT, 0, st>>>(args());
+            if constexpr (POOL) pool->grid[REFINE ? 1 : 0] = grid;
+            k_predict_marginal<REFINE, true, ARD, POOL><<<grid, PM_NT, 0, st>>>(args());
         }
         return 0;
     };
-    struct Plain { decltype(&k_predict_marginal<false, false, ARD, POOL>) lds = &k_predict_marginal<false, false, ARD, POOL>, global = &k_predict_marginal<false, true, ARD, POOL>; };
-    struct Refined { decltype(&k_predict_marginal<true, false, ARD, POOL>) lds = &k_predict_marginal<true, false, ARD, POOL>, global = &k_predict_marginal<true, true, ARD, POOL>; };
     int rc;
     if (rows > 0) {
-        if ((rc = launch(Plain{}, false))) return rc;
-        if ((rc = launch(Refined{}, true))) return rc;
+        if ((rc = launch(std::false_type{}))) return rc;
+        if ((rc = launch(std::true_type{}))) return rc;
     }
     if (w.w64 && rows > 0) {
-        Pm64Args p64{pa, w.w64, w.w64_stride};
-        int gx = (int)std::min<int64_t>(64, (rows + PM64_NT / 64 - 1) / (PM64_NT / 64));
+        int gx = pm64_grid(rows);
         if constexpr (POOL) {
             gx = std::min(gx, pool->chunks_max);
             pool->grid[2] = gx;
-            if constexpr (ARD) k_predict_marginal64<true, true><<<dim3(gx, T), PM64_NT, 0, st>>>(Pm64ArdPoolArgs{p64, *ard, *pool});
-            else k_predict_marginal64<false, true><<<dim3(gx, T), PM64_NT, 0, st>>>(Pm64PoolArgs{p64, *pool});
-        } else {
-            if constexpr (ARD) k_predict_marginal64<true><<<dim3(gx, T), PM64_NT, 0, st>>>(Pm64ArdArgs{p64, *ard});
-            else k_predict_marginal64<false><<<dim3(gx, T), PM64_NT, 0, st>>>(p64);
         }
+        k_predict_marginal64<ARD, POOL><<<dim3(gx, T), PM64_NT, 0, st>>>(args());
     }
     if constexpr (POOL)
-        if (pool->k > 0) k_pool_topk<<<T, 64, 0, st>>>(PmTopkArgs{pa, *pool, top_idx, top_val, rows > 0 ? 1 : 0});
+        if (pool->k > 0) k_pool_topk<<<T, 64, 0, st>>>(PmArgsOf<false, true>{pa, {}, *pool});
     LAUNCH_OK();
     return 0;
 }
 
-inline bool is_ard(const adkf_batch_t* b) { return (b->flags & ADKF_BATCH_ARD) != 0; }
-
-// What adkf_predict_marginal and adkf_predict_pool do before the streaming launches: the inner quantities of the support-only
-// batch b into its workspace (or the fit's, with REUSE_INNER), and the float64 A^-1 and alpha of flagged tasks.
-int pm_prepare(const adkf_batch_t* b, const float* phi, int32_t* info, void* ws, size_t ws_bytes, hipStream_t st, Workspace& w) {
-    w = carve_for(b, ws);
-    if (ws_bytes < w.bytes) return ADKF_E_WORKSPACE;
-    int rc = stage_dist(b, w, false, st);
+// adkf_predict_marginal and adkf_predict_marginal_ard: the same call on a batch that is (ard) or is not an ARD batch
+int predict_marginal(bool ard, const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
+                     const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
+    int rc = check_batch(b, false);
     if (rc) return rc;
-    if (b->flags & ADKF_BATCH_REUSE_INNER) {
-        hipMemsetAsync(info, 0, sizeof(int32_t) * (size_t)b->T, st);
-    } else {
-        InnerArgs ia = inner_args(b, w, const_cast<float*>(phi), info);
-        rc = launch_inner(ia, w, st);
-        if (rc) return rc;
-    }
-    // flagged tasks: float64 A^-1 and alpha (a no-op re-evaluation after a fit that already ran it; needed after DEFER_REFINE)
-    launch_refine(make_tv(b, w, false), b, w, false, 0, nullptr, info, st);
-    LAUNCH_OK();
-    return 0;
-}
-
-// The same for ARD batches (adkf_predict_marginal_ard, adkf_predict_pool): c.bt is the scaled batch the streaming kernels run on.
-int pm_prepare_ard(const adkf_batch_t* b, const float* phi, int32_t* info, void* ws, size_t ws_bytes, void* stream, ArdCtx& c) {
-    int rc = ard_setup(b, ws, ws_bytes, static_cast<hipStream_t>(stream), c);   // (checks the workspace size before it launches anything)
+    if (b->nq_max != 0 || b->Z_q || b->y_q || is_ard(b) != ard) return ADKF_E_BADARG;   // the support set only
+    if (!phi || !q_off || !info || !ws || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
+    if (ei && !best_f) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
-    if (b->flags & ADKF_BATCH_REUSE_INNER) {   // the fit's state: mu, Zt_s, D2ss, A^-1, alpha, the scalars (ard_fit ends with an evaluation at phi*)
-        k_ard_params<<<dim3(ceil_div(c.d, 256), c.T), 256, 0, c.st>>>(c.v, phi);
-        hipMemsetAsync(info, 0, sizeof(int32_t) * (size_t)c.T, c.st);
-    } else {
-        rc = ard_inner(c, phi, info);
-        if (rc) return rc;
-    }
-    // flagged tasks: float64 A^-1 and alpha of the scaled batch (ard_fit does not run it)
-    launch_refine(make_tv(&c.bt, c.w, false), &c.bt, c.w, false, 0, nullptr, info, c.st);
-    LAUNCH_OK();
-    return 0;
-}
-
-// ... and the query scaling of the ARD instances: 1 / l into ArdWs::c (not read by prediction otherwise); rd: the ARD buffers the
-// kernels read
-PmArd pm_ard_scaling(const ArdCtx& c, SlotRegion (&rd)[4]) {
-    const size_t td = (size_t)c.T * c.d;
-    k_pm_ard_il<<<(unsigned)((td + 255) / 256), 256, 0, c.st>>>(c.a.ell, c.a.c, (int64_t)td);
-    rd[0] = {c.a.mu, td}; rd[1] = {c.a.ell, td}; rd[2] = {c.a.c, td}; rd[3] = {c.a.Zt_s, td * c.ns};
-    return PmArd{c.a.c, c.a.ell};
+    if (rows == 0) return 0;
+    const PmCall io{flags, Zq, q_off, rows, best_f, mean, var, ei, info, nullptr};
+    return ard ? pm_launch<true>(c, io) : pm_launch<false>(c, io);
 }
 
 }  // namespace
@@ -1206,37 +1255,12 @@ int adkf_predict(const adkf_batch_t* b, const float* phi, float* mean, float* va
 
 int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
                           const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
-    int rc = check_batch(b, false);
-    if (rc) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q || is_ard(b)) return ADKF_E_BADARG;   // the support set only; ARD: adkf_predict_marginal_ard
-    if (!phi || !q_off || !info || !ws || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
-    if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
-    if (ei && !best_f) return ADKF_E_BADARG;
-    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
-    Workspace w;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = pm_prepare(b, phi, info, ws, ws_bytes, st, w);
-    if (rc) return rc;
-    if (rows == 0) return 0;
-    return pm_launch<false>(b, w, w.mean, nullptr, nullptr, 0, flags, Zq, q_off, rows, best_f, mean, var, ei, info, st);
+    return predict_marginal(false, b, phi, flags, Zq, q_off, rows, best_f, mean, var, ei, info, ws, ws_bytes, stream);
 }
 
 int adkf_predict_marginal_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
                               const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
-    int rc = check_batch(b, false);
-    if (rc) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q || !is_ard(b)) return ADKF_E_BADARG;   // ARD, the support set only
-    if (!phi || !q_off || !info || !ws || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
-    if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
-    if (ei && !best_f) return ADKF_E_BADARG;
-    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
-    ArdCtx c;
-    rc = pm_prepare_ard(b, phi, info, ws, ws_bytes, stream, c);
-    if (rc) return rc;
-    if (rows == 0) return 0;
-    SlotRegion rd[4];
-    const PmArd ard = pm_ard_scaling(c, rd);
-    return pm_launch<true>(&c.bt, c.w, c.a.mu, &ard, rd, 4, flags, Zq, q_off, rows, best_f, mean, var, ei, info, c.st);
+    return predict_marginal(true, b, phi, flags, Zq, q_off, rows, best_f, mean, var, ei, info, ws, ws_bytes, stream);
 }
 
 size_t adkf_predict_pool_scratch_bytes(int32_t T, int32_t k) {
@@ -1267,20 +1291,12 @@ int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, co
     pool.k = k; pool.chunks_max = pm_pool_chunks_max(b->T); pool.score_mean = by_mean ? 1 : 0;
     pool.cand_idx = static_cast<int64_t*>(scratch);
     pool.cand_val = reinterpret_cast<float*>(pool.cand_idx + (size_t)b->T * pool.chunks_max * k);
-    const int32_t pm_flags = flags & (ADKF_PM_LATENT | ADKF_PM_MAXIMIZE);
-    if (is_ard(b)) {
-        ArdCtx c;
-        rc = pm_prepare_ard(b, phi, info, ws, ws_bytes, stream, c);
-        if (rc) return rc;
-        SlotRegion rd[4];
-        const PmArd ard = pm_ard_scaling(c, rd);
-        return pm_launch<true, true>(&c.bt, c.w, c.a.mu, &ard, rd, 4, pm_flags, X, nullptr, rows, best_f, mean, var, ei, info, c.st, &pool, top_idx, top_val);
-    }
-    Workspace w;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = pm_prepare(b, phi, info, ws, ws_bytes, st, w);
+    pool.top_idx = top_idx; pool.top_val = top_val;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
-    return pm_launch<false, true>(b, w, w.mean, nullptr, nullptr, 0, pm_flags, X, nullptr, rows, best_f, mean, var, ei, info, st, &pool, top_idx, top_val);
+    const PmCall io{flags & (ADKF_PM_LATENT | ADKF_PM_MAXIMIZE), X, nullptr, rows, best_f, mean, var, ei, info, &pool};
+    return c.ard ? pm_launch<true, true>(c, io) : pm_launch<false, true>(c, io);
 }
 
 // adkf_thompson_pool: the scratch is V [T, S, ns] (float32), the same in float64 for flagged tasks where the workspace of this
@@ -1323,30 +1339,24 @@ int adkf_thompson_pool(const adkf_batch_t* b, const float* phi, int32_t flags, c
     const TsScratch l = ts_scratch(b->T, b->ns_max, S);
     if (scratch_bytes < l.bytes) return ADKF_E_WORKSPACE;
     if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 7u)) return ADKF_E_BADARG;
-    Workspace wk;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = pm_prepare(b, phi, info, ws, ws_bytes, st, wk);
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
+    hipStream_t st = c.st;
     const int T = b->T, ns = b->ns_max;
     char* sb = static_cast<char*>(scratch);
     TsArgs ta{};
-    PmArgs& pa = ta.p;
-    pa.Zq = X; pa.Zs = b->Z_s; pa.mean_s = wk.mean; pa.rows = rows;
-    pa.n_s = b->n_s; pa.ns_ld = ns; pa.d = b->d; pa.kind = b->kernel; pa.T = T;
-    pa.Ainv = wk.Ainv; pa.D2ss = wk.D2ss; pa.y_s = b->y_s; pa.scal = wk.scal; pa.info = info;
-    pa.refine_thresh = refine32_threshold(); pa.r64_thresh = wk.w64 ? r64_threshold() : INFINITY;
-    pa.maximize = (flags & ADKF_PM_MAXIMIZE) ? 1 : 0;
-    pa.vec = ((b->d & 3) == 0 && aligned16(X) && aligned16(b->Z_s)) ? 1 : 0;
+    ta.p = pm_args(c, flags, X, rows, info);
     ta.s.excl_idx = excl_off ? excl_idx : nullptr; ta.s.excl_off = excl_off;
     ta.s.k = S; ta.s.chunks_max = pm_pool_chunks_max(T);
     ta.s.cand_idx = reinterpret_cast<int64_t*>(sb + l.cand_idx); ta.s.cand_val = reinterpret_cast<float*>(sb + l.cand_val);
+    ta.s.top_idx = sel_idx; ta.s.top_val = sel_val; ta.s.walked = rows > 0 ? 1 : 0;
     ta.omega = omega; ta.phase = phase; ta.w = w; ta.eps = eps; ta.m = m; ta.S = S;
     ta.vec_om = ((b->d & 3) == 0 && aligned16(omega)) ? 1 : 0;
     ta.V = reinterpret_cast<float*>(sb + l.v);
-    ta.V64 = (wk.w64 && ns <= R64_MAXN) ? reinterpret_cast<double*>(sb + l.v64) : nullptr;
-    if (!ta.V64) pa.r64_thresh = INFINITY;
-    ta.w64 = wk.w64; ta.w64_stride = wk.w64_stride;
-    ta.paths = paths; ta.sel_idx = sel_idx; ta.sel_val = sel_val; ta.walked = rows > 0 ? 1 : 0;
+    ta.V64 = (c.w.w64 && ns <= R64_MAXN) ? reinterpret_cast<double*>(sb + l.v64) : nullptr;
+    if (!ta.V64) ta.p.r64_thresh = INFINITY;
+    ta.paths = paths;
     // skipped tasks keep zeros in paths; a list that no workgroup writes holds nothing
     if (paths && rows > 0) hipMemsetAsync(paths, 0, sizeof(float) * (size_t)T * S * (size_t)rows, st);
     hipMemsetAsync(ta.s.cand_idx, 0xff, sizeof(int64_t) * (size_t)T * ta.s.chunks_max * S, st);
@@ -1359,7 +1369,7 @@ int adkf_thompson_pool(const adkf_batch_t* b, const float* phi, int32_t flags, c
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ts_stream, PM_NT, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
         const int64_t items = ((rows + PM_TM - 1) / PM_TM) * T;
         ta.s.grid[0] = (int)std::min<int64_t>(items, (int64_t)num_cus() * per_cu);
-        ta.s.grid[2] = ta.V64 ? std::min((int)std::min<int64_t>(64, (rows + PM64_NT / 64 - 1) / (PM64_NT / 64)), ta.s.chunks_max) : 0;
+        ta.s.grid[2] = ta.V64 ? std::min(pm64_grid(rows), ta.s.chunks_max) : 0;
         k_ts_stream<<<ta.s.grid[0], PM_NT, 0, st>>>(ta);
         if (ta.V64) k_ts_stream64<<<dim3(ta.s.grid[2], T), PM64_NT, 0, st>>>(ta);
     }

@@ -339,10 +339,10 @@ double median_l0(const Mat& D2, int n) {
     return std::sqrt(0.5 * v[k]);
 }
 
-int check(const adkf_batch_t* b, bool need_q) {
+int check(const adkf_batch_t* b, bool need_q, bool ard_ok = false) {
     if (!b || b->T <= 0 || b->ns_max <= 0 || b->nq_max < 0 || b->d <= 0 || !b->Z_s) return ADKF_E_BADARG;
     if (b->kernel != ADKF_KERNEL_RBF && b->kernel != ADKF_KERNEL_MATERN52) return ADKF_E_BADARG;
-    if (b->flags & ADKF_BATCH_ARD) return ADKF_E_BADARG;
+    if (!ard_ok && (b->flags & ADKF_BATCH_ARD)) return ADKF_E_BADARG;
     if (need_q && (b->nq_max <= 0 || !b->Z_q)) return ADKF_E_BADARG;
     return 0;
 }
@@ -370,6 +370,64 @@ void pm_row(const Inner& in, int kind, const double* D, const float* y, int flag
         const double u = ((flags & ADKF_PM_MAXIMIZE) ? (mu - bf) : (bf - mu)) / sg;
         ei[r] = (float)(sg * (u * 0.5 * std::erfc(-u / std::sqrt(2.0)) + std::exp(-0.5 * u * u) / std::sqrt(2.0 * M_PI)));
     }
+}
+
+// One task of adkf_predict_marginal(_ard) and adkf_predict_pool: inner_stage on the support set, then row(r, in, D) for the rows
+// lo <= r < hi of Zq, D [n] the squared distances of row r to the support set.  ARD: on z~ = (z - mu) / l with mu the support column
+// mean and l = softplus(raw_lengthscale) per dimension, at unit lengthscale (phi3 = (raw_noise, raw_outputscale, softplus^-1(1)),
+// no lengthscale prior), as csrc/ard.h does; otherwise mu = 0 and l = 1, which change no bit.  Sets info[t]; false when no row was
+// evaluated (n_s == 0 or info != 0).
+template <class ROW>
+bool pm_task(const adkf_batch_t* b, const float* phi, int t, const float* Zq, int64_t lo, int64_t hi, int32_t* info, ROW row) {
+    const bool ard = (b->flags & ADKF_BATCH_ARD) != 0;
+    const int d = b->d, n = std::min(ns_of(b, t), b->ns_max);
+    info[t] = 0;
+    if (n <= 0) return false;
+    const float* Zs = b->Z_s + (size_t)t * b->ns_max * d;
+    const float* x = phi + (size_t)t * (ard ? 2 + d : 3);
+    std::vector<double> mu(d, 0.0), l(d, 1.0);
+    if (ard) {
+        for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) mu[c] += Zs[(size_t)i * d + c];
+        for (int c = 0; c < d; ++c) { mu[c] /= n; l[c] = softplus(x[2 + c]); }
+    }
+    Mat Zt((size_t)n * d);
+    for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) Zt[(size_t)i * d + c] = ((double)Zs[(size_t)i * d + c] - mu[c]) / l[c];
+    const double p[3] = {x[0], x[1], ard ? std::log(std::expm1(1.0)) : (double)x[2]};
+    const float pri[4] = {b->priors[t * 4], b->priors[t * 4 + 1], ard ? 0.f : b->priors[t * 4 + 2], ard ? -1.f : b->priors[t * 4 + 3]};
+    const Inner in = inner_stage(sqdist(Zt.data(), n, Zt.data(), n, d), b->y_s + (size_t)t * b->ns_max, n, p, pri, b->kernel, false, false);
+    info[t] = in.info;
+    if (in.info) return false;
+    std::vector<double> zt(d);
+    for (int64_t r = lo; r < hi; ++r) {
+        for (int c = 0; c < d; ++c) zt[c] = ((double)Zq[(size_t)r * d + c] - mu[c]) / l[c];
+        const Mat D = sqdist(zt.data(), 1, Zt.data(), n, d);
+        row(r, in, D.data());
+    }
+    return true;
+}
+
+int predict_marginal(bool ard, const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
+                     const float* best_f, float* mean, float* var, float* ei, int32_t* info) {
+    if (int rc = check(b, false, ard)) return rc;
+    if (((b->flags & ADKF_BATCH_ARD) != 0) != ard || b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !q_off || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
+    if (ei && !best_f) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
+    // rows outside every task's range and those of tasks with n_s == 0 or info != 0 stay 0 (as on the GPU)
+    if (rows > 0) {
+        std::fill(mean, mean + rows, 0.f);
+        if (var) std::fill(var, var + rows, 0.f);
+        if (ei) std::fill(ei, ei + rows, 0.f);
+    }
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        const int64_t lo = std::min(std::max<int64_t>(q_off[t], 0), rows), hi = std::min(std::max<int64_t>(q_off[t + 1], lo), rows);
+        pm_task(b, phi, t, Zq, lo, hi, info, [&](int64_t r, const Inner& in, const double* D) {
+            pm_row(in, b->kernel, D, b->y_s + (size_t)t * b->ns_max, flags, best_f, t, r, mean, var, ei);
+        });
+    }
+    return 0;
 }
 inline int nq_of(const adkf_batch_t* b, int t) { return b->n_q ? b->n_q[t] : b->nq_max; }
 
@@ -545,82 +603,12 @@ int adkf_predict(const adkf_batch_t* b, const float* phi, float* mean, float* va
 
 int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
                           const float* best_f, float* mean, float* var, float* ei, int32_t* info, void*, size_t, void*) {
-    if (int rc = check(b, false)) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !q_off || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
-    if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
-    if (ei && !best_f) return ADKF_E_BADARG;
-    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
-    const int d = b->d;
-    // rows outside every task's range and those of tasks with n_s == 0 or info != 0 stay 0 (as on the GPU)
-    if (rows > 0) {
-        std::fill(mean, mean + rows, 0.f);
-        if (var) std::fill(var, var + rows, 0.f);
-        if (ei) std::fill(ei, ei + rows, 0.f);
-    }
-#pragma omp parallel for schedule(dynamic)
-    for (int t = 0; t < b->T; ++t) {
-        const int n = std::min(ns_of(b, t), b->ns_max);
-        info[t] = 0;
-        if (n <= 0) continue;
-        const float* Zs = b->Z_s + (size_t)t * b->ns_max * d;
-        const double p[3] = {phi[t * 3], phi[t * 3 + 1], phi[t * 3 + 2]};
-        Inner in = inner_stage(sqdist(Zs, n, Zs, n, d), b->y_s + (size_t)t * b->ns_max, n, p, b->priors + t * 4, b->kernel, false, false);
-        info[t] = in.info;
-        int64_t lo = std::min(std::max<int64_t>(q_off[t], 0), rows), hi = std::min(std::max<int64_t>(q_off[t + 1], lo), rows);
-        for (int64_t r = lo; r < hi; ++r) {
-            if (in.info) break;
-            const Mat D = sqdist(Zq + (size_t)r * d, 1, Zs, n, d);
-            pm_row(in, b->kernel, D.data(), b->y_s + (size_t)t * b->ns_max, flags, best_f, t, r, mean, var, ei);
-        }
-    }
-    return 0;
+    return predict_marginal(false, b, phi, flags, Zq, q_off, rows, best_f, mean, var, ei, info);
 }
 
-// ARD: z~ = (z - mu) / l with mu the support column mean and l = softplus(raw_lengthscale) per dimension, then the code above at
-// unit lengthscale (phi3 = (raw_noise, raw_outputscale, softplus^-1(1)), no lengthscale prior), as csrc/ard.h does
 int adkf_predict_marginal_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
                               const float* best_f, float* mean, float* var, float* ei, int32_t* info, void*, size_t, void*) {
-    if (!b || b->T <= 0 || b->ns_max <= 0 || b->nq_max < 0 || b->d <= 0 || !b->Z_s) return ADKF_E_BADARG;
-    if (b->kernel != ADKF_KERNEL_RBF && b->kernel != ADKF_KERNEL_MATERN52) return ADKF_E_BADARG;
-    if (!(b->flags & ADKF_BATCH_ARD) || b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !q_off || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
-    if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
-    if (ei && !best_f) return ADKF_E_BADARG;
-    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
-    const int d = b->d, h = 2 + d;
-    const double raw_one = std::log(std::expm1(1.0));
-    if (rows > 0) {
-        std::fill(mean, mean + rows, 0.f);
-        if (var) std::fill(var, var + rows, 0.f);
-        if (ei) std::fill(ei, ei + rows, 0.f);
-    }
-#pragma omp parallel for schedule(dynamic)
-    for (int t = 0; t < b->T; ++t) {
-        const int n = std::min(ns_of(b, t), b->ns_max);
-        info[t] = 0;
-        if (n <= 0) continue;
-        const float* Zs = b->Z_s + (size_t)t * b->ns_max * d;
-        const float* x = phi + (size_t)t * h;
-        std::vector<double> mu(d, 0.0), l(d);
-        for (int i = 0; i < n; ++i) for (int k = 0; k < d; ++k) mu[k] += Zs[(size_t)i * d + k];
-        for (int k = 0; k < d; ++k) { mu[k] /= n; l[k] = softplus(x[2 + k]); }
-        Mat Zt((size_t)n * d);
-        for (int i = 0; i < n; ++i) for (int k = 0; k < d; ++k) Zt[(size_t)i * d + k] = ((double)Zs[(size_t)i * d + k] - mu[k]) / l[k];
-        const double p[3] = {x[0], x[1], raw_one};
-        const float pri[4] = {b->priors[t * 4], b->priors[t * 4 + 1], 0.f, -1.f};
-        Inner in = inner_stage(sqdist(Zt.data(), n, Zt.data(), n, d), b->y_s + (size_t)t * b->ns_max, n, p, pri, b->kernel, false, false);
-        info[t] = in.info;
-        int64_t lo = std::min(std::max<int64_t>(q_off[t], 0), rows), hi = std::min(std::max<int64_t>(q_off[t + 1], lo), rows);
-        std::vector<double> zt(d);
-        for (int64_t r = lo; r < hi; ++r) {
-            if (in.info) break;
-            for (int k = 0; k < d; ++k) zt[k] = ((double)Zq[(size_t)r * d + k] - mu[k]) / l[k];
-            const Mat D = sqdist(zt.data(), 1, Zt.data(), n, d);
-            pm_row(in, b->kernel, D.data(), b->y_s + (size_t)t * b->ns_max, flags, best_f, t, r, mean, var, ei);
-        }
-    }
-    return 0;
+    return predict_marginal(true, b, phi, flags, Zq, q_off, rows, best_f, mean, var, ei, info);
 }
 
 size_t adkf_predict_pool_scratch_bytes(int32_t, int32_t) { return 0; }
@@ -630,59 +618,35 @@ size_t adkf_predict_pool_scratch_bytes(int32_t, int32_t) { return 0; }
 int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
                       const int64_t* excl_idx, const int64_t* excl_off, float* mean, float* var, float* ei, int32_t k, int64_t* top_idx,
                       float* top_val, int32_t* info, void*, size_t, void*, size_t, void*) {
-    if (!b || b->T <= 0 || b->ns_max <= 0 || b->nq_max < 0 || b->d <= 0 || !b->Z_s) return ADKF_E_BADARG;
-    if (b->kernel != ADKF_KERNEL_RBF && b->kernel != ADKF_KERNEL_MATERN52) return ADKF_E_BADARG;
+    if (int rc = check(b, false, true)) return rc;
     if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
     if (!phi || !info || !b->y_s || !b->priors || rows < 0 || k < 0) return ADKF_E_BADARG;
     if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN)) return ADKF_E_BADARG;
-    const bool by_mean = (flags & ADKF_PM_SCORE_MEAN) != 0, ard = (b->flags & ADKF_BATCH_ARD) != 0;
+    const bool by_mean = (flags & ADKF_PM_SCORE_MEAN) != 0, want_e = ei || (k > 0 && !by_mean);
     if (rows > 0 && !X) return ADKF_E_BADARG;
-    if ((ei || (k > 0 && !by_mean)) && !best_f) return ADKF_E_BADARG;
+    if (want_e && !best_f) return ADKF_E_BADARG;
     if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
     if (!mean && !var && !ei && k == 0) return ADKF_E_BADARG;
     if (excl_idx && !excl_off) return ADKF_E_BADARG;
     if (k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
-    const int d = b->d, h = ard ? 2 + d : 3;
-    const double raw_one = std::log(std::expm1(1.0));
     const float ninf = -std::numeric_limits<float>::infinity();
 #pragma omp parallel for schedule(dynamic)
     for (int t = 0; t < b->T; ++t) {
-        const int n = std::min(ns_of(b, t), b->ns_max);
         const size_t o = (size_t)t * (size_t)rows;
-        info[t] = 0;
         if (mean) std::fill(mean + o, mean + o + rows, 0.f);
         if (var) std::fill(var + o, var + o + rows, 0.f);
         if (ei) std::fill(ei + o, ei + o + rows, 0.f);
         for (int q = 0; q < k; ++q) { top_idx[(size_t)t * k + q] = -1; top_val[(size_t)t * k + q] = ninf; }
-        if (n <= 0) continue;
-        const float* Zs = b->Z_s + (size_t)t * b->ns_max * d;
-        const float* x = phi + (size_t)t * h;
-        std::vector<double> mu(d, 0.0), l(d, 1.0);
-        Mat Zt((size_t)n * d);   // the support rows the distances are taken to: as they are, or centred and scaled (ARD)
-        if (ard) {
-            for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) mu[c] += Zs[(size_t)i * d + c];
-            for (int c = 0; c < d; ++c) { mu[c] /= n; l[c] = softplus(x[2 + c]); }
-        }
-        for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) Zt[(size_t)i * d + c] = ((double)Zs[(size_t)i * d + c] - mu[c]) / l[c];
-        const double p[3] = {x[0], x[1], ard ? raw_one : (double)x[2]};
-        const float pri[4] = {b->priors[t * 4], b->priors[t * 4 + 1], ard ? 0.f : b->priors[t * 4 + 2], ard ? -1.f : b->priors[t * 4 + 3]};
-        Inner in = inner_stage(sqdist(Zt.data(), n, Zt.data(), n, d), b->y_s + (size_t)t * b->ns_max, n, p, pri, b->kernel, false, false);
-        info[t] = in.info;
-        if (in.info) continue;
         std::vector<float> score(k > 0 ? (size_t)rows : 0);
-        std::vector<double> zt(d);
-        for (int64_t r = 0; r < rows; ++r) {
-            for (int c = 0; c < d; ++c) zt[c] = ((double)X[(size_t)r * d + c] - mu[c]) / l[c];
-            const Mat D = sqdist(zt.data(), 1, Zt.data(), n, d);
+        const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
             float m1, v1, e1 = 0.f;
-            const bool want_e = ei || (k > 0 && !by_mean);
-            pm_row(in, b->kernel, D.data(), b->y_s + (size_t)t * b->ns_max, flags, best_f, t, 0, &m1, &v1, want_e ? &e1 : nullptr);
+            pm_row(in, b->kernel, D, b->y_s + (size_t)t * b->ns_max, flags, best_f, t, 0, &m1, &v1, want_e ? &e1 : nullptr);
             if (mean) mean[o + r] = m1;
             if (var) var[o + r] = v1;
             if (ei) ei[o + r] = e1;
             if (k > 0) score[r] = by_mean ? ((flags & ADKF_PM_MAXIMIZE) ? m1 : -m1) : e1;
-        }
-        if (k <= 0) continue;
+        });
+        if (!done || k <= 0) continue;
         std::vector<int64_t> cand;
         const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
         for (int64_t r = 0; r < rows; ++r)

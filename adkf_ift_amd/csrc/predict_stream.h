@@ -53,6 +53,11 @@
 // answer is unique, so it does not depend on the grid.  NaN scores are never selected.
 //
 // Deterministic: no atomics; a row's result depends on its task's data and its own features only.
+//
+// Shared with thompson_stream.h, so that "pool = packed", "a task's numbers do not depend on the grid" and "Thompson's K is
+// prediction's K" hold by construction: the kernel arguments (PmArgs + the optional groups PmArd and PmPool), the pool walk
+// (PmPoolWalk, pm_task_chunks, pm_list_store), the K panel (pm_query_rows, pm_k_panel), and for flagged tasks the float64 kernel row
+// (pm64_kernel_row) and the exchange of the waves' lists (pm64_gather_lists).
 #pragma once
 #include <type_traits>
 
@@ -77,26 +82,25 @@ struct PmArgs {
     float refine_thresh, r64_thresh;        // r64_thresh: +inf when the workspace has no float64 region
     int latent, maximize, vec;
     int buf_ld;                             // leading dimension of a row tile
+    const double* w64; size_t w64_stride;   // the float64 region of refine64.h (the float64 kernels)
 };
 
 // the ARD instances: PmArgs::Zs is Zt_s, PmArgs::mean_s the support column means mu of ard.h
 struct PmArd { const float *il, *ell; };   // [T, d] each: 1 / l and l
-struct PmArdArgs { PmArgs p; PmArd r; };
 // the shared-pool instances (POOL): PmArgs::Zq is the pool X, q_off unused, mean / var / ei [T, rows] and each nullable
 struct PmPool {
     const int64_t *excl_idx, *excl_off;     // nullable: task t may not select rows excl_idx[excl_off[t] .. excl_off[t + 1]), ascending
     int64_t* cand_idx; float* cand_val;     // scratch lists [T, chunks_max, k]
     int k, chunks_max, score_mean;
-    int grid[3];                            // the grids of the three walks (k_pool_topk derives the chunks per task from them)
+    int grid[3];                            // the grids of the three walks (pm_task_chunks derives the chunks per task from them)
+    int64_t* top_idx; float* top_val;       // the selection [T, k]
+    int walked;                             // rows > 0: the walks ran
 };
-struct PmPoolArgs { PmArgs p; PmPool s; };
-struct PmArdPoolArgs { PmArgs p; PmArd r; PmPool s; };
+// what a kernel receives: the groups its instance does not have are empty
+struct PmNoArd {};
+struct PmNoPool {};
 template <bool ARD, bool POOL = false>
-using PmArgsOf = std::conditional_t<POOL, std::conditional_t<ARD, PmArdPoolArgs, PmPoolArgs>, std::conditional_t<ARD, PmArdArgs, PmArgs>>;
-__device__ __forceinline__ const PmArgs& pm_base(const PmArgs& a) { return a; }
-__device__ __forceinline__ const PmArgs& pm_base(const PmArdArgs& a) { return a.p; }
-__device__ __forceinline__ const PmArgs& pm_base(const PmPoolArgs& a) { return a.p; }
-__device__ __forceinline__ const PmArgs& pm_base(const PmArdPoolArgs& a) { return a.p; }
+struct PmArgsOf { PmArgs p; std::conditional_t<ARD, PmArd, PmNoArd> r; std::conditional_t<POOL, PmPool, PmNoPool> s; };
 
 // il = 1 / l, so that the staging loop of the ARD instances multiplies instead of divides
 __global__ __launch_bounds__(256) void k_pm_ard_il(const float* ell, float* il, int64_t n) {
@@ -235,15 +239,159 @@ __device__ __forceinline__ int pm_pool_chunks(int grid, int n, int chunks_max) {
     const int c = n > 0 ? grid / n : 0;
     return c < 1 ? 1 : (c > chunks_max ? chunks_max : c);
 }
-__device__ __forceinline__ int pm_count_kind(const PmArgs& a, int kind) {
+// a walk serves the tasks whose kind (pm_kind_of) is in the bit mask `kinds`: 1 plain, 2 refined, 3 both (thompson_stream.h)
+__device__ __forceinline__ bool pm_owns(const PmArgs& a, int t, int kinds) {
+    const int kind = pm_kind_of(a, t);
+    return kind >= 0 && ((kinds >> kind) & 1);
+}
+__device__ __forceinline__ int pm_count_kinds(const PmArgs& a, int kinds) {
     int n = 0;
-    for (int u = 0; u < a.T; ++u) n += pm_kind_of(a, u) == kind ? 1 : 0;
+    for (int u = 0; u < a.T; ++u) n += pm_owns(a, u, kinds) ? 1 : 0;
     return n;
+}
+// how many of task t's lists were written (0: skipped task, or no walk ran).  split: the float32 tasks were walked by kind, grid[0]
+// the plain ones and grid[1] the refined (prediction); otherwise in one walk, grid[0] (Thompson).  grid[2]: the float64 kernel.
+__device__ __forceinline__ int pm_task_chunks(const PmArgs& a, const PmPool& s, int t, bool split) {
+    const int kind = s.walked ? pm_kind_of(a, t) : -1;
+    if (kind < 0) return 0;
+    if (kind == 2) return s.grid[2];
+    return pm_pool_chunks(s.grid[split ? kind : 0], pm_count_kinds(a, split ? 1 << kind : 3), s.chunks_max);
+}
+// entry `lane` of the list of (task, chunk), a list of `width` entries (PmPool::k)
+__device__ __forceinline__ void pm_list_store(const PmPool& s, int t, int chunk, int lane, int width, float lv, long long li) {
+    if (lane < width) {
+        const size_t e = ((size_t)t * s.chunks_max + chunk) * width + lane;
+        s.cand_idx[e] = li; s.cand_val[e] = lv;
+    }
+}
+
+// The walk of one workgroup over a shared pool (see the top of the file): a (task, chunk, tile) cursor that only moves forward,
+// and the list (lv, li) of the task it is at, one entry per lane of the first wave, which it stores when it leaves the task.
+template <int KINDS>
+struct PmPoolWalk {
+    int pn, pC, pchunk, pj, pt, grid;
+    int64_t ptile, pntiles;
+    float lv;
+    long long li;
+    // false: nothing for this workgroup (uniform)
+    __device__ __forceinline__ bool start(const PmArgs& a, const PmPool& s) {
+        pt = -1; ptile = 0; lv = -INFINITY; li = -1;   // pt < 0 before the first task
+        grid = gridDim.x;
+        pn = pm_count_kinds(a, KINDS);
+        if (pn == 0) return false;
+        pC = pm_pool_chunks(grid, pn, s.chunks_max);
+        pchunk = blockIdx.x / pn; pj = blockIdx.x % pn;
+        pntiles = (a.rows + PM_TM - 1) / PM_TM;
+        return pchunk < pC;
+    }
+    // the next item: task t, first row r0; false at the end of the walk (uniform).  width: the entries of a list (PmPool::k)
+    __device__ __forceinline__ bool next(const PmArgs& a, const PmPool& s, int width, int& t, int64_t& r0) {
+        while (pt < 0 || ptile >= pntiles) {   // the next task of this walk
+            if (pt >= 0) {
+                pm_list_store(s, pt, pchunk, threadIdx.x, width, lv, li);
+                pj += grid;
+            }
+            if (pj >= pn) return false;
+            int seen = 0;
+            for (pt = 0; pt < a.T; ++pt)
+                if (pm_owns(a, pt, KINDS) && seen++ == pj) break;
+            if (pt >= a.T) return false;   // (cannot happen: pj < pn)
+            ptile = pchunk; lv = -INFINITY; li = -1;
+        }
+        t = pt; r0 = ptile * PM_TM; ptile += pC;
+        return true;
+    }
+};
+
+// ---- the K panel
+// the staging of m query rows from r0 on, centred with mu (ARD: and scaled with il), as the A operand of pm_mm
+template <bool ARD>
+__device__ __forceinline__ auto pm_query_rows(const PmArgs& a, const float* mu, const float* il, int64_t r0, int m) {
+    return [&a, mu, il, r0, m](int i, int k, float (&v)[4]) {
+        if (i >= m) { v[0] = v[1] = v[2] = v[3] = 0.f; return; }
+        const int64_t d = a.d;
+        float z[4], c[4];
+        pm_ld4(a.Zq + (size_t)(r0 + i) * d, k, a.d, a.vec, z); pm_ld4(mu, k, a.d, a.vec, c);
+        if constexpr (ARD) {
+            float s[4];
+            pm_ld4(il, k, a.d, a.vec, s);
+#pragma unroll
+            for (int x = 0; x < 4; ++x) v[x] = (z[x] - c[x]) * s[x];
+        } else {
+#pragma unroll
+            for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
+        }
+    };
+}
+
+// dst[i * ldd + j] = os kappa(|q_i - s_(j0 + j)|^2 il2) for the [64, 64] panel of query rows r0 .. r0 + m against the support rows
+// j0 .. j0 + 64 of Zs [n, d] (zero outside): the centred product and the row norms through pm_mm<true>, the norms of a row summed
+// over the eight lanes that staged it (acc: the caller's accumulator tile, free for reuse afterwards).  before_sync() runs between
+// the stores of the norms and the barrier that publishes them.
+template <bool ARD, class FN>
+__device__ __forceinline__ void pm_k_panel(const PmArgs& a, const float* Zs, const float* mu, const float* il, int64_t r0, int m, int n, int j0,
+                                           float os, float il2, float* As, float* Bs, float (&rowsq)[2][PM_TM], f32x4 (&acc)[2][2],
+                                           float* dst, size_t ldd, FN before_sync) {
+    const int tid = threadIdx.x, kind = a.kind;
+    const int64_t d = a.d;
+    float sqa[2] = {0.f, 0.f}, sqb[2] = {0.f, 0.f};
+    pm_mm<true>(acc, a.d, As, Bs, pm_query_rows<ARD>(a, mu, il, r0, m),
+        [&](int j, int k, float (&v)[4]) {
+            if (j0 + j >= n) { v[0] = v[1] = v[2] = v[3] = 0.f; return; }
+            if constexpr (ARD) {   // Zt_s: centred and scaled already
+                pm_ld4(Zs + (size_t)(j0 + j) * d, k, a.d, a.vec, v);
+            } else {
+                float z[4], c[4];
+                pm_ld4(Zs + (size_t)(j0 + j) * d, k, a.d, a.vec, z); pm_ld4(mu, k, a.d, a.vec, c);
+#pragma unroll
+                for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
+            }
+        }, sqa, sqb);
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {   // the eight threads that staged a row are eight adjacent lanes
+        float x = sqa[ps], y = sqb[ps];
+        x += dpp_f<DPP_XOR1>(x); x += dpp_f<DPP_XOR2>(x); x += dpp_f<DPP_HALF_MIRROR>(x);
+        y += dpp_f<DPP_XOR1>(y); y += dpp_f<DPP_XOR2>(y); y += dpp_f<DPP_HALF_MIRROR>(y);
+        if ((tid & 7) == 0) { rowsq[0][(tid >> 3) + ps * 32] = x; rowsq[1][(tid >> 3) + ps * 32] = y; }
+    }
+    before_sync();
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int ii = pm_row(i, r), jj = pm_col(j);
+                const float d2 = fmaxf(rowsq[0][ii] + rowsq[1][jj] - 2.f * acc[i][j][r], 0.f);
+                dst[(size_t)ii * ldd + jj] = (ii < m && j0 + jj < n) ? os * kappa0(kind, d2 * il2) : 0.f;
+            }
+    __syncthreads();
+}
+
+// ---- the outputs of one row (both prediction kernels): mean, the latent variance vl or the observed one vo, EI; returns the
+// row's selection score (POOL)
+template <bool POOL, class ARGS>
+__device__ __forceinline__ float pm_row_out(const ARGS& args, int t, int64_t r, float mean, float vl, float vo) {
+    const PmArgs& a = args.p;
+    const size_t row = POOL ? (size_t)t * (size_t)a.rows + (size_t)r : (size_t)r;
+    if (!POOL || a.mean) a.mean[row] = mean;
+    if (a.var) a.var[row] = a.latent ? vl : vo;
+    if constexpr (POOL) {
+        const bool by_mean = args.s.score_mean != 0;
+        float e = 0.f;
+        if (a.ei || (args.s.k > 0 && !by_mean)) e = pm_ei(mean, vl, a.best_f[t], a.maximize);
+        if (a.ei) a.ei[row] = e;
+        return by_mean ? (a.maximize ? mean : -mean) : e;
+    } else {
+        if (a.ei) a.ei[row] = pm_ei(mean, vl, a.best_f[t], a.maximize);
+        return 0.f;
+    }
 }
 
 template <bool REFINE, bool GLOBAL, bool ARD = false, bool POOL = false>
 __global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD, POOL> args) {
-    const PmArgs& a = pm_base(args);
+    const PmArgs& a = args.p;
     extern __shared__ __attribute__((aligned(16))) float pm_lds[];
     __shared__ float As[PM_TM * LD_MN], Bs[PM_TM * LD_MN];
     __shared__ float rowsq[2][PM_TM];
@@ -263,39 +411,14 @@ __global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD, POOL> 
     // persistent walk over the tiles of all tasks, in order: (t, first tile of t) is a cursor that only moves forward
     int t = 0;
     int64_t tile0 = 0;
-    // POOL: the walk of this workgroup (see the top of the file); pt < 0 before the first task
-    [[maybe_unused]] int pn = 0, pC = 1, pchunk = 0, pj = 0, pt = -1;
-    [[maybe_unused]] int64_t ptile = 0, pntiles = 0;
-    [[maybe_unused]] float lv = -INFINITY;
-    [[maybe_unused]] long long li = -1;
-    if constexpr (POOL) {
-        pn = pm_count_kind(a, REFINE ? 1 : 0);
-        if (pn == 0) return;
-        pC = pm_pool_chunks(grid, pn, args.s.chunks_max);
-        pchunk = blockIdx.x / pn; pj = blockIdx.x % pn;
-        if (pchunk >= pC) return;
-        pntiles = (a.rows + PM_TM - 1) / PM_TM;
-    }
+    [[maybe_unused]] std::conditional_t<POOL, PmPoolWalk<REFINE ? 2 : 1>, PmNoPool> walk;
+    if constexpr (POOL)
+        if (!walk.start(a, args.s)) return;
     for (int64_t g = blockIdx.x;; g += grid) {
         int64_t lo, hi, r0;
         if constexpr (POOL) {
             lo = 0; hi = a.rows;
-            while (pt < 0 || ptile >= pntiles) {   // the next task of this walk
-                if (pt >= 0) {
-                    if (args.s.k > 0 && tid < args.s.k) {
-                        const size_t e = ((size_t)pt * args.s.chunks_max + pchunk) * args.s.k + tid;
-                        args.s.cand_idx[e] = li; args.s.cand_val[e] = lv;
-                    }
-                    pj += grid;
-                }
-                if (pj >= pn) return;
-                int seen = 0;
-                for (pt = 0; pt < a.T; ++pt)
-                    if (pm_kind_of(a, pt) == (REFINE ? 1 : 0) && seen++ == pj) break;
-                if (pt >= a.T) return;   // (cannot happen: pj < pn)
-                ptile = pchunk; lv = -INFINITY; li = -1;
-            }
-            t = pt; r0 = ptile * PM_TM; ptile += pC;
+            if (!walk.next(a, args.s, args.s.k, t, r0)) return;
         } else {
             for (;;) {
                 if (t >= a.T) return;
@@ -326,52 +449,7 @@ __global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD, POOL> 
         // ---- K row tile
         for (int p = 0; p < np; ++p) {
             const int j0 = p * PM_TM;
-            float sqa[2] = {0.f, 0.f}, sqb[2] = {0.f, 0.f};
-            pm_mm<true>(acc, a.d, As, Bs,
-                [&](int i, int k, float (&v)[4]) {
-                    if (i >= m) { v[0] = v[1] = v[2] = v[3] = 0.f; return; }
-                    float z[4], c[4];
-                    pm_ld4(a.Zq + (size_t)(r0 + i) * d, k, a.d, a.vec, z); pm_ld4(mu, k, a.d, a.vec, c);
-                    if constexpr (ARD) {
-                        float s[4];
-                        pm_ld4(il, k, a.d, a.vec, s);
-#pragma unroll
-                        for (int x = 0; x < 4; ++x) v[x] = (z[x] - c[x]) * s[x];
-                    } else {
-#pragma unroll
-                        for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
-                    }
-                },
-                [&](int j, int k, float (&v)[4]) {
-                    if (j0 + j >= n) { v[0] = v[1] = v[2] = v[3] = 0.f; return; }
-                    if constexpr (ARD) {   // Zt_s: centred and scaled already
-                        pm_ld4(Zs + (size_t)(j0 + j) * d, k, a.d, a.vec, v);
-                    } else {
-                        float z[4], c[4];
-                        pm_ld4(Zs + (size_t)(j0 + j) * d, k, a.d, a.vec, z); pm_ld4(mu, k, a.d, a.vec, c);
-#pragma unroll
-                        for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
-                    }
-                }, sqa, sqb);
-#pragma unroll
-            for (int ps = 0; ps < 2; ++ps) {   // the eight threads that staged a row are eight adjacent lanes
-                float x = sqa[ps], y = sqb[ps];
-                x += dpp_f<DPP_XOR1>(x); x += dpp_f<DPP_XOR2>(x); x += dpp_f<DPP_HALF_MIRROR>(x);
-                y += dpp_f<DPP_XOR1>(y); y += dpp_f<DPP_XOR2>(y); y += dpp_f<DPP_HALF_MIRROR>(y);
-                if ((tid & 7) == 0) { rowsq[0][(tid >> 3) + ps * 32] = x; rowsq[1][(tid >> 3) + ps * 32] = y; }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int ii = pm_row(i, r), jj = pm_col(j);
-                        const float d2 = fmaxf(rowsq[0][ii] + rowsq[1][jj] - 2.f * acc[i][j][r], 0.f);
-                        Kb[(size_t)ii * ld + j0 + jj] = (ii < m && j0 + jj < n) ? os * kappa0(kind, d2 * il2) : 0.f;
-                    }
-            __syncthreads();
+            pm_k_panel<ARD>(a, Zs, mu, il, r0, m, n, j0, os, il2, As, Bs, rowsq, acc, Kb + j0, ld, [] {});
         }
         float s1[2][4], s2[2][4];   // per-lane partial sums of the rows this lane holds: C y and C K
 #pragma unroll
@@ -456,24 +534,12 @@ __global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD, POOL> 
         __syncthreads();
         [[maybe_unused]] float score = 0.f;
         if (tid < m) {
-            const size_t row = POOL ? (size_t)t * (size_t)a.rows + (size_t)(r0 + tid) : (size_t)(r0 + tid);
-            const float mean = red[0][0][tid] + red[1][0][tid];
             const float vl = os - (red[0][1][tid] + red[1][1][tid]);
-            if (!POOL || a.mean) a.mean[row] = mean;
-            if (a.var) a.var[row] = a.latent ? vl : vl + noise;
-            if constexpr (POOL) {
-                const bool by_mean = args.s.score_mean != 0;
-                float e = 0.f;
-                if (a.ei || (args.s.k > 0 && !by_mean)) e = pm_ei(mean, vl, a.best_f[t], a.maximize);
-                if (a.ei) a.ei[row] = e;
-                score = by_mean ? (a.maximize ? mean : -mean) : e;
-            } else {
-                if (a.ei) a.ei[row] = pm_ei(mean, vl, a.best_f[t], a.maximize);
-            }
+            score = pm_row_out<POOL>(args, t, r0 + tid, red[0][0][tid] + red[1][0][tid], vl, vl + noise);
         }
         if constexpr (POOL)
             if (args.s.k > 0 && wv == 0)
-                pm_list_merge(lv, li, args.s.k, score, (long long)(r0 + tid), tid < m, [&](long long r) { return pm_excluded(args.s, t, r); });
+                pm_list_merge(walk.lv, walk.li, args.s.k, score, (long long)(r0 + tid), tid < m, [&](long long r) { return pm_excluded(args.s, t, r); });
         __syncthreads();   // red / rowsq / the row tiles are rewritten by the next tile
     }
 }
@@ -481,23 +547,50 @@ __global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD, POOL> 
 // ---- the float64 evaluation of the rows of flagged tasks: one wave per row, difference-form distances from the features,
 // k_refine64's float64 A^-1 (region A1) and the kernel row parked in LDS
 constexpr int PM64_NT = 256;
-struct Pm64Args { PmArgs p; const double* w64; size_t w64_stride; };
-struct Pm64ArdArgs { Pm64Args q; PmArd r; };
-__device__ __forceinline__ const Pm64Args& pm_base(const Pm64Args& a) { return a; }
-__device__ __forceinline__ const Pm64Args& pm_base(const Pm64ArdArgs& a) { return a.q; }
-// POOL: grid (chunks, T); workgroup (c, t) walks the pool rows c * 4 + wave, stride chunks * 4, and writes the list of (t, c)
-struct Pm64PoolArgs { Pm64Args q; PmPool s; };
-struct Pm64ArdPoolArgs { Pm64Args q; PmArd r; PmPool s; };
-__device__ __forceinline__ const Pm64Args& pm_base(const Pm64PoolArgs& a) { return a.q; }
-__device__ __forceinline__ const Pm64Args& pm_base(const Pm64ArdPoolArgs& a) { return a.q; }
-template <bool ARD, bool POOL>
-using Pm64ArgsOf = std::conditional_t<POOL, std::conditional_t<ARD, Pm64ArdPoolArgs, Pm64PoolArgs>, std::conditional_t<ARD, Pm64ArdArgs, Pm64Args>>;
+constexpr int PM64_WAVES = PM64_NT / 64;
 
+// one wave: k[j] = os kappa(|zq - zs_j|^2 il2) in float64 for the n support rows of Zs, published to the wave.  ARD: Zs is Zt_s and
+// the query element is scaled as k_ard_scale scales it, (z - mu) / el in float32.
+template <bool ARD>
+__device__ __forceinline__ void pm64_kernel_row(const PmArgs& a, const float* zq, const float* Zs, int n, const float* mu, const float* el,
+                                                double os, double il2, double* k) {
+    const int lane = threadIdx.x & 63;
+    for (int j = lane; j < n; j += 64) {
+        const float* zs = Zs + (size_t)j * a.d;
+        double s = 0.0;
+        if constexpr (ARD) {
+            for (int c = 0; c < a.d; ++c) { const double e = (double)((zq[c] - mu[c]) / el[c]) - (double)zs[c]; s += e * e; }
+        } else {
+            for (int c = 0; c < a.d; ++c) { const double e = (double)zq[c] - (double)zs[c]; s += e * e; }
+        }
+        const double u = s * il2;
+        double kv;
+        if (a.kind == ADKF_KERNEL_RBF) kv = exp(-0.5 * u);
+        else { const double rr = sqrt(u); kv = (1.0 + 2.23606797749979 * rr + (5.0 / 3.0) * u) * exp(-2.23606797749979 * rr); }
+        k[j] = os * kv;
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+}
+
+// the end of a float64 walk: the first wave takes the entry (v, i) that each lane of the other waves holds, wave by wave, through
+// merge(v, i)
+template <class M>
+__device__ __forceinline__ void pm64_gather_lists(float lv, long long li, M merge) {
+    __shared__ float mv[PM64_WAVES - 1][64];
+    __shared__ long long mi[PM64_WAVES - 1][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (wv > 0) { mv[wv - 1][lane] = lv; mi[wv - 1][lane] = li; }
+    __syncthreads();
+    if (wv == 0)
+        for (int w = 0; w < PM64_WAVES - 1; ++w) merge(mv[w][lane], mi[w][lane]);
+}
+
+// POOL: grid (chunks, T); workgroup (c, t) walks the pool rows c * 4 + wave, stride chunks * 4, and writes the list of (t, c)
 template <bool ARD = false, bool POOL = false>
-__global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(Pm64ArgsOf<ARD, POOL> args) {
-    const Pm64Args& a64 = pm_base(args);
-    const PmArgs& a = a64.p;
-    __shared__ double kr[PM64_NT / 64][R64_MAXN];
+__global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(PmArgsOf<ARD, POOL> args) {
+    const PmArgs& a = args.p;
+    __shared__ double kr[PM64_WAVES][R64_MAXN];
     [[maybe_unused]] float lv = -INFINITY;   // POOL: every wave keeps a list of the rows it evaluates; merged at the end
     [[maybe_unused]] long long li = -1;
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -509,29 +602,14 @@ __global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(Pm64ArgsOf<ARD, 
     else pm_range(a, t, lo, hi);
     const float* sc = a.scal + (size_t)t * NSCAL;
     const double os = sc[S_OS], noise = sc[S_NOISE], ls = sc[S_LS], il2 = 1.0 / (ls * ls);
-    const double* A1 = a64.w64 + (size_t)t * a64.w64_stride;   // float64 A^-1 [ld, ld]
+    const double* A1 = a.w64 + (size_t)t * a.w64_stride;   // float64 A^-1 [ld, ld]
     const float* Zs = a.Zs + (size_t)t * ld * a.d;
     const float* ys = a.y_s + (size_t)t * ld;
+    const float *mu = nullptr, *el = nullptr;
+    if constexpr (ARD) { mu = a.mean_s + (size_t)t * a.d; el = args.r.ell + (size_t)t * a.d; }
     double* k = kr[wv];
-    for (int64_t r = lo + (int64_t)blockIdx.x * (PM64_NT / 64) + wv; r < hi; r += (int64_t)gridDim.x * (PM64_NT / 64)) {
-        const float* zq = a.Zq + (size_t)r * a.d;
-        for (int j = lane; j < n; j += 64) {
-            const float* zs = Zs + (size_t)j * a.d;
-            double s = 0.0;
-            if constexpr (ARD) {   // the query element scaled as k_ard_scale scales it; zs is Zt_s
-                const float *mu = a.mean_s + (size_t)t * a.d, *el = args.r.ell + (size_t)t * a.d;
-                for (int c = 0; c < a.d; ++c) { const double e = (double)((zq[c] - mu[c]) / el[c]) - (double)zs[c]; s += e * e; }
-            } else {
-                for (int c = 0; c < a.d; ++c) { const double e = (double)zq[c] - (double)zs[c]; s += e * e; }
-            }
-            const double u = s * il2;
-            double kv;
-            if (a.kind == ADKF_KERNEL_RBF) kv = exp(-0.5 * u);
-            else { const double rr = sqrt(u); kv = (1.0 + 2.23606797749979 * rr + (5.0 / 3.0) * u) * exp(-2.23606797749979 * rr); }
-            k[j] = os * kv;
-        }
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    for (int64_t r = lo + (int64_t)blockIdx.x * PM64_WAVES + wv; r < hi; r += (int64_t)gridDim.x * PM64_WAVES) {
+        pm64_kernel_row<ARD>(a, a.Zq + (size_t)r * a.d, Zs, n, mu, el, os, il2, k);
         double s1 = 0.0, s2 = 0.0;
         for (int j = lane; j < n; j += 64) {
             double c = 0.0;
@@ -541,21 +619,7 @@ __global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(Pm64ArgsOf<ARD, 
         }
         for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
         [[maybe_unused]] float score = 0.f;
-        if (lane == 0) {
-            const float mean = (float)s1, vl = (float)(os - s2);
-            const size_t row = POOL ? (size_t)t * (size_t)a.rows + (size_t)r : (size_t)r;
-            if (!POOL || a.mean) a.mean[row] = mean;
-            if (a.var) a.var[row] = a.latent ? vl : (float)(os - s2 + noise);
-            if constexpr (POOL) {
-                const bool by_mean = args.s.score_mean != 0;
-                float e = 0.f;
-                if (a.ei || (args.s.k > 0 && !by_mean)) e = pm_ei(mean, vl, a.best_f[t], a.maximize);
-                if (a.ei) a.ei[row] = e;
-                score = by_mean ? (a.maximize ? mean : -mean) : e;
-            } else {
-                if (a.ei) a.ei[row] = pm_ei(mean, vl, a.best_f[t], a.maximize);
-            }
-        }
+        if (lane == 0) score = pm_row_out<POOL>(args, t, r, (float)s1, (float)(os - s2), (float)(os - s2 + noise));
         if constexpr (POOL)
             if (args.s.k > 0) pm_list_merge(lv, li, args.s.k, score, (long long)r, lane == 0, [&](long long q) { return pm_excluded(args.s, t, q); });
         __builtin_amdgcn_wave_barrier();
@@ -563,32 +627,18 @@ __global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(Pm64ArgsOf<ARD, 
     }
     if constexpr (POOL) {
         if (args.s.k <= 0) return;   // (uniform)
-        __shared__ float mv[PM64_NT / 64 - 1][64];
-        __shared__ long long mi[PM64_NT / 64 - 1][64];
-        if (wv > 0) { mv[wv - 1][lane] = lv; mi[wv - 1][lane] = li; }
-        __syncthreads();
-        if (wv == 0) {
-            for (int w = 0; w < PM64_NT / 64 - 1; ++w)
-                pm_list_merge(lv, li, args.s.k, mv[w][lane], mi[w][lane], mi[w][lane] >= 0, [](long long) { return false; });
-            if (lane < args.s.k) {
-                const size_t e = ((size_t)t * args.s.chunks_max + blockIdx.x) * args.s.k + lane;
-                args.s.cand_idx[e] = li; args.s.cand_val[e] = lv;
-            }
-        }
+        pm64_gather_lists(lv, li, [&](float v, long long i) { pm_list_merge(lv, li, args.s.k, v, i, i >= 0, [](long long) { return false; }); });
+        if (wv == 0) pm_list_store(args.s, t, blockIdx.x, lane, args.s.k, lv, li);
     }
 }
 
 // ---- the last phase of the selection: one wave per task merges the task's lists and writes top_idx / top_val [T, k]
 // (skipped tasks, and every task when no walk ran: -1 / -inf)
-struct PmTopkArgs { PmArgs p; PmPool s; int64_t* top_idx; float* top_val; int walked; };
-__global__ __launch_bounds__(64) void k_pool_topk(PmTopkArgs args) {
+__global__ __launch_bounds__(64) void k_pool_topk(PmArgsOf<false, true> args) {
     const PmArgs& a = args.p;
     const PmPool& s = args.s;
     const int t = blockIdx.x, lane = threadIdx.x, k = s.k;
-    const int kind = args.walked ? pm_kind_of(a, t) : -1;
-    int C = 0;
-    if (kind == 2) C = s.grid[2];
-    else if (kind >= 0) C = pm_pool_chunks(s.grid[kind], pm_count_kind(a, kind), s.chunks_max);
+    const int C = pm_task_chunks(a, s, t, true);
     float lv = -INFINITY;
     long long li = -1;
     const size_t base = (size_t)t * s.chunks_max * k;
@@ -600,7 +650,7 @@ __global__ __launch_bounds__(64) void k_pool_topk(PmTopkArgs args) {
         const float v = in ? s.cand_val[base + e] : 0.f;
         pm_list_merge(lv, li, k, v, r, r >= 0, [](long long) { return false; });
     }
-    if (lane < k) { args.top_idx[(size_t)t * k + lane] = li; args.top_val[(size_t)t * k + lane] = li >= 0 ? lv : -INFINITY; }
+    if (lane < k) { s.top_idx[(size_t)t * k + lane] = li; s.top_val[(size_t)t * k + lane] = li >= 0 ? lv : -INFINITY; }
 }
 
 }  // namespace adkf

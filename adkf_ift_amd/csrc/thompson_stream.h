@@ -13,20 +13,22 @@
 //                g for the S samples (one wave per sample, butterfly sum) and r into V [T, S, ns];
 //   k_ts_solve   per (task, sample): v = A^-1 r, then ONE refinement step v += A^-1 (r - A v) with A regenerated from D2ss (as
 //                ProbCres does), in place in V.  That step is why this call has no plain / refined distinction (pm_kind_of);
-//   k_ts_stream  per (task, pool tile), a persistent grid placed over tasks and tiles exactly as the POOL instances of
-//                predict_stream.h: per 64-feature chunk P = (X - mu) Omega^T on the FP32 MFMA (pm_mm, the operand staging of the
-//                distance product), sqrt(2 s / m) cos(P / l + phase) on the vector ALU into an LDS panel, F += panel W^T on the
-//                MFMA; then per 64-column support panel the K panel exactly as k_predict_marginal computes it (centred D^2 with the
-//                norms summed while staging, then kappa) and F += K_panel V_panel^T.  Only K v is needed, not K A^-1: no [64, ns] row
-//                tile is kept, so any ns runs through this one instance with 53 KB of static LDS.  The X Omega^T product is
-//                computed per task (NOT shared across tasks): the centred form keeps the argument of the cosine at the size of
-//                (x - mu) / l.  Epilogue: the [64, S] tile goes through LDS, optionally to `paths`, and lane q of the first wave
-//                keeps sample q's best (score, row) of the walk under the total order of pm_beats, with the exclusion test of
-//                pm_excluded; at the end of the walk one pair per (task, chunk, sample) goes to scratch with ordinary stores;
+//   k_ts_stream  per (task, pool tile), a persistent grid placed over tasks and tiles by the pool walk of predict_stream.h
+//                (PmPoolWalk, over the plain and the refined tasks at once): per 64-feature chunk P = (X - mu) Omega^T on the
+//                FP32 MFMA (pm_mm with pm_query_rows, the operand staging of the distance product), sqrt(2 s / m)
+//                cos(P / l + phase) on the vector ALU into an LDS panel, F += panel W^T on the MFMA; then per 64-column support
+//                panel the K panel of prediction (pm_k_panel: centred D^2 with the norms summed while staging, then kappa)
+//                and F += K_panel V_panel^T.  Only K v is needed, not K A^-1: no [64, ns] row tile is kept, so any ns runs
+//                through this one instance with 53 KB of static LDS.  The X Omega^T product is computed per task (NOT shared
+//                across tasks): the centred form keeps the argument of the cosine at the size of (x - mu) / l.  Epilogue: the
+//                [64, S] tile goes through LDS, optionally to `paths`, and lane q of the first wave keeps sample q's best
+//                (score, row) of the walk under the total order of pm_beats, with the exclusion test of pm_excluded; at the
+//                end of the walk one pair per (task, chunk, sample) goes to scratch with ordinary stores;
 //   k_ts_merge   one wave per task: lane q reduces the chunks' pairs of sample q under the same order.
 // Tasks flagged for the float64 path (refine64.h: their K v cancels beyond float32) take the <true> instances of the first two
-// kernels - the features and r in float64, v from k_refine64's float64 A^-1 - and k_ts_stream64 (one wave per pool row, modelled
-// on k_predict_marginal64) instead of k_ts_stream.  The cosine there is cosf of the argument reduced to [-pi, pi] in float64.
+// kernels - the features and r in float64, v from k_refine64's float64 A^-1 - and k_ts_stream64 (one wave per pool row, the
+// kernel row and the exchange of the waves' pairs those of k_predict_marginal64) instead of k_ts_stream.  The cosine there is
+// cosf of the argument reduced to [-pi, pi] in float64.
 #pragma once
 #include <type_traits>
 
@@ -41,28 +43,18 @@ constexpr int TS_NS_MAX = 4096;        // the largest support set of the library
 
 struct TsArgs {
     PmArgs p;                           // Zq: the pool X; q_off, best_f, mean / var / ei, the slots unused
-    PmPool s;                           // the exclusion lists; cand_* [T, chunks_max, S]; k = S; grid[0]: k_ts_stream, grid[2]: k_ts_stream64
+    PmPool s;                           // k = S; cand_* [T, chunks_max, S]; top_* = sel_idx / sel_val [T, S]; grid[0], grid[2]
     const float *omega, *phase, *w, *eps;   // [m, d], [m], [T, S, m], [T, S, ns_ld]
     int m, S, vec_om;                   // vec_om: 16-byte loads of the rows of omega are legal
     float* V;                           // [T, S, ns_ld]: r, then v (float32 tasks)
     double* V64;                        // the same for flagged tasks (null without a float64 region)
-    const double* w64; size_t w64_stride;
     float* paths;                       // nullable [T, S, rows]
-    int64_t* sel_idx; float* sel_val;   // [T, S]
-    int walked;                         // rows > 0
 };
 
-// does the float32 (F64 = false) or the float64 (true) instance own task t
+// does the float32 (F64 = false: plain and refined tasks alike) or the float64 (true) instance own task t
+constexpr int TS_KINDS32 = 3;
 template <bool F64>
-__device__ __forceinline__ bool ts_mine(const PmArgs& a, int t) {
-    const int kind = pm_kind_of(a, t);
-    return F64 ? kind == 2 : (kind == 0 || kind == 1);
-}
-__device__ __forceinline__ int ts_count32(const PmArgs& a) {
-    int n = 0;
-    for (int u = 0; u < a.T; ++u) n += ts_mine<false>(a, u) ? 1 : 0;
-    return n;
-}
+__device__ __forceinline__ bool ts_mine(const PmArgs& a, int t) { return F64 ? pm_kind_of(a, t) == 2 : pm_owns(a, t, TS_KINDS32); }
 
 __device__ __forceinline__ float ts_cos(float x) { return cosf(x); }
 __device__ __forceinline__ double ts_cos(double x) {   // reduced in float64, evaluated in float32
@@ -117,7 +109,7 @@ __global__ __launch_bounds__(256) void k_ts_solve(TsArgs args) {
     if constexpr (F64) {
         __shared__ double rs[R64_MAXN];
         if (n > R64_MAXN) return;
-        const double* A1 = args.w64 + (size_t)t * args.w64_stride;   // float64 A^-1 [ld, ld] (symmetric)
+        const double* A1 = a.w64 + (size_t)t * a.w64_stride;   // float64 A^-1 [ld, ld] (symmetric)
         for (int i = tid; i < n; i += 256) rs[i] = args.V64[base + i];
         __syncthreads();
         for (int i = tid; i < n; i += 256) {
@@ -187,42 +179,18 @@ __global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgs args) {
     __shared__ float Pp[PM_TM * TS_LDP], Bp[PM_TM * TS_LDP];   // the A panel (features or K) and the B panel (W or V)
     __shared__ float rowsq[2][PM_TM];
     const int tid = threadIdx.x, wv = tid >> 6;
-    const int grid = gridDim.x, S = args.S;
+    const int S = args.S;
     const int64_t d = a.d;
-    // the walk of this workgroup: as the POOL instances of k_predict_marginal
-    const int pn = ts_count32(a);
-    if (pn == 0) return;
-    const int pC = pm_pool_chunks(grid, pn, args.s.chunks_max), pchunk = blockIdx.x / pn;
-    int pj = blockIdx.x % pn, pt = -1;
-    if (pchunk >= pC) return;
-    const int64_t pntiles = (a.rows + PM_TM - 1) / PM_TM;
-    int64_t ptile = 0;
-    float lv = -INFINITY;   // first wave, lane q: the best (score, row) of sample q in this walk
-    long long li = -1;
+    PmPoolWalk<TS_KINDS32> walk;   // first wave, lane q: (walk.lv, walk.li) is the best (score, row) of sample q in this walk
+    if (!walk.start(a, args.s)) return;
     for (;;) {
-        while (pt < 0 || ptile >= pntiles) {   // the next task of this walk
-            if (pt >= 0) {
-                if (tid < S) {
-                    const size_t e = ((size_t)pt * args.s.chunks_max + pchunk) * S + tid;
-                    args.s.cand_idx[e] = li; args.s.cand_val[e] = lv;
-                }
-                pj += grid;
-            }
-            if (pj >= pn) return;
-            int seen = 0;
-            for (pt = 0; pt < a.T; ++pt)
-                if (ts_mine<false>(a, pt) && seen++ == pj) break;
-            if (pt >= a.T) return;   // (cannot happen: pj < pn)
-            ptile = pchunk; lv = -INFINITY; li = -1;
-        }
-        const int t = pt;
-        const int64_t r0 = ptile * PM_TM;
-        ptile += pC;
+        int t;
+        int64_t r0;
+        if (!walk.next(a, args.s, S, t, r0)) return;
         const int mr = (int)(a.rows - r0 < PM_TM ? a.rows - r0 : PM_TM);
         const int n = pm_ns(a, t);
         const float* sc = a.scal + (size_t)t * NSCAL;
         const float os = sc[S_OS], il = 1.f / sc[S_LS], il2 = 1.f / (sc[S_LS] * sc[S_LS]), amp = sqrtf(2.f * os / (float)args.m);
-        const int kind = a.kind;
         const float* Zs = a.Zs + (size_t)t * a.ns_ld * d;
         const float* mu = a.mean_s + (size_t)t * d;
         const int np = (n + PM_TM - 1) / PM_TM;
@@ -231,13 +199,9 @@ __global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgs args) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j) F[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        auto fx = [&](int i, int k, float (&v)[4]) {   // the centred pool rows of the tile
-            if (i >= mr) { v[0] = v[1] = v[2] = v[3] = 0.f; return; }
-            float z[4], c[4];
-            pm_ld4(a.Zq + (size_t)(r0 + i) * d, k, a.d, a.vec, z); pm_ld4(mu, k, a.d, a.vec, c);
-#pragma unroll
-            for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
-        };
+        // the centred pool rows of the tile, for the feature part (by reference, once per tile: the functor itself held across
+        // the feature loop costs 22 VGPRs)
+        auto fx = [&](int i, int k, float (&v)[4]) { pm_query_rows<false>(a, mu, nullptr, r0, mr)(i, k, v); };
         float dummy[2];
         // ---- feature part: F = sqrt(2 s / m) cos((X - mu) Omega^T / l + phase) W^T
         for (int j0 = 0; j0 < args.m; j0 += PM_TM) {
@@ -260,38 +224,11 @@ __global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgs args) {
             ts_mm(F, Pp, Bp, S);
             __syncthreads();
         }
-        // ---- update part: F += K V^T, the K panel as k_predict_marginal computes it
+        // ---- update part: F += K V^T; the V panel is staged while the norms of the K panel are on their way
         for (int p = 0; p < np; ++p) {
             const int j0 = p * PM_TM;
-            float sqa[2] = {0.f, 0.f}, sqb[2] = {0.f, 0.f};
-            pm_mm<true>(acc, a.d, As, Bs, fx,
-                [&](int j, int k, float (&v)[4]) {
-                    if (j0 + j >= n) { v[0] = v[1] = v[2] = v[3] = 0.f; return; }
-                    float z[4], c[4];
-                    pm_ld4(Zs + (size_t)(j0 + j) * d, k, a.d, a.vec, z); pm_ld4(mu, k, a.d, a.vec, c);
-#pragma unroll
-                    for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
-                }, sqa, sqb);
-#pragma unroll
-            for (int ps = 0; ps < 2; ++ps) {   // the eight threads that staged a row are eight adjacent lanes
-                float x = sqa[ps], y = sqb[ps];
-                x += dpp_f<DPP_XOR1>(x); x += dpp_f<DPP_XOR2>(x); x += dpp_f<DPP_HALF_MIRROR>(x);
-                y += dpp_f<DPP_XOR1>(y); y += dpp_f<DPP_XOR2>(y); y += dpp_f<DPP_HALF_MIRROR>(y);
-                if ((tid & 7) == 0) { rowsq[0][(tid >> 3) + ps * 32] = x; rowsq[1][(tid >> 3) + ps * 32] = y; }
-            }
-            ts_stage(Bp, args.V + (size_t)t * S * a.ns_ld, a.ns_ld, S, j0, n);
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int ii = pm_row(i, r), jj = pm_col(j);
-                        const float d2 = fmaxf(rowsq[0][ii] + rowsq[1][jj] - 2.f * acc[i][j][r], 0.f);
-                        Pp[ii * TS_LDP + jj] = (ii < mr && j0 + jj < n) ? os * kappa0(kind, d2 * il2) : 0.f;
-                    }
-            __syncthreads();
+            pm_k_panel<false>(a, Zs, mu, nullptr, r0, mr, n, j0, os, il2, As, Bs, rowsq, acc, Pp, TS_LDP,
+                              [&] { ts_stage(Bp, args.V + (size_t)t * S * a.ns_ld, a.ns_ld, S, j0, n); });
             ts_mm(F, Pp, Bp, S);
             __syncthreads();
         }
@@ -312,7 +249,7 @@ __global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgs args) {
             for (int r = 0; r < mr; ++r) {
                 const float f = Pp[tid * TS_LDP + r], s = a.maximize ? f : -f;
                 const long long row = r0 + r;
-                if (s == s && pm_beats(s, row, lv, li) && !pm_excluded(args.s, t, row)) { lv = s; li = row; }
+                if (s == s && pm_beats(s, row, walk.lv, walk.li) && !pm_excluded(args.s, t, row)) { walk.lv = s; walk.li = row; }
             }
         __syncthreads();   // the panels are rewritten by the next tile
     }
@@ -322,9 +259,7 @@ __global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgs args) {
 // chunks * 4; lane q carries sample q
 __global__ __launch_bounds__(PM64_NT) void k_ts_stream64(TsArgs args) {
     const PmArgs& a = args.p;
-    __shared__ double kr[PM64_NT / 64][R64_MAXN];
-    __shared__ float mv[PM64_NT / 64 - 1][64];
-    __shared__ long long mi[PM64_NT / 64 - 1][64];
+    __shared__ double kr[PM64_WAVES][R64_MAXN];
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, S = args.S, m = args.m;
     if (!ts_mine<true>(a, t)) return;   // (uniform)
     const int n = pm_ns(a, t), ld = a.ns_ld;
@@ -339,20 +274,9 @@ __global__ __launch_bounds__(PM64_NT) void k_ts_stream64(TsArgs args) {
     double* k = kr[wv];
     float lv = -INFINITY;
     long long li = -1;
-    for (int64_t r = (int64_t)blockIdx.x * (PM64_NT / 64) + wv; r < a.rows; r += (int64_t)gridDim.x * (PM64_NT / 64)) {
+    for (int64_t r = (int64_t)blockIdx.x * PM64_WAVES + wv; r < a.rows; r += (int64_t)gridDim.x * PM64_WAVES) {
         const float* zq = a.Zq + (size_t)r * a.d;
-        for (int j = lane; j < n; j += 64) {
-            const float* zs = Zs + (size_t)j * a.d;
-            double s = 0.0;
-            for (int c = 0; c < a.d; ++c) { const double e = (double)zq[c] - (double)zs[c]; s += e * e; }
-            const double u = s * il2;
-            double kv;
-            if (a.kind == ADKF_KERNEL_RBF) kv = exp(-0.5 * u);
-            else { const double rr = sqrt(u); kv = (1.0 + 2.23606797749979 * rr + (5.0 / 3.0) * u) * exp(-2.23606797749979 * rr); }
-            k[j] = os * kv;
-        }
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        pm64_kernel_row<false>(a, zq, Zs, n, nullptr, nullptr, os, il2, k);
         double f = 0.0;
         for (int j0 = 0; j0 < m; j0 += 64) {   // (m is a multiple of 64) one feature per lane, then every lane adds its sample's 64 terms
             const float* om = args.omega + (size_t)(j0 + lane) * a.d;
@@ -372,14 +296,8 @@ __global__ __launch_bounds__(PM64_NT) void k_ts_stream64(TsArgs args) {
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
-    if (wv > 0) { mv[wv - 1][lane] = lv; mi[wv - 1][lane] = li; }
-    __syncthreads();
-    if (wv == 0 && lane < S) {
-        for (int w = 0; w < PM64_NT / 64 - 1; ++w)
-            if (mi[w][lane] >= 0 && pm_beats(mv[w][lane], mi[w][lane], lv, li)) { lv = mv[w][lane]; li = mi[w][lane]; }
-        const size_t e = ((size_t)t * args.s.chunks_max + blockIdx.x) * S + lane;
-        args.s.cand_idx[e] = li; args.s.cand_val[e] = lv;
-    }
+    pm64_gather_lists(lv, li, [&](float v, long long i) { if (i >= 0 && pm_beats(v, i, lv, li)) { lv = v; li = i; } });
+    if (wv == 0) pm_list_store(args.s, t, blockIdx.x, lane, S, lv, li);
 }
 
 // ---- one wave per task: lane q reduces the pairs of sample q over the task's chunks (skipped tasks, and every task when no
@@ -387,10 +305,7 @@ __global__ __launch_bounds__(PM64_NT) void k_ts_stream64(TsArgs args) {
 __global__ __launch_bounds__(64) void k_ts_merge(TsArgs args) {
     const PmArgs& a = args.p;
     const int t = blockIdx.x, lane = threadIdx.x, S = args.S;
-    const int kind = args.walked ? pm_kind_of(a, t) : -1;
-    int C = 0;
-    if (kind == 2) C = args.s.grid[2];
-    else if (kind >= 0) C = pm_pool_chunks(args.s.grid[0], ts_count32(a), args.s.chunks_max);
+    const int C = pm_task_chunks(a, args.s, t, false);
     if (lane >= S) return;
     float lv = -INFINITY;
     long long li = -1;
@@ -400,8 +315,8 @@ __global__ __launch_bounds__(64) void k_ts_merge(TsArgs args) {
         const float v = args.s.cand_val[e];
         if (r >= 0 && pm_beats(v, r, lv, li)) { lv = v; li = r; }
     }
-    args.sel_idx[(size_t)t * S + lane] = li;
-    args.sel_val[(size_t)t * S + lane] = li >= 0 ? lv : -INFINITY;
+    args.s.top_idx[(size_t)t * S + lane] = li;
+    args.s.top_val[(size_t)t * S + lane] = li >= 0 ? lv : -INFINITY;
 }
 
 }  // namespace adkf

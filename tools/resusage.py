@@ -14,7 +14,7 @@ def main():
     blocks = re.split(r'remark: [^\n]*Function Name: ', txt)[1:]
     rows = []
     for b in blocks:
-        name = b.split('\n')[0].strip()
+        name = b.split('\n')[0].split(' [-Rpass')[0].strip()   # the remark's tag follows the symbol on the same line
 
         def g(k):
             m = re.search(k + r': (\d+)', b)
