@@ -5,9 +5,10 @@ pools beyond ``adkf_max_points()`` rows - or any pool with ``streaming=True`` - 
 streaming marginal prediction (no size cap, workspace independent of the pool size); ``run_gp_ei_bo(streaming=True)`` then
 gets EI straight from that one call.  ``run_gp_ei_bo_batched`` runs many replicates of that loop over the same pool at once: one
 batched fit and one ``adkf_predict_pool`` call per iteration, which returns each replicate's best candidates itself.
-``run_gp_ts_bo_batched`` is the same loop under Thompson sampling: one batched fit and one ``adkf_thompson_pool`` call per
-iteration, in which every replicate draws posterior functions over the whole pool and each function picks its own best candidate -
-a diverse batch of ``query_batch_size > 1`` picks from one pass, with no ``best_f`` and nothing that can underflow.
+``run_gp_ts_bo_batched`` is the same loop under Thompson sampling: one batched fit and one ``adkf_thompson_pool`` call (with
+``ard=True``: ``adkf_thompson_pool_ard``) per iteration, in which every replicate draws posterior functions over the whole pool
+and each function picks its own best candidate - a diverse batch of ``query_batch_size > 1`` picks from one pass, with no
+``best_f`` and nothing that can underflow.
 
 Only the Matern-5/2 branch exists here (the Tanimoto kernel of the reference's fingerprint baseline is not a
 distance-based kernel and is out of the library's scope).
@@ -200,7 +201,7 @@ def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
 def run_gp_ts_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
                          kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
                          rngs: List[np.random.Generator], n_features: int = 1024, oversample: int = 4,
-                         feature_seed: int = 0) -> List[List[int]]:
+                         feature_seed: int = 0, ard: bool = False) -> List[List[int]]:
     """``len(rngs)`` replicates of a Thompson-sampling BO loop over the same pool at once (minimisation, as ``run_gp_ei_bo``);
     returns their records: the best initial index, then the picks in pick order.  Per iteration the replicates' queried sets are
     fitted by ONE ``gp_ops.fit`` (as ``run_gp_ei_bo_batched``) and ONE ``gp_ops.thompson_pool`` call draws
@@ -208,7 +209,10 @@ def run_gp_ts_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
     features (drawn once from ``feature_seed``), each function picking its best row among those the replicate has not queried.  A
     replicate takes the first ``query_batch_size`` distinct picks in sample order; a shortfall is filled with random free rows from
     its generator.  The prior weights and noise draws of replicate r come from a torch generator seeded from ``rngs[r]``, the noise
-    draws at the replicate's own support size: a replicate's record does not depend on which other replicates share the batch."""
+    draws at the replicate's own support size: a replicate's record does not depend on which other replicates share the batch.
+    ``ard``: one lengthscale per feature dimension (the reference's ``ard_num_dims``) - each replicate's ``create_gp`` start is
+    expanded to ``[2 + d]``, every lengthscale at the median heuristic (as ARD ``adkf_init_params`` starts), under the same
+    priors; the batch is an ARD batch and the draws come from ``gp_ops.thompson_pool_ard``."""
     R, n = len(rngs), x_all.shape[0]
     if not 1 <= query_batch_size <= gp_ops._lib.TS_SAMPLES_MAX:
         raise ValueError(f"query_batch_size must be in [1, {gp_ops._lib.TS_SAMPLES_MAX}], got {query_batch_size}")
@@ -238,16 +242,17 @@ def run_gp_ts_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
             Zs[r, :sizes[r]] = model.train_inputs[0].detach().float()
             ys[r, :sizes[r]] = model.train_targets.detach().float()
             pri.append(mll.priors_row(X.device))
-            phi0.append(torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])[None])
+            p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
+            phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
             w[r] = torch.randn(S, n_features, generator=gens[r])
             eps[r, :, :sizes[r]] = torch.randn(S, sizes[r], generator=gens[r])
         n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
-        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=model.ard)
+        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
         phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
         gp_ops.check_info(info, "run_gp_ts_bo_batched fit")
         b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
-        out = gp_ops.thompson_pool(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w.to(X.device), eps=eps.to(X.device),
-                                   maximize=False, exclude=queried)
+        draw = gp_ops.thompson_pool_ard if b.ard else gp_ops.thompson_pool
+        out = draw(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w.to(X.device), eps=eps.to(X.device), maximize=False, exclude=queried)
         gp_ops.check_info(out["info"], "BO posterior")
         sel = out["sel_idx"].cpu().tolist()
         for r, rng in enumerate(rngs):

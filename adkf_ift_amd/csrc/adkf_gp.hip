@@ -1076,6 +1076,98 @@ int predict_marginal(bool ard, const adkf_batch_t* b, const float* phi, int32_t 
     return ard ? pm_launch<true>(c, io) : pm_launch<false>(c, io);
 }
 
+// adkf_thompson_pool: the scratch is V [T, S, ns] (float32), the same in float64 for flagged tasks where the workspace of this
+// shape can have a float64 region, and one (row, score) pair per (task, chunk, sample)
+struct TsScratch { size_t v, v64, cand_idx, cand_val, bytes; };
+static_assert(TS_M_MAX == ADKF_TS_FEATURES_MAX && TS_S_MAX == ADKF_TS_SAMPLES_MAX && TS_NS_MAX >= MAX_POINTS, "thompson_stream.h limits");
+inline TsScratch ts_scratch(int T, int ns, int S) {
+    TsScratch l{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += align_up(bytes); return at; };
+    const size_t e = (size_t)T * S * ns, c = (size_t)T * pm_pool_chunks_max(T) * S;
+    l.v = take(e * sizeof(float));
+    l.v64 = take(ns <= R64_MAXN ? e * sizeof(double) : 0);
+    l.cand_idx = take(c * sizeof(int64_t));
+    l.cand_val = take(c * sizeof(float));
+    l.bytes = off;
+    return l;
+}
+
+// The launches of a prepared Thompson call.  ARD: c.r names the query scaling, whose 1 / l goes into ArdWs::c first (as pm_launch).
+template <bool ARD>
+int ts_launch(const PmCtx& c, TsArgs& ta, int64_t rows) {
+    hipStream_t st = c.st;
+    const int T = c.b.T, ns = c.b.ns_max, S = ta.S;
+    auto args = [&] {
+        TsArgsOf<ARD> k{};
+        static_cast<TsArgs&>(k) = ta;
+        if constexpr (ARD) k.r = c.r;
+        return k;
+    };
+    if (rows > 0) {
+        if constexpr (ARD) {
+            const size_t td = (size_t)T * c.b.d;
+            k_pm_ard_il<<<(unsigned)((td + 255) / 256), 256, 0, st>>>(c.r.ell, const_cast<float*>(c.r.il), (int64_t)td);
+        }
+        k_ts_resid<false, ARD><<<dim3(ns, T), 256, 0, st>>>(ta);
+        if (ta.V64) k_ts_resid<true, ARD><<<dim3(ns, T), 256, 0, st>>>(ta);
+        k_ts_solve<false><<<dim3(S, T), 256, 0, st>>>(ta);
+        if (ta.V64) k_ts_solve<true><<<dim3(S, T), 256, 0, st>>>(ta);
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ts_stream<ARD>, PM_NT, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+        const int64_t items = ((rows + PM_TM - 1) / PM_TM) * T;
+        ta.s.grid[0] = (int)std::min<int64_t>(items, (int64_t)num_cus() * per_cu);
+        ta.s.grid[2] = ta.V64 ? std::min(pm64_grid(rows), ta.s.chunks_max) : 0;
+        k_ts_stream<ARD><<<ta.s.grid[0], PM_NT, 0, st>>>(args());
+        if (ta.V64) k_ts_stream64<ARD><<<dim3(ta.s.grid[2], T), PM64_NT, 0, st>>>(args());
+    }
+    k_ts_merge<<<T, 64, 0, st>>>(ta);
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_thompson_pool and adkf_thompson_pool_ard: the same call on a batch that is (ard) or is not an ARD batch
+int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega,
+                  const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx,
+                  const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void* ws, size_t ws_bytes,
+                  void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_batch(b, false);
+    if (rc) return rc;
+    if (b->nq_max != 0 || b->Z_q || b->y_q || is_ard(b) != ard) return ADKF_E_BADARG;   // the support set only
+    if (!phi || !info || !ws || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!omega || !phase || !w || !eps || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
+    if (m < 64 || m > ADKF_TS_FEATURES_MAX || (m & 63)) return ADKF_E_SIZE;
+    const TsScratch l = ts_scratch(b->T, b->ns_max, S);
+    if (scratch_bytes < l.bytes) return ADKF_E_WORKSPACE;
+    if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 7u)) return ADKF_E_BADARG;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    hipStream_t st = c.st;
+    const int T = b->T, ns = b->ns_max;
+    char* sb = static_cast<char*>(scratch);
+    TsArgs ta{};
+    ta.p = pm_args(c, flags, X, rows, info);
+    ta.s.excl_idx = excl_off ? excl_idx : nullptr; ta.s.excl_off = excl_off;
+    ta.s.k = S; ta.s.chunks_max = pm_pool_chunks_max(T);
+    ta.s.cand_idx = reinterpret_cast<int64_t*>(sb + l.cand_idx); ta.s.cand_val = reinterpret_cast<float*>(sb + l.cand_val);
+    ta.s.top_idx = sel_idx; ta.s.top_val = sel_val; ta.s.walked = rows > 0 ? 1 : 0;
+    ta.omega = omega; ta.phase = phase; ta.w = w; ta.eps = eps; ta.m = m; ta.S = S;
+    ta.vec_om = ((b->d & 3) == 0 && aligned16(omega)) ? 1 : 0;
+    ta.V = reinterpret_cast<float*>(sb + l.v);
+    ta.V64 = (c.w.w64 && ns <= R64_MAXN) ? reinterpret_cast<double*>(sb + l.v64) : nullptr;
+    if (!ta.V64) ta.p.r64_thresh = INFINITY;
+    ta.paths = paths;
+    // skipped tasks keep zeros in paths; a list that no workgroup writes holds nothing
+    if (paths && rows > 0) hipMemsetAsync(paths, 0, sizeof(float) * (size_t)T * S * (size_t)rows, st);
+    hipMemsetAsync(ta.s.cand_idx, 0xff, sizeof(int64_t) * (size_t)T * ta.s.chunks_max * S, st);
+    return ard ? ts_launch<true>(c, ta, rows) : ts_launch<false>(c, ta, rows);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1299,23 +1391,6 @@ int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, co
     return c.ard ? pm_launch<true, true>(c, io) : pm_launch<false, true>(c, io);
 }
 
-// adkf_thompson_pool: the scratch is V [T, S, ns] (float32), the same in float64 for flagged tasks where the workspace of this
-// shape can have a float64 region, and one (row, score) pair per (task, chunk, sample)
-struct TsScratch { size_t v, v64, cand_idx, cand_val, bytes; };
-static_assert(TS_M_MAX == ADKF_TS_FEATURES_MAX && TS_S_MAX == ADKF_TS_SAMPLES_MAX && TS_NS_MAX >= MAX_POINTS, "thompson_stream.h limits");
-inline TsScratch ts_scratch(int T, int ns, int S) {
-    TsScratch l{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += align_up(bytes); return at; };
-    const size_t e = (size_t)T * S * ns, c = (size_t)T * pm_pool_chunks_max(T) * S;
-    l.v = take(e * sizeof(float));
-    l.v64 = take(ns <= R64_MAXN ? e * sizeof(double) : 0);
-    l.cand_idx = take(c * sizeof(int64_t));
-    l.cand_val = take(c * sizeof(float));
-    l.bytes = off;
-    return l;
-}
-
 size_t adkf_thompson_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t S, int32_t m) {
     if (T <= 0 || ns_max <= 0 || ns_max > MAX_POINTS || S < 1 || S > ADKF_TS_SAMPLES_MAX) return 0;
     if (m < 64 || m > ADKF_TS_FEATURES_MAX || (m & 63)) return 0;
@@ -1326,56 +1401,16 @@ int adkf_thompson_pool(const adkf_batch_t* b, const float* phi, int32_t flags, c
                        const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx,
                        const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void* ws, size_t ws_bytes,
                        void* scratch, size_t scratch_bytes, void* stream) {
-    int rc = check_batch(b, false);
-    if (rc) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q || is_ard(b)) return ADKF_E_BADARG;   // the support set only; ARD: not yet
-    if (!phi || !info || !ws || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
-    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
-    if (!omega || !phase || !w || !eps || !sel_idx || !sel_val) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
-    if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
-    if (m < 64 || m > ADKF_TS_FEATURES_MAX || (m & 63)) return ADKF_E_SIZE;
-    const TsScratch l = ts_scratch(b->T, b->ns_max, S);
-    if (scratch_bytes < l.bytes) return ADKF_E_WORKSPACE;
-    if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 7u)) return ADKF_E_BADARG;
-    PmCtx c;
-    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
-    if (rc) return rc;
-    hipStream_t st = c.st;
-    const int T = b->T, ns = b->ns_max;
-    char* sb = static_cast<char*>(scratch);
-    TsArgs ta{};
-    ta.p = pm_args(c, flags, X, rows, info);
-    ta.s.excl_idx = excl_off ? excl_idx : nullptr; ta.s.excl_off = excl_off;
-    ta.s.k = S; ta.s.chunks_max = pm_pool_chunks_max(T);
-    ta.s.cand_idx = reinterpret_cast<int64_t*>(sb + l.cand_idx); ta.s.cand_val = reinterpret_cast<float*>(sb + l.cand_val);
-    ta.s.top_idx = sel_idx; ta.s.top_val = sel_val; ta.s.walked = rows > 0 ? 1 : 0;
-    ta.omega = omega; ta.phase = phase; ta.w = w; ta.eps = eps; ta.m = m; ta.S = S;
-    ta.vec_om = ((b->d & 3) == 0 && aligned16(omega)) ? 1 : 0;
-    ta.V = reinterpret_cast<float*>(sb + l.v);
-    ta.V64 = (c.w.w64 && ns <= R64_MAXN) ? reinterpret_cast<double*>(sb + l.v64) : nullptr;
-    if (!ta.V64) ta.p.r64_thresh = INFINITY;
-    ta.paths = paths;
-    // skipped tasks keep zeros in paths; a list that no workgroup writes holds nothing
-    if (paths && rows > 0) hipMemsetAsync(paths, 0, sizeof(float) * (size_t)T * S * (size_t)rows, st);
-    hipMemsetAsync(ta.s.cand_idx, 0xff, sizeof(int64_t) * (size_t)T * ta.s.chunks_max * S, st);
-    if (rows > 0) {
-        k_ts_resid<false><<<dim3(ns, T), 256, 0, st>>>(ta);
-        if (ta.V64) k_ts_resid<true><<<dim3(ns, T), 256, 0, st>>>(ta);
-        k_ts_solve<false><<<dim3(S, T), 256, 0, st>>>(ta);
-        if (ta.V64) k_ts_solve<true><<<dim3(S, T), 256, 0, st>>>(ta);
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ts_stream, PM_NT, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
-        const int64_t items = ((rows + PM_TM - 1) / PM_TM) * T;
-        ta.s.grid[0] = (int)std::min<int64_t>(items, (int64_t)num_cus() * per_cu);
-        ta.s.grid[2] = ta.V64 ? std::min(pm64_grid(rows), ta.s.chunks_max) : 0;
-        k_ts_stream<<<ta.s.grid[0], PM_NT, 0, st>>>(ta);
-        if (ta.V64) k_ts_stream64<<<dim3(ta.s.grid[2], T), PM64_NT, 0, st>>>(ta);
-    }
-    k_ts_merge<<<T, 64, 0, st>>>(ta);
-    LAUNCH_OK();
-    return 0;
+    return thompson_pool(false, b, phi, flags, X, rows, omega, phase, m, w, eps, S, excl_idx, excl_off, paths, sel_idx, sel_val, info, ws,
+                         ws_bytes, scratch, scratch_bytes, stream);
+}
+
+int adkf_thompson_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega,
+                           const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx,
+                           const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void* ws, size_t ws_bytes,
+                           void* scratch, size_t scratch_bytes, void* stream) {
+    return thompson_pool(true, b, phi, flags, X, rows, omega, phase, m, w, eps, S, excl_idx, excl_off, paths, sel_idx, sel_val, info, ws,
+                         ws_bytes, scratch, scratch_bytes, stream);
 }
 
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

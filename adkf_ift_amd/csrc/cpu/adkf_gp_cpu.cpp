@@ -2,9 +2,10 @@
 // testing without a GPU"; section 8(d)(ii): the second CPU baseline, so that GPU-vs-CPU is not only GPU vs slow Python).
 //
 // Same C ABI, HOST pointers: adkf_batch_t, priors, phi layouts, info codes and flags exactly as in the header; `ws` /
-// `ws_bytes` / `stream` are accepted and ignored (adkf_workspace_bytes returns 0 here).  Non-ARD batches of any size; the one
-// exception is adkf_predict_marginal_ard, which centres and scales the features by the per-dimension lengthscales and runs
-// the isotropic code at unit lengthscale (csrc/ard.h).  adkf_thompson_pool refuses ARD batches, as the library does.
+// `ws_bytes` / `stream` are accepted and ignored (adkf_workspace_bytes returns 0 here).  Non-ARD batches of any size; the
+// exceptions are adkf_predict_marginal_ard, which centres and scales the features by the per-dimension lengthscales and runs
+// the isotropic code at unit lengthscale (csrc/ard.h), and adkf_thompson_pool_ard, which does the same for Thompson sampling.
+// adkf_thompson_pool refuses ARD batches, as the library does.
 // Plain loops, OpenMP over the tasks of a batch, float64 arithmetic inside and float32 at the boundary - a Cholesky-based
 // restatement of the same staged closed-form algebra the HIP kernels run (stage names as in DESIGN.md section 3 and
 // oracle/closed_form.py): kernel matrices from difference-form squared distances, A = L L^T, A^-1, the analytic 3 x 3 Hessian,
@@ -661,13 +662,14 @@ int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, co
 size_t adkf_thompson_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { return 0; }
 
 // Thompson sampling over a shared pool (include/adkf_gp.h): the pathwise posterior draws in float64, rounded to float32 at the
-// boundary; the selection ranks those float32 values under "larger score first, equal scores by ascending row".
-int adkf_thompson_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega,
-                       const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx,
-                       const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void*, size_t, void*, size_t,
-                       void*) {
-    if (int rc = check(b, false)) return rc;   // (refuses ARD batches)
-    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+// boundary; the selection ranks those float32 values under "larger score first, equal scores by ascending row".  ARD
+// (adkf_thompson_pool_ard): on z~ = (z - mu) / l at unit lengthscale, prepared as pm_task prepares it; otherwise the features are
+// centred with mu, the distances are taken from the rows as they are and l = 1, which changes no bit of the isotropic call.
+static int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega,
+                         const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx,
+                         const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info) {
+    if (int rc = check(b, false, ard)) return rc;
+    if (((b->flags & ADKF_BATCH_ARD) != 0) != ard || b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
     if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
     if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
     if (rows > 0 && !X) return ADKF_E_BADARG;
@@ -686,20 +688,25 @@ int adkf_thompson_pool(const adkf_batch_t* b, const float* phi, int32_t flags, c
         if (n <= 0) continue;
         const float* Zs = b->Z_s + (size_t)t * ld * d;
         const float* ys = b->y_s + (size_t)t * ld;
-        const double p[3] = {phi[t * 3], phi[t * 3 + 1], phi[t * 3 + 2]};
-        Inner in = inner_stage(sqdist(Zs, n, Zs, n, d), ys, n, p, b->priors + t * 4, b->kernel, false, false);
+        const float* x0 = phi + (size_t)t * (ard ? 2 + d : 3);
+        std::vector<double> mu(d, 0.0), l(d, 1.0);
+        for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) mu[c] += Zs[(size_t)i * d + c];
+        for (int c = 0; c < d; ++c) { mu[c] /= n; if (ard) l[c] = softplus(x0[2 + c]); }
+        const std::vector<double> dmu = ard ? mu : std::vector<double>(d, 0.0);   // the centring of the distance operands
+        Mat Zt((size_t)n * d);
+        for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) Zt[(size_t)i * d + c] = ((double)Zs[(size_t)i * d + c] - dmu[c]) / l[c];
+        const double p[3] = {x0[0], x0[1], ard ? std::log(std::expm1(1.0)) : (double)x0[2]};
+        const float pri[4] = {b->priors[t * 4], b->priors[t * 4 + 1], ard ? 0.f : b->priors[t * 4 + 2], ard ? -1.f : b->priors[t * 4 + 3]};
+        Inner in = inner_stage(sqdist(Zt.data(), n, Zt.data(), n, d), ys, n, p, pri, b->kernel, false, false);
         info[t] = in.info;
         if (in.info) continue;
-        std::vector<double> mu(d, 0.0);
-        for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) mu[c] += Zs[(size_t)i * d + c];
-        for (int c = 0; c < d; ++c) mu[c] /= n;
         const double amp = std::sqrt(2.0 * in.s / m), sigma = std::sqrt(in.noise), il2 = 1.0 / (in.l * in.l);
         std::vector<double> ft(m);
         auto features = [&](const float* x) {   // phi_j(x), j < m
             for (int j = 0; j < m; ++j) {
                 double a = 0.0;
                 const float* om = omega + (size_t)j * d;
-                for (int c = 0; c < d; ++c) a += (double)om[c] * ((double)x[c] - mu[c]);
+                for (int c = 0; c < d; ++c) a += (double)om[c] * (((double)x[c] - mu[c]) / l[c]);
                 ft[j] = amp * std::cos(a / in.l + (double)phase[j]);
             }
         };
@@ -719,11 +726,12 @@ int adkf_thompson_pool(const adkf_batch_t* b, const float* phi, int32_t flags, c
         std::vector<float> bv(S, ninf);
         std::vector<int64_t> bi(S, -1);
         const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
-        std::vector<double> k(n);
+        std::vector<double> k(n), zt(d);
         for (int64_t r = 0; r < rows; ++r) {
             const float* x = X + (size_t)r * d;
             features(x);
-            const Mat D = sqdist(x, 1, Zs, n, d);
+            for (int c = 0; c < d; ++c) zt[c] = ((double)x[c] - dmu[c]) / l[c];
+            const Mat D = sqdist(zt.data(), 1, Zt.data(), n, d);
             for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); k[j] = in.s * k0; }
             const bool excluded = xb && std::binary_search(xb, xe, r);
             for (int q = 0; q < S; ++q) {
@@ -737,6 +745,20 @@ int adkf_thompson_pool(const adkf_batch_t* b, const float* phi, int32_t flags, c
         for (int q = 0; q < S; ++q) { sel_idx[(size_t)t * S + q] = bi[q]; sel_val[(size_t)t * S + q] = bi[q] >= 0 ? bv[q] : ninf; }
     }
     return 0;
+}
+
+int adkf_thompson_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega,
+                       const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx,
+                       const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void*, size_t, void*, size_t,
+                       void*) {
+    return thompson_pool(false, b, phi, flags, X, rows, omega, phase, m, w, eps, S, excl_idx, excl_off, paths, sel_idx, sel_val, info);   // (refuses ARD batches)
+}
+
+int adkf_thompson_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega,
+                           const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx,
+                           const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void*, size_t, void*, size_t,
+                           void*) {
+    return thompson_pool(true, b, phi, flags, X, rows, omega, phase, m, w, eps, S, excl_idx, excl_off, paths, sel_idx, sel_val, info);
 }
 
 static int outer_common(const adkf_batch_t* b, const float* phi, int flags, bool with_hessian, float* f_out, float* g_phi, float* dZ_s, float* dZ_q,

@@ -29,6 +29,14 @@
 // kernels - the features and r in float64, v from k_refine64's float64 A^-1 - and k_ts_stream64 (one wave per pool row, the
 // kernel row and the exchange of the waves' pairs those of k_predict_marginal64) instead of k_ts_stream.  The cosine there is
 // cosf of the argument reduced to [-pi, pi] in float64.
+//
+// ARD batches (adkf_thompson_pool_ard, ARD = true) are the same call on the scaled features x~ = (x - mu) / l of ard.h at unit
+// lengthscale, with the one basis (omega, phase) every task shares: the support rows are ard.h's Zt_s, centred and scaled already,
+// so k_ts_resid takes omega_j . z~_i as it stands; the pool rows are scaled while they are staged ((x - mu) * il, the il = 1 / l of
+// k_pm_ard_il, as ARD streaming prediction does), for the feature product and the K panel alike, and the feature epilogue has
+// no lengthscale left to apply.  k_ts_stream64<true> scales with k_ard_scale's float32 expression (x - mu) / l before promoting to
+// float64 (the rule of k_predict_marginal64<true>).  k_ts_solve and k_ts_merge are the isotropic instances: the scaled batch's
+// scalars and D2ss are those of the unit-lengthscale pipeline that built A^-1 (scal[S_LS] = softplus(RAW_ONE) = 1, ard.h).
 #pragma once
 #include <type_traits>
 
@@ -50,6 +58,11 @@ struct TsArgs {
     double* V64;                        // the same for flagged tasks (null without a float64 region)
     float* paths;                       // nullable [T, S, rows]
 };
+// what a kernel receives: the ARD instances carry the query scaling as well (PmArgs::Zs is Zt_s, PmArgs::mean_s is mu); the
+// isotropic instances' arguments are TsArgs itself
+struct TsArgsArd : TsArgs { PmArd r; };
+template <bool ARD>
+using TsArgsOf = std::conditional_t<ARD, TsArgsArd, TsArgs>;
 
 // does the float32 (F64 = false: plain and refined tasks alike) or the float64 (true) instance own task t
 constexpr int TS_KINDS32 = 3;
@@ -63,7 +76,7 @@ __device__ __forceinline__ double ts_cos(double x) {   // reduced in float64, ev
 }
 
 // ---- r = y - g(Z_s) - sqrt(noise) eps, per (task, support row): grid (ns_ld, T)
-template <bool F64>
+template <bool F64, bool ARD = false>
 __global__ __launch_bounds__(256) void k_ts_resid(TsArgs args) {
     using R = std::conditional_t<F64, double, float>;
     const PmArgs& a = args.p;
@@ -72,17 +85,26 @@ __global__ __launch_bounds__(256) void k_ts_resid(TsArgs args) {
     if (!ts_mine<F64>(a, t)) return;   // (uniform)
     if (i >= pm_ns(a, t)) return;
     const float* sc = a.scal + (size_t)t * NSCAL;
-    const R il = (R)1 / (R)sc[S_LS], amp = sqrt((R)2 * (R)sc[S_OS] / (R)args.m), sigma = sqrt((R)sc[S_NOISE]);
-    const float* z = a.Zs + ((size_t)t * a.ns_ld + i) * a.d;
-    const float* mu = a.mean_s + (size_t)t * a.d;
+    const R amp = sqrt((R)2 * (R)sc[S_OS] / (R)args.m), sigma = sqrt((R)sc[S_NOISE]);
+    const float* z = a.Zs + ((size_t)t * a.ns_ld + i) * a.d;   // ARD: a row of Zt_s, centred and scaled already
     for (int j = tid; j < args.m; j += 256) {
         const float* om = args.omega + (size_t)j * a.d;
         R s = 0;
-        for (int c = 0; c < a.d; ++c) {
-            if constexpr (F64) s = fma((double)om[c], (double)z[c] - (double)mu[c], s);
-            else s = fmaf(om[c], z[c] - mu[c], s);
+        if constexpr (ARD) {
+            for (int c = 0; c < a.d; ++c) {
+                if constexpr (F64) s = fma((double)om[c], (double)z[c], s);
+                else s = fmaf(om[c], z[c], s);
+            }
+            cs[j] = amp * ts_cos(s + (R)args.phase[j]);
+        } else {
+            const R il = (R)1 / (R)sc[S_LS];
+            const float* mu = a.mean_s + (size_t)t * a.d;
+            for (int c = 0; c < a.d; ++c) {
+                if constexpr (F64) s = fma((double)om[c], (double)z[c] - (double)mu[c], s);
+                else s = fmaf(om[c], z[c] - mu[c], s);
+            }
+            cs[j] = amp * ts_cos(s * il + (R)args.phase[j]);
         }
-        cs[j] = amp * ts_cos(s * il + (R)args.phase[j]);
     }
     __syncthreads();
     for (int q = wv; q < args.S; q += 4) {
@@ -98,7 +120,8 @@ __global__ __launch_bounds__(256) void k_ts_resid(TsArgs args) {
     }
 }
 
-// ---- v = A^-1 r (+ one refinement step in float32), per (task, sample), in place: grid (S, T)
+// ---- v = A^-1 r (+ one refinement step in float32), per (task, sample), in place: grid (S, T).  Serves ARD batches unchanged: their
+// scalars, D2ss and A^-1 are those of the scaled batch at unit lengthscale (scal[S_LS] = 1)
 template <bool F64>
 __global__ __launch_bounds__(256) void k_ts_solve(TsArgs args) {
     const PmArgs& a = args.p;
@@ -173,7 +196,8 @@ __device__ __forceinline__ void ts_stage(float* Bp, const float* src, size_t ld,
     }
 }
 
-__global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgs args) {
+template <bool ARD = false>
+__global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgsOf<ARD> args) {
     const PmArgs& a = args.p;
     __shared__ float As[PM_TM * LD_MN], Bs[PM_TM * LD_MN];
     __shared__ float Pp[PM_TM * TS_LDP], Bp[PM_TM * TS_LDP];   // the A panel (features or K) and the B panel (W or V)
@@ -190,20 +214,23 @@ __global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgs args) {
         const int mr = (int)(a.rows - r0 < PM_TM ? a.rows - r0 : PM_TM);
         const int n = pm_ns(a, t);
         const float* sc = a.scal + (size_t)t * NSCAL;
-        const float os = sc[S_OS], il = 1.f / sc[S_LS], il2 = 1.f / (sc[S_LS] * sc[S_LS]), amp = sqrtf(2.f * os / (float)args.m);
+        const float os = sc[S_OS], il2 = 1.f / (sc[S_LS] * sc[S_LS]), amp = sqrtf(2.f * os / (float)args.m);
+        [[maybe_unused]] const float il = 1.f / sc[S_LS];   // (isotropic: the scaling of the cosine's argument)
         const float* Zs = a.Zs + (size_t)t * a.ns_ld * d;
         const float* mu = a.mean_s + (size_t)t * d;
+        const float* ril = nullptr;                         // ARD: 1 / l per dimension, applied while the pool rows are staged
+        if constexpr (ARD) ril = args.r.il + (size_t)t * d;
         const int np = (n + PM_TM - 1) / PM_TM;
         f32x4 acc[2][2], F[2][2];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j) F[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // the centred pool rows of the tile, for the feature part (by reference, once per tile: the functor itself held across
-        // the feature loop costs 22 VGPRs)
-        auto fx = [&](int i, int k, float (&v)[4]) { pm_query_rows<false>(a, mu, nullptr, r0, mr)(i, k, v); };
+        // the centred (ARD: and scaled) pool rows of the tile, for the feature part (by reference, once per tile: the functor
+        // itself held across the feature loop costs 22 VGPRs)
+        auto fx = [&](int i, int k, float (&v)[4]) { pm_query_rows<ARD>(a, mu, ril, r0, mr)(i, k, v); };
         float dummy[2];
-        // ---- feature part: F = sqrt(2 s / m) cos((X - mu) Omega^T / l + phase) W^T
+        // ---- feature part: F = sqrt(2 s / m) cos((X - mu) Omega^T / l + phase) W^T (ARD: X~ Omega^T + phase)
         for (int j0 = 0; j0 < args.m; j0 += PM_TM) {
             pm_mm<false>(acc, a.d, As, Bs, fx,
                 [&](int j, int k, float (&v)[4]) { pm_ld4(args.omega + (size_t)(j0 + j) * d, k, a.d, args.vec_om, v); }, dummy, dummy);
@@ -217,7 +244,10 @@ __global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgs args) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int ii = pm_row(i, r);
-                        Pp[ii * TS_LDP + jj] = ii < mr ? amp * ts_cos(fmaf(acc[i][j][r], il, ph)) : 0.f;
+                        float arg;
+                        if constexpr (ARD) arg = acc[i][j][r] + ph;
+                        else arg = fmaf(acc[i][j][r], il, ph);
+                        Pp[ii * TS_LDP + jj] = ii < mr ? amp * ts_cos(arg) : 0.f;
                     }
             }
             __syncthreads();
@@ -227,7 +257,7 @@ __global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgs args) {
         // ---- update part: F += K V^T; the V panel is staged while the norms of the K panel are on their way
         for (int p = 0; p < np; ++p) {
             const int j0 = p * PM_TM;
-            pm_k_panel<false>(a, Zs, mu, nullptr, r0, mr, n, j0, os, il2, As, Bs, rowsq, acc, Pp, TS_LDP,
+            pm_k_panel<ARD>(a, Zs, mu, ril, r0, mr, n, j0, os, il2, As, Bs, rowsq, acc, Pp, TS_LDP,
                               [&] { ts_stage(Bp, args.V + (size_t)t * S * a.ns_ld, a.ns_ld, S, j0, n); });
             ts_mm(F, Pp, Bp, S);
             __syncthreads();
@@ -257,7 +287,8 @@ __global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgs args) {
 
 // ---- flagged tasks: one wave per pool row in float64, grid (chunks, T); workgroup (c, t) walks the rows c * 4 + wave, stride
 // chunks * 4; lane q carries sample q
-__global__ __launch_bounds__(PM64_NT) void k_ts_stream64(TsArgs args) {
+template <bool ARD = false>
+__global__ __launch_bounds__(PM64_NT) void k_ts_stream64(TsArgsOf<ARD> args) {
     const PmArgs& a = args.p;
     __shared__ double kr[PM64_WAVES][R64_MAXN];
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, S = args.S, m = args.m;
@@ -265,9 +296,11 @@ __global__ __launch_bounds__(PM64_NT) void k_ts_stream64(TsArgs args) {
     const int n = pm_ns(a, t), ld = a.ns_ld;
     if (n <= 0 || n > R64_MAXN) return;
     const float* sc = a.scal + (size_t)t * NSCAL;
-    const double os = sc[S_OS], ls = sc[S_LS], il = 1.0 / ls, il2 = il * il, amp = sqrt(2.0 * os / (double)m);
+    [[maybe_unused]] const double os = sc[S_OS], ls = sc[S_LS], il = 1.0 / ls, il2 = il * il, amp = sqrt(2.0 * os / (double)m);
     const float* Zs = a.Zs + (size_t)t * ld * a.d;
     const float* mu = a.mean_s + (size_t)t * a.d;
+    const float* el = nullptr;   // ARD: l per dimension
+    if constexpr (ARD) el = args.r.ell + (size_t)t * a.d;
     const int ql = lane < S ? lane : S - 1;   // (lanes beyond S compute sample S - 1 again and store nothing)
     const float* wq = args.w + ((size_t)t * S + ql) * m;
     const double* vq = args.V64 + ((size_t)t * S + ql) * ld;
@@ -276,13 +309,19 @@ __global__ __launch_bounds__(PM64_NT) void k_ts_stream64(TsArgs args) {
     long long li = -1;
     for (int64_t r = (int64_t)blockIdx.x * PM64_WAVES + wv; r < a.rows; r += (int64_t)gridDim.x * PM64_WAVES) {
         const float* zq = a.Zq + (size_t)r * a.d;
-        pm64_kernel_row<false>(a, zq, Zs, n, nullptr, nullptr, os, il2, k);
+        pm64_kernel_row<ARD>(a, zq, Zs, n, mu, el, os, il2, k);
         double f = 0.0;
         for (int j0 = 0; j0 < m; j0 += 64) {   // (m is a multiple of 64) one feature per lane, then every lane adds its sample's 64 terms
             const float* om = args.omega + (size_t)(j0 + lane) * a.d;
             double s = 0.0;
-            for (int c = 0; c < a.d; ++c) s = fma((double)om[c], (double)zq[c] - (double)mu[c], s);
-            const double cv = amp * ts_cos(s * il + (double)args.phase[j0 + lane]);
+            double cv;
+            if constexpr (ARD) {   // the float32 feature of k_ard_scale, promoted (as pm64_kernel_row<true>)
+                for (int c = 0; c < a.d; ++c) s = fma((double)om[c], (double)((zq[c] - mu[c]) / el[c]), s);
+                cv = amp * ts_cos(s + (double)args.phase[j0 + lane]);
+            } else {
+                for (int c = 0; c < a.d; ++c) s = fma((double)om[c], (double)zq[c] - (double)mu[c], s);
+                cv = amp * ts_cos(s * il + (double)args.phase[j0 + lane]);
+            }
             for (int jj = 0; jj < 64; ++jj) f = fma((double)wq[j0 + jj], __shfl(cv, jj), f);
         }
         double u = 0.0;

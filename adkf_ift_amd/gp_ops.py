@@ -443,21 +443,16 @@ def rff_basis(kernel, d: int, m: int, generator: Optional[torch.Generator] = Non
     return omega.contiguous(), phase.contiguous()
 
 
-def thompson_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: torch.Tensor, phase: torch.Tensor, n_samples: int,
-                  generator: Optional[torch.Generator] = None, w: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
-                  maximize: bool = False, exclude=None, want_paths: bool = False):
-    """Thompson sampling over the shared pool ``X [rows, d]`` in one ``adkf_thompson_pool`` call: every task of the support-only
-    batch ``b`` draws ``n_samples`` (at most 64) pathwise posterior functions on the basis ``(omega [m, d], phase [m])``
-    (``rff_basis``; m a multiple of 64, at most 4096), and each function picks its best eligible row.  Returns
-    ``dict(sel_idx [T, S] int64, sel_val [T, S], paths [T, S, rows] or None, info [T], w [T, S, m], eps [T, S, ns])``:
-    ``sel_val`` is the score of the pick, +f with ``maximize`` and -f without; -1 / -inf where no row is eligible.  ``w`` / ``eps``
-    are the standard normal draws: given, or drawn here from ``generator`` (on its device) and returned.  ``exclude``: rows a task
-    may not select (``pack_exclude``).  ARD batches are not supported."""
+def _thompson_pool(name: str, b: GPBatch, phi, X, omega, phase, n_samples, generator, w, eps, maximize, exclude, want_paths):
+    """The body of ``thompson_pool`` (``name = "thompson_pool"``, isotropic batches) and ``thompson_pool_ard`` (ARD batches)."""
     lib = _lib.load()
+    ard = name == "thompson_pool_ard"
     if b.nq != 0:
-        raise ValueError("thompson_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
-    if b.ard:
-        raise ValueError("thompson_pool does not support ARD batches")
+        raise ValueError(f"{name} takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    if b.ard and not ard:
+        raise ValueError("thompson_pool does not support ARD batches: use thompson_pool_ard")
+    if ard and not b.ard:
+        raise ValueError("thompson_pool_ard takes an ARD batch (GPBatch(..., ard=True)): use thompson_pool")
     S = int(n_samples)
     if S < 1 or S > _lib.TS_SAMPLES_MAX:
         raise ValueError(f"n_samples must be in [1, {_lib.TS_SAMPLES_MAX}], got {S}")
@@ -489,9 +484,9 @@ def thompson_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: torc
     excl_idx = excl_off = None
     if exclude is not None:
         excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
-    for name, t in (("X", X), ("omega", omega), ("phase", phase), ("w", w), ("eps", eps)):
+    for arg, t in (("X", X), ("omega", omega), ("phase", phase), ("w", w), ("eps", eps)):
         if t.device != b.device:
-            raise ValueError(f"{name} lives on {t.device}, the batch on {b.device}")
+            raise ValueError(f"{arg} lives on {t.device}, the batch on {b.device}")
     paths = _new(b, b.T, S, rows) if want_paths else None
     sel_idx, sel_val = _new(b, b.T, S, dtype=torch.int64), _new(b, b.T, S)
     info = _new(b, b.T, dtype=torch.int32)
@@ -499,10 +494,34 @@ def thompson_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: torc
     scratch = torch.empty(sb, dtype=torch.uint8, device=b.device)
     ws, nb = b.workspace()
     cb = b.c_struct()
-    _lib.check(lib.adkf_thompson_pool(C.byref(cb), _ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, _ptr(X), rows, _ptr(omega), _ptr(phase),
-                                      m, _ptr(w), _ptr(eps), S, _ptr(excl_idx), _ptr(excl_off), _ptr(paths), _ptr(sel_idx), _ptr(sel_val),
-                                      _ptr(info), _ptr(ws), nb, _ptr(scratch), sb, _stream(b.device)), "adkf_thompson_pool")
+    entry = "adkf_" + name
+    _lib.check(getattr(lib, entry)(C.byref(cb), _ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, _ptr(X), rows, _ptr(omega), _ptr(phase),
+                                   m, _ptr(w), _ptr(eps), S, _ptr(excl_idx), _ptr(excl_off), _ptr(paths), _ptr(sel_idx), _ptr(sel_val),
+                                   _ptr(info), _ptr(ws), nb, _ptr(scratch), sb, _stream(b.device)), entry)
     return dict(sel_idx=sel_idx, sel_val=sel_val, paths=paths, info=info, w=w, eps=eps)
+
+
+def thompson_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: torch.Tensor, phase: torch.Tensor, n_samples: int,
+                  generator: Optional[torch.Generator] = None, w: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
+                  maximize: bool = False, exclude=None, want_paths: bool = False):
+    """Thompson sampling over the shared pool ``X [rows, d]`` in one ``adkf_thompson_pool`` call: every task of the support-only
+    batch ``b`` draws ``n_samples`` (at most 64) pathwise posterior functions on the basis ``(omega [m, d], phase [m])``
+    (``rff_basis``; m a multiple of 64, at most 4096), and each function picks its best eligible row.  Returns
+    ``dict(sel_idx [T, S] int64, sel_val [T, S], paths [T, S, rows] or None, info [T], w [T, S, m], eps [T, S, ns])``:
+    ``sel_val`` is the score of the pick, +f with ``maximize`` and -f without; -1 / -inf where no row is eligible.  ``w`` / ``eps``
+    are the standard normal draws: given, or drawn here from ``generator`` (on its device) and returned.  ``exclude``: rows a task
+    may not select (``pack_exclude``).  ARD batches go to ``thompson_pool_ard``."""
+    return _thompson_pool("thompson_pool", b, phi, X, omega, phase, n_samples, generator, w, eps, maximize, exclude, want_paths)
+
+
+def thompson_pool_ard(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: torch.Tensor, phase: torch.Tensor, n_samples: int,
+                      generator: Optional[torch.Generator] = None, w: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
+                      maximize: bool = False, exclude=None, want_paths: bool = False):
+    """``thompson_pool`` for ARD batches (``phi [T, 2 + d]``) in one ``adkf_thompson_pool_ard`` call: the same draws on the scaled
+    features ``(x - mu) / l`` with one lengthscale per feature dimension.  ``(omega, phase)`` is the same basis at unit lengthscale
+    (``rff_basis``), shared by all tasks; arguments and the returned dict are those of ``thompson_pool``.  Raises ``ValueError``
+    for a batch that is not an ARD batch."""
+    return _thompson_pool("thompson_pool_ard", b, phi, X, omega, phase, n_samples, generator, w, eps, maximize, exclude, want_paths)
 
 
 def double_path_tasks(b: GPBatch) -> torch.Tensor:

@@ -245,7 +245,7 @@ int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, co
  *          [0, 2 pi)); w [T, S, m] and eps [T, S, ns_max] standard normal (entries at i >= n_s[t] are ignored).
  *   b      support-only as for adkf_predict_pool, workspace of adkf_workspace_bytes(T, ns_max, 0, d) bytes; REUSE_DIST / REUSE_INNER
  *          mean what they mean there (the inner quantities at phi, or the fit's, plus the float64 A^-1 of flagged tasks).  ARD
- *          batches are refused (ADKF_E_BADARG): the follow-up, as streaming prediction did isotropic first.
+ *          batches are refused (ADKF_E_BADARG): they go to adkf_thompson_pool_ard below.
  *   flags  ADKF_PM_MAXIMIZE only.
  *   sel_idx, sel_val   [T, S]: sel_idx[t, q] is the eligible pool row of largest score of sample q, equal scores going to the
  *          lowest row index (the total order of adkf_predict_pool: the answer is unique and independent of the grid), sel_val its
@@ -268,6 +268,26 @@ int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, co
 #define ADKF_TS_FEATURES_MAX 4096
 size_t adkf_thompson_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t S, int32_t m);
 int adkf_thompson_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega, const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx, const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
+/* The same for ARD batches (one lengthscale per feature dimension); exactly the parameters of adkf_thompson_pool.
+ *   The quantity.  With phi[t] = (raw_noise, raw_outputscale, raw_lengthscale[0..d)), l_c = softplus(raw_lengthscale[c]), mu the
+ *          support column mean of task t and x~ = (x - mu) / l element-wise, sample q of task t is the isotropic definition on the
+ *          scaled features at unit lengthscale (as csrc/ard.h treats every ARD call):
+ *              phi_j(x) = sqrt(2 s / m) cos(omega_j . x~ + phase_j),    g(x) = sum_j w[t, q, j] phi_j(x),
+ *              r_i = y_i - g(z_i) - sqrt(noise) eps[t, q, i],    v = A^-1 r,    A = s kappa(|z~_i - z~_k|^2) + noise I,
+ *              f(x) = g(x) + sum_i s kappa(|x~ - z~_i|^2) v_i.
+ *          (omega, phase) is still ONE basis of the kernel at unit lengthscale, shared by all tasks.  With all l_c equal f is
+ *          adkf_thompson_pool's f.  The score, the eligibility rule, the total order and the -1 / -inf conventions are unchanged.
+ *   b      must carry ADKF_BATCH_ARD and be support-only (nq_max == 0, Z_q == y_q == NULL); anything else is ADKF_E_BADARG;
+ *   phi    [T, 2 + d] in the ARD layout;
+ *   ws     exactly adkf_workspace_bytes_ard(T, ns_max, 0, d) bytes whatever `rows` is (less: ADKF_E_WORKSPACE); REUSE_INNER after an
+ *          ARD adkf_fit on the same batch and workspace reuses the fit's state, as adkf_predict_marginal_ard documents; otherwise
+ *          the call evaluates at phi.  REUSE_DIST is ignored, as for every ARD call;
+ *   scratch   adkf_thompson_pool_scratch_bytes(T, ns_max, S, m) bytes (it does not depend on d).
+ * Every other argument, check, return code and their order, the outputs, and the guarantees (asynchronous, capturable, no atomics,
+ * reproducible to the bit, a task's result independent of the other tasks of the batch) are those of adkf_thompson_pool; every
+ * check runs before anything is launched. */
+int adkf_thompson_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega, const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx, const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */

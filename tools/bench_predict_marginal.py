@@ -20,7 +20,11 @@ alternately with variant (ii) above in this process (median of --reps single cal
 passes of (ii) with the library as it stands, so the line carries thompson_s < S * ii_pool_topk_s as "beats_S_passes", the matrix
 FLOP the call executes per (task, row) - 2 d m (X Omega^T, computed per task) + 2 m S + 2 d ns + 2 ns S - and its fraction of the
 FP32-matrix bound.  --out FILE also writes the line to FILE.
-Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson] [--out FILE]"""
+--thompson --ard: the same shape for ARD batches (adkf_thompson_pool_ard): one ARD batch and one isotropic batch are fitted on
+the same data, and the two Thompson calls (REUSE_INNER, paths = NULL) are timed alternately in this process (median of --reps
+single calls each).  The line holds both times, their ratio, the float64-flagged tasks of each batch, the bit-equality of a
+repeated ARD call and the distinct picks per task; exit status 1 if the ratio exceeds 1.15.
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--out FILE]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -253,6 +257,59 @@ def shape_thompson(T, ns, d, rows, S, m, reps, dev, out_path=None):
     return rec
 
 
+def shape_thompson_ard(T, ns, d, rows, S, m, reps, dev, out_path=None):
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    bi = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern")
+    phi0, _ = gp_ops.init_params_batch(bi, True, True)
+    bi.flags = gp_ops.REUSE_DIST
+    phi_i, _, _, _, info = gp_ops.fit(bi, phi0, 200)
+    gp_ops.check_info(info)
+    bi.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    ba = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern", ard=True)
+    phi0, _ = gp_ops.init_params_batch(ba, True, True)
+    phi_a, _, _, n_evals, info = gp_ops.fit(ba, phi0, 100)
+    gp_ops.check_info(info)
+    ba.flags = gp_ops.REUSE_INNER
+    X = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):
+        X[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    gc = torch.Generator().manual_seed(1)
+    omega, phase = gp_ops.rff_basis("matern", d, m, generator=gc, device=dev)
+    w, eps = torch.randn(T, S, m, generator=gc).to(dev), torch.randn(T, S, ns, generator=gc).to(dev)
+    kw = dict(omega=omega, phase=phase, n_samples=S, w=w, eps=eps)
+    f_a = lambda: gp_ops.thompson_pool_ard(ba, phi_a, X, **kw)
+    f_i = lambda: gp_ops.thompson_pool(bi, phi_i, X, **kw)
+    o1, o2 = f_a(), f_a()
+    oi = f_i()
+    torch.cuda.synchronize()
+    gp_ops.check_info(o1["info"]); gp_ops.check_info(oi["info"])
+    ts = [[], []]
+    for _ in range(reps):
+        ts[0].append(once(f_a))
+        ts[1].append(once(f_i))
+    t_a, t_i = float(np.median(ts[0])), float(np.median(ts[1]))
+    lib = _lib.load()
+    ell = torch.nn.functional.softplus(phi_a[:, 2:])
+    rec = {"shape": f"thompson ard T={T} ns={ns} d={d} rows={rows} S={S} m={m} matern REUSE_INNER paths=NULL",
+           "float64_tasks_ard": int((_scal(ba)[:, 45] > 30.0).sum()), "float64_tasks_isotropic": int((_scal(bi)[:, 45] > 30.0).sum()),
+           "workspace_bytes_ard": int(lib.adkf_workspace_bytes_ard(T, ns, 0, d)), "workspace_bytes_isotropic": int(lib.adkf_workspace_bytes(T, ns, 0, d)),
+           "scratch_bytes": int(lib.adkf_thompson_pool_scratch_bytes(T, ns, S, m)),
+           "ard_fit_evals_max": int(n_evals.max()), "ard_lengthscale_min": float(ell.min()), "ard_lengthscale_max": float(ell.max()),
+           "thompson_ard_s": t_a, "thompson_isotropic_s": t_i, "ard_over_isotropic": t_a / t_i, "within_1_15": bool(t_a <= 1.15 * t_i),
+           "distinct_picks_per_task_min_ard": int(min(len(set(r)) for r in o1["sel_idx"].cpu().tolist())),
+           "distinct_picks_per_task_min_isotropic": int(min(len(set(r)) for r in oi["sel_idx"].cpu().tolist())),
+           "repeat_is_bit_equal": bool(torch.equal(o1["sel_idx"], o2["sel_idx"]) and torch.equal(o1["sel_val"], o2["sel_val"])), "all_s": ts}
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    return rec
+
+
 def _scal(b):
     """The per-task scalars [T, 64] of a support-only workspace (carve() order of adkf_gp.hip; slot 45 is the pivot ratio that flags
     a task for the float64 path above 30)."""
@@ -316,9 +373,12 @@ def main():
     ap.add_argument("--pool", action="store_true", help="shared-pool prediction against the packed call on a replicated pool, and the batched BO loop")
     ap.add_argument("--skip-bo", action="store_true")
     ap.add_argument("--thompson", action="store_true", help="adkf_thompson_pool against variant (ii) of --pool, timed alternately")
-    ap.add_argument("--out", default=None, help="--thompson: also write the JSON line to this file")
+    ap.add_argument("--out", default=None, help="--thompson (with or without --ard): also write the JSON line to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.thompson and a.ard:
+        rec = shape_thompson_ard(16, 128, 256, 262144, 16, 1024, a.reps, dev, a.out)
+        sys.exit(0 if rec["within_1_15"] else 1)
     if a.thompson:
         rec = shape_thompson(16, 128, 256, 262144, 16, 1024, a.reps, dev, a.out)
         sys.exit(0 if rec["beats_S_passes"] else 1)
