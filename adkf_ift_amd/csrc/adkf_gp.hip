@@ -535,7 +535,7 @@ int outer_pipeline(const adkf_batch_t* b, const Workspace& w, const float* phi, 
     const float corrscale = (with_hessian && !(flags & ADKF_IGNORE_GRAD_CORRECTION)) ? 1.f : 0.f;
     if (use_fused_outer(ns, nq)) {
         // (reused inner stage: A^-1, alpha and the scalars of phi are in the workspace, info[] is written by this kernel)
-        HyperArgs ha{tv, w.Ainv, w.D2ss, w.D2qs, w.D2qq, b->y_s, b->y_q, b->priors, w.Wss, w.Wqs, w.Wqq, w.P, w.OC, w.S, w.vecs, w.scal, f_out, info,
+        HyperArgs ha{tv, w.Ainv, w.D2ss, w.D2qs, w.D2qq, b->y_s, b->y_q, b->priors, w.Wss, w.Wqs, w.Wqq, w.vecs, w.scal, f_out, info,
                      g_phi_out, v_out, H_out, T, reuse_inner ? 1 : 0, with_hessian ? 1 : 0, flags, dirscale, corrscale, refine32_threshold()};
         // FULL: every task has exactly 128 support and 128 query points in 16-byte aligned rows (affine addresses, no clamps)
         const bool full = ns == HY_N && nq == HY_N && !b->n_s && !b->n_q && tv.vec;

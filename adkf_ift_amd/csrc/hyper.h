@@ -11,7 +11,7 @@
 //   S   = K_qq + noise I - C K_sq         in the accumulator layout of the matrix-pipe sweep (factor_m.h), swept in place
 //   r = y_q - C y_s,  e = S^-1 r,  f_out,  C^T e;   W_qq and its three reductions straight from the sweep's registers
 //   Omega C = (S^-1 C - e (C^T e)^T) / 2  -> W_qs, two reductions          (oracle/closed_form.py::outer_stage)
-//   M_A = C^T (Omega C) + sym(C^T e alpha^T) -> W_ss (direct part, kept in registers), three reductions
+//   M_A = C^T (Omega C) + sym(C^T e alpha^T) -> W_ss (direct part; FULL: in registers until the mixed-partial pass), three reductions
 //   with the Hessian:  beta, gamma, delta,  P = A^-1 G,  the nine traces -> H (3 x 3),  v = H^-1 grad_phi f_out, w
 //                      (A^-1 B_v) A^-1 -> the mixed-partial part of W_ss    (::inner_stage, ::mixed_stage)
 //
@@ -31,13 +31,27 @@
 // What an element-wise pass costs here: the CU retires 64 lane-instructions per cycle, a 128 x 128 matrix is 256 cycles PER INSTRUCTION
 // per element, and a pass that loads its squared distance element by element, clamps the address and calls expf is ~70 of them:
 // 18 k cycles, more than the product it follows (16.4 k: the matrix pipe's floor) - the first version of this kernel spent 52 of
-// its 151 us there (tools/hyper_bench.hip).  Hence: (1) the exponential of a squared distance is taken ONCE per matrix and
-// layout - K_qs while its image is loaded, K_qq in the epilogue that forms S, K_ss in the epilogue of M_A - and kept in
-// registers (32 per matrix) for the later passes over the same matrix (W_qq; the traces and the mixed-partial weights; K_qs goes
-// from its LDS image into registers before the image is overwritten); (2) the image of G = dK/dl is written from those registers
-// (transposed 16-byte stores: G is symmetric) instead of being loaded and exponentiated again; (3) symmetric distance blocks are
-// read as the transposed 16-byte groups, four rows of the accumulator layout at once; (4) full 128-point batches (FULL) use affine
-// addresses without clamps; (5) the second copy of A^-1 is fetched into registers before the product in front of it.
+// its 151 us there (tools/hyper_bench.hip).  Hence, for full 128-point batches (FULL):
+//   (1) nothing a workgroup computes is parked in global memory and fetched back.  The exponential of a squared distance is
+//       taken once per matrix and lane layout and then CARRIED IN REGISTERS to the later passes over the same matrix, together
+//       with the squared distances themselves:
+//         K_qq: D2_qq and its factor from the epilogue that forms S, across the sweep, to the W_qq pass (64 registers; the sweep
+//               itself holds S in 32 - the same live set as k_inner's, inner.h);
+//         K_ss: D2_ss (RBF only), its factor and the direct part of W_ss from the epilogue of M_A, across the Hessian stage, to
+//               the traces and the mixed-partial pass, which subtracts its correction and stores W_ss ONCE.  When that pass will
+//               not run (no Hessian, or no correction) the direct part is stored by the epilogue of M_A itself.  Matern-5/2
+//               needs more temporaries per element and re-reads D2_ss in both later passes instead (the three arrays spill
+//               160 bytes per lane there);
+//         K_qs: the load pass (lane = 16-byte groups of a row) and the W_qs epilogue (accumulator layout) use different lane
+//               layouts, so registers cannot carry it: the epilogue reads D2_qs a second time and evaluates the same expression.
+//       Per launch this leaves the seven compulsory transfers (A^-1, D2_ss, D2_qs, D2_qq in; W_ss, W_qs, W_qq out), the second
+//       reads of A^-1 and D2_qs, and for Matern two more reads of D2_ss: 9 / 11 matrices instead of 21;
+//   (2) the image of G = dK/dl is written from the registers of the M_A epilogue (transposed 16-byte stores: G is symmetric)
+//       instead of being loaded and exponentiated again;
+//   (3) symmetric distance blocks are read as the transposed 16-byte groups, four rows of the accumulator layout at once;
+//   (4) affine addresses without clamps;
+//   (5) the second copy of A^-1 is fetched into registers before the product in front of it.
+// The ragged instances (FULL = false) recompute every factor from a fresh, clamped read of the squared distance where it is needed.
 // Sizes: support and query counts up to 128 (64 < max <= 128 takes this kernel; smaller batches keep the small-size kernels,
 // larger ones the blocked path); 16-byte alignment as TaskView::vec says, else the element-wise loads below.
 #pragma once
@@ -57,7 +71,6 @@ struct HyperArgs {
     TaskView tv;
     const float *Ainv, *D2ss, *D2qs, *D2qq, *y_s, *y_q, *priors;
     float *Wss, *Wqs, *Wqq;
-    float *stash_ss, *stash_qs, *stash_qq;   // [T, 128, 128] each (FULL only): exponential factors parked between passes (workspace matrices P, OC, S: free here)
     float* vecs; float* scal; float* f_out; int32_t* info;
     float *g_phi_out, *v_out, *H_out;
     int T, reset_info, with_hessian, flags;
@@ -69,7 +82,6 @@ struct HyperArgs {
 // REJECTED on parity: the golden Matern case gp_N128_Nq128_d256_k1_r1_s0 goes from 1.9e-5 to 1.1e-4 on v (tolerance 1e-4).
 __device__ __forceinline__ float hy_ex(int kind, float u) { return kind == 0 ? expf(-0.5f * u) : expf(-SQRT5 * sqrtf(u)); }
 __device__ __forceinline__ float hy_k0(int kind, float u, float ex) { return kind == 0 ? ex : (1.f + SQRT5 * sqrtf(u) + (5.f / 3.f) * u) * ex; }
-__device__ __forceinline__ float hy_ex_of_k0(int kind, float u, float k0) { return kind == 0 ? k0 : k0 / (1.f + SQRT5 * sqrtf(u) + (5.f / 3.f) * u); }
 __device__ __forceinline__ void hy_k3(int kind, float u, float ex, float& k0, float& k1, float& k2) {
     if (kind == 0) { k0 = ex; k1 = -0.5f * ex; k2 = 0.25f * ex; }
     else {
@@ -85,7 +97,7 @@ __device__ __forceinline__ void hy_k3(int kind, float u, float ex, float& k0, fl
 // across other work: hy_fetch issues all eight 16-byte loads of a lane (clamped addresses, no branch around a load), hy_put
 // transforms and stores.  FULL (ld = 128, 16-byte alignment): no clamps, affine addresses.
 // (Addresses: a uniform base plus a 32-bit lane offset that is made OPAQUE per call.  hipcc otherwise merges the identical address
-// computations of the passes that visit the same matrix - A^-1 twice, D2_ss three times, the parked factors, W_ss - into 64-bit
+// computations of the passes that visit the same matrix - A^-1 twice, D2_qs twice, D2_ss up to three times - into 64-bit
 // per-lane addresses that stay alive across the whole kernel, sixteen registers per matrix, and spills them.)
 #define HY_OPAQUE1(v_) asm volatile("" : "+v"(v_))
 // (the same for LDS: every helper derives its lane addresses from a copy of the thread index the optimiser cannot see through)
@@ -266,16 +278,6 @@ __device__ __forceinline__ unsigned hy_sym_offset() {
 __device__ __forceinline__ void hy_sym_store_tile(float* G, unsigned q, int x, const float (&v)[4]) {
     *reinterpret_cast<float4*>(G + (q + 16u * x * HY_N)) = make_float4(v[0], v[1], v[2], v[3]);
 }
-__device__ __forceinline__ void hy_sym_load(float (&v)[8][4], const float* G) {
-    const int lane = threadIdx.x & 63, p = lane & 15, g = lane >> 4, w = threadIdx.x >> 6;
-    unsigned q = (unsigned)(p * HY_N + 16 * w + 4 * g);
-    HY_OPAQUE1(q);
-#pragma unroll
-    for (int x = 0; x < 8; ++x) {
-        const float4 t = *reinterpret_cast<const float4*>(G + (q + 16u * x * HY_N));
-        v[x][0] = t.x; v[x][1] = t.y; v[x][2] = t.z; v[x][3] = t.w;
-    }
-}
 
 // Sums K per-lane values over the workgroup: float32 inside a row of sixteen lanes (DPP), then the 32 row totals of each value in
 // FLOAT64 by one thread per value (the old pipeline summed float32 per 64 x 64 tile and the tiles in float64; a float32 tree over
@@ -366,14 +368,17 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
     float* sc = a.scal + (size_t)t * NSCAL;
     const float noise = sc[S_NOISE], os = sc[S_OS], ls = sc[S_LS], il2 = 1.f / (ls * ls), gl = -2.f / ls;
     constexpr int kind = KIND;
+    // A FULL instance carries D2_qq and its exponential factor across the sweep, and the factor of K_ss and the direct W_ss across
+    // the Hessian stage, in registers (the header comment, (1)); the ragged instances recompute every factor from a fresh read.
+    // KEEP_DSS: D2_ss stays in registers as well.  With it RBF needs 251 registers; Matern-5/2 would spill 160 bytes per lane
+    // and re-reads D2_ss in the traces and the mixed-partial pass instead (251 registers, no scratch:
+    // profiles/hyper_onchip_resusage.txt).
+    constexpr bool KEEP_DSS = FULL && KIND == 0;
     const bool vec = FULL || a.tv.vec;
     const float* Ai = a.Ainv + (size_t)t * lds * lds;
     const float* Dss = a.D2ss + (size_t)t * lds * lds;
     const float* Dqs = a.D2qs + (size_t)t * ldq * lds;
     const float* Dqq = a.D2qq + (size_t)t * ldq * ldq;
-    float* st_ss = a.stash_ss + (size_t)t * HY_N * HY_N;   // (FULL only)
-    float* st_qs = a.stash_qs + (size_t)t * HY_N * HY_N;
-    float* st_qq = a.stash_qq + (size_t)t * HY_N * HY_N;
     float* vb = a.vecs + (size_t)t * NVEC * vld;
     const int kn = FULL ? 8 : (n + 15) >> 4, km = FULL ? 8 : (m + 15) >> 4;       // 16-wide k blocks that hold a real row
     const bool refine = sc[S_CONDA] > a.refine_thresh;       // (s + noise) max diag(A^-1): C and alpha get one refinement step
@@ -400,13 +405,6 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
         if (FULL || vec) {
             hy_put<FULL>(Y, HY_LDK, va, n, n, ident);              // A^-1 (symmetric)
             hy_put<FULL>(X, HY_LDK, vk, m, n, k0fun);              // kappa(D2_qs / l^2) [m][n]: K_qs without its scale s
-        }
-        if (FULL) {   // ... and row-major into the workspace: the epilogue of Omega C reads it back in the accumulator layout
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int r = (tid >> 5) + 16 * u, c4 = (tid & 31) * 4;
-                *reinterpret_cast<float4*>(st_qs + (unsigned)(r * HY_N + c4)) = *reinterpret_cast<const float4*>(X + r * HY_LDK + c4);
-            }
         }
     }
     if (!(FULL || vec)) {
@@ -479,23 +477,21 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
     hy_zero(acc);
     hy_gemm<false, false>(acc, Y, HY_LDM, X, HY_LDK, kn);      // (C K_sq / s)[i][j] = sum_k C[i][k] kappa_qs[j][k]
     float mm[8][4];
+    float dqq[8][4], eqq[8][4];                                // FULL: alive across the sweep, for the W_qq pass behind it
     {
-        float dv[8][4];
-        hy_dist<FULL, true>(dv, Dqq, ldq, m, m);
-        const unsigned sq = hy_sym_offset();
+        hy_dist<FULL, true>(dqq, Dqq, ldq, m, m);
 #pragma unroll
         for (int x = 0; x < 8; ++x) {
-            float eqq[4];
 #pragma unroll
             for (int y = 0; y < 4; ++y) {
                 const int i = i0 + y, j = j0 + 16 * x;
-                const float u = dv[x][y] * il2;
-                eqq[y] = hy_ex(kind, u);
-                const float sv = os * hy_k0(kind, u, eqq[y]) + (i == j ? noise : 0.f) - acc[x][y];
+                const float u = dqq[x][y] * il2;
+                eqq[x][y] = hy_ex(kind, u);
+                const float sv = os * hy_k0(kind, u, eqq[x][y]) + (i == j ? noise : 0.f) - acc[x][y];
                 mm[x][y] = (in_q(i) && in_q(j)) ? sv : (i == j ? 1.f : 0.f);
             }
-            if (FULL) hy_sym_store_tile(st_qq, sq, x, eqq);    // the exponential factor of K_qq: parked for the W_qq pass behind the sweep
             HY_OPAQUE4(mm[x]);
+            if (FULL) HY_OPAQUE4(eqq[x]);
             HY_FENCE();
         }
     }
@@ -539,9 +535,7 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
         for (int x = 0; x < 8; ++x) si[x] = (f32x4_t){mm[x][0], mm[x][1], mm[x][2], mm[x][3]};
         hy_store_t(si, X, HY_LDK, -1.f);                       // S^-1 (identity beyond m)
         float* Wo = a.Wqq + (size_t)t * ldq * ldq;
-        float dv[8][4], eqq[8][4];
-        hy_dist<FULL, true>(dv, Dqq, ldq, m, m);
-        if (FULL) hy_sym_load(eqq, st_qq);
+        if (!FULL) hy_dist<FULL, true>(dqq, Dqq, ldq, m, m);
         const float wsc = a.dirscale * os * il2;
         const unsigned sq = hy_sym_offset();
 #pragma unroll
@@ -553,7 +547,7 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
                 wq[y] = 0.f;
                 if (in_q(i) && in_q(j)) {
                     const float om = 0.5f * (-mm[x][y] - e_i[y] * e_j[x]);
-                    float k0, k1, k2; const float u = dv[x][y] * il2; hy_k3(kind, u, FULL ? eqq[x][y] : hy_ex(kind, u), k0, k1, k2);
+                    float k0, k1, k2; const float u = dqq[x][y] * il2; hy_k3(kind, u, FULL ? eqq[x][y] : hy_ex(kind, u), k0, k1, k2);
                     wq[y] = wsc * om * k1;
                     if (!FULL) Wo[(unsigned)(i * ldq + j)] = wq[y];
                     if (i == j) r8[0] += om;
@@ -576,9 +570,8 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
         rows_cols(ev, e_i, e_j);
         rows_cols(al, al_i, al_j);
         rows_cols(cte, cte_i, cte_j);
-        float dv[8][4], kq[8][4];
-        hy_dist<FULL, false>(dv, Dqs, lds, m, n);
-        if (FULL) hy_dist<true, false>(kq, st_qs, HY_N, HY_N, HY_N);   // kappa_qs as parked by the load pass
+        float dv[8][4];
+        hy_dist<FULL, false>(dv, Dqs, lds, m, n);                  // (second read: the load pass saw D2_qs in another lane layout)
         const float wsc = a.dirscale * os * il2;
 #pragma unroll
         for (int x = 0; x < 8; ++x) {
@@ -590,7 +583,7 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
                     oc = 0.5f * (acc[x][y] - e_i[y] * cte_j[x]);
                     const float MB = -2.f * oc - e_i[y] * al_j[x];
                     float k0, k1, k2; const float u = dv[x][y] * il2;
-                    hy_k3(kind, u, FULL ? hy_ex_of_k0(kind, u, kq[x][y] / os) : hy_ex(kind, u), k0, k1, k2);
+                    hy_k3(kind, u, hy_ex(kind, u), k0, k1, k2);
                     Wo[(unsigned)(i * lds + j)] = wsc * MB * k1;
                     r8[3] += MB * k0;
                     r8[4] += MB * os * k1 * u * gl;
@@ -607,29 +600,30 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
     hy_zero(acc);
     hy_gemm<true, false>(acc, Y, HY_LDM, X, HY_LDK, km);       // M_A[i][j] = sum_k C[k][i] (Omega C)[k][j]
     float* Wss_o = a.Wss + (size_t)t * lds * lds;
+    // FULL: the direct part of W_ss waits in registers for the mixed-partial pass whenever that pass will run (uniform)
+    const bool defer_wss = FULL && a.with_hessian && a.corrscale != 0.f;
+    float dss[8][4], ess[8][4], wss[8][4];                     // FULL (dss: KEEP_DSS): alive until the mixed-partial pass
     {
         float al_i[4], al_j[8], cte_i[4], cte_j[8];
         rows_cols(al, al_i, al_j);
         rows_cols(cte, cte_i, cte_j);
-        float dv[8][4];
-        hy_dist<FULL, true>(dv, Dss, lds, n, n);
+        hy_dist<FULL, true>(dss, Dss, lds, n, n);
         const float wsc = a.dirscale * os * il2;
         const unsigned sq = hy_sym_offset();
 #pragma unroll
         for (int x = 0; x < 8; ++x) {
-            float ess[4], wss[4];
 #pragma unroll
             for (int y = 0; y < 4; ++y) {
                 const int i = i0 + y, j = j0 + 16 * x;
-                wss[y] = 0.f; ess[y] = 0.f;
+                wss[x][y] = 0.f; ess[x][y] = 0.f;
                 float gv = 0.f;
                 if (in_s(i) && in_s(j)) {
                     const float MA = acc[x][y] + 0.5f * (cte_i[y] * al_j[x] + al_i[y] * cte_j[x]);
-                    const float u = dv[x][y] * il2;
-                    ess[y] = hy_ex(kind, u);
-                    float k0, k1, k2; hy_k3(kind, u, ess[y], k0, k1, k2);
-                    wss[y] = wsc * MA * k1;
-                    if (!FULL) Wss_o[(unsigned)(i * lds + j)] = wss[y];
+                    const float u = dss[x][y] * il2;
+                    ess[x][y] = hy_ex(kind, u);
+                    float k0, k1, k2; hy_k3(kind, u, ess[x][y], k0, k1, k2);
+                    wss[x][y] = wsc * MA * k1;
+                    if (!FULL) Wss_o[(unsigned)(i * lds + j)] = wss[x][y];
                     gv = os * k1 * u * gl;                      // G = dK/dl
                     if (i == j) r8[5] += MA;
                     r8[6] += MA * k0;
@@ -637,9 +631,10 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
                 }
                 acc[x][y] = gv;
             }
-            // the direct part of W_ss goes out now (symmetric: transposed 16-byte groups); the mixed-partial pass updates it in place.
-            // The exponential factor of K_ss is parked for the traces and that pass.
-            if (FULL) { hy_sym_store_tile(Wss_o, sq, x, wss); hy_sym_store_tile(st_ss, sq, x, ess); }
+            // the direct part of W_ss goes out now (symmetric: transposed 16-byte groups) unless the mixed-partial pass will finish it
+            if (FULL && !defer_wss) hy_sym_store_tile(Wss_o, sq, x, wss[x]);
+            if (FULL) HY_OPAQUE4(ess[x]);
+            if (FULL) HY_OPAQUE4(wss[x]);
             HY_OPAQUE3(r8[5], r8[6], r8[7]); HY_OPAQUE4(acc[x]);
             HY_FENCE();
         }
@@ -672,9 +667,7 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
         {
             float al_i[4], al_j[8];
             rows_cols(al, al_i, al_j);
-            float dv[8][4], ess[8][4];
-            hy_dist<FULL, true>(dv, Dss, lds, n, n);
-            if (FULL) hy_sym_load(ess, st_ss);
+            if (!KEEP_DSS) hy_dist<FULL, true>(dss, Dss, lds, n, n);
 #pragma unroll
             for (int x = 0; x < 8; ++x) {
 #pragma unroll
@@ -682,7 +675,7 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
                     const int i = i0 + y, j = j0 + 16 * x;
                     if (in_s(i) && in_s(j)) {
                         const float ai = Y[i * HY_LDK + j];
-                        float k0, k1, k2; const float u = dv[x][y] * il2; hy_k3(kind, u, FULL ? ess[x][y] : hy_ex(kind, u), k0, k1, k2);
+                        float k0, k1, k2; const float u = dss[x][y] * il2; hy_k3(kind, u, FULL ? ess[x][y] : hy_ex(kind, u), k0, k1, k2);
                         const float Kll = os * (k2 * 4.f * u * u + k1 * 6.f * u) * il2;
                         h9[0] += ai * ai; h9[1] += acc[x][y] * ai; h9[3] += ai * Kll; h9[4] += al_i[y] * al_j[x] * Kll;
                     }
@@ -759,9 +752,7 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
             __syncthreads();                                   // (w is visible too)
             hy_zero(acc);
             hy_gemm<true, false>(acc, X, HY_LDK, Y, HY_LDK, kn);   // ((A^-1 B_v) A^-1)[i][j] = sum_k B'[i][k] A^-1[j][k]
-            float dv[8][4], ess[8][4], wss[8][4];
-            hy_dist<FULL, true>(dv, Dss, lds, n, n);
-            if (FULL) { hy_sym_load(ess, st_ss); hy_sym_load(wss, Wss_o); }
+            if (!KEEP_DSS) hy_dist<FULL, true>(dss, Dss, lds, n, n);
             const float ifn = 1.f / (float)n;
             const unsigned sq = hy_sym_offset();
             float w_i[4], w_j[8], al_i[4], al_j[8];
@@ -775,7 +766,7 @@ __global__ __launch_bounds__(HY_NT, 1) void k_hyper(HyperArgs a) {
                     if (in_s(i) && in_s(j)) {
                         const float dgdA = (-0.5f * acc[x][y] + 0.5f * (w_i[y] * al_j[x] + al_i[y] * w_j[x])) * ifn;
                         const float Q = 0.5f * (Y[i * HY_LDK + j] - al_i[y] * al_j[x]) * ifn;
-                        float k0, k1, k2; const float u = dv[x][y] * il2; hy_k3(kind, u, FULL ? ess[x][y] : hy_ex(kind, u), k0, k1, k2);
+                        float k0, k1, k2; const float u = dss[x][y] * il2; hy_k3(kind, u, FULL ? ess[x][y] : hy_ex(kind, u), k0, k1, k2);
                         const float dBv = cs * os * k1 + cl * os * gl * (k1 + u * k2);
                         const float corr = a.corrscale * (dgdA * os * k1 * il2 + Q * dBv * il2);
                         if (FULL) wss[x][y] -= corr;

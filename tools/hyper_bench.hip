@@ -20,9 +20,9 @@ int main() {
                 const float a = i == j ? 5.f + rnd() : 0.02f * (rnd() - 0.5f);  // a diagonally dominant "A^-1"
                 ai[((size_t)t * n + i) * n + j] = a; ai[((size_t)t * n + j) * n + i] = a;
             }
-    float *st1, *st2, *st3, *Ainv, *Dss, *Dqs, *Dqq, *ys, *yq, *pri, *scal, *vecs, *Wss, *Wqs, *Wqq, *fo, *gp, *vo, *Ho;
+    float *Ainv, *Dss, *Dqs, *Dqq, *ys, *yq, *pri, *scal, *vecs, *Wss, *Wqs, *Wqq, *fo, *gp, *vo, *Ho;
     int32_t* info;
-    for (float** p : {&Ainv, &Dss, &Dqs, &Dqq, &Wss, &Wqs, &Wqq, &st1, &st2, &st3}) hipMalloc(p, NN * 4);
+    for (float** p : {&Ainv, &Dss, &Dqs, &Dqq, &Wss, &Wqs, &Wqq}) hipMalloc(p, NN * 4);
     hipMalloc(&ys, (size_t)T * n * 4); hipMalloc(&yq, (size_t)T * n * 4); hipMalloc(&pri, T * 16); hipMalloc(&scal, (size_t)T * NSCAL * 4);
     hipMalloc(&vecs, (size_t)T * NVEC * n * 4); hipMalloc(&fo, T * 4); hipMalloc(&gp, T * 12); hipMalloc(&vo, T * 12); hipMalloc(&Ho, T * 36); hipMalloc(&info, T * 4);
     hipMemcpy(Ainv, ai.data(), NN * 4, hipMemcpyHostToDevice);
@@ -38,7 +38,7 @@ int main() {
     hipMemcpy(pri, pr.data(), pr.size() * 4, hipMemcpyHostToDevice);
     HyperArgs a{};
     a.tv.n_s = nullptr; a.tv.n_q = nullptr; a.tv.ns_ld = n; a.tv.nq_ld = n; a.tv.vld = n; a.tv.kind = 0; a.tv.scal = scal; a.tv.vecs = vecs; a.tv.vec = true;
-    a.Ainv = Ainv; a.D2ss = Dss; a.D2qs = Dqs; a.D2qq = Dqq; a.y_s = ys; a.y_q = yq; a.priors = pri; a.Wss = Wss; a.Wqs = Wqs; a.Wqq = Wqq; a.stash_ss = st1; a.stash_qs = st2; a.stash_qq = st3;
+    a.Ainv = Ainv; a.D2ss = Dss; a.D2qs = Dqs; a.D2qq = Dqq; a.y_s = ys; a.y_q = yq; a.priors = pri; a.Wss = Wss; a.Wqs = Wqs; a.Wqq = Wqq;
     a.vecs = vecs; a.scal = scal; a.f_out = fo; a.info = info; a.g_phi_out = gp; a.v_out = vo; a.H_out = Ho;
     a.T = T; a.reset_info = 1; a.with_hessian = 1; a.flags = 0; a.dirscale = 1.f; a.corrscale = 1.f; a.refine_thresh = 3.f;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hyper<true, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)HY_LDS_BYTES) != hipSuccess) { printf("no LDS opt-in\n"); return 1; }
