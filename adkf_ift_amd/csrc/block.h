@@ -25,11 +25,20 @@ struct BlockArgs {
     float eps; int V, hid;
 };
 
-// new = ((p0 + amp p1) + att p2) + bias with every product and sum rounded on its own, in the order PyTorch evaluates the expression
-// of adkf_ift_amd/gnn.py::GNNBlock (no fused multiply-add): the node states of the fused and of the unfused path are then the same
-// numbers, not merely equally accurate ones
+// new = ((p0 + amp p1) + att p2) + bias and x1 = x + alpha new with every product and sum rounded on its own, in the order PyTorch
+// evaluates the expression of adkf_ift_amd/gnn.py::GNNBlock (no fused multiply-add): the node states of the fused and of the unfused
+// path are then the same numbers, not merely equally accurate ones (tests/test_gpu_gnn_kernels.py: bit for bit against the float32
+// CPU evaluation).  HIP's __fadd_rn / __fmul_rn are plain + and * which hipcc contracts into v_fma like any other; what keeps the
+// operations apart is the pragma (device code is compiled with -ffp-contract=fast-honor-pragmas).
 __device__ __forceinline__ float blk_new(float p0, float p1, float p2, float am, float at, float b) {
-    return __fadd_rn(__fadd_rn(__fadd_rn(p0, __fmul_rn(am, p1)), __fmul_rn(at, p2)), b);
+#pragma clang fp contract(off)
+    const float t1 = am * p1, t2 = at * p2;
+    return ((p0 + t1) + t2) + b;
+}
+__device__ __forceinline__ float blk_x1(float x, float alpha, float nw) {
+#pragma clang fp contract(off)
+    const float t = alpha * nw;
+    return x + t;
 }
 
 template <int C>   // C = hid / 64
@@ -47,7 +56,7 @@ __global__ __launch_bounds__(256) void k_block_fwd(BlockArgs a) {
         for (int c = 0; c < C; ++c) {
             const int j = lane + 64 * c;
             const float nw = blk_new(pr[j], pr[hid + j], pr[2 * hid + j], am, at, bias[c]);
-            x1[c] = __fadd_rn(a.x[(size_t)v * hid + j], __fmul_rn(alpha, nw));
+            x1[c] = blk_x1(a.x[(size_t)v * hid + j], alpha, nw);
             s += x1[c];
         }
         const float mean = wave_sum(s) / (float)hid;

@@ -264,6 +264,16 @@ class TowerMessagePassing(nn.Module):
         return agg.reshape(V, -1)
 
 
+def _addr(t: torch.Tensor):
+    """Device address of ``t`` for a C entry.  A tensor without elements (the message list of a batch without a single edge, or
+    of single-atom graphs only) has the address 0, which the entries reject as a missing argument: such a list is passed as one
+    unused row instead - the kernels read nothing of it (every segment is empty) and still write what belongs to the nodes."""
+    import ctypes as C
+    if t.numel() == 0:
+        t = t.new_empty((1,) + tuple(t.shape[1:]))
+    return C.c_void_p(t.data_ptr())
+
+
 class _MessageFunction(torch.autograd.Function):
     """relu(cat(x[src], x[tgt]) W_et + b_et) for every edge type and tower -> [E_all, H, out] (``adkf_msg_forward`` /
     ``adkf_msg_backward``, csrc/pna.h: ONE launch of each kind for all edge types).  x [V, H*in] float32 contiguous; weights[et]
@@ -298,7 +308,7 @@ class _MessageFunction(torch.autograd.Function):
         st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         tab = _MessageFunction._table(plan, weights, biases)
         _lib.check(lib.adkf_msg_forward(C.c_void_p(x.data_ptr()), C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim,
-                                        C.c_void_p(msgs.data_ptr()), st), "adkf_msg_forward")
+                                        _addr(msgs), st), "adkf_msg_forward")
         ctx.save_for_backward(x, msgs, *weights)
         ctx.plan, ctx.dims, ctx.n_et = plan, (H, in_dim, out_dim), n_et
         return msgs
@@ -318,7 +328,7 @@ class _MessageFunction(torch.autograd.Function):
         E_all = int(plan.all_tgts.shape[0])
         # no floating-point atomics anywhere (csrc/pna.h): d cat is written once per edge and d x gathered over each node's
         # edge lists; d W / d b are per-chunk partials summed in a fixed order - every output element is written, none pre-filled
-        dcat = torch.empty(max(E_all, 1), H, 2 * in_dim, dtype=torch.float32, device=dev)
+        dcat = torch.empty(E_all, H, 2 * in_dim, dtype=torch.float32, device=dev)
         dW_all = [torch.empty_like(w) for w in weights]
         db_all = torch.empty(n_et, H, out_dim, dtype=torch.float32, device=dev)
         dbs = [db_all[et] for et in range(n_et)]
@@ -326,9 +336,9 @@ class _MessageFunction(torch.autograd.Function):
         need = int(lib.adkf_msg_backward_scratch_bytes(C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim))
         scratch = torch.empty(max(need, 4) // 4, dtype=torch.float32, device=dev)
         dx = torch.empty_like(x)
-        _lib.check(lib.adkf_msg_backward(ptr(x), C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim, ptr(msgs), ptr(d_msgs),
-                                         ptr(plan.perm_src), ptr(plan.rowptr_src), ptr(plan.perm), ptr(plan.rowptr), x.shape[0],
-                                         ptr(dcat), ptr(dx), ptr(scratch), scratch.numel() * 4, st), "adkf_msg_backward")
+        _lib.check(lib.adkf_msg_backward(ptr(x), C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim, _addr(msgs), _addr(d_msgs),
+                                         _addr(plan.perm_src), ptr(plan.rowptr_src), _addr(plan.perm), ptr(plan.rowptr), x.shape[0],
+                                         _addr(dcat), ptr(dx), ptr(scratch), scratch.numel() * 4, st), "adkf_msg_backward")
         return (dx, None, None, None, None, *dW_all, *dbs)
 
 
@@ -346,7 +356,7 @@ class _PNAAggregate(torch.autograd.Function):
         agg = torch.empty(V, H, 4 * m, dtype=torch.float32, device=msgs.device)
         argmax = torch.empty(V, H, m, dtype=torch.int32, device=msgs.device)
         st = C.c_void_p(torch.cuda.current_stream(msgs.device).cuda_stream)
-        _lib.check(lib.adkf_pna_aggregate(C.c_void_p(msgs.data_ptr()), C.c_void_p(perm.data_ptr()), C.c_void_p(rowptr.data_ptr()),
+        _lib.check(lib.adkf_pna_aggregate(_addr(msgs), _addr(perm), C.c_void_p(rowptr.data_ptr()),
                                           V, H, m, C.c_void_p(agg.data_ptr()), C.c_void_p(argmax.data_ptr()), st), "adkf_pna_aggregate")
         ctx.save_for_backward(msgs, perm, rowptr, agg, argmax)
         ctx.mark_non_differentiable(argmax)
@@ -363,9 +373,9 @@ class _PNAAggregate(torch.autograd.Function):
         d_agg = d_agg.contiguous()
         d_msgs = torch.empty_like(msgs)
         st = C.c_void_p(torch.cuda.current_stream(msgs.device).cuda_stream)
-        _lib.check(lib.adkf_pna_aggregate_backward(C.c_void_p(msgs.data_ptr()), C.c_void_p(perm.data_ptr()), C.c_void_p(rowptr.data_ptr()),
+        _lib.check(lib.adkf_pna_aggregate_backward(_addr(msgs), _addr(perm), C.c_void_p(rowptr.data_ptr()),
                                                    C.c_void_p(agg.data_ptr()), C.c_void_p(argmax.data_ptr()), C.c_void_p(d_agg.data_ptr()),
-                                                   V, H, m4 // 4, C.c_void_p(d_msgs.data_ptr()), st), "adkf_pna_aggregate_backward")
+                                                   V, H, m4 // 4, _addr(d_msgs), st), "adkf_pna_aggregate_backward")
         return d_msgs, None, None, None
 
 
@@ -391,8 +401,8 @@ class _MessagePass(torch.autograd.Function):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         ptr = lambda t: C.c_void_p(t.data_ptr())
         tab = _MessageFunction._table(plan, weights, biases)
-        _lib.check(lib.adkf_msg_forward(ptr(x), C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim, ptr(msgs), st), "adkf_msg_forward")
-        _lib.check(lib.adkf_pna_aggregate(ptr(msgs), ptr(plan.perm), ptr(plan.rowptr), V, H, m, ptr(agg), ptr(argmax), st), "adkf_pna_aggregate")
+        _lib.check(lib.adkf_msg_forward(ptr(x), C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim, _addr(msgs), st), "adkf_msg_forward")
+        _lib.check(lib.adkf_pna_aggregate(_addr(msgs), _addr(plan.perm), ptr(plan.rowptr), V, H, m, ptr(agg), ptr(argmax), st), "adkf_pna_aggregate")
         ctx.save_for_backward(x, msgs, agg, argmax, *weights)
         ctx.plan, ctx.dims, ctx.n_et = plan, (H, in_dim, out_dim), n_et
         ctx.mark_non_differentiable(argmax, msgs)
@@ -415,7 +425,7 @@ class _MessagePass(torch.autograd.Function):
         if E_all > 0:
             _lib.check(lib.adkf_pna_aggregate_backward_relu(ptr(msgs), ptr(plan.perm), ptr(plan.rowptr), ptr(agg), ptr(argmax), ptr(d_agg),
                                                             V, H, m, ptr(d_pre), st), "adkf_pna_aggregate_backward_relu")
-        dcat = torch.empty(max(E_all, 1), H, 2 * in_dim, dtype=torch.float32, device=dev)
+        dcat = torch.empty(E_all, H, 2 * in_dim, dtype=torch.float32, device=dev)
         dW_all = [torch.empty_like(w) for w in weights]
         db_all = torch.empty(n_et, H, out_dim, dtype=torch.float32, device=dev)
         dbs = [db_all[et] for et in range(n_et)]
@@ -423,9 +433,9 @@ class _MessagePass(torch.autograd.Function):
         need = int(lib.adkf_msg_backward_scratch_bytes(C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim))
         scratch = torch.empty(max(need, 4) // 4, dtype=torch.float32, device=dev)
         dx = torch.empty_like(x)
-        _lib.check(lib.adkf_msg_backward(ptr(x), C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim, None, ptr(d_pre),
-                                         ptr(plan.perm_src), ptr(plan.rowptr_src), ptr(plan.perm), ptr(plan.rowptr), V,
-                                         ptr(dcat), ptr(dx), ptr(scratch), scratch.numel() * 4, st), "adkf_msg_backward")
+        _lib.check(lib.adkf_msg_backward(ptr(x), C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim, None, _addr(d_pre),
+                                         _addr(plan.perm_src), ptr(plan.rowptr_src), _addr(plan.perm), ptr(plan.rowptr), V,
+                                         _addr(dcat), ptr(dx), ptr(scratch), scratch.numel() * 4, st), "adkf_msg_backward")
         return (dx, None, None, None, None, *dW_all, *dbs)
 
 

@@ -333,7 +333,10 @@ int adkf_ift_hypergrad_cg(const adkf_batch_t* b, const float* phi, int32_t flags
  * rowptr_* [V + 1]); every edge type's dW [H, 2 in, out] and db [H, out] are sums over fixed chunks of its edges (partials in
  * `scratch`, at least adkf_msg_backward_scratch_bytes() bytes), added in a fixed order.  Nothing needs initialising; an edge type
  * without edges gets exact zeros.  msgs = NULL in the backward: d_msgs is already the gradient in front of the ReLU
- * (adkf_pna_aggregate_backward_relu below) and no mask is applied. */
+ * (adkf_pna_aggregate_backward_relu below) and no mask is applied.
+ * A batch without a single edge (E_all = 0) is legal: nothing of msgs / d_msgs / dcat / perm_* is read or written, the forward
+ * launches nothing, the backward writes zeros to every dW, db and dx.  The pointers must still be non-NULL (a NULL argument is
+ * ADKF_E_BADARG here and in adkf_pna_aggregate*): a caller whose empty tensors have no address passes any valid one. */
 typedef struct adkf_msg_et {
     const int64_t* src; /* [E] source node of every edge */
     const int64_t* tgt; /* [E] target node */
@@ -404,6 +407,8 @@ int adkf_pna_aggregate_backward_relu(const float* msgs, const int64_t* perm, con
 /* a1 (the element-wise middle of GNNBlock.forward, fs_mol/modules/gnn.py:477-515, between the output projection of the message
  * passing and the BOOM MLP):   new = p0 + amp[v] p1 + att[v] p2 + bias  (p = [p0 | p1 | p2] [V, 3 hid]: the projected unscaled
  * aggregates; amp / att [V]: the PNA scalers),   x1 = x + alpha new  (ReZero),   h = LayerNorm(x1; gamma, beta, eps).
+ * x1 is formed as ((p0 + amp p1) + att p2) + bias, then x + alpha new, every product and every sum rounded on its own (no fused
+ * multiply-add): bit for bit the numbers of the float32 PyTorch expression of adkf_ift_amd/gnn.py::GNNBlock.
  * Outputs x1, h [V, hid] and the row statistics mu, rstd [V] the backward needs.  hid a multiple of 64, at most 256 (else
  * ADKF_E_SIZE: the caller keeps its own path).  The backward takes the gradients arriving at x1 (g_x1) and h (g_h) and writes d_p
  * [V, 3 hid], d_x [V, hid] and the parameter gradients d_bias, d_gamma, d_beta [hid], d_alpha [1], reduced over the nodes in a fixed

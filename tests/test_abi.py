@@ -154,3 +154,90 @@ def test_entry_points_fail_cleanly_without_a_device(lib, ns, nq):
         opt = _lib.FitOptions(5, 1, 1e-5, 2.22e-9, None, None)
         assert lib.adkf_fit(C.byref(b), p(phi), C.byref(opt), p(f), p(l0), None, p(info), p(ws), nb, None) == -4
     assert b"device" in lib.adkf_last_hip_error() or lib.adkf_last_hip_error()
+
+
+# ---- the GNN entries (csrc/pna.h, csrc/block.h, csrc/readout.h): rejected arguments return before any launch -----------------------
+_E_BADARG, _E_SIZE, _E_WORKSPACE = -1, -2, -3
+
+
+def _dummy(n):
+    """n distinct non-null addresses that are never dereferenced: every call below must return from its argument checks."""
+    import ctypes as C
+    return [C.c_void_p(4096 + 64 * i) for i in range(n)]
+
+
+def _msg_table(Es, backward):
+    import ctypes as C
+
+    from adkf_ift_amd import _lib
+    tab = (_lib.MsgEt * len(Es))()
+    for et, E in enumerate(Es):
+        tab[et].src, tab[et].tgt, tab[et].W = 4096, 8192, 12288
+        tab[et].bias = None if backward else 16384
+        tab[et].dW, tab[et].db = (20480, 24576) if backward else (None, None)
+        tab[et].E = E
+    return C.cast(tab, C.c_void_p), tab
+
+
+def test_block_combine_rejects_unsupported_widths_and_a_short_scratch(lib):
+    d = _dummy(20)
+    for hid in (100, 320):
+        assert lib.adkf_block_combine(*d[:8], 1e-5, 8, hid, *d[8:12], None) == _E_SIZE
+        assert lib.adkf_block_combine_backward(*d[:11], 8, hid, *d[11:18], 1 << 30, None) == _E_SIZE
+    for V, hid in ((8, 64), (129, 256)):
+        need = lib.adkf_block_combine_scratch_bytes(V, hid)
+        assert need == 4 * ((V + 127) // 128) * (3 * hid + 1)
+        assert lib.adkf_block_combine_backward(*d[:11], V, hid, *d[11:18], need - 1, None) == _E_WORKSPACE
+
+
+def test_readout_pooling_rejects_shapes_beyond_its_budgets(lib):
+    d = _dummy(24)
+    V, G = 10, 2
+    assert lib.adkf_readout_pool(*d[:7], V, G, 65, 4, 16, *d[7:13], None) == _E_BADARG
+    for nh, K, ldh, D in ((65, 64, 64, 16), (4, 1025, 1025, 16), (4, 64, 63, 16), (4, 64, 64, 2049)):
+        assert lib.adkf_readout_pool_hidden(*d[:4], ldh, *d[4:7], V, G, nh, K, D, *d[7:15], None) == _E_BADARG, (nh, K, ldh, D)
+        assert lib.adkf_readout_pool_hidden_backward(*d[:2], ldh, *d[2:11], V, G, nh, K, D, *d[11:16], None) == _E_BADARG, (nh, K, ldh, D)
+
+
+def test_message_entries_reject_bad_tables_and_a_short_scratch(lib):
+    d = _dummy(12)
+    H, inn, out = 3, 5, 7
+    for backward in (False, True):
+        for Es, n_et in (((10, 10, 10, 10, 10), 5), ((10, -1), 2)):
+            ptr, keep = _msg_table(Es, backward)
+            if backward:
+                rc = lib.adkf_msg_backward(d[0], ptr, n_et, H, inn, out, d[1], d[2], d[3], d[4], d[5], d[6], 50, d[7], d[8], d[9], 1 << 30, None)
+            else:
+                rc = lib.adkf_msg_forward(d[0], ptr, n_et, H, inn, out, d[1], None)
+            assert rc == _E_BADARG, (backward, Es)
+    ptr, keep = _msg_table((513, 0, 10), True)
+    need = lib.adkf_msg_backward_scratch_bytes(ptr, 3, H, inn, out)
+    assert need > 0
+    assert lib.adkf_msg_backward(d[0], ptr, 3, H, inn, out, d[1], d[2], d[3], d[4], d[5], d[6], 50, d[7], d[8], d[9], need - 1, None) == _E_WORKSPACE
+    assert lib.adkf_msg_backward(d[0], ptr, 3, H, inn, out, d[1], d[2], d[3], d[4], d[5], d[6], 50, d[7], d[8], None, 0, None) == _E_WORKSPACE
+
+
+def test_message_forward_without_any_edge_launches_nothing(lib):
+    """A batch of single-atom graphs: every edge type is empty, nothing is launched and the call succeeds - with or without a device.
+    (adkf_ift_amd/gnn.py passes one unused row where the empty message tensor has no address.)"""
+    d = _dummy(2)
+    ptr, keep = _msg_table((0, 0, 0), False)
+    assert lib.adkf_msg_forward(d[0], ptr, 3, 4, 4, 18, d[1], None) == 0
+    assert lib.adkf_msg_forward(d[0], ptr, 3, 4, 4, 18, None, None) == _E_BADARG     # a missing output is still a bad argument
+
+
+def test_message_backward_chunking_is_a_function_of_E_alone(lib):
+    """scratch = 4 sum_et nsplit(E_et) (2 H in out + H out) bytes with nsplit(E) = ceil(E / chunk), chunk = max(512, ceil(E / 64) rounded up
+    to a multiple of 32): one partial of d W | d b per chunk (csrc/pna.h)."""
+    nsplit = {0: 0, 1: 1, 512: 1, 513: 2, 4100: 9, 32768: 64, 32769: 61}
+    for E, n in nsplit.items():
+        chunk = max(512, -(-(-(-E // 64)) // 32) * 32)
+        assert n == (-(-E // chunk) if E > 0 else 0)
+    for H, inn, out in ((3, 5, 7), (4, 32, 192)):
+        per = 2 * H * inn * out + H * out
+        for E, n in nsplit.items():
+            ptr, keep = _msg_table((E,), True)
+            assert lib.adkf_msg_backward_scratch_bytes(ptr, 1, H, inn, out) == 4 * n * per, E
+        for Es in ((0, 1, 512, 513), (4100, 32768, 32769), (32769, 0, 4100, 513)):
+            ptr, keep = _msg_table(Es, True)
+            assert lib.adkf_msg_backward_scratch_bytes(ptr, len(Es), H, inn, out) == 4 * sum(nsplit[E] for E in Es) * per, Es
