@@ -143,6 +143,17 @@ def load():
     return lib
 
 
+def ptr(t):
+    """Device address of tensor ``t`` for a C entry; ``None`` (an output or input not asked for) stays ``None``."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(device) -> C.c_void_p:
+    """torch's current stream on ``device``: every entry launches on the stream the caller's tensors are ordered on."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 def check(rc: int, what: str):
     if rc != 0:
         detail = f" ({_lib.adkf_last_hip_error().decode()})" if rc == -4 and _lib is not None else ""

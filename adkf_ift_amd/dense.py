@@ -5,11 +5,12 @@ respect to the input; the weight gradient (a reduction over all rows: another op
 ``linear(x, weight, bias)`` is ``F.linear`` for every shape; it takes the HIP kernel where that pays - float32 CUDA tensors, at least
 ``MIN_ROWS`` rows, contraction and output widths that are multiples of 32 and at least ``MIN_K`` / ``MIN_N`` - and ``F.linear`` otherwise.
 ``ADKF_X3_DENSE=0`` (read at import) sends everything to ``F.linear`` for A/B runs."""
-import ctypes as C
 import os
 
 import torch
 import torch.nn.functional as F
+
+from . import _lib
 
 ENABLED = os.environ.get("ADKF_X3_DENSE", "1") != "0"
 # the weight gradient on the BF16 pipe as well (k_dense3_tn): measured EQUAL to the library GEMM on the C3 step (51.0 - 51.1 ms either way,
@@ -21,51 +22,42 @@ MIN_ROWS, MIN_K, MIN_N = 4096, 512, 128   # measured at C3 (tools/r05_dense.sh a
 
 def _split(w: torch.Tensor) -> torch.Tensor:
     """[rows, K] float32 -> planes [3, rows, K] of bfloat16 bit patterns (their sum is w exactly)."""
-    from . import _lib
     lib = _lib.load()
     w = w.contiguous()
     planes = torch.empty((3,) + tuple(w.shape), dtype=torch.int16, device=w.device)
-    st = C.c_void_p(torch.cuda.current_stream(w.device).cuda_stream)
-    _lib.check(lib.adkf_split_planes(C.c_void_p(w.data_ptr()), C.c_void_p(planes.data_ptr()), w.shape[0], w.shape[1], st), "adkf_split_planes")
+    _lib.check(lib.adkf_split_planes(_lib.ptr(w), _lib.ptr(planes), w.shape[0], w.shape[1], _lib.stream(w.device)), "adkf_split_planes")
     return planes
 
 
 def _split_t(w: torch.Tensor) -> torch.Tensor:
     """[K, N] float32 (a weight as ``x @ w`` takes it) -> planes [3, N, K]: the planes of w^T without forming w^T."""
-    from . import _lib
     lib = _lib.load()
     w = w.contiguous()
     K, N = w.shape
     planes = torch.empty((3, N, K), dtype=torch.int16, device=w.device)
-    st = C.c_void_p(torch.cuda.current_stream(w.device).cuda_stream)
-    _lib.check(lib.adkf_split_planes_t(C.c_void_p(w.data_ptr()), C.c_void_p(planes.data_ptr()), K, N, st), "adkf_split_planes_t")
+    _lib.check(lib.adkf_split_planes_t(_lib.ptr(w), _lib.ptr(planes), K, N, _lib.stream(w.device)), "adkf_split_planes_t")
     return planes
 
 
 def _dense(x: torch.Tensor, planes: torch.Tensor, bias, N: int) -> torch.Tensor:
-    from . import _lib
     lib = _lib.load()
     M, K = x.shape
     y = torch.empty(M, N, dtype=torch.float32, device=x.device)
-    st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(lib.adkf_dense_forward(C.c_void_p(x.data_ptr()), x.stride(0), C.c_void_p(planes.data_ptr()),
-                                      C.c_void_p(bias.data_ptr()) if bias is not None else None, C.c_void_p(y.data_ptr()), N, M, N, K, st),
-               "adkf_dense_forward")
+    _lib.check(lib.adkf_dense_forward(_lib.ptr(x), x.stride(0), _lib.ptr(planes), _lib.ptr(bias), _lib.ptr(y), N, M, N, K,
+                                      _lib.stream(x.device)), "adkf_dense_forward")
     return y
 
 
 def _weight_grad(g: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     """g^T x on the BF16 pipe (csrc/dense_x3.h::k_dense3_tn): row ranges, partial products added in a fixed order."""
-    from . import _lib
     lib = _lib.load()
     M, N = g.shape
     K = x.shape[1]
     dw = torch.empty(N, K, dtype=torch.float32, device=g.device)
     need = lib.adkf_dense_weight_grad_scratch_bytes(M, N, K)
     scratch = torch.empty(need, dtype=torch.uint8, device=g.device)
-    st = C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
-    _lib.check(lib.adkf_dense_weight_grad(C.c_void_p(g.data_ptr()), g.stride(0), C.c_void_p(x.data_ptr()), x.stride(0), C.c_void_p(dw.data_ptr()),
-                                          M, N, K, C.c_void_p(scratch.data_ptr()), need, st), "adkf_dense_weight_grad")
+    _lib.check(lib.adkf_dense_weight_grad(_lib.ptr(g), g.stride(0), _lib.ptr(x), x.stride(0), _lib.ptr(dw),
+                                          M, N, K, _lib.ptr(scratch), need, _lib.stream(g.device)), "adkf_dense_weight_grad")
     return dw
 
 

@@ -30,7 +30,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import dense
+from . import dense, gnn_ops
 
 SMALL_NUMBER = 1e-7
 _FUSED_BLOCK = __import__("os").environ.get("ADKF_GNN_FUSED_BLOCK", "1") != "0"   # diagnostics: 0 keeps the PyTorch ops in the middle of a block
@@ -211,6 +211,11 @@ class TowerMessagePassing(nn.Module):
         attenuate scalers into the output projection (GNNBlock) instead of materialising the [V, H * 12m] concatenation."""
         V, H, m = x.shape[0], self.H, self.msg
         xt = x.view(V, H, self.in_dim)
+
+        def scaled(agg):   # the PNA scalers: identity | amplify | attenuate (fs_mol/modules/gnn.py:244-251)
+            amp, att = plan.amplify.unsqueeze(-1).to(x.dtype), plan.attenuate.unsqueeze(-1).to(x.dtype)
+            return torch.cat((agg, amp * agg, att * agg), dim=2)
+
         if x.is_cuda and x.dtype == torch.float32 and self.depth == 1 and self.kind != "plain":
             # GPU fast path (csrc/pna.h): per edge type ONE batched MFMA GEMM that gathers source / target states on the fly
             # and applies bias + ReLU in its epilogue, then ONE aggregation kernel; no fallback here - a missing library raises
@@ -224,8 +229,7 @@ class TowerMessagePassing(nn.Module):
             if self.capture_argmax is not None:
                 self.capture_argmax.append(amax)
             if self.kind == "pna" and scale:
-                amp, att = plan.amplify.unsqueeze(-1).to(x.dtype), plan.attenuate.unsqueeze(-1).to(x.dtype)
-                agg = torch.cat((agg, amp * agg, att * agg), dim=2)
+                agg = scaled(agg)
             return agg.reshape(V, -1)
         msgs = []
         for et in range(len(plan.srcs)):
@@ -247,8 +251,7 @@ class TowerMessagePassing(nn.Module):
             # index and scatter launches below per layer; no fallback on the GPU: a missing library raises
             agg, _ = _PNAAggregate.apply(msgs.contiguous(), plan.perm, plan.rowptr, V)
             if self.kind == "pna":
-                amp, att = plan.amplify.unsqueeze(-1).to(x.dtype), plan.attenuate.unsqueeze(-1).to(x.dtype)
-                agg = torch.cat((agg, amp * agg, att * agg), dim=2)
+                agg = scaled(agg)
             return agg.reshape(V, -1)
         s_sum = x.new_zeros(V, H, m).index_add_(0, tg, msgs[..., :m])
         mean_msgs = msgs[..., m:2 * m]
@@ -259,124 +262,45 @@ class TowerMessagePassing(nn.Module):
         s_max = x.new_zeros(V, H, m).scatter_reduce_(0, idx, msgs[..., 2 * m:3 * m], reduce="amax", include_self=False)
         agg = torch.cat((s_sum, s_mean, s_std, s_max), dim=2)                  # [V, H, 4m], tower-major like the reference cat
         if self.kind == "pna" and scale:
-            amp, att = plan.amplify.unsqueeze(-1).to(x.dtype), plan.attenuate.unsqueeze(-1).to(x.dtype)
-            agg = torch.cat((agg, amp * agg, att * agg), dim=2)                # gnn.py:244-251
+            agg = scaled(agg)
         return agg.reshape(V, -1)
 
 
-def _addr(t: torch.Tensor):
-    """Device address of ``t`` for a C entry.  A tensor without elements (the message list of a batch without a single edge, or
-    of single-atom graphs only) has the address 0, which the entries reject as a missing argument: such a list is passed as one
-    unused row instead - the kernels read nothing of it (every segment is empty) and still write what belongs to the nodes."""
-    import ctypes as C
-    if t.numel() == 0:
-        t = t.new_empty((1,) + tuple(t.shape[1:]))
-    return C.c_void_p(t.data_ptr())
-
-
 class _MessageFunction(torch.autograd.Function):
-    """relu(cat(x[src], x[tgt]) W_et + b_et) for every edge type and tower -> [E_all, H, out] (``adkf_msg_forward`` /
-    ``adkf_msg_backward``, csrc/pna.h: ONE launch of each kind for all edge types).  x [V, H*in] float32 contiguous; weights[et]
+    """relu(cat(x[src], x[tgt]) W_et + b_et) for every edge type and tower -> [E_all, H, out] (``gnn_ops.msg_forward`` /
+    ``msg_backward``, csrc/pna.h: ONE launch of each kind for all edge types).  x [V, H*in] float32 contiguous; weights[et]
     [H, 2 in, out], biases[et] [H, out]."""
 
     @staticmethod
-    def _table(plan, weights, biases=None, dWs=None, dbs=None):
-        import ctypes as C
-
-        from . import _lib
-        n_et = len(weights)
-        tab = (_lib.MsgEt * n_et)()
-        for et in range(n_et):
-            tab[et].src, tab[et].tgt = plan.srcs[et].data_ptr(), plan.tgts[et].data_ptr()
-            tab[et].W = weights[et].data_ptr()
-            tab[et].bias = biases[et].data_ptr() if biases is not None else None
-            tab[et].dW = dWs[et].data_ptr() if dWs is not None else None
-            tab[et].db = dbs[et].data_ptr() if dbs is not None else None
-            tab[et].E = int(plan.srcs[et].shape[0])
-        return tab
-
-    @staticmethod
     def forward(ctx, x, plan, H, in_dim, out_dim, *params):
-        import ctypes as C
-
-        from . import _lib
-        lib = _lib.load()
         n_et = len(params) // 2
         weights, biases = [w.contiguous() for w in params[:n_et]], [b.contiguous() for b in params[n_et:]]
-        E_all = int(plan.all_tgts.shape[0])
-        msgs = torch.empty(E_all, H, out_dim, dtype=torch.float32, device=x.device)
-        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        tab = _MessageFunction._table(plan, weights, biases)
-        _lib.check(lib.adkf_msg_forward(C.c_void_p(x.data_ptr()), C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim,
-                                        _addr(msgs), st), "adkf_msg_forward")
+        msgs = gnn_ops.msg_forward(x, plan, H, in_dim, out_dim, weights, biases)
         ctx.save_for_backward(x, msgs, *weights)
         ctx.plan, ctx.dims, ctx.n_et = plan, (H, in_dim, out_dim), n_et
         return msgs
 
     @staticmethod
     def backward(ctx, d_msgs):
-        import ctypes as C
-
-        from . import _lib
-        lib = _lib.load()
         x, msgs, *weights = ctx.saved_tensors
-        plan, (H, in_dim, out_dim), n_et = ctx.plan, ctx.dims, ctx.n_et
-        d_msgs = d_msgs.contiguous()
-        dev = x.device
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        E_all = int(plan.all_tgts.shape[0])
-        # no floating-point atomics anywhere (csrc/pna.h): d cat is written once per edge and d x gathered over each node's
-        # edge lists; d W / d b are per-chunk partials summed in a fixed order - every output element is written, none pre-filled
-        dcat = torch.empty(E_all, H, 2 * in_dim, dtype=torch.float32, device=dev)
-        dW_all = [torch.empty_like(w) for w in weights]
-        db_all = torch.empty(n_et, H, out_dim, dtype=torch.float32, device=dev)
-        dbs = [db_all[et] for et in range(n_et)]
-        tab = _MessageFunction._table(plan, weights, None, dW_all, dbs)
-        need = int(lib.adkf_msg_backward_scratch_bytes(C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim))
-        scratch = torch.empty(max(need, 4) // 4, dtype=torch.float32, device=dev)
-        dx = torch.empty_like(x)
-        _lib.check(lib.adkf_msg_backward(ptr(x), C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim, _addr(msgs), _addr(d_msgs),
-                                         _addr(plan.perm_src), ptr(plan.rowptr_src), _addr(plan.perm), ptr(plan.rowptr), x.shape[0],
-                                         _addr(dcat), ptr(dx), ptr(scratch), scratch.numel() * 4, st), "adkf_msg_backward")
+        dx, dW_all, dbs = gnn_ops.msg_backward(x, ctx.plan, *ctx.dims, weights, msgs, d_msgs.contiguous())
         return (dx, None, None, None, None, *dW_all, *dbs)
 
 
 class _PNAAggregate(torch.autograd.Function):
-    """[E, H, 3m] messages -> [V, H, 4m] (sum | mean | std | max) through ``adkf_pna_aggregate`` (csrc/pna.h)."""
+    """[E, H, 3m] messages -> [V, H, 4m] (sum | mean | std | max) through ``gnn_ops.pna_aggregate`` (csrc/pna.h)."""
 
     @staticmethod
     def forward(ctx, msgs, perm, rowptr, V):
-        import ctypes as C
-
-        from . import _lib
-        lib = _lib.load()
-        E, H, m3 = msgs.shape
-        m = m3 // 3
-        agg = torch.empty(V, H, 4 * m, dtype=torch.float32, device=msgs.device)
-        argmax = torch.empty(V, H, m, dtype=torch.int32, device=msgs.device)
-        st = C.c_void_p(torch.cuda.current_stream(msgs.device).cuda_stream)
-        _lib.check(lib.adkf_pna_aggregate(_addr(msgs), _addr(perm), C.c_void_p(rowptr.data_ptr()),
-                                          V, H, m, C.c_void_p(agg.data_ptr()), C.c_void_p(argmax.data_ptr()), st), "adkf_pna_aggregate")
+        agg, argmax = gnn_ops.pna_aggregate(msgs, perm, rowptr, V)
         ctx.save_for_backward(msgs, perm, rowptr, agg, argmax)
         ctx.mark_non_differentiable(argmax)
         return agg, argmax
 
     @staticmethod
     def backward(ctx, d_agg, _d_argmax=None):
-        import ctypes as C
-
-        from . import _lib
-        lib = _lib.load()
         msgs, perm, rowptr, agg, argmax = ctx.saved_tensors
-        V, H, m4 = agg.shape
-        d_agg = d_agg.contiguous()
-        d_msgs = torch.empty_like(msgs)
-        st = C.c_void_p(torch.cuda.current_stream(msgs.device).cuda_stream)
-        _lib.check(lib.adkf_pna_aggregate_backward(_addr(msgs), _addr(perm), C.c_void_p(rowptr.data_ptr()),
-                                                   C.c_void_p(agg.data_ptr()), C.c_void_p(argmax.data_ptr()), C.c_void_p(d_agg.data_ptr()),
-                                                   V, H, m4 // 4, _addr(d_msgs), st), "adkf_pna_aggregate_backward")
-        return d_msgs, None, None, None
+        return gnn_ops.pna_aggregate_backward(msgs, perm, rowptr, agg, argmax, d_agg.contiguous()), None, None, None
 
 
 class _MessagePass(torch.autograd.Function):
@@ -387,22 +311,10 @@ class _MessagePass(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, plan, H, in_dim, out_dim, *params):
-        import ctypes as C
-
-        from . import _lib
-        lib = _lib.load()
         n_et = len(params) // 2
         weights, biases = [w.contiguous() for w in params[:n_et]], [b.contiguous() for b in params[n_et:]]
-        E_all, V, m = int(plan.all_tgts.shape[0]), x.shape[0], out_dim // 3
-        dev = x.device
-        msgs = torch.empty(E_all, H, out_dim, dtype=torch.float32, device=dev)
-        agg = torch.empty(V, H, 4 * m, dtype=torch.float32, device=dev)
-        argmax = torch.empty(V, H, m, dtype=torch.int32, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        tab = _MessageFunction._table(plan, weights, biases)
-        _lib.check(lib.adkf_msg_forward(ptr(x), C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim, _addr(msgs), st), "adkf_msg_forward")
-        _lib.check(lib.adkf_pna_aggregate(_addr(msgs), _addr(plan.perm), ptr(plan.rowptr), V, H, m, ptr(agg), ptr(argmax), st), "adkf_pna_aggregate")
+        msgs = gnn_ops.msg_forward(x, plan, H, in_dim, out_dim, weights, biases)
+        agg, argmax = gnn_ops.pna_aggregate(msgs, plan.perm, plan.rowptr, x.shape[0])
         ctx.save_for_backward(x, msgs, agg, argmax, *weights)
         ctx.plan, ctx.dims, ctx.n_et = plan, (H, in_dim, out_dim), n_et
         ctx.mark_non_differentiable(argmax, msgs)
@@ -410,78 +322,34 @@ class _MessagePass(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_agg, _d_argmax=None, _d_msgs=None):
-        import ctypes as C
-
-        from . import _lib
-        lib = _lib.load()
         x, msgs, agg, argmax, *weights = ctx.saved_tensors
-        plan, (H, in_dim, out_dim), n_et = ctx.plan, ctx.dims, ctx.n_et
-        dev, V, m = x.device, x.shape[0], out_dim // 3
-        d_agg = d_agg.contiguous()
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        E_all = int(plan.all_tgts.shape[0])
-        d_pre = torch.empty_like(msgs)
-        if E_all > 0:
-            _lib.check(lib.adkf_pna_aggregate_backward_relu(ptr(msgs), ptr(plan.perm), ptr(plan.rowptr), ptr(agg), ptr(argmax), ptr(d_agg),
-                                                            V, H, m, ptr(d_pre), st), "adkf_pna_aggregate_backward_relu")
-        dcat = torch.empty(E_all, H, 2 * in_dim, dtype=torch.float32, device=dev)
-        dW_all = [torch.empty_like(w) for w in weights]
-        db_all = torch.empty(n_et, H, out_dim, dtype=torch.float32, device=dev)
-        dbs = [db_all[et] for et in range(n_et)]
-        tab = _MessageFunction._table(plan, weights, None, dW_all, dbs)
-        need = int(lib.adkf_msg_backward_scratch_bytes(C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim))
-        scratch = torch.empty(max(need, 4) // 4, dtype=torch.float32, device=dev)
-        dx = torch.empty_like(x)
-        _lib.check(lib.adkf_msg_backward(ptr(x), C.cast(tab, C.c_void_p), n_et, H, in_dim, out_dim, None, _addr(d_pre),
-                                         _addr(plan.perm_src), ptr(plan.rowptr_src), _addr(plan.perm), ptr(plan.rowptr), V,
-                                         _addr(dcat), ptr(dx), ptr(scratch), scratch.numel() * 4, st), "adkf_msg_backward")
+        plan, d_agg = ctx.plan, d_agg.contiguous()
+        if plan.all_tgts.shape[0] > 0:
+            d_pre = gnn_ops.pna_aggregate_backward(msgs, plan.perm, plan.rowptr, agg, argmax, d_agg, relu=True)
+        else:
+            d_pre = torch.empty_like(msgs)     # not a single edge: no message to send a gradient to
+        dx, dW_all, dbs = gnn_ops.msg_backward(x, plan, *ctx.dims, weights, None, d_pre)
         return (dx, None, None, None, None, *dW_all, *dbs)
 
 
 class _BlockCombine(torch.autograd.Function):
     """new = p0 + amp p1 + att p2 + bias;  x1 = x + alpha new;  h = LayerNorm(x1)  ->  (x1, h)   as one HIP kernel forward and one
-    backward (``adkf_block_combine``, csrc/block.h) instead of nine / ~twenty element-wise and reduction launches per block."""
+    backward (``gnn_ops.block_combine``, csrc/block.h) instead of nine / ~twenty element-wise and reduction launches per block."""
 
     @staticmethod
     def forward(ctx, p, x, amp, att, bias, alpha, gamma, beta, eps):
-        import ctypes as C
-
-        from . import _lib
-        lib = _lib.load()
-        V, hid = x.shape
         p, x, amp, att = p.contiguous(), x.contiguous(), amp.contiguous(), att.contiguous()
         bias, gamma, beta = bias.contiguous(), gamma.contiguous(), beta.contiguous()
-        x1, h = torch.empty_like(x), torch.empty_like(x)
-        mu = torch.empty(V, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mu)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        st = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(lib.adkf_block_combine(ptr(p), ptr(x), ptr(amp), ptr(att), ptr(bias), ptr(alpha), ptr(gamma), ptr(beta), float(eps), V, hid,
-                                          ptr(x1), ptr(h), ptr(mu), ptr(rstd), st), "adkf_block_combine")
+        x1, h, mu, rstd = gnn_ops.block_combine(p, x, amp, att, bias, alpha, gamma, beta, eps)
         ctx.save_for_backward(p, x1, amp, att, bias, alpha, gamma, mu, rstd)
         return x1, h
 
     @staticmethod
     def backward(ctx, g_x1, g_h):
-        import ctypes as C
-
-        from . import _lib
-        lib = _lib.load()
         p, x1, amp, att, bias, alpha, gamma, mu, rstd = ctx.saved_tensors
-        V, hid = x1.shape
-        dev = x1.device
         g_x1 = torch.zeros_like(x1) if g_x1 is None else g_x1.contiguous()
         g_h = torch.zeros_like(x1) if g_h is None else g_h.contiguous()
-        d_p, d_x = torch.empty_like(p), torch.empty_like(x1)
-        d_bias, d_gamma, d_beta, d_alpha = torch.empty_like(bias), torch.empty_like(gamma), torch.empty_like(gamma), torch.empty_like(alpha)
-        need = int(lib.adkf_block_combine_scratch_bytes(V, hid))
-        scratch = torch.empty(need // 4, dtype=torch.float32, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.adkf_block_combine_backward(ptr(p), ptr(x1), ptr(amp), ptr(att), ptr(bias), ptr(alpha), ptr(gamma), ptr(mu), ptr(rstd),
-                                                   ptr(g_x1), ptr(g_h), V, hid, ptr(d_p), ptr(d_x), ptr(d_bias), ptr(d_alpha), ptr(d_gamma),
-                                                   ptr(d_beta), ptr(scratch), need, st), "adkf_block_combine_backward")
+        d_p, d_x, d_bias, d_alpha, d_gamma, d_beta = gnn_ops.block_combine_backward(p, x1, amp, att, bias, alpha, gamma, mu, rstd, g_x1, g_h)
         return d_p, d_x, None, None, d_bias, d_alpha, d_gamma, d_beta, None
 
 
@@ -576,86 +444,49 @@ def _segment_softmax(scores: torch.Tensor, index: torch.Tensor, num_segments: in
     return ex / den[index]
 
 
+def _graph_segments(node_to_graph: torch.Tensor, num_graphs: int):
+    """(perm, rowptr): the nodes by graph, for a batch that carries no plan (three tiny launches and a host synchronisation)."""
+    counts = torch.bincount(node_to_graph, minlength=num_graphs)
+    return torch.argsort(node_to_graph, stable=True), torch.cat((counts.new_zeros(1), torch.cumsum(counts, 0)))
+
+
 class _ReadoutPool(torch.autograd.Function):
-    """Per-graph pooling of the combined read-out on the GPU (``adkf_readout_pool`` / ``_backward``, csrc/readout.h): segment
+    """Per-graph pooling of the combined read-out on the GPU (``gnn_ops.readout_pool`` / ``_backward``, csrc/readout.h): segment
     softmax + weighted mean, sigmoid-weighted sum and max in ONE kernel, each per-graph sum in the fixed order of the graph's
     node list; the backward writes every element once.  Bit-reproducible, unlike ``index_add_`` and the backward of a gather."""
 
     @staticmethod
     def forward(ctx, s_mean, v_mean, s_sum, v_sum, emb, node_to_graph, num_graphs, nh, hd, perm=None, rowptr=None):
-        import ctypes as C
-
-        from . import _lib
-        lib = _lib.load()
-        dev = emb.device
         V, D, G = emb.shape[0], emb.shape[1], int(num_graphs)
         s_mean, v_mean, s_sum, v_sum, emb = (t.contiguous() for t in (s_mean, v_mean, s_sum, v_sum, emb))
         n2g = node_to_graph.contiguous()
-        if perm is None or rowptr is None:      # (no plan on the batch: three tiny launches and a host synchronisation)
-            counts = torch.bincount(n2g, minlength=G)
-            perm = torch.argsort(n2g, stable=True)
-            rowptr = torch.cat((counts.new_zeros(1), torch.cumsum(counts, 0)))
-        f32 = dict(dtype=torch.float32, device=dev)
-        w_mean, w_sum = torch.empty(V, nh, **f32), torch.empty(V, nh, **f32)
-        g_mean, g_sum, g_max = torch.empty(G, nh * hd, **f32), torch.empty(G, nh * hd, **f32), torch.empty(G, D, **f32)
-        argmax = torch.empty(G, D, dtype=torch.int32, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(lib.adkf_readout_pool(ptr(s_mean), ptr(v_mean), ptr(s_sum), ptr(v_sum), ptr(emb), ptr(perm), ptr(rowptr), V, G, nh, hd, D,
-                                         ptr(w_mean), ptr(w_sum), ptr(g_mean), ptr(g_sum), ptr(g_max), ptr(argmax), st), "adkf_readout_pool")
+        if perm is None or rowptr is None:
+            perm, rowptr = _graph_segments(n2g, G)
+        w_mean, w_sum, g_mean, g_sum, g_max, argmax = gnn_ops.readout_pool(s_mean, v_mean, s_sum, v_sum, emb, perm, rowptr, G, nh, hd)
         ctx.save_for_backward(v_mean, v_sum, w_mean, w_sum, g_mean, argmax, n2g)
         ctx.dims = (V, G, nh, hd, D)
         return g_mean, g_sum, g_max
 
     @staticmethod
     def backward(ctx, dg_mean, dg_sum, dg_max):
-        import ctypes as C
-
-        from . import _lib
-        lib = _lib.load()
-        v_mean, v_sum, w_mean, w_sum, g_mean, argmax, n2g = ctx.saved_tensors
-        V, G, nh, hd, D = ctx.dims
-        dev = v_mean.device
-        dg_mean, dg_sum, dg_max = dg_mean.contiguous(), dg_sum.contiguous(), dg_max.contiguous()
-        f32 = dict(dtype=torch.float32, device=dev)
-        d_s_mean, d_s_sum = torch.empty(V, nh, **f32), torch.empty(V, nh, **f32)
-        d_v_mean, d_v_sum, d_emb = torch.empty(V, nh * hd, **f32), torch.empty(V, nh * hd, **f32), torch.empty(V, D, **f32)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(lib.adkf_readout_pool_backward(ptr(v_mean), ptr(v_sum), ptr(w_mean), ptr(w_sum), ptr(g_mean), ptr(argmax), ptr(n2g),
-                                                  ptr(dg_mean), ptr(dg_sum), ptr(dg_max), V, G, nh, hd, D, ptr(d_s_mean), ptr(d_v_mean),
-                                                  ptr(d_s_sum), ptr(d_v_sum), ptr(d_emb), st), "adkf_readout_pool_backward")
+        d_s_mean, d_v_mean, d_s_sum, d_v_sum, d_emb = gnn_ops.readout_pool_backward(
+            *ctx.saved_tensors, dg_mean.contiguous(), dg_sum.contiguous(), dg_max.contiguous(), ctx.dims)
         return d_s_mean, d_v_mean, d_s_sum, d_v_sum, d_emb, None, None, None, None, None, None
 
 
 class _ReadoutPoolHidden(torch.autograd.Function):
-    """The same pooling taken BEFORE the last layer of the two value MLPs (``adkf_readout_pool_hidden`` / ``_backward``,
+    """The same pooling taken BEFORE the last layer of the two value MLPs (``gnn_ops.readout_pool_hidden`` / ``_backward``,
     csrc/readout.h): per graph and head the pooled hidden activations ``p[h, g, :] = sum_v w[v, h] r_v`` and the weight totals,
     so that the value layers multiply ``[G, K]`` matrices instead of ``[V, K]`` ones.  ``h_mean`` / ``h_sum`` may be column
     blocks of one activation tensor (row stride passed to the kernel: no copies).  Same order guarantees as ``_ReadoutPool``."""
 
     @staticmethod
     def forward(ctx, s_mean, h_mean, s_sum, h_sum, emb, num_graphs, nh, perm, rowptr):
-        import ctypes as C
-
-        from . import _lib
-        lib = _lib.load()
-        dev = emb.device
         V, D, G, K = emb.shape[0], emb.shape[1], int(num_graphs), h_mean.shape[1]
         s_mean, s_sum, emb = s_mean.contiguous(), s_sum.contiguous(), emb.contiguous()
-        if h_mean.stride(1) != 1 or h_sum.stride(1) != 1 or h_mean.stride(0) != h_sum.stride(0):
-            h_mean, h_sum = h_mean.contiguous(), h_sum.contiguous()
-        ldh = h_mean.stride(0) if V > 1 else K
-        f32 = dict(dtype=torch.float32, device=dev)
-        w_mean, w_sum = torch.empty(V, nh, **f32), torch.empty(V, nh, **f32)
-        p_mean, p_sum = torch.empty(nh, G, K, **f32), torch.empty(nh, G, K, **f32)
-        wtot_mean, wtot_sum = torch.empty(G, nh, **f32), torch.empty(G, nh, **f32)
-        g_max, argmax = torch.empty(G, D, **f32), torch.empty(G, D, dtype=torch.int32, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(lib.adkf_readout_pool_hidden(ptr(s_mean), ptr(h_mean), ptr(s_sum), ptr(h_sum), ldh, ptr(emb), ptr(perm), ptr(rowptr), V, G, nh,
-                                                K, D, ptr(w_mean), ptr(w_sum), ptr(p_mean), ptr(p_sum), ptr(wtot_mean), ptr(wtot_sum), ptr(g_max),
-                                                ptr(argmax), st), "adkf_readout_pool_hidden")
+        h_mean, h_sum, ldh = gnn_ops.shared_row_stride(h_mean, h_sum)
+        w_mean, w_sum, p_mean, p_sum, wtot_mean, wtot_sum, g_max, argmax = gnn_ops.readout_pool_hidden(
+            s_mean, h_mean, s_sum, h_sum, ldh, emb, perm, rowptr, G, nh)
         ctx.save_for_backward(h_mean, h_sum, w_mean, w_sum, argmax, perm, rowptr)
         ctx.dims = (V, G, nh, K, D, ldh)
         ctx.mark_non_differentiable(wtot_mean)
@@ -663,23 +494,8 @@ class _ReadoutPoolHidden(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dp_mean, dp_sum, _dwtot_mean, dwtot_sum, dg_max):
-        import ctypes as C
-
-        from . import _lib
-        lib = _lib.load()
-        h_mean, h_sum, w_mean, w_sum, argmax, perm, rowptr = ctx.saved_tensors
-        V, G, nh, K, D, ldh = ctx.dims
-        dev = w_mean.device
-        dp_mean, dp_sum, dwtot_sum, dg_max = dp_mean.contiguous(), dp_sum.contiguous(), dwtot_sum.contiguous(), dg_max.contiguous()
-        f32 = dict(dtype=torch.float32, device=dev)
-        d_s_mean, d_s_sum = torch.empty(V, nh, **f32), torch.empty(V, nh, **f32)
-        d_h_mean, d_h_sum, d_emb = torch.empty(V, K, **f32), torch.empty(V, K, **f32), torch.empty(V, D, **f32)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(lib.adkf_readout_pool_hidden_backward(ptr(h_mean), ptr(h_sum), ldh, ptr(w_mean), ptr(w_sum), ptr(argmax), ptr(perm), ptr(rowptr),
-                                                         ptr(dp_mean), ptr(dp_sum), ptr(dwtot_sum), ptr(dg_max), V, G, nh, K, D, ptr(d_s_mean),
-                                                         ptr(d_h_mean), ptr(d_s_sum), ptr(d_h_sum), ptr(d_emb), st),
-                   "adkf_readout_pool_hidden_backward")
+        d_s_mean, d_h_mean, d_s_sum, d_h_sum, d_emb = gnn_ops.readout_pool_hidden_backward(
+            *ctx.saved_tensors, dp_mean.contiguous(), dp_sum.contiguous(), dwtot_sum.contiguous(), dg_max.contiguous(), ctx.dims)
         return d_s_mean, d_h_mean, d_s_sum, d_h_sum, d_emb, None, None, None, None
 
 
@@ -722,9 +538,8 @@ class CombinedGraphReadout(nn.Module):
             if _POOL_HIDDEN and hid <= 1024 and node_embeddings.shape[1] <= 2048:   # (the kernels' register budgets, csrc/readout.h)
                 # pooling is linear in the last layer of the value MLPs: pool their HIDDEN activations per head, then nh products of
                 # [G, hid] x [hid, hd] instead of [V, hid] x [hid, nh hd] over all nodes (csrc/readout.h)
-                if not ok:      # (no plan on the batch: three tiny launches and a host synchronisation)
-                    counts = torch.bincount(node_to_graph_id, minlength=num_graphs)
-                    segs = (torch.argsort(node_to_graph_id, stable=True), torch.cat((counts.new_zeros(1), torch.cumsum(counts, 0))))
+                if not ok:
+                    segs = _graph_segments(node_to_graph_id, num_graphs)
                 p_mean, p_sum, wt_mean, wt_sum, g_max = _ReadoutPoolHidden.apply(self.mean_score_out(h_ms), h_mv, self.sum_score_out(h_ss), h_sv,
                                                                                  node_embeddings, num_graphs, self.nh, *segs)
                 g_mean = self._project_pooled(p_mean, wt_mean, self.mean_value_out)

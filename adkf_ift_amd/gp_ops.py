@@ -14,7 +14,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import KERNEL_MATERN52, KERNEL_RBF, Batch, FitOptions
+from ._lib import KERNEL_MATERN52, KERNEL_RBF, Batch, FitOptions, ptr, stream
 
 KERNELS = {"rbf": KERNEL_RBF, "RBF": KERNEL_RBF, "matern": KERNEL_MATERN52}
 REUSE_DIST = 1
@@ -38,10 +38,6 @@ def kernel_id(kernel) -> int:
 # (SURVEY App. A7).  On an fp32 objective of magnitude ~1 it means "stop when an accepted step does not lower f at all";
 # 1e-7 (one ulp) looked equivalent and was not: it stopped fits that were still creeping along the lengthscale valley.
 FTOL_DEFAULT = 2.22e-9
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _f32(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
@@ -136,8 +132,8 @@ class GPBatch:
         b = Batch()
         flags = int(self.flags) | (ARD if self.ard else 0)
         b.T, b.ns_max, b.nq_max, b.d, b.kernel, b.flags = self.T, self.ns, self.nq, self.d, self.kernel, flags
-        b.n_s, b.n_q = _ptr(self.n_s), _ptr(self.n_q)
-        b.Z_s, b.y_s, b.Z_q, b.y_q, b.priors = _ptr(self.Z_s), _ptr(self.y_s), _ptr(self.Z_q), _ptr(self.y_q), _ptr(self.priors)
+        b.n_s, b.n_q = ptr(self.n_s), ptr(self.n_q)
+        b.Z_s, b.y_s, b.Z_q, b.y_q, b.priors = ptr(self.Z_s), ptr(self.y_s), ptr(self.Z_q), ptr(self.y_q), ptr(self.priors)
         return b
 
     def workspace(self) -> Tuple[torch.Tensor, int]:
@@ -161,10 +157,6 @@ class GPBatch:
         return phi
 
 
-def _stream(dev) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _new(b: GPBatch, *shape, dtype=torch.float32):
     return torch.empty(*shape, dtype=dtype, device=b.device)
 
@@ -172,7 +164,7 @@ def _new(b: GPBatch, *shape, dtype=torch.float32):
 def check_info(info: torch.Tensor, what: str = "GP factorisation"):
     """Raises like gpytorch's NotPSDError would in the reference (SURVEY 8b error convention)."""
     lib = _lib.load()
-    rc = lib.adkf_check_info(_ptr(info), info.numel(), _stream(info.device))
+    rc = lib.adkf_check_info(ptr(info), info.numel(), stream(info.device))
     if rc > 0:
         code = int(info[rc - 1].item())
         if code >= 200000:   # ADKF_INFO_CG_BASE
@@ -189,7 +181,7 @@ def median_lengthscale(b: GPBatch) -> torch.Tensor:
     l0 = _new(b, b.T)
     ws, nb = b.workspace()
     cb = b.c_struct()
-    _lib.check(lib.adkf_median_lengthscale(C.byref(cb), _ptr(l0), _ptr(ws), nb, _stream(b.device)), "adkf_median_lengthscale")
+    _lib.check(lib.adkf_median_lengthscale(C.byref(cb), ptr(l0), ptr(ws), nb, stream(b.device)), "adkf_median_lengthscale")
     return l0
 
 
@@ -203,8 +195,8 @@ def init_params(Z_s: torch.Tensor, use_numeric_labels: bool = False, use_lengths
     phi, priors, l0 = _new(b, b.T, 3), _new(b, b.T, 4), _new(b, b.T)
     ws, nb = b.workspace()
     cb = b.c_struct()
-    _lib.check(lib.adkf_init_params(C.byref(cb), int(use_numeric_labels), int(use_lengthscale_prior), _ptr(phi),
-                                    _ptr(priors), _ptr(l0), _ptr(ws), nb, _stream(b.device)), "adkf_init_params")
+    _lib.check(lib.adkf_init_params(C.byref(cb), int(use_numeric_labels), int(use_lengthscale_prior), ptr(phi),
+                                    ptr(priors), ptr(l0), ptr(ws), nb, stream(b.device)), "adkf_init_params")
     return phi, priors, l0
 
 
@@ -216,8 +208,8 @@ def init_params_batch(b: GPBatch, use_numeric_labels: bool = False, use_lengthsc
     phi, l0 = _new(b, b.T, b.h), _new(b, b.T)
     ws, nb = b.workspace()
     cb = b.c_struct()
-    _lib.check(lib.adkf_init_params(C.byref(cb), int(use_numeric_labels), int(use_lengthscale_prior), _ptr(phi),
-                                    _ptr(b.priors), _ptr(l0), _ptr(ws), nb, _stream(b.device)), "adkf_init_params")
+    _lib.check(lib.adkf_init_params(C.byref(cb), int(use_numeric_labels), int(use_lengthscale_prior), ptr(phi),
+                                    ptr(b.priors), ptr(l0), ptr(ws), nb, stream(b.device)), "adkf_init_params")
     return phi, l0
 
 
@@ -230,8 +222,8 @@ def mll_value_grad(b: GPBatch, phi: torch.Tensor, want_grad_phi=True, want_dZ=Fa
     info = _new(b, b.T, dtype=torch.int32)
     ws, nb = b.workspace()
     cb = b.c_struct()
-    _lib.check(lib.adkf_mll_value_grad(C.byref(cb), _ptr(phi), _ptr(f), _ptr(g), _ptr(dZ), _ptr(info), _ptr(ws), nb,
-                                       _stream(b.device)), "adkf_mll_value_grad")
+    _lib.check(lib.adkf_mll_value_grad(C.byref(cb), ptr(phi), ptr(f), ptr(g), ptr(dZ), ptr(info), ptr(ws), nb,
+                                       stream(b.device)), "adkf_mll_value_grad")
     return f, g, dZ, info
 
 
@@ -252,8 +244,8 @@ def fit(b: GPBatch, phi0: torch.Tensor, max_evals: int = 200, gtol: float = 1e-5
                      events[0].cuda_event if events else None, events[1].cuda_event if events else None)
     ws, nb = b.workspace()
     cb = b.c_struct()
-    _lib.check(lib.adkf_fit(C.byref(cb), _ptr(phi), C.byref(opt), _ptr(f), _ptr(gn), _ptr(ne), _ptr(info), _ptr(ws), nb,
-                            _stream(b.device)), "adkf_fit")
+    _lib.check(lib.adkf_fit(C.byref(cb), ptr(phi), C.byref(opt), ptr(f), ptr(gn), ptr(ne), ptr(info), ptr(ws), nb,
+                            stream(b.device)), "adkf_fit")
     return phi, f, gn, ne, info
 
 
@@ -266,8 +258,8 @@ def predict(b: GPBatch, phi: torch.Tensor, want_var=True, want_cov=False):
     info = _new(b, b.T, dtype=torch.int32)
     ws, nb = b.workspace()
     cb = b.c_struct()
-    _lib.check(lib.adkf_predict(C.byref(cb), _ptr(phi), _ptr(mean), _ptr(var), _ptr(cov), _ptr(info), _ptr(ws), nb,
-                                _stream(b.device)), "adkf_predict")
+    _lib.check(lib.adkf_predict(C.byref(cb), ptr(phi), ptr(mean), ptr(var), ptr(cov), ptr(info), ptr(ws), nb,
+                                stream(b.device)), "adkf_predict")
     return mean, var, cov, info
 
 
@@ -331,8 +323,8 @@ def predict_marginal(b: GPBatch, phi: torch.Tensor, Zq: torch.Tensor, q_off: tor
     ws, nb = b.workspace()
     cb = b.c_struct()
     name = "adkf_predict_marginal_ard" if b.ard else "adkf_predict_marginal"
-    _lib.check(getattr(lib, name)(C.byref(cb), _ptr(phi), flags, _ptr(Zq), _ptr(q_off), rows, _ptr(best_f), _ptr(mean), _ptr(var),
-                                  _ptr(ei), _ptr(info), _ptr(ws), nb, _stream(b.device)), name)
+    _lib.check(getattr(lib, name)(C.byref(cb), ptr(phi), flags, ptr(Zq), ptr(q_off), rows, ptr(best_f), ptr(mean), ptr(var),
+                                  ptr(ei), ptr(info), ptr(ws), nb, stream(b.device)), name)
     return mean, var, ei, info
 
 
@@ -413,9 +405,9 @@ def predict_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, latent: bool
     flags = (_lib.PM_LATENT if latent else 0) | (_lib.PM_MAXIMIZE if maximize else 0) | (_lib.PM_SCORE_MEAN if score == "mean" else 0)
     ws, nb = b.workspace()
     cb = b.c_struct()
-    _lib.check(lib.adkf_predict_pool(C.byref(cb), _ptr(phi), flags, _ptr(X), rows, _ptr(best_f), _ptr(excl_idx), _ptr(excl_off),
-                                     _ptr(mean), _ptr(var), _ptr(ei), topk, _ptr(top_idx), _ptr(top_val), _ptr(info), _ptr(ws), nb,
-                                     _ptr(scratch), sb, _stream(b.device)), "adkf_predict_pool")
+    _lib.check(lib.adkf_predict_pool(C.byref(cb), ptr(phi), flags, ptr(X), rows, ptr(best_f), ptr(excl_idx), ptr(excl_off),
+                                     ptr(mean), ptr(var), ptr(ei), topk, ptr(top_idx), ptr(top_val), ptr(info), ptr(ws), nb,
+                                     ptr(scratch), sb, stream(b.device)), "adkf_predict_pool")
     return dict(mean=mean, var=var, ei=ei, top_idx=top_idx, top_val=top_val, info=info)
 
 
@@ -495,9 +487,9 @@ def _thompson_pool(name: str, b: GPBatch, phi, X, omega, phase, n_samples, gener
     ws, nb = b.workspace()
     cb = b.c_struct()
     entry = "adkf_" + name
-    _lib.check(getattr(lib, entry)(C.byref(cb), _ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, _ptr(X), rows, _ptr(omega), _ptr(phase),
-                                   m, _ptr(w), _ptr(eps), S, _ptr(excl_idx), _ptr(excl_off), _ptr(paths), _ptr(sel_idx), _ptr(sel_val),
-                                   _ptr(info), _ptr(ws), nb, _ptr(scratch), sb, _stream(b.device)), entry)
+    _lib.check(getattr(lib, entry)(C.byref(cb), ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, ptr(X), rows, ptr(omega), ptr(phase),
+                                   m, ptr(w), ptr(eps), S, ptr(excl_idx), ptr(excl_off), ptr(paths), ptr(sel_idx), ptr(sel_val),
+                                   ptr(info), ptr(ws), nb, ptr(scratch), sb, stream(b.device)), entry)
     return dict(sel_idx=sel_idx, sel_val=sel_val, paths=paths, info=info, w=w, eps=eps)
 
 
@@ -531,7 +523,7 @@ def double_path_tasks(b: GPBatch) -> torch.Tensor:
     flagged = _new(b, b.T, dtype=torch.int32)
     ws, nb = b.workspace()
     cb = b.c_struct()
-    _lib.check(lib.adkf_double_path_tasks(C.byref(cb), _ptr(flagged), _ptr(ws), nb, _stream(b.device)), "adkf_double_path_tasks")
+    _lib.check(lib.adkf_double_path_tasks(C.byref(cb), ptr(flagged), ptr(ws), nb, stream(b.device)), "adkf_double_path_tasks")
     return flagged
 
 
@@ -545,8 +537,8 @@ def outer_nll_value_grad(b: GPBatch, phi: torch.Tensor, want_grads=True):
     info = _new(b, b.T, dtype=torch.int32)
     ws, nb = b.workspace()
     cb = b.c_struct()
-    _lib.check(lib.adkf_outer_nll_value_grad(C.byref(cb), _ptr(phi), _ptr(f), _ptr(g), _ptr(dZs), _ptr(dZq), _ptr(info),
-                                             _ptr(ws), nb, _stream(b.device)), "adkf_outer_nll_value_grad")
+    _lib.check(lib.adkf_outer_nll_value_grad(C.byref(cb), ptr(phi), ptr(f), ptr(g), ptr(dZs), ptr(dZq), ptr(info),
+                                             ptr(ws), nb, stream(b.device)), "adkf_outer_nll_value_grad")
     return f, g, dZs, dZq, info
 
 
@@ -569,14 +561,14 @@ def ift_hypergrad(b: GPBatch, phi: torch.Tensor, ignore_grad_correction=False, i
     if b.ard:
         out = dict(f_out=_new(b, b.T), dZ_s=dZ_s, dZ_q=dZ_q, g_phi=_new(b, b.T, b.h), v=_new(b, b.T, b.h), H=None,
                    info=_new(b, b.T, dtype=torch.int32), cg_iters=_new(b, b.T, dtype=torch.int32))
-        _lib.check(lib.adkf_ift_hypergrad_cg(C.byref(cb), _ptr(phi), flags, int(cg_maxiter or 48), float(cg_tol), _ptr(out["f_out"]),
-                                             _ptr(dZ_s), _ptr(dZ_q), _ptr(out["g_phi"]), _ptr(out["v"]), _ptr(out["cg_iters"]),
-                                             _ptr(out["info"]), _ptr(ws), nb, _stream(b.device)), "adkf_ift_hypergrad_cg")
+        _lib.check(lib.adkf_ift_hypergrad_cg(C.byref(cb), ptr(phi), flags, int(cg_maxiter or 48), float(cg_tol), ptr(out["f_out"]),
+                                             ptr(dZ_s), ptr(dZ_q), ptr(out["g_phi"]), ptr(out["v"]), ptr(out["cg_iters"]),
+                                             ptr(out["info"]), ptr(ws), nb, stream(b.device)), "adkf_ift_hypergrad_cg")
         return out
     out = dict(f_out=_new(b, b.T), dZ_s=dZ_s, dZ_q=dZ_q, g_phi=_new(b, b.T, 3),
                v=_new(b, b.T, 3), H=_new(b, b.T, 9), info=_new(b, b.T, dtype=torch.int32))
-    _lib.check(lib.adkf_ift_hypergrad(C.byref(cb), _ptr(phi), flags, _ptr(out["f_out"]), _ptr(out["dZ_s"]), _ptr(out["dZ_q"]),
-                                      _ptr(out["g_phi"]), _ptr(out["v"]), _ptr(out["H"]), _ptr(out["info"]), _ptr(ws), nb,
-                                      _stream(b.device)), "adkf_ift_hypergrad")
+    _lib.check(lib.adkf_ift_hypergrad(C.byref(cb), ptr(phi), flags, ptr(out["f_out"]), ptr(out["dZ_s"]), ptr(out["dZ_q"]),
+                                      ptr(out["g_phi"]), ptr(out["v"]), ptr(out["H"]), ptr(out["info"]), ptr(ws), nb,
+                                      stream(b.device)), "adkf_ift_hypergrad")
     out["H"] = out["H"].view(b.T, 3, 3)
     return out

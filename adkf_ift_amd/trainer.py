@@ -226,8 +226,7 @@ class ClipAdam(torch.optim.Adam):
         parts = 256   # ADKF_SUMSQ_PARTS
         if self._partials is None or self._partials.numel() != parts * len(todo) or self._partials.device != dev:
             self._partials = torch.empty(parts * len(todo), dtype=torch.float32, device=dev)
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
+        ptr, st = _lib.ptr, _lib.stream(dev)
         clip = float("inf") if clip_value is None else float(clip_value)
         if self.FUSE_ONE and len(todo) == 1 and todo[0][1].numel() <= self.ONE_MAX:
             group, p = todo[0]

@@ -11,20 +11,11 @@ import time
 
 import numpy as np
 
+from adkf_ift_amd._lib import SIGNATURES, Batch, FitOptions   # noqa: F401  (the header's structs and prototypes, tests/test_abi.py)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "adkf_ift_amd", "csrc", "cpu", "adkf_gp_cpu.cpp")
 LIB = os.path.join(ROOT, "adkf_ift_amd", "libadkf_gp_cpu.so")
-
-
-class Batch(C.Structure):   # adkf_batch_t
-    _fields_ = [("T", C.c_int32), ("ns_max", C.c_int32), ("nq_max", C.c_int32), ("d", C.c_int32), ("kernel", C.c_int32), ("flags", C.c_int32),
-                ("n_s", C.c_void_p), ("n_q", C.c_void_p), ("Z_s", C.c_void_p), ("y_s", C.c_void_p), ("Z_q", C.c_void_p), ("y_q", C.c_void_p),
-                ("priors", C.c_void_p)]
-
-
-class FitOptions(C.Structure):   # adkf_fit_options_t
-    _fields_ = [("max_evals", C.c_int32), ("exact_evals", C.c_int32), ("gtol", C.c_float), ("ftol", C.c_float), ("ev_start", C.c_void_p),
-                ("ev_stop", C.c_void_p)]
 
 
 def build(force: bool = False) -> str:
@@ -40,7 +31,12 @@ _lib = None
 def load():
     global _lib
     if _lib is None:
-        _lib = C.CDLL(build())
+        lib = C.CDLL(build())
+        for name, (res, args) in SIGNATURES.items():
+            if hasattr(lib, name):     # the twin has the GP entries only
+                fn = getattr(lib, name)
+                fn.restype, fn.argtypes = res, args
+        _lib = lib
     return _lib
 
 
@@ -75,7 +71,7 @@ def init_params(Z_s, numeric=False, use_ls_prior=True, n_s=None):
     T = Z_s.shape[0]
     b = CpuBatch(Z_s, np.zeros(Z_s.shape[:2], np.float32), np.zeros((T, 4), np.float32), 0, n_s=n_s)
     phi, pri, l0 = np.empty((T, 3), np.float32), np.empty((T, 4), np.float32), np.empty(T, np.float32)
-    _check(load().adkf_init_params(C.byref(b.c), int(numeric), int(use_ls_prior), _p(phi), _p(pri), _p(l0), None, C.c_size_t(0), None), "adkf_init_params")
+    _check(load().adkf_init_params(C.byref(b.c), int(numeric), int(use_ls_prior), _p(phi), _p(pri), _p(l0), None, 0, None), "adkf_init_params")
     return phi, pri, l0
 
 
@@ -83,7 +79,7 @@ def mll_value_grad(b: CpuBatch, phi, want_dZ=True):
     phi = _f32(phi)
     f, g, info = np.empty(b.T, np.float32), np.empty((b.T, 3), np.float32), np.empty(b.T, np.int32)
     dZ = np.empty((b.T, b.ns, b.d), np.float32) if want_dZ else None
-    _check(load().adkf_mll_value_grad(C.byref(b.c), _p(phi), _p(f), _p(g), _p(dZ), _p(info), None, C.c_size_t(0), None), "adkf_mll_value_grad")
+    _check(load().adkf_mll_value_grad(C.byref(b.c), _p(phi), _p(f), _p(g), _p(dZ), _p(info), None, 0, None), "adkf_mll_value_grad")
     return f, g, dZ, info
 
 
@@ -91,7 +87,7 @@ def fit(b: CpuBatch, phi0, max_evals=200, gtol=1e-5, ftol=2.220446049250313e-09,
     phi = _f32(phi0).copy()
     f, gn, ne, info = np.empty(b.T, np.float32), np.empty(b.T, np.float32), np.empty(b.T, np.int32), np.empty(b.T, np.int32)
     opt = FitOptions(int(max_evals), int(exact_evals), float(gtol), float(ftol), None, None)
-    _check(load().adkf_fit(C.byref(b.c), _p(phi), C.byref(opt), _p(f), _p(gn), _p(ne), _p(info), None, C.c_size_t(0), None), "adkf_fit")
+    _check(load().adkf_fit(C.byref(b.c), _p(phi), C.byref(opt), _p(f), _p(gn), _p(ne), _p(info), None, 0, None), "adkf_fit")
     return phi, f, gn, ne, info
 
 
@@ -99,7 +95,7 @@ def predict(b: CpuBatch, phi, want_cov=False):
     phi = _f32(phi)
     mean, var, info = np.empty((b.T, b.nq), np.float32), np.empty((b.T, b.nq), np.float32), np.empty(b.T, np.int32)
     cov = np.empty((b.T, b.nq, b.nq), np.float32) if want_cov else None
-    _check(load().adkf_predict(C.byref(b.c), _p(phi), _p(mean), _p(var), _p(cov), _p(info), None, C.c_size_t(0), None), "adkf_predict")
+    _check(load().adkf_predict(C.byref(b.c), _p(phi), _p(mean), _p(var), _p(cov), _p(info), None, 0, None), "adkf_predict")
     return mean, var, cov, info
 
 
@@ -108,7 +104,7 @@ def ift_hypergrad(b: CpuBatch, phi, flags=0):
     out = dict(f_out=np.empty(b.T, np.float32), dZ_s=np.empty((b.T, b.ns, b.d), np.float32), dZ_q=np.empty((b.T, b.nq, b.d), np.float32),
                g_phi=np.empty((b.T, 3), np.float32), v=np.empty((b.T, 3), np.float32), H=np.empty((b.T, 3, 3), np.float32), info=np.empty(b.T, np.int32))
     _check(load().adkf_ift_hypergrad(C.byref(b.c), _p(phi), int(flags), _p(out["f_out"]), _p(out["dZ_s"]), _p(out["dZ_q"]), _p(out["g_phi"]),
-                                     _p(out["v"]), _p(out["H"]), _p(out["info"]), None, C.c_size_t(0), None), "adkf_ift_hypergrad")
+                                     _p(out["v"]), _p(out["H"]), _p(out["info"]), None, 0, None), "adkf_ift_hypergrad")
     return out
 
 
@@ -116,7 +112,7 @@ def outer_nll_value_grad(b: CpuBatch, phi):
     phi = _f32(phi)
     f, g, info = np.empty(b.T, np.float32), np.empty((b.T, 3), np.float32), np.empty(b.T, np.int32)
     dZs, dZq = np.empty((b.T, b.ns, b.d), np.float32), np.empty((b.T, b.nq, b.d), np.float32)
-    _check(load().adkf_outer_nll_value_grad(C.byref(b.c), _p(phi), _p(f), _p(g), _p(dZs), _p(dZq), _p(info), None, C.c_size_t(0), None),
+    _check(load().adkf_outer_nll_value_grad(C.byref(b.c), _p(phi), _p(f), _p(g), _p(dZs), _p(dZq), _p(info), None, 0, None),
            "adkf_outer_nll_value_grad")
     return f, g, dZs, dZq, info
 

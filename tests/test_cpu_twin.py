@@ -34,6 +34,20 @@ def test_exports_every_gp_entry_point_of_the_header():
         assert hasattr(lib, name), name
 
 
+def test_bound_from_the_table_the_header_is_checked_against():
+    """The twin's prototypes and structs are the ones of adkf_ift_amd/_lib.py (which tests/test_abi.py holds against the header),
+    not copies: a signature change reaches the twin's callers through that one table."""
+    from adkf_ift_amd import _lib
+
+    assert TW.Batch is _lib.Batch and TW.FitOptions is _lib.FitOptions
+    lib = TW.load()
+    bound = [name for name in _lib.SIGNATURES if hasattr(lib, name)]
+    assert {"adkf_fit", "adkf_ift_hypergrad", "adkf_predict_marginal_ard", "adkf_predict_pool", "adkf_thompson_pool_ard"} <= set(bound)
+    for name in bound:
+        fn = getattr(lib, name)
+        assert fn.restype == _lib.SIGNATURES[name][0] and fn.argtypes == _lib.SIGNATURES[name][1], name
+
+
 def test_golden_cases(golden_dir):
     files = sorted(glob.glob(os.path.join(golden_dir, "gp_*.npz")))
     assert len(files) >= 30

@@ -9,8 +9,6 @@ import torch
 
 from adkf_ift_amd import _lib
 
-ARGS = [C.POINTER(_lib.Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
 BADARG, LAUNCH = -1, -4
 
 
@@ -96,8 +94,6 @@ def _twin():
     except subprocess.CalledProcessError as e:   # the compiler is there but cannot build it (e.g. no OpenMP)
         pytest.skip(f"CPU twin could not be built: {e}")
     fn = tw.adkf_predict_marginal   # a twin library without the entry point fails here
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(cpu_twin.Batch)] + ARGS[1:]
     return cpu_twin, fn
 
 

@@ -9,8 +9,6 @@ import torch
 
 from adkf_ift_amd import _lib
 
-POOL_ARGS = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
 BADARG, SIZE, WORKSPACE, LAUNCH = -1, -2, -3, -4
 ARD = 4
 LATENT, MAXIMIZE, SCORE_MEAN = 1, 2, 4
@@ -120,11 +118,7 @@ def _twin():
     except subprocess.CalledProcessError as e:   # the compiler is there but cannot build it (e.g. no OpenMP)
         pytest.skip(f"CPU twin could not be built: {e}")
     fn = tw.adkf_predict_pool   # a twin library without the entry point fails here
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(cpu_twin.Batch)] + POOL_ARGS
     sb = tw.adkf_predict_pool_scratch_bytes
-    sb.restype = C.c_size_t
-    sb.argtypes = [C.c_int32, C.c_int32]
     assert sb(4, 8) == 0
     return cpu_twin, fn
 

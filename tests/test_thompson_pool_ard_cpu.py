@@ -10,7 +10,7 @@ import torch
 
 from adkf_ift_amd import _lib
 from test_predict_pool_cpu import select_ref
-from test_thompson_pool_cpu import ARD, BADARG, LAUNCH, MAXIMIZE, SIZE, TS_ARGS, WORKSPACE, _draws, _np_basis, paths_ref
+from test_thompson_pool_cpu import ARD, BADARG, LAUNCH, MAXIMIZE, SIZE, WORKSPACE, _draws, _np_basis, paths_ref
 
 RAW_ONE = math.log(math.expm1(1.0))   # softplus^-1(1)
 
@@ -104,13 +104,7 @@ def _twin():
         tw = cpu_twin.load()
     except subprocess.CalledProcessError as e:   # the compiler is there but cannot build it (e.g. no OpenMP)
         pytest.skip(f"CPU twin could not be built: {e}")
-    fns = []
-    for name in ("adkf_thompson_pool_ard", "adkf_thompson_pool"):   # a twin library without the entry point fails here
-        fn = getattr(tw, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.POINTER(cpu_twin.Batch)] + TS_ARGS
-        fns.append(fn)
-    return cpu_twin, fns[0], fns[1]
+    return cpu_twin, tw.adkf_thompson_pool_ard, tw.adkf_thompson_pool   # a twin library without the entry point fails here
 
 
 # per task and dimension, all distinct, in [0.5, 2.0]

@@ -11,8 +11,6 @@ import torch
 from adkf_ift_amd import _lib
 from test_predict_pool_cpu import select_ref
 
-TS_ARGS = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
 BADARG, SIZE, WORKSPACE, LAUNCH = -1, -2, -3, -4
 ARD, MAXIMIZE = 4, 2
 
@@ -100,11 +98,7 @@ def _twin():
     except subprocess.CalledProcessError as e:   # the compiler is there but cannot build it (e.g. no OpenMP)
         pytest.skip(f"CPU twin could not be built: {e}")
     fn = tw.adkf_thompson_pool   # a twin library without the entry point fails here
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(cpu_twin.Batch)] + TS_ARGS
     sb = tw.adkf_thompson_pool_scratch_bytes
-    sb.restype = C.c_size_t
-    sb.argtypes = [C.c_int32] * 4
     assert sb(4, 8, 4, 64) == 0
     return cpu_twin, fn
 
