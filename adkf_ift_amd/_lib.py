@@ -18,6 +18,7 @@ INFO_OUTER_BASE = 100000
 PM_LATENT = 1     # adkf_predict_marginal: var without the observation noise
 PM_MAXIMIZE = 2   # ... ei for maximisation
 PM_SCORE_MEAN = 4  # adkf_predict_pool: rank by the posterior mean instead of ei
+PM_LOG_EI = 16    # ... ei, and the ei score of adkf_predict_pool, hold log EI (8 is not a flag)
 POOL_TOPK_MAX = 64
 TS_SAMPLES_MAX = 64      # adkf_thompson_pool: posterior draws per task
 TS_FEATURES_MAX = 4096   # ... random Fourier features (a multiple of 64, at least 64)

@@ -8,7 +8,8 @@ batched fit and one ``adkf_predict_pool`` call per iteration, which returns each
 ``run_gp_ts_bo_batched`` is the same loop under Thompson sampling: one batched fit and one ``adkf_thompson_pool`` call (with
 ``ard=True``: ``adkf_thompson_pool_ard``) per iteration, in which every replicate draws posterior functions over the whole pool
 and each function picks its own best candidate - a diverse batch of ``query_batch_size > 1`` picks from one pass, with no
-``best_f`` and nothing that can underflow.
+``best_f`` and nothing that can underflow.  Both EI loops take ``acquisition="log_ei"``: the same candidates ranked by log EI
+(``ADKF_PM_LOG_EI``), which stays finite where float32 EI is 0 on the whole pool and the ``"ei"`` loops fall back to random picks.
 
 Only the Matern-5/2 branch exists here (the Tanimoto kernel of the reference's fingerprint baseline is not a
 distance-based kernel and is out of the library's scope).
@@ -61,13 +62,14 @@ def _support_batch(model: ExactGPLayer, mll: ExactMarginalLogLikelihood):
 
 @torch.no_grad()
 def streaming_posterior(model: ExactGPLayer, mll: ExactMarginalLogLikelihood, X: torch.Tensor, best_f: Optional[float] = None,
-                        maximize: bool = False):
-    """(mean, latent variance, EI or None) at every row of X in ONE ``adkf_predict_marginal`` call, for pools of any size."""
+                        maximize: bool = False, log_ei: bool = False):
+    """(mean, latent variance, EI or None) at every row of X in ONE ``adkf_predict_marginal`` call, for pools of any size.
+    ``log_ei`` (needs ``best_f``): log EI in the place of EI."""
     b, phi = _support_batch(model, mll)
     X = X.detach().float().contiguous()
     q_off = torch.tensor([0, X.shape[0]], dtype=torch.int64, device=X.device)
     bf = None if best_f is None else torch.full((1,), float(best_f), dtype=torch.float32, device=X.device)
-    mean, var, ei, info = gp_ops.predict_marginal(b, phi, X, q_off, latent=True, best_f=bf, maximize=maximize)
+    mean, var, ei, info = gp_ops.predict_marginal(b, phi, X, q_off, latent=True, best_f=bf, maximize=maximize, log_ei=log_ei)
     gp_ops.check_info(info, "BO posterior")
     return mean, var.clamp_min(1e-12), ei
 
@@ -104,12 +106,45 @@ def expected_improvement(mean: torch.Tensor, var: torch.Tensor, best_f: float, m
     return sigma * (u * normal.cdf(u) + torch.exp(normal.log_prob(u)))
 
 
+def log_expected_improvement(mean: torch.Tensor, var: torch.Tensor, best_f: float, maximize: bool = False) -> torch.Tensor:
+    """log of ``expected_improvement`` without passing through it (botorch's LogExpectedImprovement; Ament et al. 2023):
+    log sigma + log h(u), h(u) = phi(u) + u Phi(u), finite for any u.  In float64 whatever the input dtype, which the result
+    has: h itself for u > -1; below, with a = -u, h = phi(u) (1 - a sqrt(pi / 2) erfcx(a / sqrt 2)) down to u = -30 (the bracket
+    cancels to ~1 / a^2: an absolute error of a few eps64 a^2) and beyond that its asymptotic series
+    a^-2 (1 - 3 a^-2 + 15 a^-4 - ...), eight terms.  The host restatement of ``ADKF_PM_LOG_EI``."""
+    sigma = var.double().sqrt()
+    u = (mean.double() - best_f) / sigma
+    if not maximize:
+        u = -u
+    a = -u
+    direct = torch.log(torch.exp(-0.5 * u * u) / math.sqrt(2.0 * math.pi) + u * 0.5 * torch.erfc(-u / math.sqrt(2.0)))
+    mid = torch.log1p(-a * math.sqrt(math.pi / 2.0) * torch.special.erfcx(a / math.sqrt(2.0)))
+    w = 1.0 / (a * a)
+    series = torch.zeros_like(w)
+    for c in (34459425.0, -2027025.0, 135135.0, -10395.0, 945.0, -105.0, 15.0, -3.0):   # (-1)^k (2k + 1)!!, k = 8 .. 1 (Horner)
+        series = (series + c) * w
+    tail = torch.log(w) + torch.log1p(series)
+    log_h = torch.where(u > -1.0, direct, -0.5 * a * a - 0.5 * math.log(2.0 * math.pi) + torch.where(u > -30.0, mid, tail))
+    return (sigma.log() + log_h).to(mean.dtype)
+
+
+def _acquisition(acquisition: str) -> bool:
+    """True for "log_ei", False for "ei"."""
+    if acquisition not in ("ei", "log_ei"):
+        raise ValueError(f"acquisition must be 'ei' or 'log_ei', got {acquisition!r}")
+    return acquisition == "log_ei"
+
+
 def run_gp_ei_bo(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
                  kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
-                 rng: Optional[np.random.Generator] = None, streaming: bool = False) -> List[int]:
+                 rng: Optional[np.random.Generator] = None, streaming: bool = False, acquisition: str = "ei") -> List[int]:
     """bo_utils.py:342-397 (minimisation; points sorted by ascending y).  Returns the BO record: the best initial index
     followed by the queried indices in the order the reference appends them.  ``streaming``: EI of the whole pool from one
-    ``adkf_predict_marginal`` call (no pool-size cap)."""
+    ``adkf_predict_marginal`` call (no pool-size cap).  ``acquisition``: ``"ei"`` (the reference's: a candidate counts when its EI
+    is positive, and random picks fill in for the rest - all of them once float32 EI has underflowed on the pool) or
+    ``"log_ei"`` (the same ranking on log EI; a candidate counts when its score is finite, so a pool with finite predictions
+    never needs the random fallback)."""
+    log = _acquisition(acquisition)
     rng = rng or np.random.default_rng()
     n = x_all.shape[0]
     y_all = (y_all - y_all.mean()) / y_all.std()
@@ -121,12 +156,16 @@ def run_gp_ei_bo(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int,
         likelihood, model, mll = create_gp(xq, yq, kernel_type, device, noise_init, noise_prior)
         fit_gpytorch_scipy(mll)
         if streaming:
-            acq = streaming_posterior(model, mll, x_all, best_f=best, maximize=False)[2].cpu()
+            acq = streaming_posterior(model, mll, x_all, best_f=best, maximize=False, log_ei=log)[2].cpu()
         else:
             mean, var = latent_posterior(model, mll, x_all)
-            acq = expected_improvement(mean, var, best, maximize=False).cpu()
+            acq = (log_expected_improvement if log else expected_improvement)(mean, var, best, maximize=False).cpu()
         acq[queried] = -float("inf")
-        nonzero = int((acq > 0).sum())
+        if log:   # usable: a finite score
+            acq[~torch.isfinite(acq)] = -float("inf")
+            nonzero = int((acq > -float("inf")).sum())
+        else:
+            nonzero = int((acq > 0).sum())
         free = lambda taken: [i for i in range(n) if i not in taken]
         if nonzero == 0:
             pick = rng.choice(free(queried), size=query_batch_size, replace=False).tolist()
@@ -143,12 +182,14 @@ def run_gp_ei_bo(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int,
 @torch.no_grad()
 def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
                          kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
-                         rngs: List[np.random.Generator]) -> List[List[int]]:
+                         rngs: List[np.random.Generator], acquisition: str = "ei") -> List[List[int]]:
     """``len(rngs)`` replicates of ``run_gp_ei_bo`` over the same pool at once; returns their records.  Per iteration the
     replicates' queried sets form ONE batch (initial parameters and priors as ``create_gp`` makes them for each), fitted by ONE
     ``gp_ops.fit`` with ``fit_gpytorch_scipy``'s options and scored by ONE ``gp_ops.predict_pool`` call that excludes each
     replicate's queried points and returns its ``query_batch_size`` best candidates: no EI vector ever exists.  Every replicate
-    draws from its own generator in the order the sequential loop does."""
+    draws from its own generator in the order the sequential loop does.  ``acquisition``: as ``run_gp_ei_bo``; with ``"log_ei"``
+    the call ranks by log EI and a returned candidate counts when its score is finite and its index is not -1."""
+    log = _acquisition(acquisition)
     R, n = len(rngs), x_all.shape[0]
     y_all = (y_all - y_all.mean()) / y_all.std()
     X = x_all.detach().float().contiguous()
@@ -180,11 +221,12 @@ def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
         b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
         out = gp_ops.predict_pool(b, phi, X, latent=True, best_f=torch.tensor(best, dtype=torch.float32, device=X.device),
                                   maximize=False, want_mean=False, want_var=False, want_ei=False, topk=query_batch_size,
-                                  exclude=queried)
+                                  exclude=queried, log_ei=log)
         gp_ops.check_info(out["info"], "BO posterior")
         top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
+        usable = (torch.isfinite(top_val) & (top_idx >= 0)) if log else top_val > 0   # (a prefix of each row: descending scores)
         for r, rng in enumerate(rngs):
-            nonzero = int((top_val[r] > 0).sum())   # of the query_batch_size best: all that the branches below distinguish
+            nonzero = int(usable[r].sum())   # of the query_batch_size best: all that the branches below distinguish
             if nonzero == 0:
                 pick = rng.choice(free(queried[r]), size=query_batch_size, replace=False).tolist()
             elif nonzero < query_batch_size:

@@ -952,6 +952,7 @@ PmArgs pm_args(const PmCtx& c, int32_t flags, const float* Zq, int64_t rows, con
     pa.info = info;
     pa.refine_thresh = refine32_threshold(); pa.r64_thresh = c.w.w64 ? r64_threshold() : INFINITY;
     pa.latent = (flags & ADKF_PM_LATENT) ? 1 : 0; pa.maximize = (flags & ADKF_PM_MAXIMIZE) ? 1 : 0;
+    pa.log_ei = (flags & ADKF_PM_LOG_EI) ? 1 : 0;
     pa.vec = ((b.d & 3) == 0 && aligned16(Zq) && aligned16(b.Z_s)) ? 1 : 0;
     pa.buf_ld = ceil_div(b.ns_max, PM_TM) * PM_TM + 4;
     pa.w64 = c.w.w64; pa.w64_stride = c.w.w64_stride;
@@ -1067,7 +1068,8 @@ int predict_marginal(bool ard, const adkf_batch_t* b, const float* phi, int32_t 
     if (!phi || !q_off || !info || !ws || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
     if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
     if (ei && !best_f) return ADKF_E_BADARG;
-    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    if ((flags & ADKF_PM_LOG_EI) && !ei) return ADKF_E_BADARG;
     PmCtx c;
     rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
@@ -1367,8 +1369,9 @@ int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, co
     if (rc) return rc;
     if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;   // the support set only
     if (!phi || !info || !ws || !b->y_s || !b->priors || rows < 0 || k < 0) return ADKF_E_BADARG;
-    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN)) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
     const bool by_mean = (flags & ADKF_PM_SCORE_MEAN) != 0;
+    if ((flags & ADKF_PM_LOG_EI) && !ei && (k == 0 || by_mean)) return ADKF_E_BADARG;   // nothing would read it
     if (rows > 0 && !X) return ADKF_E_BADARG;
     if ((ei || (k > 0 && !by_mean)) && !best_f) return ADKF_E_BADARG;
     if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
@@ -1387,7 +1390,7 @@ int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, co
     PmCtx c;
     rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
-    const PmCall io{flags & (ADKF_PM_LATENT | ADKF_PM_MAXIMIZE), X, nullptr, rows, best_f, mean, var, ei, info, &pool};
+    const PmCall io{flags & (ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI), X, nullptr, rows, best_f, mean, var, ei, info, &pool};
     return c.ard ? pm_launch<true, true>(c, io) : pm_launch<false, true>(c, io);
 }
 

@@ -349,7 +349,23 @@ int check(const adkf_batch_t* b, bool need_q, bool ard_ok = false) {
 }
 inline int ns_of(const adkf_batch_t* b, int t) { return b->n_s ? b->n_s[t] : b->ns_max; }
 
-// adkf_predict_marginal(_ard): mean, variance and EI of row r from its squared distances D [n] to the support set of a task
+// log h(u), h(u) = phi(u) + u Phi(u) (ADKF_PM_LOG_EI): through erfc down to u = -8; below that, with a = -u,
+// h(u) = phi(u) a^-2 (1 - 3 a^-2 + 15 a^-4 - ...), the asymptotic series summed while its terms shrink (the smallest is below
+// 2e-13 at a = 8)
+double log_h(double u) {
+    if (u > -8.0) return std::log(std::exp(-0.5 * u * u) / std::sqrt(2.0 * M_PI) + u * 0.5 * std::erfc(-u / std::sqrt(2.0)));
+    const double w = 1.0 / (u * u);
+    double sum = 1.0, term = 1.0;
+    for (int k = 1; k < 64; ++k) {
+        const double next = -term * (2 * k + 1) * w;
+        if (std::fabs(next) >= std::fabs(term)) break;
+        sum += term = next;
+    }
+    return -0.5 * u * u - 0.5 * std::log(2.0 * M_PI) + std::log(w) + std::log(sum);
+}
+
+// adkf_predict_marginal(_ard): mean, variance and EI (ADKF_PM_LOG_EI: log EI) of row r from its squared distances D [n] to the
+// support set of a task
 void pm_row(const Inner& in, int kind, const double* D, const float* y, int flags, const float* best_f, int t, int64_t r, float* mean,
             float* var, float* ei) {
     const int n = in.n;
@@ -369,7 +385,8 @@ void pm_row(const Inner& in, int kind, const double* D, const float* y, int flag
     if (ei) {
         const double sg = std::sqrt(std::max(vl, 1e-12)), bf = best_f[t];
         const double u = ((flags & ADKF_PM_MAXIMIZE) ? (mu - bf) : (bf - mu)) / sg;
-        ei[r] = (float)(sg * (u * 0.5 * std::erfc(-u / std::sqrt(2.0)) + std::exp(-0.5 * u * u) / std::sqrt(2.0 * M_PI)));
+        if (flags & ADKF_PM_LOG_EI) ei[r] = (float)(std::log(sg) + log_h(u));
+        else ei[r] = (float)(sg * (u * 0.5 * std::erfc(-u / std::sqrt(2.0)) + std::exp(-0.5 * u * u) / std::sqrt(2.0 * M_PI)));
     }
 }
 
@@ -414,7 +431,8 @@ int predict_marginal(bool ard, const adkf_batch_t* b, const float* phi, int32_t 
     if (!phi || !q_off || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
     if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
     if (ei && !best_f) return ADKF_E_BADARG;
-    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE)) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    if ((flags & ADKF_PM_LOG_EI) && !ei) return ADKF_E_BADARG;
     // rows outside every task's range and those of tasks with n_s == 0 or info != 0 stay 0 (as on the GPU)
     if (rows > 0) {
         std::fill(mean, mean + rows, 0.f);
@@ -622,8 +640,9 @@ int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, co
     if (int rc = check(b, false, true)) return rc;
     if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
     if (!phi || !info || !b->y_s || !b->priors || rows < 0 || k < 0) return ADKF_E_BADARG;
-    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN)) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
     const bool by_mean = (flags & ADKF_PM_SCORE_MEAN) != 0, want_e = ei || (k > 0 && !by_mean);
+    if ((flags & ADKF_PM_LOG_EI) && !want_e) return ADKF_E_BADARG;   // nothing would read it
     if (rows > 0 && !X) return ADKF_E_BADARG;
     if (want_e && !best_f) return ADKF_E_BADARG;
     if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;

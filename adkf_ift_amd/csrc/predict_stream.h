@@ -80,7 +80,7 @@ struct PmArgs {
     size_t slot_floats;
     const int32_t* info;                    // tasks with info != 0 (failed factorisation) are skipped: their rows stay 0
     float refine_thresh, r64_thresh;        // r64_thresh: +inf when the workspace has no float64 region
-    int latent, maximize, vec;
+    int latent, maximize, log_ei, vec;      // log_ei: the ei array and the EI score hold log EI (pm_log_ei)
     int buf_ld;                             // leading dimension of a row tile
     const double* w64; size_t w64_stride;   // the float64 region of refine64.h (the float64 kernels)
 };
@@ -191,6 +191,36 @@ __device__ __forceinline__ float pm_ei(float mean, float var_latent, float best,
     const float cdf = 0.5f * erfcf(-u * 0.70710678118654752f);
     const float pdf = 0.3989422804014327f * expf(-0.5f * u * u);
     return sigma * fmaf(u, cdf, pdf);
+}
+
+// log EI = log sigma + log h(u), h(u) = phi(u) + u Phi(u), with pm_ei's sigma and u, never through EI (Ament et al. 2023): finite
+// wherever u * u is, -inf where it overflows at u < 0.  h is formed only where it neither cancels nor underflows, u > -1.  Below,
+// with a = -u,
+//     h(u) = phi(u) b(a),    b(a) = 1 - a sqrt(pi / 2) erfcx(a / sqrt 2) = a^-2 (1 - 3 a^-2 + 15 a^-4 - 105 a^-6 + 945 a^-8 - ...),
+// the first form down to u = -12 (b cancels to ~a^-2: an absolute error of a few eps32 a^2 in the logarithm, the size u's own
+// rounding gives it), the series beyond (its first omitted term is 1.7e-7 at a = 12).  A NaN mean gives NaN.
+// Not inlined: one call per row, and the temporaries of erfcxf and the logarithms stay out of the kernels' register budget (inlined,
+// every instance gains 3 VGPRs and the plain ARD pool instance drops from 3 waves per SIMD to 2).
+__device__ __noinline__ float pm_log_ei(float mean, float var_latent, float best, int maximize) {
+    const float sigma = sqrtf(fmaxf(var_latent, 1e-12f));
+    const float u = (maximize ? (mean - best) : (best - mean)) / sigma;
+    float lh;
+    if (u > -1.f) {
+        const float cdf = 0.5f * erfcf(-u * 0.70710678118654752f);
+        const float pdf = 0.3989422804014327f * expf(-0.5f * u * u);
+        lh = logf(fmaf(u, cdf, pdf));
+    } else {
+        const float a = -u, a2 = a * a;
+        float lb;
+        if (u > -12.f) {
+            lb = logf(fmaf(-(a * 1.2533141373155003f), erfcxf(a * 0.70710678118654752f), 1.f));
+        } else {
+            const float w = 1.f / a2;   // 0 once a * a overflows: the series is 1, and -a^2 / 2 = -inf decides
+            lb = logf(fmaf(fmaf(fmaf(fmaf(945.f, w, -105.f), w, 15.f), w, -3.f), w, 1.f)) - 2.f * logf(a);
+        }
+        lh = (lb - 0.9189385332046727f) - 0.5f * a2;
+    }
+    return logf(sigma) + lh;
 }
 
 // ---- shared-pool selection
@@ -369,8 +399,8 @@ __device__ __forceinline__ void pm_k_panel(const PmArgs& a, const float* Zs, con
     __syncthreads();
 }
 
-// ---- the outputs of one row (both prediction kernels): mean, the latent variance vl or the observed one vo, EI; returns the
-// row's selection score (POOL)
+// ---- the outputs of one row (both prediction kernels): mean, the latent variance vl or the observed one vo, EI (PmArgs::log_ei:
+// log EI); returns the row's selection score (POOL)
 template <bool POOL, class ARGS>
 __device__ __forceinline__ float pm_row_out(const ARGS& args, int t, int64_t r, float mean, float vl, float vo) {
     const PmArgs& a = args.p;
@@ -380,11 +410,12 @@ __device__ __forceinline__ float pm_row_out(const ARGS& args, int t, int64_t r, 
     if constexpr (POOL) {
         const bool by_mean = args.s.score_mean != 0;
         float e = 0.f;
-        if (a.ei || (args.s.k > 0 && !by_mean)) e = pm_ei(mean, vl, a.best_f[t], a.maximize);
+        if (a.ei || (args.s.k > 0 && !by_mean))
+            e = a.log_ei ? pm_log_ei(mean, vl, a.best_f[t], a.maximize) : pm_ei(mean, vl, a.best_f[t], a.maximize);
         if (a.ei) a.ei[row] = e;
         return by_mean ? (a.maximize ? mean : -mean) : e;
     } else {
-        if (a.ei) a.ei[row] = pm_ei(mean, vl, a.best_f[t], a.maximize);
+        if (a.ei) a.ei[row] = a.log_ei ? pm_log_ei(mean, vl, a.best_f[t], a.maximize) : pm_ei(mean, vl, a.best_f[t], a.maximize);
         return 0.f;
     }
 }

@@ -291,13 +291,17 @@ def unpack_rows(x: torch.Tensor, q_off: torch.Tensor, nq: int) -> torch.Tensor:
 
 
 def predict_marginal(b: GPBatch, phi: torch.Tensor, Zq: torch.Tensor, q_off: torch.Tensor, latent: bool = False,
-                     best_f: Optional[torch.Tensor] = None, maximize: bool = False, want_var: bool = True):
+                     best_f: Optional[torch.Tensor] = None, maximize: bool = False, want_var: bool = True, log_ei: bool = False):
     """Marginal posterior of packed query rows (``pack_rows``) against the support set of ``b`` (which carries no query set):
     returns (mean [rows], var [rows] or None, ei [rows] or None, info [T]).  ``var`` includes the observation noise unless
     ``latent``; ``ei`` (only with ``best_f [T]``) is Expected Improvement on the latent variance, for minimisation unless
-    ``maximize``.  No size cap and a workspace independent of the number of rows (include/adkf_gp.h).  ARD batches (``phi``
+    ``maximize``.  With ``log_ei`` (needs ``best_f``) ``ei`` holds log EI instead, evaluated without forming EI: finite where
+    float32 EI underflows to 0 (from about 14 posterior standard deviations short of ``best_f``); rows the call leaves at 0 stay 0.
+    No size cap and a workspace independent of the number of rows (include/adkf_gp.h).  ARD batches (``phi``
     [T, 2 + d]) go through ``adkf_predict_marginal_ard``."""
     lib = _lib.load()
+    if log_ei and best_f is None:
+        raise ValueError("log_ei needs best_f [T]")
     if b.nq != 0:
         raise ValueError("predict_marginal takes a support-only batch (no Z_q / y_q): the query rows come packed in Zq")
     phi = b.check_phi(phi)
@@ -319,7 +323,7 @@ def predict_marginal(b: GPBatch, phi: torch.Tensor, Zq: torch.Tensor, q_off: tor
     var = _new(b, rows) if want_var else None
     ei = _new(b, rows) if best_f is not None else None
     info = _new(b, b.T, dtype=torch.int32)
-    flags = (_lib.PM_LATENT if latent else 0) | (_lib.PM_MAXIMIZE if maximize else 0)
+    flags = (_lib.PM_LATENT if latent else 0) | (_lib.PM_MAXIMIZE if maximize else 0) | (_lib.PM_LOG_EI if log_ei else 0)
     ws, nb = b.workspace()
     cb = b.c_struct()
     name = "adkf_predict_marginal_ard" if b.ard else "adkf_predict_marginal"
@@ -357,12 +361,14 @@ def pack_exclude(exclude, T: int, rows: int, device=None) -> Tuple[torch.Tensor,
 
 def predict_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, latent: bool = False, best_f: Optional[torch.Tensor] = None,
                  maximize: bool = False, score: str = "ei", want_mean: bool = True, want_var: bool = True,
-                 want_ei: Optional[bool] = None, topk: int = 0, exclude=None):
+                 want_ei: Optional[bool] = None, topk: int = 0, exclude=None, log_ei: bool = False):
     """Every task of the support-only batch ``b`` scores the SAME pool ``X [rows, d]`` in one ``adkf_predict_pool`` call.
     Returns ``dict(mean, var, ei, top_idx, top_val, info)``: the per-row outputs asked for as ``[T, rows]`` tensors (None
     otherwise; ``want_ei`` defaults to "``best_f`` given"), ``top_idx [T, topk]`` (int64) / ``top_val [T, topk]`` - each task's
     ``topk`` (at most 64) rows of largest score, descending, equal scores by ascending row, -1 / -inf where fewer are eligible -
     and ``info [T]``.  ``score``: ``"ei"`` (needs ``best_f``) or ``"mean"`` (+mean with ``maximize``, -mean without).
+    ``log_ei``: ``ei`` and the ``"ei"`` score (hence ``top_val``) are log EI, which keeps an order where float32 EI is 0 on every
+    row; it needs something that reads it (``want_ei``, or ``topk > 0`` with ``score="ei"``).
     ``exclude``: rows a task may not select (``pack_exclude``).  With no per-row output and ``topk > 0`` nothing of size
     T x rows is allocated or written."""
     lib = _lib.load()
@@ -387,6 +393,8 @@ def predict_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, latent: bool
         raise ValueError("ei and ranking by ei need best_f [T]")
     if not (want_mean or want_var or want_ei or topk > 0):
         raise ValueError("no output asked for")
+    if log_ei and not (want_ei or (topk > 0 and score == "ei")):
+        raise ValueError("log_ei without want_ei or a selection ranked by ei: nothing would read it")
     rows = X.shape[0]
     excl_idx = excl_off = None
     if exclude is not None and topk > 0:
@@ -403,6 +411,7 @@ def predict_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, latent: bool
     sb = int(lib.adkf_predict_pool_scratch_bytes(b.T, topk))
     scratch = torch.empty(sb, dtype=torch.uint8, device=b.device) if sb else None
     flags = (_lib.PM_LATENT if latent else 0) | (_lib.PM_MAXIMIZE if maximize else 0) | (_lib.PM_SCORE_MEAN if score == "mean" else 0)
+    flags |= _lib.PM_LOG_EI if log_ei else 0
     ws, nb = b.workspace()
     cb = b.c_struct()
     _lib.check(lib.adkf_predict_pool(C.byref(cb), ptr(phi), flags, ptr(X), rows, ptr(best_f), ptr(excl_idx), ptr(excl_off),

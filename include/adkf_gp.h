@@ -182,14 +182,23 @@ int adkf_predict(const adkf_batch_t* b, const float* phi, float* mean, float* va
  *   mean   [rows]; var [rows] (nullable) includes the noise unless ADKF_PM_LATENT; ei [rows] (nullable, needs best_f [T]):
  *          Expected Improvement sigma (u Phi(u) + phi(u)) on the LATENT variance, u = (best_f - mean) / sigma for
  *          minimisation, (mean - best_f) / sigma with ADKF_PM_MAXIMIZE; info [T] as adkf_predict.  Rows that belong to no
- *          task's range, and the rows of tasks with n_s == 0 or info != 0, are written as 0. */
+ *          task's range, and the rows of tasks with n_s == 0 or info != 0, are written as 0.
+ *          In float32 that EI is 0, or a negative denormal, from about u <= -14.  With ADKF_PM_LOG_EI (needs ei, ADKF_E_BADARG
+ *          without) the ei array holds log EI instead: log sigma + log h(u), h(u) = phi(u) + u Phi(u), with the same
+ *          sigma = sqrt(max(var_latent, 1e-12)), u, best_f and ADKF_PM_MAXIMIZE sense, evaluated without ever forming EI (Ament et
+ *          al., NeurIPS 2023; csrc/predict_stream.h: pm_log_ei).  It is finite for every finite (mean, var, best_f) whose u * u
+ *          does not overflow float32 (-inf where it overflows at u < 0), NaN for a NaN mean, and exp of it is the EI above
+ *          wherever that one is accurate.  The rows written as 0 stay 0 under the flag: that 0 is the fill value, not a
+ *          logarithm. */
 #define ADKF_PM_LATENT 1   /* var without the observation noise: the latent f, what BoTorch's analytic EI reads */
 #define ADKF_PM_MAXIMIZE 2 /* ei for maximisation (default: minimisation, as bayes_opt.run_gp_ei_bo) */
+#define ADKF_PM_LOG_EI 16  /* ei holds log EI, which does not underflow; adkf_predict_pool ranks by it (bit 8 is not a flag) */
 int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows, const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream);
 
 /* The same for ARD batches (one lengthscale per feature dimension); exactly the parameters of adkf_predict_marginal.
  *   b      must carry ADKF_BATCH_ARD and be support-only (nq_max == 0, Z_q == y_q == NULL); anything else is ADKF_E_BADARG,
- *          as are a missing Zq with rows > 0, ei without best_f and flag bits other than ADKF_PM_LATENT | ADKF_PM_MAXIMIZE.
+ *          as are a missing Zq with rows > 0, ei without best_f, ADKF_PM_LOG_EI without ei and flag bits other than
+ *          ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI.
  *          Every argument is checked before anything is launched;
  *   phi    [T, 2 + d] in the ARD layout (raw_noise, raw_outputscale, raw_lengthscale[0..d));
  *   ws     exactly adkf_workspace_bytes_ard(T, ns_max, 0, d) bytes whatever `rows` is (less: ADKF_E_WORKSPACE);
@@ -206,24 +215,27 @@ int adkf_predict_marginal_ard(const adkf_batch_t* b, const float* phi, int32_t f
  *          adkf_predict_marginal_ard (phi [T, 2 + d], ws of adkf_workspace_bytes_ard(T, ns_max, 0, d) bytes), without it as
  *          adkf_predict_marginal (adkf_workspace_bytes(T, ns_max, 0, d)).  REUSE_DIST / REUSE_INNER mean what they mean there.
  *          The workspace size depends neither on rows nor on k.
- *   flags  ADKF_PM_LATENT, ADKF_PM_MAXIMIZE, ADKF_PM_SCORE_MEAN; any other bit is ADKF_E_BADARG.
+ *   flags  ADKF_PM_LATENT, ADKF_PM_MAXIMIZE, ADKF_PM_SCORE_MEAN, ADKF_PM_LOG_EI; any other bit is ADKF_E_BADARG.
  *   mean, var, ei   each nullable, [T, rows] row-major (task t, row r at t * rows + r); the values of the packed call: var
- *          includes the noise unless ADKF_PM_LATENT, ei (needs best_f [T]) is on the latent variance.  With all three NULL the
- *          kernels write nothing per row.
- *   k, top_idx, top_val   k == 0: no selection.  Otherwise ([T, k] each) the score of row r for task t is its ei value, or with
+ *          includes the noise unless ADKF_PM_LATENT, ei (needs best_f [T]) is on the latent variance and holds log EI with
+ *          ADKF_PM_LOG_EI.  With all three NULL the kernels write nothing per row.
+ *   k, top_idx, top_val   k == 0: no selection.  Otherwise ([T, k] each) the score of row r for task t is its ei value (its log EI
+ *          with ADKF_PM_LOG_EI: the same maximiser, and an order where float32 EI is 0 on every row), or with
  *          ADKF_PM_SCORE_MEAN +mean under ADKF_PM_MAXIMIZE and -mean without; top_idx[t, 0..k) are the k eligible rows of largest
  *          score in descending score, equal scores in ascending row index (a total order: the answer is unique and independent of
  *          the grid), top_val their scores.  A row is eligible unless it is listed in excl_idx[excl_off[t] .. excl_off[t + 1])
  *          (nullable; int64, each task's range sorted ascending) or its score is NaN.  With fewer than k eligible rows the tail is
  *          top_idx = -1, top_val = -inf.
- *   Tasks with n_s == 0 or info != 0: their [rows] slices are 0 (as the packed call zeroes such rows), their selection -1 / -inf.
+ *   Tasks with n_s == 0 or info != 0: their [rows] slices are 0 (as the packed call zeroes such rows; under ADKF_PM_LOG_EI too,
+ *          where that 0 is the fill value, not a logarithm), their selection -1 / -inf.
  *   scratch   adkf_predict_pool_scratch_bytes(T, k) bytes, 8-byte aligned: the candidate lists of the selection.  It depends
  *          on T and k only (at most 3 MB), never on rows; 0 for k == 0.  Nothing for the caller to initialise.
  * Rejected before anything is launched, ADKF_E_BADARG unless noted: a batch with a query set; rows < 0; rows > 0 without X; ei
  * without best_f; k > 0 ranking by ei without best_f; k < 0; k > 0 without top_idx or top_val; no output at all (mean, var, ei
- * NULL and k == 0); excl_idx without excl_off; k > ADKF_POOL_TOPK_MAX (ADKF_E_SIZE); a scratch or a workspace that is too small
- * (ADKF_E_WORKSPACE). */
+ * NULL and k == 0); ADKF_PM_LOG_EI with nothing that reads it (ei NULL and either k == 0 or ADKF_PM_SCORE_MEAN); excl_idx without
+ * excl_off; k > ADKF_POOL_TOPK_MAX (ADKF_E_SIZE); a scratch or a workspace that is too small (ADKF_E_WORKSPACE). */
 #define ADKF_PM_SCORE_MEAN 4 /* adkf_predict_pool only: rank by the posterior mean instead of ei (no best_f needed) */
+/* ADKF_PM_LOG_EI (16, defined above): ei [T, rows], the EI score and so top_val are log EI; eligibility, order and tail unchanged */
 #define ADKF_POOL_TOPK_MAX 64
 size_t adkf_predict_pool_scratch_bytes(int32_t T, int32_t k);
 int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, float* mean, float* var, float* ei, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
