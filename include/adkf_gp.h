@@ -461,13 +461,18 @@ int adkf_clip_adam_step_one(float* p, float* g, float* m, float* v, int64_t n, f
 /* a1 / a2 (the dense layers of the feature extractor and of the fc head: torch.nn.Linear, fs_mol/modules/gnn.py:477-515,
  * fs_mol/modules/graph_readout.py, fs_mol/models/adaptive_dkt.py:50-65) with FP32 products on the BF16 matrix pipe (csrc/dense_x3.h,
  * csrc/gemm_x3.h: a float is the exact sum of three bfloat16 values; six BF16 MFMAs per product block; errors below the FP32 GEMM's).
- *   adkf_split_planes         planes[q][r][k], q = 0..2: the three bfloat16 pieces of x[r][k] (x0 = bf16(x), x1 = bf16(x - x0), x2 = the rest:
- *                       their sum is x exactly).  `planes`: 3 * rows * K uint16, 16-byte aligned; K even.
+ *   adkf_split_planes         planes[q][r][k], q = 0..2: the three bfloat16 pieces of x[r][k] (x0 = bf16(x), x1 = bf16(x - x0), x2 = the rest,
+ *                       every cut rounding to nearest even: their sum is x exactly for |x| >= 2^-108 and for 0; below that a piece is a
+ *                       bfloat16 denormal and nothing is promised).  `planes`: 3 * rows * K uint16, 16-byte aligned; K even; rows * K a
+ *                       multiple of 8; x 8-byte aligned.
  *   adkf_split_planes_t       the same from the transpose: w[K][N] (a weight stored input-major, as torch.matmul(x, w) takes it) ->
  *                       planes[q][n][k], i.e. the planes adkf_dense_forward wants for y = x w.  K even; N * K a multiple of 8.
  *   adkf_dense_forward  y[M, N] = x[M, K] w[N, K]^T (+ bias[N]): torch's F.linear, with w given as the planes adkf_split_planes wrote
  *                       (weights are split once per update, activations on the fly).  K a multiple of 32; ldx, ldy the row strides
- *                       of x, y in floats (ldx a multiple of 4); x, y, w_planes 16-byte aligned.  The backward product with respect to x is
+ *                       of x, y in floats (ldx a multiple of 4); x and w_planes 16-byte aligned, y 4-byte aligned (the stores are 16-byte wide where y and ldy
+ *                       allow it).  A row of x that holds a non-finite value - or a finite one above bfloat16's largest finite value,
+ *                       3.3895e38, whose first piece is inf - gives non-finite outputs in that row of y and nowhere else; the same holds
+ *                       for a row of w and its column of y.  The backward product with respect to x is
  *                       the same call on the planes of w^T.  Returns ADKF_E_LAUNCH when the device refuses the kernel's 120 KB of
  *                       dynamic LDS.  Short contractions over many rows (K = 64, 128 or 256 and at least one 128-row tile per CU) take a
  *                       persistent form of the kernel (k_dense3_sk: a row tile's whole K extent in registers); the results are the same bits. */

@@ -241,3 +241,53 @@ def test_message_backward_chunking_is_a_function_of_E_alone(lib):
         for Es in ((0, 1, 512, 513), (4100, 32768, 32769), (32769, 0, 4100, 513)):
             ptr, keep = _msg_table(Es, True)
             assert lib.adkf_msg_backward_scratch_bytes(ptr, len(Es), H, inn, out) == 4 * sum(nsplit[E] for E in Es) * per, Es
+
+
+# ---- the dense entries (csrc/dense_x3.h): rejected arguments return before any launch -----------------------------------------------
+def test_split_entries_reject_bad_arguments(lib):
+    import ctypes as C
+    x, planes = C.c_void_p(4096), C.c_void_p(8192)
+    for fn in (lib.adkf_split_planes, lib.adkf_split_planes_t):
+        assert fn(None, planes, 8, 8, None) == _E_BADARG and fn(x, None, 8, 8, None) == _E_BADARG
+        for a, b in ((0, 8), (8, 0), (-8, 8), (8, -8)):
+            assert fn(x, planes, a, b, None) == _E_BADARG, (a, b)
+        assert fn(x, C.c_void_p(8192 + 8), 8, 8, None) == _E_BADARG                 # planes: 16-byte aligned
+    assert lib.adkf_split_planes(x, planes, 8, 7, None) == _E_BADARG                # K odd
+    assert lib.adkf_split_planes_t(x, planes, 7, 8, None) == _E_BADARG
+    assert lib.adkf_split_planes(x, planes, 1, 4, None) == _E_BADARG                # rows K not a multiple of 8
+    assert lib.adkf_split_planes(x, planes, 3, 6, None) == _E_BADARG
+    assert lib.adkf_split_planes_t(x, planes, 2, 3, None) == _E_BADARG              # N K not a multiple of 8
+    assert lib.adkf_split_planes(C.c_void_p(4096 + 4), planes, 8, 8, None) == _E_BADARG      # x: 8-byte aligned (pairs)
+    assert lib.adkf_split_planes_t(C.c_void_p(4096 + 2), planes, 8, 8, None) == _E_BADARG    # w: a float
+
+
+def test_dense_forward_rejects_bad_arguments(lib):
+    import ctypes as C
+    x, planes, bias, y = _dummy(4)
+    M, N, K = 5, 3, 32
+    call = lambda x=x, ldx=K, planes=planes, y=y, ldy=N, M=M, N=N, K=K: lib.adkf_dense_forward(x, ldx, planes, bias, y, ldy, M, N, K, None)
+    for kw in (dict(x=None), dict(planes=None), dict(y=None), dict(M=0), dict(N=0), dict(K=0, ldx=0), dict(M=-1), dict(N=-3), dict(K=-32),
+               dict(ldx=K - 4), dict(ldy=N - 1)):
+        assert call(**kw) == _E_BADARG, kw
+    for kw in (dict(K=48, ldx=48), dict(K=31, ldx=32), dict(ldx=K + 1), dict(ldx=K + 2)):      # K a multiple of 32, ldx of 4
+        assert call(**kw) == _E_SIZE, kw
+    for kw in (dict(x=C.c_void_p(4096 + 8)), dict(x=C.c_void_p(4096 + 4)), dict(planes=C.c_void_p(8192 + 8)), dict(planes=C.c_void_p(8192 + 2))):
+        assert call(**kw) == _E_BADARG, kw
+
+
+def test_dense_weight_grad_rejects_bad_arguments_and_a_short_scratch(lib):
+    g, x, dw, scratch = _dummy(4)
+    M, N, K = 300, 5, 7
+    need = lib.adkf_dense_weight_grad_scratch_bytes(M, N, K)
+    assert need >= 4 * N * K and need % (4 * N * K) == 0
+    call = lambda g=g, ldg=N, x=x, ldx=K, dw=dw, M=M, N=N, K=K, scratch=scratch, nb=need: lib.adkf_dense_weight_grad(
+        g, ldg, x, ldx, dw, M, N, K, scratch, nb, None)
+    for kw in (dict(g=None), dict(x=None), dict(dw=None), dict(scratch=None), dict(M=0), dict(N=0), dict(K=0), dict(M=-1), dict(N=-1),
+               dict(K=-1), dict(ldg=N - 1), dict(ldx=K - 1)):
+        assert call(**kw) == _E_BADARG, kw
+    assert call(nb=need - 1) == _E_WORKSPACE and call(nb=0) == _E_WORKSPACE
+    for M, N, K in ((1, 1, 1), (4099, 33, 70), (8193, 8, 8)):
+        need = lib.adkf_dense_weight_grad_scratch_bytes(M, N, K)
+        assert need > 0 and call(M=M, N=N, K=K, ldg=N, ldx=K, nb=need - 1) == _E_WORKSPACE
+    for shape in ((0, 8, 8), (8, 0, 8), (8, 8, 0), (-1, 8, 8), (8, -1, 8), (8, 8, -1)):
+        assert lib.adkf_dense_weight_grad_scratch_bytes(*shape) == 0, shape
