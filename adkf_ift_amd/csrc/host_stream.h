@@ -1,0 +1,329 @@
+// Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool and
+// their ARD forms): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
+#pragma once
+#include "host_ard.h"
+
+namespace {
+
+constexpr int PM_POOL_LISTS = 4096;   // cap of the candidate lists of a call (the scratch size must not depend on the device)
+inline int pm_pool_chunks_max(int T) { return std::max(1, PM_POOL_LISTS / T); }
+// the workgroups per task of the float64 kernels: four rows per workgroup and pass
+inline int pm64_grid(int64_t rows) { return (int)std::min<int64_t>(64, (rows + PM64_WAVES - 1) / PM64_WAVES); }
+
+// adkf_predict_marginal borrows regions of a support-only workspace that prediction does not read - [P, W_ss] and, beyond 128
+// points, the blocked sweep's scratch [lg_Dinv, lg_F] - for its row-tile slots.  Both spans are checked here against every
+// buffer prediction reads (a reorder of carve() that broke that makes the span unusable instead of silently overwritten).
+// also_read: further buffers the kernels read (adkf_predict_marginal_ard: the ARD region's mu, il, l and Zt_s, carved after
+// the base carve).
+struct SlotRegion { float* base; size_t floats; };
+void pm_slot_regions(const Workspace& w, int T, int ns, SlotRegion (&r)[2], const SlotRegion* also_read = nullptr, int n_also = 0) {
+    const size_t Tz = (size_t)T;
+    r[0] = {w.P, (size_t)(w.Wss - w.P) + Tz * ns * ns};
+    r[1] = {w.lg_Dinv, w.lg_Dinv ? (size_t)(w.lg_F - w.lg_Dinv) + Tz * LB * w.vld : 0};
+    const char* rd[][2] = {   // [begin, end) of what the prediction kernels and k_refine64 (level 0) read or keep
+        {reinterpret_cast<const char*>(w.mean), reinterpret_cast<const char*>(w.D2ss)},   // (mean [T, d] is carved first, D2ss right after)
+        {reinterpret_cast<const char*>(w.D2ss), reinterpret_cast<const char*>(w.D2ss + Tz * ns * ns)},
+        {reinterpret_cast<const char*>(w.Ainv), reinterpret_cast<const char*>(w.Ainv + Tz * ns * ns)},
+        {reinterpret_cast<const char*>(w.vecs), reinterpret_cast<const char*>(w.vecs + Tz * NVEC * w.vld)},
+        {reinterpret_cast<const char*>(w.scal), reinterpret_cast<const char*>(w.scal + Tz * NSCAL)},
+        {reinterpret_cast<const char*>(w.lg_fit), reinterpret_cast<const char*>(w.lg_fit ? w.lg_fit + Tz : nullptr)},
+        {reinterpret_cast<const char*>(w.w64), reinterpret_cast<const char*>(w.w64 ? w.w64 + 2 * Tz * w.w64_stride : nullptr)}};
+    for (SlotRegion& q : r) {
+        if (!q.base || q.floats == 0) { q = {nullptr, 0}; continue; }
+        const char *b0 = reinterpret_cast<const char*>(q.base), *b1 = reinterpret_cast<const char*>(q.base + q.floats);
+        for (const auto& x : rd)
+            if (x[0] && x[0] < b1 && b0 < x[1]) { q = {nullptr, 0}; break; }
+        for (int k = 0; k < n_also && q.base; ++k) {
+            const char *x0 = reinterpret_cast<const char*>(also_read[k].base), *x1 = reinterpret_cast<const char*>(also_read[k].base + also_read[k].floats);
+            if (x0 && x0 < b1 && b0 < x1) q = {nullptr, 0};
+        }
+    }
+}
+
+// What the streaming kernels of adkf_predict_marginal(_ard), adkf_predict_pool and adkf_thompson_pool run on, once pm_prepare has
+// put the inner quantities of the support-only batch into the workspace.
+struct PmCtx {
+    adkf_batch_t b;             // the batch the kernels see; ARD: the scaled batch (Z_s = Zt_s)
+    Workspace w;
+    const float* mean_s;        // the support column means
+    bool ard;
+    PmArd r;                    // ARD: the query scaling
+    SlotRegion also_read[4];    // ARD: the buffers of the ARD region the kernels read (kept out of the row-tile slots)
+    int n_also;
+    hipStream_t st;
+};
+
+// The inner quantities of b into its workspace (or the fit's, with REUSE_INNER) and the float64 A^-1 and alpha of flagged tasks.  ARD:
+// PmCtx::r names the query scaling, whose 1 / l pm_launch writes into ArdWs::c (not read by prediction otherwise).
+int pm_prepare(const adkf_batch_t* b, const float* phi, int32_t* info, void* ws, size_t ws_bytes, void* stream, PmCtx& c) {
+    c.st = static_cast<hipStream_t>(stream);
+    c.ard = is_ard(b);
+    c.r = PmArd{};
+    c.n_also = 0;
+    int rc;
+    if (c.ard) {
+        ArdCtx ac;
+        rc = ard_setup(b, ws, ws_bytes, c.st, ac);   // (checks the workspace size before it launches anything)
+        if (rc) return rc;
+        if (b->flags & ADKF_BATCH_REUSE_INNER) {   // the fit's state: mu, Zt_s, D2ss, A^-1, alpha, the scalars (ard_fit ends with an evaluation at phi*)
+            k_ard_params<<<dim3(ceil_div(ac.d, 256), ac.T), 256, 0, c.st>>>(ac.v, phi);
+            hipMemsetAsync(info, 0, sizeof(int32_t) * (size_t)ac.T, c.st);
+        } else {
+            rc = ard_inner(ac, phi, info);
+            if (rc) return rc;
+        }
+        const size_t td = (size_t)ac.T * ac.d;
+        c.b = ac.bt; c.w = ac.w; c.mean_s = ac.a.mu;
+        c.r = PmArd{ac.a.c, ac.a.ell};
+        c.also_read[0] = {ac.a.mu, td}; c.also_read[1] = {ac.a.ell, td}; c.also_read[2] = {ac.a.c, td}; c.also_read[3] = {ac.a.Zt_s, td * ac.ns};
+        c.n_also = 4;
+    } else {
+        c.w = carve_for(b, ws);
+        if (ws_bytes < c.w.bytes) return ADKF_E_WORKSPACE;
+        rc = stage_dist(b, c.w, false, c.st);
+        if (rc) return rc;
+        rc = inner_stage(b, c.w, phi, info, true, c.st);
+        if (rc) return rc;
+        c.b = *b; c.mean_s = c.w.mean;
+    }
+    // flagged tasks: float64 A^-1 and alpha (a no-op re-evaluation after a fit that already ran it; needed after DEFER_REFINE, and
+    // ard_fit does not run it)
+    launch_refine(make_tv(&c.b, c.w, false), &c.b, c.w, false, 0, nullptr, info, c.st);
+    LAUNCH_OK();
+    return 0;
+}
+
+// The kernel arguments that do not depend on the call's outputs; Zq [rows, d]: the packed query rows or the shared pool.
+PmArgs pm_args(const PmCtx& c, int32_t flags, const float* Zq, int64_t rows, const int32_t* info) {
+    const adkf_batch_t& b = c.b;
+    PmArgs pa{};
+    pa.Zq = Zq; pa.Zs = b.Z_s; pa.mean_s = c.mean_s; pa.rows = rows;
+    pa.n_s = b.n_s; pa.ns_ld = b.ns_max; pa.d = b.d; pa.kind = b.kernel; pa.T = b.T;
+    pa.Ainv = c.w.Ainv; pa.D2ss = c.w.D2ss; pa.y_s = b.y_s; pa.scal = c.w.scal;
+    pa.info = info;
+    pa.refine_thresh = refine32_threshold(); pa.r64_thresh = c.w.w64 ? r64_threshold() : INFINITY;
+    pa.latent = (flags & ADKF_PM_LATENT) ? 1 : 0; pa.maximize = (flags & ADKF_PM_MAXIMIZE) ? 1 : 0;
+    pa.log_ei = (flags & ADKF_PM_LOG_EI) ? 1 : 0;
+    pa.vec = ((b.d & 3) == 0 && aligned16(Zq) && aligned16(b.Z_s)) ? 1 : 0;
+    pa.buf_ld = ceil_div(b.ns_max, PM_TM) * PM_TM + 4;
+    pa.w64 = c.w.w64; pa.w64_stride = c.w.w64_stride;
+    return pa;
+}
+
+// ARD: the query scaling il = 1 / l, into ArdWs::c
+void launch_ard_il(const PmCtx& c) {
+    const size_t td = (size_t)c.b.T * c.b.d;
+    k_pm_ard_il<<<(unsigned)((td + 255) / 256), 256, 0, c.st>>>(c.r.ell, const_cast<float*>(c.r.il), (int64_t)td);
+}
+
+// The rows and outputs of a prediction call.  POOL (adkf_predict_pool): Zq is the shared pool, q_off unused, mean / var / ei are
+// [T, rows] and nullable, *pool carries the selection (its grid[] is filled by pm_launch).
+struct PmCall {
+    int32_t flags;
+    const float* Zq; const int64_t* q_off; int64_t rows;
+    const float* best_f;
+    float *mean, *var, *ei;
+    int32_t* info;
+    PmPool* pool;
+};
+
+// The streaming launches of a prepared call.
+template <bool ARD, bool POOL = false>
+int pm_launch(const PmCtx& c, const PmCall& io) {
+    const Workspace& w = c.w;
+    hipStream_t st = c.st;
+    PmPool* pool = io.pool;
+    const int T = c.b.T, ns = c.b.ns_max;
+    const int64_t rows = io.rows;
+    if constexpr (ARD) launch_ard_il(c);
+    PmArgs pa = pm_args(c, io.flags, io.Zq, rows, io.info);
+    pa.q_off = io.q_off; pa.best_f = io.best_f; pa.mean = io.mean; pa.var = io.var; pa.ei = io.ei;
+    const int ns_pad = pa.buf_ld - 4;
+    constexpr int static_lds = (2 * PM_TM * LD_MN + 2 * PM_TM + 4 * PM_TM) * (int)sizeof(float);
+    constexpr int dyn_max = PM_LDS_BYTES - static_lds;
+    static const bool optin = lds_optin(dyn_max, {kernel_ptr(&k_predict_marginal<false, false, ARD, POOL>), kernel_ptr(&k_predict_marginal<true, false, ARD, POOL>)});
+    // upper bound of the tile count (the true one depends on q_off, which lives on the device); POOL: the number of items
+    const int64_t tiles = POOL ? ((rows + PM_TM - 1) / PM_TM) * T : rows / PM_TM + T;
+    // global row-tile slots: [P, W_ss] and, beyond 128 points, the blocked path's scratch [lg_Dinv, lg_F] - neither is read by prediction
+    // a workgroup's row tiles: K (plain); K, C and the vector A^-1 y (refined)
+    auto tile_floats = [&](bool refine) { return refine ? (size_t)2 * PM_TM * pa.buf_ld + ns_pad : (size_t)PM_TM * pa.buf_ld; };
+    auto set_slots = [&](bool refine) {
+        pa.slot_floats = tile_floats(refine);
+        SlotRegion r[2];
+        pm_slot_regions(w, T, ns, r, c.also_read, c.n_also);
+        for (int q = 0; q < 2; ++q) { pa.slots[q] = r[q].base; pa.slot_count[q] = (int)std::min<size_t>(r[q].floats / pa.slot_floats, 1 << 20); }
+        return (int64_t)pa.slot_count[0] + pa.slot_count[1];
+    };
+    auto args = [&] {
+        PmArgsOf<ARD, POOL> k{};
+        k.p = pa;
+        if constexpr (ARD) k.r = c.r;
+        if constexpr (POOL) k.s = *pool;
+        return k;
+    };
+    // every output row starts at 0: rows outside every task's range and those of skipped tasks (n_s == 0, info != 0) stay so
+    const size_t out_n = POOL ? (size_t)rows * T : (size_t)rows;
+    if (io.mean && out_n) hipMemsetAsync(io.mean, 0, sizeof(float) * out_n, st);
+    if (io.var && out_n) hipMemsetAsync(io.var, 0, sizeof(float) * out_n, st);
+    if (io.ei && out_n) hipMemsetAsync(io.ei, 0, sizeof(float) * out_n, st);
+    if constexpr (POOL) {   // every list starts empty: one that no workgroup writes holds nothing
+        if (pool->k > 0) hipMemsetAsync(pool->cand_idx, 0xff, sizeof(int64_t) * (size_t)T * pool->chunks_max * pool->k, st);
+        pool->grid[0] = pool->grid[1] = pool->grid[2] = 0;
+        pool->walked = rows > 0 ? 1 : 0;
+    }
+    auto launch = [&](auto refine_c) {
+        constexpr bool REFINE = decltype(refine_c)::value;
+        const size_t dyn = tile_floats(REFINE) * sizeof(float);
+        if (optin && dyn <= (size_t)dyn_max) {
+            int per_cu = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_predict_marginal<REFINE, false, ARD, POOL>, PM_NT, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+            const int grid = (int)std::min<int64_t>(tiles, (int64_t)num_cus() * per_cu);
+            if constexpr (POOL) pool->grid[REFINE ? 1 : 0] = grid;
+            k_predict_marginal<REFINE, false, ARD, POOL><<<grid, PM_NT, dyn, st>>>(args());
+        } else {
+            const int64_t slots = set_slots(REFINE);
+            if (slots < 1) return ADKF_E_WORKSPACE;
+            const int grid = (int)std::min<int64_t>(tiles, std::min<int64_t>(slots, (int64_t)num_cus() * 8));
+            if constexpr (POOL) pool->grid[REFINE ? 1 : 0] = grid;
+            k_predict_marginal<REFINE, true, ARD, POOL><<<grid, PM_NT, 0, st>>>(args());
+        }
+        return 0;
+    };
+    int rc;
+    if (rows > 0) {
+        if ((rc = launch(std::false_type{}))) return rc;
+        if ((rc = launch(std::true_type{}))) return rc;
+    }
+    if (w.w64 && rows > 0) {
+        int gx = pm64_grid(rows);
+        if constexpr (POOL) {
+            gx = std::min(gx, pool->chunks_max);
+            pool->grid[2] = gx;
+        }
+        k_predict_marginal64<ARD, POOL><<<dim3(gx, T), PM64_NT, 0, st>>>(args());
+    }
+    if constexpr (POOL)
+        if (pool->k > 0) k_pool_topk<<<T, 64, 0, st>>>(PmArgsOf<false, true>{pa, {}, *pool});
+    LAUNCH_OK();
+    return 0;
+}
+
+// What adkf_predict_marginal, adkf_thompson_pool (with their ARD forms) and adkf_predict_pool ask of their batch and first arguments:
+// the support set only, with its labels, priors and phi.
+int check_support_only(const adkf_batch_t* b, const float* phi, const int32_t* info, const void* ws, int64_t rows) {
+    const int rc = check_batch(b, false);
+    if (rc) return rc;
+    if (b->nq_max != 0 || b->Z_q || b->y_q || !phi || !info || !ws || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    return 0;
+}
+
+// adkf_predict_marginal and adkf_predict_marginal_ard: the same call on a batch that is (ard) or is not an ARD batch
+int predict_marginal(bool ard, const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
+                     const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (is_ard(b) != ard || !q_off) return ADKF_E_BADARG;
+    if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
+    if (ei && !best_f) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    if ((flags & ADKF_PM_LOG_EI) && !ei) return ADKF_E_BADARG;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    if (rows == 0) return 0;
+    const PmCall io{flags, Zq, q_off, rows, best_f, mean, var, ei, info, nullptr};
+    return ard ? pm_launch<true>(c, io) : pm_launch<false>(c, io);
+}
+
+// adkf_thompson_pool: the scratch is V [T, S, ns] (float32), the same in float64 for flagged tasks where the workspace of this
+// shape can have a float64 region, and one (row, score) pair per (task, chunk, sample)
+struct TsScratch { float* v; double* v64; int64_t* cand_idx; float* cand_val; size_t bytes; };
+static_assert(TS_M_MAX == ADKF_TS_FEATURES_MAX && TS_S_MAX == ADKF_TS_SAMPLES_MAX && TS_NS_MAX >= MAX_POINTS, "thompson_stream.h limits");
+inline TsScratch ts_scratch(void* base, int T, int ns, int S) {
+    Arena ar{static_cast<char*>(base), 0};
+    const size_t e = (size_t)T * S * ns, c = (size_t)T * pm_pool_chunks_max(T) * S;
+    float* v = ar.floats(e);
+    double* v64 = ar.as<double>(ns <= R64_MAXN ? e : 0);
+    int64_t* cand_idx = ar.as<int64_t>(c);
+    return {v, v64, cand_idx, ar.floats(c), ar.off};
+}
+
+// adkf_predict_pool: the scratch is the candidate lists, cand_idx [T, chunks_max, k] (int64) directly followed by cand_val (float32)
+struct PoolScratch { int64_t* cand_idx; float* cand_val; size_t bytes; };
+inline PoolScratch pool_scratch(void* base, int T, int k) {
+    const size_t n = (size_t)T * pm_pool_chunks_max(T) * k;
+    int64_t* idx = static_cast<int64_t*>(base);
+    return {idx, base ? reinterpret_cast<float*>(idx + n) : nullptr, n * (sizeof(int64_t) + sizeof(float))};
+}
+
+// The launches of a prepared Thompson call.  ARD: c.r names the query scaling, whose 1 / l goes into ArdWs::c first (as pm_launch).
+template <bool ARD>
+int ts_launch(const PmCtx& c, TsArgs& ta, int64_t rows) {
+    hipStream_t st = c.st;
+    const int T = c.b.T, ns = c.b.ns_max, S = ta.S;
+    auto args = [&] {
+        TsArgsOf<ARD> k{};
+        static_cast<TsArgs&>(k) = ta;
+        if constexpr (ARD) k.r = c.r;
+        return k;
+    };
+    if (rows > 0) {
+        if constexpr (ARD) launch_ard_il(c);
+        k_ts_resid<false, ARD><<<dim3(ns, T), 256, 0, st>>>(ta);
+        if (ta.V64) k_ts_resid<true, ARD><<<dim3(ns, T), 256, 0, st>>>(ta);
+        k_ts_solve<false><<<dim3(S, T), 256, 0, st>>>(ta);
+        if (ta.V64) k_ts_solve<true><<<dim3(S, T), 256, 0, st>>>(ta);
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ts_stream<ARD>, PM_NT, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+        const int64_t items = ((rows + PM_TM - 1) / PM_TM) * T;
+        ta.s.grid[0] = (int)std::min<int64_t>(items, (int64_t)num_cus() * per_cu);
+        ta.s.grid[2] = ta.V64 ? std::min(pm64_grid(rows), ta.s.chunks_max) : 0;
+        k_ts_stream<ARD><<<ta.s.grid[0], PM_NT, 0, st>>>(args());
+        if (ta.V64) k_ts_stream64<ARD><<<dim3(ta.s.grid[2], T), PM64_NT, 0, st>>>(args());
+    }
+    k_ts_merge<<<T, 64, 0, st>>>(ta);
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_thompson_pool and adkf_thompson_pool_ard: the same call on a batch that is (ard) or is not an ARD batch
+int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega,
+                  const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx,
+                  const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void* ws, size_t ws_bytes,
+                  void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (is_ard(b) != ard) return ADKF_E_BADARG;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!omega || !phase || !w || !eps || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
+    if (m < 64 || m > ADKF_TS_FEATURES_MAX || (m & 63)) return ADKF_E_SIZE;
+    const TsScratch l = ts_scratch(scratch, b->T, b->ns_max, S);
+    if (scratch_bytes < l.bytes) return ADKF_E_WORKSPACE;
+    if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 7u)) return ADKF_E_BADARG;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    hipStream_t st = c.st;
+    const int T = b->T, ns = b->ns_max;
+    TsArgs ta{};
+    ta.p = pm_args(c, flags, X, rows, info);
+    ta.s.excl_idx = excl_off ? excl_idx : nullptr; ta.s.excl_off = excl_off;
+    ta.s.k = S; ta.s.chunks_max = pm_pool_chunks_max(T);
+    ta.s.cand_idx = l.cand_idx; ta.s.cand_val = l.cand_val;
+    ta.s.top_idx = sel_idx; ta.s.top_val = sel_val; ta.s.walked = rows > 0 ? 1 : 0;
+    ta.omega = omega; ta.phase = phase; ta.w = w; ta.eps = eps; ta.m = m; ta.S = S;
+    ta.vec_om = ((b->d & 3) == 0 && aligned16(omega)) ? 1 : 0;
+    ta.V = l.v;
+    ta.V64 = (c.w.w64 && ns <= R64_MAXN) ? l.v64 : nullptr;
+    if (!ta.V64) ta.p.r64_thresh = INFINITY;
+    ta.paths = paths;
+    // skipped tasks keep zeros in paths; a list that no workgroup writes holds nothing
+    if (paths && rows > 0) hipMemsetAsync(paths, 0, sizeof(float) * (size_t)T * S * (size_t)rows, st);
+    hipMemsetAsync(ta.s.cand_idx, 0xff, sizeof(int64_t) * (size_t)T * ta.s.chunks_max * S, st);
+    return ard ? ts_launch<true>(c, ta, rows) : ts_launch<false>(c, ta, rows);
+}
+
+}  // namespace

@@ -12,7 +12,7 @@
 // Shape of the launch: 512-thread workgroups (what the sweep of factor_m.h needs), each half (four waves) updating one 64 x 64 tile
 // with the arithmetic of k_bgemm<ProbLgUpdate> - same operand staging, same MFMA order, same epilogue expressions: the results are
 // BIT-IDENTICAL to the three-launch path (tests/test_gpu_parity.py::test_fused_block_step_equals_three_launches), which stays
-// available (ADKF_LG_FUSED=0) for A/B runs and takes the batches whose leading dimension is not a multiple of four.
+// available (ADKF_BATCH_LG_UNFUSED) for A/B runs and takes the batches whose leading dimension is not a multiple of four.
 //
 // Visibility (MI355X: a CU's L1 is never refreshed by other CUs' stores, the XCDs' L2s are not coherent): the three tiles of the next
 // diagonal block are written WRITE-THROUGH (sc1) by whoever computes them, every storing wave drains its stores (s_waitcnt vmcnt(0)),

@@ -19,7 +19,7 @@
 // the residual, so this reassociation changes them by a relative eps32 only).  That keeps C as one more row tile and A^-1 y as
 // a vector, and saves ProbCfix's product.  The two kinds of task run in two launches of the same kernel (each skips the other's
 // tasks), so the common one needs one row tile of LDS only.  Row tiles that do not fit in LDS (beyond 512 points plain, 256
-// refined) live in per-workgroup slots carved from workspace regions prediction does not read (adkf_gp.hip: pm_slot_regions);
+// refined) live in per-workgroup slots carved from workspace regions prediction does not read (host_stream.h: pm_slot_regions);
 // the grid is then as large as the number of slots - correct, not tuned.
 //
 // Per 64-column support panel the 64 x d query tile is streamed (and its norms summed) again: ns / 64 times per tile.  At

@@ -3,19 +3,15 @@ FP32 products on the BF16 matrix pipe: ``adkf_dense_forward`` (csrc/dense_x3.h) 
 respect to the input; the weight gradient (a reduction over all rows: another operand layout) stays a library GEMM.
 
 ``linear(x, weight, bias)`` is ``F.linear`` for every shape; it takes the HIP kernel where that pays - float32 CUDA tensors, at least
-``MIN_ROWS`` rows, contraction and output widths that are multiples of 32 and at least ``MIN_K`` / ``MIN_N`` - and ``F.linear`` otherwise.
-``ADKF_X3_DENSE=0`` (read at import) sends everything to ``F.linear`` for A/B runs."""
-import os
-
+``MIN_ROWS`` rows, contraction and output widths that are multiples of 32 and at least ``MIN_K`` / ``MIN_N`` - and ``F.linear`` otherwise."""
 import torch
 import torch.nn.functional as F
 
 from . import _lib
 
-ENABLED = os.environ.get("ADKF_X3_DENSE", "1") != "0"
 # the weight gradient on the BF16 pipe as well (k_dense3_tn): measured EQUAL to the library GEMM on the C3 step (51.0 - 51.1 ms either way,
-# tools/r05_dense.sh at 4c3bc9b), so the library product stays the default; 1 selects the kernel (fixed-order partial sums: bit-reproducible)
-WEIGHT_GRAD = os.environ.get("ADKF_X3_DENSE_WGRAD", "0") == "1"
+# tools/r05_dense.sh at 4c3bc9b), so the library product stays the default; True selects the kernel (fixed-order partial sums: bit-reproducible)
+WEIGHT_GRAD = False   # tests flip it to run k_dense3_tn
 # (the fc head - 2 304 rows at C3 - measured on the kernel too: 51.1 -> 51.5 ms per step: its few row tiles do not fill the chip)
 MIN_ROWS, MIN_K, MIN_N = 4096, 512, 128   # measured at C3 (tools/r05_dense.sh at 4c3bc9b): 52.1 -> 50.9 ms per step with every such layer, 51.2 with the wide (>= 512) ones only
 
@@ -96,7 +92,7 @@ class _X3Linear(torch.autograd.Function):
 
 def takes_hip_kernel(x: torch.Tensor, weight: torch.Tensor) -> bool:
     N, K = weight.shape
-    return (ENABLED and x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= MIN_ROWS
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= MIN_ROWS
             and K >= MIN_K and K % 32 == 0 and N % 32 == 0 and N >= MIN_N)
 
 

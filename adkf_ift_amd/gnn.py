@@ -33,9 +33,9 @@ import torch.nn.functional as F
 from . import dense, gnn_ops
 
 SMALL_NUMBER = 1e-7
-_FUSED_BLOCK = __import__("os").environ.get("ADKF_GNN_FUSED_BLOCK", "1") != "0"   # diagnostics: 0 keeps the PyTorch ops in the middle of a block
-_FUSED_MP = __import__("os").environ.get("ADKF_GNN_FUSED_MP", "1") != "0"   # diagnostics: 0 keeps message functions and aggregation as two autograd nodes
-_POOL_HIDDEN = __import__("os").environ.get("ADKF_READOUT_POOL_HIDDEN", "1") != "0"   # diagnostics: 0 pools the value MLPs' outputs (round 3's order)
+_FUSED_BLOCK = True   # tests flip it: False keeps the PyTorch ops in the middle of a block
+_FUSED_MP = True   # tests flip it: False keeps message functions and aggregation as two autograd nodes
+_POOL_HIDDEN = True   # tests flip it: False pools the value MLPs' outputs (round 3's order)
 NUM_NODE_FEATURES = 32   # fs_mol/data/fsmol_dataset.py:21
 NUM_EDGE_TYPES = 3       # fs_mol/data/fsmol_dataset.py:22
 PNA_DELTA = 1.1515       # fs_mol/modules/gnn.py:237

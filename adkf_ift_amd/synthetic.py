@@ -66,8 +66,8 @@ def make_tasks(T: int, N: int, d: int, N_q: Optional[int] = None, regression: bo
     return SyntheticTasks(torch.stack(Xs), torch.stack(Xq), torch.stack(ys), torch.stack(yq), W)
 
 
-_X3_DW = __import__("os").environ.get("ADKF_X3_DW", "1") != "0"   # A/B: 0 keeps the chunked bmm + sum
-_X3_FWD = __import__("os").environ.get("ADKF_X3_FWD", "1") != "0"   # A/B: 0 keeps the forward product on the library GEMM
+_X3_DW = True   # tests flip it: False keeps the chunked bmm + sum
+_X3_FWD = True   # tests flip it: False keeps the forward product on the library GEMM
 
 
 class _ChunkedLinear(torch.autograd.Function):

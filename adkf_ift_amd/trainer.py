@@ -14,8 +14,6 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple
 
-import os
-
 import torch
 import torch.distributed as dist
 
@@ -166,7 +164,6 @@ class ClipAdam(torch.optim.Adam):
 
     MAX_TENSORS = 8
     ONE_MAX = 131072   # ADKF_CLIP_ADAM_ONE_MAX: a single tensor up to this size takes ONE launch (``adkf_clip_adam_step_one``)
-    FUSE_ONE = os.environ.get("ADKF_CLIP_ADAM_ONE", "1") != "0"   # A/B: 0 keeps the two launches
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, foreach=False, fused=False)
@@ -228,7 +225,7 @@ class ClipAdam(torch.optim.Adam):
             self._partials = torch.empty(parts * len(todo), dtype=torch.float32, device=dev)
         ptr, st = _lib.ptr, _lib.stream(dev)
         clip = float("inf") if clip_value is None else float(clip_value)
-        if self.FUSE_ONE and len(todo) == 1 and todo[0][1].numel() <= self.ONE_MAX:
+        if len(todo) == 1 and todo[0][1].numel() <= self.ONE_MAX:
             group, p = todo[0]
             state = self._adam_state(p)
             b1, b2 = group["betas"]

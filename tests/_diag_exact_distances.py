@@ -1,6 +1,6 @@
 """Diagnostics (not collected): does the accuracy of the squared distances decide the float32 error of dL/dZ on the worst task of the
 point-permutation batch?  The workspace's D^2 blocks are overwritten with float64-computed, float32-rounded ones (layout:
-csrc/adkf_gp.hip::carve) before the fit and the hypergradient run on them (REUSE_DIST)."""
+csrc/host_gp.h::carve) before the fit and the hypergradient run on them (REUSE_DIST)."""
 import os, sys
 import numpy as np
 import torch

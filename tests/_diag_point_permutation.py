@@ -1,6 +1,6 @@
 """Diagnostics (not collected by pytest): the point-permutation property of tests/test_gpu_properties.py task by task - how far the
 two float32 evaluations are apart, and how far EACH is from the float64 oracle at the same parameters, for the worst tasks.
-`python tests/_diag_point_permutation.py` on the GPU box; ADKF_X3=0 selects the FP32 distance kernel.  Uses the oracle."""
+`python tests/_diag_point_permutation.py` on the GPU box.  Uses the oracle."""
 import os
 import sys
 

@@ -1,6 +1,6 @@
 """Diagnostics (not collected by pytest): replay ONE case of tests/test_gpu_stress.py and print the error of every output of every
-task against the float64 oracle.  `python tests/_diag_stress_case.py CASE` on the GPU box; environment switches of the library
-(ADKF_X3=0 ...) apply.  Test infrastructure: uses the oracle."""
+task against the float64 oracle.  `python tests/_diag_stress_case.py CASE` on the GPU box; the library's environment thresholds
+(ADKF_R64_THRESHOLD ...) apply.  Test infrastructure: uses the oracle."""
 import os
 import sys
 

@@ -58,12 +58,12 @@ def sk_cases(cus):
 
 
 def takes_persistent_form(M, K, cus):
-    """adkf_dense_forward's own selection rule (csrc/adkf_gp.hip)."""
+    """adkf_dense_forward's own selection rule (csrc/host_dense.h)."""
     return K in (64, 128, 256) and -(-M // 128) >= cus
 
 
 def wgrad_ranges(M, N, K, cus):
-    """Row ranges of adkf_dense_weight_grad (csrc/adkf_gp.hip::dense_tn_splits); its scratch is 4 N K bytes for each."""
+    """Row ranges of adkf_dense_weight_grad (csrc/host_dense.h::dense_tn_splits); its scratch is 4 N K bytes for each."""
     tiles = -(-N // 128) * -(-K // 128)
     s = max(1, min(-(-4 * cus // tiles), (M + 127) // 128, 64))
     rps = -(-(-(-M // s)) // 32) * 32

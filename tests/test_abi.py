@@ -38,6 +38,27 @@ def test_host_only_entry_points(lib):
     assert big > 11 * 256 * 128 * 128 * 4  # the eleven N x N work matrices
 
 
+# What the size functions returned before the host layer was split by subsystem (a build of a970107): callers size their buffers by
+# them, tests and tools read the workspace by the carve order behind them.  Shapes: at most 128 points (no blocked-sweep region), more
+# than 128 (with it), more than 1024 (no float64 region), support-only batches, and more tasks than the 4096 candidate lists of a pool call.
+PINNED_SIZES = {
+    "adkf_workspace_bytes": {(4, 16, 16, 8): 794624, (256, 128, 128, 256): 625443840, (8, 1024, 0, 64): 431082240,
+                             (3, 200, 256, 24): 22236928, (2, 17, 41, 33): 649728, (1, 2048, 0, 16): 69520896},
+    "adkf_workspace_bytes_ard": {(4, 16, 0, 8): 745216, (4, 16, 16, 8): 826624, (3, 200, 0, 24): 9691136, (64, 128, 128, 256): 217598720},
+    "adkf_predict_pool_scratch_bytes": {(3, 64): 3144960, (1, 1): 49152, (5000, 8): 480000, (256, 64): 3145728},
+    "adkf_thompson_pool_scratch_bytes": {(3, 200, 16, 1024): 901632, (1, 16, 1, 64): 49664, (256, 128, 64, 4096): 28311552,
+                                         (2, 2048, 8, 128): 524288},
+    "adkf_block_combine_scratch_bytes": {(1000, 128): 12320},
+}
+
+
+@pytest.mark.skipif("ADKF_R64_MAXN" in os.environ, reason="ADKF_R64_MAXN changes the workspace sizes")
+def test_size_functions_return_the_pinned_sizes(lib):
+    for name, cases in PINNED_SIZES.items():
+        for args, nbytes in cases.items():
+            assert getattr(lib, name)(*args) == nbytes, (name, args)
+
+
 def test_bad_arguments_are_rejected_without_touching_the_gpu(lib):
     import ctypes as C
 

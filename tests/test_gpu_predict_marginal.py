@@ -72,7 +72,7 @@ R64_THRESHOLD, REFINE32_THRESHOLD = 30.0, 3.0
 
 
 def _scalars(b):
-    """The per-task scalars [T, 64] the fit left in the workspace of a support-only batch: the carve() order of adkf_gp.hip
+    """The per-task scalars [T, 64] the fit left in the workspace of a support-only batch: the carve() order of csrc/host_gp.h
     (mean, D2ss, Ainv, P, W_ss, vecs, scal; every block 256-byte aligned; the query blocks are empty)."""
     ws, _ = b.workspace()
     al = lambda nfloat: (nfloat * 4 + 255) // 256 * 256

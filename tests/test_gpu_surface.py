@@ -560,7 +560,6 @@ def test_one_launch_clip_adam_and_the_planes_it_writes(dev, shape, clip, wd):
     from adkf_ift_amd import dense
     from adkf_ift_amd.trainer import ClipAdam
 
-    assert ClipAdam.FUSE_ONE
     g = torch.Generator().manual_seed(11)
     p = torch.randn(shape, generator=g).to(dev).requires_grad_(True)
     q = p.detach().clone().requires_grad_(True)

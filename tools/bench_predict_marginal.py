@@ -49,7 +49,7 @@ def timed(fn, reps):
 
 def _refined(b):
     """[T] bool: tasks that take the refined-C step (more than 128 points, or S_CONDA above 3: problems.h ProbCres's gate); the
-    scalars sit in the support-only workspace after W_ss (carve() order of adkf_gp.hip)."""
+    scalars sit in the support-only workspace after W_ss (carve() order of csrc/host_gp.h)."""
     return (_scal(b)[:, 47] > 3.0) | (b.ns > 128)
 
 
@@ -311,7 +311,7 @@ def shape_thompson_ard(T, ns, d, rows, S, m, reps, dev, out_path=None):
 
 
 def _scal(b):
-    """The per-task scalars [T, 64] of a support-only workspace (carve() order of adkf_gp.hip; slot 45 is the pivot ratio that flags
+    """The per-task scalars [T, 64] of a support-only workspace (carve() order of csrc/host_gp.h; slot 45 is the pivot ratio that flags
     a task for the float64 path above 30)."""
     ws, _ = b.workspace()
     al = lambda nfloat: (nfloat * 4 + 255) // 256 * 256
