@@ -182,14 +182,20 @@ def run_gp_ei_bo(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int,
 @torch.no_grad()
 def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
                          kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
-                         rngs: List[np.random.Generator], acquisition: str = "ei") -> List[List[int]]:
+                         rngs: List[np.random.Generator], acquisition: str = "ei", batch: str = "topk") -> List[List[int]]:
     """``len(rngs)`` replicates of ``run_gp_ei_bo`` over the same pool at once; returns their records.  Per iteration the
     replicates' queried sets form ONE batch (initial parameters and priors as ``create_gp`` makes them for each), fitted by ONE
     ``gp_ops.fit`` with ``fit_gpytorch_scipy``'s options and scored by ONE ``gp_ops.predict_pool`` call that excludes each
     replicate's queried points and returns its ``query_batch_size`` best candidates: no EI vector ever exists.  Every replicate
     draws from its own generator in the order the sequential loop does.  ``acquisition``: as ``run_gp_ei_bo``; with ``"log_ei"``
-    the call ranks by log EI and a returned candidate counts when its score is finite and its index is not -1."""
+    the call ranks by log EI and a returned candidate counts when its score is finite and its index is not -1.
+    ``batch``: ``"topk"`` takes the ``query_batch_size`` rows of largest EI, as the sequential loop does (they tend to be
+    neighbours of the winner); ``"believer"`` takes the Kriging-believer batch of ONE ``gp_ops.believer_pool`` call instead -
+    sequential-greedy EI in which every pick is believed at its posterior mean - under the same rule for what counts.  With
+    ``query_batch_size = 1`` the two are the same loop."""
     log = _acquisition(acquisition)
+    if batch not in ("topk", "believer"):
+        raise ValueError(f"batch must be 'topk' or 'believer', got {batch!r}")
     R, n = len(rngs), x_all.shape[0]
     y_all = (y_all - y_all.mean()) / y_all.std()
     X = x_all.detach().float().contiguous()
@@ -219,12 +225,18 @@ def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
         phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
         gp_ops.check_info(info, "run_gp_ei_bo_batched fit")
         b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
-        out = gp_ops.predict_pool(b, phi, X, latent=True, best_f=torch.tensor(best, dtype=torch.float32, device=X.device),
-                                  maximize=False, want_mean=False, want_var=False, want_ei=False, topk=query_batch_size,
-                                  exclude=queried, log_ei=log)
+        best_f = torch.tensor(best, dtype=torch.float32, device=X.device)
+        if batch == "believer":
+            out = gp_ops.believer_pool(b, phi, X, best_f=best_f, q=query_batch_size, maximize=False, log_ei=log, exclude=queried)
+            top_idx, top_val = out["sel_idx"].cpu(), out["sel_val"].cpu()
+        else:
+            out = gp_ops.predict_pool(b, phi, X, latent=True, best_f=best_f, maximize=False, want_mean=False, want_var=False,
+                                      want_ei=False, topk=query_batch_size, exclude=queried, log_ei=log)
+            top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
         gp_ops.check_info(out["info"], "BO posterior")
-        top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
         usable = (torch.isfinite(top_val) & (top_idx >= 0)) if log else top_val > 0   # (a prefix of each row: descending scores)
+        if batch == "believer":   # a believer score can round above its predecessor: keep the prefix
+            usable = usable.long().cumprod(1).bool()
         for r, rng in enumerate(rngs):
             nonzero = int(usable[r].sum())   # of the query_batch_size best: all that the branches below distinguish
             if nonzero == 0:

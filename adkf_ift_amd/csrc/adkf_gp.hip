@@ -24,6 +24,7 @@
 #include "dense_x3.h"
 #include "predict_stream.h"
 #include "thompson_stream.h"
+#include "believer_stream.h"
 
 #include "host_common.h"
 #include "host_gp.h"
@@ -270,6 +271,19 @@ int adkf_thompson_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flag
                            void* scratch, size_t scratch_bytes, void* stream) {
     return thompson_pool(true, b, phi, flags, X, rows, omega, phase, m, w, eps, S, excl_idx, excl_off, paths, sel_idx, sel_val, info, ws,
                          ws_bytes, scratch, scratch_bytes, stream);
+}
+
+size_t adkf_believer_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t q) {
+    if (T <= 0 || ns_max <= 0 || ns_max > MAX_POINTS || d <= 0 || q < 1 || q > ADKF_POOL_TOPK_MAX) return 0;
+    return bv_scratch(nullptr, T, ns_max, d, q).bytes;
+}
+
+int adkf_believer_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
+                       const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
+                       float* sel_mean, float* sel_var, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes,
+                       void* stream) {
+    return believer_pool(b, phi, flags, X, rows, best_f, excl_idx, excl_off, q, trace, sel_idx, sel_val, sel_mean, sel_var, info, ws, ws_bytes,
+                         scratch, scratch_bytes, stream);
 }
 
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

@@ -1,0 +1,344 @@
+// Kriging-believer batch selection over a shared pool (adkf_believer_pool): q sequential-greedy EI picks per task, each pick
+// "believed" at its posterior mean (Ginsbourger, Le Riche and Carraro 2010).  The mean never changes; the latent variance of every
+// pool row shrinks by a rank-one downdate per pick, and the incumbent moves to the believed value.  With p_0 .. p_(j-1) the picks of
+// task t so far (x_p their pool rows), A = K_ss + noise I:
+//     w_i      = A^-1 k(Z_s, x_(p_i))
+//     c0(x, i) = k(x, x_(p_i)) - k(x, Z_s) . w_i                 posterior covariance of x and pick i
+//     G G^T    = [c0(x_(p_i), l)] + noise I                      G lower triangular, one new row per pick
+//     ell(x)   = G^-1 c0(x, .)                                   forward substitution, i ascending
+//     v_j(x)   = v_0(x) - sum_(i<j) ell_i(x)^2                   score_j(x) = EI(m(x), v_j(x), best_j) (pm_ei / pm_log_ei)
+// Per step j: the pool walks of prediction (plain, refined, float64 - pm_kind_of), then one workgroup per task (k_bv_step).  The
+// launch boundaries order the steps; nothing is atomic, every sum has a fixed order, and nothing of size T x rows is kept.
+//
+//   the walk  is k_predict_marginal's tile itself (K row tile, C = K A^-1, the two reductions, REFINE's correction) with
+//             BvEpilogue in the place of prediction's epilogue.  With c picks made, it adds F = K_tile W^T (pm_mm over the row tile,
+//             W the picks' w rows, [q, ns]) and the kernel panel of the tile against the picks (pm_k_panel with the picks' stored
+//             feature rows as its "support"); c0 = Kxp - F goes into pm_mm's two staging buffers, which are adjacent and free by then
+//             (a [64, 65] panel in 2 * 64 * 34 floats), so the instance needs NO LDS beyond prediction's: its row tiles move to the
+//             global slots at prediction's sizes (host_stream.h derives both from the same expression).  Thread i < 64 then runs the
+//             substitution of row i against G (uniform loads), takes v_j and the score, and the first wave merges the scores into the
+//             walk's one-entry list; the exclusion test also scans the picks made so far.  At c = 0 none of this runs and the row's
+//             score is prediction's, bit for bit.
+//   float64   tasks (refine64.h) take k_bv_walk64, k_predict_marginal64's wave-per-row loop with float64 w and G: lane i forms
+//             c0(x, i), the substitution runs over the lanes (row i of G against the ell broadcast so far).
+//   k_bv_step merges the chunks' pairs under pm_beats, writes sel_*, forms k(Z_s, x_p) from the features in float64, solves
+//             w = A^-1 k (float32 tasks: k_ts_solve's product and ONE refinement step with A regenerated from D2ss; flagged tasks:
+//             k_refine64's float64 A^-1), takes the pick's mean w . y and variance s - k . w - |ell|^2 from it, and stores the pick's
+//             feature row, the new row of G (G[j, :j] = ell, G[j, j] = sqrt(v_j + noise)), the new incumbent and the pick count.  With
+//             no eligible row it reports -1 / -inf and changes nothing, so every later step does the same.
+#pragma once
+#include "thompson_stream.h"
+
+namespace adkf {
+
+constexpr int BV_LDC = PM_TM + 1;      // leading dimension of the c0 panel (a thread per row walks it: no bank conflicts)
+static_assert(PM_TM * BV_LDC <= 2 * PM_TM * LD_MN, "the c0 panel lives in pm_mm's staging buffers");
+
+struct BvArgs {
+    int q, j;                           // picks per task; the step of this launch
+    float* W; double* W64;              // [T, q, ns_ld]: w of pick i (float64 tasks: W64; null without a float64 region)
+    float* Xp;                          // [T, q, d]: the picks' feature rows
+    float* G; double* G64;              // [T, q, q] lower triangular
+    float* best; int32_t* cnt;          // [T]: the incumbent and the picks made
+    float* trace;                       // nullable [T, q, rows]
+    int64_t* sel_idx; float *sel_val, *sel_mean, *sel_var;   // [T, q]; the last two nullable
+};
+struct BvEpilogue;
+using BvKargs = PmArgsOf<false, true, BvEpilogue>;   // p.Zq: the pool; s.k = 1, s.cand_* [T, chunks_max]
+
+__device__ __forceinline__ bool bv_picked(const BvArgs& v, int t, int c, long long r) {
+    for (int i = 0; i < c; ++i)
+        if (v.sel_idx[(size_t)t * v.q + i] == r) return true;
+    return false;
+}
+__device__ __forceinline__ float bv_score(const PmArgs& a, const BvArgs& v, int t, float mean, float vl) {
+    return a.log_ei ? pm_log_ei(mean, vl, v.best[t], a.maximize) : pm_ei(mean, vl, v.best[t], a.maximize);
+}
+__device__ __forceinline__ double bv_kappa64(int kind, double u) {
+    if (kind == ADKF_KERNEL_RBF) return exp(-0.5 * u);
+    const double rr = sqrt(u);
+    return (1.0 + 2.23606797749979 * rr + (5.0 / 3.0) * u) * exp(-2.23606797749979 * rr);
+}
+
+struct BvEpilogue {
+    using Args = BvArgs;
+    template <bool ARD, bool POOL, class ARGS, class WALK>
+    static __device__ __forceinline__ void run(const ARGS& args, const PmTile& tl, WALK& walk, f32x4 (&acc)[2][2]) {
+        static_assert(!ARD && POOL, "adkf_believer_pool: isotropic batches over a shared pool");
+        const PmArgs& a = args.p;
+        const BvArgs& v = args.v;
+        const int tid = threadIdx.x, t = tl.t, q = v.q;
+        const int c = v.cnt[t];   // (uniform) picks made, at most the step
+        float* C0 = tl.As;
+        if (c > 0) {
+            // ---- F = K_tile W^T over the row tile, then the kernel panel against the picks, c0 = Kxp - F
+            const float* Wt = v.W + (size_t)t * q * a.ns_ld;
+            const float* Kb = tl.Kb;
+            const int ld = tl.ld, n = tl.n, ns_ld = a.ns_ld;
+            float dummy[2];
+            pm_mm<false>(acc, tl.nk, tl.As, tl.Bs,
+                [=](int i, int k, float (&x)[4]) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) x[e] = Kb[(size_t)i * ld + k + e];
+                },
+                [=](int i, int k, float (&x)[4]) {
+                    if (i >= c) { x[0] = x[1] = x[2] = x[3] = 0.f; return; }
+                    pm_ld4(Wt + (size_t)i * ns_ld, k, n, false, x);
+                }, dummy, dummy);
+            f32x4 F[2][2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) F[i][j] = acc[i][j];
+            pm_k_panel<false>(a, v.Xp + (size_t)t * q * a.d, tl.mu, nullptr, tl.r0, tl.m, c, 0, tl.os, tl.il2, tl.As, tl.Bs, *tl.rowsq, acc,
+                              C0, BV_LDC, [] {});
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) C0[pm_row(i, r) * BV_LDC + pm_col(j)] -= F[i][j][r];   // (this thread's own elements)
+            __syncthreads();
+        }
+        float score = 0.f;
+        if (tid < tl.m) {
+            float vl = tl.os - (tl.red[0][1][tid] + tl.red[1][1][tid]);
+            const float mean = tl.red[0][0][tid] + tl.red[1][0][tid];
+            if (c > 0) {   // ell = G^-1 c0 in place, i ascending
+                const float* G = v.G + (size_t)t * q * q;
+                float* e = C0 + tid * BV_LDC;
+                float ss = 0.f;
+                for (int i = 0; i < c; ++i) {
+                    float s = e[i];
+                    for (int l = 0; l < i; ++l) s = fmaf(-G[i * q + l], e[l], s);
+                    s /= G[i * q + i];
+                    e[i] = s;
+                    ss = fmaf(s, s, ss);
+                }
+                vl -= ss;
+            }
+            score = bv_score(a, v, t, mean, vl);
+            if (v.trace) v.trace[((size_t)t * q + v.j) * (size_t)a.rows + (size_t)(tl.r0 + tid)] = score;
+        }
+        if ((tid >> 6) == 0)
+            pm_list_merge(walk.lv, walk.li, 1, score, (long long)(tl.r0 + tid), tid < tl.m,
+                          [&](long long r) { return pm_excluded(args.s, t, r) || bv_picked(v, t, c, r); });
+    }
+};
+
+// ---- flagged tasks: k_predict_marginal64's loop (grid (chunks, T), one wave per pool row) with the downdate in float64
+__global__ __launch_bounds__(PM64_NT) void k_bv_walk64(BvKargs args) {
+    const PmArgs& a = args.p;
+    const BvArgs& v = args.v;
+    __shared__ double kr[PM64_WAVES][R64_MAXN];
+    float lv = -INFINITY;
+    long long li = -1;
+    const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, q = v.q;
+    if (pm_kind_of(a, t) != 2) return;   // (uniform)
+    const int n = pm_ns(a, t), ld = a.ns_ld;
+    if (n <= 0 || n > R64_MAXN) return;
+    const int c = v.cnt[t];
+    const float* sc = a.scal + (size_t)t * NSCAL;
+    const double os = sc[S_OS], ls = sc[S_LS], il2 = 1.0 / (ls * ls);
+    const double* A1 = a.w64 + (size_t)t * a.w64_stride;   // float64 A^-1 [ld, ld]
+    const float* Zs = a.Zs + (size_t)t * ld * a.d;
+    const float* ys = a.y_s + (size_t)t * ld;
+    const double* Wt = v.W64 + (size_t)t * q * ld;
+    const double* G = v.G64 + (size_t)t * q * q;
+    const float* Xp = v.Xp + (size_t)t * q * a.d;
+    double* k = kr[wv];
+    for (int64_t r = (int64_t)blockIdx.x * PM64_WAVES + wv; r < a.rows; r += (int64_t)gridDim.x * PM64_WAVES) {
+        const float* zq = a.Zq + (size_t)r * a.d;
+        pm64_kernel_row<false>(a, zq, Zs, n, nullptr, nullptr, os, il2, k);
+        double s1 = 0.0, s2 = 0.0;
+        for (int j = lane; j < n; j += 64) {
+            double cc = 0.0;
+            for (int i = 0; i < n; ++i) cc += k[i] * A1[(size_t)i * ld + j];
+            s1 += cc * (double)ys[j];
+            s2 += cc * k[j];
+        }
+        for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+        double vl = os - s2;
+        if (c > 0) {
+            double c0 = 0.0;   // lane i: c0(x, i)
+            if (lane < c) {
+                const float* xp = Xp + (size_t)lane * a.d;
+                double s = 0.0, f = 0.0;
+                for (int e = 0; e < a.d; ++e) { const double df = (double)zq[e] - (double)xp[e]; s += df * df; }
+                for (int i = 0; i < n; ++i) f += k[i] * Wt[(size_t)lane * ld + i];
+                c0 = os * bv_kappa64(a.kind, s * il2) - f;
+            }
+            double part = 0.0, ss = 0.0;   // lane i: sum_(l < i) G[i, l] ell_l so far
+            for (int i = 0; i < c; ++i) {
+                double e = lane == i ? (c0 - part) / G[(size_t)i * q + i] : 0.0;
+                e = __shfl(e, i);
+                if (lane > i && lane < c) part += G[(size_t)lane * q + i] * e;
+                ss += e * e;
+            }
+            vl -= ss;
+        }
+        float score = 0.f;
+        if (lane == 0) {
+            score = bv_score(a, v, t, (float)s1, (float)vl);
+            if (v.trace) v.trace[((size_t)t * q + v.j) * (size_t)a.rows + (size_t)r] = score;
+        }
+        pm_list_merge(lv, li, 1, score, (long long)r, lane == 0, [&](long long x) { return pm_excluded(args.s, t, x) || bv_picked(v, t, c, x); });
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    }
+    pm64_gather_lists(lv, li, [&](float x, long long i) { pm_list_merge(lv, li, 1, x, i, i >= 0, [](long long) { return false; }); });
+    if (wv == 0) pm_list_store(args.s, t, blockIdx.x, lane, 1, lv, li);
+}
+
+// the per-task state before step 0
+__global__ __launch_bounds__(256) void k_bv_init(BvArgs v, const float* best_f, int T) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < T) { v.cnt[t] = 0; v.best[t] = best_f[t]; }
+}
+
+// the sum of x over the workgroup's 256 threads in a fixed order, to every thread
+__device__ __forceinline__ double bv_block_sum(double x, double* red) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    red[tid] = x;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// ---- the end of step j: one workgroup per task (see the top of the file)
+__global__ __launch_bounds__(256) void k_bv_step(BvKargs args) {
+    const PmArgs& a = args.p;
+    const PmPool& s = args.s;
+    const BvArgs& v = args.v;
+    __shared__ __attribute__((aligned(16))) float fb[3 * TS_NS_MAX];
+    __shared__ double red[256];
+    __shared__ double c0s[PM_TOPK_MAX];
+    __shared__ long long pick_s;
+    __shared__ float val_s;
+    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, q = v.q;
+    const size_t o = (size_t)t * q + v.j;
+    if (wv == 0) {   // the task's lists under the total order (skipped tasks, and every task when no walk ran, have none)
+        const int C = pm_task_chunks(a, s, t, true);
+        float lv = -INFINITY;
+        long long li = -1;
+        const size_t base = (size_t)t * s.chunks_max;
+        for (int e0 = 0; e0 < C; e0 += 64) {
+            const int e = e0 + lane;
+            const bool in = e < C;
+            const long long r = in ? (long long)s.cand_idx[base + e] : -1;
+            const float x = in ? s.cand_val[base + e] : 0.f;
+            pm_list_merge(lv, li, 1, x, r, r >= 0, [](long long) { return false; });
+        }
+        if (lane == 0) { pick_s = li; val_s = lv; }
+    }
+    __syncthreads();
+    const long long p = pick_s;
+    if (p < 0) {   // (uniform) no eligible row: the state stays as it is
+        if (tid == 0) {
+            v.sel_idx[o] = -1; v.sel_val[o] = -INFINITY;
+            if (v.sel_mean) v.sel_mean[o] = 0.f;
+            if (v.sel_var) v.sel_var[o] = 0.f;
+        }
+        return;
+    }
+    const bool f64 = pm_kind_of(a, t) == 2;
+    const int n = pm_ns(a, t), ld = a.ns_ld, d = a.d, c = v.cnt[t];
+    const float* sc = a.scal + (size_t)t * NSCAL;
+    const double os = sc[S_OS], noise = sc[S_NOISE], il2 = 1.0 / ((double)sc[S_LS] * (double)sc[S_LS]);
+    const float* xp = a.Zq + (size_t)p * d;
+    const float* Zs = a.Zs + (size_t)t * ld * d;
+    const float* ys = a.y_s + (size_t)t * ld;
+    float* Xt = v.Xp + (size_t)t * q * d;
+    for (int e = tid; e < d; e += 256) Xt[(size_t)c * d + e] = xp[e];
+    float *rs = fb, *vs = fb + TS_NS_MAX, *es = fb + 2 * TS_NS_MAX;   // float32 tasks: k, then w in vs
+    double *k64 = reinterpret_cast<double*>(fb), *w64 = k64 + R64_MAXN;   // float64 tasks (n <= R64_MAXN): k and w
+    // ---- k(Z_s, x_p) from the features, in float64
+    for (int i = tid; i < n; i += 256) {
+        const float* zs = Zs + (size_t)i * d;
+        double sq = 0.0;
+        for (int e = 0; e < d; ++e) { const double df = (double)xp[e] - (double)zs[e]; sq += df * df; }
+        const double kv = os * bv_kappa64(a.kind, sq * il2);
+        if (f64) k64[i] = kv; else rs[i] = (float)kv;
+    }
+    __syncthreads();
+    // ---- w = A^-1 k
+    if (f64) {
+        const double* A1 = a.w64 + (size_t)t * a.w64_stride;
+        double* Wn = v.W64 + ((size_t)t * q + c) * ld;
+        for (int i = tid; i < n; i += 256) {
+            double x = 0.0;
+            for (int k = 0; k < n; ++k) x += A1[(size_t)k * ld + i] * k64[k];
+            w64[i] = x; Wn[i] = x;
+        }
+    } else {   // k_ts_solve's float32 product and refinement step
+        const float osf = sc[S_OS], noisef = sc[S_NOISE], il2f = 1.f / (sc[S_LS] * sc[S_LS]);
+        const float* Ai = a.Ainv + (size_t)t * ld * ld;
+        const float* Dss = a.D2ss + (size_t)t * ld * ld;
+        float* Wn = v.W + ((size_t)t * q + c) * ld;
+        for (int i = tid; i < n; i += 256) {
+            float x = 0.f;
+            for (int k = 0; k < n; ++k) x = fmaf(Ai[(size_t)k * ld + i], rs[k], x);
+            vs[i] = x;
+        }
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) {
+            float x = 0.f;
+            for (int k = 0; k < n; ++k) x = fmaf(osf * kappa0(a.kind, Dss[(size_t)k * ld + i] * il2f) + (k == i ? noisef : 0.f), vs[k], x);
+            es[i] = rs[i] - x;
+        }
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) {
+            float x = 0.f;
+            for (int k = 0; k < n; ++k) x = fmaf(Ai[(size_t)k * ld + i], es[k], x);
+            x += vs[i];
+            vs[i] = x; Wn[i] = x;   // (vs[i] is read by this thread only in this loop)
+        }
+    }
+    __syncthreads();
+    // ---- the pick's mean w . y and prior-step variance s - k . w
+    double pm = 0.0, pk = 0.0;
+    for (int i = tid; i < n; i += 256) {
+        const double wi = f64 ? w64[i] : (double)vs[i], ki = f64 ? k64[i] : (double)rs[i];
+        pm += wi * (double)ys[i];
+        pk += wi * ki;
+    }
+    const double mean = bv_block_sum(pm, red), v0 = os - bv_block_sum(pk, red);
+    // ---- c0(x_p, i) for the earlier picks: one wave per pick
+    for (int i = wv; i < c; i += 4) {
+        const float* xi = Xt + (size_t)i * d;
+        double sq = 0.0, f = 0.0;
+        for (int e = lane; e < d; e += 64) { const double df = (double)xp[e] - (double)xi[e]; sq += df * df; }
+        for (int k = lane; k < n; k += 64)
+            f += f64 ? k64[k] * v.W64[((size_t)t * q + i) * ld + k] : (double)rs[k] * (double)v.W[((size_t)t * q + i) * ld + k];
+        for (int x = 32; x > 0; x >>= 1) { sq += __shfl_xor(sq, x); f += __shfl_xor(f, x); }
+        if (lane == 0) c0s[i] = os * bv_kappa64(a.kind, sq * il2) - f;
+    }
+    __syncthreads();
+    if (tid == 0) {   // the new row of G, the outputs and the state
+        double ss = 0.0;
+        for (int i = 0; i < c; ++i) {
+            double x = c0s[i];
+            for (int l = 0; l < i; ++l) x -= (f64 ? v.G64[((size_t)t * q + i) * q + l] : (double)v.G[((size_t)t * q + i) * q + l]) * c0s[l];
+            x /= f64 ? v.G64[((size_t)t * q + i) * q + i] : (double)v.G[((size_t)t * q + i) * q + i];
+            c0s[i] = x;
+            ss += x * x;
+        }
+        const double vj = v0 - ss, gd = sqrt(fmax(vj + noise, 1e-30));
+        for (int i = 0; i <= c; ++i) {
+            const double g = i < c ? c0s[i] : gd;
+            if (f64) v.G64[((size_t)t * q + c) * q + i] = g; else v.G[((size_t)t * q + c) * q + i] = (float)g;
+        }
+        const float mf = (float)mean;
+        v.sel_idx[o] = p; v.sel_val[o] = val_s;
+        if (v.sel_mean) v.sel_mean[o] = mf;
+        if (v.sel_var) v.sel_var[o] = (float)vj;
+        v.best[t] = a.maximize ? fmaxf(v.best[t], mf) : fminf(v.best[t], mf);
+        v.cnt[t] = c + 1;
+    }
+}
+
+}  // namespace adkf

@@ -364,6 +364,14 @@ double log_h(double u) {
     return -0.5 * u * u - 0.5 * std::log(2.0 * M_PI) + std::log(w) + std::log(sum);
 }
 
+// EI (ADKF_PM_LOG_EI: log EI) of a row from its mean and latent variance
+float pm_ei(double mu, double vl, double bf, int flags) {
+    const double sg = std::sqrt(std::max(vl, 1e-12));
+    const double u = ((flags & ADKF_PM_MAXIMIZE) ? (mu - bf) : (bf - mu)) / sg;
+    if (flags & ADKF_PM_LOG_EI) return (float)(std::log(sg) + log_h(u));
+    return (float)(sg * (u * 0.5 * std::erfc(-u / std::sqrt(2.0)) + std::exp(-0.5 * u * u) / std::sqrt(2.0 * M_PI)));
+}
+
 // adkf_predict_marginal(_ard): mean, variance and EI (ADKF_PM_LOG_EI: log EI) of row r from its squared distances D [n] to the
 // support set of a task
 void pm_row(const Inner& in, int kind, const double* D, const float* y, int flags, const float* best_f, int t, int64_t r, float* mean,
@@ -382,12 +390,7 @@ void pm_row(const Inner& in, int kind, const double* D, const float* y, int flag
     const double vl = in.s - q;
     mean[r] = (float)mu;
     if (var) var[r] = (float)((flags & ADKF_PM_LATENT) ? vl : vl + in.noise);
-    if (ei) {
-        const double sg = std::sqrt(std::max(vl, 1e-12)), bf = best_f[t];
-        const double u = ((flags & ADKF_PM_MAXIMIZE) ? (mu - bf) : (bf - mu)) / sg;
-        if (flags & ADKF_PM_LOG_EI) ei[r] = (float)(std::log(sg) + log_h(u));
-        else ei[r] = (float)(sg * (u * 0.5 * std::erfc(-u / std::sqrt(2.0)) + std::exp(-0.5 * u * u) / std::sqrt(2.0 * M_PI)));
-    }
+    if (ei) ei[r] = pm_ei(mu, vl, best_f[t], flags);
 }
 
 // One task of adkf_predict_marginal(_ard) and adkf_predict_pool: inner_stage on the support set, then row(r, in, D) for the rows
@@ -778,6 +781,95 @@ int adkf_thompson_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flag
                            const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void*, size_t, void*, size_t,
                            void*) {
     return thompson_pool(true, b, phi, flags, X, rows, omega, phase, m, w, eps, S, excl_idx, excl_off, paths, sel_idx, sel_val, info);
+}
+
+size_t adkf_believer_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { return 0; }
+
+// Kriging-believer batch selection (include/adkf_gp.h): the mean, the latent variance and K A^-1 of every pool row once, then per
+// step one more column of ell (the forward substitution of the header, one row of G at a time) and the scores in float32, ranked
+// under "larger score first, equal scores by ascending row".
+int adkf_believer_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
+                       const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
+                       float* sel_mean, float* sel_var, int32_t* info, void*, size_t, void*, size_t, void*) {
+    if (int rc = check(b, false)) return rc;   // (refuses ARD batches)
+    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!best_f || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (q < 1) return ADKF_E_BADARG;
+    if (q > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    const int d = b->d;
+    const float ninf = -std::numeric_limits<float>::infinity();
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        for (int j = 0; j < q; ++j) {
+            const size_t o = (size_t)t * q + j;
+            sel_idx[o] = -1; sel_val[o] = ninf;
+            if (sel_mean) sel_mean[o] = 0.f;
+            if (sel_var) sel_var[o] = 0.f;
+        }
+        if (trace && rows > 0) std::fill(trace + (size_t)t * q * rows, trace + (size_t)(t + 1) * q * rows, 0.f);
+        const int n = std::min(ns_of(b, t), b->ns_max);
+        const size_t R = (size_t)rows;
+        Mat Kr(R * std::max(n, 0)), Cr(R * std::max(n, 0)), mu(R), v(R), L(R * q);
+        double s = 0.0, noise = 0.0, il2 = 0.0;
+        const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
+            s = in.s; noise = in.noise; il2 = 1.0 / (in.l * in.l);
+            const float* y = b->y_s + (size_t)t * b->ns_max;
+            double* k = &Kr[(size_t)r * n];
+            double* c = &Cr[(size_t)r * n];
+            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); k[j] = in.s * k0; }
+            double m1 = 0.0, qf = 0.0;
+            for (int j = 0; j < n; ++j) {
+                double cj = 0.0;
+                for (int i = 0; i < n; ++i) cj += k[i] * in.Ainv[(size_t)i * n + j];
+                c[j] = cj;
+                m1 += cj * (double)y[j];
+                qf += cj * k[j];
+            }
+            mu[r] = m1; v[r] = in.s - qf;
+        });
+        if (!done) continue;
+        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
+        std::vector<char> taken(R, 0);
+        std::vector<float> score(R);
+        Mat G((size_t)q * q, 0.0);
+        double best = best_f[t];
+        for (int j = 0; j < q; ++j) {
+            int64_t p = -1;
+            for (int64_t r = 0; r < rows; ++r) {
+                score[r] = pm_ei(mu[r], v[r], best, flags);
+                if (trace) trace[((size_t)t * q + j) * R + r] = score[r];
+                if (score[r] != score[r] || taken[r] || (xb && std::binary_search(xb, xe, r))) continue;
+                if (p < 0 || score[r] > score[p]) p = r;   // (rows ascend: a tie keeps the lower index)
+            }
+            if (p < 0) continue;   // no eligible row: this step and all later ones keep -1 / -inf, the state (hence trace) stays
+            const size_t o = (size_t)t * q + j;
+            sel_idx[o] = p; sel_val[o] = score[p];
+            if (sel_mean) sel_mean[o] = (float)mu[p];
+            if (sel_var) sel_var[o] = (float)v[p];
+            // the new row of G, then column j of ell and the downdate for every row (the picked one included)
+            for (int l = 0; l < j; ++l) G[(size_t)j * q + l] = L[(size_t)p * q + l];
+            G[(size_t)j * q + j] = std::sqrt(v[p] + noise);
+            const Mat Dp = sqdist(X + (size_t)p * d, 1, X, (int)rows, d);
+            for (int64_t r = 0; r < rows; ++r) {
+                double k0, k1, k2;
+                kappa(b->kernel, Dp[r] * il2, k0, k1, k2);
+                double c0 = s * k0;
+                for (int i = 0; i < n; ++i) c0 -= Kr[(size_t)r * n + i] * Cr[(size_t)p * n + i];
+                for (int l = 0; l < j; ++l) c0 -= G[(size_t)j * q + l] * L[(size_t)r * q + l];
+                const double e = c0 / G[(size_t)j * q + j];
+                L[(size_t)r * q + j] = e;
+                v[r] -= e * e;
+            }
+            taken[p] = 1;
+            const double mp = (double)(float)mu[p];
+            best = (flags & ADKF_PM_MAXIMIZE) ? std::max(best, mp) : std::min(best, mp);
+        }
+    }
+    return 0;
 }
 
 static int outer_common(const adkf_batch_t* b, const float* phi, int flags, bool with_hessian, float* f_out, float* g_phi, float* dZ_s, float* dZ_q,

@@ -1,5 +1,5 @@
-// Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool and
-// their ARD forms): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
+// Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
+// ARD forms, and adkf_believer_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
 #pragma once
 #include "host_ard.h"
 
@@ -127,33 +127,64 @@ struct PmCall {
     PmPool* pool;
 };
 
+// One walk of k_predict_marginal over the tasks of one kind (REFINE: the refined ones) with the epilogue EPI (arguments v): row tiles
+// in LDS while they fit, otherwise in the global slots.  Both sizes come from the kernel's own LDS use: its static arrays, plus
+// EPI_LDS bytes of the epilogue's (0 for prediction's and for the believer's, which works in the staging buffers).  POOL: the grid
+// goes into pool->grid[REFINE].  tiles: an upper bound of the number of items.
+template <bool REFINE, bool ARD, bool POOL, class EPI = PmRowEpilogue, int EPI_LDS = 0>
+int pm_launch_walk(const PmCtx& c, PmArgs& pa, PmPool* pool, const typename EPI::Args& v, int64_t tiles) {
+    const Workspace& w = c.w;
+    hipStream_t st = c.st;
+    const int T = c.b.T, ns = c.b.ns_max;
+    const int ns_pad = pa.buf_ld - 4;
+    constexpr int static_lds = (2 * PM_TM * LD_MN + 2 * PM_TM + 4 * PM_TM) * (int)sizeof(float) + EPI_LDS;
+    constexpr int dyn_max = PM_LDS_BYTES - static_lds;
+    static const bool optin = lds_optin(dyn_max, {kernel_ptr(&k_predict_marginal<REFINE, false, ARD, POOL, EPI>)});
+    // a workgroup's row tiles: K (plain); K, C and the vector A^-1 y (refined)
+    const size_t tile_floats = REFINE ? (size_t)2 * PM_TM * pa.buf_ld + ns_pad : (size_t)PM_TM * pa.buf_ld;
+    auto args = [&] {
+        PmArgsOf<ARD, POOL, EPI> k{};
+        k.p = pa;
+        if constexpr (ARD) k.r = c.r;
+        if constexpr (POOL) k.s = *pool;
+        k.v = v;
+        return k;
+    };
+    const size_t dyn = tile_floats * sizeof(float);
+    if (optin && dyn <= (size_t)dyn_max) {
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_predict_marginal<REFINE, false, ARD, POOL, EPI>, PM_NT, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+        const int grid = (int)std::min<int64_t>(tiles, (int64_t)num_cus() * per_cu);
+        if constexpr (POOL) pool->grid[REFINE ? 1 : 0] = grid;
+        k_predict_marginal<REFINE, false, ARD, POOL, EPI><<<grid, PM_NT, dyn, st>>>(args());
+    } else {
+        // global row-tile slots: [P, W_ss] and, beyond 128 points, the blocked path's scratch [lg_Dinv, lg_F] - neither is read by prediction
+        pa.slot_floats = tile_floats;
+        SlotRegion r[2];
+        pm_slot_regions(w, T, ns, r, c.also_read, c.n_also);
+        for (int q = 0; q < 2; ++q) { pa.slots[q] = r[q].base; pa.slot_count[q] = (int)std::min<size_t>(r[q].floats / pa.slot_floats, 1 << 20); }
+        const int64_t slots = (int64_t)pa.slot_count[0] + pa.slot_count[1];
+        if (slots < 1) return ADKF_E_WORKSPACE;
+        const int grid = (int)std::min<int64_t>(tiles, std::min<int64_t>(slots, (int64_t)num_cus() * 8));
+        if constexpr (POOL) pool->grid[REFINE ? 1 : 0] = grid;
+        k_predict_marginal<REFINE, true, ARD, POOL, EPI><<<grid, PM_NT, 0, st>>>(args());
+    }
+    return 0;
+}
+
 // The streaming launches of a prepared call.
 template <bool ARD, bool POOL = false>
 int pm_launch(const PmCtx& c, const PmCall& io) {
     const Workspace& w = c.w;
     hipStream_t st = c.st;
     PmPool* pool = io.pool;
-    const int T = c.b.T, ns = c.b.ns_max;
+    const int T = c.b.T;
     const int64_t rows = io.rows;
     if constexpr (ARD) launch_ard_il(c);
     PmArgs pa = pm_args(c, io.flags, io.Zq, rows, io.info);
     pa.q_off = io.q_off; pa.best_f = io.best_f; pa.mean = io.mean; pa.var = io.var; pa.ei = io.ei;
-    const int ns_pad = pa.buf_ld - 4;
-    constexpr int static_lds = (2 * PM_TM * LD_MN + 2 * PM_TM + 4 * PM_TM) * (int)sizeof(float);
-    constexpr int dyn_max = PM_LDS_BYTES - static_lds;
-    static const bool optin = lds_optin(dyn_max, {kernel_ptr(&k_predict_marginal<false, false, ARD, POOL>), kernel_ptr(&k_predict_marginal<true, false, ARD, POOL>)});
     // upper bound of the tile count (the true one depends on q_off, which lives on the device); POOL: the number of items
     const int64_t tiles = POOL ? ((rows + PM_TM - 1) / PM_TM) * T : rows / PM_TM + T;
-    // global row-tile slots: [P, W_ss] and, beyond 128 points, the blocked path's scratch [lg_Dinv, lg_F] - neither is read by prediction
-    // a workgroup's row tiles: K (plain); K, C and the vector A^-1 y (refined)
-    auto tile_floats = [&](bool refine) { return refine ? (size_t)2 * PM_TM * pa.buf_ld + ns_pad : (size_t)PM_TM * pa.buf_ld; };
-    auto set_slots = [&](bool refine) {
-        pa.slot_floats = tile_floats(refine);
-        SlotRegion r[2];
-        pm_slot_regions(w, T, ns, r, c.also_read, c.n_also);
-        for (int q = 0; q < 2; ++q) { pa.slots[q] = r[q].base; pa.slot_count[q] = (int)std::min<size_t>(r[q].floats / pa.slot_floats, 1 << 20); }
-        return (int64_t)pa.slot_count[0] + pa.slot_count[1];
-    };
     auto args = [&] {
         PmArgsOf<ARD, POOL> k{};
         k.p = pa;
@@ -171,28 +202,10 @@ int pm_launch(const PmCtx& c, const PmCall& io) {
         pool->grid[0] = pool->grid[1] = pool->grid[2] = 0;
         pool->walked = rows > 0 ? 1 : 0;
     }
-    auto launch = [&](auto refine_c) {
-        constexpr bool REFINE = decltype(refine_c)::value;
-        const size_t dyn = tile_floats(REFINE) * sizeof(float);
-        if (optin && dyn <= (size_t)dyn_max) {
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_predict_marginal<REFINE, false, ARD, POOL>, PM_NT, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
-            const int grid = (int)std::min<int64_t>(tiles, (int64_t)num_cus() * per_cu);
-            if constexpr (POOL) pool->grid[REFINE ? 1 : 0] = grid;
-            k_predict_marginal<REFINE, false, ARD, POOL><<<grid, PM_NT, dyn, st>>>(args());
-        } else {
-            const int64_t slots = set_slots(REFINE);
-            if (slots < 1) return ADKF_E_WORKSPACE;
-            const int grid = (int)std::min<int64_t>(tiles, std::min<int64_t>(slots, (int64_t)num_cus() * 8));
-            if constexpr (POOL) pool->grid[REFINE ? 1 : 0] = grid;
-            k_predict_marginal<REFINE, true, ARD, POOL><<<grid, PM_NT, 0, st>>>(args());
-        }
-        return 0;
-    };
     int rc;
     if (rows > 0) {
-        if ((rc = launch(std::false_type{}))) return rc;
-        if ((rc = launch(std::true_type{}))) return rc;
+        if ((rc = pm_launch_walk<false, ARD, POOL>(c, pa, pool, {}, tiles))) return rc;
+        if ((rc = pm_launch_walk<true, ARD, POOL>(c, pa, pool, {}, tiles))) return rc;
     }
     if (w.w64 && rows > 0) {
         int gx = pm64_grid(rows);
@@ -324,6 +337,81 @@ int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
     if (paths && rows > 0) hipMemsetAsync(paths, 0, sizeof(float) * (size_t)T * S * (size_t)rows, st);
     hipMemsetAsync(ta.s.cand_idx, 0xff, sizeof(int64_t) * (size_t)T * ta.s.chunks_max * S, st);
     return ard ? ts_launch<true>(c, ta, rows) : ts_launch<false>(c, ta, rows);
+}
+
+// adkf_believer_pool: the scratch is w [T, q, ns] (and its float64 twin where a workspace of this shape can have a float64 region),
+// the picks' feature rows [T, q, d], G [T, q, q] (and its twin), the incumbent and the pick count per task, and one (row, score)
+// pair per (task, chunk)
+struct BvScratch { float* W; double* W64; float* Xp; float* G; double* G64; float* best; int32_t* cnt; int64_t* cand_idx; float* cand_val; size_t bytes; };
+inline BvScratch bv_scratch(void* base, int T, int ns, int d, int q) {
+    Arena ar{static_cast<char*>(base), 0};
+    const size_t e = (size_t)T * q * ns, g = (size_t)T * q * q, c = (size_t)T * pm_pool_chunks_max(T);
+    BvScratch l{};
+    l.W = ar.floats(e);
+    l.W64 = ar.as<double>(ns <= R64_MAXN ? e : 0);
+    l.Xp = ar.floats((size_t)T * q * d);
+    l.G = ar.floats(g);
+    l.G64 = ar.as<double>(ns <= R64_MAXN ? g : 0);
+    l.best = ar.floats((size_t)T);
+    l.cnt = ar.as<int32_t>((size_t)T);
+    l.cand_idx = ar.as<int64_t>(c);
+    l.cand_val = ar.floats(c);
+    l.bytes = ar.off;
+    return l;
+}
+
+// adkf_believer_pool: q chained steps, each the walks of prediction with the believer's epilogue and one workgroup per task
+int believer_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
+                  const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* sel_mean,
+                  float* sel_var, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (is_ard(b)) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!best_f || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (q < 1) return ADKF_E_BADARG;
+    if (q > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    const BvScratch l = bv_scratch(scratch, b->T, b->ns_max, b->d, q);
+    if (scratch_bytes < l.bytes) return ADKF_E_WORKSPACE;
+    if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 7u)) return ADKF_E_BADARG;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    hipStream_t st = c.st;
+    const int T = b->T, ns = b->ns_max;
+    PmArgs pa = pm_args(c, flags, X, rows, info);
+    pa.best_f = best_f;
+    const bool have64 = c.w.w64 && ns <= R64_MAXN;
+    if (!have64) pa.r64_thresh = INFINITY;
+    PmPool pool{};
+    pool.excl_idx = excl_off ? excl_idx : nullptr; pool.excl_off = excl_off;
+    pool.k = 1; pool.chunks_max = pm_pool_chunks_max(T);
+    pool.cand_idx = l.cand_idx; pool.cand_val = l.cand_val;
+    pool.walked = rows > 0 ? 1 : 0;
+    BvArgs v{};
+    v.q = q;
+    v.W = l.W; v.W64 = have64 ? l.W64 : nullptr; v.Xp = l.Xp; v.G = l.G; v.G64 = have64 ? l.G64 : nullptr;
+    v.best = l.best; v.cnt = l.cnt; v.trace = trace;
+    v.sel_idx = sel_idx; v.sel_val = sel_val; v.sel_mean = sel_mean; v.sel_var = sel_var;
+    // skipped tasks keep zeros in trace; a list that no workgroup writes holds nothing
+    if (trace && rows > 0) hipMemsetAsync(trace, 0, sizeof(float) * (size_t)T * q * (size_t)rows, st);
+    hipMemsetAsync(pool.cand_idx, 0xff, sizeof(int64_t) * (size_t)T * pool.chunks_max, st);
+    k_bv_init<<<ceil_div(T, 256), 256, 0, st>>>(v, best_f, T);
+    const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
+    pool.grid[2] = (have64 && rows > 0) ? std::min(pm64_grid(rows), pool.chunks_max) : 0;
+    for (int j = 0; j < q; ++j) {
+        v.j = j;
+        if (rows > 0) {
+            if ((rc = pm_launch_walk<false, false, true, BvEpilogue>(c, pa, &pool, v, tiles))) return rc;
+            if ((rc = pm_launch_walk<true, false, true, BvEpilogue>(c, pa, &pool, v, tiles))) return rc;
+            if (have64) k_bv_walk64<<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(BvKargs{pa, {}, pool, v});
+        }
+        k_bv_step<<<T, 256, 0, st>>>(BvKargs{pa, {}, pool, v});
+    }
+    LAUNCH_OK();
+    return 0;
 }
 
 }  // namespace

@@ -58,6 +58,11 @@
 // prediction's K" hold by construction: the kernel arguments (PmArgs + the optional groups PmArd and PmPool), the pool walk
 // (PmPoolWalk, pm_task_chunks, pm_list_store), the K panel (pm_query_rows, pm_k_panel), and for flagged tasks the float64 kernel row
 // (pm64_kernel_row) and the exchange of the waves' lists (pm64_gather_lists).
+//
+// Shared with believer_stream.h: k_predict_marginal itself.  What a tile's rows become once the K row tile and the two reductions
+// are in place is the template parameter EPI: PmRowEpilogue (the default) writes prediction's outputs and merges the scores;
+// BvEpilogue downdates the variance with the picks made so far before it scores.  The instances of the default are the kernels
+// as they were, arithmetic and order.
 #pragma once
 #include <type_traits>
 
@@ -99,8 +104,11 @@ struct PmPool {
 // what a kernel receives: the groups its instance does not have are empty
 struct PmNoArd {};
 struct PmNoPool {};
-template <bool ARD, bool POOL = false>
-struct PmArgsOf { PmArgs p; std::conditional_t<ARD, PmArd, PmNoArd> r; std::conditional_t<POOL, PmPool, PmNoPool> s; };
+struct PmNoEpilogueArgs {};
+struct PmRowEpilogue;
+// EPI: what a tile's rows become once their two reductions are done (PmRowEpilogue: the outputs of prediction); v: its arguments
+template <bool ARD, bool POOL = false, class EPI = PmRowEpilogue>
+struct PmArgsOf { PmArgs p; std::conditional_t<ARD, PmArd, PmNoArd> r; std::conditional_t<POOL, PmPool, PmNoPool> s; typename EPI::Args v; };
 
 // il = 1 / l, so that the staging loop of the ARD instances multiplies instead of divides
 __global__ __launch_bounds__(256) void k_pm_ard_il(const float* ell, float* il, int64_t n) {
@@ -420,11 +428,41 @@ __device__ __forceinline__ float pm_row_out(const ARGS& args, int t, int64_t r, 
     }
 }
 
-template <bool REFINE, bool GLOBAL, bool ARD = false, bool POOL = false>
-__global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD, POOL> args) {
+// ---- one tile of k_predict_marginal when its epilogue runs: the K row tile and the two reductions are in place
+struct PmTile {
+    int t; int64_t r0;                      // the task and the tile's first row
+    int m, n, nk, ld;                       // rows of the tile, support points, their padded extent, leading dimension of Kb
+    float os, noise, il2;
+    const float *mu, *il;                   // the centring (ARD: and scaling) of the query rows
+    const float* Kb;                        // the K row tile [64, ld], zero beyond (m, n)
+    float *As, *Bs;                         // pm_mm's staging buffers, ADJACENT (2 * PM_TM * LD_MN floats from As) and free
+    float (*rowsq)[2][PM_TM];
+    float (*red)[2][PM_TM];                 // red[wc][0 | 1][row]: the halves of sum_j C_ij y_j and sum_j C_ij K_ij
+};
+
+// the epilogue of prediction: the first 64 threads write the outputs of their row; POOL: the first wave merges the scores into the walk's list
+struct PmRowEpilogue {
+    using Args = PmNoEpilogueArgs;
+    template <bool ARD, bool POOL, class ARGS, class WALK>
+    static __device__ __forceinline__ void run(const ARGS& args, const PmTile& tl, WALK& walk, f32x4 (&)[2][2]) {
+        const int tid = threadIdx.x;
+        [[maybe_unused]] float score = 0.f;
+        if (tid < tl.m) {
+            const float vl = tl.os - (tl.red[0][1][tid] + tl.red[1][1][tid]);
+            score = pm_row_out<POOL>(args, tl.t, tl.r0 + tid, tl.red[0][0][tid] + tl.red[1][0][tid], vl, vl + tl.noise);
+        }
+        if constexpr (POOL)
+            if (args.s.k > 0 && (tid >> 6) == 0)
+                pm_list_merge(walk.lv, walk.li, args.s.k, score, (long long)(tl.r0 + tid), tid < tl.m, [&](long long r) { return pm_excluded(args.s, tl.t, r); });
+    }
+};
+
+template <bool REFINE, bool GLOBAL, bool ARD = false, bool POOL = false, class EPI = PmRowEpilogue>
+__global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD, POOL, EPI> args) {
     const PmArgs& a = args.p;
     extern __shared__ __attribute__((aligned(16))) float pm_lds[];
-    __shared__ float As[PM_TM * LD_MN], Bs[PM_TM * LD_MN];
+    __shared__ float ABs[2 * PM_TM * LD_MN];
+    float *As = ABs, *Bs = ABs + PM_TM * LD_MN;
     __shared__ float rowsq[2][PM_TM];
     __shared__ float red[2][2][PM_TM];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wc = wv & 1;
@@ -563,14 +601,7 @@ __global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD, POOL> 
                 if ((lane & 15) == 0) { red[wc][0][pm_row(i, r)] = x; red[wc][1][pm_row(i, r)] = y; }
             }
         __syncthreads();
-        [[maybe_unused]] float score = 0.f;
-        if (tid < m) {
-            const float vl = os - (red[0][1][tid] + red[1][1][tid]);
-            score = pm_row_out<POOL>(args, t, r0 + tid, red[0][0][tid] + red[1][0][tid], vl, vl + noise);
-        }
-        if constexpr (POOL)
-            if (args.s.k > 0 && wv == 0)
-                pm_list_merge(walk.lv, walk.li, args.s.k, score, (long long)(r0 + tid), tid < m, [&](long long r) { return pm_excluded(args.s, t, r); });
+        EPI::template run<ARD, POOL>(args, PmTile{t, r0, m, n, nk, ld, os, noise, il2, mu, il, Kb, As, Bs, &rowsq, red}, walk, acc);
         __syncthreads();   // red / rowsq / the row tiles are rewritten by the next tile
     }
 }

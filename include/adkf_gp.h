@@ -301,6 +301,43 @@ int adkf_thompson_pool(const adkf_batch_t* b, const float* phi, int32_t flags, c
  * check runs before anything is launched. */
 int adkf_thompson_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega, const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx, const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Kriging-believer batch selection over a shared pool (csrc/believer_stream.h; Ginsbourger, Le Riche and Carraro 2010): q
+ * sequential-greedy EI picks per task from the SAME pool X [rows, d] in one call.  Each pick is "believed" at its posterior mean, so
+ * the mean of every row stays what it is, the latent variance shrinks by a rank-one downdate per pick, and the incumbent moves to
+ * the believed value.  The k rows of largest EI (adkf_predict_pool) are neighbours of the winner; these q rows are a batch.
+ *   The quantity.  (noise, s, l) from phi[t], A = K_ss + noise I, m(x) and v_0(x) adkf_predict_pool's mean and latent variance.
+ *          After picks p_0 .. p_(j-1) of task t, x_p the pool row of pick p:
+ *              w_i      = A^-1 k(Z_s, x_(p_i)),      c0(x, i) = k(x, x_(p_i)) - k(x, Z_s) . w_i      (i < j),
+ *              G G^T    = [c0(x_(p_i), l)]_(i,l<j) + noise I,  G lower triangular,    ell(x) = G^-1 c0(x, .),
+ *              v_j(x)   = v_0(x) - sum_(i<j) ell_i(x)^2,
+ *              best_0   = best_f[t],    best_(j+1) = min(best_j, m(x_(p_j)))   (max with ADKF_PM_MAXIMIZE),
+ *              score_j(x) = EI(m(x), v_j(x), best_j)   (log EI with ADKF_PM_LOG_EI), on sqrt(max(v, 1e-12)) as everywhere.
+ *          p_j is the eligible row of largest score_j, equal scores going to the lowest row index (the total order of
+ *          adkf_predict_pool).  A row is eligible unless it is listed in excl_idx[excl_off[t] .. excl_off[t + 1]) (nullable; as
+ *          adkf_predict_pool), it is one of p_0 .. p_(j-1), or its score is NaN.  With no eligible row at step j, that step and all
+ *          later ones report -1 / -inf (0 in sel_mean / sel_var) and the state stops changing.  The noise stays in G: a picked row
+ *          keeps the latent variance v noise / (v + noise) > 0.  Step 0 is adkf_predict_pool with k = 1, bit for bit.
+ *   b      support-only, workspace of adkf_workspace_bytes(T, ns_max, 0, d) bytes whatever rows and q are; REUSE_DIST / REUSE_INNER
+ *          mean what they mean for adkf_predict_pool.  ARD batches are refused (ADKF_E_BADARG).
+ *   flags  ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI; any other bit is ADKF_E_BADARG.
+ *   sel_idx, sel_val   [T, q], required: the pick of each step and its score.
+ *   sel_mean, sel_var  [T, q], each nullable: m(x_(p_j)), the believed value, and v_j(x_(p_j)).
+ *   trace  nullable, [T, q, rows] with element (t, j, r) at (t q + j) rows + r: score_j of every row, eligible or not, for tests
+ *          and diagnostics.  With trace == NULL the call writes T q tuples and nothing per row.
+ *   Tasks with n_s == 0 or info != 0: -1 / -inf in every step, zeros in sel_mean, sel_var and trace.
+ *   scratch   adkf_believer_pool_scratch_bytes(T, ns_max, d, q) bytes, 8-byte aligned: w [T, q, ns_max] (and its float64 twin for
+ *          flagged tasks up to 1024 points), the picks' feature rows [T, q, d], G [T, q, q] (and its twin), the incumbent and the
+ *          pick count per task, the per-chunk candidate pairs.  A function of (T, ns_max, d, q) only, never of rows.  Nothing for
+ *          the caller to initialise.
+ * Asynchronous on `stream`, no allocation, no synchronisation, no atomics: reproducible to the bit, and a task's result depends on
+ * that task's data, the pool and its exclusion list only - not on the grid or on the other tasks of the batch.
+ * Rejected before anything is launched, ADKF_E_BADARG unless noted: a batch with a query set; an ARD batch; any other flag bit;
+ * rows < 0; rows > 0 without X; a missing best_f, sel_idx, sel_val, info or ws; excl_idx without excl_off; q < 1;
+ * q > ADKF_POOL_TOPK_MAX (ADKF_E_SIZE); a workspace or a scratch that is too small (ADKF_E_WORKSPACE); a scratch that is not 8-byte
+ * aligned. */
+size_t adkf_believer_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t q);
+int adkf_believer_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

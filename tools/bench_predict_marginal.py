@@ -24,7 +24,12 @@ FP32-matrix bound.  --out FILE also writes the line to FILE.
 the same data, and the two Thompson calls (REUSE_INNER, paths = NULL) are timed alternately in this process (median of --reps
 single calls each).  The line holds both times, their ratio, the float64-flagged tasks of each batch, the bit-equality of a
 repeated ARD call and the distinct picks per task; exit status 1 if the ratio exceeds 1.15.
-Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--out FILE]"""
+--believer: Kriging-believer batch selection (adkf_believer_pool, trace = NULL) at T=16 ns=128 d=256, one pool of 100 000 rows, q = 8,
+Matern, REUSE_INNER, timed alternately in this process (median of --reps single calls each) with what a caller can do without it:
+q calls of adkf_predict_pool(k = 1) on the same batch (which leaves out the refit such a caller would also need).  The line holds
+both times, their ratio against the estimate from the tile's products (1.5 at ns = 128), the scratch bytes, the bit-equality of step 0
+with predict_pool and of a repeated call, and the picks shared with the EI top-q.
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer] [--out FILE]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -310,6 +315,54 @@ def shape_thompson_ard(T, ns, d, rows, S, m, reps, dev, out_path=None):
     return rec
 
 
+def shape_believer(T, ns, d, rows, q, reps, dev, out_path=None):
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    b = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern")
+    phi0, _ = gp_ops.init_params_batch(b, True, True)
+    b.flags = gp_ops.REUSE_DIST
+    phi, _, _, _, info = gp_ops.fit(b, phi0, 200)
+    gp_ops.check_info(info)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    X = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):
+        X[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    best = ys.median(1).values.contiguous()
+    top1 = lambda: gp_ops.predict_pool(b, phi, X, latent=True, best_f=best, want_mean=False, want_var=False, want_ei=False, topk=1)
+    f_bv = lambda: gp_ops.believer_pool(b, phi, X, best_f=best, q=q)
+    f_q = lambda: [top1() for _ in range(q)]
+    o1, o2 = f_bv(), f_bv()
+    ref = top1()
+    topq = gp_ops.predict_pool(b, phi, X, latent=True, best_f=best, want_mean=False, want_var=False, want_ei=False, topk=q)
+    torch.cuda.synchronize()
+    gp_ops.check_info(o1["info"])
+    ts = [[], [], []]
+    for _ in range(reps):
+        ts[0].append(once(f_bv))
+        ts[1].append(once(f_q))
+        ts[2].append(once(top1))
+    t_bv, t_q, t_1 = (float(np.median(x)) for x in ts)
+    lib = _lib.load()
+    shared = [len(set(a) & set(c)) for a, c in zip(o1["sel_idx"].cpu().tolist(), topq["top_idx"].cpu().tolist())]
+    rec = {"shape": f"believer T={T} ns={ns} d={d} rows={rows} q={q} matern REUSE_INNER trace=NULL", "refined_tasks": int(_refined(b).sum()),
+           "float64_tasks": int((_scal(b)[:, 45] > 30.0).sum()), "workspace_bytes": int(lib.adkf_workspace_bytes(T, ns, 0, d)),
+           "scratch_bytes": int(lib.adkf_believer_pool_scratch_bytes(T, ns, d, q)),
+           "believer_s": t_bv, "q_calls_of_predict_pool_k1_s": t_q, "one_predict_pool_k1_s": t_1, "believer_over_q_calls": t_bv / t_q,
+           "step_over_one_pass": t_bv / (q * t_1), "estimate_step_over_one_pass": 1.5,
+           "step_0_is_predict_pool_bitwise": bool(torch.equal(o1["sel_idx"][:, 0], ref["top_idx"][:, 0]) and torch.equal(o1["sel_val"][:, 0], ref["top_val"][:, 0])),
+           "repeat_is_bit_equal": bool(all(torch.equal(o1[n], o2[n]) for n in ("sel_idx", "sel_val", "sel_mean", "sel_var"))),
+           "distinct_picks_per_task_min": int(min(len(set(r)) for r in o1["sel_idx"].cpu().tolist())),
+           "picks_shared_with_ei_top_q_per_task": shared, "all_s": ts}
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    return rec
+
+
 def _scal(b):
     """The per-task scalars [T, 64] of a support-only workspace (carve() order of csrc/host_gp.h; slot 45 is the pivot ratio that flags
     a task for the float64 path above 30)."""
@@ -373,9 +426,13 @@ def main():
     ap.add_argument("--pool", action="store_true", help="shared-pool prediction against the packed call on a replicated pool, and the batched BO loop")
     ap.add_argument("--skip-bo", action="store_true")
     ap.add_argument("--thompson", action="store_true", help="adkf_thompson_pool against variant (ii) of --pool, timed alternately")
-    ap.add_argument("--out", default=None, help="--thompson (with or without --ard): also write the JSON line to this file")
+    ap.add_argument("--believer", action="store_true", help="adkf_believer_pool against q calls of adkf_predict_pool(k = 1), timed alternately")
+    ap.add_argument("--out", default=None, help="--thompson (with or without --ard), --believer: also write the JSON line to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.believer:
+        shape_believer(16, 128, 256, 100000, 8, a.reps, dev, a.out)
+        return
     if a.thompson and a.ard:
         rec = shape_thompson_ard(16, 128, 256, 262144, 16, 1024, a.reps, dev, a.out)
         sys.exit(0 if rec["within_1_15"] else 1)
