@@ -4,7 +4,9 @@ evaluated for EVERY candidate with one ``adkf_predict`` call (the reference loop
 pools beyond ``adkf_max_points()`` rows - or any pool with ``streaming=True`` - go through ``adkf_predict_marginal``, the
 streaming marginal prediction (no size cap, workspace independent of the pool size); ``run_gp_ei_bo(streaming=True)`` then
 gets EI straight from that one call.  ``run_gp_ei_bo_batched`` runs many replicates of that loop over the same pool at once: one
-batched fit and one ``adkf_predict_pool`` call per iteration, which returns each replicate's best candidates itself.
+batched fit and one ``adkf_predict_pool`` call per iteration, which returns each replicate's best candidates itself (or one
+``adkf_believer_pool`` call for a Kriging-believer batch; with ``ard=True`` the batch is an ARD batch and that call is
+``adkf_believer_pool_ard``).
 ``run_gp_ts_bo_batched`` is the same loop under Thompson sampling: one batched fit and one ``adkf_thompson_pool`` call (with
 ``ard=True``: ``adkf_thompson_pool_ard``) per iteration, in which every replicate draws posterior functions over the whole pool
 and each function picks its own best candidate - a diverse batch of ``query_batch_size > 1`` picks from one pass, with no
@@ -182,7 +184,8 @@ def run_gp_ei_bo(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int,
 @torch.no_grad()
 def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
                          kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
-                         rngs: List[np.random.Generator], acquisition: str = "ei", batch: str = "topk") -> List[List[int]]:
+                         rngs: List[np.random.Generator], acquisition: str = "ei", batch: str = "topk",
+                         ard: bool = False) -> List[List[int]]:
     """``len(rngs)`` replicates of ``run_gp_ei_bo`` over the same pool at once; returns their records.  Per iteration the
     replicates' queried sets form ONE batch (initial parameters and priors as ``create_gp`` makes them for each), fitted by ONE
     ``gp_ops.fit`` with ``fit_gpytorch_scipy``'s options and scored by ONE ``gp_ops.predict_pool`` call that excludes each
@@ -192,7 +195,10 @@ def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
     ``batch``: ``"topk"`` takes the ``query_batch_size`` rows of largest EI, as the sequential loop does (they tend to be
     neighbours of the winner); ``"believer"`` takes the Kriging-believer batch of ONE ``gp_ops.believer_pool`` call instead -
     sequential-greedy EI in which every pick is believed at its posterior mean - under the same rule for what counts.  With
-    ``query_batch_size = 1`` the two are the same loop."""
+    ``query_batch_size = 1`` the two are the same loop.
+    ``ard``: one lengthscale per feature dimension (the reference's ``ard_num_dims``) - each replicate's ``create_gp`` start is
+    expanded to ``[2 + d]`` as ``run_gp_ts_bo_batched(ard=True)`` expands it; the batch is an ARD batch, which ``predict_pool``
+    takes as it is and for which ``"believer"`` calls ``gp_ops.believer_pool_ard``."""
     log = _acquisition(acquisition)
     if batch not in ("topk", "believer"):
         raise ValueError(f"batch must be 'topk' or 'believer', got {batch!r}")
@@ -219,15 +225,17 @@ def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
             Zs[r, :sizes[r]] = model.train_inputs[0].detach().float()
             ys[r, :sizes[r]] = model.train_targets.detach().float()
             pri.append(mll.priors_row(X.device))
-            phi0.append(torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])[None])
+            p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
+            phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
         n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
-        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=model.ard)
+        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
         phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
         gp_ops.check_info(info, "run_gp_ei_bo_batched fit")
         b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
         best_f = torch.tensor(best, dtype=torch.float32, device=X.device)
         if batch == "believer":
-            out = gp_ops.believer_pool(b, phi, X, best_f=best_f, q=query_batch_size, maximize=False, log_ei=log, exclude=queried)
+            believe = gp_ops.believer_pool_ard if b.ard else gp_ops.believer_pool
+            out = believe(b, phi, X, best_f=best_f, q=query_batch_size, maximize=False, log_ei=log, exclude=queried)
             top_idx, top_val = out["sel_idx"].cpu(), out["sel_val"].cpu()
         else:
             out = gp_ops.predict_pool(b, phi, X, latent=True, best_f=best_f, maximize=False, want_mean=False, want_var=False,

@@ -26,6 +26,14 @@
 //             k_refine64's float64 A^-1), takes the pick's mean w . y and variance s - k . w - |ell|^2 from it, and stores the pick's
 //             feature row, the new row of G (G[j, :j] = ell, G[j, j] = sqrt(v_j + noise)), the new incumbent and the pick count.  With
 //             no eligible row it reports -1 / -inf and changes nothing, so every later step does the same.
+//
+// ARD batches (adkf_believer_pool_ard, ARD = true) run the same kernels on the scaled features x~ = (x - mu) / l of ard.h at unit
+// lengthscale: the walk's tile is prediction's ARD tile (pool rows scaled while they are staged, a.Zs = Zt_s), and the pick panel is
+// pm_k_panel<true>, which expects its "support" centred and scaled already - so k_bv_step<true> stores the pick's SCALED row in Xp,
+// with the expression the walk of that task's kind applies to the same pool row: (x - mu) * il for float32 tasks (pm_query_rows<true>),
+// k_ard_scale's (x - mu) / l in float32 for flagged ones (pm64_kernel_row<true>, k_bv_walk64<true>).  A pool row and its stored copy
+// are then the same float32 numbers; only one kind of kernel reads a task's Xp, so one buffer serves both.  The scalars, D2ss and
+// A^-1 are those of the unit-lengthscale pipeline (scal[S_LS] = softplus(RAW_ONE) = 1), so the solve, G and the state are unchanged.
 #pragma once
 #include "thompson_stream.h"
 
@@ -44,7 +52,8 @@ struct BvArgs {
     int64_t* sel_idx; float *sel_val, *sel_mean, *sel_var;   // [T, q]; the last two nullable
 };
 struct BvEpilogue;
-using BvKargs = PmArgsOf<false, true, BvEpilogue>;   // p.Zq: the pool; s.k = 1, s.cand_* [T, chunks_max]
+template <bool ARD>
+using BvKargs = PmArgsOf<ARD, true, BvEpilogue>;   // p.Zq: the pool; s.k = 1, s.cand_* [T, chunks_max]; ARD: r, the query scaling
 
 __device__ __forceinline__ bool bv_picked(const BvArgs& v, int t, int c, long long r) {
     for (int i = 0; i < c; ++i)
@@ -64,7 +73,7 @@ struct BvEpilogue {
     using Args = BvArgs;
     template <bool ARD, bool POOL, class ARGS, class WALK>
     static __device__ __forceinline__ void run(const ARGS& args, const PmTile& tl, WALK& walk, f32x4 (&acc)[2][2]) {
-        static_assert(!ARD && POOL, "adkf_believer_pool: isotropic batches over a shared pool");
+        static_assert(POOL, "adkf_believer_pool(_ard): a shared pool");
         const PmArgs& a = args.p;
         const BvArgs& v = args.v;
         const int tid = threadIdx.x, t = tl.t, q = v.q;
@@ -90,7 +99,7 @@ struct BvEpilogue {
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) F[i][j] = acc[i][j];
-            pm_k_panel<false>(a, v.Xp + (size_t)t * q * a.d, tl.mu, nullptr, tl.r0, tl.m, c, 0, tl.os, tl.il2, tl.As, tl.Bs, *tl.rowsq, acc,
+            pm_k_panel<ARD>(a, v.Xp + (size_t)t * q * a.d, tl.mu, tl.il, tl.r0, tl.m, c, 0, tl.os, tl.il2, tl.As, tl.Bs, *tl.rowsq, acc,
                               C0, BV_LDC, [] {});
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -127,7 +136,8 @@ struct BvEpilogue {
 };
 
 // ---- flagged tasks: k_predict_marginal64's loop (grid (chunks, T), one wave per pool row) with the downdate in float64
-__global__ __launch_bounds__(PM64_NT) void k_bv_walk64(BvKargs args) {
+template <bool ARD>
+__global__ __launch_bounds__(PM64_NT) void k_bv_walk64(BvKargs<ARD> args) {
     const PmArgs& a = args.p;
     const BvArgs& v = args.v;
     __shared__ double kr[PM64_WAVES][R64_MAXN];
@@ -146,10 +156,12 @@ __global__ __launch_bounds__(PM64_NT) void k_bv_walk64(BvKargs args) {
     const double* Wt = v.W64 + (size_t)t * q * ld;
     const double* G = v.G64 + (size_t)t * q * q;
     const float* Xp = v.Xp + (size_t)t * q * a.d;
+    const float *mu = nullptr, *el = nullptr;
+    if constexpr (ARD) { mu = a.mean_s + (size_t)t * a.d; el = args.r.ell + (size_t)t * a.d; }
     double* k = kr[wv];
     for (int64_t r = (int64_t)blockIdx.x * PM64_WAVES + wv; r < a.rows; r += (int64_t)gridDim.x * PM64_WAVES) {
         const float* zq = a.Zq + (size_t)r * a.d;
-        pm64_kernel_row<false>(a, zq, Zs, n, nullptr, nullptr, os, il2, k);
+        pm64_kernel_row<ARD>(a, zq, Zs, n, mu, el, os, il2, k);
         double s1 = 0.0, s2 = 0.0;
         for (int j = lane; j < n; j += 64) {
             double cc = 0.0;
@@ -164,7 +176,11 @@ __global__ __launch_bounds__(PM64_NT) void k_bv_walk64(BvKargs args) {
             if (lane < c) {
                 const float* xp = Xp + (size_t)lane * a.d;
                 double s = 0.0, f = 0.0;
-                for (int e = 0; e < a.d; ++e) { const double df = (double)zq[e] - (double)xp[e]; s += df * df; }
+                if constexpr (ARD) {   // the float32 feature of k_ard_scale against the stored one (k_bv_step<true>)
+                    for (int e = 0; e < a.d; ++e) { const double df = (double)((zq[e] - mu[e]) / el[e]) - (double)xp[e]; s += df * df; }
+                } else {
+                    for (int e = 0; e < a.d; ++e) { const double df = (double)zq[e] - (double)xp[e]; s += df * df; }
+                }
                 for (int i = 0; i < n; ++i) f += k[i] * Wt[(size_t)lane * ld + i];
                 c0 = os * bv_kappa64(a.kind, s * il2) - f;
             }
@@ -210,7 +226,8 @@ __device__ __forceinline__ double bv_block_sum(double x, double* red) {
 }
 
 // ---- the end of step j: one workgroup per task (see the top of the file)
-__global__ __launch_bounds__(256) void k_bv_step(BvKargs args) {
+template <bool ARD>
+__global__ __launch_bounds__(256) void k_bv_step(BvKargs<ARD> args) {
     const PmArgs& a = args.p;
     const PmPool& s = args.s;
     const BvArgs& v = args.v;
@@ -253,7 +270,14 @@ __global__ __launch_bounds__(256) void k_bv_step(BvKargs args) {
     const float* Zs = a.Zs + (size_t)t * ld * d;
     const float* ys = a.y_s + (size_t)t * ld;
     float* Xt = v.Xp + (size_t)t * q * d;
-    for (int e = tid; e < d; e += 256) Xt[(size_t)c * d + e] = xp[e];
+    if constexpr (ARD) {   // the row as the walk of this task's kind scales it; everything below reads the stored copy
+        const float *mu = a.mean_s + (size_t)t * d, *il = args.r.il + (size_t)t * d, *el = args.r.ell + (size_t)t * d;
+        for (int e = tid; e < d; e += 256) Xt[(size_t)c * d + e] = f64 ? (xp[e] - mu[e]) / el[e] : (xp[e] - mu[e]) * il[e];
+        __syncthreads();
+        xp = Xt + (size_t)c * d;
+    } else {
+        for (int e = tid; e < d; e += 256) Xt[(size_t)c * d + e] = xp[e];
+    }
     float *rs = fb, *vs = fb + TS_NS_MAX, *es = fb + 2 * TS_NS_MAX;   // float32 tasks: k, then w in vs
     double *k64 = reinterpret_cast<double*>(fb), *w64 = k64 + R64_MAXN;   // float64 tasks (n <= R64_MAXN): k and w
     // ---- k(Z_s, x_p) from the features, in float64

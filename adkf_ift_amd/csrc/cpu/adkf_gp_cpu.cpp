@@ -4,8 +4,8 @@
 // Same C ABI, HOST pointers: adkf_batch_t, priors, phi layouts, info codes and flags exactly as in the header; `ws` /
 // `ws_bytes` / `stream` are accepted and ignored (adkf_workspace_bytes returns 0 here).  Non-ARD batches of any size; the
 // exceptions are adkf_predict_marginal_ard, which centres and scales the features by the per-dimension lengthscales and runs
-// the isotropic code at unit lengthscale (csrc/ard.h), and adkf_thompson_pool_ard, which does the same for Thompson sampling.
-// adkf_thompson_pool refuses ARD batches, as the library does.
+// the isotropic code at unit lengthscale (csrc/ard.h), and adkf_thompson_pool_ard and adkf_believer_pool_ard, which do the same for
+// Thompson sampling and Kriging-believer selection.  adkf_thompson_pool and adkf_believer_pool refuse ARD batches, as the library does.
 // Plain loops, OpenMP over the tasks of a batch, float64 arithmetic inside and float32 at the boundary - a Cholesky-based
 // restatement of the same staged closed-form algebra the HIP kernels run (stage names as in DESIGN.md section 3 and
 // oracle/closed_form.py): kernel matrices from difference-form squared distances, A = L L^T, A^-1, the analytic 3 x 3 Hessian,
@@ -787,12 +787,14 @@ size_t adkf_believer_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { re
 
 // Kriging-believer batch selection (include/adkf_gp.h): the mean, the latent variance and K A^-1 of every pool row once, then per
 // step one more column of ell (the forward substitution of the header, one row of G at a time) and the scores in float32, ranked
-// under "larger score first, equal scores by ascending row".
-int adkf_believer_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
-                       const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
-                       float* sel_mean, float* sel_var, int32_t* info, void*, size_t, void*, size_t, void*) {
-    if (int rc = check(b, false)) return rc;   // (refuses ARD batches)
-    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+// under "larger score first, equal scores by ascending row".  ARD (adkf_believer_pool_ard): pm_task prepares the support set and the
+// pool rows on z~ = (z - mu) / l at unit lengthscale, and the distances between pool rows are taken on x / l (mu cancels); otherwise
+// l = 1 and the rows are taken as they are, which changes no bit of the isotropic call.
+static int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
+                         const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
+                         float* sel_mean, float* sel_var, int32_t* info) {
+    if (int rc = check(b, false, ard)) return rc;
+    if (((b->flags & ADKF_BATCH_ARD) != 0) != ard || b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
     if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
     if (flags & ~(ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
     if (rows > 0 && !X) return ADKF_E_BADARG;
@@ -832,6 +834,11 @@ int adkf_believer_pool(const adkf_batch_t* b, const float* phi, int32_t flags, c
             mu[r] = m1; v[r] = in.s - qf;
         });
         if (!done) continue;
+        Mat Xl(ard ? R * d : 0);   // ARD: the pool rows over l
+        if (ard) {
+            const float* x0 = phi + (size_t)t * (2 + d);
+            for (size_t r = 0; r < R; ++r) for (int c = 0; c < d; ++c) Xl[r * d + c] = (double)X[r * d + c] / softplus(x0[2 + c]);
+        }
         const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
         std::vector<char> taken(R, 0);
         std::vector<float> score(R);
@@ -853,7 +860,7 @@ int adkf_believer_pool(const adkf_batch_t* b, const float* phi, int32_t flags, c
             // the new row of G, then column j of ell and the downdate for every row (the picked one included)
             for (int l = 0; l < j; ++l) G[(size_t)j * q + l] = L[(size_t)p * q + l];
             G[(size_t)j * q + j] = std::sqrt(v[p] + noise);
-            const Mat Dp = sqdist(X + (size_t)p * d, 1, X, (int)rows, d);
+            const Mat Dp = ard ? sqdist(Xl.data() + (size_t)p * d, 1, Xl.data(), (int)rows, d) : sqdist(X + (size_t)p * d, 1, X, (int)rows, d);
             for (int64_t r = 0; r < rows; ++r) {
                 double k0, k1, k2;
                 kappa(b->kernel, Dp[r] * il2, k0, k1, k2);
@@ -870,6 +877,18 @@ int adkf_believer_pool(const adkf_batch_t* b, const float* phi, int32_t flags, c
         }
     }
     return 0;
+}
+
+int adkf_believer_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
+                       const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
+                       float* sel_mean, float* sel_var, int32_t* info, void*, size_t, void*, size_t, void*) {
+    return believer_pool(false, b, phi, flags, X, rows, best_f, excl_idx, excl_off, q, trace, sel_idx, sel_val, sel_mean, sel_var, info);   // (refuses ARD batches)
+}
+
+int adkf_believer_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
+                           const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
+                           float* sel_mean, float* sel_var, int32_t* info, void*, size_t, void*, size_t, void*) {
+    return believer_pool(true, b, phi, flags, X, rows, best_f, excl_idx, excl_off, q, trace, sel_idx, sel_val, sel_mean, sel_var, info);
 }
 
 static int outer_common(const adkf_batch_t* b, const float* phi, int flags, bool with_hessian, float* f_out, float* g_phi, float* dZ_s, float* dZ_q,

@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, and adkf_believer_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
+// ARD forms, adkf_believer_pool and adkf_believer_pool_ard): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
 #pragma once
 #include "host_ard.h"
 
@@ -360,13 +360,43 @@ inline BvScratch bv_scratch(void* base, int T, int ns, int d, int q) {
     return l;
 }
 
-// adkf_believer_pool: q chained steps, each the walks of prediction with the believer's epilogue and one workgroup per task
-int believer_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
+// The steps of a prepared believer call: q chained steps, each the walks of prediction with the believer's epilogue and one workgroup
+// per task.  ARD: c.r names the query scaling, whose 1 / l goes into ArdWs::c first (as pm_launch).
+template <bool ARD>
+int bv_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, BvArgs& v, int64_t rows, bool have64) {
+    hipStream_t st = c.st;
+    const int T = c.b.T;
+    auto args = [&] {
+        BvKargs<ARD> k{};
+        k.p = pa;
+        if constexpr (ARD) k.r = c.r;
+        k.s = pool; k.v = v;
+        return k;
+    };
+    if constexpr (ARD) launch_ard_il(c);
+    const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
+    pool.grid[2] = (have64 && rows > 0) ? std::min(pm64_grid(rows), pool.chunks_max) : 0;
+    int rc;
+    for (int j = 0; j < v.q; ++j) {
+        v.j = j;
+        if (rows > 0) {
+            if ((rc = pm_launch_walk<false, ARD, true, BvEpilogue>(c, pa, &pool, v, tiles))) return rc;
+            if ((rc = pm_launch_walk<true, ARD, true, BvEpilogue>(c, pa, &pool, v, tiles))) return rc;
+            if (have64) k_bv_walk64<ARD><<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(args());
+        }
+        k_bv_step<ARD><<<T, 256, 0, st>>>(args());
+    }
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_believer_pool and adkf_believer_pool_ard: the same call on a batch that is (ard) or is not an ARD batch
+int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
                   const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* sel_mean,
                   float* sel_var, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
     int rc = check_support_only(b, phi, info, ws, rows);
     if (rc) return rc;
-    if (is_ard(b)) return ADKF_E_BADARG;
+    if (is_ard(b) != ard) return ADKF_E_BADARG;
     if (flags & ~(ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
     if (rows > 0 && !X) return ADKF_E_BADARG;
     if (!best_f || !sel_idx || !sel_val) return ADKF_E_BADARG;
@@ -399,19 +429,7 @@ int believer_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
     if (trace && rows > 0) hipMemsetAsync(trace, 0, sizeof(float) * (size_t)T * q * (size_t)rows, st);
     hipMemsetAsync(pool.cand_idx, 0xff, sizeof(int64_t) * (size_t)T * pool.chunks_max, st);
     k_bv_init<<<ceil_div(T, 256), 256, 0, st>>>(v, best_f, T);
-    const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
-    pool.grid[2] = (have64 && rows > 0) ? std::min(pm64_grid(rows), pool.chunks_max) : 0;
-    for (int j = 0; j < q; ++j) {
-        v.j = j;
-        if (rows > 0) {
-            if ((rc = pm_launch_walk<false, false, true, BvEpilogue>(c, pa, &pool, v, tiles))) return rc;
-            if ((rc = pm_launch_walk<true, false, true, BvEpilogue>(c, pa, &pool, v, tiles))) return rc;
-            if (have64) k_bv_walk64<<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(BvKargs{pa, {}, pool, v});
-        }
-        k_bv_step<<<T, 256, 0, st>>>(BvKargs{pa, {}, pool, v});
-    }
-    LAUNCH_OK();
-    return 0;
+    return ard ? bv_launch<true>(c, pa, pool, v, rows, have64) : bv_launch<false>(c, pa, pool, v, rows, have64);
 }
 
 }  // namespace

@@ -420,21 +420,16 @@ def predict_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, latent: bool
     return dict(mean=mean, var=var, ei=ei, top_idx=top_idx, top_val=top_val, info=info)
 
 
-def believer_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, best_f: torch.Tensor, q: int, maximize: bool = False,
-                  log_ei: bool = False, exclude=None, want_trace: bool = False):
-    """A Kriging-believer batch per task from the shared pool ``X [rows, d]`` in one ``adkf_believer_pool`` call: ``q`` (at most
-    64) sequential-greedy EI picks, each believed at its posterior mean, so that a pick lowers the variance - hence the EI - of its
-    neighbours and moves the incumbent before the next one is chosen.  Step 0 is ``predict_pool(topk=1)``.  Returns
-    ``dict(sel_idx, sel_val, sel_mean, sel_var, trace, info)``: ``sel_idx [T, q]`` (int64) the picks in pick order and
-    ``sel_val`` their scores (EI, or log EI with ``log_ei``) at the step they were picked, -1 / -inf from the step at which no
-    eligible row was left; ``sel_mean`` the believed values, ``sel_var`` the latent variance each pick had when it was picked;
-    ``trace [T, q, rows]`` (``want_trace``, else None) the score of every row at every step; ``info [T]``.  ``exclude``: rows a
-    task may not select (``pack_exclude``).  Raises ``ValueError`` for an ARD batch."""
+def _believer_pool(name: str, b: GPBatch, phi, X, best_f, q, maximize, log_ei, exclude, want_trace):
+    """The body of ``believer_pool`` (``name = "believer_pool"``, isotropic batches) and ``believer_pool_ard`` (ARD batches)."""
     lib = _lib.load()
+    ard = name == "believer_pool_ard"
     if b.nq != 0:
-        raise ValueError("believer_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
-    if b.ard:
-        raise ValueError("believer_pool does not support ARD batches")
+        raise ValueError(f"{name} takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    if b.ard and not ard:
+        raise ValueError("believer_pool does not support ARD batches: use believer_pool_ard")
+    if ard and not b.ard:
+        raise ValueError("believer_pool_ard takes an ARD batch (GPBatch(..., ard=True)): use believer_pool")
     q = int(q)
     if q < 1 or q > _lib.POOL_TOPK_MAX:
         raise ValueError(f"q must be in [1, {_lib.POOL_TOPK_MAX}], got {q}")
@@ -443,14 +438,14 @@ def believer_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, best_f: tor
     if X.dim() != 2 or X.shape[1] != b.d:
         raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
     if best_f is None:
-        raise ValueError("believer_pool needs best_f [T]")
+        raise ValueError(f"{name} needs best_f [T]")
     best_f = _f32(best_f, "best_f").reshape(-1)
     if best_f.numel() != b.T:
         raise ValueError(f"best_f must have T = {b.T} entries")
     rows = X.shape[0]
-    for name, t in (("X", X), ("best_f", best_f)):
+    for arg, t in (("X", X), ("best_f", best_f)):
         if t.device != b.device:
-            raise ValueError(f"{name} lives on {t.device}, the batch on {b.device}")
+            raise ValueError(f"{arg} lives on {t.device}, the batch on {b.device}")
     excl_idx = excl_off = None
     if exclude is not None:
         excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
@@ -463,10 +458,33 @@ def believer_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, best_f: tor
     flags = (_lib.PM_MAXIMIZE if maximize else 0) | (_lib.PM_LOG_EI if log_ei else 0)
     ws, nb = b.workspace()
     cb = b.c_struct()
-    _lib.check(lib.adkf_believer_pool(C.byref(cb), ptr(phi), flags, ptr(X), rows, ptr(best_f), ptr(excl_idx), ptr(excl_off), q,
-                                      ptr(trace), ptr(sel_idx), ptr(sel_val), ptr(sel_mean), ptr(sel_var), ptr(info), ptr(ws), nb,
-                                      ptr(scratch), sb, stream(b.device)), "adkf_believer_pool")
+    entry = "adkf_" + name
+    _lib.check(getattr(lib, entry)(C.byref(cb), ptr(phi), flags, ptr(X), rows, ptr(best_f), ptr(excl_idx), ptr(excl_off), q,
+                                   ptr(trace), ptr(sel_idx), ptr(sel_val), ptr(sel_mean), ptr(sel_var), ptr(info), ptr(ws), nb,
+                                   ptr(scratch), sb, stream(b.device)), entry)
     return dict(sel_idx=sel_idx, sel_val=sel_val, sel_mean=sel_mean, sel_var=sel_var, trace=trace, info=info)
+
+
+def believer_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, best_f: torch.Tensor, q: int, maximize: bool = False,
+                  log_ei: bool = False, exclude=None, want_trace: bool = False):
+    """A Kriging-believer batch per task from the shared pool ``X [rows, d]`` in one ``adkf_believer_pool`` call: ``q`` (at most
+    64) sequential-greedy EI picks, each believed at its posterior mean, so that a pick lowers the variance - hence the EI - of its
+    neighbours and moves the incumbent before the next one is chosen.  Step 0 is ``predict_pool(topk=1)``.  Returns
+    ``dict(sel_idx, sel_val, sel_mean, sel_var, trace, info)``: ``sel_idx [T, q]`` (int64) the picks in pick order and
+    ``sel_val`` their scores (EI, or log EI with ``log_ei``) at the step they were picked, -1 / -inf from the step at which no
+    eligible row was left; ``sel_mean`` the believed values, ``sel_var`` the latent variance each pick had when it was picked;
+    ``trace [T, q, rows]`` (``want_trace``, else None) the score of every row at every step; ``info [T]``.  ``exclude``: rows a
+    task may not select (``pack_exclude``).  ARD batches go to ``believer_pool_ard``."""
+    return _believer_pool("believer_pool", b, phi, X, best_f, q, maximize, log_ei, exclude, want_trace)
+
+
+def believer_pool_ard(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, best_f: torch.Tensor, q: int, maximize: bool = False,
+                      log_ei: bool = False, exclude=None, want_trace: bool = False):
+    """``believer_pool`` for ARD batches (``phi [T, 2 + d]``) in one ``adkf_believer_pool_ard`` call: the same picks on the scaled
+    features ``(x - mu) / l`` with one lengthscale per feature dimension.  Step 0 is ``predict_pool(topk=1)`` on the same ARD
+    batch; arguments and the returned dict are those of ``believer_pool``.  Raises ``ValueError`` for a batch that is not an ARD
+    batch."""
+    return _believer_pool("believer_pool_ard", b, phi, X, best_f, q, maximize, log_ei, exclude, want_trace)
 
 
 def rff_basis(kernel, d: int, m: int, generator: Optional[torch.Generator] = None, device=None) -> Tuple[torch.Tensor, torch.Tensor]:

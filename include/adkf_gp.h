@@ -338,6 +338,25 @@ int adkf_thompson_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flag
 size_t adkf_believer_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t q);
 int adkf_believer_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* adkf_believer_pool for ARD batches (one lengthscale per feature dimension, phi [T, 2 + d]: adkf_workspace_bytes_ard).
+ *   The quantity.  (noise, s, l_1 .. l_d) from phi[t], mu the support column mean, x~ = (x - mu) / l elementwise; every kernel value
+ *          of adkf_believer_pool's recurrence is taken on the scaled features at unit lengthscale,
+ *              k(x, x') = s kappa(|x~ - x'~|^2),
+ *          for pool rows, support rows and picks alike; m(x) and v_0(x) are ARD adkf_predict_pool's.  With all l_c equal the picks
+ *          are adkf_believer_pool's.  Eligibility, the total order, the incumbent rule and the -1 / -inf conventions are unchanged,
+ *          and step 0 is ARD adkf_predict_pool with k = 1, bit for bit.
+ *   b      must carry ADKF_BATCH_ARD and be support-only (nq_max == 0, Z_q == y_q == NULL); anything else is ADKF_E_BADARG;
+ *   phi    [T, 2 + d] in the ARD layout;
+ *   ws     exactly adkf_workspace_bytes_ard(T, ns_max, 0, d) bytes whatever rows and q are (less: ADKF_E_WORKSPACE); REUSE_INNER after
+ *          an ARD adkf_fit on the same batch and workspace reuses the fit's state, as adkf_predict_marginal_ard documents; otherwise
+ *          the call evaluates at phi.  REUSE_DIST is ignored, as for every ARD call;
+ *   scratch   adkf_believer_pool_scratch_bytes(T, ns_max, d, q) bytes: the layout does not depend on the kind of batch (the picks'
+ *          rows [T, q, d] hold the SCALED rows here).
+ * Every other argument, check, return code and their order, the outputs, and the guarantees (asynchronous, capturable, no atomics,
+ * reproducible to the bit, a task's result independent of the other tasks of the batch) are those of adkf_believer_pool; every
+ * check runs before anything is launched. */
+int adkf_believer_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

@@ -29,7 +29,14 @@ Matern, REUSE_INNER, timed alternately in this process (median of --reps single 
 q calls of adkf_predict_pool(k = 1) on the same batch (which leaves out the refit such a caller would also need).  The line holds
 both times, their ratio against the estimate from the tile's products (1.5 at ns = 128), the scratch bytes, the bit-equality of step 0
 with predict_pool and of a repeated call, and the picks shared with the EI top-q.
-Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer] [--out FILE]"""
+--believer --ard: the same shape for ARD batches (adkf_believer_pool_ard): one ARD batch and one isotropic batch are fitted on the
+same data, and four calls (REUSE_INNER, trace = NULL) are timed alternately in this process (median of --reps single calls each;
+use --reps 7): the ARD believer, the isotropic believer, ARD predict_pool(topk=1) and isotropic predict_pool(topk=1).  The yardstick
+for the ARD believer's ratio to the isotropic one is predict_pool's ARD / isotropic ratio of the same run: the ARD walk adds one load
+and one multiply per staged query element, and the believer adds nothing ARD-specific on top.  The line holds the four times, both
+ratios, each series' spread (max - min) / median, the float64-flagged tasks of each batch, the bit-equality of step 0 with ARD
+predict_pool and of a repeated call, and the distinct picks per task.
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--out FILE]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -363,6 +370,63 @@ def shape_believer(T, ns, d, rows, q, reps, dev, out_path=None):
     return rec
 
 
+def shape_believer_ard(T, ns, d, rows, q, reps, dev, out_path=None):
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    bi = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern")
+    phi0, _ = gp_ops.init_params_batch(bi, True, True)
+    bi.flags = gp_ops.REUSE_DIST
+    phi_i, _, _, _, info = gp_ops.fit(bi, phi0, 200)
+    gp_ops.check_info(info)
+    bi.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    ba = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern", ard=True)
+    phi0, _ = gp_ops.init_params_batch(ba, True, True)
+    phi_a, _, _, n_evals, info = gp_ops.fit(ba, phi0, 100)
+    gp_ops.check_info(info)
+    ba.flags = gp_ops.REUSE_INNER
+    X = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):
+        X[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    best = ys.median(1).values.contiguous()
+    kw = dict(latent=True, best_f=best, want_mean=False, want_var=False, want_ei=False, topk=1)
+    fs = [lambda: gp_ops.believer_pool_ard(ba, phi_a, X, best_f=best, q=q), lambda: gp_ops.believer_pool(bi, phi_i, X, best_f=best, q=q),
+          lambda: gp_ops.predict_pool(ba, phi_a, X, **kw), lambda: gp_ops.predict_pool(bi, phi_i, X, **kw)]
+    o1, o2 = fs[0](), fs[0]()
+    oi, ref = fs[1](), fs[2]()
+    fs[3]()
+    torch.cuda.synchronize()
+    gp_ops.check_info(o1["info"]); gp_ops.check_info(oi["info"])
+    ts = [[], [], [], []]
+    for _ in range(reps):
+        for k, f in enumerate(fs):
+            ts[k].append(once(f))
+    t_ba, t_bi, t_pa, t_pi = (float(np.median(x)) for x in ts)
+    spread = [float((max(x) - min(x)) / np.median(x)) for x in ts]
+    lib = _lib.load()
+    ell = torch.nn.functional.softplus(phi_a[:, 2:])
+    rec = {"shape": f"believer ard T={T} ns={ns} d={d} rows={rows} q={q} matern REUSE_INNER trace=NULL",
+           "float64_tasks_ard": int((_scal(ba)[:, 45] > 30.0).sum()), "float64_tasks_isotropic": int((_scal(bi)[:, 45] > 30.0).sum()),
+           "refined_tasks_ard": int(_refined(ba).sum()), "refined_tasks_isotropic": int(_refined(bi).sum()),
+           "workspace_bytes_ard": int(lib.adkf_workspace_bytes_ard(T, ns, 0, d)), "workspace_bytes_isotropic": int(lib.adkf_workspace_bytes(T, ns, 0, d)),
+           "scratch_bytes": int(lib.adkf_believer_pool_scratch_bytes(T, ns, d, q)),
+           "ard_fit_evals_max": int(n_evals.max()), "ard_lengthscale_min": float(ell.min()), "ard_lengthscale_max": float(ell.max()),
+           "believer_ard_s": t_ba, "believer_isotropic_s": t_bi, "predict_pool_k1_ard_s": t_pa, "predict_pool_k1_isotropic_s": t_pi,
+           "believer_ard_over_isotropic": t_ba / t_bi, "predict_pool_ard_over_isotropic": t_pa / t_pi,
+           "spread_max_minus_min_over_median": dict(zip(("believer_ard", "believer_isotropic", "predict_pool_ard", "predict_pool_isotropic"), spread)),
+           "step_0_is_predict_pool_bitwise": bool(torch.equal(o1["sel_idx"][:, 0], ref["top_idx"][:, 0]) and torch.equal(o1["sel_val"][:, 0], ref["top_val"][:, 0])),
+           "repeat_is_bit_equal": bool(all(torch.equal(o1[n], o2[n]) for n in ("sel_idx", "sel_val", "sel_mean", "sel_var"))),
+           "distinct_picks_per_task_min_ard": int(min(len(set(r)) for r in o1["sel_idx"].cpu().tolist())),
+           "distinct_picks_per_task_min_isotropic": int(min(len(set(r)) for r in oi["sel_idx"].cpu().tolist())), "all_s": ts}
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    return rec
+
+
 def _scal(b):
     """The per-task scalars [T, 64] of a support-only workspace (carve() order of csrc/host_gp.h; slot 45 is the pivot ratio that flags
     a task for the float64 path above 30)."""
@@ -427,9 +491,12 @@ def main():
     ap.add_argument("--skip-bo", action="store_true")
     ap.add_argument("--thompson", action="store_true", help="adkf_thompson_pool against variant (ii) of --pool, timed alternately")
     ap.add_argument("--believer", action="store_true", help="adkf_believer_pool against q calls of adkf_predict_pool(k = 1), timed alternately")
-    ap.add_argument("--out", default=None, help="--thompson (with or without --ard), --believer: also write the JSON line to this file")
+    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard): also write the JSON line to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.believer and a.ard:
+        shape_believer_ard(16, 128, 256, 100000, 8, a.reps, dev, a.out)
+        return
     if a.believer:
         shape_believer(16, 128, 256, 100000, 8, a.reps, dev, a.out)
         return
