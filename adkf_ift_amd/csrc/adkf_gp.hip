@@ -237,16 +237,12 @@ int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, co
     if (excl_idx && !excl_off) return ADKF_E_BADARG;
     if (k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
     const PoolScratch l = pool_scratch(scratch, b->T, k);
-    if (scratch_bytes < l.bytes) return ADKF_E_WORKSPACE;
-    if (l.bytes > 0 && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 7u))) return ADKF_E_BADARG;
-    PmPool pool{};
-    pool.excl_idx = excl_off ? excl_idx : nullptr; pool.excl_off = excl_off;
-    pool.k = k; pool.chunks_max = pm_pool_chunks_max(b->T); pool.score_mean = by_mean ? 1 : 0;
-    pool.cand_idx = l.cand_idx; pool.cand_val = l.cand_val;
-    pool.top_idx = top_idx; pool.top_val = top_val;
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
     PmCtx c;
     rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
+    PmPool pool = pm_pool(excl_idx, excl_off, k, b->T, l.cand_idx, l.cand_val, rows, c.st);
+    pool.score_mean = by_mean ? 1 : 0; pool.top_idx = top_idx; pool.top_val = top_val;
     const PmCall io{flags & (ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI), X, nullptr, rows, best_f, mean, var, ei, info, &pool};
     return c.ard ? pm_launch<true, true>(c, io) : pm_launch<false, true>(c, io);
 }

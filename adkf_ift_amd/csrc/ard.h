@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void k_ard_scale(ArdView a, const float* Z, fl
     const int n = n_arr ? n_arr[t] : ld;
     const size_t o = ((size_t)t * ld + i) * a.d;
     const float *mu = a.mu + (size_t)t * a.d, *el = a.ell + (size_t)t * a.d;
-    for (int k = lane; k < a.d; k += 64) Zt[o + k] = i < n ? (Z[o + k] - mu[k]) / el[k] : 0.f;
+    for (int k = lane; k < a.d; k += 64) Zt[o + k] = i < n ? ard_scaled(Z[o + k], mu[k], el[k]) : 0.f;
 }
 
 // out[k] = sum_i A_ik B_ik over the rows of one task (64 columns x 4 row groups; grid: ceil(d / 64) x T); optional second

@@ -19,10 +19,12 @@
 //             substitution of row i against G (uniform loads), takes v_j and the score, and the first wave merges the scores into the
 //             walk's one-entry list; the exclusion test also scans the picks made so far.  At c = 0 none of this runs and the row's
 //             score is prediction's, bit for bit.
-//   float64   tasks (refine64.h) take k_bv_walk64, k_predict_marginal64's wave-per-row loop with float64 w and G: lane i forms
-//             c0(x, i), the substitution runs over the lanes (row i of G against the ell broadcast so far).
-//   k_bv_step merges the chunks' pairs under pm_beats, writes sel_*, forms k(Z_s, x_p) from the features in float64, solves
-//             w = A^-1 k (float32 tasks: k_ts_solve's product and ONE refinement step with A regenerated from D2ss; flagged tasks:
+//   float64   tasks (refine64.h) take k_bv_walk64, k_predict_marginal64's wave-per-row loop (pm64_task, pm64_posterior_row,
+//             pm64_finish_walk) with float64 w and G: lane i forms c0(x, i), the substitution runs over the lanes (row i of G against
+//             the ell broadcast so far).
+//   k_bv_step merges the chunks' pairs under pm_beats (pm_merge_task_lists, k_pool_topk's merge at width 1), writes sel_*, forms
+//             k(Z_s, x_p) from the features in float64 (refine64.h's float64 kappa0, as the float64 walk), solves w = A^-1 k (float32
+//             tasks: pm_solve_refined, k_ts_solve's product and ONE refinement step with A regenerated from D2ss; flagged tasks:
 //             k_refine64's float64 A^-1), takes the pick's mean w . y and variance s - k . w - |ell|^2 from it, and stores the pick's
 //             feature row, the new row of G (G[j, :j] = ell, G[j, j] = sqrt(v_j + noise)), the new incumbent and the pick count.  With
 //             no eligible row it reports -1 / -inf and changes nothing, so every later step does the same.
@@ -30,9 +32,10 @@
 // ARD batches (adkf_believer_pool_ard, ARD = true) run the same kernels on the scaled features x~ = (x - mu) / l of ard.h at unit
 // lengthscale: the walk's tile is prediction's ARD tile (pool rows scaled while they are staged, a.Zs = Zt_s), and the pick panel is
 // pm_k_panel<true>, which expects its "support" centred and scaled already - so k_bv_step<true> stores the pick's SCALED row in Xp,
-// with the expression the walk of that task's kind applies to the same pool row: (x - mu) * il for float32 tasks (pm_query_rows<true>),
-// k_ard_scale's (x - mu) / l in float32 for flagged ones (pm64_kernel_row<true>, k_bv_walk64<true>).  A pool row and its stored copy
-// are then the same float32 numbers; only one kind of kernel reads a task's Xp, so one buffer serves both.  The scalars, D2ss and
+// through the function the walk of that task's kind applies to the same pool row: ard_scaled_il, (x - mu) * il, for float32 tasks
+// (pm_query_rows<true>); ard_scaled, k_ard_scale's (x - mu) / l in float32, for flagged ones (pm64_kernel_row<true>, k_bv_walk64<true>).
+// A pool row and its stored copy are the same float32 numbers because both come out of one function (device_utils.h), not because two
+// expressions were kept alike; only one kind of kernel reads a task's Xp, so one buffer serves both.  The scalars, D2ss and
 // A^-1 are those of the unit-lengthscale pipeline (scal[S_LS] = softplus(RAW_ONE) = 1), so the solve, G and the state are unchanged.
 #pragma once
 #include "thompson_stream.h"
@@ -62,11 +65,6 @@ __device__ __forceinline__ bool bv_picked(const BvArgs& v, int t, int c, long lo
 }
 __device__ __forceinline__ float bv_score(const PmArgs& a, const BvArgs& v, int t, float mean, float vl) {
     return a.log_ei ? pm_log_ei(mean, vl, v.best[t], a.maximize) : pm_ei(mean, vl, v.best[t], a.maximize);
-}
-__device__ __forceinline__ double bv_kappa64(int kind, double u) {
-    if (kind == ADKF_KERNEL_RBF) return exp(-0.5 * u);
-    const double rr = sqrt(u);
-    return (1.0 + 2.23606797749979 * rr + (5.0 / 3.0) * u) * exp(-2.23606797749979 * rr);
 }
 
 struct BvEpilogue {
@@ -144,45 +142,30 @@ __global__ __launch_bounds__(PM64_NT) void k_bv_walk64(BvKargs<ARD> args) {
     float lv = -INFINITY;
     long long li = -1;
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, q = v.q;
-    if (pm_kind_of(a, t) != 2) return;   // (uniform)
-    const int n = pm_ns(a, t), ld = a.ns_ld;
-    if (n <= 0 || n > R64_MAXN) return;
-    const int c = v.cnt[t];
-    const float* sc = a.scal + (size_t)t * NSCAL;
-    const double os = sc[S_OS], ls = sc[S_LS], il2 = 1.0 / (ls * ls);
-    const double* A1 = a.w64 + (size_t)t * a.w64_stride;   // float64 A^-1 [ld, ld]
-    const float* Zs = a.Zs + (size_t)t * ld * a.d;
-    const float* ys = a.y_s + (size_t)t * ld;
+    Pm64Task tk;
+    if (!pm64_task<ARD>(args, t, tk)) return;   // (uniform)
+    const int n = tk.n, ld = tk.ld, c = v.cnt[t];
     const double* Wt = v.W64 + (size_t)t * q * ld;
     const double* G = v.G64 + (size_t)t * q * q;
     const float* Xp = v.Xp + (size_t)t * q * a.d;
-    const float *mu = nullptr, *el = nullptr;
-    if constexpr (ARD) { mu = a.mean_s + (size_t)t * a.d; el = args.r.ell + (size_t)t * a.d; }
     double* k = kr[wv];
     for (int64_t r = (int64_t)blockIdx.x * PM64_WAVES + wv; r < a.rows; r += (int64_t)gridDim.x * PM64_WAVES) {
         const float* zq = a.Zq + (size_t)r * a.d;
-        pm64_kernel_row<ARD>(a, zq, Zs, n, mu, el, os, il2, k);
-        double s1 = 0.0, s2 = 0.0;
-        for (int j = lane; j < n; j += 64) {
-            double cc = 0.0;
-            for (int i = 0; i < n; ++i) cc += k[i] * A1[(size_t)i * ld + j];
-            s1 += cc * (double)ys[j];
-            s2 += cc * k[j];
-        }
-        for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
-        double vl = os - s2;
+        double s1, s2;
+        pm64_posterior_row<ARD>(a, tk, zq, k, s1, s2);
+        double vl = tk.os - s2;
         if (c > 0) {
             double c0 = 0.0;   // lane i: c0(x, i)
             if (lane < c) {
                 const float* xp = Xp + (size_t)lane * a.d;
                 double s = 0.0, f = 0.0;
-                if constexpr (ARD) {   // the float32 feature of k_ard_scale against the stored one (k_bv_step<true>)
-                    for (int e = 0; e < a.d; ++e) { const double df = (double)((zq[e] - mu[e]) / el[e]) - (double)xp[e]; s += df * df; }
+                if constexpr (ARD) {   // the float32 feature of k_ard_scale against the stored one (k_bv_step<true>: ard_scaled, both)
+                    for (int e = 0; e < a.d; ++e) { const double df = (double)ard_scaled(zq[e], tk.mu[e], tk.el[e]) - (double)xp[e]; s += df * df; }
                 } else {
                     for (int e = 0; e < a.d; ++e) { const double df = (double)zq[e] - (double)xp[e]; s += df * df; }
                 }
                 for (int i = 0; i < n; ++i) f += k[i] * Wt[(size_t)lane * ld + i];
-                c0 = os * bv_kappa64(a.kind, s * il2) - f;
+                c0 = tk.os * kappa0(a.kind, s * tk.il2) - f;
             }
             double part = 0.0, ss = 0.0;   // lane i: sum_(l < i) G[i, l] ell_l so far
             for (int i = 0; i < c; ++i) {
@@ -202,8 +185,7 @@ __global__ __launch_bounds__(PM64_NT) void k_bv_walk64(BvKargs<ARD> args) {
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
-    pm64_gather_lists(lv, li, [&](float x, long long i) { pm_list_merge(lv, li, 1, x, i, i >= 0, [](long long) { return false; }); });
-    if (wv == 0) pm_list_store(args.s, t, blockIdx.x, lane, 1, lv, li);
+    pm64_finish_walk(args.s, t, 1, lv, li, [&](float x, long long i) { pm_list_merge(lv, li, 1, x, i, i >= 0, [](long long) { return false; }); });
 }
 
 // the per-task state before step 0
@@ -239,17 +221,9 @@ __global__ __launch_bounds__(256) void k_bv_step(BvKargs<ARD> args) {
     const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, q = v.q;
     const size_t o = (size_t)t * q + v.j;
     if (wv == 0) {   // the task's lists under the total order (skipped tasks, and every task when no walk ran, have none)
-        const int C = pm_task_chunks(a, s, t, true);
-        float lv = -INFINITY;
-        long long li = -1;
-        const size_t base = (size_t)t * s.chunks_max;
-        for (int e0 = 0; e0 < C; e0 += 64) {
-            const int e = e0 + lane;
-            const bool in = e < C;
-            const long long r = in ? (long long)s.cand_idx[base + e] : -1;
-            const float x = in ? s.cand_val[base + e] : 0.f;
-            pm_list_merge(lv, li, 1, x, r, r >= 0, [](long long) { return false; });
-        }
+        float lv;
+        long long li;
+        pm_merge_task_lists(a, s, t, 1, lv, li);
         if (lane == 0) { pick_s = li; val_s = lv; }
     }
     __syncthreads();
@@ -272,7 +246,7 @@ __global__ __launch_bounds__(256) void k_bv_step(BvKargs<ARD> args) {
     float* Xt = v.Xp + (size_t)t * q * d;
     if constexpr (ARD) {   // the row as the walk of this task's kind scales it; everything below reads the stored copy
         const float *mu = a.mean_s + (size_t)t * d, *il = args.r.il + (size_t)t * d, *el = args.r.ell + (size_t)t * d;
-        for (int e = tid; e < d; e += 256) Xt[(size_t)c * d + e] = f64 ? (xp[e] - mu[e]) / el[e] : (xp[e] - mu[e]) * il[e];
+        for (int e = tid; e < d; e += 256) Xt[(size_t)c * d + e] = f64 ? ard_scaled(xp[e], mu[e], el[e]) : ard_scaled_il(xp[e], mu[e], il[e]);
         __syncthreads();
         xp = Xt + (size_t)c * d;
     } else {
@@ -285,7 +259,7 @@ __global__ __launch_bounds__(256) void k_bv_step(BvKargs<ARD> args) {
         const float* zs = Zs + (size_t)i * d;
         double sq = 0.0;
         for (int e = 0; e < d; ++e) { const double df = (double)xp[e] - (double)zs[e]; sq += df * df; }
-        const double kv = os * bv_kappa64(a.kind, sq * il2);
+        const double kv = os * kappa0(a.kind, sq * il2);
         if (f64) k64[i] = kv; else rs[i] = (float)kv;
     }
     __syncthreads();
@@ -298,29 +272,11 @@ __global__ __launch_bounds__(256) void k_bv_step(BvKargs<ARD> args) {
             for (int k = 0; k < n; ++k) x += A1[(size_t)k * ld + i] * k64[k];
             w64[i] = x; Wn[i] = x;
         }
-    } else {   // k_ts_solve's float32 product and refinement step
-        const float osf = sc[S_OS], noisef = sc[S_NOISE], il2f = 1.f / (sc[S_LS] * sc[S_LS]);
-        const float* Ai = a.Ainv + (size_t)t * ld * ld;
-        const float* Dss = a.D2ss + (size_t)t * ld * ld;
+    } else {   // k_ts_solve's solve
         float* Wn = v.W + ((size_t)t * q + c) * ld;
-        for (int i = tid; i < n; i += 256) {
-            float x = 0.f;
-            for (int k = 0; k < n; ++k) x = fmaf(Ai[(size_t)k * ld + i], rs[k], x);
-            vs[i] = x;
-        }
-        __syncthreads();
-        for (int i = tid; i < n; i += 256) {
-            float x = 0.f;
-            for (int k = 0; k < n; ++k) x = fmaf(osf * kappa0(a.kind, Dss[(size_t)k * ld + i] * il2f) + (k == i ? noisef : 0.f), vs[k], x);
-            es[i] = rs[i] - x;
-        }
-        __syncthreads();
-        for (int i = tid; i < n; i += 256) {
-            float x = 0.f;
-            for (int k = 0; k < n; ++k) x = fmaf(Ai[(size_t)k * ld + i], es[k], x);
-            x += vs[i];
-            vs[i] = x; Wn[i] = x;   // (vs[i] is read by this thread only in this loop)
-        }
+        pm_solve_refined(a.Ainv + (size_t)t * ld * ld, a.D2ss + (size_t)t * ld * ld, a.kind, sc[S_OS], sc[S_NOISE], 1.f / (sc[S_LS] * sc[S_LS]), n, ld,
+                         rs, vs, es);
+        for (int i = tid; i < n; i += 256) Wn[i] = vs[i];
     }
     __syncthreads();
     // ---- the pick's mean w . y and prior-step variance s - k . w
@@ -339,7 +295,7 @@ __global__ __launch_bounds__(256) void k_bv_step(BvKargs<ARD> args) {
         for (int k = lane; k < n; k += 64)
             f += f64 ? k64[k] * v.W64[((size_t)t * q + i) * ld + k] : (double)rs[k] * (double)v.W[((size_t)t * q + i) * ld + k];
         for (int x = 32; x > 0; x >>= 1) { sq += __shfl_xor(sq, x); f += __shfl_xor(f, x); }
-        if (lane == 0) c0s[i] = os * bv_kappa64(a.kind, sq * il2) - f;
+        if (lane == 0) c0s[i] = os * kappa0(a.kind, sq * il2) - f;
     }
     __syncthreads();
     if (tid == 0) {   // the new row of G, the outputs and the state

@@ -82,11 +82,18 @@ __device__ __forceinline__ float kappa0_t(float u) {
     const float r = sqrtf(u);
     return (1.f + SQRT5 * r + (5.f / 3.f) * u) * (FAST ? exp_fast(-SQRT5 * r) : expf(-SQRT5 * r));
 }
+// (float32; refine64.h has the float64 twin kappa0(int, double) - the type of u alone chooses between them)
 __device__ __forceinline__ float kappa0(int kind, float u) {
     if (kind == 0) return expf(-0.5f * u);
     float r = sqrtf(u);
     return (1.f + SQRT5 * r + (5.f / 3.f) * u) * expf(-SQRT5 * r);
 }
+
+// The ARD feature scaling z~ = (z - mu) / l in float32: the one expression behind ard.h's Zt (k_ard_scale) and behind every kernel
+// that scales a row itself and must meet those numbers again (the float64 streaming kernels, the believer's stored picks).  The
+// float32 streaming tiles multiply by il = 1 / l instead (k_pm_ard_il), through the twin.
+__device__ __forceinline__ float ard_scaled(float z, float mu, float l) { return (z - mu) / l; }
+__device__ __forceinline__ float ard_scaled_il(float z, float mu, float il) { return (z - mu) * il; }
 
 // ---------------------------------------------------------------------------------------------------
 // reductions: wave shuffles first, one LDS hop across waves (deterministic order)

@@ -116,8 +116,48 @@ void launch_ard_il(const PmCtx& c) {
     k_pm_ard_il<<<(unsigned)((td + 255) / 256), 256, 0, c.st>>>(c.r.ell, const_cast<float*>(c.r.il), (int64_t)td);
 }
 
+// What a kernel of the PmArgsOf family receives: pa, and the groups its instance has (ARD: the query scaling; POOL: *pool; v: the
+// epilogue's arguments)
+template <bool ARD, bool POOL, class EPI = PmRowEpilogue>
+PmArgsOf<ARD, POOL, EPI> pm_kargs(const PmCtx& c, const PmArgs& pa, const PmPool* pool, const typename EPI::Args& v = {}) {
+    PmArgsOf<ARD, POOL, EPI> k{};
+    k.p = pa;
+    if constexpr (ARD) k.r = c.r;
+    if constexpr (POOL) k.s = *pool;
+    k.v = v;
+    return k;
+}
+
+// The grid of a persistent kernel (block, dyn bytes of dynamic LDS) over `items` work items: as many workgroups as are resident at once
+template <class K>
+int pm_persistent_grid(K kernel, int block, size_t dyn, int64_t items) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+    return (int)std::min<int64_t>(items, (int64_t)num_cus() * per_cu);
+}
+
+// The selection state of a pool call: lists of k entries per (task, chunk) in the scratch, every list empty at the start (one that no
+// workgroup writes holds nothing), the exclusion lists only with their offsets.  The caller adds score_mean and top_*; the launches
+// fill grid[].
+PmPool pm_pool(const int64_t* excl_idx, const int64_t* excl_off, int k, int T, int64_t* cand_idx, float* cand_val, int64_t rows, hipStream_t st) {
+    PmPool s{};
+    s.excl_idx = excl_off ? excl_idx : nullptr; s.excl_off = excl_off;
+    s.k = k; s.chunks_max = pm_pool_chunks_max(T);
+    s.cand_idx = cand_idx; s.cand_val = cand_val;
+    s.walked = rows > 0 ? 1 : 0;
+    if (k > 0) hipMemsetAsync(cand_idx, 0xff, sizeof(int64_t) * (size_t)T * s.chunks_max * k, st);
+    return s;
+}
+
+// a caller's scratch of `need` bytes: large enough, and (where anything is needed) there and 8-byte aligned
+int check_scratch(const void* scratch, size_t have, size_t need) {
+    if (have < need) return ADKF_E_WORKSPACE;
+    if (need > 0 && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 7u))) return ADKF_E_BADARG;
+    return 0;
+}
+
 // The rows and outputs of a prediction call.  POOL (adkf_predict_pool): Zq is the shared pool, q_off unused, mean / var / ei are
-// [T, rows] and nullable, *pool carries the selection (its grid[] is filled by pm_launch).
+// [T, rows] and nullable, *pool (pm_pool) carries the selection; pm_launch fills its grid[].
 struct PmCall {
     int32_t flags;
     const float* Zq; const int64_t* q_off; int64_t rows;
@@ -142,21 +182,11 @@ int pm_launch_walk(const PmCtx& c, PmArgs& pa, PmPool* pool, const typename EPI:
     static const bool optin = lds_optin(dyn_max, {kernel_ptr(&k_predict_marginal<REFINE, false, ARD, POOL, EPI>)});
     // a workgroup's row tiles: K (plain); K, C and the vector A^-1 y (refined)
     const size_t tile_floats = REFINE ? (size_t)2 * PM_TM * pa.buf_ld + ns_pad : (size_t)PM_TM * pa.buf_ld;
-    auto args = [&] {
-        PmArgsOf<ARD, POOL, EPI> k{};
-        k.p = pa;
-        if constexpr (ARD) k.r = c.r;
-        if constexpr (POOL) k.s = *pool;
-        k.v = v;
-        return k;
-    };
     const size_t dyn = tile_floats * sizeof(float);
     if (optin && dyn <= (size_t)dyn_max) {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_predict_marginal<REFINE, false, ARD, POOL, EPI>, PM_NT, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
-        const int grid = (int)std::min<int64_t>(tiles, (int64_t)num_cus() * per_cu);
+        const int grid = pm_persistent_grid(k_predict_marginal<REFINE, false, ARD, POOL, EPI>, PM_NT, dyn, tiles);
         if constexpr (POOL) pool->grid[REFINE ? 1 : 0] = grid;
-        k_predict_marginal<REFINE, false, ARD, POOL, EPI><<<grid, PM_NT, dyn, st>>>(args());
+        k_predict_marginal<REFINE, false, ARD, POOL, EPI><<<grid, PM_NT, dyn, st>>>(pm_kargs<ARD, POOL, EPI>(c, pa, pool, v));
     } else {
         // global row-tile slots: [P, W_ss] and, beyond 128 points, the blocked path's scratch [lg_Dinv, lg_F] - neither is read by prediction
         pa.slot_floats = tile_floats;
@@ -167,7 +197,7 @@ int pm_launch_walk(const PmCtx& c, PmArgs& pa, PmPool* pool, const typename EPI:
         if (slots < 1) return ADKF_E_WORKSPACE;
         const int grid = (int)std::min<int64_t>(tiles, std::min<int64_t>(slots, (int64_t)num_cus() * 8));
         if constexpr (POOL) pool->grid[REFINE ? 1 : 0] = grid;
-        k_predict_marginal<REFINE, true, ARD, POOL, EPI><<<grid, PM_NT, 0, st>>>(args());
+        k_predict_marginal<REFINE, true, ARD, POOL, EPI><<<grid, PM_NT, 0, st>>>(pm_kargs<ARD, POOL, EPI>(c, pa, pool, v));
     }
     return 0;
 }
@@ -185,23 +215,11 @@ int pm_launch(const PmCtx& c, const PmCall& io) {
     pa.q_off = io.q_off; pa.best_f = io.best_f; pa.mean = io.mean; pa.var = io.var; pa.ei = io.ei;
     // upper bound of the tile count (the true one depends on q_off, which lives on the device); POOL: the number of items
     const int64_t tiles = POOL ? ((rows + PM_TM - 1) / PM_TM) * T : rows / PM_TM + T;
-    auto args = [&] {
-        PmArgsOf<ARD, POOL> k{};
-        k.p = pa;
-        if constexpr (ARD) k.r = c.r;
-        if constexpr (POOL) k.s = *pool;
-        return k;
-    };
     // every output row starts at 0: rows outside every task's range and those of skipped tasks (n_s == 0, info != 0) stay so
     const size_t out_n = POOL ? (size_t)rows * T : (size_t)rows;
     if (io.mean && out_n) hipMemsetAsync(io.mean, 0, sizeof(float) * out_n, st);
     if (io.var && out_n) hipMemsetAsync(io.var, 0, sizeof(float) * out_n, st);
     if (io.ei && out_n) hipMemsetAsync(io.ei, 0, sizeof(float) * out_n, st);
-    if constexpr (POOL) {   // every list starts empty: one that no workgroup writes holds nothing
-        if (pool->k > 0) hipMemsetAsync(pool->cand_idx, 0xff, sizeof(int64_t) * (size_t)T * pool->chunks_max * pool->k, st);
-        pool->grid[0] = pool->grid[1] = pool->grid[2] = 0;
-        pool->walked = rows > 0 ? 1 : 0;
-    }
     int rc;
     if (rows > 0) {
         if ((rc = pm_launch_walk<false, ARD, POOL>(c, pa, pool, {}, tiles))) return rc;
@@ -213,10 +231,10 @@ int pm_launch(const PmCtx& c, const PmCall& io) {
             gx = std::min(gx, pool->chunks_max);
             pool->grid[2] = gx;
         }
-        k_predict_marginal64<ARD, POOL><<<dim3(gx, T), PM64_NT, 0, st>>>(args());
+        k_predict_marginal64<ARD, POOL><<<dim3(gx, T), PM64_NT, 0, st>>>(pm_kargs<ARD, POOL>(c, pa, pool));
     }
     if constexpr (POOL)
-        if (pool->k > 0) k_pool_topk<<<T, 64, 0, st>>>(PmArgsOf<false, true>{pa, {}, *pool});
+        if (pool->k > 0) k_pool_topk<<<T, 64, 0, st>>>(pm_kargs<false, true>(c, pa, pool));
     LAUNCH_OK();
     return 0;
 }
@@ -286,10 +304,7 @@ int ts_launch(const PmCtx& c, TsArgs& ta, int64_t rows) {
         if (ta.V64) k_ts_resid<true, ARD><<<dim3(ns, T), 256, 0, st>>>(ta);
         k_ts_solve<false><<<dim3(S, T), 256, 0, st>>>(ta);
         if (ta.V64) k_ts_solve<true><<<dim3(S, T), 256, 0, st>>>(ta);
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ts_stream<ARD>, PM_NT, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
-        const int64_t items = ((rows + PM_TM - 1) / PM_TM) * T;
-        ta.s.grid[0] = (int)std::min<int64_t>(items, (int64_t)num_cus() * per_cu);
+        ta.s.grid[0] = pm_persistent_grid(k_ts_stream<ARD>, PM_NT, 0, ((rows + PM_TM - 1) / PM_TM) * T);
         ta.s.grid[2] = ta.V64 ? std::min(pm64_grid(rows), ta.s.chunks_max) : 0;
         k_ts_stream<ARD><<<ta.s.grid[0], PM_NT, 0, st>>>(args());
         if (ta.V64) k_ts_stream64<ARD><<<dim3(ta.s.grid[2], T), PM64_NT, 0, st>>>(args());
@@ -314,8 +329,7 @@ int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
     if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
     if (m < 64 || m > ADKF_TS_FEATURES_MAX || (m & 63)) return ADKF_E_SIZE;
     const TsScratch l = ts_scratch(scratch, b->T, b->ns_max, S);
-    if (scratch_bytes < l.bytes) return ADKF_E_WORKSPACE;
-    if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 7u)) return ADKF_E_BADARG;
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
     PmCtx c;
     rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
@@ -323,19 +337,16 @@ int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
     const int T = b->T, ns = b->ns_max;
     TsArgs ta{};
     ta.p = pm_args(c, flags, X, rows, info);
-    ta.s.excl_idx = excl_off ? excl_idx : nullptr; ta.s.excl_off = excl_off;
-    ta.s.k = S; ta.s.chunks_max = pm_pool_chunks_max(T);
-    ta.s.cand_idx = l.cand_idx; ta.s.cand_val = l.cand_val;
-    ta.s.top_idx = sel_idx; ta.s.top_val = sel_val; ta.s.walked = rows > 0 ? 1 : 0;
+    ta.s = pm_pool(excl_idx, excl_off, S, T, l.cand_idx, l.cand_val, rows, st);
+    ta.s.top_idx = sel_idx; ta.s.top_val = sel_val;
     ta.omega = omega; ta.phase = phase; ta.w = w; ta.eps = eps; ta.m = m; ta.S = S;
     ta.vec_om = ((b->d & 3) == 0 && aligned16(omega)) ? 1 : 0;
     ta.V = l.v;
     ta.V64 = (c.w.w64 && ns <= R64_MAXN) ? l.v64 : nullptr;
     if (!ta.V64) ta.p.r64_thresh = INFINITY;
     ta.paths = paths;
-    // skipped tasks keep zeros in paths; a list that no workgroup writes holds nothing
+    // skipped tasks keep zeros in paths
     if (paths && rows > 0) hipMemsetAsync(paths, 0, sizeof(float) * (size_t)T * S * (size_t)rows, st);
-    hipMemsetAsync(ta.s.cand_idx, 0xff, sizeof(int64_t) * (size_t)T * ta.s.chunks_max * S, st);
     return ard ? ts_launch<true>(c, ta, rows) : ts_launch<false>(c, ta, rows);
 }
 
@@ -366,13 +377,6 @@ template <bool ARD>
 int bv_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, BvArgs& v, int64_t rows, bool have64) {
     hipStream_t st = c.st;
     const int T = c.b.T;
-    auto args = [&] {
-        BvKargs<ARD> k{};
-        k.p = pa;
-        if constexpr (ARD) k.r = c.r;
-        k.s = pool; k.v = v;
-        return k;
-    };
     if constexpr (ARD) launch_ard_il(c);
     const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
     pool.grid[2] = (have64 && rows > 0) ? std::min(pm64_grid(rows), pool.chunks_max) : 0;
@@ -382,9 +386,9 @@ int bv_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, BvArgs& v, int64_t rows,
         if (rows > 0) {
             if ((rc = pm_launch_walk<false, ARD, true, BvEpilogue>(c, pa, &pool, v, tiles))) return rc;
             if ((rc = pm_launch_walk<true, ARD, true, BvEpilogue>(c, pa, &pool, v, tiles))) return rc;
-            if (have64) k_bv_walk64<ARD><<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(args());
+            if (have64) k_bv_walk64<ARD><<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(pm_kargs<ARD, true, BvEpilogue>(c, pa, &pool, v));
         }
-        k_bv_step<ARD><<<T, 256, 0, st>>>(args());
+        k_bv_step<ARD><<<T, 256, 0, st>>>(pm_kargs<ARD, true, BvEpilogue>(c, pa, &pool, v));
     }
     LAUNCH_OK();
     return 0;
@@ -404,8 +408,7 @@ int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
     if (q < 1) return ADKF_E_BADARG;
     if (q > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
     const BvScratch l = bv_scratch(scratch, b->T, b->ns_max, b->d, q);
-    if (scratch_bytes < l.bytes) return ADKF_E_WORKSPACE;
-    if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 7u)) return ADKF_E_BADARG;
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
     PmCtx c;
     rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
@@ -415,19 +418,14 @@ int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
     pa.best_f = best_f;
     const bool have64 = c.w.w64 && ns <= R64_MAXN;
     if (!have64) pa.r64_thresh = INFINITY;
-    PmPool pool{};
-    pool.excl_idx = excl_off ? excl_idx : nullptr; pool.excl_off = excl_off;
-    pool.k = 1; pool.chunks_max = pm_pool_chunks_max(T);
-    pool.cand_idx = l.cand_idx; pool.cand_val = l.cand_val;
-    pool.walked = rows > 0 ? 1 : 0;
+    PmPool pool = pm_pool(excl_idx, excl_off, 1, T, l.cand_idx, l.cand_val, rows, st);
     BvArgs v{};
     v.q = q;
     v.W = l.W; v.W64 = have64 ? l.W64 : nullptr; v.Xp = l.Xp; v.G = l.G; v.G64 = have64 ? l.G64 : nullptr;
     v.best = l.best; v.cnt = l.cnt; v.trace = trace;
     v.sel_idx = sel_idx; v.sel_val = sel_val; v.sel_mean = sel_mean; v.sel_var = sel_var;
-    // skipped tasks keep zeros in trace; a list that no workgroup writes holds nothing
+    // skipped tasks keep zeros in trace
     if (trace && rows > 0) hipMemsetAsync(trace, 0, sizeof(float) * (size_t)T * q * (size_t)rows, st);
-    hipMemsetAsync(pool.cand_idx, 0xff, sizeof(int64_t) * (size_t)T * pool.chunks_max, st);
     k_bv_init<<<ceil_div(T, 256), 256, 0, st>>>(v, best_f, T);
     return ard ? bv_launch<true>(c, pa, pool, v, rows, have64) : bv_launch<false>(c, pa, pool, v, rows, have64);
 }

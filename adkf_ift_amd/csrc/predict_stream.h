@@ -34,8 +34,8 @@
 // ARD batches (adkf_predict_marginal_ard) run the same kernels on the scaled features z~ = (z - mu) / l of ard.h at unit
 // lengthscale (ARD = true): the support rows are ard.h's Zt_s, centred and scaled already; the query rows cannot be scaled into a
 // buffer (their number is unbounded), so they are scaled while they are staged, (z - mu) * il with il = 1 / l computed once per
-// call (k_pm_ard_il).  k_predict_marginal64<true> scales with k_ard_scale's float32 expression (z - mu) / l before promoting to
-// float64, so a flagged task's rows see the features ARD adkf_predict would give them.
+// call (k_pm_ard_il; ard_scaled_il).  k_predict_marginal64<true> scales with k_ard_scale's own function, ard_scaled: (z - mu) / l in
+// float32, then promoted to float64, so a flagged task's rows see the features ARD adkf_predict would give them.
 //
 // Shared pool (adkf_predict_pool, POOL = true): every task scores the SAME rows X [rows, d].  An item is (task, pool tile);
 // the row source is X + r * d for every task and the destination t * rows + r.  Every workgroup counts the tasks of its
@@ -56,10 +56,14 @@
 //
 // Shared with thompson_stream.h, so that "pool = packed", "a task's numbers do not depend on the grid" and "Thompson's K is
 // prediction's K" hold by construction: the kernel arguments (PmArgs + the optional groups PmArd and PmPool), the pool walk
-// (PmPoolWalk, pm_task_chunks, pm_list_store), the K panel (pm_query_rows, pm_k_panel), and for flagged tasks the float64 kernel row
-// (pm64_kernel_row) and the exchange of the waves' lists (pm64_gather_lists).
+// (PmPoolWalk, pm_task_chunks, pm_list_store), the K panel (pm_query_rows, pm_k_panel), and for flagged tasks the preamble of a float64
+// kernel (Pm64Task, filled by pm64_task: k_predict_marginal64, k_ts_stream64, k_bv_walk64), the float64 kernel row (pm64_kernel_row:
+// k_ts_stream64, and pm64_posterior_row) and the end of a float64 walk (pm64_finish_walk, the three kernels again: the waves' lists
+// through the caller's merge - pm_list_merge here and in the believer, a compare of pairs in Thompson - then the store by the first wave).
 //
-// Shared with believer_stream.h: k_predict_marginal itself.  What a tile's rows become once the K row tile and the two reductions
+// Shared with believer_stream.h: the float64 posterior of one pool row (pm64_posterior_row: the kernel row, c = k A^-1, c . y and c . k
+// summed in one order - k_predict_marginal64 and k_bv_walk64), the merge of a task's lists (pm_merge_task_lists: k_pool_topk at width
+// k, k_bv_step at width 1; k_ts_merge is a compare per lane, another shape), and k_predict_marginal itself.  What a tile's rows become once the K row tile and the two reductions
 // are in place is the template parameter EPI: PmRowEpilogue (the default) writes prediction's outputs and merges the scores;
 // BvEpilogue downdates the variance with the picks made so far before it scores.  The instances of the default are the kernels
 // as they were, arithmetic and order.
@@ -303,6 +307,22 @@ __device__ __forceinline__ void pm_list_store(const PmPool& s, int t, int chunk,
     }
 }
 
+// one wave: the lists of task t that the walks of prediction wrote, `width` entries each, merged under the total order into (lv, li),
+// entry `lane` in each lane (a skipped task, and every task when no walk ran, has no list: -inf / -1)
+__device__ __forceinline__ void pm_merge_task_lists(const PmArgs& a, const PmPool& s, int t, int width, float& lv, long long& li) {
+    const int lane = threadIdx.x & 63;
+    const int total = pm_task_chunks(a, s, t, true) * width;
+    const size_t base = (size_t)t * s.chunks_max * width;
+    lv = -INFINITY; li = -1;
+    for (int e0 = 0; e0 < total; e0 += 64) {
+        const int e = e0 + lane;
+        const bool in = e < total;
+        const long long r = in ? (long long)s.cand_idx[base + e] : -1;
+        const float v = in ? s.cand_val[base + e] : 0.f;
+        pm_list_merge(lv, li, width, v, r, r >= 0, [](long long) { return false; });
+    }
+}
+
 // The walk of one workgroup over a shared pool (see the top of the file): a (task, chunk, tile) cursor that only moves forward,
 // and the list (lv, li) of the task it is at, one entry per lane of the first wave, which it stores when it leaves the task.
 template <int KINDS>
@@ -354,7 +374,7 @@ __device__ __forceinline__ auto pm_query_rows(const PmArgs& a, const float* mu, 
             float s[4];
             pm_ld4(il, k, a.d, a.vec, s);
 #pragma unroll
-            for (int x = 0; x < 4; ++x) v[x] = (z[x] - c[x]) * s[x];
+            for (int x = 0; x < 4; ++x) v[x] = ard_scaled_il(z[x], c[x], s[x]);
         } else {
 #pragma unroll
             for (int x = 0; x < 4; ++x) v[x] = z[x] - c[x];
@@ -611,41 +631,82 @@ __global__ __launch_bounds__(PM_NT) void k_predict_marginal(PmArgsOf<ARD, POOL, 
 constexpr int PM64_NT = 256;
 constexpr int PM64_WAVES = PM64_NT / 64;
 
-// one wave: k[j] = os kappa(|zq - zs_j|^2 il2) in float64 for the n support rows of Zs, published to the wave.  ARD: Zs is Zt_s and
-// the query element is scaled as k_ard_scale scales it, (z - mu) / el in float32.
+// a flagged task as the float64 kernels see it
+struct Pm64Task {
+    int n, ld;                              // support points (at most R64_MAXN) and their leading dimension
+    double os, noise, ls;
+    double il2;                             // 1 / ls^2, the walks of prediction and of the believer.  NOT Thompson's: k_ts_stream64 has always formed
+                                            // (1 / ls)^2, which differs in the last bit, and passes that to pm64_kernel_row itself - il2 is a parameter
+                                            // there so that a caller states which of the two its bits were built with
+    const double* A1;                       // float64 A^-1 [ld, ld] (k_refine64)
+    const float *Zs, *ys, *mu, *el;         // ARD: Zs is Zt_s; el, l per dimension, is null otherwise
+};
+// false: the float64 kernels do not own task t (uniform)
+template <bool ARD, class ARGS>
+__device__ __forceinline__ bool pm64_task(const ARGS& args, int t, Pm64Task& k) {
+    const PmArgs& a = args.p;
+    if (pm_kind_of(a, t) != 2) return false;
+    k.n = pm_ns(a, t); k.ld = a.ns_ld;
+    if (k.n <= 0 || k.n > R64_MAXN) return false;
+    const float* sc = a.scal + (size_t)t * NSCAL;
+    k.os = sc[S_OS]; k.noise = sc[S_NOISE]; k.ls = sc[S_LS]; k.il2 = 1.0 / (k.ls * k.ls);
+    k.A1 = a.w64 + (size_t)t * a.w64_stride;
+    k.Zs = a.Zs + (size_t)t * k.ld * a.d;
+    k.ys = a.y_s + (size_t)t * k.ld;
+    k.mu = a.mean_s + (size_t)t * a.d;
+    k.el = nullptr;
+    if constexpr (ARD) k.el = args.r.ell + (size_t)t * a.d;
+    return true;
+}
+
+// one wave: k[j] = os kappa(|zq - zs_j|^2 il2) in float64 for the support rows of the task, published to the wave.  ARD: the query
+// element is scaled as k_ard_scale scales it (ard_scaled, in float32) before it is promoted.
 template <bool ARD>
-__device__ __forceinline__ void pm64_kernel_row(const PmArgs& a, const float* zq, const float* Zs, int n, const float* mu, const float* el,
-                                                double os, double il2, double* k) {
+__device__ __forceinline__ void pm64_kernel_row(const PmArgs& a, const Pm64Task& tk, const float* zq, double il2, double* k) {
     const int lane = threadIdx.x & 63;
-    for (int j = lane; j < n; j += 64) {
-        const float* zs = Zs + (size_t)j * a.d;
+    for (int j = lane; j < tk.n; j += 64) {
+        const float* zs = tk.Zs + (size_t)j * a.d;
         double s = 0.0;
         if constexpr (ARD) {
-            for (int c = 0; c < a.d; ++c) { const double e = (double)((zq[c] - mu[c]) / el[c]) - (double)zs[c]; s += e * e; }
+            for (int c = 0; c < a.d; ++c) { const double e = (double)ard_scaled(zq[c], tk.mu[c], tk.el[c]) - (double)zs[c]; s += e * e; }
         } else {
             for (int c = 0; c < a.d; ++c) { const double e = (double)zq[c] - (double)zs[c]; s += e * e; }
         }
-        const double u = s * il2;
-        double kv;
-        if (a.kind == ADKF_KERNEL_RBF) kv = exp(-0.5 * u);
-        else { const double rr = sqrt(u); kv = (1.0 + 2.23606797749979 * rr + (5.0 / 3.0) * u) * exp(-2.23606797749979 * rr); }
-        k[j] = os * kv;
+        k[j] = tk.os * kappa0(a.kind, s * il2);
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 }
 
+// one wave: the float64 posterior of the pool row zq - the kernel row into k, c = k A^-1, then s1 = c . y and s2 = c . k in every lane
+// (mean s1, latent variance os - s2).  Every sum has a fixed order.
+template <bool ARD>
+__device__ __forceinline__ void pm64_posterior_row(const PmArgs& a, const Pm64Task& tk, const float* zq, double* k, double& s1, double& s2) {
+    const int lane = threadIdx.x & 63;
+    pm64_kernel_row<ARD>(a, tk, zq, tk.il2, k);
+    s1 = 0.0; s2 = 0.0;
+    for (int j = lane; j < tk.n; j += 64) {
+        double c = 0.0;
+        for (int q = 0; q < tk.n; ++q) c += k[q] * tk.A1[(size_t)q * tk.ld + j];
+        s1 += c * (double)tk.ys[j];
+        s2 += c * k[j];
+    }
+    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+}
+
 // the end of a float64 walk: the first wave takes the entry (v, i) that each lane of the other waves holds, wave by wave, through
-// merge(v, i)
+// merge(v, i) - which updates (lv, li) - and stores its list, `width` entries, as that of (t, blockIdx.x)
 template <class M>
-__device__ __forceinline__ void pm64_gather_lists(float lv, long long li, M merge) {
+__device__ __forceinline__ void pm64_finish_walk(const PmPool& s, int t, int width, float& lv, long long& li, M merge) {
     __shared__ float mv[PM64_WAVES - 1][64];
     __shared__ long long mi[PM64_WAVES - 1][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (wv > 0) { mv[wv - 1][lane] = lv; mi[wv - 1][lane] = li; }
     __syncthreads();
-    if (wv == 0)
+    if (wv == 0) {
         for (int w = 0; w < PM64_WAVES - 1; ++w) merge(mv[w][lane], mi[w][lane]);
+        pm_list_store(s, t, blockIdx.x, lane, width, lv, li);
+    }
 }
 
 // POOL: grid (chunks, T); workgroup (c, t) walks the pool rows c * 4 + wave, stride chunks * 4, and writes the list of (t, c)
@@ -656,32 +717,16 @@ __global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(PmArgsOf<ARD, PO
     [[maybe_unused]] float lv = -INFINITY;   // POOL: every wave keeps a list of the rows it evaluates; merged at the end
     [[maybe_unused]] long long li = -1;
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (pm_kind_of(a, t) != 2) return;   // (uniform)
-    const int n = pm_ns(a, t), ld = a.ns_ld;
-    if (n <= 0 || n > R64_MAXN) return;
+    Pm64Task tk;
+    if (!pm64_task<ARD>(args, t, tk)) return;   // (uniform)
     int64_t lo, hi;
     if constexpr (POOL) { lo = 0; hi = a.rows; }
     else pm_range(a, t, lo, hi);
-    const float* sc = a.scal + (size_t)t * NSCAL;
-    const double os = sc[S_OS], noise = sc[S_NOISE], ls = sc[S_LS], il2 = 1.0 / (ls * ls);
-    const double* A1 = a.w64 + (size_t)t * a.w64_stride;   // float64 A^-1 [ld, ld]
-    const float* Zs = a.Zs + (size_t)t * ld * a.d;
-    const float* ys = a.y_s + (size_t)t * ld;
-    const float *mu = nullptr, *el = nullptr;
-    if constexpr (ARD) { mu = a.mean_s + (size_t)t * a.d; el = args.r.ell + (size_t)t * a.d; }
-    double* k = kr[wv];
     for (int64_t r = lo + (int64_t)blockIdx.x * PM64_WAVES + wv; r < hi; r += (int64_t)gridDim.x * PM64_WAVES) {
-        pm64_kernel_row<ARD>(a, a.Zq + (size_t)r * a.d, Zs, n, mu, el, os, il2, k);
-        double s1 = 0.0, s2 = 0.0;
-        for (int j = lane; j < n; j += 64) {
-            double c = 0.0;
-            for (int q = 0; q < n; ++q) c += k[q] * A1[(size_t)q * ld + j];
-            s1 += c * (double)ys[j];
-            s2 += c * k[j];
-        }
-        for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+        double s1, s2;
+        pm64_posterior_row<ARD>(a, tk, a.Zq + (size_t)r * a.d, kr[wv], s1, s2);
         [[maybe_unused]] float score = 0.f;
-        if (lane == 0) score = pm_row_out<POOL>(args, t, r, (float)s1, (float)(os - s2), (float)(os - s2 + noise));
+        if (lane == 0) score = pm_row_out<POOL>(args, t, r, (float)s1, (float)(tk.os - s2), (float)(tk.os - s2 + tk.noise));
         if constexpr (POOL)
             if (args.s.k > 0) pm_list_merge(lv, li, args.s.k, score, (long long)r, lane == 0, [&](long long q) { return pm_excluded(args.s, t, q); });
         __builtin_amdgcn_wave_barrier();
@@ -689,8 +734,7 @@ __global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(PmArgsOf<ARD, PO
     }
     if constexpr (POOL) {
         if (args.s.k <= 0) return;   // (uniform)
-        pm64_gather_lists(lv, li, [&](float v, long long i) { pm_list_merge(lv, li, args.s.k, v, i, i >= 0, [](long long) { return false; }); });
-        if (wv == 0) pm_list_store(args.s, t, blockIdx.x, lane, args.s.k, lv, li);
+        pm64_finish_walk(args.s, t, args.s.k, lv, li, [&](float v, long long i) { pm_list_merge(lv, li, args.s.k, v, i, i >= 0, [](long long) { return false; }); });
     }
 }
 
@@ -700,18 +744,9 @@ __global__ __launch_bounds__(64) void k_pool_topk(PmArgsOf<false, true> args) {
     const PmArgs& a = args.p;
     const PmPool& s = args.s;
     const int t = blockIdx.x, lane = threadIdx.x, k = s.k;
-    const int C = pm_task_chunks(a, s, t, true);
-    float lv = -INFINITY;
-    long long li = -1;
-    const size_t base = (size_t)t * s.chunks_max * k;
-    const int total = C * k;
-    for (int e0 = 0; e0 < total; e0 += 64) {
-        const int e = e0 + lane;
-        const bool in = e < total;
-        const long long r = in ? (long long)s.cand_idx[base + e] : -1;
-        const float v = in ? s.cand_val[base + e] : 0.f;
-        pm_list_merge(lv, li, k, v, r, r >= 0, [](long long) { return false; });
-    }
+    float lv;
+    long long li;
+    pm_merge_task_lists(a, s, t, k, lv, li);
     if (lane < k) { s.top_idx[(size_t)t * k + lane] = li; s.top_val[(size_t)t * k + lane] = li >= 0 ? lv : -INFINITY; }
 }
 

@@ -232,6 +232,12 @@ __device__ __forceinline__ void kappa3_e(int kind, double u, double e, double& k
 }
 __device__ __forceinline__ double exp_cached(const double* E, size_t idx, int kind, double u) { return E ? E[idx] : exp_term_d(kind, u); }
 
+// kappa alone (kappa3_d's k0), for the float64 rows of the streaming kernels
+__device__ __forceinline__ double kappa0(int kind, double u) {
+    if (kind == 0) return exp(-0.5 * u);
+    const double r = sqrt(u);
+    return (1.0 + 2.23606797749979 * r + (5.0 / 3.0) * u) * exp(-2.23606797749979 * r);
+}
 __device__ __forceinline__ void kappa3_d(int kind, double u, double& k0, double& k1, double& k2) {
     if (kind == 0) { k0 = exp(-0.5 * u); k1 = -0.5 * k0; k2 = 0.25 * k0; }
     else {

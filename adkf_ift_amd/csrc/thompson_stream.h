@@ -12,7 +12,8 @@
 //   k_ts_resid   per (task, support row): the m features of the row (one per thread, the feature row of omega streamed), then
 //                g for the S samples (one wave per sample, butterfly sum) and r into V [T, S, ns];
 //   k_ts_solve   per (task, sample): v = A^-1 r, then ONE refinement step v += A^-1 (r - A v) with A regenerated from D2ss (as
-//                ProbCres does), in place in V.  That step is why this call has no plain / refined distinction (pm_kind_of);
+//                ProbCres does), in place in V (pm_solve_refined).  That step is why this call has no plain / refined distinction
+//                (pm_kind_of);
 //   k_ts_stream  per (task, pool tile), a persistent grid placed over tasks and tiles by the pool walk of predict_stream.h
 //                (PmPoolWalk, over the plain and the refined tasks at once): per 64-feature chunk P = (X - mu) Omega^T on the
 //                FP32 MFMA (pm_mm with pm_query_rows, the operand staging of the distance product), sqrt(2 s / m)
@@ -26,17 +27,20 @@
 //                end of the walk one pair per (task, chunk, sample) goes to scratch with ordinary stores;
 //   k_ts_merge   one wave per task: lane q reduces the chunks' pairs of sample q under the same order.
 // Tasks flagged for the float64 path (refine64.h: their K v cancels beyond float32) take the <true> instances of the first two
-// kernels - the features and r in float64, v from k_refine64's float64 A^-1 - and k_ts_stream64 (one wave per pool row, the
-// kernel row and the exchange of the waves' pairs those of k_predict_marginal64) instead of k_ts_stream.  The cosine there is
-// cosf of the argument reduced to [-pi, pi] in float64.
+// kernels - the features and r in float64, v from k_refine64's float64 A^-1 - and k_ts_stream64 (one wave per pool row; the task
+// preamble, the kernel row and the end of the walk are k_predict_marginal64's: pm64_task, pm64_kernel_row, pm64_finish_walk) instead
+// of k_ts_stream.  The cosine there is cosf of the argument reduced to [-pi, pi] in float64.
 //
 // ARD batches (adkf_thompson_pool_ard, ARD = true) are the same call on the scaled features x~ = (x - mu) / l of ard.h at unit
 // lengthscale, with the one basis (omega, phase) every task shares: the support rows are ard.h's Zt_s, centred and scaled already,
 // so k_ts_resid takes omega_j . z~_i as it stands; the pool rows are scaled while they are staged ((x - mu) * il, the il = 1 / l of
 // k_pm_ard_il, as ARD streaming prediction does), for the feature product and the K panel alike, and the feature epilogue has
-// no lengthscale left to apply.  k_ts_stream64<true> scales with k_ard_scale's float32 expression (x - mu) / l before promoting to
-// float64 (the rule of k_predict_marginal64<true>).  k_ts_solve and k_ts_merge are the isotropic instances: the scaled batch's
+// no lengthscale left to apply.  k_ts_stream64<true> scales with k_ard_scale's function (ard_scaled: (x - mu) / l in float32) before
+// promoting to float64 (the rule of k_predict_marginal64<true>).  k_ts_solve and k_ts_merge are the isotropic instances: the scaled batch's
 // scalars and D2ss are those of the unit-lengthscale pipeline that built A^-1 (scal[S_LS] = softplus(RAW_ONE) = 1, ard.h).
+//
+// Shared with believer_stream.h: pm_solve_refined, the float32 solve with its refinement step (k_ts_solve<false> copies v to V, k_bv_step
+// to W and goes on with it).
 #pragma once
 #include <type_traits>
 
@@ -120,6 +124,31 @@ __global__ __launch_bounds__(256) void k_ts_resid(TsArgs args) {
     }
 }
 
+// One workgroup of 256 threads, float32: v = A^-1 r, then ONE refinement step v += A^-1 (r - A v) with A = os kappa(D2ss il2) + noise I
+// regenerated from Dss (as ProbCres does).  Ai: the symmetric A^-1 (column i is row i); rs, vs, es: LDS arrays of n floats of the
+// caller, r in rs (published), v left in vs - entry i by thread i % 256, no barrier after it - and es used up.
+__device__ __forceinline__ void pm_solve_refined(const float* Ai, const float* Dss, int kind, float os, float noise, float il2, int n, int ld,
+                                                 const float* rs, float* vs, float* es) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < n; i += 256) {
+        float s = 0.f;
+        for (int k = 0; k < n; ++k) s = fmaf(Ai[(size_t)k * ld + i], rs[k], s);
+        vs[i] = s;
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {
+        float s = 0.f;
+        for (int k = 0; k < n; ++k) s = fmaf(os * kappa0(kind, Dss[(size_t)k * ld + i] * il2) + (k == i ? noise : 0.f), vs[k], s);
+        es[i] = rs[i] - s;
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {
+        float s = 0.f;
+        for (int k = 0; k < n; ++k) s = fmaf(Ai[(size_t)k * ld + i], es[k], s);
+        vs[i] += s;
+    }
+}
+
 // ---- v = A^-1 r (+ one refinement step in float32), per (task, sample), in place: grid (S, T).  Serves ARD batches unchanged: their
 // scalars, D2ss and A^-1 are those of the scaled batch at unit lengthscale (scal[S_LS] = 1)
 template <bool F64>
@@ -143,28 +172,11 @@ __global__ __launch_bounds__(256) void k_ts_solve(TsArgs args) {
     } else {
         __shared__ float rs[TS_NS_MAX], vs[TS_NS_MAX], es[TS_NS_MAX];
         const float* sc = a.scal + (size_t)t * NSCAL;
-        const float os = sc[S_OS], noise = sc[S_NOISE], il2 = 1.f / (sc[S_LS] * sc[S_LS]);
-        const float* Ai = a.Ainv + (size_t)t * ld * ld;    // symmetric: column i is row i
-        const float* Dss = a.D2ss + (size_t)t * ld * ld;
         for (int i = tid; i < n; i += 256) rs[i] = args.V[base + i];
         __syncthreads();
-        for (int i = tid; i < n; i += 256) {
-            float s = 0.f;
-            for (int k = 0; k < n; ++k) s = fmaf(Ai[(size_t)k * ld + i], rs[k], s);
-            vs[i] = s;
-        }
-        __syncthreads();
-        for (int i = tid; i < n; i += 256) {
-            float s = 0.f;
-            for (int k = 0; k < n; ++k) s = fmaf(os * kappa0(a.kind, Dss[(size_t)k * ld + i] * il2) + (k == i ? noise : 0.f), vs[k], s);
-            es[i] = rs[i] - s;
-        }
-        __syncthreads();
-        for (int i = tid; i < n; i += 256) {
-            float s = 0.f;
-            for (int k = 0; k < n; ++k) s = fmaf(Ai[(size_t)k * ld + i], es[k], s);
-            args.V[base + i] = vs[i] + s;
-        }
+        pm_solve_refined(a.Ainv + (size_t)t * ld * ld, a.D2ss + (size_t)t * ld * ld, a.kind, sc[S_OS], sc[S_NOISE], 1.f / (sc[S_LS] * sc[S_LS]), n, ld,
+                         rs, vs, es);
+        for (int i = tid; i < n; i += 256) args.V[base + i] = vs[i];
     }
 }
 
@@ -292,15 +304,10 @@ __global__ __launch_bounds__(PM64_NT) void k_ts_stream64(TsArgsOf<ARD> args) {
     const PmArgs& a = args.p;
     __shared__ double kr[PM64_WAVES][R64_MAXN];
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, S = args.S, m = args.m;
-    if (!ts_mine<true>(a, t)) return;   // (uniform)
-    const int n = pm_ns(a, t), ld = a.ns_ld;
-    if (n <= 0 || n > R64_MAXN) return;
-    const float* sc = a.scal + (size_t)t * NSCAL;
-    [[maybe_unused]] const double os = sc[S_OS], ls = sc[S_LS], il = 1.0 / ls, il2 = il * il, amp = sqrt(2.0 * os / (double)m);
-    const float* Zs = a.Zs + (size_t)t * ld * a.d;
-    const float* mu = a.mean_s + (size_t)t * a.d;
-    const float* el = nullptr;   // ARD: l per dimension
-    if constexpr (ARD) el = args.r.ell + (size_t)t * a.d;
+    Pm64Task tk;
+    if (!pm64_task<ARD>(args, t, tk)) return;   // (uniform)
+    const int n = tk.n, ld = tk.ld;
+    [[maybe_unused]] const double il = 1.0 / tk.ls, il2 = il * il, amp = sqrt(2.0 * tk.os / (double)m);   // (il2 not Pm64Task's 1 / ls^2: this kernel's bits)
     const int ql = lane < S ? lane : S - 1;   // (lanes beyond S compute sample S - 1 again and store nothing)
     const float* wq = args.w + ((size_t)t * S + ql) * m;
     const double* vq = args.V64 + ((size_t)t * S + ql) * ld;
@@ -309,17 +316,17 @@ __global__ __launch_bounds__(PM64_NT) void k_ts_stream64(TsArgsOf<ARD> args) {
     long long li = -1;
     for (int64_t r = (int64_t)blockIdx.x * PM64_WAVES + wv; r < a.rows; r += (int64_t)gridDim.x * PM64_WAVES) {
         const float* zq = a.Zq + (size_t)r * a.d;
-        pm64_kernel_row<ARD>(a, zq, Zs, n, mu, el, os, il2, k);
+        pm64_kernel_row<ARD>(a, tk, zq, il2, k);
         double f = 0.0;
         for (int j0 = 0; j0 < m; j0 += 64) {   // (m is a multiple of 64) one feature per lane, then every lane adds its sample's 64 terms
             const float* om = args.omega + (size_t)(j0 + lane) * a.d;
             double s = 0.0;
             double cv;
-            if constexpr (ARD) {   // the float32 feature of k_ard_scale, promoted (as pm64_kernel_row<true>)
-                for (int c = 0; c < a.d; ++c) s = fma((double)om[c], (double)((zq[c] - mu[c]) / el[c]), s);
+            if constexpr (ARD) {   // the float32 feature of k_ard_scale (ard_scaled), promoted as pm64_kernel_row<true> promotes it
+                for (int c = 0; c < a.d; ++c) s = fma((double)om[c], (double)ard_scaled(zq[c], tk.mu[c], tk.el[c]), s);
                 cv = amp * ts_cos(s + (double)args.phase[j0 + lane]);
             } else {
-                for (int c = 0; c < a.d; ++c) s = fma((double)om[c], (double)zq[c] - (double)mu[c], s);
+                for (int c = 0; c < a.d; ++c) s = fma((double)om[c], (double)zq[c] - (double)tk.mu[c], s);
                 cv = amp * ts_cos(s * il + (double)args.phase[j0 + lane]);
             }
             for (int jj = 0; jj < 64; ++jj) f = fma((double)wq[j0 + jj], __shfl(cv, jj), f);
@@ -335,8 +342,7 @@ __global__ __launch_bounds__(PM64_NT) void k_ts_stream64(TsArgsOf<ARD> args) {
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
-    pm64_gather_lists(lv, li, [&](float v, long long i) { if (i >= 0 && pm_beats(v, i, lv, li)) { lv = v; li = i; } });
-    if (wv == 0) pm_list_store(args.s, t, blockIdx.x, lane, S, lv, li);
+    pm64_finish_walk(args.s, t, S, lv, li, [&](float v, long long i) { if (i >= 0 && pm_beats(v, i, lv, li)) { lv = v; li = i; } });
 }
 
 // ---- one wave per task: lane q reduces the pairs of sample q over the task's chunks (skipped tasks, and every task when no
