@@ -80,8 +80,10 @@ struct ProbDist {
     __device__ void b_fin(int k, int j, const float4 (&r)[2], float (&v)[4]) const { a_fin(j, k, r, v); }
     __device__ void a4(int i, int k, float (&v)[4]) const { float4 r[2]; a_raw(i, k, r); a_fin(i, k, r, v); }
     __device__ void b4(int k, int j, float (&v)[4]) const { float4 r[2]; b_raw(k, j, r); b_fin(k, j, r, v); }
-    // symmetric (X == Y): only the tiles on or above the diagonal are computed; they also write their mirror image, so
-    // the result is EXACTLY symmetric
+    // symmetric (X == Y): only the tiles on or above the diagonal are computed, and of a tile ON the diagonal only the entries on
+    // or above it; every entry above the diagonal also writes its mirror image, so the result is EXACTLY symmetric.  (A diagonal
+    // tile that stored both of its halves was not, on the split-bfloat16 pipe: gemm_x3.h adds x0 y2 before x2 y0 and x0 y1 before
+    // x1 y0, so entry (j, i) sums the same products as (i, j) in another order and may differ from it in the last bit.)
     __device__ bool active(int m0, int n0) const { return !symmetric || m0 <= n0; }
     // squared norms of the centred rows: summed by the GEMM kernel itself while it stages the operands (gemm.h: set_rowsq),
     // so no separate pass over Z and no norm arrays
@@ -91,12 +93,13 @@ struct ProbDist {
         return (symmetric && i == j) ? 0.f : v;
     }
     __device__ void epi(int i, int j, float acc, float*) const {
+        if (symmetric && i > j) return;   // (a diagonal tile's lower half: written as the mirror image of the upper one)
         const float v = value(i, j, acc);
         Do[(size_t)i * y_ld + j] = v;
-        if (symmetric && (i / GT) < (j / GT)) Do[(size_t)j * y_ld + i] = v;
+        if (symmetric && i < j) Do[(size_t)j * y_ld + i] = v;
     }
     __device__ void epi4(int i0, int j, const float (&acc)[4], float* red) const {   // mirror image as ONE 16-byte store
-        if (!(symmetric && vec && (i0 / GT) < (j / GT))) {
+        if (!(symmetric && vec && i0 + 3 < j)) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) epi(i0 + r, j, acc[r], red);
             return;

@@ -1,6 +1,6 @@
 """Diagnostics (not collected): does the accuracy of the squared distances decide the float32 error of dL/dZ on the worst task of the
 point-permutation batch?  The workspace's D^2 blocks are overwritten with float64-computed, float32-rounded ones (layout:
-csrc/host_gp.h::carve) before the fit and the hypergradient run on them (REUSE_DIST)."""
+csrc/host_gp.h::carve through tests/gp_stage_inputs.py::stage_view) before the fit and the hypergradient run on them (REUSE_DIST)."""
 import os, sys
 import numpy as np
 import torch
@@ -15,16 +15,11 @@ def run(dev, Zs, ys, Zq, yq, phi=None, exact=False):
     b = gp_ops.GPBatch(Zs, ys, pri, "rbf", Z_q=Zq, y_q=yq)
     phi0, l0 = gp_ops.init_params_batch(b)
     if exact:
+        from gp_stage_inputs import stage_view
         ws, _ = b.workspace()
-        flat = ws.view(torch.uint8)
-        al = lambda n: (n * 4 + 255) // 256 * 256
-        off = al(T * d)
         zs, zq = Zs.double(), Zq.double()
-        for X, Y in ((zs, zs), (zq, zs), (zq, zq)):
-            D = (X.unsqueeze(2) - Y.unsqueeze(1)).pow(2).sum(-1).float().contiguous()
-            nb = D.numel() * 4
-            flat[off:off + nb] = D.view(torch.uint8).flatten()
-            off += al(D.numel())
+        for out, (X, Y) in zip(stage_view(ws, T, N, Zq.shape[1], d)[1:4], ((zs, zs), (zq, zs), (zq, zq))):
+            out.copy_((X.unsqueeze(2) - Y.unsqueeze(1)).pow(2).sum(-1).float())
     b.flags = gp_ops.REUSE_DIST
     if phi is None:
         phi, f, gn, ne, info = gp_ops.fit(b, phi0, max_evals=20, exact_evals=True)
