@@ -22,6 +22,7 @@
 #include "large_fused.h"
 #include "gemm_x3.h"
 #include "dense_x3.h"
+#include "dist_task.h"
 #include "predict_stream.h"
 #include "thompson_stream.h"
 #include "believer_stream.h"
