@@ -12,6 +12,8 @@ batched fit and one ``adkf_predict_pool`` call per iteration, which returns each
 and each function picks its own best candidate - a diverse batch of ``query_batch_size > 1`` picks from one pass, with no
 ``best_f`` and nothing that can underflow.  Both EI loops take ``acquisition="log_ei"``: the same candidates ranked by log EI
 (``ADKF_PM_LOG_EI``), which stays finite where float32 EI is 0 on the whole pool and the ``"ei"`` loops fall back to random picks.
+``run_gp_mes_bo_batched`` is the loop under max-value entropy search: one batched fit, one ``gp_ops.max_value_samples`` call (the
+minima of pathwise posterior draws over the whole pool) and one ``adkf_mes_pool`` call per iteration, with no ``best_f`` in the score.
 
 Only the Matern-5/2 branch exists here (the Tanimoto kernel of the reference's fingerprint baseline is not a
 distance-based kernel and is out of the library's scope).
@@ -326,6 +328,84 @@ def run_gp_ts_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
                     break
             if len(pick) < query_batch_size:
                 pick += rng.choice(free(queried[r] + pick), size=query_batch_size - len(pick), replace=False).tolist()
+            queried[r] = list(set(queried[r] + pick))
+            records[r].extend(pick)
+    return records
+
+
+@torch.no_grad()
+def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
+                          kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
+                          rngs: List[np.random.Generator], n_features: int = 1024, oversample: int = 4,
+                          feature_seed: int = 0, ard: bool = False, n_max_samples: int = 16) -> List[List[int]]:
+    """``len(rngs)`` replicates of a max-value entropy search BO loop (Wang & Jegelka 2017) over the same pool at once
+    (minimisation, as ``run_gp_ei_bo``); returns their records: the best initial index, then the picks in descending score.  Per
+    iteration the replicates' queried sets are fitted by ONE ``gp_ops.fit`` (as ``run_gp_ei_bo_batched``), ONE
+    ``gp_ops.max_value_samples`` call draws ``n_max_samples`` (at most 64) samples of each replicate's minimum over the WHOLE pool -
+    the minima of pathwise posterior draws on a random-Fourier basis of ``n_features`` features (drawn once from ``feature_seed``) -
+    each clamped to be no worse than the replicate's best observed value, and ONE ``gp_ops.mes_pool`` call scores the pool and
+    returns each replicate's ``query_batch_size`` best rows among those it has not queried.  A returned candidate counts when its
+    index is not -1 and its score is finite; a shortfall is filled with random free rows from the replicate's generator, as in
+    ``run_gp_ei_bo_batched``.  No ``best_f`` enters the score and nothing can underflow.  The prior weights and noise draws of
+    replicate r come from a torch generator seeded from ``rngs[r]``, the noise draws at the replicate's own support size: a
+    replicate's record does not depend on which other replicates share the batch.  ``oversample`` is accepted for the signature of
+    ``run_gp_ts_bo_batched`` and not used.  ``ard``: as ``run_gp_ts_bo_batched``; the same two calls serve ARD batches."""
+    R, n = len(rngs), x_all.shape[0]
+    if not 1 <= query_batch_size <= gp_ops._lib.POOL_TOPK_MAX:
+        raise ValueError(f"query_batch_size must be in [1, {gp_ops._lib.POOL_TOPK_MAX}], got {query_batch_size}")
+    S = int(n_max_samples)
+    if not 1 <= S <= gp_ops._lib.TS_SAMPLES_MAX:
+        raise ValueError(f"n_max_samples must be in [1, {gp_ops._lib.TS_SAMPLES_MAX}], got {n_max_samples}")
+    y_all = (y_all - y_all.mean()) / y_all.std()
+    X = x_all.detach().float().contiguous()
+    omega, phase = gp_ops.rff_basis(kernel_type, X.shape[1], n_features, generator=torch.Generator().manual_seed(int(feature_seed)),
+                                    device=X.device)
+    queried = [rng.choice(np.arange(init_from, n), size=num_init_points, replace=False).tolist() for rng in rngs]
+    records = [[min(q)] for q in queried]
+    gens = [torch.Generator().manual_seed(int(rng.integers(0, 2 ** 62))) for rng in rngs]
+
+    def free(taken):
+        taken = set(taken)
+        return [i for i in range(n) if i not in taken]
+
+    for _ in range(num_bo_iters):
+        sizes = [len(q) for q in queried]
+        ns = max(sizes)
+        Zs = torch.zeros(R, ns, X.shape[1], dtype=torch.float32, device=X.device)
+        ys = torch.zeros(R, ns, dtype=torch.float32, device=X.device)
+        w = torch.empty(R, S, n_features, dtype=torch.float32)
+        eps = torch.zeros(R, S, ns, dtype=torch.float32)
+        pri, phi0, best = [], [], []
+        for r, q in enumerate(queried):
+            xq, yq = x_all[q], y_all[q]
+            best.append(yq.min().item())
+            _, model, mll = create_gp(xq, yq, kernel_type, device, noise_init, noise_prior)
+            Zs[r, :sizes[r]] = model.train_inputs[0].detach().float()
+            ys[r, :sizes[r]] = model.train_targets.detach().float()
+            pri.append(mll.priors_row(X.device))
+            p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
+            phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
+            w[r] = torch.randn(S, n_features, generator=gens[r])
+            eps[r, :, :sizes[r]] = torch.randn(S, sizes[r], generator=gens[r])
+        n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
+        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
+        phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
+        gp_ops.check_info(info, "run_gp_mes_bo_batched fit")
+        b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+        mv = gp_ops.max_value_samples(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w.to(X.device), eps=eps.to(X.device),
+                                      maximize=False)
+        gp_ops.check_info(mv["info"], "BO posterior")
+        # the minimum of f is no worse than the best value seen
+        ystar = torch.minimum(mv["ystar"], torch.tensor(best, dtype=torch.float32, device=X.device)[:, None])
+        out = gp_ops.mes_pool(b, phi, X, ystar=ystar, maximize=False, topk=query_batch_size, exclude=queried)
+        gp_ops.check_info(out["info"], "BO posterior")
+        top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
+        usable = torch.isfinite(top_val) & (top_idx >= 0)   # (a prefix of each row: descending scores, the -1 / -inf tail last)
+        for r, rng in enumerate(rngs):
+            nonzero = int(usable[r].sum())
+            pick = top_idx[r, :nonzero].tolist()
+            if nonzero < query_batch_size:
+                pick += rng.choice(free(queried[r] + pick), size=query_batch_size - nonzero, replace=False).tolist()
             queried[r] = list(set(queried[r] + pick))
             records[r].extend(pick)
     return records

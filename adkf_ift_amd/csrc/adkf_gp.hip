@@ -26,6 +26,7 @@
 #include "predict_stream.h"
 #include "thompson_stream.h"
 #include "believer_stream.h"
+#include "mes_stream.h"
 
 #include "host_common.h"
 #include "host_gp.h"
@@ -289,6 +290,13 @@ int adkf_believer_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flag
                            void* stream) {
     return believer_pool(true, b, phi, flags, X, rows, best_f, excl_idx, excl_off, q, trace, sel_idx, sel_val, sel_mean, sel_var, info, ws,
                          ws_bytes, scratch, scratch_bytes, stream);
+}
+
+int adkf_mes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* ystar, int32_t S,
+                  const int64_t* excl_idx, const int64_t* excl_off, float* score, int32_t k, int64_t* top_idx, float* top_val, int32_t* info,
+                  void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    return mes_pool(b, phi, flags, X, rows, ystar, S, excl_idx, excl_off, score, k, top_idx, top_val, info, ws, ws_bytes, scratch, scratch_bytes,
+                    stream);
 }
 
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

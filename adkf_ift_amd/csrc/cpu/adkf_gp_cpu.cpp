@@ -681,6 +681,92 @@ int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, co
     return 0;
 }
 
+// g(gamma) = gamma phi(gamma) / (2 Phi(gamma)) - log Phi(gamma) of adkf_mes_pool in float64: log1p where Phi -> 1; as written down to
+// gamma = -8 (the two terms cancel from ~a^2 / 2 <= 32: a few 1e-15); below that through Mills' ratio, with a = -gamma, w = a^-2 and
+// Phi(-a) = phi(a) M / a, M = 1 + w U, U = -1 + 3 w - 15 w^2 + ... (summed while its terms shrink, as log_h):
+//     g = U / (2 M) + log(2 pi) / 2 + log a - log M,
+// in which a^2 / 2 never appears.  +-inf and NaN give NaN.
+static double mes_term(double g) {
+    if (!std::isfinite(g)) return std::numeric_limits<double>::quiet_NaN();
+    if (g > -8.0) {
+        const double pdf = std::exp(-0.5 * g * g) / std::sqrt(2.0 * M_PI);
+        if (g > 0.0) {
+            const double q = 0.5 * std::erfc(g / std::sqrt(2.0));
+            return 0.5 * g * pdf / (1.0 - q) - std::log1p(-q);
+        }
+        const double cdf = 0.5 * std::erfc(-g / std::sqrt(2.0));
+        return 0.5 * g * pdf / cdf - std::log(cdf);
+    }
+    const double a = -g, w = (1.0 / a) / a;
+    double U = -1.0, term = -1.0;
+    for (int k = 1; k < 64; ++k) {
+        const double next = -term * (2 * k + 1) * w;
+        if (std::fabs(next) >= std::fabs(term)) break;
+        U += term = next;
+    }
+    const double M = 1.0 + w * U;
+    return 0.5 * U / M + 0.5 * std::log(2.0 * M_PI) + std::log(a) - std::log(M);
+}
+
+// Max-value entropy search over a shared pool (include/adkf_gp.h): the posterior of adkf_predict_pool and mes_term in float64,
+// the score rounded to float32 at the boundary; the selection ranks those float32 values under adkf_predict_pool's total order.
+int adkf_mes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* ystar, int32_t S,
+                  const int64_t* excl_idx, const int64_t* excl_off, float* score, int32_t k, int64_t* top_idx, float* top_val, int32_t* info,
+                  void*, size_t, void*, size_t, void*) {
+    if (int rc = check(b, false, true)) return rc;
+    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (!ystar) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (k < 0) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (k == 0 && !score) return ADKF_E_BADARG;
+    if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
+    if (k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    const float ninf = -std::numeric_limits<float>::infinity();
+    const bool maximize = (flags & ADKF_PM_MAXIMIZE) != 0;
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        const size_t o = (size_t)t * (size_t)rows;
+        if (score) std::fill(score + o, score + o + rows, 0.f);
+        for (int q = 0; q < k; ++q) { top_idx[(size_t)t * k + q] = -1; top_val[(size_t)t * k + q] = ninf; }
+        std::vector<float> sc((size_t)rows);
+        const float* y = b->y_s + (size_t)t * b->ns_max;
+        const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
+            const int n = in.n;
+            const double il2 = 1.0 / (in.l * in.l);
+            std::vector<double> kr(n);
+            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); kr[j] = in.s * k0; }
+            double mu = 0.0, q = 0.0;
+            for (int j = 0; j < n; ++j) {
+                double cj = 0.0;
+                for (int i = 0; i < n; ++i) cj += kr[i] * in.Ainv[(size_t)i * n + j];
+                mu += cj * (double)y[j];
+                q += cj * kr[j];
+            }
+            const double sg = std::sqrt(std::max(in.s - q, 1e-12));
+            double sum = 0.0;
+            for (int s = 0; s < S; ++s) {
+                const double ys = ystar[(size_t)t * S + s];
+                sum += mes_term((maximize ? (ys - mu) : (mu - ys)) / sg);
+            }
+            sc[r] = (float)(sum / S);
+            if (score) score[o + r] = sc[r];
+        });
+        if (!done || k <= 0) continue;
+        std::vector<int64_t> cand;
+        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
+        for (int64_t r = 0; r < rows; ++r)
+            if (sc[r] == sc[r] && !(xb && std::binary_search(xb, xe, r))) cand.push_back(r);
+        const size_t kk = std::min<size_t>(k, cand.size());
+        std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return sc[a] > sc[c] || (sc[a] == sc[c] && a < c); });
+        for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)t * k + q] = cand[q]; top_val[(size_t)t * k + q] = sc[cand[q]]; }
+    }
+    return 0;
+}
+
 size_t adkf_thompson_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { return 0; }
 
 // Thompson sampling over a shared pool (include/adkf_gp.h): the pathwise posterior draws in float64, rounded to float32 at the

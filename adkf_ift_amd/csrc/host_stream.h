@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool and adkf_believer_pool_ard): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard and adkf_mes_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
 #pragma once
 #include "host_ard.h"
 
@@ -428,6 +428,57 @@ int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
     if (trace && rows > 0) hipMemsetAsync(trace, 0, sizeof(float) * (size_t)T * q * (size_t)rows, st);
     k_bv_init<<<ceil_div(T, 256), 256, 0, st>>>(v, best_f, T);
     return ard ? bv_launch<true>(c, pa, pool, v, rows, have64) : bv_launch<false>(c, pa, pool, v, rows, have64);
+}
+
+// The launches of a prepared max-value entropy search call, as pm_launch<ARD, true>: the walks of prediction with MesEpilogue, the
+// float64 walk where the workspace has a float64 region, then prediction's merge of the lists.
+template <bool ARD>
+int mes_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, const MesArgs& v, int64_t rows) {
+    hipStream_t st = c.st;
+    const int T = c.b.T;
+    if constexpr (ARD) launch_ard_il(c);
+    const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
+    // every score starts at 0: the rows of skipped tasks (n_s == 0, info != 0) stay so
+    if (v.score && rows > 0) hipMemsetAsync(v.score, 0, sizeof(float) * (size_t)rows * T, st);
+    int rc;
+    if (rows > 0) {
+        if ((rc = pm_launch_walk<false, ARD, true, MesEpilogue>(c, pa, &pool, v, tiles))) return rc;
+        if ((rc = pm_launch_walk<true, ARD, true, MesEpilogue>(c, pa, &pool, v, tiles))) return rc;
+    }
+    if (c.w.w64 && rows > 0) {
+        pool.grid[2] = std::min(pm64_grid(rows), pool.chunks_max);
+        k_mes_walk64<ARD><<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(pm_kargs<ARD, true, MesEpilogue>(c, pa, &pool, v));
+    }
+    if (pool.k > 0) k_pool_topk<<<T, 64, 0, st>>>(pm_kargs<false, true>(c, pa, &pool));
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_mes_pool: isotropic and ARD batches alike (as adkf_predict_pool); the scratch is adkf_predict_pool's candidate lists
+int mes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* ystar, int32_t S,
+             const int64_t* excl_idx, const int64_t* excl_off, float* score, int32_t k, int64_t* top_idx, float* top_val, int32_t* info,
+             void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (!ystar) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (k < 0) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (k == 0 && !score) return ADKF_E_BADARG;
+    if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
+    if (k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    const PoolScratch l = pool_scratch(scratch, b->T, k);
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    PmPool pool = pm_pool(excl_idx, excl_off, k, b->T, l.cand_idx, l.cand_val, rows, c.st);
+    pool.top_idx = top_idx; pool.top_val = top_val;
+    PmArgs pa = pm_args(c, flags, X, rows, info);
+    const MesArgs v{ystar, S, score};
+    return c.ard ? mes_launch<true>(c, pa, pool, v, rows) : mes_launch<false>(c, pa, pool, v, rows);
 }
 
 }  // namespace

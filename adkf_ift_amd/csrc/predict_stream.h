@@ -65,8 +65,8 @@
 // summed in one order - k_predict_marginal64 and k_bv_walk64), the merge of a task's lists (pm_merge_task_lists: k_pool_topk at width
 // k, k_bv_step at width 1; k_ts_merge is a compare per lane, another shape), and k_predict_marginal itself.  What a tile's rows become once the K row tile and the two reductions
 // are in place is the template parameter EPI: PmRowEpilogue (the default) writes prediction's outputs and merges the scores;
-// BvEpilogue downdates the variance with the picks made so far before it scores.  The instances of the default are the kernels
-// as they were, arithmetic and order.
+// BvEpilogue downdates the variance with the picks made so far before it scores; MesEpilogue (mes_stream.h) scores every row against
+// max-value samples with all four waves.  The instances of the default are the kernels as they were, arithmetic and order.
 #pragma once
 #include <type_traits>
 

@@ -592,6 +592,72 @@ def thompson_pool_ard(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: 
     return _thompson_pool("thompson_pool_ard", b, phi, X, omega, phase, n_samples, generator, w, eps, maximize, exclude, want_paths)
 
 
+def mes_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, ystar: torch.Tensor, maximize: bool = False, topk: int = 0,
+             exclude=None, want_score: Optional[bool] = None):
+    """Max-value entropy search (Wang & Jegelka 2017) over the shared pool ``X [rows, d]`` in one ``adkf_mes_pool`` call, for
+    isotropic and ARD batches alike.  ``ystar [T, S]`` (S at most 64, on the batch's device) holds samples of each task's optimum
+    value - of max f with ``maximize``, of min f without; ``max_value_samples`` draws them.  The score of a row is
+    ``mean_s g(gamma_s)`` with ``gamma_s = +-(ystar_s - mean) / sigma`` and ``g(gamma) = gamma phi(gamma) / (2 Phi(gamma)) -
+    log Phi(gamma)``: positive, larger where observing the row says more about the optimum value; no ``best_f`` is involved.
+    Returns ``dict(score, top_idx, top_val, info)``: ``score [T, rows]`` (``want_score``, which defaults to ``topk == 0``; else
+    None), ``top_idx [T, topk]`` (int64) / ``top_val [T, topk]`` as ``predict_pool`` returns them (None with ``topk == 0``) and
+    ``info [T]``.  A NaN or infinite ``ystar[t, s]`` makes the scores of task t NaN, which are never selected.  ``exclude``: rows a
+    task may not select (``pack_exclude``).  With ``want_score=False`` nothing of size T x rows is allocated or written."""
+    lib = _lib.load()
+    if b.nq != 0:
+        raise ValueError("mes_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    topk = int(topk)
+    if topk < 0 or topk > _lib.POOL_TOPK_MAX:
+        raise ValueError(f"topk must be in [0, {_lib.POOL_TOPK_MAX}], got {topk}")
+    if want_score is None:
+        want_score = topk == 0
+    if not (want_score or topk > 0):
+        raise ValueError("no output asked for")
+    if not torch.is_tensor(ystar) or ystar.dim() != 2 or ystar.shape[0] != b.T:
+        raise ValueError(f"ystar must be a tensor [T, S] = [{b.T}, S], got {tuple(ystar.shape) if torch.is_tensor(ystar) else ystar!r}")
+    S = ystar.shape[1]
+    if S < 1 or S > _lib.TS_SAMPLES_MAX:
+        raise ValueError(f"the number of max-value samples must be in [1, {_lib.TS_SAMPLES_MAX}], got {S}")
+    ystar = _f32(ystar, "ystar")
+    phi = b.check_phi(phi)
+    X = _f32(X, "X")
+    if X.dim() != 2 or X.shape[1] != b.d:
+        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    rows = X.shape[0]
+    for arg, t in (("X", X), ("ystar", ystar)):
+        if t.device != b.device:
+            raise ValueError(f"{arg} lives on {t.device}, the batch on {b.device}")
+    excl_idx = excl_off = None
+    if exclude is not None and topk > 0:
+        excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
+    score = _new(b, b.T, rows) if want_score else None
+    top_idx = _new(b, b.T, topk, dtype=torch.int64) if topk > 0 else None
+    top_val = _new(b, b.T, topk) if topk > 0 else None
+    info = _new(b, b.T, dtype=torch.int32)
+    sb = int(lib.adkf_predict_pool_scratch_bytes(b.T, topk))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device) if sb else None
+    ws, nb = b.workspace()
+    cb = b.c_struct()
+    _lib.check(lib.adkf_mes_pool(C.byref(cb), ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, ptr(X), rows, ptr(ystar), S, ptr(excl_idx),
+                                 ptr(excl_off), ptr(score), topk, ptr(top_idx), ptr(top_val), ptr(info), ptr(ws), nb, ptr(scratch), sb,
+                                 stream(b.device)), "adkf_mes_pool")
+    return dict(score=score, top_idx=top_idx, top_val=top_val, info=info)
+
+
+def max_value_samples(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: torch.Tensor, phase: torch.Tensor, n_samples: int,
+                      generator: Optional[torch.Generator] = None, w: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
+                      maximize: bool = False):
+    """``n_samples`` samples of each task's optimum value over the pool ``X [rows, d]``, as ``mes_pool`` takes them: the optima of
+    pathwise posterior draws, from ONE ``thompson_pool`` (ARD batches: ``thompson_pool_ard``) call without exclusions and without
+    paths.  Returns ``dict(ystar [T, S], info [T], w, eps)``: ``ystar`` holds max f with ``maximize`` and min f without (the call's
+    ``sel_val`` is +f and -f; -inf, hence +-inf here, for a skipped task or an empty pool), ``w`` / ``eps`` the standard normal
+    draws, given or drawn from ``generator`` as ``thompson_pool`` draws them."""
+    draw = thompson_pool_ard if b.ard else thompson_pool
+    out = draw(b, phi, X, omega=omega, phase=phase, n_samples=n_samples, generator=generator, w=w, eps=eps, maximize=maximize)
+    ystar = out["sel_val"] if maximize else -out["sel_val"]
+    return dict(ystar=ystar, info=out["info"], w=out["w"], eps=out["eps"])
+
+
 def double_path_tasks(b: GPBatch) -> torch.Tensor:
     """[T] int32: 1 where the last ``ift_hypergrad`` / ``outer_nll_value_grad`` on this batch sent the task through the float64
     path (ill-conditioned tasks, csrc/refine64.h).  Diagnostic."""

@@ -357,6 +357,40 @@ int adkf_believer_pool(const adkf_batch_t* b, const float* phi, int32_t flags, c
  * check runs before anything is launched. */
 int adkf_believer_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Max-value entropy search over a shared pool (csrc/mes_stream.h; Wang and Jegelka 2017): every task of the batch scores the SAME
+ * rows X [rows, d] by the information each row carries about the VALUE of the task's optimum, and the call can return each task's
+ * best k rows itself.  The information-theoretic member of the pool family: no incumbent best_f is involved.
+ *   The quantity.  m(x) and v(x) adkf_predict_pool's mean and latent variance, sigma = sqrt(max(v, 1e-12)) as everywhere, and S
+ *          samples ystar[t, 0..S) of the optimum value of task t:
+ *              gamma_s  = (ystar[t, s] - m) / sigma   with ADKF_PM_MAXIMIZE (ystar: samples of max f),
+ *              gamma_s  = (m - ystar[t, s]) / sigma   without                (ystar: samples of min f),
+ *              g(gamma) = gamma phi(gamma) / (2 Phi(gamma)) - log Phi(gamma),
+ *              score(x) = (1 / S) sum_s g(gamma_s).
+ *          g is positive and strictly decreasing.  It is formed without its cancellation at gamma <= -1 (both terms grow like
+ *          gamma^2 / 2) and with log1p where Phi -> 1, so a float32 score is good to a few eps32 (1 + gamma^2); the S terms of a row
+ *          are added in a fixed order.
+ *   ystar  [T, S], an input: given it the call is a deterministic function.  The maxima over the pool of pathwise posterior draws are
+ *          such samples - adkf_thompson_pool's sel_val without exclusions is max f with ADKF_PM_MAXIMIZE and -min f without (negate
+ *          it).  A NaN or infinite ystar[t, s] makes every score of task t NaN: not skipped, not clamped, never selected.
+ *   b      support-only as for adkf_predict_pool, of either kind: with ADKF_BATCH_ARD in b->flags phi is [T, 2 + d] and ws has
+ *          adkf_workspace_bytes_ard(T, ns_max, 0, d) bytes, without it [T, 3] and adkf_workspace_bytes(T, ns_max, 0, d).  REUSE_DIST /
+ *          REUSE_INNER mean what they mean there.  The workspace size depends on neither rows, S nor k.
+ *   flags  ADKF_PM_MAXIMIZE only.
+ *   score  nullable, [T, rows] (task t, row r at t * rows + r).  With score == NULL nothing of size T x rows is written.
+ *   k, top_idx, top_val   k == 0: no selection.  Otherwise ([T, k] each) the k eligible rows of largest score in descending score,
+ *          equal scores in ascending row index (the total order of adkf_predict_pool), and their scores; a row is eligible unless it
+ *          is listed in excl_idx[excl_off[t] .. excl_off[t + 1]) (nullable; as adkf_predict_pool) or its score is NaN.  With fewer
+ *          than k eligible rows, and with rows == 0, the tail is top_idx = -1, top_val = -inf.
+ *   Tasks with n_s == 0 or info != 0: their [rows] slice of score is 0 (the fill value), their selection -1 / -inf.
+ *   scratch   adkf_predict_pool_scratch_bytes(T, k) bytes, 8-byte aligned: the candidate lists of adkf_predict_pool (0 for k == 0).
+ * Asynchronous on `stream`, no allocation, no synchronisation, no atomics: reproducible to the bit, and a task's scores and selection
+ * depend on that task's data, its ystar row, the pool and its exclusion list only - not on the grid or the other tasks of the batch.
+ * Rejected before anything is launched, ADKF_E_BADARG unless noted: a batch with a query set; any flag bit other than
+ * ADKF_PM_MAXIMIZE; ystar == NULL; rows < 0; rows > 0 without X; excl_idx without excl_off; k < 0; k > 0 without top_idx or top_val;
+ * k == 0 without score; S < 1 or S > ADKF_TS_SAMPLES_MAX (ADKF_E_SIZE); k > ADKF_POOL_TOPK_MAX (ADKF_E_SIZE); a scratch or a
+ * workspace that is too small (ADKF_E_WORKSPACE); a scratch that is not 8-byte aligned. */
+int adkf_mes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* ystar, int32_t S, const int64_t* excl_idx, const int64_t* excl_off, float* score, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

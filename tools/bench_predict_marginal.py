@@ -36,7 +36,12 @@ for the ARD believer's ratio to the isotropic one is predict_pool's ARD / isotro
 and one multiply per staged query element, and the believer adds nothing ARD-specific on top.  The line holds the four times, both
 ratios, each series' spread (max - min) / median, the float64-flagged tasks of each batch, the bit-equality of step 0 with ARD
 predict_pool and of a repeated call, and the distinct picks per task.
-Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--out FILE]"""
+--mes: max-value entropy search (adkf_mes_pool, score = NULL, k = 8) at T=16 ns=128 d=256, one pool of 100 000 rows, Matern,
+REUSE_INNER, for S = 1, 16 and 64 max-value samples, timed alternately in this process (median of --reps single calls each) with
+adkf_predict_pool(k = 8, log EI, nothing per row) on the same fitted batch and pool: the same walk with one evaluation of the
+bracket per row where MES makes S.  The line holds the four times, the ratio to the log-EI call per S, each series' spread
+(max - min) / median and the bit-equality of a repeated call.  No target: the line is what says whether the S evaluations show.
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--mes] [--out FILE]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -370,6 +375,53 @@ def shape_believer(T, ns, d, rows, q, reps, dev, out_path=None):
     return rec
 
 
+def shape_mes(T, ns, d, rows, k, reps, dev, out_path=None):
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    b = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern")
+    phi0, _ = gp_ops.init_params_batch(b, True, True)
+    b.flags = gp_ops.REUSE_DIST
+    phi, _, _, _, info = gp_ops.fit(b, phi0, 200)
+    gp_ops.check_info(info)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    X = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):
+        X[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    best = ys.median(1).values.contiguous()
+    f_lei = lambda: gp_ops.predict_pool(b, phi, X, latent=True, best_f=best, want_mean=False, want_var=False, want_ei=False, topk=k, log_ei=True)
+    Ss = (1, 16, 64)
+    # samples of min f: below the smallest label, spread over one prior standard deviation
+    ystar = {S: (ys.min(1).values[:, None] - torch.rand(T, S, device=dev, generator=g)).contiguous() for S in Ss}
+    f_mes = {S: (lambda S=S: gp_ops.mes_pool(b, phi, X, ystar=ystar[S], topk=k)) for S in Ss}
+    o1, o2 = f_mes[16](), f_mes[16]()
+    f_lei()
+    torch.cuda.synchronize()
+    gp_ops.check_info(o1["info"])
+    ts = {"log_ei": [], **{f"mes_S{S}": [] for S in Ss}}
+    for _ in range(reps):
+        ts["log_ei"].append(once(f_lei))
+        for S in Ss:
+            ts[f"mes_S{S}"].append(once(f_mes[S]))
+    med = {n: float(np.median(x)) for n, x in ts.items()}
+    lib = _lib.load()
+    rec = {"shape": f"mes T={T} ns={ns} d={d} rows={rows} k={k} matern REUSE_INNER score=NULL", "refined_tasks": int(_refined(b).sum()),
+           "float64_tasks": int((_scal(b)[:, 45] > 30.0).sum()), "workspace_bytes": int(lib.adkf_workspace_bytes(T, ns, 0, d)),
+           "scratch_bytes": int(lib.adkf_predict_pool_scratch_bytes(T, k)),
+           "predict_pool_log_ei_s": med["log_ei"], **{f"mes_S{S}_s": med[f"mes_S{S}"] for S in Ss},
+           **{f"mes_S{S}_over_log_ei": med[f"mes_S{S}"] / med["log_ei"] for S in Ss},
+           "spread_max_minus_min_over_median": {n: (max(x) - min(x)) / float(np.median(x)) for n, x in ts.items()},
+           "repeat_is_bit_equal": bool(torch.equal(o1["top_idx"], o2["top_idx"]) and torch.equal(o1["top_val"], o2["top_val"])),
+           "all_selected": bool((o1["top_idx"] >= 0).all() and torch.isfinite(o1["top_val"]).all()), "all_s": ts}
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    return rec
+
+
 def shape_believer_ard(T, ns, d, rows, q, reps, dev, out_path=None):
     g = torch.Generator(device=dev).manual_seed(0)
     W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
@@ -491,9 +543,13 @@ def main():
     ap.add_argument("--skip-bo", action="store_true")
     ap.add_argument("--thompson", action="store_true", help="adkf_thompson_pool against variant (ii) of --pool, timed alternately")
     ap.add_argument("--believer", action="store_true", help="adkf_believer_pool against q calls of adkf_predict_pool(k = 1), timed alternately")
-    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard): also write the JSON line to this file")
+    ap.add_argument("--mes", action="store_true", help="adkf_mes_pool at S = 1, 16, 64 against adkf_predict_pool(k, log EI), timed alternately")
+    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard), --mes: also write the JSON line to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.mes:
+        shape_mes(16, 128, 256, 100000, 8, a.reps, dev, a.out)
+        return
     if a.believer and a.ard:
         shape_believer_ard(16, 128, 256, 100000, 8, a.reps, dev, a.out)
         return
