@@ -337,7 +337,8 @@ def run_gp_ts_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
 def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
                           kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
                           rngs: List[np.random.Generator], n_features: int = 1024, oversample: int = 4,
-                          feature_seed: int = 0, ard: bool = False, n_max_samples: int = 16) -> List[List[int]]:
+                          feature_seed: int = 0, ard: bool = False, n_max_samples: int = 16,
+                          max_value: str = "thompson") -> List[List[int]]:
     """``len(rngs)`` replicates of a max-value entropy search BO loop (Wang & Jegelka 2017) over the same pool at once
     (minimisation, as ``run_gp_ei_bo``); returns their records: the best initial index, then the picks in descending score.  Per
     iteration the replicates' queried sets are fitted by ONE ``gp_ops.fit`` (as ``run_gp_ei_bo_batched``), ONE
@@ -349,8 +350,14 @@ def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
     ``run_gp_ei_bo_batched``.  No ``best_f`` enters the score and nothing can underflow.  The prior weights and noise draws of
     replicate r come from a torch generator seeded from ``rngs[r]``, the noise draws at the replicate's own support size: a
     replicate's record does not depend on which other replicates share the batch.  ``oversample`` is accepted for the signature of
-    ``run_gp_ts_bo_batched`` and not used.  ``ard``: as ``run_gp_ts_bo_batched``; the same two calls serve ARD batches."""
+    ``run_gp_ts_bo_batched`` and not used.  ``ard``: as ``run_gp_ts_bo_batched``; the same two calls serve ARD batches.
+    ``max_value``: ``"thompson"`` (the default) as described; ``"gumbel"`` draws the samples with ONE ``gp_ops.gumbel_pool`` call
+    instead - a Gumbel fitted to the quartiles of the maximum of the pool's independent marginals (Wang & Jegelka 2017, section 3.1) -
+    which needs no basis (none is drawn) and only ``n_max_samples`` uniforms per replicate, replicate r's from its own generator."""
     R, n = len(rngs), x_all.shape[0]
+    if max_value not in ("thompson", "gumbel"):
+        raise ValueError(f"max_value must be 'thompson' or 'gumbel', got {max_value!r}")
+    gumbel = max_value == "gumbel"
     if not 1 <= query_batch_size <= gp_ops._lib.POOL_TOPK_MAX:
         raise ValueError(f"query_batch_size must be in [1, {gp_ops._lib.POOL_TOPK_MAX}], got {query_batch_size}")
     S = int(n_max_samples)
@@ -358,8 +365,9 @@ def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
         raise ValueError(f"n_max_samples must be in [1, {gp_ops._lib.TS_SAMPLES_MAX}], got {n_max_samples}")
     y_all = (y_all - y_all.mean()) / y_all.std()
     X = x_all.detach().float().contiguous()
-    omega, phase = gp_ops.rff_basis(kernel_type, X.shape[1], n_features, generator=torch.Generator().manual_seed(int(feature_seed)),
-                                    device=X.device)
+    if not gumbel:
+        omega, phase = gp_ops.rff_basis(kernel_type, X.shape[1], n_features, generator=torch.Generator().manual_seed(int(feature_seed)),
+                                        device=X.device)
     queried = [rng.choice(np.arange(init_from, n), size=num_init_points, replace=False).tolist() for rng in rngs]
     records = [[min(q)] for q in queried]
     gens = [torch.Generator().manual_seed(int(rng.integers(0, 2 ** 62))) for rng in rngs]
@@ -373,8 +381,11 @@ def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
         ns = max(sizes)
         Zs = torch.zeros(R, ns, X.shape[1], dtype=torch.float32, device=X.device)
         ys = torch.zeros(R, ns, dtype=torch.float32, device=X.device)
-        w = torch.empty(R, S, n_features, dtype=torch.float32)
-        eps = torch.zeros(R, S, ns, dtype=torch.float32)
+        if gumbel:
+            u = torch.empty(R, S, dtype=torch.float32)
+        else:
+            w = torch.empty(R, S, n_features, dtype=torch.float32)
+            eps = torch.zeros(R, S, ns, dtype=torch.float32)
         pri, phi0, best = [], [], []
         for r, q in enumerate(queried):
             xq, yq = x_all[q], y_all[q]
@@ -385,15 +396,21 @@ def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
             pri.append(mll.priors_row(X.device))
             p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
             phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
-            w[r] = torch.randn(S, n_features, generator=gens[r])
-            eps[r, :, :sizes[r]] = torch.randn(S, sizes[r], generator=gens[r])
+            if gumbel:
+                u[r] = torch.rand(S, generator=gens[r])
+            else:
+                w[r] = torch.randn(S, n_features, generator=gens[r])
+                eps[r, :, :sizes[r]] = torch.randn(S, sizes[r], generator=gens[r])
         n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
         b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
         phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
         gp_ops.check_info(info, "run_gp_mes_bo_batched fit")
         b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
-        mv = gp_ops.max_value_samples(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w.to(X.device), eps=eps.to(X.device),
-                                      maximize=False)
+        if gumbel:
+            mv = gp_ops.gumbel_pool(b, phi, X, u=u.to(X.device), maximize=False)
+        else:
+            mv = gp_ops.max_value_samples(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w.to(X.device), eps=eps.to(X.device),
+                                          maximize=False)
         gp_ops.check_info(mv["info"], "BO posterior")
         # the minimum of f is no worse than the best value seen
         ystar = torch.minimum(mv["ystar"], torch.tensor(best, dtype=torch.float32, device=X.device)[:, None])

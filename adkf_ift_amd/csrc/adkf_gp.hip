@@ -3,7 +3,7 @@
 // (except adkf_check_info), everything enqueued on the caller's stream.
 //
 // One translation unit.  The host code of each subsystem is a header of its own: host_common.h (helpers, the three values read from
-// the environment), host_gp.h (GP pipeline), host_ard.h, host_stream.h (streaming prediction, pool selection, Thompson sampling),
+// the environment), host_gp.h (GP pipeline), host_ard.h, host_stream.h (streaming prediction, pool selection and sampling),
 // and - entry points included, at the end of this file - host_gnn.h and host_dense.h (dense layers, optimiser).  This file has the
 // entry points of the GP, ARD and streaming calls.  The kernel headers come first, in the order the device code is emitted in.
 #include <hip/hip_runtime.h>
@@ -27,6 +27,7 @@
 #include "thompson_stream.h"
 #include "believer_stream.h"
 #include "mes_stream.h"
+#include "gumbel_stream.h"
 
 #include "host_common.h"
 #include "host_gp.h"
@@ -297,6 +298,17 @@ int adkf_mes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
                   void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
     return mes_pool(b, phi, flags, X, rows, ystar, S, excl_idx, excl_off, score, k, top_idx, top_val, info, ws, ws_bytes, scratch, scratch_bytes,
                     stream);
+}
+
+size_t adkf_gumbel_pool_scratch_bytes(int32_t T) {
+    if (T <= 0) return 0;
+    return gb_scratch(nullptr, T).bytes;
+}
+
+int adkf_gumbel_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* u, int32_t S,
+                     float* ystar, float* quant, float* gumbel, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes,
+                     void* stream) {
+    return gumbel_pool(b, phi, flags, X, rows, u, S, ystar, quant, gumbel, info, ws, ws_bytes, scratch, scratch_bytes, stream);
 }
 
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

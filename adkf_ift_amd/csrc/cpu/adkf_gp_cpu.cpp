@@ -767,6 +767,104 @@ int adkf_mes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
     return 0;
 }
 
+size_t adkf_gumbel_pool_scratch_bytes(int32_t) { return 0; }
+
+// -log Phi(gamma) of adkf_gumbel_pool in float64, clamped at 32 (csrc/gumbel_stream.h): log1p where Phi -> 1; erfc itself below 0 (it
+// does not underflow before the clamp is reached, at gamma ~ -7.6).  NaN gives NaN.
+static double neg_log_cdf(double g) {
+    if (g != g) return g;
+    if (g > 0.0) return -std::log1p(-0.5 * std::erfc(g / std::sqrt(2.0)));
+    if (g < -9.0) return 32.0;
+    return std::min(32.0, -std::log(0.5 * std::erfc(-g / std::sqrt(2.0))));
+}
+
+// Gumbel max-value sampling over a shared pool (include/adkf_gp.h), the scheme of csrc/gumbel_stream.h on host pointers: the float64
+// posterior of adkf_predict_pool rounded to float32, the float32 probes, the clamp, the 2^-31 fixed point summed in integers, the
+// interpolation and the fit in float64, the draw in float32.
+int adkf_gumbel_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* u, int32_t S,
+                     float* ystar, float* quant, float* gumbel, int32_t* info, void*, size_t, void*, size_t, void*) {
+    if (int rc = check(b, false, true)) return rc;
+    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (!u || !ystar) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
+    if (rows > ((int64_t)1 << 27)) return ADKF_E_SIZE;
+    constexpr int G = ADKF_GUMBEL_PROBES;
+    const float ninf = -std::numeric_limits<float>::infinity();
+    const bool maximize = (flags & ADKF_PM_MAXIMIZE) != 0;
+    double klo = 0.0, khi = 40.0;   // kappa = max(1, Phi^-1(1 - 0.25 / rows)) by bisection
+    for (int it = 0; it < 100; ++it) {
+        const double mid = 0.5 * (klo + khi);
+        if (0.5 * std::erfc(mid / std::sqrt(2.0)) > 0.25 / (double)std::max<int64_t>(rows, 1)) klo = mid; else khi = mid;
+    }
+    const float kappa = (float)std::max(1.0, khi);
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        std::vector<float> mu((size_t)rows), sg((size_t)rows);
+        const float* y = b->y_s + (size_t)t * b->ns_max;
+        const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
+            float m1, v1;
+            pm_row(in, b->kernel, D, y, ADKF_PM_LATENT, nullptr, t, 0, &m1, &v1, nullptr);
+            mu[r] = maximize ? m1 : -m1;
+            sg[r] = std::sqrt(std::max(v1, 1e-12f));
+        });
+        float fa = ninf, fb = ninf, fq[3] = {ninf, ninf, ninf};
+        if (done && rows > 0) {
+            float lo = ninf, hi = ninf;
+            for (int64_t r = 0; r < rows; ++r) {
+                const float l = mu[r] - sg[r], h = std::fma(kappa, sg[r], mu[r]);
+                if (l == l && h == h) { lo = std::max(lo, l); hi = std::max(hi, h); }
+            }
+            float z[G];
+            double nl[G];
+            auto pass = [&] {
+                for (int g = 0; g < G; ++g) {
+                    z[g] = g == G - 1 ? hi : std::fma(hi - lo, (float)g / (float)(G - 1), lo);
+                    uint64_t sum = 0;
+                    for (int64_t r = 0; r < rows; ++r) {
+                        const double term = neg_log_cdf((double)((z[g] - mu[r]) / sg[r]));
+                        sum += (uint64_t)std::llrint((term == term ? term : 32.0) * 2147483648.0);
+                    }
+                    nl[g] = -(double)sum / 2147483648.0;
+                }
+            };
+            pass();
+            int g_lo = 0, g_hi = G - 1;
+            for (int g = 0; g < G; ++g) if (nl[g] <= std::log(0.25)) g_lo = g;
+            for (int g = G - 1; g >= 0; --g) if (nl[g] >= std::log(0.75)) g_hi = g;
+            if (g_hi < g_lo) g_hi = g_lo;
+            lo = z[g_lo]; hi = z[g_hi];
+            pass();
+            const double lq[3] = {std::log(0.25), std::log(0.5), std::log(0.75)};
+            double q[3];
+            for (int i = 0; i < 3; ++i) {
+                int g1 = -1;
+                for (int g = 0; g < G; ++g) if (nl[g] >= lq[i]) { g1 = g; break; }
+                if (g1 < 0) q[i] = z[G - 1];
+                else if (g1 == 0 || nl[g1] == nl[g1 - 1] || z[g1] == z[g1 - 1]) q[i] = z[g1 > 0 ? g1 - 1 : 0];
+                else q[i] = (double)z[g1 - 1] + ((double)z[g1] - (double)z[g1 - 1]) * ((lq[i] - nl[g1 - 1]) / (nl[g1] - nl[g1 - 1]));
+            }
+            double bb = (q[2] - q[0]) / (std::log(std::log(4.0)) - std::log(std::log(4.0 / 3.0)));
+            if (!(bb > 0.0)) bb = 0.0;
+            fa = (float)(q[1] + bb * std::log(std::log(2.0))); fb = (float)bb;
+            for (int i = 0; i < 3; ++i) fq[i] = (float)q[i];
+        }
+        if (quant) for (int i = 0; i < 3; ++i) quant[(size_t)t * 3 + i] = fq[i];
+        if (gumbel) { gumbel[(size_t)t * 2] = fa; gumbel[(size_t)t * 2 + 1] = fb; }
+        for (int s = 0; s < S; ++s) {
+            float h = ninf;
+            if (done && rows > 0) {
+                const float uc = std::min(std::max(u[(size_t)t * S + s], 5.9604644775390625e-8f), 1.f - 5.9604644775390625e-8f);
+                h = fa - fb * std::log(-std::log(uc));
+            }
+            ystar[(size_t)t * S + s] = maximize ? h : -h;
+        }
+    }
+    return 0;
+}
+
 size_t adkf_thompson_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { return 0; }
 
 // Thompson sampling over a shared pool (include/adkf_gp.h): the pathwise posterior draws in float64, rounded to float32 at the

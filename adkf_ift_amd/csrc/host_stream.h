@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard and adkf_mes_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool and adkf_gumbel_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
 #pragma once
 #include "host_ard.h"
 
@@ -479,6 +479,80 @@ int mes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float
     PmArgs pa = pm_args(c, flags, X, rows, info);
     const MesArgs v{ystar, S, score};
     return c.ard ? mes_launch<true>(c, pa, pool, v, rows) : mes_launch<false>(c, pa, pool, v, rows);
+}
+
+// adkf_gumbel_pool: the scratch is the fixed-point sums [T, 64] (uint64), the probes [T, 64] (float32) and the images of the two
+// maxima [T, 2] (uint32) - independent of rows, S and the device
+struct GbScratch { unsigned long long* sums; float* probes; unsigned int* mx; size_t bytes; };
+inline GbScratch gb_scratch(void* base, int T) {
+    Arena ar{static_cast<char*>(base), 0};
+    GbScratch l{};
+    l.sums = ar.as<unsigned long long>((size_t)T * GB_PROBES);
+    l.probes = ar.floats((size_t)T * GB_PROBES);
+    l.mx = ar.as<unsigned int>((size_t)T * 2);
+    l.bytes = ar.off;
+    return l;
+}
+
+// kappa = max(1, Phi^-1(1 - 0.25 / rows)): the upper end of the bracket in deviations (gumbel_stream.h), by bisection on erfc
+inline float gb_kappa(int64_t rows) {
+    const double p = 0.25 / (double)std::max<int64_t>(rows, 1);
+    double lo = 0.0, hi = 40.0;
+    for (int it = 0; it < 100; ++it) {
+        const double mid = 0.5 * (lo + hi);
+        if (0.5 * std::erfc(mid * 0.70710678118654752) > p) lo = mid; else hi = mid;
+    }
+    return (float)std::max(1.0, hi);
+}
+
+// The launches of a prepared Gumbel call: three walks (bracket, probe pass 1, probe pass 2), each the walks of prediction with
+// GumbelEpilogue and the float64 walk, with one wave per task between them and at the end.  No host synchronisation.
+template <bool ARD>
+int gb_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, GumbelArgs v, int64_t rows) {
+    hipStream_t st = c.st;
+    const int T = c.b.T;
+    if (rows > 0) {
+        if constexpr (ARD) launch_ard_il(c);
+        const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
+        for (int walk = 0; walk < 3; ++walk) {
+            v.bracket = walk == 0 ? 1 : 0;
+            int rc;
+            if ((rc = pm_launch_walk<false, ARD, true, GumbelEpilogue>(c, pa, &pool, v, tiles))) return rc;
+            if ((rc = pm_launch_walk<true, ARD, true, GumbelEpilogue>(c, pa, &pool, v, tiles))) return rc;
+            if (c.w.w64) k_gumbel_walk64<ARD><<<dim3(pm64_grid(rows), T), PM64_NT, 0, st>>>(pm_kargs<ARD, true, GumbelEpilogue>(c, pa, &pool, v));
+            if (walk < 2) k_gumbel_window<<<T, 64, 0, st>>>(v, walk);
+        }
+    }
+    k_gumbel_fit<<<T, 64, 0, st>>>(pa, v);
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_gumbel_pool: isotropic and ARD batches alike (as adkf_mes_pool)
+int gumbel_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* u, int32_t S,
+                float* ystar, float* quant, float* gumbel, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes,
+                void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (!u || !ystar) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
+    if (rows > GB_ROWS_MAX) return ADKF_E_SIZE;
+    const GbScratch l = gb_scratch(scratch, b->T);
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    PmPool pool = pm_pool(nullptr, nullptr, 0, b->T, nullptr, nullptr, rows, c.st);
+    PmArgs pa = pm_args(c, flags, X, rows, info);
+    GumbelArgs v{};
+    v.probes = l.probes; v.sums = l.sums; v.mx = l.mx;
+    v.kappa = gb_kappa(rows);
+    v.u = u; v.S = S; v.ystar = ystar; v.quant = quant; v.gumbel = gumbel;
+    // the sums and the images of the maxima start at 0 ("no row yet")
+    hipMemsetAsync(scratch, 0, l.bytes, c.st);
+    return c.ard ? gb_launch<true>(c, pa, pool, v, rows) : gb_launch<false>(c, pa, pool, v, rows);
 }
 
 }  // namespace

@@ -66,7 +66,8 @@
 // k, k_bv_step at width 1; k_ts_merge is a compare per lane, another shape), and k_predict_marginal itself.  What a tile's rows become once the K row tile and the two reductions
 // are in place is the template parameter EPI: PmRowEpilogue (the default) writes prediction's outputs and merges the scores;
 // BvEpilogue downdates the variance with the picks made so far before it scores; MesEpilogue (mes_stream.h) scores every row against
-// max-value samples with all four waves.  The instances of the default are the kernels as they were, arithmetic and order.
+// max-value samples with all four waves; GumbelEpilogue (gumbel_stream.h) reduces the tile's rows to two maxima or 64 fixed-point sums
+// per task.  The instances of the default are the kernels as they were, arithmetic and order.
 #pragma once
 #include <type_traits>
 

@@ -658,6 +658,60 @@ def max_value_samples(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: 
     return dict(ystar=ystar, info=out["info"], w=out["w"], eps=out["eps"])
 
 
+def gumbel_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, n_samples: Optional[int] = None, u: Optional[torch.Tensor] = None,
+                generator: Optional[torch.Generator] = None, maximize: bool = False):
+    """Gumbel max-value sampling (Wang & Jegelka 2017, section 3.1; BoTorch's ``_sample_max_value_Gumbel``) over the shared pool
+    ``X [rows, d]`` in one ``adkf_gumbel_pool`` call, for isotropic and ARD batches alike: samples of each task's optimum value as
+    ``mes_pool`` takes them, from the pool's posterior marginals alone (no random-Fourier basis).  The marginals are taken as
+    independent; the quartiles of ``Pr[max < z] = prod_i Phi((z - m_i) / sigma_i)`` are found by two passes of 64 probes, a Gumbel
+    ``(a, b)`` is fitted to them and ``ystar = a - b log(-log u)`` is drawn.  Returns ``dict(ystar [T, S], quant [T, 3],
+    gumbel [T, 2], u [T, S], info [T])``: ``ystar`` holds samples of max f with ``maximize`` and of min f without; ``quant`` (the
+    quartiles) and ``gumbel`` (a, b) are in the score's sense, of +f with ``maximize`` and of -f without.  ``u`` (uniforms in (0, 1),
+    on the batch's device) is given, or ``n_samples`` (at most 64) of them per task are drawn here from ``generator`` (on its device)
+    and returned.  Skipped tasks and an empty pool give -inf in ``quant`` and ``gumbel`` and -inf / +inf in ``ystar``.  A task's
+    result is the same bits alone or in a batch, and under any permutation of the pool's rows."""
+    lib = _lib.load()
+    if b.nq != 0:
+        raise ValueError("gumbel_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    if u is None:
+        if n_samples is None:
+            raise ValueError("gumbel_pool needs n_samples or u")
+        S = int(n_samples)
+        if S < 1 or S > _lib.TS_SAMPLES_MAX:
+            raise ValueError(f"n_samples must be in [1, {_lib.TS_SAMPLES_MAX}], got {S}")
+    else:
+        if not torch.is_tensor(u) or u.dim() != 2 or u.shape[0] != b.T:
+            raise ValueError(f"u must be a tensor [T, S] = [{b.T}, S], got {tuple(u.shape) if torch.is_tensor(u) else u!r}")
+        S = u.shape[1]
+        if S < 1 or S > _lib.TS_SAMPLES_MAX:
+            raise ValueError(f"the number of samples must be in [1, {_lib.TS_SAMPLES_MAX}], got {S}")
+        if n_samples is not None and int(n_samples) != S:
+            raise ValueError(f"n_samples = {n_samples} does not match u [T, {S}]")
+    phi = b.check_phi(phi)
+    X = _f32(X, "X")
+    if X.dim() != 2 or X.shape[1] != b.d:
+        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    if u is None:
+        gdev = generator.device if generator is not None else b.device
+        u = torch.rand(b.T, S, dtype=torch.float32, generator=generator, device=gdev).to(b.device).contiguous()
+    else:
+        u = _f32(u, "u")
+    rows = X.shape[0]
+    for arg, t in (("X", X), ("u", u)):
+        if t.device != b.device:
+            raise ValueError(f"{arg} lives on {t.device}, the batch on {b.device}")
+    ystar, quant, gumbel = _new(b, b.T, S), _new(b, b.T, 3), _new(b, b.T, 2)
+    info = _new(b, b.T, dtype=torch.int32)
+    sb = int(lib.adkf_gumbel_pool_scratch_bytes(b.T))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device)
+    ws, nb = b.workspace()
+    cb = b.c_struct()
+    _lib.check(lib.adkf_gumbel_pool(C.byref(cb), ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, ptr(X), rows, ptr(u), S, ptr(ystar),
+                                    ptr(quant), ptr(gumbel), ptr(info), ptr(ws), nb, ptr(scratch), sb, stream(b.device)),
+               "adkf_gumbel_pool")
+    return dict(ystar=ystar, quant=quant, gumbel=gumbel, u=u, info=info)
+
+
 def double_path_tasks(b: GPBatch) -> torch.Tensor:
     """[T] int32: 1 where the last ``ift_hypergrad`` / ``outer_nll_value_grad`` on this batch sent the task through the float64
     path (ill-conditioned tasks, csrc/refine64.h).  Diagnostic."""

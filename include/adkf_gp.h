@@ -391,6 +391,36 @@ int adkf_believer_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flag
  * workspace that is too small (ADKF_E_WORKSPACE); a scratch that is not 8-byte aligned. */
 int adkf_mes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* ystar, int32_t S, const int64_t* excl_idx, const int64_t* excl_off, float* score, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Gumbel max-value sampling over a shared pool (csrc/gumbel_stream.h; Wang and Jegelka 2017, section 3.1; BoTorch's
+ * _sample_max_value_Gumbel): S samples of the VALUE of each task's optimum over the rows X [rows, d], as adkf_mes_pool takes them in
+ * ystar, from the pool's posterior marginals alone - no random-Fourier basis, no per-sample solve, S uniforms per task.
+ *   The quantity.  m_i and v_i adkf_predict_pool's mean and latent variance of row i, sigma_i = sqrt(max(v_i, 1e-12)), and in the
+ *          score's sense h = +f with ADKF_PM_MAXIMIZE and h = -f without (mu_i = +-m_i).  The marginals are taken as independent:
+ *              Pr[max_i h_i < z] = prod_i Phi((z - mu_i) / sigma_i).
+ *          Its quartiles are bracketed by lo = max_i (mu_i - sigma_i) and hi = max_i (mu_i + kappa sigma_i), kappa = max(1,
+ *          Phi^-1(1 - 0.25 / rows)), and located by two passes of ADKF_GUMBEL_PROBES = 64 equidistant probes of log Pr with linear
+ *          interpolation in the bracketing cell (within about 2e-4 b of the exact quartiles).  A Gumbel is fitted to them,
+ *              b = (q75 - q25) / (log log 4 - log log(4 / 3)),   a = q50 + b log log 2,
+ *          and ystar_h[t, s] = a - b log(-log u[t, s]), u clamped to [2^-24, 1 - 2^-24].  Three walks of the pool per call.
+ *   u      [T, S] uniforms in (0, 1), an input: given them the call is a deterministic function.
+ *   ystar  [T, S]: samples of max f with ADKF_PM_MAXIMIZE (ystar_h), of min f without (-ystar_h).
+ *   quant  nullable, [T, 3]: the quartiles q25, q50, q75 in the score's sense.   gumbel  nullable, [T, 2]: (a, b), the same sense.
+ *   b, ws  support-only, of either kind (ADKF_BATCH_ARD or not), as for adkf_mes_pool.   flags  ADKF_PM_MAXIMIZE only.
+ *   Tasks with n_s == 0 or info != 0, and every task when rows == 0: quant = gumbel = -inf, ystar = -inf with ADKF_PM_MAXIMIZE and
+ *          +inf without (adkf_mes_pool turns such samples into NaN scores, which are never selected).
+ *   scratch   adkf_gumbel_pool_scratch_bytes(T) bytes, 8-byte aligned; the size depends on neither rows, S nor the device.
+ * The terms -log Phi are summed as unsigned 64-bit fixed-point numbers (2^-31 per unit, each term clamped at 32) with integer adds and
+ * integer atomics only, the two maxima through an order-preserving integer image: no floating-point atomics, and a task's quant,
+ * gumbel and ystar are the same bits alone or in a batch, on any grid, and under any permutation of the pool's rows.  The sums
+ * cannot wrap for rows <= 2^27; the rounding of a sum is at most rows 2^-32.  Asynchronous on `stream`, no allocation, no
+ * synchronisation, capturable.  Rejected before anything is launched, ADKF_E_BADARG unless noted: a batch with a query set; any flag
+ * bit other than ADKF_PM_MAXIMIZE; u, ystar, info or ws == NULL; rows < 0; rows > 0 without X; S < 1 or S > ADKF_TS_SAMPLES_MAX
+ * (ADKF_E_SIZE); rows > 2^27 (ADKF_E_SIZE); a scratch or a workspace that is too small (ADKF_E_WORKSPACE); a scratch that is not
+ * 8-byte aligned. */
+#define ADKF_GUMBEL_PROBES 64
+size_t adkf_gumbel_pool_scratch_bytes(int32_t T);
+int adkf_gumbel_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* u, int32_t S, float* ystar, float* quant, float* gumbel, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

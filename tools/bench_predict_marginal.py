@@ -41,7 +41,12 @@ REUSE_INNER, for S = 1, 16 and 64 max-value samples, timed alternately in this p
 adkf_predict_pool(k = 8, log EI, nothing per row) on the same fitted batch and pool: the same walk with one evaluation of the
 bracket per row where MES makes S.  The line holds the four times, the ratio to the log-EI call per S, each series' spread
 (max - min) / median and the bit-equality of a repeated call.  No target: the line is what says whether the S evaluations show.
-Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--mes] [--out FILE]"""
+--gumbel: Gumbel max-value sampling (adkf_gumbel_pool, S = 16 uniforms per task) on --mes's batch and pool (T=16 ns=128 d=256, 100 000
+rows, Matern, REUSE_INNER), timed alternately in this process (median of --reps single calls each) with adkf_predict_pool(k = 8,
+log EI, nothing per row) and with gp_ops.max_value_samples at S = 16, m = 1024 (w and eps already on the device).  The call is three
+walks of the pool, each with an epilogue of 64 evaluations per row like MES at S = 64.  The line holds the three times, both
+ratios, each series' spread (max - min) / median, the scratch bytes and the bit-equality of a repeated call.  No target.
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--mes] [--gumbel] [--out FILE]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -422,6 +427,57 @@ def shape_mes(T, ns, d, rows, k, reps, dev, out_path=None):
     return rec
 
 
+def shape_gumbel(T, ns, d, rows, k, S, m, reps, dev, out_path=None):
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    b = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern")
+    phi0, _ = gp_ops.init_params_batch(b, True, True)
+    b.flags = gp_ops.REUSE_DIST
+    phi, _, _, _, info = gp_ops.fit(b, phi0, 200)
+    gp_ops.check_info(info)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    X = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):
+        X[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    best = ys.median(1).values.contiguous()
+    u = torch.rand(T, S, device=dev, generator=g)
+    omega, phase = gp_ops.rff_basis("matern", d, m, generator=torch.Generator().manual_seed(0), device=dev)
+    w, eps = torch.randn(T, S, m, device=dev, generator=g), torch.randn(T, S, ns, device=dev, generator=g)
+    f_lei = lambda: gp_ops.predict_pool(b, phi, X, latent=True, best_f=best, want_mean=False, want_var=False, want_ei=False, topk=k, log_ei=True)
+    f_gb = lambda: gp_ops.gumbel_pool(b, phi, X, u=u)
+    f_mv = lambda: gp_ops.max_value_samples(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w, eps=eps)
+    o1, o2 = f_gb(), f_gb()
+    f_lei(); f_mv()
+    torch.cuda.synchronize()
+    gp_ops.check_info(o1["info"])
+    ts = {"log_ei": [], "gumbel": [], "max_value_samples": []}
+    for _ in range(reps):
+        ts["log_ei"].append(once(f_lei))
+        ts["gumbel"].append(once(f_gb))
+        ts["max_value_samples"].append(once(f_mv))
+    med = {n: float(np.median(x)) for n, x in ts.items()}
+    lib = _lib.load()
+    same = lambda x, y: bool(torch.equal(x.view(torch.int32), y.view(torch.int32)))
+    rec = {"shape": f"gumbel T={T} ns={ns} d={d} rows={rows} S={S} matern REUSE_INNER; predict_pool k={k} log EI; max_value_samples m={m}",
+           "refined_tasks": int(_refined(b).sum()), "float64_tasks": int((_scal(b)[:, 45] > 30.0).sum()),
+           "workspace_bytes": int(lib.adkf_workspace_bytes(T, ns, 0, d)), "scratch_bytes": int(lib.adkf_gumbel_pool_scratch_bytes(T)),
+           "thompson_scratch_bytes": int(lib.adkf_thompson_pool_scratch_bytes(T, ns, S, m)),
+           "predict_pool_log_ei_s": med["log_ei"], "gumbel_s": med["gumbel"], "max_value_samples_s": med["max_value_samples"],
+           "gumbel_over_log_ei": med["gumbel"] / med["log_ei"], "gumbel_over_max_value_samples": med["gumbel"] / med["max_value_samples"],
+           "spread_max_minus_min_over_median": {n: (max(x) - min(x)) / float(np.median(x)) for n, x in ts.items()},
+           "repeat_is_bit_equal": all(same(o1[n], o2[n]) for n in ("ystar", "quant", "gumbel")),
+           "all_finite": bool(torch.isfinite(o1["ystar"]).all()), "gumbel_b_range": [float(o1["gumbel"][:, 1].min()), float(o1["gumbel"][:, 1].max())],
+           "all_s": ts}
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    return rec
+
+
 def shape_believer_ard(T, ns, d, rows, q, reps, dev, out_path=None):
     g = torch.Generator(device=dev).manual_seed(0)
     W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
@@ -544,11 +600,15 @@ def main():
     ap.add_argument("--thompson", action="store_true", help="adkf_thompson_pool against variant (ii) of --pool, timed alternately")
     ap.add_argument("--believer", action="store_true", help="adkf_believer_pool against q calls of adkf_predict_pool(k = 1), timed alternately")
     ap.add_argument("--mes", action="store_true", help="adkf_mes_pool at S = 1, 16, 64 against adkf_predict_pool(k, log EI), timed alternately")
-    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard), --mes: also write the JSON line to this file")
+    ap.add_argument("--gumbel", action="store_true", help="adkf_gumbel_pool against adkf_predict_pool(k, log EI) and max_value_samples(S = 16, m = 1024), timed alternately")
+    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard), --mes, --gumbel: also write the JSON line to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.mes:
         shape_mes(16, 128, 256, 100000, 8, a.reps, dev, a.out)
+        return
+    if a.gumbel:
+        shape_gumbel(16, 128, 256, 100000, 8, 16, 1024, a.reps, dev, a.out)
         return
     if a.believer and a.ard:
         shape_believer_ard(16, 128, 256, 100000, 8, a.reps, dev, a.out)
