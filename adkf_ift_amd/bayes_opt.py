@@ -338,7 +338,7 @@ def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
                           kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
                           rngs: List[np.random.Generator], n_features: int = 1024, oversample: int = 4,
                           feature_seed: int = 0, ard: bool = False, n_max_samples: int = 16,
-                          max_value: str = "thompson") -> List[List[int]]:
+                          max_value: str = "thompson", batch: str = "topk") -> List[List[int]]:
     """``len(rngs)`` replicates of a max-value entropy search BO loop (Wang & Jegelka 2017) over the same pool at once
     (minimisation, as ``run_gp_ei_bo``); returns their records: the best initial index, then the picks in descending score.  Per
     iteration the replicates' queried sets are fitted by ONE ``gp_ops.fit`` (as ``run_gp_ei_bo_batched``), ONE
@@ -353,10 +353,18 @@ def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
     ``run_gp_ts_bo_batched`` and not used.  ``ard``: as ``run_gp_ts_bo_batched``; the same two calls serve ARD batches.
     ``max_value``: ``"thompson"`` (the default) as described; ``"gumbel"`` draws the samples with ONE ``gp_ops.gumbel_pool`` call
     instead - a Gumbel fitted to the quartiles of the maximum of the pool's independent marginals (Wang & Jegelka 2017, section 3.1) -
-    which needs no basis (none is drawn) and only ``n_max_samples`` uniforms per replicate, replicate r's from its own generator."""
+    which needs no basis (none is drawn) and only ``n_max_samples`` uniforms per replicate, replicate r's from its own generator.
+    ``batch``: ``"topk"`` (the default) takes the ``query_batch_size`` rows of largest MES score as described (they tend to be
+    neighbours of the winner and carry almost the same information); ``"gibbon"`` replaces the ``mes_pool`` call with ONE
+    ``gp_ops.gibbon_pool(q=query_batch_size)`` call on the same clamped samples - the greedy GIBBON batch (Moss et al. 2021), in
+    which a pick lowers the score of the rows correlated with it - keeps the usable prefix of its picks (index not -1, value
+    finite; later values may be negative) and fills a shortfall in the same way; the records are in pick order.  At
+    ``query_batch_size = 1`` the two are DIFFERENT loops: GIBBON's single-point score ``a`` is not the MES score ``g``."""
     R, n = len(rngs), x_all.shape[0]
     if max_value not in ("thompson", "gumbel"):
         raise ValueError(f"max_value must be 'thompson' or 'gumbel', got {max_value!r}")
+    if batch not in ("topk", "gibbon"):
+        raise ValueError(f"batch must be 'topk' or 'gibbon', got {batch!r}")
     gumbel = max_value == "gumbel"
     if not 1 <= query_batch_size <= gp_ops._lib.POOL_TOPK_MAX:
         raise ValueError(f"query_batch_size must be in [1, {gp_ops._lib.POOL_TOPK_MAX}], got {query_batch_size}")
@@ -414,10 +422,16 @@ def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
         gp_ops.check_info(mv["info"], "BO posterior")
         # the minimum of f is no worse than the best value seen
         ystar = torch.minimum(mv["ystar"], torch.tensor(best, dtype=torch.float32, device=X.device)[:, None])
-        out = gp_ops.mes_pool(b, phi, X, ystar=ystar, maximize=False, topk=query_batch_size, exclude=queried)
+        if batch == "gibbon":
+            out = gp_ops.gibbon_pool(b, phi, X, ystar=ystar, q=query_batch_size, maximize=False, exclude=queried)
+            top_idx, top_val = out["sel_idx"].cpu(), out["sel_val"].cpu()
+        else:
+            out = gp_ops.mes_pool(b, phi, X, ystar=ystar, maximize=False, topk=query_batch_size, exclude=queried)
+            top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
         gp_ops.check_info(out["info"], "BO posterior")
-        top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
         usable = torch.isfinite(top_val) & (top_idx >= 0)   # (a prefix of each row: descending scores, the -1 / -inf tail last)
+        if batch == "gibbon":   # pick order, not score order: keep the prefix
+            usable = usable.long().cumprod(1).bool()
         for r, rng in enumerate(rngs):
             nonzero = int(usable[r].sum())
             pick = top_idx[r, :nonzero].tolist()

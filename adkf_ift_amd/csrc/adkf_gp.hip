@@ -28,6 +28,7 @@
 #include "believer_stream.h"
 #include "mes_stream.h"
 #include "gumbel_stream.h"
+#include "gibbon_stream.h"
 
 #include "host_common.h"
 #include "host_gp.h"
@@ -309,6 +310,14 @@ int adkf_gumbel_pool(const adkf_batch_t* b, const float* phi, int32_t flags, con
                      float* ystar, float* quant, float* gumbel, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes,
                      void* stream) {
     return gumbel_pool(b, phi, flags, X, rows, u, S, ystar, quant, gumbel, info, ws, ws_bytes, scratch, scratch_bytes, stream);
+}
+
+int adkf_gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* ystar, int32_t S,
+                     const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
+                     float* sel_mean, float* sel_var, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes,
+                     void* stream) {
+    return gibbon_pool(b, phi, flags, X, rows, ystar, S, excl_idx, excl_off, q, trace, sel_idx, sel_val, sel_mean, sel_var, info, ws, ws_bytes,
+                       scratch, scratch_bytes, stream);
 }
 
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

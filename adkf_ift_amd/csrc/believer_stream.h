@@ -37,6 +37,9 @@
 // A pool row and its stored copy are the same float32 numbers because both come out of one function (device_utils.h), not because two
 // expressions were kept alike; only one kind of kernel reads a task's Xp, so one buffer serves both.  The scalars, D2ss and
 // A^-1 are those of the unit-lengthscale pipeline (scal[S_LS] = softplus(RAW_ONE) = 1), so the solve, G and the state are unchanged.
+//
+// The c0 panel, the substitution of one row and the float64 downdate are functions (bv_c0_panel, bv_downdate, bv64_downdate) because
+// adkf_gibbon_pool (gibbon_stream.h) downdates the same variance with the same state, k_bv_init and k_bv_step, under another score.
 #pragma once
 #include "thompson_stream.h"
 
@@ -67,6 +70,55 @@ __device__ __forceinline__ float bv_score(const PmArgs& a, const BvArgs& v, int 
     return a.log_ei ? pm_log_ei(mean, vl, v.best[t], a.maximize) : pm_ei(mean, vl, v.best[t], a.maximize);
 }
 
+// ---- with c > 0 picks made (uniform): F = K_tile W^T over the row tile, then the kernel panel against the picks; c0 = Kxp - F is left
+// in pm_mm's staging buffers ([64, BV_LDC] from tl.As), behind a barrier.  All 256 threads.
+template <bool ARD>
+__device__ __forceinline__ void bv_c0_panel(const PmArgs& a, const BvArgs& v, const PmTile& tl, f32x4 (&acc)[2][2], int c) {
+    const int t = tl.t, q = v.q;
+    float* C0 = tl.As;
+    const float* Wt = v.W + (size_t)t * q * a.ns_ld;
+    const float* Kb = tl.Kb;
+    const int ld = tl.ld, n = tl.n, ns_ld = a.ns_ld;
+    float dummy[2];
+    pm_mm<false>(acc, tl.nk, tl.As, tl.Bs,
+        [=](int i, int k, float (&x)[4]) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[e] = Kb[(size_t)i * ld + k + e];
+        },
+        [=](int i, int k, float (&x)[4]) {
+            if (i >= c) { x[0] = x[1] = x[2] = x[3] = 0.f; return; }
+            pm_ld4(Wt + (size_t)i * ns_ld, k, n, false, x);
+        }, dummy, dummy);
+    f32x4 F[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) F[i][j] = acc[i][j];
+    pm_k_panel<ARD>(a, v.Xp + (size_t)t * q * a.d, tl.mu, tl.il, tl.r0, tl.m, c, 0, tl.os, tl.il2, tl.As, tl.Bs, *tl.rowsq, acc,
+                      C0, BV_LDC, [] {});
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) C0[pm_row(i, r) * BV_LDC + pm_col(j)] -= F[i][j][r];   // (this thread's own elements)
+    __syncthreads();
+}
+// ell = G^-1 c0 of one row of the panel, in place, i ascending; returns |ell|^2, what the row's latent variance loses
+__device__ __forceinline__ float bv_downdate(const BvArgs& v, int t, int c, float* e) {
+    const int q = v.q;
+    const float* G = v.G + (size_t)t * q * q;
+    float ss = 0.f;
+    for (int i = 0; i < c; ++i) {
+        float s = e[i];
+        for (int l = 0; l < i; ++l) s = fmaf(-G[i * q + l], e[l], s);
+        s /= G[i * q + i];
+        e[i] = s;
+        ss = fmaf(s, s, ss);
+    }
+    return ss;
+}
+
 struct BvEpilogue {
     using Args = BvArgs;
     template <bool ARD, bool POOL, class ARGS, class WALK>
@@ -77,53 +129,12 @@ struct BvEpilogue {
         const int tid = threadIdx.x, t = tl.t, q = v.q;
         const int c = v.cnt[t];   // (uniform) picks made, at most the step
         float* C0 = tl.As;
-        if (c > 0) {
-            // ---- F = K_tile W^T over the row tile, then the kernel panel against the picks, c0 = Kxp - F
-            const float* Wt = v.W + (size_t)t * q * a.ns_ld;
-            const float* Kb = tl.Kb;
-            const int ld = tl.ld, n = tl.n, ns_ld = a.ns_ld;
-            float dummy[2];
-            pm_mm<false>(acc, tl.nk, tl.As, tl.Bs,
-                [=](int i, int k, float (&x)[4]) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) x[e] = Kb[(size_t)i * ld + k + e];
-                },
-                [=](int i, int k, float (&x)[4]) {
-                    if (i >= c) { x[0] = x[1] = x[2] = x[3] = 0.f; return; }
-                    pm_ld4(Wt + (size_t)i * ns_ld, k, n, false, x);
-                }, dummy, dummy);
-            f32x4 F[2][2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) F[i][j] = acc[i][j];
-            pm_k_panel<ARD>(a, v.Xp + (size_t)t * q * a.d, tl.mu, tl.il, tl.r0, tl.m, c, 0, tl.os, tl.il2, tl.As, tl.Bs, *tl.rowsq, acc,
-                              C0, BV_LDC, [] {});
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) C0[pm_row(i, r) * BV_LDC + pm_col(j)] -= F[i][j][r];   // (this thread's own elements)
-            __syncthreads();
-        }
+        if (c > 0) bv_c0_panel<ARD>(a, v, tl, acc, c);
         float score = 0.f;
         if (tid < tl.m) {
             float vl = tl.os - (tl.red[0][1][tid] + tl.red[1][1][tid]);
             const float mean = tl.red[0][0][tid] + tl.red[1][0][tid];
-            if (c > 0) {   // ell = G^-1 c0 in place, i ascending
-                const float* G = v.G + (size_t)t * q * q;
-                float* e = C0 + tid * BV_LDC;
-                float ss = 0.f;
-                for (int i = 0; i < c; ++i) {
-                    float s = e[i];
-                    for (int l = 0; l < i; ++l) s = fmaf(-G[i * q + l], e[l], s);
-                    s /= G[i * q + i];
-                    e[i] = s;
-                    ss = fmaf(s, s, ss);
-                }
-                vl -= ss;
-            }
+            if (c > 0) vl -= bv_downdate(v, t, c, C0 + tid * BV_LDC);
             score = bv_score(a, v, t, mean, vl);
             if (v.trace) v.trace[((size_t)t * q + v.j) * (size_t)a.rows + (size_t)(tl.r0 + tid)] = score;
         }
@@ -132,6 +143,34 @@ struct BvEpilogue {
                           [&](long long r) { return pm_excluded(args.s, t, r) || bv_picked(v, t, c, r); });
     }
 };
+
+// the float64 downdate of one pool row zq (kernel row k) with c > 0 picks made, over the lanes of a wave: lane i forms c0(x, i), the
+// substitution runs over the lanes (row i of G against the ell broadcast so far); returns |ell|^2 to every lane
+template <bool ARD>
+__device__ __forceinline__ double bv64_downdate(const PmArgs& a, const Pm64Task& tk, const float* zq, const double* k, const double* Wt,
+                                                const double* G, const float* Xp, int c, int q, int lane) {
+    const int n = tk.n, ld = tk.ld;
+    double c0 = 0.0;   // lane i: c0(x, i)
+    if (lane < c) {
+        const float* xp = Xp + (size_t)lane * a.d;
+        double s = 0.0, f = 0.0;
+        if constexpr (ARD) {   // the float32 feature of k_ard_scale against the stored one (k_bv_step<true>: ard_scaled, both)
+            for (int e = 0; e < a.d; ++e) { const double df = (double)ard_scaled(zq[e], tk.mu[e], tk.el[e]) - (double)xp[e]; s += df * df; }
+        } else {
+            for (int e = 0; e < a.d; ++e) { const double df = (double)zq[e] - (double)xp[e]; s += df * df; }
+        }
+        for (int i = 0; i < n; ++i) f += k[i] * Wt[(size_t)lane * ld + i];
+        c0 = tk.os * kappa0(a.kind, s * tk.il2) - f;
+    }
+    double part = 0.0, ss = 0.0;   // lane i: sum_(l < i) G[i, l] ell_l so far
+    for (int i = 0; i < c; ++i) {
+        double e = lane == i ? (c0 - part) / G[(size_t)i * q + i] : 0.0;
+        e = __shfl(e, i);
+        if (lane > i && lane < c) part += G[(size_t)lane * q + i] * e;
+        ss += e * e;
+    }
+    return ss;
+}
 
 // ---- flagged tasks: k_predict_marginal64's loop (grid (chunks, T), one wave per pool row) with the downdate in float64
 template <bool ARD>
@@ -144,8 +183,8 @@ __global__ __launch_bounds__(PM64_NT) void k_bv_walk64(BvKargs<ARD> args) {
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, q = v.q;
     Pm64Task tk;
     if (!pm64_task<ARD>(args, t, tk)) return;   // (uniform)
-    const int n = tk.n, ld = tk.ld, c = v.cnt[t];
-    const double* Wt = v.W64 + (size_t)t * q * ld;
+    const int c = v.cnt[t];
+    const double* Wt = v.W64 + (size_t)t * q * tk.ld;
     const double* G = v.G64 + (size_t)t * q * q;
     const float* Xp = v.Xp + (size_t)t * q * a.d;
     double* k = kr[wv];
@@ -154,28 +193,7 @@ __global__ __launch_bounds__(PM64_NT) void k_bv_walk64(BvKargs<ARD> args) {
         double s1, s2;
         pm64_posterior_row<ARD>(a, tk, zq, k, s1, s2);
         double vl = tk.os - s2;
-        if (c > 0) {
-            double c0 = 0.0;   // lane i: c0(x, i)
-            if (lane < c) {
-                const float* xp = Xp + (size_t)lane * a.d;
-                double s = 0.0, f = 0.0;
-                if constexpr (ARD) {   // the float32 feature of k_ard_scale against the stored one (k_bv_step<true>: ard_scaled, both)
-                    for (int e = 0; e < a.d; ++e) { const double df = (double)ard_scaled(zq[e], tk.mu[e], tk.el[e]) - (double)xp[e]; s += df * df; }
-                } else {
-                    for (int e = 0; e < a.d; ++e) { const double df = (double)zq[e] - (double)xp[e]; s += df * df; }
-                }
-                for (int i = 0; i < n; ++i) f += k[i] * Wt[(size_t)lane * ld + i];
-                c0 = tk.os * kappa0(a.kind, s * tk.il2) - f;
-            }
-            double part = 0.0, ss = 0.0;   // lane i: sum_(l < i) G[i, l] ell_l so far
-            for (int i = 0; i < c; ++i) {
-                double e = lane == i ? (c0 - part) / G[(size_t)i * q + i] : 0.0;
-                e = __shfl(e, i);
-                if (lane > i && lane < c) part += G[(size_t)lane * q + i] * e;
-                ss += e * e;
-            }
-            vl -= ss;
-        }
+        if (c > 0) vl -= bv64_downdate<ARD>(a, tk, zq, k, Wt, G, Xp, c, q, lane);
         float score = 0.f;
         if (lane == 0) {
             score = bv_score(a, v, t, (float)s1, (float)vl);

@@ -969,23 +969,50 @@ int adkf_thompson_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flag
 
 size_t adkf_believer_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { return 0; }
 
+// log1p(-rho2 h(gamma)) of adkf_gibbon_pool in float64, h = tau (gamma + tau), tau = phi / Phi: as written down to gamma = -8 (gamma + tau
+// cancels from ~8 to ~0.12: a few 1e-15); below that through Mills' ratio as mes_term, with a = -gamma, w = a^-2, Phi(-a) = phi(a) M / a,
+// M = 1 + w U: tau = a / M and gamma + tau = -a w U / M, so h = -U / M^2.  +-inf and NaN give NaN.
+static double gibbon_term(double g, double rho2) {
+    if (!std::isfinite(g)) return std::numeric_limits<double>::quiet_NaN();
+    double h;
+    if (g > -8.0) {
+        const double pdf = std::exp(-0.5 * g * g) / std::sqrt(2.0 * M_PI);
+        const double tau = g > 0.0 ? pdf / (1.0 - 0.5 * std::erfc(g / std::sqrt(2.0))) : pdf / (0.5 * std::erfc(-g / std::sqrt(2.0)));
+        h = tau * (g + tau);
+    } else {
+        const double a = -g, w = (1.0 / a) / a;
+        double U = -1.0, term = -1.0;
+        for (int k = 1; k < 64; ++k) {
+            const double next = -term * (2 * k + 1) * w;
+            if (std::fabs(next) >= std::fabs(term)) break;
+            U += term = next;
+        }
+        const double M = 1.0 + w * U;
+        h = -U / (M * M);
+    }
+    return std::log1p(-rho2 * std::min(h, 1.0));
+}
+
 // Kriging-believer batch selection (include/adkf_gp.h): the mean, the latent variance and K A^-1 of every pool row once, then per
 // step one more column of ell (the forward substitution of the header, one row of G at a time) and the scores in float32, ranked
 // under "larger score first, equal scores by ascending row".  ARD (adkf_believer_pool_ard): pm_task prepares the support set and the
 // pool rows on z~ = (z - mu) / l at unit lengthscale, and the distances between pool rows are taken on x / l (mu cancels); otherwise
 // l = 1 and the rows are taken as they are, which changes no bit of the isotropic call.
+// GIBBON (adkf_gibbon_pool: ystar given, S samples per task, no best_f): the same greedy loop and downdate with the score
+// a(x) + 1/2 log((max(v_j, 1e-12) + noise) / (max(v_0, 1e-12) + noise)), a(x) from gibbon_term, computed once per row; the mean and
+// the variances enter the score in float64 (the device rounds them to float32 first).
 static int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
                          const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
-                         float* sel_mean, float* sel_var, int32_t* info) {
+                         float* sel_mean, float* sel_var, int32_t* info, const float* ystar = nullptr, int32_t S = 0, bool gibbon = false) {
     if (int rc = check(b, false, ard)) return rc;
     if (((b->flags & ADKF_BATCH_ARD) != 0) != ard || b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
     if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
-    if (flags & ~(ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    if (flags & ~(gibbon ? ADKF_PM_MAXIMIZE : (ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI))) return ADKF_E_BADARG;
     if (rows > 0 && !X) return ADKF_E_BADARG;
-    if (!best_f || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (!(gibbon ? ystar : best_f) || !sel_idx || !sel_val) return ADKF_E_BADARG;
     if (excl_idx && !excl_off) return ADKF_E_BADARG;
-    if (q < 1) return ADKF_E_BADARG;
-    if (q > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    if (q < 1 || (gibbon && S < 1)) return ADKF_E_BADARG;
+    if (q > ADKF_POOL_TOPK_MAX || (gibbon && S > ADKF_TS_SAMPLES_MAX)) return ADKF_E_SIZE;
     const int d = b->d;
     const float ninf = -std::numeric_limits<float>::infinity();
 #pragma omp parallel for schedule(dynamic)
@@ -1027,11 +1054,23 @@ static int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int3
         std::vector<char> taken(R, 0);
         std::vector<float> score(R);
         Mat G((size_t)q * q, 0.0);
-        double best = best_f[t];
+        double best = gibbon ? 0.0 : best_f[t];
+        Mat v0(gibbon ? v : Mat()), ax(gibbon ? R : 0);   // GIBBON: the step-0 variance and a(x)
+        if (gibbon)
+            for (size_t r = 0; r < R; ++r) {
+                const double vc = std::max(v0[r], 1e-12), sg = std::sqrt(vc), rho2 = vc / (vc + noise);
+                double sum = 0.0;
+                for (int k = 0; k < S; ++k) {
+                    const double ys = ystar[(size_t)t * S + k];
+                    sum += gibbon_term(((flags & ADKF_PM_MAXIMIZE) ? (ys - mu[r]) : (mu[r] - ys)) / sg, rho2);
+                }
+                ax[r] = -0.5 * sum / S;
+            }
         for (int j = 0; j < q; ++j) {
             int64_t p = -1;
             for (int64_t r = 0; r < rows; ++r) {
-                score[r] = pm_ei(mu[r], v[r], best, flags);
+                score[r] = gibbon ? (float)(ax[r] + 0.5 * std::log((std::max(v[r], 1e-12) + noise) / (std::max(v0[r], 1e-12) + noise)))
+                                  : pm_ei(mu[r], v[r], best, flags);
                 if (trace) trace[((size_t)t * q + j) * R + r] = score[r];
                 if (score[r] != score[r] || taken[r] || (xb && std::binary_search(xb, xe, r))) continue;
                 if (p < 0 || score[r] > score[p]) p = r;   // (rows ascend: a tie keeps the lower index)
@@ -1073,6 +1112,14 @@ int adkf_believer_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flag
                            const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
                            float* sel_mean, float* sel_var, int32_t* info, void*, size_t, void*, size_t, void*) {
     return believer_pool(true, b, phi, flags, X, rows, best_f, excl_idx, excl_off, q, trace, sel_idx, sel_val, sel_mean, sel_var, info);
+}
+
+// GIBBON batch max-value entropy search (include/adkf_gp.h): believer_pool's loop with the GIBBON score, for either kind of batch
+int adkf_gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* ystar, int32_t S,
+                     const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
+                     float* sel_mean, float* sel_var, int32_t* info, void*, size_t, void*, size_t, void*) {
+    const bool ard = b && (b->flags & ADKF_BATCH_ARD) != 0;
+    return believer_pool(ard, b, phi, flags, X, rows, nullptr, excl_idx, excl_off, q, trace, sel_idx, sel_val, sel_mean, sel_var, info, ystar, S, true);
 }
 
 static int outer_common(const adkf_batch_t* b, const float* phi, int flags, bool with_hessian, float* f_out, float* g_phi, float* dZ_s, float* dZ_q,

@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool and adkf_gumbel_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool and adkf_gumbel_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
 #pragma once
 #include "host_ard.h"
 
@@ -479,6 +479,65 @@ int mes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float
     PmArgs pa = pm_args(c, flags, X, rows, info);
     const MesArgs v{ystar, S, score};
     return c.ard ? mes_launch<true>(c, pa, pool, v, rows) : mes_launch<false>(c, pa, pool, v, rows);
+}
+
+// The steps of a prepared GIBBON call, as bv_launch: q chained steps, each the walks of prediction with GibbonEpilogue, the float64
+// walk, and the believer's own k_bv_step on the believer's part of the arguments.
+template <bool ARD>
+int gibbon_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, GibbonArgs& v, int64_t rows, bool have64) {
+    hipStream_t st = c.st;
+    const int T = c.b.T;
+    if constexpr (ARD) launch_ard_il(c);
+    const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
+    pool.grid[2] = (have64 && rows > 0) ? std::min(pm64_grid(rows), pool.chunks_max) : 0;
+    int rc;
+    for (int j = 0; j < v.b.q; ++j) {
+        v.b.j = j;
+        if (rows > 0) {
+            if ((rc = pm_launch_walk<false, ARD, true, GibbonEpilogue>(c, pa, &pool, v, tiles))) return rc;
+            if ((rc = pm_launch_walk<true, ARD, true, GibbonEpilogue>(c, pa, &pool, v, tiles))) return rc;
+            if (have64) k_gb_walk64<ARD><<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(pm_kargs<ARD, true, GibbonEpilogue>(c, pa, &pool, v));
+        }
+        k_bv_step<ARD><<<T, 256, 0, st>>>(pm_kargs<ARD, true, BvEpilogue>(c, pa, &pool, v.b));
+    }
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_gibbon_pool: isotropic and ARD batches alike (as adkf_mes_pool); the scratch is the believer's, with the believer's layout
+int gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* ystar, int32_t S,
+                const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* sel_mean,
+                float* sel_var, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!ystar || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (q < 1 || S < 1) return ADKF_E_BADARG;
+    if (q > ADKF_POOL_TOPK_MAX || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
+    const BvScratch l = bv_scratch(scratch, b->T, b->ns_max, b->d, q);
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    hipStream_t st = c.st;
+    const int T = b->T, ns = b->ns_max;
+    PmArgs pa = pm_args(c, flags, X, rows, info);
+    const bool have64 = c.w.w64 && ns <= R64_MAXN;
+    if (!have64) pa.r64_thresh = INFINITY;
+    PmPool pool = pm_pool(excl_idx, excl_off, 1, T, l.cand_idx, l.cand_val, rows, st);
+    GibbonArgs v{};
+    v.b.q = q;
+    v.b.W = l.W; v.b.W64 = have64 ? l.W64 : nullptr; v.b.Xp = l.Xp; v.b.G = l.G; v.b.G64 = have64 ? l.G64 : nullptr;
+    v.b.best = l.best; v.b.cnt = l.cnt; v.b.trace = trace;
+    v.b.sel_idx = sel_idx; v.b.sel_val = sel_val; v.b.sel_mean = sel_mean; v.b.sel_var = sel_var;
+    v.ystar = ystar; v.S = S;
+    // skipped tasks keep zeros in trace
+    if (trace && rows > 0) hipMemsetAsync(trace, 0, sizeof(float) * (size_t)T * q * (size_t)rows, st);
+    // there is no incumbent: the believer's slot [T] is filled from the first T floats of ystar (S >= 1) and never read by a score
+    k_bv_init<<<ceil_div(T, 256), 256, 0, st>>>(v.b, ystar, T);
+    return c.ard ? gibbon_launch<true>(c, pa, pool, v, rows, have64) : gibbon_launch<false>(c, pa, pool, v, rows, have64);
 }
 
 // adkf_gumbel_pool: the scratch is the fixed-point sums [T, 64] (uint64), the probes [T, 64] (float32) and the images of the two

@@ -67,7 +67,7 @@
 // are in place is the template parameter EPI: PmRowEpilogue (the default) writes prediction's outputs and merges the scores;
 // BvEpilogue downdates the variance with the picks made so far before it scores; MesEpilogue (mes_stream.h) scores every row against
 // max-value samples with all four waves; GumbelEpilogue (gumbel_stream.h) reduces the tile's rows to two maxima or 64 fixed-point sums
-// per task.  The instances of the default are the kernels as they were, arithmetic and order.
+// per task; GibbonEpilogue (gibbon_stream.h) runs the believer's downdate and then MES's four-wave sum of the GIBBON terms.  The instances of the default are the kernels as they were, arithmetic and order.
 #pragma once
 #include <type_traits>
 

@@ -644,6 +644,58 @@ def mes_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, ystar: torch.Ten
     return dict(score=score, top_idx=top_idx, top_val=top_val, info=info)
 
 
+def gibbon_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, ystar: torch.Tensor, q: int, maximize: bool = False, exclude=None,
+                want_trace: bool = False):
+    """A GIBBON batch (Moss et al. 2021; BoTorch's ``qLowerBoundMaxValueEntropy``) per task from the shared pool ``X [rows, d]`` in
+    one ``adkf_gibbon_pool`` call, for isotropic and ARD batches alike: ``q`` (at most 64) sequential-greedy picks of the lower bound
+    on the information a batch of noisy observations carries about the task's optimum value.  ``ystar [T, S]`` (S at most 64, on the
+    batch's device) holds samples of that value, as ``mes_pool`` takes them.  The score of a row at step j is
+    ``a(x) + log((v_j + noise) / (v_0 + noise)) / 2``: ``a = -mean_s log1p(-rho2 h(gamma_s)) / 2`` the single-point score
+    (``h = tau (gamma + tau)``, ``tau = phi / Phi``, ``rho2 = v_0 / (v_0 + noise)``) and ``v_j`` the latent variance of the row given
+    the picks made so far, so a pick lowers the score of its neighbours - which the ``topk`` rows of ``mes_pool`` are.  No
+    ``best_f`` is involved.  Returns ``dict(sel_idx, sel_val, sel_mean, sel_var, trace, info)`` as ``believer_pool`` does:
+    ``sel_idx [T, q]`` (int64) the picks in pick order and ``sel_val`` their scores at the step they were picked (later ones may be
+    negative: a pick counts when its index is not -1 and its value is finite), -1 / -inf from the step at which no eligible row was
+    left; ``sel_mean`` the posterior means of the picks, ``sel_var`` the latent variance each pick had when it was picked;
+    ``trace [T, q, rows]`` (``want_trace``, else None) the score of every row at every step; ``info [T]``.  A NaN or infinite
+    ``ystar[t, s]`` makes the scores of task t NaN: no pick.  ``exclude``: rows a task may not select (``pack_exclude``)."""
+    lib = _lib.load()
+    if b.nq != 0:
+        raise ValueError("gibbon_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    q = int(q)
+    if q < 1 or q > _lib.POOL_TOPK_MAX:
+        raise ValueError(f"q must be in [1, {_lib.POOL_TOPK_MAX}], got {q}")
+    if not torch.is_tensor(ystar) or ystar.dim() != 2 or ystar.shape[0] != b.T:
+        raise ValueError(f"ystar must be a tensor [T, S] = [{b.T}, S], got {tuple(ystar.shape) if torch.is_tensor(ystar) else ystar!r}")
+    S = ystar.shape[1]
+    if S < 1 or S > _lib.TS_SAMPLES_MAX:
+        raise ValueError(f"the number of max-value samples S must be in [1, {_lib.TS_SAMPLES_MAX}], got {S}")
+    ystar = _f32(ystar, "ystar")
+    phi = b.check_phi(phi)
+    X = _f32(X, "X")
+    if X.dim() != 2 or X.shape[1] != b.d:
+        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    rows = X.shape[0]
+    for arg, t in (("X", X), ("ystar", ystar)):
+        if t.device != b.device:
+            raise ValueError(f"{arg} lives on {t.device}, the batch on {b.device}")
+    excl_idx = excl_off = None
+    if exclude is not None:
+        excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
+    sel_idx = _new(b, b.T, q, dtype=torch.int64)
+    sel_val, sel_mean, sel_var = _new(b, b.T, q), _new(b, b.T, q), _new(b, b.T, q)
+    trace = _new(b, b.T, q, rows) if want_trace else None
+    info = _new(b, b.T, dtype=torch.int32)
+    sb = int(lib.adkf_believer_pool_scratch_bytes(b.T, b.ns, b.d, q))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device)
+    ws, nb = b.workspace()
+    cb = b.c_struct()
+    _lib.check(lib.adkf_gibbon_pool(C.byref(cb), ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, ptr(X), rows, ptr(ystar), S, ptr(excl_idx),
+                                    ptr(excl_off), q, ptr(trace), ptr(sel_idx), ptr(sel_val), ptr(sel_mean), ptr(sel_var), ptr(info),
+                                    ptr(ws), nb, ptr(scratch), sb, stream(b.device)), "adkf_gibbon_pool")
+    return dict(sel_idx=sel_idx, sel_val=sel_val, sel_mean=sel_mean, sel_var=sel_var, trace=trace, info=info)
+
+
 def max_value_samples(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: torch.Tensor, phase: torch.Tensor, n_samples: int,
                       generator: Optional[torch.Generator] = None, w: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
                       maximize: bool = False):

@@ -421,6 +421,49 @@ int adkf_mes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
 size_t adkf_gumbel_pool_scratch_bytes(int32_t T);
 int adkf_gumbel_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* u, int32_t S, float* ystar, float* quant, float* gumbel, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* GIBBON batch max-value entropy search over a shared pool (csrc/gibbon_stream.h; Moss, Leslie, Gonzalez and Rayson 2021; BoTorch's
+ * qLowerBoundMaxValueEntropy): q sequential-greedy picks per task from the SAME pool X [rows, d] in one call, of the lower bound on
+ * the information a BATCH of noisy observations carries about the VALUE of the task's optimum.  The batch form of adkf_mes_pool: its k
+ * best rows are neighbours of the winner and carry almost the same information; these q rows are a batch.
+ *   The quantity.  m(x) and v_0(x) adkf_predict_pool's mean and latent variance, noise the task's, sigma = sqrt(max(v_0, 1e-12)) as
+ *          everywhere, S samples ystar[t, 0..S) of the optimum value of task t and gamma_s as adkf_mes_pool forms it
+ *          ((ystar[t, s] - m) / sigma with ADKF_PM_MAXIMIZE, (m - ystar[t, s]) / sigma without):
+ *              tau(g)   = phi(g) / Phi(g),      h(g) = tau(g) (g + tau(g))                 0 < h < 1,
+ *              rho2(x)  = max(v_0, 1e-12) / (max(v_0, 1e-12) + noise),
+ *              a(x)     = -(1 / 2S) sum_s log1p(-rho2 h(gamma_s))                          the single-point GIBBON score, >= 0.
+ *          The batch criterion is alpha(B) = 1/2 log |R_B| + sum_(i in B) a(x_i), R_B the predictive correlation matrix of the noisy
+ *          observations at B, and the greedy increment of adding x to the picks p_0 .. p_(j-1) is exactly
+ *              score_j(x) = a(x) + 1/2 log((max(v_j(x), 1e-12) + noise) / (max(v_0(x), 1e-12) + noise)),
+ *          v_j(x) = v_0(x) - sum_(i<j) ell_i(x)^2 the downdated latent variance of adkf_believer_pool (w_i, c0, G and ell as there;
+ *          G G^T carries the noise on its diagonal).  The mean never moves, ystar never changes between steps and there is no
+ *          incumbent.  score_0 = a; later scores may be negative and are valid scores; score_j(x) <= score_0(x) for every row.
+ *          h is formed without the cancellation of g + tau at gamma <= -1 (h = tau^2 b(a), a = -gamma, b the bracket of log EI, its
+ *          series beyond gamma = -12) and with the complement of the tail where Phi -> 1; 1 - rho2 h >= noise / (v_0 + noise) > 0,
+ *          always through log1p.  The S terms of a row are added in a fixed order.
+ *          p_j is the eligible row of largest score_j, equal scores going to the lowest row index (the total order of
+ *          adkf_predict_pool).  A row is eligible unless it is listed in excl_idx[excl_off[t] .. excl_off[t + 1]) (nullable), it is one
+ *          of p_0 .. p_(j-1), or its score is NaN.  With no eligible row at step j, that step and all later ones report -1 / -inf (0
+ *          in sel_mean / sel_var) and the state stops changing.  A pick counts when its index is not -1 and its value is finite.
+ *   ystar  [T, S], an input, as for adkf_mes_pool.  A NaN or infinite ystar[t, s] makes every score of task t NaN: no pick.
+ *   b      support-only, of either kind: with ADKF_BATCH_ARD in b->flags phi is [T, 2 + d], ws has adkf_workspace_bytes_ard(T, ns_max,
+ *          0, d) bytes and every kernel value is taken on the scaled features (the picks' rows are stored scaled, as
+ *          adkf_believer_pool_ard stores them); without it [T, 3] and adkf_workspace_bytes(T, ns_max, 0, d).
+ *   flags  ADKF_PM_MAXIMIZE only.
+ *   q, S   1 <= q <= ADKF_POOL_TOPK_MAX, 1 <= S <= ADKF_TS_SAMPLES_MAX.
+ *   sel_idx, sel_val   [T, q], required: the pick of each step and its score.
+ *   sel_mean, sel_var  [T, q], each nullable: m(x_(p_j)) and v_j(x_(p_j)).
+ *   trace  nullable, [T, q, rows] with element (t, j, r) at (t q + j) rows + r: score_j of every row, eligible or not.  With
+ *          trace == NULL the call writes T q tuples and nothing per row.
+ *   Tasks with n_s == 0 or info != 0: -1 / -inf in every step, zeros in sel_mean, sel_var and trace.
+ *   scratch   adkf_believer_pool_scratch_bytes(T, ns_max, d, q) bytes, 8-byte aligned: the believer's state with the believer's layout.
+ * Asynchronous on `stream`, no allocation, no synchronisation, no atomics: reproducible to the bit, and a task's result depends on
+ * that task's data, its ystar row, the pool and its exclusion list only - not on the grid or on the other tasks of the batch.
+ * Rejected before anything is launched, ADKF_E_BADARG unless noted: a batch with a query set; any flag bit other than
+ * ADKF_PM_MAXIMIZE; rows < 0; rows > 0 without X; a missing ystar, sel_idx, sel_val, info or ws; excl_idx without excl_off; q < 1;
+ * S < 1; q > ADKF_POOL_TOPK_MAX or S > ADKF_TS_SAMPLES_MAX (ADKF_E_SIZE); a workspace or a scratch that is too small
+ * (ADKF_E_WORKSPACE); a scratch that is not 8-byte aligned. */
+int adkf_gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* ystar, int32_t S, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

@@ -41,12 +41,18 @@ REUSE_INNER, for S = 1, 16 and 64 max-value samples, timed alternately in this p
 adkf_predict_pool(k = 8, log EI, nothing per row) on the same fitted batch and pool: the same walk with one evaluation of the
 bracket per row where MES makes S.  The line holds the four times, the ratio to the log-EI call per S, each series' spread
 (max - min) / median and the bit-equality of a repeated call.  No target: the line is what says whether the S evaluations show.
+--gibbon: GIBBON batch max-value entropy search (adkf_gibbon_pool, q = 8, S = 16, trace = NULL) on --mes's batch and pool (T=16 ns=128
+d=256, 100 000 rows, Matern, REUSE_INNER), timed alternately in this process (median of --reps single calls each) with
+adkf_believer_pool(q = 8, log EI) - the same q walks and downdate with one evaluation per row and step where GIBBON makes S - and
+with q calls of adkf_mes_pool(S = 16, k = 8), the same S evaluations per row and walk without the downdate.  The line holds the
+three times, both ratios, each series' spread (max - min) / median, the scratch bytes, the bit-equality of a repeated call and how
+many picks each task's batch shares with its MES top-q.  No target.
 --gumbel: Gumbel max-value sampling (adkf_gumbel_pool, S = 16 uniforms per task) on --mes's batch and pool (T=16 ns=128 d=256, 100 000
 rows, Matern, REUSE_INNER), timed alternately in this process (median of --reps single calls each) with adkf_predict_pool(k = 8,
 log EI, nothing per row) and with gp_ops.max_value_samples at S = 16, m = 1024 (w and eps already on the device).  The call is three
 walks of the pool, each with an epilogue of 64 evaluations per row like MES at S = 64.  The line holds the three times, both
 ratios, each series' spread (max - min) / median, the scratch bytes and the bit-equality of a repeated call.  No target.
-Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--mes] [--gumbel] [--out FILE]"""
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--mes] [--gibbon] [--gumbel] [--out FILE]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -478,6 +484,57 @@ def shape_gumbel(T, ns, d, rows, k, S, m, reps, dev, out_path=None):
     return rec
 
 
+def shape_gibbon(T, ns, d, rows, q, S, reps, dev, out_path=None):
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    b = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern")
+    phi0, _ = gp_ops.init_params_batch(b, True, True)
+    b.flags = gp_ops.REUSE_DIST
+    phi, _, _, _, info = gp_ops.fit(b, phi0, 200)
+    gp_ops.check_info(info)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    X = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):
+        X[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    best = ys.median(1).values.contiguous()
+    # samples of min f: below the smallest label, spread over one prior standard deviation (--mes's)
+    ystar = (ys.min(1).values[:, None] - torch.rand(T, S, device=dev, generator=g)).contiguous()
+    f_gb = lambda: gp_ops.gibbon_pool(b, phi, X, ystar=ystar, q=q)
+    f_bv = lambda: gp_ops.believer_pool(b, phi, X, best_f=best, q=q, log_ei=True)
+    mes1 = lambda: gp_ops.mes_pool(b, phi, X, ystar=ystar, topk=q)
+    f_mes = lambda: [mes1() for _ in range(q)]
+    o1, o2 = f_gb(), f_gb()
+    f_bv(); topq = mes1()
+    torch.cuda.synchronize()
+    gp_ops.check_info(o1["info"])
+    ts = {"gibbon": [], "believer_log_ei": [], "q_calls_of_mes_pool": []}
+    for _ in range(reps):
+        ts["gibbon"].append(once(f_gb))
+        ts["believer_log_ei"].append(once(f_bv))
+        ts["q_calls_of_mes_pool"].append(once(f_mes))
+    med = {n: float(np.median(x)) for n, x in ts.items()}
+    lib = _lib.load()
+    shared = [len(set(a) & set(c)) for a, c in zip(o1["sel_idx"].cpu().tolist(), topq["top_idx"].cpu().tolist())]
+    rec = {"shape": f"gibbon T={T} ns={ns} d={d} rows={rows} q={q} S={S} matern REUSE_INNER trace=NULL", "refined_tasks": int(_refined(b).sum()),
+           "float64_tasks": int((_scal(b)[:, 45] > 30.0).sum()), "workspace_bytes": int(lib.adkf_workspace_bytes(T, ns, 0, d)),
+           "scratch_bytes": int(lib.adkf_believer_pool_scratch_bytes(T, ns, d, q)),
+           "gibbon_s": med["gibbon"], "believer_log_ei_s": med["believer_log_ei"], "q_calls_of_mes_pool_s": med["q_calls_of_mes_pool"],
+           "gibbon_over_believer": med["gibbon"] / med["believer_log_ei"], "gibbon_over_q_calls_of_mes_pool": med["gibbon"] / med["q_calls_of_mes_pool"],
+           "spread_max_minus_min_over_median": {n: (max(x) - min(x)) / float(np.median(x)) for n, x in ts.items()},
+           "repeat_is_bit_equal": bool(all(torch.equal(o1[n].view(torch.int32), o2[n].view(torch.int32)) for n in ("sel_idx", "sel_val", "sel_mean", "sel_var"))),
+           "all_selected": bool((o1["sel_idx"] >= 0).all() and torch.isfinite(o1["sel_val"]).all()),
+           "distinct_picks_per_task_min": int(min(len(set(r)) for r in o1["sel_idx"].cpu().tolist())),
+           "picks_shared_with_mes_top_q_per_task": shared, "all_s": ts}
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    return rec
+
+
 def shape_believer_ard(T, ns, d, rows, q, reps, dev, out_path=None):
     g = torch.Generator(device=dev).manual_seed(0)
     W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
@@ -600,12 +657,16 @@ def main():
     ap.add_argument("--thompson", action="store_true", help="adkf_thompson_pool against variant (ii) of --pool, timed alternately")
     ap.add_argument("--believer", action="store_true", help="adkf_believer_pool against q calls of adkf_predict_pool(k = 1), timed alternately")
     ap.add_argument("--mes", action="store_true", help="adkf_mes_pool at S = 1, 16, 64 against adkf_predict_pool(k, log EI), timed alternately")
+    ap.add_argument("--gibbon", action="store_true", help="adkf_gibbon_pool(q = 8, S = 16) against adkf_believer_pool(q = 8, log EI) and q calls of adkf_mes_pool(S = 16), timed alternately")
     ap.add_argument("--gumbel", action="store_true", help="adkf_gumbel_pool against adkf_predict_pool(k, log EI) and max_value_samples(S = 16, m = 1024), timed alternately")
-    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard), --mes, --gumbel: also write the JSON line to this file")
+    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard), --mes, --gibbon, --gumbel: also write the JSON line to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.mes:
         shape_mes(16, 128, 256, 100000, 8, a.reps, dev, a.out)
+        return
+    if a.gibbon:
+        shape_gibbon(16, 128, 256, 100000, 8, 16, a.reps, dev, a.out)
         return
     if a.gumbel:
         shape_gumbel(16, 128, 256, 100000, 8, 16, 1024, a.reps, dev, a.out)
