@@ -20,6 +20,7 @@ PM_MAXIMIZE = 2   # ... ei for maximisation
 PM_SCORE_MEAN = 4  # adkf_predict_pool: rank by the posterior mean instead of ei
 PM_LOG_EI = 16    # ... ei, and the ei score of adkf_predict_pool, hold log EI (8 is not a flag)
 POOL_TOPK_MAX = 64
+KG_REFS_MAX = 64         # adkf_kg_pool: reference rows per task
 TS_SAMPLES_MAX = 64      # adkf_thompson_pool: posterior draws per task
 TS_FEATURES_MAX = 4096   # ... random Fourier features (a multiple of 64, at least 64)
 
@@ -94,6 +95,10 @@ SIGNATURES = {
     "adkf_gibbon_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adkf_kg_pool_scratch_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "adkf_kg_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_outer_nll_value_grad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_ift_hypergrad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

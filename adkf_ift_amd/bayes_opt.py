@@ -14,6 +14,8 @@ and each function picks its own best candidate - a diverse batch of ``query_batc
 (``ADKF_PM_LOG_EI``), which stays finite where float32 EI is 0 on the whole pool and the ``"ei"`` loops fall back to random picks.
 ``run_gp_mes_bo_batched`` is the loop under max-value entropy search: one batched fit, one ``gp_ops.max_value_samples`` call (the
 minima of pathwise posterior draws over the whole pool) and one ``adkf_mes_pool`` call per iteration, with no ``best_f`` in the score.
+``run_gp_kg_bo_batched`` is the loop under the knowledge gradient for correlated beliefs: one batched fit, one mean top-``n_refs`` call
+for the reference rows and one ``adkf_kg_pool`` call (log KG) per iteration; it prices the observation noise and needs no ``best_f``.
 
 Only the Matern-5/2 branch exists here (the Tanimoto kernel of the reference's fingerprint baseline is not a
 distance-based kernel and is out of the library's scope).
@@ -333,6 +335,20 @@ def run_gp_ts_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
     return records
 
 
+def _take_picks(top_idx: torch.Tensor, usable: torch.Tensor, query_batch_size: int, rngs, queried, records, n: int) -> None:
+    """The end of an iteration of ``run_gp_mes_bo_batched`` and ``run_gp_kg_bo_batched``: replicate r takes the usable prefix of its
+    candidates ``top_idx[r]`` (``usable[r]``: a prefix mask), fills a shortfall with random rows it has not queried, drawn from its own
+    generator ``rngs[r]``, and adds the picks to ``queried[r]`` and ``records[r]`` (both updated in place)."""
+    for r, rng in enumerate(rngs):
+        nonzero = int(usable[r].sum())
+        pick = top_idx[r, :nonzero].tolist()
+        if nonzero < query_batch_size:
+            taken = set(queried[r] + pick)
+            pick += rng.choice([i for i in range(n) if i not in taken], size=query_batch_size - nonzero, replace=False).tolist()
+        queried[r] = list(set(queried[r] + pick))
+        records[r].extend(pick)
+
+
 @torch.no_grad()
 def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
                           kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
@@ -379,10 +395,6 @@ def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
     queried = [rng.choice(np.arange(init_from, n), size=num_init_points, replace=False).tolist() for rng in rngs]
     records = [[min(q)] for q in queried]
     gens = [torch.Generator().manual_seed(int(rng.integers(0, 2 ** 62))) for rng in rngs]
-
-    def free(taken):
-        taken = set(taken)
-        return [i for i in range(n) if i not in taken]
 
     for _ in range(num_bo_iters):
         sizes = [len(q) for q in queried]
@@ -432,11 +444,60 @@ def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
         usable = torch.isfinite(top_val) & (top_idx >= 0)   # (a prefix of each row: descending scores, the -1 / -inf tail last)
         if batch == "gibbon":   # pick order, not score order: keep the prefix
             usable = usable.long().cumprod(1).bool()
-        for r, rng in enumerate(rngs):
-            nonzero = int(usable[r].sum())
-            pick = top_idx[r, :nonzero].tolist()
-            if nonzero < query_batch_size:
-                pick += rng.choice(free(queried[r] + pick), size=query_batch_size - nonzero, replace=False).tolist()
-            queried[r] = list(set(queried[r] + pick))
-            records[r].extend(pick)
+        _take_picks(top_idx, usable, query_batch_size, rngs, queried, records, n)
+    return records
+
+
+@torch.no_grad()
+def run_gp_kg_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
+                         kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
+                         rngs: List[np.random.Generator], ard: bool = False, n_refs: int = 32) -> List[List[int]]:
+    """``len(rngs)`` replicates of a knowledge-gradient BO loop (Frazier, Powell & Dayanik 2009) over the same pool at once
+    (minimisation, as ``run_gp_ei_bo``); returns their records: the best initial index, then the picks in descending score.  Per
+    iteration the replicates' queried sets are fitted by ONE ``gp_ops.fit`` (as ``run_gp_ei_bo_batched``), ONE
+    ``gp_ops.predict_pool(score="mean", topk=n_refs)`` call with no exclusions takes each replicate's ``n_refs`` (at most 64) rows
+    of lowest posterior mean over the WHOLE pool - queried rows included: they belong in the discretisation - and ONE
+    ``gp_ops.kg_pool(log=True, topk=query_batch_size, exclude=queried)`` call scores the pool against them and returns each
+    replicate's best rows among those it has not queried.  The score is log KG, which keeps an order where float32 KG is 0 on every
+    row; it prices the observation noise and needs no ``best_f``.  A returned candidate counts when its index is not -1 and its
+    score is finite; a shortfall is filled with random free rows from the replicate's generator, as in ``run_gp_mes_bo_batched``.
+    Nothing random enters the score: a replicate's record does not depend on which other replicates share the batch."""
+    R, n = len(rngs), x_all.shape[0]
+    if not 1 <= query_batch_size <= gp_ops._lib.POOL_TOPK_MAX:
+        raise ValueError(f"query_batch_size must be in [1, {gp_ops._lib.POOL_TOPK_MAX}], got {query_batch_size}")
+    M = int(n_refs)
+    if not 1 <= M <= gp_ops._lib.KG_REFS_MAX:
+        raise ValueError(f"n_refs must be in [1, {gp_ops._lib.KG_REFS_MAX}], got {n_refs}")
+    y_all = (y_all - y_all.mean()) / y_all.std()
+    X = x_all.detach().float().contiguous()
+    queried = [rng.choice(np.arange(init_from, n), size=num_init_points, replace=False).tolist() for rng in rngs]
+    records = [[min(q)] for q in queried]
+
+    for _ in range(num_bo_iters):
+        sizes = [len(q) for q in queried]
+        ns = max(sizes)
+        Zs = torch.zeros(R, ns, X.shape[1], dtype=torch.float32, device=X.device)
+        ys = torch.zeros(R, ns, dtype=torch.float32, device=X.device)
+        pri, phi0 = [], []
+        for r, q in enumerate(queried):
+            xq, yq = x_all[q], y_all[q]
+            _, model, mll = create_gp(xq, yq, kernel_type, device, noise_init, noise_prior)
+            Zs[r, :sizes[r]] = model.train_inputs[0].detach().float()
+            ys[r, :sizes[r]] = model.train_targets.detach().float()
+            pri.append(mll.priors_row(X.device))
+            p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
+            phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
+        n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
+        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
+        phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
+        gp_ops.check_info(info, "run_gp_kg_bo_batched fit")
+        b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+        refs = gp_ops.predict_pool(b, phi, X, maximize=False, topk=M, score="mean", want_mean=False, want_var=False, want_ei=False)
+        gp_ops.check_info(refs["info"], "BO posterior")
+        out = gp_ops.kg_pool(b, phi, X, ref_idx=refs["top_idx"], maximize=False, log=True, topk=query_batch_size, exclude=queried,
+                             want_score=False)
+        gp_ops.check_info(out["info"], "BO posterior")
+        top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
+        usable = torch.isfinite(top_val) & (top_idx >= 0)   # (a prefix of each row: descending scores, the -1 / -inf tail last)
+        _take_picks(top_idx, usable, query_batch_size, rngs, queried, records, n)
     return records

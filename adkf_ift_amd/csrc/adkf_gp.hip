@@ -29,6 +29,7 @@
 #include "mes_stream.h"
 #include "gumbel_stream.h"
 #include "gibbon_stream.h"
+#include "kg_stream.h"
 
 #include "host_common.h"
 #include "host_gp.h"
@@ -318,6 +319,18 @@ int adkf_gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, con
                      void* stream) {
     return gibbon_pool(b, phi, flags, X, rows, ystar, S, excl_idx, excl_off, q, trace, sel_idx, sel_val, sel_mean, sel_var, info, ws, ws_bytes,
                        scratch, scratch_bytes, stream);
+}
+
+size_t adkf_kg_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t M, int32_t k) {
+    if (T <= 0 || ns_max <= 0 || ns_max > MAX_POINTS || d <= 0 || M < 1 || M > ADKF_KG_REFS_MAX || k < 0 || k > ADKF_POOL_TOPK_MAX) return 0;
+    return kg_scratch(nullptr, T, ns_max, d, M, k).bytes;
+}
+
+int adkf_kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* ref_idx, int32_t M,
+                 const int64_t* excl_idx, const int64_t* excl_off, float* score, float* cov, float* ref_mean, int32_t k, int64_t* top_idx,
+                 float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    return kg_pool(b, phi, flags, X, rows, ref_idx, M, excl_idx, excl_off, score, cov, ref_mean, k, top_idx, top_val, info, ws, ws_bytes, scratch,
+                   scratch_bytes, stream);
 }
 
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

@@ -40,6 +40,8 @@
 //
 // The c0 panel, the substitution of one row and the float64 downdate are functions (bv_c0_panel, bv_downdate, bv64_downdate) because
 // adkf_gibbon_pool (gibbon_stream.h) downdates the same variance with the same state, k_bv_init and k_bv_step, under another score.
+// The float64 c0 of a lane (bv64_c0) and the first parts of k_bv_step - the stored row, k(Z_s, x) and w = A^-1 k (bv_store_row,
+// bv_kernel_col, bv_solve_w) - are functions because adkf_kg_pool (kg_stream.h) builds the same state for a fixed reference set.
 #pragma once
 #include "thompson_stream.h"
 
@@ -144,13 +146,12 @@ struct BvEpilogue {
     }
 };
 
-// the float64 downdate of one pool row zq (kernel row k) with c > 0 picks made, over the lanes of a wave: lane i forms c0(x, i), the
-// substitution runs over the lanes (row i of G against the ell broadcast so far); returns |ell|^2 to every lane
+// lane i < c of a wave: c0(x, i) in float64 for the pool row zq (kernel row k) against the stored row i of Xp and its w (0 in the other lanes)
 template <bool ARD>
-__device__ __forceinline__ double bv64_downdate(const PmArgs& a, const Pm64Task& tk, const float* zq, const double* k, const double* Wt,
-                                                const double* G, const float* Xp, int c, int q, int lane) {
+__device__ __forceinline__ double bv64_c0(const PmArgs& a, const Pm64Task& tk, const float* zq, const double* k, const double* Wt, const float* Xp,
+                                          int c, int lane) {
     const int n = tk.n, ld = tk.ld;
-    double c0 = 0.0;   // lane i: c0(x, i)
+    double c0 = 0.0;
     if (lane < c) {
         const float* xp = Xp + (size_t)lane * a.d;
         double s = 0.0, f = 0.0;
@@ -162,6 +163,15 @@ __device__ __forceinline__ double bv64_downdate(const PmArgs& a, const Pm64Task&
         for (int i = 0; i < n; ++i) f += k[i] * Wt[(size_t)lane * ld + i];
         c0 = tk.os * kappa0(a.kind, s * tk.il2) - f;
     }
+    return c0;
+}
+
+// the float64 downdate of one pool row zq (kernel row k) with c > 0 picks made, over the lanes of a wave: lane i forms c0(x, i), the
+// substitution runs over the lanes (row i of G against the ell broadcast so far); returns |ell|^2 to every lane
+template <bool ARD>
+__device__ __forceinline__ double bv64_downdate(const PmArgs& a, const Pm64Task& tk, const float* zq, const double* k, const double* Wt,
+                                                const double* G, const float* Xp, int c, int q, int lane) {
+    const double c0 = bv64_c0<ARD>(a, tk, zq, k, Wt, Xp, c, lane);   // lane i: c0(x, i)
     double part = 0.0, ss = 0.0;   // lane i: sum_(l < i) G[i, l] ell_l so far
     for (int i = 0; i < c; ++i) {
         double e = lane == i ? (c0 - part) / G[(size_t)i * q + i] : 0.0;
@@ -225,6 +235,58 @@ __device__ __forceinline__ double bv_block_sum(double x, double* red) {
     return red[0];
 }
 
+// ---- the parts of k_bv_step that k_kg_refs (kg_stream.h) runs on a reference row: one workgroup of 256 threads each
+// the pool row xp of task t into dst [d] - ARD: scaled by the function the walk of the task's kind applies (see the top of the file),
+// published - and the row everything after reads: the stored copy (ARD) or xp itself
+template <bool ARD, class ARGS>
+__device__ __forceinline__ const float* bv_store_row(const ARGS& args, int t, bool f64, const float* xp, float* dst) {
+    const PmArgs& a = args.p;
+    const int tid = threadIdx.x, d = a.d;
+    if constexpr (ARD) {   // the row as the walk of this task's kind scales it; everything below reads the stored copy
+        const float *mu = a.mean_s + (size_t)t * d, *il = args.r.il + (size_t)t * d, *el = args.r.ell + (size_t)t * d;
+        for (int e = tid; e < d; e += 256) dst[e] = f64 ? ard_scaled(xp[e], mu[e], el[e]) : ard_scaled_il(xp[e], mu[e], il[e]);
+        __syncthreads();
+        return dst;
+    } else {
+        for (int e = tid; e < d; e += 256) dst[e] = xp[e];
+        return xp;
+    }
+}
+// k(Z_s, x_p) from the features, in float64, into k64 (flagged tasks) or rs (rounded); published
+__device__ __forceinline__ void bv_kernel_col(const PmArgs& a, const float* Zs, const float* xp, int n, double os, double il2, bool f64,
+                                              double* k64, float* rs) {
+    const int d = a.d;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float* zs = Zs + (size_t)i * d;
+        double sq = 0.0;
+        for (int e = 0; e < d; ++e) { const double df = (double)xp[e] - (double)zs[e]; sq += df * df; }
+        const double kv = os * kappa0(a.kind, sq * il2);
+        if (f64) k64[i] = kv; else rs[i] = (float)kv;
+    }
+    __syncthreads();
+}
+// w = A^-1 k, published: flagged tasks through k_refine64's float64 A^-1 (k in fb as doubles, w behind it at R64_MAXN, and in Wn64),
+// float32 tasks through pm_solve_refined (k in fb, w in fb + TS_NS_MAX, and in Wn; the third array is used up)
+__device__ __forceinline__ void bv_solve_w(const PmArgs& a, int t, int n, bool f64, float* fb, float* Wn, double* Wn64) {
+    const int tid = threadIdx.x, ld = a.ns_ld;
+    if (f64) {
+        double *k64 = reinterpret_cast<double*>(fb), *w64 = k64 + R64_MAXN;
+        const double* A1 = a.w64 + (size_t)t * a.w64_stride;
+        for (int i = tid; i < n; i += 256) {
+            double x = 0.0;
+            for (int k = 0; k < n; ++k) x += A1[(size_t)k * ld + i] * k64[k];
+            w64[i] = x; Wn64[i] = x;
+        }
+    } else {   // k_ts_solve's solve
+        const float* sc = a.scal + (size_t)t * NSCAL;
+        float *rs = fb, *vs = fb + TS_NS_MAX, *es = fb + 2 * TS_NS_MAX;
+        pm_solve_refined(a.Ainv + (size_t)t * ld * ld, a.D2ss + (size_t)t * ld * ld, a.kind, sc[S_OS], sc[S_NOISE], 1.f / (sc[S_LS] * sc[S_LS]), n, ld,
+                         rs, vs, es);
+        for (int i = tid; i < n; i += 256) Wn[i] = vs[i];
+    }
+    __syncthreads();
+}
+
 // ---- the end of step j: one workgroup per task (see the top of the file)
 template <bool ARD>
 __global__ __launch_bounds__(256) void k_bv_step(BvKargs<ARD> args) {
@@ -262,41 +324,11 @@ __global__ __launch_bounds__(256) void k_bv_step(BvKargs<ARD> args) {
     const float* Zs = a.Zs + (size_t)t * ld * d;
     const float* ys = a.y_s + (size_t)t * ld;
     float* Xt = v.Xp + (size_t)t * q * d;
-    if constexpr (ARD) {   // the row as the walk of this task's kind scales it; everything below reads the stored copy
-        const float *mu = a.mean_s + (size_t)t * d, *il = args.r.il + (size_t)t * d, *el = args.r.ell + (size_t)t * d;
-        for (int e = tid; e < d; e += 256) Xt[(size_t)c * d + e] = f64 ? ard_scaled(xp[e], mu[e], el[e]) : ard_scaled_il(xp[e], mu[e], il[e]);
-        __syncthreads();
-        xp = Xt + (size_t)c * d;
-    } else {
-        for (int e = tid; e < d; e += 256) Xt[(size_t)c * d + e] = xp[e];
-    }
-    float *rs = fb, *vs = fb + TS_NS_MAX, *es = fb + 2 * TS_NS_MAX;   // float32 tasks: k, then w in vs
+    xp = bv_store_row<ARD>(args, t, f64, xp, Xt + (size_t)c * d);
+    float *rs = fb, *vs = fb + TS_NS_MAX;   // float32 tasks: k, then w in vs (bv_solve_w)
     double *k64 = reinterpret_cast<double*>(fb), *w64 = k64 + R64_MAXN;   // float64 tasks (n <= R64_MAXN): k and w
-    // ---- k(Z_s, x_p) from the features, in float64
-    for (int i = tid; i < n; i += 256) {
-        const float* zs = Zs + (size_t)i * d;
-        double sq = 0.0;
-        for (int e = 0; e < d; ++e) { const double df = (double)xp[e] - (double)zs[e]; sq += df * df; }
-        const double kv = os * kappa0(a.kind, sq * il2);
-        if (f64) k64[i] = kv; else rs[i] = (float)kv;
-    }
-    __syncthreads();
-    // ---- w = A^-1 k
-    if (f64) {
-        const double* A1 = a.w64 + (size_t)t * a.w64_stride;
-        double* Wn = v.W64 + ((size_t)t * q + c) * ld;
-        for (int i = tid; i < n; i += 256) {
-            double x = 0.0;
-            for (int k = 0; k < n; ++k) x += A1[(size_t)k * ld + i] * k64[k];
-            w64[i] = x; Wn[i] = x;
-        }
-    } else {   // k_ts_solve's solve
-        float* Wn = v.W + ((size_t)t * q + c) * ld;
-        pm_solve_refined(a.Ainv + (size_t)t * ld * ld, a.D2ss + (size_t)t * ld * ld, a.kind, sc[S_OS], sc[S_NOISE], 1.f / (sc[S_LS] * sc[S_LS]), n, ld,
-                         rs, vs, es);
-        for (int i = tid; i < n; i += 256) Wn[i] = vs[i];
-    }
-    __syncthreads();
+    bv_kernel_col(a, Zs, xp, n, os, il2, f64, k64, rs);
+    bv_solve_w(a, t, n, f64, fb, v.W + ((size_t)t * q + c) * ld, f64 ? v.W64 + ((size_t)t * q + c) * ld : nullptr);
     // ---- the pick's mean w . y and prior-step variance s - k . w
     double pm = 0.0, pk = 0.0;
     for (int i = tid; i < n; i += 256) {

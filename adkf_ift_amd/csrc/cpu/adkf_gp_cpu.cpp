@@ -1122,6 +1122,137 @@ int adkf_gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, con
     return believer_pool(ard, b, phi, flags, X, rows, nullptr, excl_idx, excl_off, q, trace, sel_idx, sel_val, sel_mean, sel_var, info, ystar, S, true);
 }
 
+size_t adkf_kg_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t, int32_t) { return 0; }
+
+// KG or log KG of the lines (a_l, b_l) in float64, Frazier's sorted form: the lines by ascending slope (equal slopes: the largest
+// intercept only), the upper envelope by a stack of breakpoints, then the sum of (b_next - b_cur) h(-|c|) over consecutive survivors
+// (h through log_h: the tail keeps its digits), or its log-sum-exp.  One surviving line: 0 / -inf.
+static double kg_value(std::vector<std::pair<double, double>> ln, bool want_log) {   // (b, a) pairs
+    const double ninf = -std::numeric_limits<double>::infinity();
+    std::sort(ln.begin(), ln.end(), [](const std::pair<double, double>& x, const std::pair<double, double>& y) { return x.first < y.first || (x.first == y.first && x.second > y.second); });
+    std::vector<std::pair<double, double>> hull;   // survivors, ascending slope
+    std::vector<double> start;                     // start[i]: from where survivor i is on top
+    for (const auto& l : ln) {
+        if (!hull.empty() && hull.back().first == l.first) continue;   // an equal slope with a smaller (or equal) intercept
+        double z = ninf;
+        while (!hull.empty()) {
+            z = (hull.back().second - l.second) / (l.first - hull.back().first);
+            if (z > start.back()) break;
+            hull.pop_back(); start.pop_back();
+            z = ninf;
+        }
+        hull.push_back(l); start.push_back(hull.size() == 1 ? ninf : z);
+    }
+    std::vector<double> lt;
+    for (size_t i = 0; i + 1 < hull.size(); ++i) lt.push_back(std::log(hull[i + 1].first - hull[i].first) + log_h(-std::fabs(start[i + 1])));
+    if (lt.empty()) return want_log ? ninf : 0.0;
+    const double mx = *std::max_element(lt.begin(), lt.end());
+    if (mx == ninf) return want_log ? ninf : 0.0;
+    double sum = 0.0;
+    for (double x : lt) sum += std::exp(x - mx);
+    return want_log ? mx + std::log(sum) : std::exp(mx) * sum;
+}
+
+// Knowledge-gradient selection over a shared pool (include/adkf_gp.h): the mean, the latent variance and K A^-1 of every pool row
+// once, the covariance of every row with every valid reference entry from them, then kg_value per row in float64, rounded to float32
+// at the boundary; the selection ranks those float32 values under adkf_predict_pool's total order.  ARD: pm_task prepares the
+// support set and the pool rows on z~ = (z - mu) / l, and the distances between pool rows are taken on x / l (mu cancels).
+int adkf_kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* ref_idx, int32_t M,
+                 const int64_t* excl_idx, const int64_t* excl_off, float* score, float* cov, float* ref_mean, int32_t k, int64_t* top_idx,
+                 float* top_val, int32_t* info, void*, size_t, void*, size_t, void*) {
+    if (int rc = check(b, false, true)) return rc;
+    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    if (!ref_idx) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (k < 0) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (k == 0 && !score && !cov && !ref_mean) return ADKF_E_BADARG;
+    if (M < 1 || M > ADKF_KG_REFS_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    const bool ard = (b->flags & ADKF_BATCH_ARD) != 0, want_log = (flags & ADKF_PM_LOG_EI) != 0;
+    const double sgn = (flags & ADKF_PM_MAXIMIZE) ? 1.0 : -1.0;
+    const int d = b->d;
+    const float ninf = -std::numeric_limits<float>::infinity();
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        const size_t R = (size_t)rows, o = (size_t)t * R;
+        if (score) std::fill(score + o, score + o + R, 0.f);
+        if (cov) std::fill(cov + o * M, cov + (o + R) * M, 0.f);
+        if (ref_mean) std::fill(ref_mean + (size_t)t * M, ref_mean + (size_t)(t + 1) * M, 0.f);
+        for (int q = 0; q < k; ++q) { top_idx[(size_t)t * k + q] = -1; top_val[(size_t)t * k + q] = ninf; }
+        const int n = std::min(ns_of(b, t), b->ns_max);
+        Mat Kr(R * std::max(n, 0)), Cr(R * std::max(n, 0)), mu(R), v(R);
+        double s = 0.0, noise = 0.0, il2 = 0.0;
+        const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
+            s = in.s; noise = in.noise; il2 = 1.0 / (in.l * in.l);
+            const float* y = b->y_s + (size_t)t * b->ns_max;
+            double* kr = &Kr[(size_t)r * n];
+            double* c = &Cr[(size_t)r * n];
+            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); kr[j] = in.s * k0; }
+            double m1 = 0.0, qf = 0.0;
+            for (int j = 0; j < n; ++j) {
+                double cj = 0.0;
+                for (int i = 0; i < n; ++i) cj += kr[i] * in.Ainv[(size_t)i * n + j];
+                c[j] = cj;
+                m1 += cj * (double)y[j];
+                qf += cj * kr[j];
+            }
+            mu[r] = m1; v[r] = in.s - qf;
+        });
+        if (!done) continue;
+        Mat Xl(ard ? R * d : 0);   // ARD: the pool rows over l
+        if (ard) {
+            const float* x0 = phi + (size_t)t * (2 + d);
+            for (size_t r = 0; r < R; ++r) for (int c = 0; c < d; ++c) Xl[r * d + c] = (double)X[r * d + c] / softplus(x0[2 + c]);
+        }
+        // the valid entries: inside the pool, first occurrences
+        std::vector<int64_t> ref(M, -1);
+        for (int j = 0; j < M; ++j) {
+            const int64_t p = ref_idx[(size_t)t * M + j];
+            if (p < 0 || p >= rows) continue;
+            bool first = true;
+            for (int i = 0; i < j && first; ++i) first = ref_idx[(size_t)t * M + i] != p;
+            if (first) ref[j] = p;
+        }
+        Mat C(R * M, 0.0);   // cov(x_r, entry j)
+        for (int j = 0; j < M; ++j) {
+            const int64_t p = ref[j];
+            if (p < 0) continue;
+            if (ref_mean) ref_mean[(size_t)t * M + j] = (float)mu[p];
+            const Mat Dp = ard ? sqdist(Xl.data() + (size_t)p * d, 1, Xl.data(), (int)rows, d) : sqdist(X + (size_t)p * d, 1, X, (int)rows, d);
+            for (size_t r = 0; r < R; ++r) {
+                double k0, k1, k2;
+                kappa(b->kernel, Dp[r] * il2, k0, k1, k2);
+                double c0 = s * k0;
+                for (int i = 0; i < n; ++i) c0 -= Kr[r * n + i] * Cr[(size_t)p * n + i];
+                C[r * M + j] = c0;
+                if (cov) cov[(o + r) * M + j] = (float)c0;
+            }
+        }
+        std::vector<float> sc(R);
+        for (size_t r = 0; r < R; ++r) {
+            const double vc = std::max(v[r], 1e-12), sd = std::sqrt(vc + noise);
+            std::vector<std::pair<double, double>> ln;
+            for (int j = 0; j < M; ++j)
+                if (ref[j] >= 0 && ref[j] != (int64_t)r) ln.emplace_back(C[r * M + j] / sd, sgn * mu[ref[j]]);
+            ln.emplace_back(vc / sd, sgn * mu[r]);
+            sc[r] = (mu[r] == mu[r] && v[r] == v[r]) ? (float)kg_value(ln, want_log) : std::numeric_limits<float>::quiet_NaN();   // a NaN row: NaN
+            if (score) score[o + r] = sc[r];
+        }
+        if (k <= 0) continue;
+        std::vector<int64_t> cand;
+        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
+        for (int64_t r = 0; r < rows; ++r)
+            if (sc[r] == sc[r] && !(xb && std::binary_search(xb, xe, r))) cand.push_back(r);
+        const size_t kk = std::min<size_t>(k, cand.size());
+        std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return sc[a] > sc[c] || (sc[a] == sc[c] && a < c); });
+        for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)t * k + q] = cand[q]; top_val[(size_t)t * k + q] = sc[cand[q]]; }
+    }
+    return 0;
+}
+
 static int outer_common(const adkf_batch_t* b, const float* phi, int flags, bool with_hessian, float* f_out, float* g_phi, float* dZ_s, float* dZ_q,
                         float* v_out, float* H_out, int32_t* info) {
     const int d = b->d;

@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool and adkf_gumbel_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool and adkf_kg_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
 #pragma once
 #include "host_ard.h"
 
@@ -538,6 +538,82 @@ int gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const fl
     // there is no incumbent: the believer's slot [T] is filled from the first T floats of ystar (S >= 1) and never read by a score
     k_bv_init<<<ceil_div(T, 256), 256, 0, st>>>(v.b, ystar, T);
     return c.ard ? gibbon_launch<true>(c, pa, pool, v, rows, have64) : gibbon_launch<false>(c, pa, pool, v, rows, have64);
+}
+
+// adkf_kg_pool: the scratch is the reference state - w [T, M, ns] (and its float64 twin where a workspace of this shape can have a
+// float64 region), the entries' feature rows [T, M, d], their means [T, M] and their pool rows [T, M] (-1: a skipped entry) - and
+// prediction's candidate lists [T, chunks_max, k].  It does not depend on rows.
+struct KgScratch { float* W; double* W64; float* Xp; float* am; int64_t* ridx; int64_t* cand_idx; float* cand_val; size_t bytes; };
+inline KgScratch kg_scratch(void* base, int T, int ns, int d, int M, int k) {
+    Arena ar{static_cast<char*>(base), 0};
+    const size_t e = (size_t)T * M * ns, c = (size_t)T * pm_pool_chunks_max(T) * k;
+    KgScratch l{};
+    l.W = ar.floats(e);
+    l.W64 = ar.as<double>(ns <= R64_MAXN ? e : 0);
+    l.Xp = ar.floats((size_t)T * M * d);
+    l.am = ar.floats((size_t)T * M);
+    l.ridx = ar.as<int64_t>((size_t)T * M);
+    l.cand_idx = ar.as<int64_t>(c);
+    l.cand_val = ar.floats(c);
+    l.bytes = ar.off;
+    return l;
+}
+
+// The launches of a prepared knowledge-gradient call: the reference state (one workgroup per entry and task), then as mes_launch - the
+// walks of prediction with KgEpilogue, the float64 walk, prediction's merge of the lists.
+template <bool ARD>
+int kg_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, const KgArgs& v, int64_t rows, bool have64) {
+    hipStream_t st = c.st;
+    const int T = c.b.T;
+    if constexpr (ARD) launch_ard_il(c);
+    const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
+    // every output starts at 0: the rows of skipped tasks (n_s == 0, info != 0) stay so
+    if (v.score && rows > 0) hipMemsetAsync(v.score, 0, sizeof(float) * (size_t)rows * T, st);
+    if (v.cov && rows > 0) hipMemsetAsync(v.cov, 0, sizeof(float) * (size_t)rows * T * v.M, st);
+    k_kg_refs<ARD><<<dim3(v.M, T), 256, 0, st>>>(pm_kargs<ARD, true, KgEpilogue>(c, pa, &pool, v));
+    int rc;
+    if (rows > 0) {
+        if ((rc = pm_launch_walk<false, ARD, true, KgEpilogue>(c, pa, &pool, v, tiles))) return rc;
+        if ((rc = pm_launch_walk<true, ARD, true, KgEpilogue>(c, pa, &pool, v, tiles))) return rc;
+    }
+    if (have64 && rows > 0) {
+        pool.grid[2] = std::min(pm64_grid(rows), pool.chunks_max);
+        k_kg_walk64<ARD><<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(pm_kargs<ARD, true, KgEpilogue>(c, pa, &pool, v));
+    }
+    if (pool.k > 0) k_pool_topk<<<T, 64, 0, st>>>(pm_kargs<false, true>(c, pa, &pool));
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_kg_pool: isotropic and ARD batches alike (as adkf_mes_pool)
+int kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* ref_idx, int32_t M,
+            const int64_t* excl_idx, const int64_t* excl_off, float* score, float* cov, float* ref_mean, int32_t k, int64_t* top_idx,
+            float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags & ~(ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    if (!ref_idx) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (k < 0) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (k == 0 && !score && !cov && !ref_mean) return ADKF_E_BADARG;
+    if (M < 1 || M > ADKF_KG_REFS_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    const KgScratch l = kg_scratch(scratch, b->T, b->ns_max, b->d, M, k);
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    PmPool pool = pm_pool(excl_idx, excl_off, k, b->T, l.cand_idx, l.cand_val, rows, c.st);
+    pool.top_idx = top_idx; pool.top_val = top_val;
+    PmArgs pa = pm_args(c, flags, X, rows, info);
+    const bool have64 = c.w.w64 && b->ns_max <= R64_MAXN;
+    if (!have64) pa.r64_thresh = INFINITY;
+    KgArgs v{};
+    v.M = M; v.ref_idx = ref_idx;
+    v.W = l.W; v.W64 = have64 ? l.W64 : nullptr; v.Xp = l.Xp; v.am = l.am; v.ridx = l.ridx;
+    v.score = score; v.cov = cov; v.ref_mean = ref_mean;
+    return c.ard ? kg_launch<true>(c, pa, pool, v, rows, have64) : kg_launch<false>(c, pa, pool, v, rows, have64);
 }
 
 // adkf_gumbel_pool: the scratch is the fixed-point sums [T, 64] (uint64), the probes [T, 64] (float32) and the images of the two

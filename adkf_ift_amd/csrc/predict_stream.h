@@ -260,7 +260,11 @@ __device__ __forceinline__ bool pm_excluded(const PmPool& s, int t, long long r)
 template <class EX>
 __device__ __forceinline__ void pm_list_merge(float& lv, long long& li, int k, float s, long long r, bool valid, EX excl) {
     const int lane = threadIdx.x & 63;
-    bool pass = valid && s == s && pm_beats(s, r, __shfl(lv, k - 1), __shfl(li, k - 1));
+    // the k-th entry is read by every lane, outside the test: a shuffle behind `valid &&` runs with the invalid lanes switched off, and
+    // reads 0 from lane k - 1 when that lane is one of them (fewer candidates than k) - only positive scores then passed
+    const float kv = __shfl(lv, k - 1);
+    const long long ki = __shfl(li, k - 1);
+    bool pass = valid && s == s && pm_beats(s, r, kv, ki);
     if (pass) pass = !excl(r);
     unsigned long long mask = __ballot(pass);
     while (mask) {

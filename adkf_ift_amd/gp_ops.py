@@ -696,6 +696,70 @@ def gibbon_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, ystar: torch.
     return dict(sel_idx=sel_idx, sel_val=sel_val, sel_mean=sel_mean, sel_var=sel_var, trace=trace, info=info)
 
 
+def kg_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, ref_idx: Optional[torch.Tensor] = None, n_refs: int = 32,
+            maximize: bool = False, log: bool = False, topk: int = 0, exclude=None, want_score: bool = True, want_cov: bool = False):
+    """The knowledge gradient for correlated beliefs (Frazier, Powell & Dayanik 2009; Scott, Frazier & Powell 2011) over the shared
+    pool ``X [rows, d]`` in one ``adkf_kg_pool`` call, for isotropic and ARD batches alike: a row is scored by how much one noisy
+    observation there is expected to raise (``maximize``; lower without) the best posterior mean over the row itself and the
+    reference rows ``ref_idx [T, M]`` (int64 pool indices, M at most 64, on the batch's device).  Entries outside ``[0, rows)`` are
+    skipped - the ``top_idx`` of ``predict_pool`` with its -1 tail can be passed as it is - and a repeated index counts once.  With
+    ``ref_idx=None`` each task's ``n_refs`` rows of best posterior mean, in the call's sense, are taken first, from one
+    ``predict_pool(score="mean")`` call with no exclusions: rows already queried belong in the discretisation.  ``log``: the score is
+    log KG, finite where float32 KG underflows to 0 (-inf for a row with no other line than its own).  Returns ``dict(score, cov,
+    ref_mean, ref_idx, top_idx, top_val, info)``: ``score [T, rows]`` (``want_score``, else None), ``cov [T, rows, M]``
+    (``want_cov``, else None) the latent posterior covariance of every row with every reference entry (0 for skipped entries),
+    ``ref_mean [T, M]`` the entries' posterior means (0 for skipped entries), ``ref_idx`` as used, ``top_idx [T, topk]`` /
+    ``top_val`` as ``predict_pool`` returns them (None with ``topk == 0``) and ``info [T]``.  ``exclude``: rows a task may not
+    select (``pack_exclude``); they are still scored."""
+    lib = _lib.load()
+    if b.nq != 0:
+        raise ValueError("kg_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    topk = int(topk)
+    if topk < 0 or topk > _lib.POOL_TOPK_MAX:
+        raise ValueError(f"topk must be in [0, {_lib.POOL_TOPK_MAX}], got {topk}")
+    if ref_idx is None:
+        n_refs = int(n_refs)
+        if n_refs < 1 or n_refs > _lib.KG_REFS_MAX:
+            raise ValueError(f"n_refs must be in [1, {_lib.KG_REFS_MAX}], got {n_refs}")
+    else:
+        if not torch.is_tensor(ref_idx) or ref_idx.dtype != torch.int64 or ref_idx.dim() != 2 or ref_idx.shape[0] != b.T:
+            raise ValueError(f"ref_idx must be an int64 tensor [T, M] = [{b.T}, M], got "
+                             f"{(tuple(ref_idx.shape), ref_idx.dtype) if torch.is_tensor(ref_idx) else ref_idx!r}")
+        if ref_idx.shape[1] < 1 or ref_idx.shape[1] > _lib.KG_REFS_MAX:
+            raise ValueError(f"the number of reference rows M must be in [1, {_lib.KG_REFS_MAX}], got {ref_idx.shape[1]}")
+    phi = b.check_phi(phi)
+    X = _f32(X, "X")
+    if X.dim() != 2 or X.shape[1] != b.d:
+        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    rows = X.shape[0]
+    if X.device != b.device:
+        raise ValueError(f"X lives on {X.device}, the batch on {b.device}")
+    if ref_idx is None:
+        ref_idx = predict_pool(b, phi, X, maximize=maximize, topk=n_refs, score="mean", want_mean=False, want_var=False, want_ei=False)["top_idx"]
+    elif ref_idx.device != b.device:
+        raise ValueError(f"ref_idx lives on {ref_idx.device}, the batch on {b.device}")
+    ref_idx = ref_idx.contiguous()
+    M = ref_idx.shape[1]
+    excl_idx = excl_off = None
+    if exclude is not None and topk > 0:
+        excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
+    score = _new(b, b.T, rows) if want_score else None
+    cov = _new(b, b.T, rows, M) if want_cov else None
+    ref_mean = _new(b, b.T, M)
+    top_idx = _new(b, b.T, topk, dtype=torch.int64) if topk > 0 else None
+    top_val = _new(b, b.T, topk) if topk > 0 else None
+    info = _new(b, b.T, dtype=torch.int32)
+    sb = int(lib.adkf_kg_pool_scratch_bytes(b.T, b.ns, b.d, M, topk))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device)
+    flags = (_lib.PM_MAXIMIZE if maximize else 0) | (_lib.PM_LOG_EI if log else 0)
+    ws, nb = b.workspace()
+    cb = b.c_struct()
+    _lib.check(lib.adkf_kg_pool(C.byref(cb), ptr(phi), flags, ptr(X), rows, ptr(ref_idx), M, ptr(excl_idx), ptr(excl_off), ptr(score),
+                                ptr(cov), ptr(ref_mean), topk, ptr(top_idx), ptr(top_val), ptr(info), ptr(ws), nb, ptr(scratch), sb,
+                                stream(b.device)), "adkf_kg_pool")
+    return dict(score=score, cov=cov, ref_mean=ref_mean, ref_idx=ref_idx, top_idx=top_idx, top_val=top_val, info=info)
+
+
 def max_value_samples(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: torch.Tensor, phase: torch.Tensor, n_samples: int,
                       generator: Optional[torch.Generator] = None, w: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
                       maximize: bool = False):

@@ -464,6 +464,55 @@ int adkf_gumbel_pool(const adkf_batch_t* b, const float* phi, int32_t flags, con
  * (ADKF_E_WORKSPACE); a scratch that is not 8-byte aligned. */
 int adkf_gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* ystar, int32_t S, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Knowledge-gradient selection over a shared pool (csrc/kg_stream.h; Frazier, Powell and Dayanik 2009; Scott, Frazier and Powell
+ * 2011, "KGCP"; the single-step form of BoTorch's qKnowledgeGradient on a discrete set): every row of the SAME pool X [rows, d] is
+ * scored, per task, by how much one noisy observation there is expected to raise the best posterior mean over the row itself and a
+ * reference set of at most ADKF_KG_REFS_MAX other pool rows.  It prices the observation noise, and needs neither an incumbent nor
+ * max-value samples.
+ *   The quantity.  m(.), cov(., .) the latent posterior of adkf_predict_pool, noise the task's, R_t = ref_idx[t, 0 .. M) the reference
+ *          rows.  For a pool row x: vc = max(v(x), 1e-12) (the clamp of EI), s = sqrt(vc + noise), sgn = +1 with ADKF_PM_MAXIMIZE and
+ *          -1 without (the slopes keep their sign, Z being symmetric), and
+ *              reference line j   a_j = sgn m(r_j),   b_j = cov(x, r_j) / s,
+ *              own line           a_x = sgn m(x),     b_x = vc / s,
+ *              KG(x) = E_Z[max_l (a_l + b_l Z)] - max_l a_l >= 0,   Z standard normal.
+ *          Reference entries outside [0, rows) are skipped, so a top_idx of adkf_predict_pool with its -1 tail can be passed as it
+ *          is; a repeated index counts once, its first occurrence being the one kept.  x always contributes its own line from its own
+ *          mean and variance, and a reference entry equal to x's own index is skipped for that row - exactly, by index, so no pair
+ *          of nearly coincident lines is ever created.
+ *          KG is evaluated in Frazier's form, a sum of non-negative terms over the lines of the upper envelope in ascending slope,
+ *              sum (b_next - b_cur) h(-|c|),   c = (a_cur - a_next) / (b_next - b_cur),   h(u) = phi(u) + u Phi(u);
+ *          E[max] is never formed and max a never subtracted.  With ADKF_PM_LOG_EI the score is log KG, the log-sum-exp of
+ *          log(b_next - b_cur) + log h(-|c|) with log h as log EI forms it: finite where KG underflows.  One surviving line gives
+ *          KG = 0 and log KG = -inf (a row that is the only valid reference entry of its task, for instance).  The set of lines
+ *          judged active may differ from the exact one only by lines whose interval is empty up to rounding; each crossing is
+ *          recomputed from the pair of consecutive active lines, so such a line changes the sum by rounding only.
+ *   b      support-only, of either kind, as for adkf_mes_pool; REUSE_DIST / REUSE_INNER and info as for adkf_predict_pool.
+ *   flags  ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI.
+ *   ref_idx   [T, M] pool row indices, 1 <= M <= ADKF_KG_REFS_MAX.
+ *   score  nullable, [T, rows]: KG or log KG.
+ *   cov    nullable, [T, rows, M] (task t, row r, entry j at (t * rows + r) * M + j): the latent posterior covariance of each row with
+ *          each reference entry, 0 for skipped entries (the own-index entry of a row is NOT skipped here: it holds v(x)).
+ *   ref_mean  nullable, [T, M]: the posterior mean of each reference entry in its natural sign, 0 for skipped entries.
+ *   k, top_idx, top_val, excl_idx, excl_off   the selection of adkf_predict_pool on the score: its unique order, its exclusion lists,
+ *          its -1 / -inf tail; a NaN score is never selected.
+ *   Tasks with n_s == 0 or info != 0: zero slices of score, cov and ref_mean, and a -1 / -inf selection.
+ *   Non-finite data.  A pool row whose own mean or variance is NaN scores NaN and is never selected.  A line whose covariance with the
+ *          row is NaN is left out of that row's envelope as a skipped entry is, and a NaN intercept does not move the interval of
+ *          another line: a reference row with NaN or infinite features (its w, mean and covariances are then NaN, and cov / ref_mean
+ *          report them) lowers no score to NaN - the other rows are scored without it.  Keep such rows out of ref_idx.
+ *   scratch   adkf_kg_pool_scratch_bytes(T, ns_max, d, M, k) bytes, 8-byte aligned: the reference state (w = A^-1 k(Z_s, r_j) [T, M,
+ *          ns_max], its float64 copy where the workspace has a float64 region, the stored rows [T, M, d], the means and the entries'
+ *          indices) and the candidate lists of adkf_predict_pool.  It depends on neither rows nor the device.
+ * Asynchronous on `stream`, no allocation, no synchronisation, no atomics: reproducible to the bit, and a task's score, cov, ref_mean
+ * and selection depend on that task's data, its reference rows, the pool and its exclusion list only - not on the grid or on the other
+ * tasks of the batch.  Rejected before anything is launched, ADKF_E_BADARG unless noted: M < 1, M > ADKF_KG_REFS_MAX or
+ * k > ADKF_POOL_TOPK_MAX (ADKF_E_SIZE); ref_idx == NULL; a batch with a query set; rows < 0; rows > 0 without X; any flag bit other
+ * than the two; k < 0; k > 0 without top_idx or top_val; excl_idx without excl_off; no output at all (k == 0 and score, cov and
+ * ref_mean all NULL); a scratch or a workspace that is too small (ADKF_E_WORKSPACE); a scratch that is not 8-byte aligned. */
+#define ADKF_KG_REFS_MAX 64
+size_t adkf_kg_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t M, int32_t k);
+int adkf_kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* ref_idx, int32_t M, const int64_t* excl_idx, const int64_t* excl_off, float* score, float* cov, float* ref_mean, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

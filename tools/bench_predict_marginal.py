@@ -52,7 +52,13 @@ rows, Matern, REUSE_INNER), timed alternately in this process (median of --reps 
 log EI, nothing per row) and with gp_ops.max_value_samples at S = 16, m = 1024 (w and eps already on the device).  The call is three
 walks of the pool, each with an epilogue of 64 evaluations per row like MES at S = 64.  The line holds the three times, both
 ratios, each series' spread (max - min) / median, the scratch bytes and the bit-equality of a repeated call.  No target.
-Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--mes] [--gibbon] [--gumbel] [--out FILE]"""
+--kg: knowledge-gradient selection (adkf_kg_pool, log KG, k = 8, nothing per row) on --mes's batch and pool (T=16 ns=128 d=256, 100 000
+rows, Matern, REUSE_INNER) with M = 32 and M = 64 reference rows (each task's rows of lowest posterior mean, taken once, outside the
+timing), timed alternately in this process (median of --reps single calls each) with adkf_predict_pool(k = 8, log EI, nothing per
+row) - the same walk without the reference panel and the envelope - and with adkf_believer_pool(q = 8, log EI), eight walks whose
+last carries a panel of 7 stored rows.  The line holds the four times, the ratios, each series' spread (max - min) / median, the
+scratch bytes and the bit-equality of a repeated call.  No target.
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--mes] [--gibbon] [--gumbel] [--kg] [--out FILE]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -484,6 +490,60 @@ def shape_gumbel(T, ns, d, rows, k, S, m, reps, dev, out_path=None):
     return rec
 
 
+def shape_kg(T, ns, d, rows, k, Ms, reps, dev, out_path=None):
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    b = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern")
+    phi0, _ = gp_ops.init_params_batch(b, True, True)
+    b.flags = gp_ops.REUSE_DIST
+    phi, _, _, _, info = gp_ops.fit(b, phi0, 200)
+    gp_ops.check_info(info)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    X = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):
+        X[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    best = ys.median(1).values.contiguous()
+    refs = {M: gp_ops.predict_pool(b, phi, X, topk=M, score="mean", want_mean=False, want_var=False, want_ei=False)["top_idx"] for M in Ms}
+    f_lei = lambda: gp_ops.predict_pool(b, phi, X, latent=True, best_f=best, want_mean=False, want_var=False, want_ei=False, topk=k, log_ei=True)
+    f_bv = lambda: gp_ops.believer_pool(b, phi, X, best_f=best, q=k, log_ei=True)
+    f_kg = {M: (lambda M=M: gp_ops.kg_pool(b, phi, X, ref_idx=refs[M], log=True, topk=k, want_score=False)) for M in Ms}
+    o1 = {M: f_kg[M]() for M in Ms}
+    o2 = {M: f_kg[M]() for M in Ms}
+    f_lei(); f_bv()
+    torch.cuda.synchronize()
+    for M in Ms:
+        gp_ops.check_info(o1[M]["info"])
+    ts = {"log_ei": [], "believer_log_ei": [], **{f"kg_M{M}": [] for M in Ms}}
+    for _ in range(reps):
+        ts["log_ei"].append(once(f_lei))
+        ts["believer_log_ei"].append(once(f_bv))
+        for M in Ms:
+            ts[f"kg_M{M}"].append(once(f_kg[M]))
+    med = {n: float(np.median(x)) for n, x in ts.items()}
+    lib = _lib.load()
+    rec = {"shape": f"kg T={T} ns={ns} d={d} rows={rows} k={k} log KG matern REUSE_INNER score=NULL; predict_pool k={k} log EI; believer q={k} log EI",
+           "refined_tasks": int(_refined(b).sum()), "float64_tasks": int((_scal(b)[:, 45] > 30.0).sum()),
+           "workspace_bytes": int(lib.adkf_workspace_bytes(T, ns, 0, d)),
+           "scratch_bytes": {str(M): int(lib.adkf_kg_pool_scratch_bytes(T, ns, d, M, k)) for M in Ms},
+           "predict_pool_log_ei_s": med["log_ei"], "believer_log_ei_s": med["believer_log_ei"],
+           "kg_s": {str(M): med[f"kg_M{M}"] for M in Ms},
+           "kg_over_log_ei": {str(M): med[f"kg_M{M}"] / med["log_ei"] for M in Ms},
+           "kg_over_believer": {str(M): med[f"kg_M{M}"] / med["believer_log_ei"] for M in Ms},
+           "spread_max_minus_min_over_median": {n: (max(x) - min(x)) / float(np.median(x)) for n, x in ts.items()},
+           "repeat_is_bit_equal": bool(all(torch.equal(o1[M]["top_idx"], o2[M]["top_idx"]) and
+                                           torch.equal(o1[M]["top_val"].view(torch.int32), o2[M]["top_val"].view(torch.int32)) for M in Ms)),
+           "all_selected": bool(all((o1[M]["top_idx"] >= 0).all() and torch.isfinite(o1[M]["top_val"]).all() for M in Ms)),
+           "all_s": ts}
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    return rec
+
+
 def shape_gibbon(T, ns, d, rows, q, S, reps, dev, out_path=None):
     g = torch.Generator(device=dev).manual_seed(0)
     W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
@@ -659,11 +719,15 @@ def main():
     ap.add_argument("--mes", action="store_true", help="adkf_mes_pool at S = 1, 16, 64 against adkf_predict_pool(k, log EI), timed alternately")
     ap.add_argument("--gibbon", action="store_true", help="adkf_gibbon_pool(q = 8, S = 16) against adkf_believer_pool(q = 8, log EI) and q calls of adkf_mes_pool(S = 16), timed alternately")
     ap.add_argument("--gumbel", action="store_true", help="adkf_gumbel_pool against adkf_predict_pool(k, log EI) and max_value_samples(S = 16, m = 1024), timed alternately")
-    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard), --mes, --gibbon, --gumbel: also write the JSON line to this file")
+    ap.add_argument("--kg", action="store_true", help="adkf_kg_pool(log KG, k = 8) at M = 32 and 64 against adkf_predict_pool(k, log EI) and adkf_believer_pool(q = 8, log EI), timed alternately")
+    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard), --mes, --gibbon, --gumbel, --kg: also write the JSON line to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.mes:
         shape_mes(16, 128, 256, 100000, 8, a.reps, dev, a.out)
+        return
+    if a.kg:
+        shape_kg(16, 128, 256, 100000, 8, (32, 64), a.reps, dev, a.out)
         return
     if a.gibbon:
         shape_gibbon(16, 128, 256, 100000, 8, 16, a.reps, dev, a.out)

@@ -1,0 +1,72 @@
+"""Bitwise comparison of the pool calls between two builds of the library (a refactoring must return the other build's bits).
+
+    python tools/pool_bits.py dump OUT.pt        in each of the two trees (each with its own built library), on the GPU
+    python tools/pool_bits.py compare A.pt B.pt  exit status 1 and the names of the arrays that differ, if any
+
+dump runs, on the problems of the GPU tests (tests/test_gpu_believer_pool._explicit: plain at 48 points, refined at 200, global slots
+at 1024; the ARD problem of tests/test_gpu_believer_pool_ard; tests/test_gpu_predict_pool._ill_batch, whose flagged tasks take the
+float64 walks): believer_pool with EI and with log EI and gibbon_pool, each with trace, predict_pool(log EI, k = 8), believer_pool_ard -
+and saves every returned tensor.  All lists are full (pools of 130 to 333 rows), so the arrays do not depend on how a short list is
+merged."""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def dump(path):
+    import torch
+
+    import test_gpu_believer_pool as BV
+    import test_gpu_believer_pool_ard as BVA
+    import test_gpu_predict_pool as P
+    from adkf_ift_amd import gp_ops
+
+    dev = torch.device("cuda:0")
+    out = {}
+
+    def put(tag, o):
+        for k, v in o.items():
+            if torch.is_tensor(v):
+                out[f"{tag}/{k}"] = v.cpu()
+
+    for kernel, n_s, d, rows, q in (("matern", [48, 45, 31], 16, 300, 8), ("rbf", [200, 197, 133], 64, 333, 8), ("matern", [1024, 700], 12, 130, 4)):
+        b, phi, Zs, ys, n_s, X, best = BV._explicit(dev, kernel, n_s, d, rows, 500 + max(n_s))
+        ystar = (ys.min(1).values[:, None] - torch.linspace(0.1, 1.0, 5)[None]).to(dev).contiguous()
+        for log in (False, True):
+            put(f"believer/{kernel}{max(n_s)}/log_ei={log}", gp_ops.believer_pool(b, phi, X, best_f=best.to(dev), q=q, log_ei=log, want_trace=True))
+        put(f"gibbon/{kernel}{max(n_s)}", gp_ops.gibbon_pool(b, phi, X, ystar=ystar, q=q, want_trace=True))
+        put(f"predict_pool/{kernel}{max(n_s)}", gp_ops.predict_pool(b, phi, X, best_f=best.to(dev), topk=8, log_ei=True))
+    b, phi, Zs, ys, n_s, X, best = BVA._explicit(dev, "matern", [48, 45, 31], 12, 300, 548)
+    put("believer_ard", gp_ops.believer_pool_ard(b, phi, X, best_f=best.to(dev), q=8, want_trace=True))
+    b, phi, Zs, ys, n_s, _ = P._ill_batch(dev)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    X = torch.cat([P._pool(300, 2, 3), b.Z_s[1, :5].cpu()]).to(dev)
+    best = torch.tensor([float(ys[t, :n_s[t]].median()) for t in range(len(n_s))], device=dev)
+    put("float64/believer", gp_ops.believer_pool(b, phi, X, best_f=best, q=6, want_trace=True))
+    put("float64/gibbon", gp_ops.gibbon_pool(b, phi, X, ystar=(best[:, None] - torch.tensor([[1.0, 2.0]], device=dev)).contiguous(), q=6, want_trace=True))
+    torch.save(out, path)
+    print("saved", len(out), "arrays to", path)
+
+
+def compare(pa, pb):
+    import torch
+
+    a, b = torch.load(pa), torch.load(pb)
+    if a.keys() != b.keys():
+        print("different sets of arrays:", sorted(set(a) ^ set(b)))
+        return 1
+    bad = [k for k in a if a[k].shape != b[k].shape or not torch.equal(a[k].contiguous().view(torch.uint8), b[k].contiguous().view(torch.uint8))]
+    print("arrays compared", len(a), "different", bad)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "dump":
+        dump(sys.argv[2])
+    elif len(sys.argv) == 4 and sys.argv[1] == "compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    else:
+        sys.exit(__doc__)
