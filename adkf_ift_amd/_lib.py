@@ -99,6 +99,10 @@ SIGNATURES = {
     "adkf_kg_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adkf_jes_pool_scratch_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "adkf_jes_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_outer_nll_value_grad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_ift_hypergrad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

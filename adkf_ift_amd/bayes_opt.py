@@ -16,6 +16,8 @@ and each function picks its own best candidate - a diverse batch of ``query_batc
 minima of pathwise posterior draws over the whole pool) and one ``adkf_mes_pool`` call per iteration, with no ``best_f`` in the score.
 ``run_gp_kg_bo_batched`` is the loop under the knowledge gradient for correlated beliefs: one batched fit, one mean top-``n_refs`` call
 for the reference rows and one ``adkf_kg_pool`` call (log KG) per iteration; it prices the observation noise and needs no ``best_f``.
+``run_gp_jes_bo_batched`` is the loop under joint entropy search: one batched fit, one ``gp_ops.optimum_samples`` call (the minima of
+pathwise posterior draws over the whole pool, location and value) and one ``adkf_jes_pool`` call per iteration.
 
 Only the Matern-5/2 branch exists here (the Tanimoto kernel of the reference's fingerprint baseline is not a
 distance-based kernel and is out of the library's scope).
@@ -336,7 +338,7 @@ def run_gp_ts_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
 
 
 def _take_picks(top_idx: torch.Tensor, usable: torch.Tensor, query_batch_size: int, rngs, queried, records, n: int) -> None:
-    """The end of an iteration of ``run_gp_mes_bo_batched`` and ``run_gp_kg_bo_batched``: replicate r takes the usable prefix of its
+    """The end of an iteration of ``run_gp_mes_bo_batched``, ``run_gp_kg_bo_batched`` and ``run_gp_jes_bo_batched``: replicate r takes the usable prefix of its
     candidates ``top_idx[r]`` (``usable[r]``: a prefix mask), fills a shortfall with random rows it has not queried, drawn from its own
     generator ``rngs[r]``, and adds the picks to ``queried[r]`` and ``records[r]`` (both updated in place)."""
     for r, rng in enumerate(rngs):
@@ -496,6 +498,77 @@ def run_gp_kg_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
         gp_ops.check_info(refs["info"], "BO posterior")
         out = gp_ops.kg_pool(b, phi, X, ref_idx=refs["top_idx"], maximize=False, log=True, topk=query_batch_size, exclude=queried,
                              want_score=False)
+        gp_ops.check_info(out["info"], "BO posterior")
+        top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
+        usable = torch.isfinite(top_val) & (top_idx >= 0)   # (a prefix of each row: descending scores, the -1 / -inf tail last)
+        _take_picks(top_idx, usable, query_batch_size, rngs, queried, records, n)
+    return records
+
+
+@torch.no_grad()
+def run_gp_jes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
+                          kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
+                          rngs: List[np.random.Generator], n_features: int = 1024, oversample: int = 4,
+                          feature_seed: int = 0, ard: bool = False, n_opt_samples: int = 16,
+                          cond_noise: float = 1e-6) -> List[List[int]]:
+    """``len(rngs)`` replicates of a joint entropy search BO loop (Hvarfner, Hutter & Nardi 2022) over the same pool at once
+    (minimisation, as ``run_gp_ei_bo``); returns their records: the best initial index, then the picks in descending score.  Per
+    iteration the replicates' queried sets are fitted by ONE ``gp_ops.fit`` (as ``run_gp_ei_bo_batched``), ONE
+    ``gp_ops.optimum_samples`` call draws ``n_opt_samples`` (at most 64) samples of each replicate's minimum over the WHOLE pool,
+    location and value together - the minima of pathwise posterior draws on a random-Fourier basis of ``n_features`` features (drawn
+    once from ``feature_seed``) - and ONE ``gp_ops.jes_pool(topk=query_batch_size, exclude=queried)`` call scores the pool
+    against them, conditioning on each sampled optimum under the noise variance ``cond_noise``, and returns each replicate's best rows
+    among those it has not queried.  The sampled value is NOT clamped to the best observation, as ``run_gp_mes_bo_batched`` clamps
+    it: location and value are one joint sample.  A returned candidate counts when its index is not -1 and its score is finite; a
+    shortfall is filled with random free rows from the replicate's generator, as in ``run_gp_mes_bo_batched``.  The prior weights and
+    noise draws of replicate r come from a torch generator seeded from ``rngs[r]``, exactly as ``run_gp_mes_bo_batched`` draws them,
+    the noise draws at the replicate's own support size: a replicate's record does not depend on which other replicates share the
+    batch.  ``oversample`` is accepted for the signature of ``run_gp_ts_bo_batched`` and not used.  ``ard``: as
+    ``run_gp_ts_bo_batched``; the same two calls serve ARD batches."""
+    R, n = len(rngs), x_all.shape[0]
+    if not 1 <= query_batch_size <= gp_ops._lib.POOL_TOPK_MAX:
+        raise ValueError(f"query_batch_size must be in [1, {gp_ops._lib.POOL_TOPK_MAX}], got {query_batch_size}")
+    S = int(n_opt_samples)
+    if not 1 <= S <= gp_ops._lib.TS_SAMPLES_MAX:
+        raise ValueError(f"n_opt_samples must be in [1, {gp_ops._lib.TS_SAMPLES_MAX}], got {n_opt_samples}")
+    if not 0.0 <= float(cond_noise) < float("inf"):
+        raise ValueError(f"cond_noise must be finite and >= 0, got {cond_noise}")
+    y_all = (y_all - y_all.mean()) / y_all.std()
+    X = x_all.detach().float().contiguous()
+    omega, phase = gp_ops.rff_basis(kernel_type, X.shape[1], n_features, generator=torch.Generator().manual_seed(int(feature_seed)),
+                                    device=X.device)
+    queried = [rng.choice(np.arange(init_from, n), size=num_init_points, replace=False).tolist() for rng in rngs]
+    records = [[min(q)] for q in queried]
+    gens = [torch.Generator().manual_seed(int(rng.integers(0, 2 ** 62))) for rng in rngs]
+
+    for _ in range(num_bo_iters):
+        sizes = [len(q) for q in queried]
+        ns = max(sizes)
+        Zs = torch.zeros(R, ns, X.shape[1], dtype=torch.float32, device=X.device)
+        ys = torch.zeros(R, ns, dtype=torch.float32, device=X.device)
+        w = torch.empty(R, S, n_features, dtype=torch.float32)
+        eps = torch.zeros(R, S, ns, dtype=torch.float32)
+        pri, phi0 = [], []
+        for r, q in enumerate(queried):
+            xq, yq = x_all[q], y_all[q]
+            _, model, mll = create_gp(xq, yq, kernel_type, device, noise_init, noise_prior)
+            Zs[r, :sizes[r]] = model.train_inputs[0].detach().float()
+            ys[r, :sizes[r]] = model.train_targets.detach().float()
+            pri.append(mll.priors_row(X.device))
+            p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
+            phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
+            w[r] = torch.randn(S, n_features, generator=gens[r])
+            eps[r, :, :sizes[r]] = torch.randn(S, sizes[r], generator=gens[r])
+        n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
+        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
+        phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
+        gp_ops.check_info(info, "run_gp_jes_bo_batched fit")
+        b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+        opt = gp_ops.optimum_samples(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w.to(X.device), eps=eps.to(X.device),
+                                     maximize=False)
+        gp_ops.check_info(opt["info"], "BO posterior")
+        out = gp_ops.jes_pool(b, phi, X, opt_idx=opt["opt_idx"], opt_val=opt["opt_val"], cond_noise=cond_noise, maximize=False,
+                              topk=query_batch_size, exclude=queried, want_score=False)
         gp_ops.check_info(out["info"], "BO posterior")
         top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
         usable = torch.isfinite(top_val) & (top_idx >= 0)   # (a prefix of each row: descending scores, the -1 / -inf tail last)

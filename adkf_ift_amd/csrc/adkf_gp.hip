@@ -30,6 +30,7 @@
 #include "gumbel_stream.h"
 #include "gibbon_stream.h"
 #include "kg_stream.h"
+#include "jes_stream.h"
 
 #include "host_common.h"
 #include "host_gp.h"
@@ -331,6 +332,19 @@ int adkf_kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const f
                  float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
     return kg_pool(b, phi, flags, X, rows, ref_idx, M, excl_idx, excl_off, score, cov, ref_mean, k, top_idx, top_val, info, ws, ws_bytes, scratch,
                    scratch_bytes, stream);
+}
+
+size_t adkf_jes_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t S, int32_t k) {
+    if (T <= 0 || ns_max <= 0 || ns_max > MAX_POINTS || d <= 0 || S < 1 || S > ADKF_TS_SAMPLES_MAX || k < 0 || k > ADKF_POOL_TOPK_MAX) return 0;
+    return jes_scratch(nullptr, T, ns_max, d, S, k).bytes;
+}
+
+int adkf_jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* opt_idx,
+                  const float* opt_val, int32_t S, float cond_noise, const int64_t* excl_idx, const int64_t* excl_off, float* score,
+                  float* opt_mean, float* opt_var, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes,
+                  void* scratch, size_t scratch_bytes, void* stream) {
+    return jes_pool(b, phi, flags, X, rows, opt_idx, opt_val, S, cond_noise, excl_idx, excl_off, score, opt_mean, opt_var, k, top_idx, top_val,
+                    info, ws, ws_bytes, scratch, scratch_bytes, stream);
 }
 
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

@@ -1253,6 +1253,104 @@ int adkf_kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const f
     return 0;
 }
 
+size_t adkf_jes_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t, int32_t) { return 0; }
+
+// Joint entropy search over a shared pool (include/adkf_gp.h): the mean, the latent variance and K A^-1 of every pool row once, the
+// covariance of every row with every valid sample's row from them (a repeated row is computed again: it counts again), then the S
+// terms per row in float64 (gibbon_term), rounded to float32 at the boundary; the selection ranks those float32 values under
+// adkf_predict_pool's total order.  ARD: as adkf_kg_pool.
+int adkf_jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* opt_idx,
+                  const float* opt_val, int32_t S, float cond_noise, const int64_t* excl_idx, const int64_t* excl_off, float* score,
+                  float* opt_mean, float* opt_var, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void*, size_t, void*, size_t,
+                  void*) {
+    if (int rc = check(b, false, true)) return rc;
+    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (!opt_idx || !opt_val) return ADKF_E_BADARG;
+    if (!(cond_noise >= 0.f) || !std::isfinite(cond_noise)) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (k < 0) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (k == 0 && !score && !opt_mean && !opt_var) return ADKF_E_BADARG;
+    if (S < 1 || S > ADKF_TS_SAMPLES_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    const bool ard = (b->flags & ADKF_BATCH_ARD) != 0, maximize = (flags & ADKF_PM_MAXIMIZE) != 0;
+    const int d = b->d;
+    const float ninf = -std::numeric_limits<float>::infinity(), fnan = std::numeric_limits<float>::quiet_NaN();
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        const size_t R = (size_t)rows, o = (size_t)t * R;
+        if (score) std::fill(score + o, score + o + R, 0.f);
+        if (opt_mean) std::fill(opt_mean + (size_t)t * S, opt_mean + (size_t)(t + 1) * S, 0.f);
+        if (opt_var) std::fill(opt_var + (size_t)t * S, opt_var + (size_t)(t + 1) * S, 0.f);
+        for (int q = 0; q < k; ++q) { top_idx[(size_t)t * k + q] = -1; top_val[(size_t)t * k + q] = ninf; }
+        const int n = std::min(ns_of(b, t), b->ns_max);
+        Mat Kr(R * std::max(n, 0)), Cr(R * std::max(n, 0)), mu(R), v(R);
+        double s = 0.0, noise = 0.0, il2 = 0.0;
+        const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
+            s = in.s; noise = in.noise; il2 = 1.0 / (in.l * in.l);
+            const float* y = b->y_s + (size_t)t * b->ns_max;
+            double* kr = &Kr[(size_t)r * n];
+            double* c = &Cr[(size_t)r * n];
+            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); kr[j] = in.s * k0; }
+            double m1 = 0.0, qf = 0.0;
+            for (int j = 0; j < n; ++j) {
+                double cj = 0.0;
+                for (int i = 0; i < n; ++i) cj += kr[i] * in.Ainv[(size_t)i * n + j];
+                c[j] = cj;
+                m1 += cj * (double)y[j];
+                qf += cj * kr[j];
+            }
+            mu[r] = m1; v[r] = in.s - qf;
+        });
+        if (!done) continue;
+        Mat Xl(ard ? R * d : 0);   // ARD: the pool rows over l
+        if (ard) {
+            const float* x0 = phi + (size_t)t * (2 + d);
+            for (size_t r = 0; r < R; ++r) for (int c = 0; c < d; ++c) Xl[r * d + c] = (double)X[r * d + c] / softplus(x0[2 + c]);
+        }
+        int s_eff = 0;
+        bool bad = false;
+        Mat sum(R, 0.0);
+        for (int j = 0; j < S; ++j) {
+            const int64_t p = opt_idx[(size_t)t * S + j];
+            if (p < 0 || p >= rows) continue;
+            ++s_eff;
+            const double fs = opt_val[(size_t)t * S + j];
+            if (!std::isfinite(fs)) bad = true;
+            if (opt_mean) opt_mean[(size_t)t * S + j] = (float)mu[p];
+            if (opt_var) opt_var[(size_t)t * S + j] = (float)v[p];
+            const double dd = std::max(v[p], 1e-12) + (double)cond_noise, gain = (fs - mu[p]) / dd;
+            const Mat Dp = ard ? sqdist(Xl.data() + (size_t)p * d, 1, Xl.data(), (int)rows, d) : sqdist(X + (size_t)p * d, 1, X, (int)rows, d);
+            for (size_t r = 0; r < R; ++r) {
+                double k0, k1, k2;
+                kappa(b->kernel, Dp[r] * il2, k0, k1, k2);
+                double c0 = s * k0;
+                for (int i = 0; i < n; ++i) c0 -= Kr[r * n + i] * Cr[(size_t)p * n + i];
+                const double vc = std::max(v[r], 1e-12), vs = std::max(v[r] - c0 * c0 / dd, 1e-12), ms = mu[r] + c0 * gain;
+                const double g = (maximize ? (fs - ms) : (ms - fs)) / std::sqrt(vs);
+                sum[r] += std::log((vc + noise) / (vs + noise)) - gibbon_term(g, vs / (vs + noise));
+            }
+        }
+        std::vector<float> sc(R);
+        for (size_t r = 0; r < R; ++r) {
+            const bool nan = s_eff == 0 || bad || mu[r] != mu[r] || v[r] != v[r];
+            sc[r] = nan ? fnan : (float)(0.5 * sum[r] / s_eff);
+            if (score) score[o + r] = sc[r];
+        }
+        if (k <= 0) continue;
+        std::vector<int64_t> cand;
+        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
+        for (int64_t r = 0; r < rows; ++r)
+            if (sc[r] == sc[r] && !(xb && std::binary_search(xb, xe, r))) cand.push_back(r);
+        const size_t kk = std::min<size_t>(k, cand.size());
+        std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return sc[a] > sc[c] || (sc[a] == sc[c] && a < c); });
+        for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)t * k + q] = cand[q]; top_val[(size_t)t * k + q] = sc[cand[q]]; }
+    }
+    return 0;
+}
+
 static int outer_common(const adkf_batch_t* b, const float* phi, int flags, bool with_hessian, float* f_out, float* g_phi, float* dZ_s, float* dZ_q,
                         float* v_out, float* H_out, int32_t* info) {
     const int d = b->d;

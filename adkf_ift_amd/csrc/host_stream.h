@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool and adkf_kg_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool and adkf_jes_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
 #pragma once
 #include "host_ard.h"
 
@@ -614,6 +614,89 @@ int kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float*
     v.W = l.W; v.W64 = have64 ? l.W64 : nullptr; v.Xp = l.Xp; v.am = l.am; v.ridx = l.ridx;
     v.score = score; v.cov = cov; v.ref_mean = ref_mean;
     return c.ard ? kg_launch<true>(c, pa, pool, v, rows, have64) : kg_launch<false>(c, pa, pool, v, rows, have64);
+}
+
+// adkf_jes_pool: the scratch is the knowledge gradient's reference state for M = S - w [T, S, ns] (and its float64 twin where a
+// workspace of this shape can have a float64 region), the entries' feature rows [T, S, d], their means and pool rows [T, S] - then the
+// entries' latent variance, 1 / d_s and gain [T, S] each, the task's scale [T], and prediction's candidate lists [T, chunks_max, k].
+// It does not depend on rows.
+struct JesScratch { float* W; double* W64; float* Xp; float *am, *ov, *invd, *gain, *scale; int64_t* ridx; int64_t* cand_idx; float* cand_val; size_t bytes; };
+inline JesScratch jes_scratch(void* base, int T, int ns, int d, int S, int k) {
+    Arena ar{static_cast<char*>(base), 0};
+    const size_t e = (size_t)T * S * ns, c = (size_t)T * pm_pool_chunks_max(T) * k;
+    JesScratch l{};
+    l.W = ar.floats(e);
+    l.W64 = ar.as<double>(ns <= R64_MAXN ? e : 0);
+    l.Xp = ar.floats((size_t)T * S * d);
+    l.am = ar.floats((size_t)T * S);
+    l.ridx = ar.as<int64_t>((size_t)T * S);
+    l.ov = ar.floats((size_t)T * S);
+    l.invd = ar.floats((size_t)T * S);
+    l.gain = ar.floats((size_t)T * S);
+    l.scale = ar.floats((size_t)T);
+    l.cand_idx = ar.as<int64_t>(c);
+    l.cand_val = ar.floats(c);
+    l.bytes = ar.off;
+    return l;
+}
+
+// The launches of a prepared joint-entropy-search call, as kg_launch: the reference state (one workgroup per sample and task), the
+// walks of prediction with JesEpilogue, the float64 walk, prediction's merge of the lists.
+template <bool ARD>
+int jes_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, const JesArgs& v, int64_t rows, bool have64) {
+    hipStream_t st = c.st;
+    const int T = c.b.T;
+    if constexpr (ARD) launch_ard_il(c);
+    const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
+    // every score starts at 0: the rows of skipped tasks (n_s == 0, info != 0) stay so
+    if (v.score && rows > 0) hipMemsetAsync(v.score, 0, sizeof(float) * (size_t)rows * T, st);
+    k_jes_refs<ARD><<<dim3(v.S, T), 256, 0, st>>>(pm_kargs<ARD, true, JesEpilogue>(c, pa, &pool, v));
+    int rc;
+    if (rows > 0) {
+        if ((rc = pm_launch_walk<false, ARD, true, JesEpilogue>(c, pa, &pool, v, tiles))) return rc;
+        if ((rc = pm_launch_walk<true, ARD, true, JesEpilogue>(c, pa, &pool, v, tiles))) return rc;
+    }
+    if (have64 && rows > 0) {
+        pool.grid[2] = std::min(pm64_grid(rows), pool.chunks_max);
+        k_jes_walk64<ARD><<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(pm_kargs<ARD, true, JesEpilogue>(c, pa, &pool, v));
+    }
+    if (pool.k > 0) k_pool_topk<<<T, 64, 0, st>>>(pm_kargs<false, true>(c, pa, &pool));
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_jes_pool: isotropic and ARD batches alike (as adkf_kg_pool)
+int jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* opt_idx, const float* opt_val,
+             int32_t S, float cond_noise, const int64_t* excl_idx, const int64_t* excl_off, float* score, float* opt_mean, float* opt_var,
+             int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes,
+             void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (!opt_idx || !opt_val) return ADKF_E_BADARG;
+    if (!(cond_noise >= 0.f && cond_noise < INFINITY)) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (k < 0) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (k == 0 && !score && !opt_mean && !opt_var) return ADKF_E_BADARG;
+    if (S < 1 || S > ADKF_TS_SAMPLES_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    const JesScratch l = jes_scratch(scratch, b->T, b->ns_max, b->d, S, k);
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    PmPool pool = pm_pool(excl_idx, excl_off, k, b->T, l.cand_idx, l.cand_val, rows, c.st);
+    pool.top_idx = top_idx; pool.top_val = top_val;
+    PmArgs pa = pm_args(c, flags, X, rows, info);
+    const bool have64 = c.w.w64 && b->ns_max <= R64_MAXN;
+    if (!have64) pa.r64_thresh = INFINITY;
+    JesArgs v{};
+    v.S = S; v.opt_idx = opt_idx; v.opt_val = opt_val; v.cond_noise = cond_noise;
+    v.W = l.W; v.W64 = have64 ? l.W64 : nullptr; v.Xp = l.Xp; v.am = l.am; v.ov = l.ov; v.invd = l.invd; v.gain = l.gain; v.ridx = l.ridx;
+    v.scale = l.scale;
+    v.score = score; v.opt_mean = opt_mean; v.opt_var = opt_var;
+    return c.ard ? jes_launch<true>(c, pa, pool, v, rows, have64) : jes_launch<false>(c, pa, pool, v, rows, have64);
 }
 
 // adkf_gumbel_pool: the scratch is the fixed-point sums [T, 64] (uint64), the probes [T, 64] (float32) and the images of the two

@@ -774,6 +774,83 @@ def max_value_samples(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: 
     return dict(ystar=ystar, info=out["info"], w=out["w"], eps=out["eps"])
 
 
+def optimum_samples(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: torch.Tensor, phase: torch.Tensor, n_samples: int,
+                    generator: Optional[torch.Generator] = None, w: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
+                    maximize: bool = False):
+    """``n_samples`` samples of each task's optimum over the pool ``X [rows, d]`` - its location AND its value, as ``jes_pool`` takes
+    them: the optima of pathwise posterior draws, from ONE ``thompson_pool`` (ARD batches: ``thompson_pool_ard``) call without
+    exclusions and without paths, with ``max_value_samples``' arguments.  Returns ``dict(opt_idx [T, S] int64, opt_val [T, S],
+    info [T], w, eps)``: ``opt_idx`` is the pool row at which draw s attains its optimum (-1 for a skipped task or an empty pool),
+    ``opt_val`` the value there in its natural sign - max f with ``maximize``, min f without (+-inf where ``opt_idx`` is -1) -
+    and ``w`` / ``eps`` the standard normal draws, given or drawn from ``generator`` as ``thompson_pool`` draws them."""
+    draw = thompson_pool_ard if b.ard else thompson_pool
+    out = draw(b, phi, X, omega=omega, phase=phase, n_samples=n_samples, generator=generator, w=w, eps=eps, maximize=maximize)
+    opt_val = out["sel_val"] if maximize else -out["sel_val"]
+    return dict(opt_idx=out["sel_idx"], opt_val=opt_val, info=out["info"], w=out["w"], eps=out["eps"])
+
+
+def jes_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, opt_idx: torch.Tensor, opt_val: torch.Tensor, cond_noise: float = 1e-6,
+             maximize: bool = False, topk: int = 0, exclude=None, want_score: Optional[bool] = None):
+    """Joint entropy search (Hvarfner, Hutter & Nardi 2022; BoTorch's ``qLowerBoundJointEntropySearch`` at q = 1) over the shared
+    pool ``X [rows, d]`` in one ``adkf_jes_pool`` call, for isotropic and ARD batches alike.  ``opt_idx [T, S]`` (int64 pool rows)
+    and ``opt_val [T, S]`` (S at most 64, both on the batch's device) hold samples of each task's optimum, location and value
+    together - of max f with ``maximize``, of min f without; ``optimum_samples`` draws them.  A row is scored by the entropy of the
+    noisy observation there minus the mean over the samples of its entropy given ``f(x*_s) = f*_s`` (under the noise variance
+    ``cond_noise``, finite and >= 0) and ``f <= f*_s``, moment-matched: non-negative, larger where observing the row says more about
+    the optimum; no ``best_f`` is involved.  Entries of ``opt_idx`` outside ``[0, rows)`` are skipped samples (``thompson_pool``'s
+    -1 can be passed as it is), a repeated row counts each time; with no valid sample, or a NaN or infinite ``opt_val`` on a valid
+    one, the scores of that task are NaN, which are never selected.  Returns ``dict(score, opt_mean, opt_var, top_idx, top_val,
+    info)``: ``score [T, rows]`` (``want_score``, which defaults to ``topk == 0``; else None), ``opt_mean [T, S]`` / ``opt_var`` the
+    posterior mean and latent variance at each sampled location (0 for skipped samples), ``top_idx [T, topk]`` (int64) /
+    ``top_val [T, topk]`` as ``predict_pool`` returns them (None with ``topk == 0``) and ``info [T]``.  ``exclude``: rows a task may
+    not select (``pack_exclude``); they are still scored."""
+    lib = _lib.load()
+    if b.nq != 0:
+        raise ValueError("jes_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    topk = int(topk)
+    if topk < 0 or topk > _lib.POOL_TOPK_MAX:
+        raise ValueError(f"topk must be in [0, {_lib.POOL_TOPK_MAX}], got {topk}")
+    if want_score is None:
+        want_score = topk == 0
+    if not torch.is_tensor(opt_idx) or opt_idx.dtype != torch.int64 or opt_idx.dim() != 2 or opt_idx.shape[0] != b.T:
+        raise ValueError(f"opt_idx must be an int64 tensor [T, S] = [{b.T}, S], got "
+                         f"{(tuple(opt_idx.shape), opt_idx.dtype) if torch.is_tensor(opt_idx) else opt_idx!r}")
+    S = opt_idx.shape[1]
+    if S < 1 or S > _lib.TS_SAMPLES_MAX:
+        raise ValueError(f"the number of optimum samples S must be in [1, {_lib.TS_SAMPLES_MAX}], got {S}")
+    if not torch.is_tensor(opt_val) or tuple(opt_val.shape) != (b.T, S):
+        raise ValueError(f"opt_val must be a tensor [T, S] = [{b.T}, {S}], got {tuple(opt_val.shape) if torch.is_tensor(opt_val) else opt_val!r}")
+    cond_noise = float(cond_noise)
+    if not (0.0 <= cond_noise < float("inf")):
+        raise ValueError(f"cond_noise must be finite and >= 0, got {cond_noise}")
+    opt_val = _f32(opt_val, "opt_val")
+    opt_idx = opt_idx.contiguous()
+    phi = b.check_phi(phi)
+    X = _f32(X, "X")
+    if X.dim() != 2 or X.shape[1] != b.d:
+        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    rows = X.shape[0]
+    for arg, t in (("X", X), ("opt_idx", opt_idx), ("opt_val", opt_val)):
+        if t.device != b.device:
+            raise ValueError(f"{arg} lives on {t.device}, the batch on {b.device}")
+    excl_idx = excl_off = None
+    if exclude is not None and topk > 0:
+        excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
+    score = _new(b, b.T, rows) if want_score else None
+    opt_mean, opt_var = _new(b, b.T, S), _new(b, b.T, S)
+    top_idx = _new(b, b.T, topk, dtype=torch.int64) if topk > 0 else None
+    top_val = _new(b, b.T, topk) if topk > 0 else None
+    info = _new(b, b.T, dtype=torch.int32)
+    sb = int(lib.adkf_jes_pool_scratch_bytes(b.T, b.ns, b.d, S, topk))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device)
+    ws, nb = b.workspace()
+    cb = b.c_struct()
+    _lib.check(lib.adkf_jes_pool(C.byref(cb), ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, ptr(X), rows, ptr(opt_idx), ptr(opt_val), S,
+                                 cond_noise, ptr(excl_idx), ptr(excl_off), ptr(score), ptr(opt_mean), ptr(opt_var), topk, ptr(top_idx),
+                                 ptr(top_val), ptr(info), ptr(ws), nb, ptr(scratch), sb, stream(b.device)), "adkf_jes_pool")
+    return dict(score=score, opt_mean=opt_mean, opt_var=opt_var, top_idx=top_idx, top_val=top_val, info=info)
+
+
 def gumbel_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, n_samples: Optional[int] = None, u: Optional[torch.Tensor] = None,
                 generator: Optional[torch.Generator] = None, maximize: bool = False):
     """Gumbel max-value sampling (Wang & Jegelka 2017, section 3.1; BoTorch's ``_sample_max_value_Gumbel``) over the shared pool

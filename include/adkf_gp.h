@@ -513,6 +513,54 @@ int adkf_gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, con
 size_t adkf_kg_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t M, int32_t k);
 int adkf_kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* ref_idx, int32_t M, const int64_t* excl_idx, const int64_t* excl_off, float* score, float* cov, float* ref_mean, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Joint entropy search over a shared pool (csrc/jes_stream.h; Hvarfner, Hutter and Nardi 2022; BoTorch's
+ * qLowerBoundJointEntropySearch at q = 1): every row of the SAME pool X [rows, d] is scored, per task, by the information one noisy
+ * observation there carries about the task's optimum - its LOCATION and VALUE together - given S samples of that pair.
+ * adkf_thompson_pool's sel_idx / sel_val are such samples and can be passed as they are (sel_val in its natural sign).
+ *   The quantity.  m(.), v(.), cov(., .) the latent posterior of adkf_predict_pool, noise the task's, (x*_s, f*_s) = (pool row
+ *          opt_idx[t, s], opt_val[t, s]) the samples; f*_s is a maximum with ADKF_PM_MAXIMIZE and a minimum without.  Per valid s:
+ *              d_s      = max(v(x*_s), 1e-12) + cond_noise,
+ *              c_s(x)   = cov(x, x*_s),
+ *              v_s(x)   = max(v(x) - c_s(x)^2 / d_s, 1e-12)           the latent variance given f(x*_s) = f*_s,
+ *              m_s(x)   = m(x) + c_s(x) (f*_s - m(x*_s)) / d_s,
+ *              gamma_s  = (f*_s - m_s) / sqrt(v_s) with ADKF_PM_MAXIMIZE, (m_s - f*_s) / sqrt(v_s) without,
+ *              rho2_s   = v_s / (v_s + noise),
+ *              term_s   = log((vc + noise) / (v_s + noise)) - log1p(-rho2_s h(gamma_s)),   vc = max(v(x), 1e-12),
+ *              score(x) = (1 / (2 S_eff)) sum over the valid s of term_s,
+ *          h(g) = tau (g + tau), tau = phi / Phi, formed as adkf_gibbon_pool forms it.  The score is the entropy of the noisy
+ *          observation at x minus the mean over the samples of its moment-matched entropy given the sample; both parts of every
+ *          term are >= 0, so score >= 0.  The S terms of a row are added in a fixed order.
+ *          An entry of opt_idx outside [0, rows) is a skipped sample (adkf_thompson_pool's -1 included) and S_eff counts the valid
+ *          ones.  A repeated row is NOT merged: two draws may share a location and differ in value, so each counts (unlike
+ *          adkf_kg_pool's first-occurrence rule).  S_eff == 0 makes every score of the task NaN, and nothing is selected.  A NaN or
+ *          infinite opt_val[t, s] on a valid entry makes every score of task t NaN (adkf_mes_pool's rule).  A pool row whose own mean
+ *          or variance is NaN scores NaN and is never selected.  Nothing is special, by index, at x = x*_s: the subtraction in v_s
+ *          cancels there, the clamp catches it, and the term stays well conditioned because rho2_s -> 0 damps whatever gamma_s
+ *          rounds to.
+ *          With every sample valid and cond_noise so large that c_s^2 / d_s and c_s (f*_s - m(x*_s)) / d_s round away, the score is
+ *          adkf_gibbon_pool's step-0 score a(x) for ystar = opt_val, bit for bit.
+ *   b      support-only, of either kind, as for adkf_mes_pool; REUSE_DIST / REUSE_INNER and info as for adkf_predict_pool.
+ *   flags  ADKF_PM_MAXIMIZE only.
+ *   opt_idx, opt_val   [T, S], required, 1 <= S <= ADKF_TS_SAMPLES_MAX.
+ *   cond_noise   the noise variance under which the optimum is conditioned on; finite and >= 0.
+ *   score  nullable, [T, rows].
+ *   opt_mean, opt_var  [T, S], each nullable: m(x*_s) and the unclamped latent v(x*_s), 0 for skipped samples.
+ *   k, top_idx, top_val, excl_idx, excl_off   the selection of adkf_predict_pool on the score: its unique order, its exclusion lists,
+ *          its -1 / -inf tail; a NaN score is never selected.
+ *   Tasks with n_s == 0 or info != 0: zero slices of score, opt_mean and opt_var, and a -1 / -inf selection.
+ *   scratch   adkf_jes_pool_scratch_bytes(T, ns_max, d, S, k) bytes, 8-byte aligned: adkf_kg_pool's reference state for M = S, the
+ *          entries' v(x*_s), 1 / d_s and (f*_s - m(x*_s)) / d_s [T, S] each, one scale per task and the candidate lists of
+ *          adkf_predict_pool.  It depends on neither rows nor the device.
+ * Asynchronous on `stream`, no allocation, no synchronisation, no atomics: reproducible to the bit, and a task's result depends on
+ * that task's data, its samples, the pool and its exclusion list only - not on the grid or on the other tasks of the batch.
+ * Rejected before anything is launched, ADKF_E_BADARG unless noted: S < 1, S > ADKF_TS_SAMPLES_MAX or k > ADKF_POOL_TOPK_MAX
+ * (ADKF_E_SIZE); opt_idx == NULL or opt_val == NULL; a negative, NaN or infinite cond_noise; a batch with a query set; rows < 0;
+ * rows > 0 without X; any flag bit other than ADKF_PM_MAXIMIZE; k < 0; k > 0 without top_idx or top_val; excl_idx without excl_off;
+ * no output at all (k == 0 and score, opt_mean and opt_var all NULL); a scratch or a workspace that is too small
+ * (ADKF_E_WORKSPACE); a scratch that is not 8-byte aligned. */
+size_t adkf_jes_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t S, int32_t k);
+int adkf_jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* opt_idx, const float* opt_val, int32_t S, float cond_noise, const int64_t* excl_idx, const int64_t* excl_off, float* score, float* opt_mean, float* opt_var, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

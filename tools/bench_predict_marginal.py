@@ -58,7 +58,13 @@ timing), timed alternately in this process (median of --reps single calls each) 
 row) - the same walk without the reference panel and the envelope - and with adkf_believer_pool(q = 8, log EI), eight walks whose
 last carries a panel of 7 stored rows.  The line holds the four times, the ratios, each series' spread (max - min) / median, the
 scratch bytes and the bit-equality of a repeated call.  No target.
-Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--mes] [--gibbon] [--gumbel] [--kg] [--out FILE]"""
+--jes: joint entropy search (adkf_jes_pool, k = 8, nothing per row) on --mes's batch and pool (T=16 ns=128 d=256, 100 000 rows, Matern,
+REUSE_INNER) with S = 16 and S = 64 optimum samples (one gp_ops.optimum_samples call per S at m = 1024, outside the timing), timed
+alternately in this process (median of --reps single calls each) with adkf_kg_pool(log KG, k = 8) at M = S on the same rows - the same
+reference panel followed by the envelope where JES makes S evaluations - with adkf_mes_pool(k = 8) on the same values - the same S
+evaluations without the panel - and with adkf_predict_pool(k = 8, log EI, nothing per row).  The line holds the times, the ratios, each
+series' spread (max - min) / median, the scratch bytes and the bit-equality of a repeated call.  No target.
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--mes] [--gibbon] [--gumbel] [--kg] [--jes] [--out FILE]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -544,6 +550,71 @@ def shape_kg(T, ns, d, rows, k, Ms, reps, dev, out_path=None):
     return rec
 
 
+def shape_jes(T, ns, d, rows, k, Ss, m, reps, dev, out_path=None):
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    b = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern")
+    phi0, _ = gp_ops.init_params_batch(b, True, True)
+    b.flags = gp_ops.REUSE_DIST
+    phi, _, _, _, info = gp_ops.fit(b, phi0, 200)
+    gp_ops.check_info(info)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    X = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):
+        X[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    best = ys.median(1).values.contiguous()
+    omega, phase = gp_ops.rff_basis("matern", d, m, generator=torch.Generator().manual_seed(0), device=dev)
+    opt = {}
+    for S in Ss:
+        w, eps = torch.randn(T, S, m, device=dev, generator=g), torch.randn(T, S, ns, device=dev, generator=g)
+        opt[S] = gp_ops.optimum_samples(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w, eps=eps)
+        gp_ops.check_info(opt[S]["info"])
+    f_lei = lambda: gp_ops.predict_pool(b, phi, X, latent=True, best_f=best, want_mean=False, want_var=False, want_ei=False, topk=k, log_ei=True)
+    f_jes = {S: (lambda S=S: gp_ops.jes_pool(b, phi, X, opt_idx=opt[S]["opt_idx"], opt_val=opt[S]["opt_val"], topk=k, want_score=False)) for S in Ss}
+    f_kg = {S: (lambda S=S: gp_ops.kg_pool(b, phi, X, ref_idx=opt[S]["opt_idx"], log=True, topk=k, want_score=False)) for S in Ss}
+    f_mes = {S: (lambda S=S: gp_ops.mes_pool(b, phi, X, ystar=opt[S]["opt_val"], topk=k, want_score=False)) for S in Ss}
+    o1 = {S: f_jes[S]() for S in Ss}
+    o2 = {S: f_jes[S]() for S in Ss}
+    f_lei()
+    for S in Ss:
+        f_kg[S](); f_mes[S]()
+    torch.cuda.synchronize()
+    for S in Ss:
+        gp_ops.check_info(o1[S]["info"])
+    ts = {"log_ei": [], **{f"{n}_S{S}": [] for S in Ss for n in ("jes", "kg", "mes")}}
+    for _ in range(reps):
+        ts["log_ei"].append(once(f_lei))
+        for S in Ss:
+            ts[f"jes_S{S}"].append(once(f_jes[S]))
+            ts[f"kg_S{S}"].append(once(f_kg[S]))
+            ts[f"mes_S{S}"].append(once(f_mes[S]))
+    med = {n: float(np.median(x)) for n, x in ts.items()}
+    lib = _lib.load()
+    rec = {"shape": f"jes T={T} ns={ns} d={d} rows={rows} k={k} matern REUSE_INNER score=NULL cond_noise=1e-6; kg log KG M=S on opt_idx; mes on opt_val; predict_pool k={k} log EI",
+           "refined_tasks": int(_refined(b).sum()), "float64_tasks": int((_scal(b)[:, 45] > 30.0).sum()),
+           "workspace_bytes": int(lib.adkf_workspace_bytes(T, ns, 0, d)),
+           "scratch_bytes": {str(S): int(lib.adkf_jes_pool_scratch_bytes(T, ns, d, S, k)) for S in Ss},
+           "distinct_locations_per_task_min": {str(S): int(min(len(set(r)) for r in opt[S]["opt_idx"].cpu().tolist())) for S in Ss},
+           "predict_pool_log_ei_s": med["log_ei"],
+           "jes_s": {str(S): med[f"jes_S{S}"] for S in Ss}, "kg_s": {str(S): med[f"kg_S{S}"] for S in Ss}, "mes_s": {str(S): med[f"mes_S{S}"] for S in Ss},
+           "jes_over_kg": {str(S): med[f"jes_S{S}"] / med[f"kg_S{S}"] for S in Ss},
+           "jes_over_mes": {str(S): med[f"jes_S{S}"] / med[f"mes_S{S}"] for S in Ss},
+           "jes_over_log_ei": {str(S): med[f"jes_S{S}"] / med["log_ei"] for S in Ss},
+           "spread_max_minus_min_over_median": {n: (max(x) - min(x)) / float(np.median(x)) for n, x in ts.items()},
+           "repeat_is_bit_equal": bool(all(torch.equal(o1[S]["top_idx"], o2[S]["top_idx"]) and
+                                           torch.equal(o1[S]["top_val"].view(torch.int32), o2[S]["top_val"].view(torch.int32)) for S in Ss)),
+           "all_selected": bool(all((o1[S]["top_idx"] >= 0).all() and torch.isfinite(o1[S]["top_val"]).all() for S in Ss)),
+           "all_s": ts}
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    return rec
+
+
 def shape_gibbon(T, ns, d, rows, q, S, reps, dev, out_path=None):
     g = torch.Generator(device=dev).manual_seed(0)
     W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
@@ -720,7 +791,8 @@ def main():
     ap.add_argument("--gibbon", action="store_true", help="adkf_gibbon_pool(q = 8, S = 16) against adkf_believer_pool(q = 8, log EI) and q calls of adkf_mes_pool(S = 16), timed alternately")
     ap.add_argument("--gumbel", action="store_true", help="adkf_gumbel_pool against adkf_predict_pool(k, log EI) and max_value_samples(S = 16, m = 1024), timed alternately")
     ap.add_argument("--kg", action="store_true", help="adkf_kg_pool(log KG, k = 8) at M = 32 and 64 against adkf_predict_pool(k, log EI) and adkf_believer_pool(q = 8, log EI), timed alternately")
-    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard), --mes, --gibbon, --gumbel, --kg: also write the JSON line to this file")
+    ap.add_argument("--jes", action="store_true", help="adkf_jes_pool(k = 8) at S = 16 and 64 against adkf_kg_pool(log KG, k = 8) at M = S, adkf_mes_pool(k = 8) and adkf_predict_pool(k, log EI), timed alternately")
+    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard), --mes, --gibbon, --gumbel, --kg, --jes: also write the JSON line to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.mes:
@@ -728,6 +800,9 @@ def main():
         return
     if a.kg:
         shape_kg(16, 128, 256, 100000, 8, (32, 64), a.reps, dev, a.out)
+        return
+    if a.jes:
+        shape_jes(16, 128, 256, 100000, 8, (16, 64), 1024, a.reps, dev, a.out)
         return
     if a.gibbon:
         shape_gibbon(16, 128, 256, 100000, 8, 16, a.reps, dev, a.out)

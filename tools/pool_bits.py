@@ -5,8 +5,9 @@
 
 dump runs, on the problems of the GPU tests (tests/test_gpu_believer_pool._explicit: plain at 48 points, refined at 200, global slots
 at 1024; the ARD problem of tests/test_gpu_believer_pool_ard; tests/test_gpu_predict_pool._ill_batch, whose flagged tasks take the
-float64 walks): believer_pool with EI and with log EI and gibbon_pool, each with trace, predict_pool(log EI, k = 8), believer_pool_ard -
-and saves every returned tensor.  All lists are full (pools of 130 to 333 rows), so the arrays do not depend on how a short list is
+float64 walks): believer_pool with EI and with log EI and gibbon_pool, each with trace, predict_pool(log EI, k = 8), believer_pool_ard,
+kg_pool with KG and with log KG (score, cov, ref_mean and the selection; M = 16 reference rows of lowest posterior mean, a -1 and a
+repetition among them) - and saves every returned tensor.  All lists are full (pools of 130 to 333 rows), so the arrays do not depend on how a short list is
 merged."""
 import os
 import sys
@@ -32,6 +33,12 @@ def dump(path):
             if torch.is_tensor(v):
                 out[f"{tag}/{k}"] = v.cpu()
 
+    def kg_refs(b, phi, X):
+        refs = gp_ops.predict_pool(b, phi, X, topk=16, score="mean", want_mean=False, want_var=False, want_ei=False)["top_idx"].clone()
+        refs[:, 4] = -1
+        refs[:, 5] = refs[:, 0]
+        return refs
+
     for kernel, n_s, d, rows, q in (("matern", [48, 45, 31], 16, 300, 8), ("rbf", [200, 197, 133], 64, 333, 8), ("matern", [1024, 700], 12, 130, 4)):
         b, phi, Zs, ys, n_s, X, best = BV._explicit(dev, kernel, n_s, d, rows, 500 + max(n_s))
         ystar = (ys.min(1).values[:, None] - torch.linspace(0.1, 1.0, 5)[None]).to(dev).contiguous()
@@ -39,13 +46,19 @@ def dump(path):
             put(f"believer/{kernel}{max(n_s)}/log_ei={log}", gp_ops.believer_pool(b, phi, X, best_f=best.to(dev), q=q, log_ei=log, want_trace=True))
         put(f"gibbon/{kernel}{max(n_s)}", gp_ops.gibbon_pool(b, phi, X, ystar=ystar, q=q, want_trace=True))
         put(f"predict_pool/{kernel}{max(n_s)}", gp_ops.predict_pool(b, phi, X, best_f=best.to(dev), topk=8, log_ei=True))
+        refs = kg_refs(b, phi, X)
+        for log in (False, True):
+            put(f"kg/{kernel}{max(n_s)}/log={log}", gp_ops.kg_pool(b, phi, X, ref_idx=refs, log=log, topk=8, want_cov=True))
     b, phi, Zs, ys, n_s, X, best = BVA._explicit(dev, "matern", [48, 45, 31], 12, 300, 548)
     put("believer_ard", gp_ops.believer_pool_ard(b, phi, X, best_f=best.to(dev), q=8, want_trace=True))
+    put("kg_ard", gp_ops.kg_pool(b, phi, X, ref_idx=kg_refs(b, phi, X), log=True, topk=8, want_cov=True))
     b, phi, Zs, ys, n_s, _ = P._ill_batch(dev)
     b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
     X = torch.cat([P._pool(300, 2, 3), b.Z_s[1, :5].cpu()]).to(dev)
     best = torch.tensor([float(ys[t, :n_s[t]].median()) for t in range(len(n_s))], device=dev)
     put("float64/believer", gp_ops.believer_pool(b, phi, X, best_f=best, q=6, want_trace=True))
+    for log in (False, True):
+        put(f"float64/kg/log={log}", gp_ops.kg_pool(b, phi, X, ref_idx=kg_refs(b, phi, X), log=log, topk=8, want_cov=True))
     put("float64/gibbon", gp_ops.gibbon_pool(b, phi, X, ystar=(best[:, None] - torch.tensor([[1.0, 2.0]], device=dev)).contiguous(), q=6, want_trace=True))
     torch.save(out, path)
     print("saved", len(out), "arrays to", path)
