@@ -574,3 +574,105 @@ def run_gp_jes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
         usable = torch.isfinite(top_val) & (top_idx >= 0)   # (a prefix of each row: descending scores, the -1 / -inf tail last)
         _take_picks(top_idx, usable, query_batch_size, rngs, queried, records, n)
     return records
+
+
+def _hypervolume_2d(Y: torch.Tensor, maximize, ref: torch.Tensor) -> float:
+    """The area dominated by the points ``Y [n, 2]`` and bounded by ``ref``, on the host (``gp_ops.pareto_front``'s staircase)."""
+    sg = torch.tensor([-1.0 if m else 1.0 for m in maximize], dtype=torch.float64)
+    st = gp_ops.pareto_front(Y.double().cpu(), maximize, ref.double().cpu()) * sg
+    r = ref.double().cpu() * sg
+    hv, right = 0.0, float(r[0])
+    for i in range(st.shape[0] - 1, -1, -1):   # from the worst first coordinate to the best: one rectangle per step
+        hv += (right - float(st[i, 0])) * (float(r[1]) - float(st[i, 1]))
+        right = float(st[i, 0])
+    return hv
+
+
+def _ehvi_ref_point(Y: torch.Tensor, maximize) -> torch.Tensor:
+    """The worst queried value per objective plus 0.1 of the queried range (BoTorch's heuristic).  An objective whose queried values
+    are all equal has no range: the margin is then 0.1 (of the unit variance the columns are standardised to), so that the reference
+    point never lies ON the queried points - which would clean the whole front away."""
+    lo, hi = Y.min(0).values, Y.max(0).values
+    mx = torch.tensor([bool(m) for m in maximize], device=Y.device)
+    margin = 0.1 * torch.where(hi > lo, hi - lo, torch.ones_like(hi))
+    return torch.where(mx, lo - margin, hi + margin)
+
+
+@torch.no_grad()
+def run_gp_ehvi_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
+                           kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
+                           rngs: List[np.random.Generator], maximize=(False, False), acquisition: str = "log_ehvi",
+                           ard: bool = False):
+    """``len(rngs)`` replicates of a two-objective BO loop by expected hypervolume improvement over the same pool at once; ``y_all``
+    is ``[n, 2]``, ``maximize`` the sense per objective.  R replicates make 2 R tasks in ONE batch - task 2 r + j is objective j of
+    replicate r - and group r = (2 r, 2 r + 1).  Per iteration the queried sets are fitted by ONE ``gp_ops.fit`` and ONE
+    ``gp_ops.ehvi_pool(topk=query_batch_size, exclude=queried)`` call scores the pool for every replicate against the front of its
+    own queried values (``gp_ops.pareto_front``) and its reference point - the worst queried value per objective plus 0.1 of the
+    queried range (0.1 where the range is 0), recomputed every iteration - and returns its best rows among those it has not queried.
+    A replicate whose queried values have more than 64 non-dominated points is beyond ``ehvi_pool``'s front and raises.  Each column
+    of ``y_all`` is standardised once.  ``acquisition``: ``"log_ehvi"`` (a candidate counts when its index is not -1 and its score is finite) or
+    ``"ehvi"`` (when its score is positive); a shortfall is filled with random free rows from the replicate's generator, as in
+    ``run_gp_mes_bo_batched``.  Returns ``(records, hypervolume)``: per replicate the initial indices followed by the picks in
+    descending score, and the dominated hypervolume of its queried values (standardised units) after the initial design and after
+    every iteration, all against the FINAL reference point - computed on the host."""
+    R, n = len(rngs), x_all.shape[0]
+    if not 1 <= query_batch_size <= gp_ops._lib.POOL_TOPK_MAX:
+        raise ValueError(f"query_batch_size must be in [1, {gp_ops._lib.POOL_TOPK_MAX}], got {query_batch_size}")
+    if y_all.dim() != 2 or tuple(y_all.shape) != (n, 2):
+        raise ValueError(f"y_all must be [n, 2] = [{n}, 2], got {tuple(y_all.shape)}")
+    if acquisition not in ("log_ehvi", "ehvi"):
+        raise ValueError(f"acquisition must be 'log_ehvi' or 'ehvi', got {acquisition!r}")
+    log = acquisition == "log_ehvi"
+    maximize = tuple(bool(m) for m in maximize)
+    y_all = (y_all - y_all.mean(0)) / y_all.std(0)
+    X = x_all.detach().float().contiguous()
+    queried = [rng.choice(np.arange(init_from, n), size=num_init_points, replace=False).tolist() for rng in rngs]
+    records = [list(q) for q in queried]
+    history = [[list(q)] for q in queried]
+    obj = torch.tensor([[2 * r, 2 * r + 1] for r in range(R)], dtype=torch.int32)
+    obj_max = torch.tensor([[int(maximize[0]), int(maximize[1])]] * R, dtype=torch.int32)
+
+    for _ in range(num_bo_iters):
+        sizes = [len(q) for q in queried for _ in range(2)]
+        ns = max(sizes)
+        Zs = torch.zeros(2 * R, ns, X.shape[1], dtype=torch.float32, device=X.device)
+        ys = torch.zeros(2 * R, ns, dtype=torch.float32, device=X.device)
+        pri, phi0, fronts, refs = [], [], [], []
+        for r, q in enumerate(queried):
+            for j in range(2):
+                t = 2 * r + j
+                _, model, mll = create_gp(x_all[q], y_all[q, j], kernel_type, device, noise_init, noise_prior)
+                Zs[t, :sizes[t]] = model.train_inputs[0].detach().float()
+                ys[t, :sizes[t]] = model.train_targets.detach().float()
+                pri.append(mll.priors_row(X.device))
+                p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
+                phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
+            Yq = y_all[q].float()
+            refs.append(_ehvi_ref_point(Yq, maximize))
+            fronts.append(gp_ops.pareto_front(Yq.cpu(), maximize))
+            if fronts[-1].shape[0] > gp_ops._lib.EHVI_FRONT_MAX:   # (a truncated front would overstate every improvement)
+                raise ValueError(f"replicate {r} has {fronts[-1].shape[0]} non-dominated queried points; ehvi_pool takes a front of at most "
+                                 f"{gp_ops._lib.EHVI_FRONT_MAX}")
+        P = max(1, max(f.shape[0] for f in fronts))
+        front = torch.zeros(R, P, 2)
+        for r, f in enumerate(fronts):
+            front[r, :f.shape[0]] = f
+        front_n = torch.tensor([f.shape[0] for f in fronts], dtype=torch.int32)
+        n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
+        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
+        phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
+        gp_ops.check_info(info, "run_gp_ehvi_bo_batched fit")
+        b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+        out = gp_ops.ehvi_pool(b, phi, X, obj=obj, ref=torch.stack(refs).cpu(), front=front, front_n=front_n, obj_maximize=obj_max, log=log,
+                               topk=query_batch_size, exclude=queried, want_score=False)
+        gp_ops.check_info(out["info"], "BO posterior")
+        top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
+        usable = (torch.isfinite(top_val) if log else top_val > 0) & (top_idx >= 0)   # (a prefix of each row)
+        _take_picks(top_idx, usable, query_batch_size, rngs, queried, records, n)
+        for r in range(R):
+            history[r].append(list(records[r]))
+    hypervolume = []
+    for r in range(R):
+        ref = _ehvi_ref_point(y_all[records[r]].float(), maximize)
+        hypervolume.append([_hypervolume_2d(y_all[q].float(), maximize, ref) for q in history[r]])
+    return records, hypervolume

@@ -31,6 +31,7 @@
 #include "gibbon_stream.h"
 #include "kg_stream.h"
 #include "jes_stream.h"
+#include "ehvi_stream.h"
 
 #include "host_common.h"
 #include "host_gp.h"
@@ -345,6 +346,20 @@ int adkf_jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
                   void* scratch, size_t scratch_bytes, void* stream) {
     return jes_pool(b, phi, flags, X, rows, opt_idx, opt_val, S, cond_noise, excl_idx, excl_off, score, opt_mean, opt_var, k, top_idx, top_val,
                     info, ws, ws_bytes, scratch, scratch_bytes, stream);
+}
+
+size_t adkf_ehvi_pool_scratch_bytes(int32_t T, int32_t G, int32_t k) {
+    if (T <= 0 || G < 1 || k < 0 || k > ADKF_POOL_TOPK_MAX) return 0;
+    return ehvi_scratch(nullptr, T, G, k).bytes;
+}
+
+int adkf_ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, int32_t G, const int32_t* obj,
+                   const int32_t* obj_max, const float* ref, const float* front, const int32_t* front_n, int32_t P, const int32_t* con,
+                   const float* con_thr, const int32_t* con_geq, int32_t C, const int64_t* excl_idx, const int64_t* excl_off, float* score,
+                   float* stair, int32_t* stair_n, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes,
+                   void* scratch, size_t scratch_bytes, void* stream) {
+    return ehvi_pool(b, phi, flags, X, rows, G, obj, obj_max, ref, front, front_n, P, con, con_thr, con_geq, C, excl_idx, excl_off, score,
+                     stair, stair_n, k, top_idx, top_val, info, ws, ws_bytes, scratch, scratch_bytes, stream);
 }
 
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

@@ -1351,6 +1351,171 @@ int adkf_jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
     return 0;
 }
 
+size_t adkf_ehvi_pool_scratch_bytes(int32_t, int32_t, int32_t) { return 0; }
+
+// log(1 - exp(d)), d < 0
+static double log1mexp(double d) { return d > -M_LN2 ? std::log(-std::expm1(d)) : std::log1p(-std::exp(d)); }
+
+// log Phi(z): log1p where Phi -> 1, through erfc down to z = -30, Mills' ratio below
+static double log_cdf(double z) {
+    if (z > 0.0) return std::log1p(-0.5 * std::erfc(z / std::sqrt(2.0)));
+    if (z > -30.0) return std::log(0.5 * std::erfc(-z / std::sqrt(2.0)));
+    const double w = 1.0 / (z * z);
+    return -0.5 * z * z - std::log(-z) - 0.5 * std::log(2.0 * M_PI) + std::log1p(w * (-1.0 + w * (3.0 - 15.0 * w)));
+}
+
+// Constrained expected hypervolume improvement across tasks over a shared pool (include/adkf_gp.h): the mean and the latent variance
+// of every task at every pool row first, then per group the staircase (the device's cleaning rule, on the float32 values) and the score
+// in float64 - the log form in log space throughout - rounded to float32 at the boundary; the selection ranks those float32 values
+// under adkf_predict_pool's total order.
+int adkf_ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, int32_t G, const int32_t* obj,
+                   const int32_t* obj_max, const float* ref, const float* front, const int32_t* front_n, int32_t P, const int32_t* con,
+                   const float* con_thr, const int32_t* con_geq, int32_t C, const int64_t* excl_idx, const int64_t* excl_off, float* score,
+                   float* stair, int32_t* stair_n, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void*, size_t, void*, size_t,
+                   void*) {
+    if (int rc = check(b, false, true)) return rc;
+    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (flags & ~ADKF_PM_LOG_EI) return ADKF_E_BADARG;
+    if (G < 1 || k < 0) return ADKF_E_BADARG;
+    if (P < 0 || P > ADKF_EHVI_FRONT_MAX || C < 0 || C > ADKF_EHVI_CONS_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    if (!obj || !ref || !front_n) return ADKF_E_BADARG;
+    if (P > 0 && !front) return ADKF_E_BADARG;
+    if (C > 0 && (!con || !con_thr || !con_geq)) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (k == 0 && !score && !stair && !stair_n) return ADKF_E_BADARG;
+    const bool want_log = (flags & ADKF_PM_LOG_EI) != 0;
+    const int T = b->T;
+    const size_t R = (size_t)rows;
+    const float ninf = -std::numeric_limits<float>::infinity(), fnan = std::numeric_limits<float>::quiet_NaN();
+    const double dinf = std::numeric_limits<double>::infinity();
+    Mat mu((size_t)T * R), vl((size_t)T * R);
+    std::vector<char> done(T, 0);
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < T; ++t) {
+        const float* y = b->y_s + (size_t)t * b->ns_max;
+        done[t] = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
+            const int n = in.n;
+            const double il2 = 1.0 / (in.l * in.l);
+            std::vector<double> kr(n);
+            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); kr[j] = in.s * k0; }
+            double m1 = 0.0, q = 0.0;
+            for (int j = 0; j < n; ++j) {
+                double cj = 0.0;
+                for (int i = 0; i < n; ++i) cj += kr[i] * in.Ainv[(size_t)i * n + j];
+                m1 += cj * (double)y[j];
+                q += cj * kr[j];
+            }
+            mu[(size_t)t * R + r] = m1; vl[(size_t)t * R + r] = in.s - q;
+        }) ? 1 : 0;
+    }
+    auto psi = [&](double m, double s, double c, bool lg) {
+        if (c == -dinf) return lg ? -dinf : 0.0;
+        const double z = (c - m) / s;
+        if (lg) return std::log(s) + log_h(z);
+        return s * (z * 0.5 * std::erfc(-z / std::sqrt(2.0)) + std::exp(-0.5 * z * z) / std::sqrt(2.0 * M_PI));
+    };
+#pragma omp parallel for schedule(dynamic)
+    for (int g = 0; g < G; ++g) {
+        const int o1 = obj[2 * g], o2 = obj[2 * g + 1];
+        const bool two = o2 != -1;
+        bool bad = o1 < 0 || o1 >= T || (two && (o2 < 0 || o2 >= T || o2 == o1));
+        const float sg1 = (obj_max && obj_max[2 * g]) ? -1.f : 1.f, sg2 = (obj_max && obj_max[2 * g + 1]) ? -1.f : 1.f;
+        const float r1 = sg1 * ref[2 * g], r2 = two ? sg2 * ref[2 * g + 1] : 0.f;
+        bad = bad || r1 != r1 || r2 != r2;
+        if (!bad) bad = !done[o1] || (two && !done[o2]);
+        int ct[ADKF_EHVI_CONS_MAX];
+        for (int c = 0; c < ADKF_EHVI_CONS_MAX; ++c) {
+            ct[c] = c < C ? con[(size_t)g * C + c] : -1;
+            if (ct[c] == -1) continue;
+            if (ct[c] < 0 || ct[c] >= T) { bad = true; ct[c] = -1; continue; }
+            const float thr = con_thr[(size_t)g * C + c];
+            if (thr != thr || !done[ct[c]]) bad = true;
+        }
+        // the staircase
+        int n = two ? front_n[g] : 0;
+        n = std::min(std::max(n, 0), (int)P);
+        std::vector<float> fa(n), fb(n);
+        std::vector<char> keep(n);
+        for (int i = 0; i < n; ++i) {
+            fa[i] = sg1 * front[((size_t)g * P + i) * 2]; fb[i] = sg2 * front[((size_t)g * P + i) * 2 + 1];
+            keep[i] = fa[i] == fa[i] && fb[i] == fb[i] && fa[i] < r1 && fb[i] < r2;
+        }
+        const std::vector<char> valid = keep;
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n && keep[i]; ++j)
+                if (valid[j] && j != i && fa[j] <= fa[i] && fb[j] <= fb[i] && (fa[j] < fa[i] || fb[j] < fb[i] || j < i)) keep[i] = 0;
+        std::vector<std::pair<float, float>> st;
+        for (int i = 0; i < n; ++i) if (keep[i]) st.emplace_back(fa[i], fb[i]);
+        std::sort(st.begin(), st.end());
+        const int Pg = (int)st.size();
+        if (stair_n) stair_n[g] = Pg;
+        if (stair)
+            for (int i = 0; i < P; ++i) {
+                stair[((size_t)g * P + i) * 2] = i < Pg ? sg1 * st[i].first : 0.f;
+                stair[((size_t)g * P + i) * 2 + 1] = i < Pg ? sg2 * st[i].second : 0.f;
+            }
+        for (int q = 0; q < k; ++q) { top_idx[(size_t)g * k + q] = -1; top_val[(size_t)g * k + q] = ninf; }
+        std::vector<float> sc(R, fnan);
+        if (!bad) {
+            for (size_t r = 0; r < R; ++r) {
+                const double m1 = (double)sg1 * mu[(size_t)o1 * R + r], s1 = std::sqrt(std::max(vl[(size_t)o1 * R + r], 1e-12));
+                double val;   // EHVI or its logarithm
+                if (!two) {
+                    val = psi(m1, s1, r1, want_log);
+                } else {
+                    const double m2 = (double)sg2 * mu[(size_t)o2 * R + r], s2 = std::sqrt(std::max(vl[(size_t)o2 * R + r], 1e-12));
+                    std::vector<double> term(Pg + 1);
+                    double lo = want_log ? -dinf : 0.0;
+                    for (int i = 0; i <= Pg; ++i) {
+                        const double hi = psi(m1, s1, i < Pg ? st[i].first : r1, want_log);
+                        const double f2 = psi(m2, s2, i == 0 ? r2 : st[i - 1].second, want_log);
+                        if (want_log) {
+                            double w = hi;
+                            if (i > 0 && hi != -dinf) w = lo - hi >= 0.0 ? -dinf : hi + log1mexp(lo - hi);
+                            term[i] = w + f2;
+                        } else {
+                            term[i] = (hi - lo) * f2;
+                        }
+                        lo = hi;
+                    }
+                    if (want_log) {
+                        double mx = -dinf, sum = 0.0;
+                        bool nan = false;
+                        for (double x : term) { if (x != x) nan = true; else mx = std::max(mx, x); }
+                        for (double x : term) if (x != -dinf) sum += std::exp(x - mx);
+                        val = nan ? std::numeric_limits<double>::quiet_NaN() : (sum == 0.0 ? -dinf : mx + std::log(sum));
+                    } else {
+                        val = 0.0;
+                        for (double x : term) val += x;
+                    }
+                }
+                double w = want_log ? 0.0 : 1.0;
+                for (int c = 0; c < ADKF_EHVI_CONS_MAX; ++c) {
+                    if (ct[c] < 0) continue;
+                    const double mc = mu[(size_t)ct[c] * R + r], sd = std::sqrt(std::max(vl[(size_t)ct[c] * R + r], 1e-12));
+                    const double thr = con_thr[(size_t)g * C + c];
+                    const double z = (con_geq[(size_t)g * C + c] ? (mc - thr) : (thr - mc)) / sd;
+                    if (want_log) w += log_cdf(z); else w *= 0.5 * std::erfc(-z / std::sqrt(2.0));
+                }
+                sc[r] = (float)(want_log ? val + w : val * w);
+            }
+        }
+        if (score) std::copy(sc.begin(), sc.end(), score + (size_t)g * R);
+        if (bad || k <= 0) continue;
+        std::vector<int64_t> cand;
+        const int64_t *xb = excl_idx ? excl_idx + excl_off[g] : nullptr, *xe = excl_idx ? excl_idx + excl_off[g + 1] : nullptr;
+        for (int64_t r = 0; r < rows; ++r)
+            if (sc[r] == sc[r] && !(xb && std::binary_search(xb, xe, r))) cand.push_back(r);
+        const size_t kk = std::min<size_t>(k, cand.size());
+        std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return sc[a] > sc[c] || (sc[a] == sc[c] && a < c); });
+        for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)g * k + q] = cand[q]; top_val[(size_t)g * k + q] = sc[cand[q]]; }
+    }
+    return 0;
+}
+
 static int outer_common(const adkf_batch_t* b, const float* phi, int flags, bool with_hessian, float* f_out, float* g_phi, float* dZ_s, float* dZ_q,
                         float* v_out, float* H_out, int32_t* info) {
     const int d = b->d;

@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool and adkf_jes_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool and adkf_ehvi_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
 #pragma once
 #include "host_ard.h"
 
@@ -771,6 +771,94 @@ int gumbel_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const fl
     // the sums and the images of the maxima start at 0 ("no row yet")
     hipMemsetAsync(scratch, 0, l.bytes, c.st);
     return c.ard ? gb_launch<true>(c, pa, pool, v, rows) : gb_launch<false>(c, pa, pool, v, rows);
+}
+
+// adkf_ehvi_pool: the scratch is stage A's mean and latent variance of one chunk of the pool, [T, EHVI_CHUNK_ROWS] each, the groups'
+// state [G] and the candidate lists, one per (group, walker), at most max(PM_POOL_LISTS, G) of k entries.  It depends on neither rows,
+// ns nor d, and it does not shrink when T, G or k grow.
+struct EhviScratch { float *m, *v; EhviGroup* grp; int64_t* cand_idx; float* cand_val; size_t bytes; };
+inline EhviScratch ehvi_scratch(void* base, int T, int G, int k) {
+    Arena ar{static_cast<char*>(base), 0};
+    const size_t mv = (size_t)T * EHVI_CHUNK_ROWS, c = (size_t)std::max(PM_POOL_LISTS, G) * k;
+    EhviScratch l{};
+    l.m = ar.floats(mv);
+    l.v = ar.floats(mv);
+    l.grp = ar.as<EhviGroup>((size_t)G);
+    l.cand_idx = ar.as<int64_t>(c);
+    l.cand_val = ar.floats(c);
+    l.bytes = ar.off;
+    return l;
+}
+static_assert(EHVI_FRONT_MAX == ADKF_EHVI_FRONT_MAX && EHVI_CONS_MAX == ADKF_EHVI_CONS_MAX && EHVI_CHUNK_ROWS == ADKF_EHVI_CHUNK_ROWS &&
+              EHVI_CHUNK_ROWS % PM_TM == 0, "ehvi_stream.h limits");
+
+// The launches of a prepared EHVI call: the groups' state, then per chunk of the pool prediction's own pool launch (latent mean and
+// variance into the scratch, no selection) and the scores of that chunk; at the end one wave per group merges the group's lists.
+template <bool ARD>
+int ehvi_launch(const PmCtx& c, EhviArgs& e, const float* X, int64_t rows, int32_t* info) {
+    hipStream_t st = c.st;
+    const int T = c.b.T, G = e.G, k = e.s.k;
+    if (k > 0) hipMemsetAsync(e.s.cand_idx, 0xff, sizeof(int64_t) * (size_t)G * e.s.chunks_max * k, st);
+    // the groups' "cannot be evaluated" flags read info and n_s here, once: pm_prepare has written info, and nothing below writes it
+    // again (prediction's walks only read it), so the flags hold for every chunk
+    k_ehvi_stair<<<G, 64, 0, st>>>(pm_args(c, 0, X, rows, info), e);
+    // one grid for every chunk, so that a list has the same walker throughout
+    const int64_t items = (int64_t)G * ((std::min<int64_t>(rows, EHVI_CHUNK_ROWS) + PM_TM - 1) / PM_TM);
+    const int grid = pm_persistent_grid(k_ehvi_score, EHVI_NT, 0, std::max<int64_t>(items, 1));
+    e.cpg = std::max(1, std::min(grid / G, e.s.chunks_max));
+    float* m = const_cast<float*>(e.m);
+    float* v = const_cast<float*>(e.v);
+    for (int64_t c0 = 0; c0 < rows; c0 += EHVI_CHUNK_ROWS) {
+        const int64_t L = std::min<int64_t>(EHVI_CHUNK_ROWS, rows - c0);
+        PmPool none = pm_pool(nullptr, nullptr, 0, T, nullptr, nullptr, L, st);
+        const PmCall io{ADKF_PM_LATENT, X + (size_t)c0 * c.b.d, nullptr, L, nullptr, m, v, nullptr, info, &none};
+        // the whole of prediction's sequence per chunk, the zeroing of [T, L] and (ARD) the 1 / l pass included: a few small launches
+        // per 16384 rows, the price of not having a second copy of that sequence to keep equal to it
+        const int rc = pm_launch<ARD, true>(c, io);
+        if (rc) return rc;
+        e.c0 = c0; e.L = L;
+        k_ehvi_score<<<grid, EHVI_NT, 0, st>>>(e);
+    }
+    if (k > 0) k_ehvi_topk<<<G, 64, 0, st>>>(e);
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_ehvi_pool: isotropic and ARD batches alike (as adkf_mes_pool)
+int ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, int32_t G, const int32_t* obj,
+              const int32_t* obj_max, const float* ref, const float* front, const int32_t* front_n, int32_t P, const int32_t* con,
+              const float* con_thr, const int32_t* con_geq, int32_t C, const int64_t* excl_idx, const int64_t* excl_off, float* score,
+              float* stair, int32_t* stair_n, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes,
+              void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags & ~ADKF_PM_LOG_EI) return ADKF_E_BADARG;
+    if (G < 1 || k < 0) return ADKF_E_BADARG;
+    if (P < 0 || P > ADKF_EHVI_FRONT_MAX || C < 0 || C > ADKF_EHVI_CONS_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    if (!obj || !ref || !front_n) return ADKF_E_BADARG;
+    if (P > 0 && !front) return ADKF_E_BADARG;
+    if (C > 0 && (!con || !con_thr || !con_geq)) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (k == 0 && !score && !stair && !stair_n) return ADKF_E_BADARG;
+    const EhviScratch l = ehvi_scratch(scratch, b->T, G, k);
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    EhviArgs e{};
+    e.G = G; e.P = P; e.C = C; e.log = (flags & ADKF_PM_LOG_EI) ? 1 : 0;
+    e.obj = obj; e.obj_max = obj_max; e.ref = ref; e.front = front; e.front_n = front_n;
+    e.con = con; e.con_thr = con_thr; e.con_geq = con_geq;
+    e.stair = stair; e.stair_n = stair_n;
+    e.grp = l.grp; e.m = l.m; e.v = l.v;
+    e.rows = rows; e.score = score;
+    e.s.excl_idx = excl_off ? excl_idx : nullptr; e.s.excl_off = excl_off;
+    e.s.k = k; e.s.chunks_max = pm_pool_chunks_max(G);
+    e.s.cand_idx = l.cand_idx; e.s.cand_val = l.cand_val;
+    e.s.top_idx = top_idx; e.s.top_val = top_val;
+    return c.ard ? ehvi_launch<true>(c, e, X, rows, info) : ehvi_launch<false>(c, e, X, rows, info);
 }
 
 }  // namespace

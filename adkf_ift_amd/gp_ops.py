@@ -851,6 +851,141 @@ def jes_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, opt_idx: torch.T
     return dict(score=score, opt_mean=opt_mean, opt_var=opt_var, top_idx=top_idx, top_val=top_val, info=info)
 
 
+def pareto_front(Y, maximize=(False, False), ref=None) -> torch.Tensor:
+    """The staircase of the two-objective values ``Y [n, 2]`` as ``ehvi_pool`` cleans a front on the device: points with a NaN leave,
+    then (with ``ref``) points not strictly better than the reference point in both coordinates, then points weakly dominated by
+    another one (of exact duplicates the one of lowest index stays).  ``maximize``: the sense per objective.  Returns ``[P, 2]`` in
+    the caller's units, sorted as the device sorts it: by the first objective from its best value to its worst (the second objective
+    then runs from worst to best).  Pure torch; runs on CPU tensors too."""
+    Y = torch.as_tensor(Y)
+    if Y.dim() != 2 or Y.shape[1] != 2:
+        raise ValueError(f"Y must be [n, 2], got {tuple(Y.shape)}")
+    if not Y.is_floating_point():
+        Y = Y.float()
+    sg = torch.tensor([-1.0 if m else 1.0 for m in maximize], dtype=Y.dtype, device=Y.device)
+    F = Y * sg   # everything below minimises
+    valid = ~torch.isnan(F).any(1)
+    if ref is not None:
+        r = torch.as_tensor(ref, dtype=Y.dtype, device=Y.device).reshape(2) * sg
+        valid = valid & (F[:, 0] < r[0]) & (F[:, 1] < r[1])
+    i = torch.arange(F.shape[0], device=Y.device)
+    a, c = F[:, 0], F[:, 1]
+    weak = (a[None, :] <= a[:, None]) & (c[None, :] <= c[:, None])   # [i, j]: j is nowhere worse than i
+    first = (a[None, :] < a[:, None]) | (c[None, :] < c[:, None]) | (i[None, :] < i[:, None])
+    dominated = (weak & first & valid[None, :] & (i[None, :] != i[:, None])).any(1)
+    S = F[valid & ~dominated]
+    return S[torch.argsort(S[:, 0], stable=True)] * sg
+
+
+def _int_table(x, name: str, G: Optional[int], width: Optional[int], what: str) -> torch.Tensor:
+    """An integer table [G, width] on the host (None: any extent), from a tensor or nested lists."""
+    try:
+        t = torch.as_tensor(x)
+    except Exception:
+        t = None
+    if t is None or t.is_floating_point() or t.dim() != 2 or (G is not None and t.shape[0] != G) or (width is not None and t.shape[1] != width):
+        raise ValueError(f"{name} must be {what}, got {tuple(t.shape) if t is not None else x!r}")
+    return t.to(torch.int32)
+
+
+def ehvi_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, obj, ref, front=None, front_n=None, obj_maximize=None, con=None,
+              con_thr=None, con_geq=None, log: bool = False, topk: int = 0, exclude=None, want_score: Optional[bool] = None,
+              want_stair: bool = False):
+    """Constrained expected hypervolume improvement ACROSS the tasks of the batch (Emmerich et al. 2011, Yang et al. 2019; BoTorch's
+    analytic ``ExpectedHypervolumeImprovement`` weighted as its ``ConstrainedExpectedImprovement`` weights EI; ``log``: their log
+    forms) over the shared pool ``X [rows, d]`` in one ``adkf_ehvi_pool`` call, for isotropic and ARD batches alike.  The T tasks are
+    properties of the same rows; group g names its objective tasks ``obj[g] = (t1, t2)`` (``t2 == -1``: one objective, plain
+    constrained EI with ``best_f = ref[g, 0]``), their senses ``obj_maximize[g]`` (default: minimise both), the reference point
+    ``ref[g]``, its front ``front[g, :front_n[g]]`` ``[G, P, 2]`` in the objectives' own units (P at most 64; ``pareto_front`` makes
+    one, but any set of points will do: the device cleans it) and up to four constraint tasks ``con[g]`` (-1: unused) with thresholds
+    ``con_thr[g]``, feasible when the latent ``f <= thr`` (``con_geq[g, c] = 1``: when ``f >= thr``).  A task may serve in several
+    groups.  A group that cannot be evaluated - a task index out of range, both objectives the same task, a member task that is
+    empty or failed, a NaN in ``ref`` or in a used threshold - scores NaN and selects nothing.
+    Returns ``dict(score, top_idx, top_val, stair, stair_n, info)``: ``score [G, rows]`` (``want_score``, which defaults to
+    ``topk == 0``; else None), ``top_idx [G, topk]`` (int64) / ``top_val`` as ``predict_pool`` returns them per task (None with
+    ``topk == 0``), ``stair [G, P, 2]`` / ``stair_n [G]`` (int32) the cleaned staircase per group (``want_stair``; else None) and
+    ``info [T]``.  ``exclude``: rows a GROUP may not select (``pack_exclude`` over G lists); they are still scored."""
+    lib = _lib.load()
+    if b.nq != 0:
+        raise ValueError("ehvi_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    topk = int(topk)
+    if topk < 0 or topk > _lib.POOL_TOPK_MAX:
+        raise ValueError(f"topk must be in [0, {_lib.POOL_TOPK_MAX}], got {topk}")
+    if want_score is None:
+        want_score = topk == 0
+    obj = _int_table(obj, "obj", None, 2, "an integer table [G, 2] of task indices (-1 in the second column: one objective)")
+    G = obj.shape[0]
+    if G < 1:
+        raise ValueError("obj must be an integer table [G, 2] with at least one group")
+    ref = torch.as_tensor(ref, dtype=torch.float32) if not torch.is_tensor(ref) else ref.float()
+    if tuple(ref.shape) != (G, 2):
+        raise ValueError(f"ref must be [G, 2] = [{G}, 2], got {tuple(ref.shape)}")
+    if obj_maximize is not None:
+        obj_maximize = _int_table(torch.as_tensor(obj_maximize).to(torch.int32), "obj_maximize", G, 2, f"a 0 | 1 table [G, 2] = [{G}, 2]")
+    P = 0
+    if front is not None:
+        front = torch.as_tensor(front, dtype=torch.float32) if not torch.is_tensor(front) else front.float()
+        if front.dim() != 3 or front.shape[0] != G or front.shape[2] != 2:
+            raise ValueError(f"front must be [G, P, 2] = [{G}, P, 2], got {tuple(front.shape)}")
+        P = front.shape[1]
+        if P > _lib.EHVI_FRONT_MAX:
+            raise ValueError(f"the number of front points P must be in [0, {_lib.EHVI_FRONT_MAX}], got {P}")
+        if P == 0:
+            front = None
+    if front_n is None:
+        front_n = torch.full((G,), P, dtype=torch.int32)
+    else:
+        front_n = torch.as_tensor(front_n).to(torch.int32).reshape(-1)
+        if front_n.numel() != G:
+            raise ValueError(f"front_n must be [G] = [{G}], got {tuple(front_n.shape)}")
+    Cn = 0
+    if con is not None:
+        con = _int_table(con, "con", G, None, f"an integer table [G, C] = [{G}, C] of task indices (-1: unused)")
+        Cn = con.shape[1]
+        if Cn > _lib.EHVI_CONS_MAX:
+            raise ValueError(f"the number of constraints C must be in [0, {_lib.EHVI_CONS_MAX}], got {Cn}")
+        if Cn == 0:
+            con = None
+    if Cn > 0:
+        if con_thr is None:
+            raise ValueError("con_thr must be given with con")
+        con_thr = torch.as_tensor(con_thr, dtype=torch.float32) if not torch.is_tensor(con_thr) else con_thr.float()
+        if tuple(con_thr.shape) != (G, Cn):
+            raise ValueError(f"con_thr must be [G, C] = [{G}, {Cn}], got {tuple(con_thr.shape)}")
+        con_geq = torch.zeros(G, Cn, dtype=torch.int32) if con_geq is None else _int_table(
+            torch.as_tensor(con_geq).to(torch.int32), "con_geq", G, Cn, f"a 0 | 1 table [G, C] = [{G}, {Cn}]")
+    else:
+        con_thr = con_geq = None
+    if topk == 0 and not want_score and not want_stair:
+        raise ValueError("no output requested: topk == 0, want_score and want_stair are all off")
+    phi = b.check_phi(phi)
+    X = _f32(X, "X")
+    if X.dim() != 2 or X.shape[1] != b.d:
+        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    rows = X.shape[0]
+    dev = b.device
+    put = lambda t: None if t is None else t.to(dev).contiguous()
+    obj, obj_maximize, ref, front, front_n, con, con_thr, con_geq = (put(t) for t in (obj, obj_maximize, ref, front, front_n, con, con_thr, con_geq))
+    excl_idx = excl_off = None
+    if exclude is not None and topk > 0:
+        excl_idx, excl_off = pack_exclude(exclude, G, rows, dev)
+    score = _new(b, G, rows) if want_score else None
+    stair = _new(b, G, P, 2) if want_stair else None
+    stair_n = _new(b, G, dtype=torch.int32) if want_stair else None
+    top_idx = _new(b, G, topk, dtype=torch.int64) if topk > 0 else None
+    top_val = _new(b, G, topk) if topk > 0 else None
+    info = _new(b, b.T, dtype=torch.int32)
+    sb = int(lib.adkf_ehvi_pool_scratch_bytes(b.T, G, topk))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=dev)
+    ws, nb = b.workspace()
+    cb = b.c_struct()
+    _lib.check(lib.adkf_ehvi_pool(C.byref(cb), ptr(phi), _lib.PM_LOG_EI if log else 0, ptr(X), rows, G, ptr(obj), ptr(obj_maximize), ptr(ref),
+                                  ptr(front), ptr(front_n), P, ptr(con), ptr(con_thr), ptr(con_geq), Cn, ptr(excl_idx), ptr(excl_off),
+                                  ptr(score), ptr(stair) if P > 0 else None, ptr(stair_n), topk, ptr(top_idx), ptr(top_val), ptr(info),
+                                  ptr(ws), nb, ptr(scratch), sb, stream(dev)), "adkf_ehvi_pool")
+    return dict(score=score, top_idx=top_idx, top_val=top_val, stair=stair, stair_n=stair_n, info=info)
+
+
 def gumbel_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, n_samples: Optional[int] = None, u: Optional[torch.Tensor] = None,
                 generator: Optional[torch.Generator] = None, maximize: bool = False):
     """Gumbel max-value sampling (Wang & Jegelka 2017, section 3.1; BoTorch's ``_sample_max_value_Gumbel``) over the shared pool

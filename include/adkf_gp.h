@@ -561,6 +561,62 @@ int adkf_kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const f
 size_t adkf_jes_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t S, int32_t k);
 int adkf_jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* opt_idx, const float* opt_val, int32_t S, float cond_noise, const int64_t* excl_idx, const int64_t* excl_off, float* score, float* opt_mean, float* opt_var, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Constrained expected hypervolume improvement ACROSS tasks over a shared pool (csrc/ehvi_stream.h; Emmerich, Deutz and Klinkenberg
+ * 2011 and Yang et al. 2019 for the exact two-objective form, BoTorch's analytic ExpectedHypervolumeImprovement; Schonlau 1998 and
+ * Gardner et al. 2014 for the feasibility weight, BoTorch's ConstrainedExpectedImprovement; ADKF_PM_LOG_EI: their log forms).  It
+ * replaces a adkf_predict_pool call for mean and var [T, rows] combined on the host.  The T tasks of the batch are properties of the
+ * SAME pool rows X [rows, d]; a GROUP g names one or two objective tasks and up to ADKF_EHVI_CONS_MAX constraint tasks among them (a
+ * task may serve in several groups), and every pool row gets one score per group.
+ *   The quantity.  m_t, v_t the latent posterior of adkf_predict_pool at the row, s_t = sqrt(max(v_t, 1e-12)).  An objective with
+ *          obj_max != 0 is maximised: its mean, its column of the front and its reference coordinate are negated, so that everything
+ *          below minimises.  psi_t(c) = E[(c - y_t)+] = s_t (z Phi(z) + phi(z)), z = (c - m_t) / s_t, psi_t(-inf) = 0: the ei of
+ *          adkf_predict_pool with ADKF_PM_LATENT and best_f = c.
+ *          Two objectives: the reference point r = ref[g] and the front[g] points of index below front_n[g] (clamped to [0, P]) are
+ *          cleaned into a STAIRCASE: points with a NaN leave, then points not strictly better than r in both coordinates, then points
+ *          weakly dominated by another one (of exact duplicates the one of lowest index stays); the rest is sorted by the first
+ *          coordinate ascending (the second is then strictly descending): (a_1, b_1) .. (a_P', b_P').  With a_0 = -inf, b_0 = r2 and
+ *          a_(P'+1) = r1,
+ *              EHVI = sum_{i = 0 .. P'} [psi_1(a_(i+1)) - psi_1(a_i)] psi_2(b_i).
+ *          One objective (obj[g, 1] == -1): EHVI = psi_1(r1), EI with best_f = r1; the front is not read.
+ *          Constraints: PoF = prod_c Phi(z_c) in the order of the list, z_c = (thr_c - m_c) / s_c with con_geq == 0 (feasible when
+ *          f <= thr) and (m_c - thr_c) / s_c otherwise, on the latent f.  An entry con[g, c] == -1 is unused.
+ *          score = EHVI PoF; with ADKF_PM_LOG_EI, log EHVI + sum_c log Phi(z_c), formed in log space throughout (log psi as the log EI
+ *          of adkf_predict_pool, the strips joined by a fixed-order log-sum-exp), which keeps an order where the linear score is 0.
+ *          A single-objective group without constraints has, on every row, the bits of adkf_predict_pool's ei (ADKF_PM_LATENT, the
+ *          objective's sense, best_f = ref[g, 0]), and its selection.
+ *          A group cannot be evaluated when a task index is outside [0, T) (other than the -1 of "unused"), obj[g, 0] < 0, both
+ *          objectives are the same task, a member task has n_s == 0 or info != 0, a used coordinate of ref[g] is NaN, or a used
+ *          threshold is NaN: every score of the group is NaN and it selects nothing (top_idx -1, top_val -inf).  A pool row whose
+ *          mean is NaN scores NaN in the groups whose tasks see it, and is never selected.
+ *   b      support-only, of either kind, as for adkf_mes_pool; REUSE_DIST / REUSE_INNER and info [T] as for adkf_predict_pool.
+ *   flags  ADKF_PM_LOG_EI only (the senses are per objective: ADKF_PM_MAXIMIZE is a bad argument here).
+ *   G      groups, at least 1.  obj [G, 2] (int32), obj_max [G, 2] (0 | 1; NULL: all 0), ref [G, 2].
+ *   front  [G, P, 2] with front_n [G], 0 <= P <= ADKF_EHVI_FRONT_MAX; NULL if and only if P == 0.
+ *   con, con_thr, con_geq   [G, C] each, 0 <= C <= ADKF_EHVI_CONS_MAX; required when C > 0.
+ *   excl_idx, excl_off   as for adkf_predict_pool, but per GROUP: excl_off is [G + 1].
+ *   score  nullable, [G, rows].
+ *   stair, stair_n   each nullable, [G, P, 2] and [G]: the cleaned staircase in the caller's units and sense, zero beyond stair_n[g]
+ *          (0 points for a single-objective group).
+ *   k, top_idx, top_val   the selection of adkf_predict_pool on the score, per group: [G, k], k <= ADKF_POOL_TOPK_MAX, its unique
+ *          order, its -1 / -inf tail; a NaN score is never selected.
+ *   scratch   adkf_ehvi_pool_scratch_bytes(T, G, k) bytes, 8-byte aligned: the mean and latent variance of one chunk of
+ *          ADKF_EHVI_CHUNK_ROWS pool rows, [T, chunk] each (the pool is walked in such chunks, each through prediction's own launch,
+ *          so m and v are adkf_predict_pool's bit for bit), the groups' state and the candidate lists.  It depends on neither rows,
+ *          ns_max nor d; the size function returns 0 for T < 1, G < 1, k < 0 or k > ADKF_POOL_TOPK_MAX.
+ * Asynchronous on `stream`, no allocation, no synchronisation, no atomics: reproducible to the bit, and a group's result depends on
+ * its own tasks, front, reference, constraints, exclusion list and the pool only - not on the grid, on the other groups of the call
+ * or on where the chunk boundaries fall.
+ * Rejected before anything is launched, ADKF_E_BADARG unless noted: G < 1; P < 0 or P > ADKF_EHVI_FRONT_MAX, C < 0 or
+ * C > ADKF_EHVI_CONS_MAX, k > ADKF_POOL_TOPK_MAX (ADKF_E_SIZE); obj, ref or front_n == NULL; P > 0 without front; C > 0 without con,
+ * con_thr or con_geq; any flag bit other than ADKF_PM_LOG_EI; a batch with a query set; rows < 0; rows > 0 without X; k < 0; k > 0
+ * without top_idx or top_val; excl_idx without excl_off; no output at all (k == 0 and score, stair and stair_n all NULL); a scratch or
+ * a workspace that is too small (ADKF_E_WORKSPACE); a scratch that is not 8-byte aligned. */
+#define ADKF_EHVI_FRONT_MAX 64
+#define ADKF_EHVI_CONS_MAX 4
+#define ADKF_EHVI_CHUNK_ROWS 16384 /* a multiple of 64: 128 KB of scratch per task, 8 bytes of traffic per (task, row) against ~2 ns d flops */
+size_t adkf_ehvi_pool_scratch_bytes(int32_t T, int32_t G, int32_t k);
+int adkf_ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, int32_t G, const int32_t* obj, const int32_t* obj_max, const float* ref, const float* front, const int32_t* front_n, int32_t P, const int32_t* con, const float* con_thr, const int32_t* con_geq, int32_t C, const int64_t* excl_idx, const int64_t* excl_off, float* score, float* stair, int32_t* stair_n, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

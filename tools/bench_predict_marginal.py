@@ -64,7 +64,15 @@ alternately in this process (median of --reps single calls each) with adkf_kg_po
 reference panel followed by the envelope where JES makes S evaluations - with adkf_mes_pool(k = 8) on the same values - the same S
 evaluations without the panel - and with adkf_predict_pool(k = 8, log EI, nothing per row).  The line holds the times, the ratios, each
 series' spread (max - min) / median, the scratch bytes and the bit-equality of a repeated call.  No target.
-Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--mes] [--gibbon] [--gumbel] [--kg] [--jes] [--out FILE]"""
+--ehvi: constrained EHVI across tasks (adkf_ehvi_pool, k = 8, nothing per row) on --mes's batch and pool: 8 two-objective groups
+(2 g, 2 g + 1) with mixed senses, fronts of P points drawn around the support labels, in log form at P = 16 and P = 64, in linear form
+at P = 16, and at P = 16 with C = 2 constraint tasks - random fronts, which clean down to a handful of steps - and on an anti-chain of
+64 points, every one a step of the staircase (65 strips a row: the most there can be), in log form, in linear form and in log form
+with C = 2, timed alternately in this process (median of --reps single calls each) with
+adkf_predict_pool(latent, mean and var, no selection) - what its stage A runs per chunk - and adkf_predict_pool(k = 8, log EI,
+nothing per row).  The line holds the times, the ratios, the share of stage A, each series' spread, the scratch bytes, the staircase
+sizes and the bit-equality of a repeated call.  No target.
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--mes] [--gibbon] [--gumbel] [--kg] [--jes] [--ehvi] [--out FILE]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -550,6 +558,81 @@ def shape_kg(T, ns, d, rows, k, Ms, reps, dev, out_path=None):
     return rec
 
 
+def shape_ehvi(T, ns, d, rows, k, reps, dev, out_path=None):
+    """T / 2 two-objective groups (2 g, 2 g + 1) with mixed senses, fronts from the support labels padded with jittered copies."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    b = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern")
+    phi0, _ = gp_ops.init_params_batch(b, True, True)
+    b.flags = gp_ops.REUSE_DIST
+    phi, _, _, _, info = gp_ops.fit(b, phi0, 200)
+    gp_ops.check_info(info)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    X = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):
+        X[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    best = ys.median(1).values.contiguous()
+    G = T // 2
+    hg = torch.Generator().manual_seed(1)
+    yh = ys.cpu()
+    obj = torch.tensor([[2 * q, 2 * q + 1] for q in range(G)], dtype=torch.int32)
+    mx = torch.tensor([[q % 2, (q // 2) % 2] for q in range(G)], dtype=torch.int32)
+    pts = torch.stack([yh[0::2], yh[1::2]], 2)                                     # [G, ns, 2]
+    lo_, hi_ = pts.min(1).values, pts.max(1).values
+    ref = torch.where(mx != 0, lo_ - 0.1 * (hi_ - lo_), hi_ + 0.1 * (hi_ - lo_))
+    front = {P: (pts[:, torch.randint(ns, (P,), generator=hg)] + 0.05 * torch.randn(G, P, 2, generator=hg)) for P in (16, 64)}
+    # an anti-chain over the label range, from (best, worst) to (worst, best): every one of its 64 points is a step of the staircase
+    u = (torch.arange(64) + 0.5) / 64
+    best_, worst_ = torch.where(mx != 0, hi_, lo_), torch.where(mx != 0, lo_, hi_)
+    chain = torch.stack([best_[:, None, 0] + u[None] * (worst_ - best_)[:, None, 0],
+                         best_[:, None, 1] + (1 - u[None]) * (worst_ - best_)[:, None, 1]], 2)[:, torch.randperm(64, generator=hg)]
+    con = torch.tensor([[(2 * q + 2) % T, (2 * q + 3) % T] for q in range(G)], dtype=torch.int32)
+    thr = torch.tensor([[float(yh[(2 * q + 2) % T].median()), float(yh[(2 * q + 3) % T].median())] for q in range(G)])
+    kw = dict(obj=obj, ref=ref, obj_maximize=mx, topk=k, want_score=False, want_stair=True)
+    variants = {"log_P16": dict(front=front[16], log=True), "log_P64": dict(front=front[64], log=True), "lin_P16": dict(front=front[16]),
+                "log_P16_C2": dict(front=front[16], log=True, con=con, con_thr=thr),
+                "log_chain64": dict(front=chain, log=True), "lin_chain64": dict(front=chain),
+                "log_chain64_C2": dict(front=chain, log=True, con=con, con_thr=thr)}
+    f_e = {n: (lambda v=v: gp_ops.ehvi_pool(b, phi, X, **kw, **v)) for n, v in variants.items()}
+    f_mv = lambda: gp_ops.predict_pool(b, phi, X, latent=True, want_mean=True, want_var=True)
+    f_lei = lambda: gp_ops.predict_pool(b, phi, X, latent=True, best_f=best, want_mean=False, want_var=False, want_ei=False, topk=k, log_ei=True)
+    o1 = {n: f() for n, f in f_e.items()}
+    o2 = {n: f() for n, f in f_e.items()}
+    f_mv(); f_lei()
+    torch.cuda.synchronize()
+    for n in o1:
+        gp_ops.check_info(o1[n]["info"])
+    ts = {"mean_var": [], "log_ei": [], **{n: [] for n in f_e}}
+    for _ in range(reps):
+        ts["mean_var"].append(once(f_mv))
+        ts["log_ei"].append(once(f_lei))
+        for n, f in f_e.items():
+            ts[n].append(once(f))
+    med = {n: float(np.median(x)) for n, x in ts.items()}
+    lib = _lib.load()
+    rec = {"shape": f"ehvi T={T} G={G} ns={ns} d={d} rows={rows} k={k} matern REUSE_INNER score=NULL; predict_pool latent mean+var; predict_pool k={k} log EI",
+           "refined_tasks": int(_refined(b).sum()), "float64_tasks": int((_scal(b)[:, 45] > 30.0).sum()),
+           "workspace_bytes": int(lib.adkf_workspace_bytes(T, ns, 0, d)), "scratch_bytes": int(lib.adkf_ehvi_pool_scratch_bytes(T, G, k)),
+           "chunk_rows": int(_lib.EHVI_CHUNK_ROWS), "stair_points": {n: o1[n]["stair_n"].tolist() for n in o1},
+           "predict_pool_mean_var_s": med["mean_var"], "predict_pool_log_ei_s": med["log_ei"], "ehvi_s": {n: med[n] for n in f_e},
+           "ehvi_over_mean_var": {n: med[n] / med["mean_var"] for n in f_e}, "ehvi_over_log_ei": {n: med[n] / med["log_ei"] for n in f_e},
+           # stage A is prediction's own launch per chunk with both outputs: the mean_var call is its cost, the rest is the score kernels
+           "stage_a_share": {n: med["mean_var"] / med[n] for n in f_e},
+           "spread_max_minus_min_over_median": {n: (max(x) - min(x)) / float(np.median(x)) for n, x in ts.items()},
+           "repeat_is_bit_equal": bool(all(torch.equal(o1[n]["top_idx"], o2[n]["top_idx"]) and
+                                           torch.equal(o1[n]["top_val"].view(torch.int32), o2[n]["top_val"].view(torch.int32)) for n in o1)),
+           "all_selected": bool(all((o1[n]["top_idx"] >= 0).all() and torch.isfinite(o1[n]["top_val"]).all() for n in o1)),
+           "all_s": ts}
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    return rec
+
+
 def shape_jes(T, ns, d, rows, k, Ss, m, reps, dev, out_path=None):
     g = torch.Generator(device=dev).manual_seed(0)
     W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
@@ -792,7 +875,8 @@ def main():
     ap.add_argument("--gumbel", action="store_true", help="adkf_gumbel_pool against adkf_predict_pool(k, log EI) and max_value_samples(S = 16, m = 1024), timed alternately")
     ap.add_argument("--kg", action="store_true", help="adkf_kg_pool(log KG, k = 8) at M = 32 and 64 against adkf_predict_pool(k, log EI) and adkf_believer_pool(q = 8, log EI), timed alternately")
     ap.add_argument("--jes", action="store_true", help="adkf_jes_pool(k = 8) at S = 16 and 64 against adkf_kg_pool(log KG, k = 8) at M = S, adkf_mes_pool(k = 8) and adkf_predict_pool(k, log EI), timed alternately")
-    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard), --mes, --gibbon, --gumbel, --kg, --jes: also write the JSON line to this file")
+    ap.add_argument("--ehvi", action="store_true", help="adkf_ehvi_pool(k = 8) over 8 two-objective groups - log form at P = 16 and 64, linear at P = 16, P = 16 with C = 2, and a 64-step anti-chain staircase (log, linear, log with C = 2) - against adkf_predict_pool(latent mean and var) and adkf_predict_pool(k, log EI), timed alternately")
+    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard), --mes, --gibbon, --gumbel, --kg, --jes, --ehvi: also write the JSON line to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.mes:
@@ -803,6 +887,9 @@ def main():
         return
     if a.jes:
         shape_jes(16, 128, 256, 100000, 8, (16, 64), 1024, a.reps, dev, a.out)
+        return
+    if a.ehvi:
+        shape_ehvi(16, 128, 256, 100000, 8, a.reps, dev, a.out)
         return
     if a.gibbon:
         shape_gibbon(16, 128, 256, 100000, 8, 16, a.reps, dev, a.out)

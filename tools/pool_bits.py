@@ -7,7 +7,9 @@ dump runs, on the problems of the GPU tests (tests/test_gpu_believer_pool._expli
 at 1024; the ARD problem of tests/test_gpu_believer_pool_ard; tests/test_gpu_predict_pool._ill_batch, whose flagged tasks take the
 float64 walks): believer_pool with EI and with log EI and gibbon_pool, each with trace, predict_pool(log EI, k = 8), believer_pool_ard,
 kg_pool with KG and with log KG (score, cov, ref_mean and the selection; M = 16 reference rows of lowest posterior mean, a -1 and a
-repetition among them) - and saves every returned tensor.  All lists are full (pools of 130 to 333 rows), so the arrays do not depend on how a short list is
+repetition among them), and ehvi_pool on the problems of tests/test_gpu_ehvi_pool.py's score test (score, staircase and selection, linear
+and log, with and without the constraints) - and saves every returned tensor.  compare looks at the arrays both files have, so a
+tree can be held against one from before a call existed.  All lists are full (pools of 130 to 333 rows), so the arrays do not depend on how a short list is
 merged."""
 import os
 import sys
@@ -60,6 +62,16 @@ def dump(path):
     for log in (False, True):
         put(f"float64/kg/log={log}", gp_ops.kg_pool(b, phi, X, ref_idx=kg_refs(b, phi, X), log=log, topk=8, want_cov=True))
     put("float64/gibbon", gp_ops.gibbon_pool(b, phi, X, ystar=(best[:, None] - torch.tensor([[1.0, 2.0]], device=dev)).contiguous(), q=6, want_trace=True))
+    import test_gpu_ehvi_pool as EV
+    from test_ehvi_pool_cpu import GPU_CASES
+
+    for case in range(len(GPU_CASES)):
+        b, phi, X, grp, _, _ = EV._built_case(dev, case)
+        free = dict(grp, C=0, con=None, con_thr=None, con_geq=None)
+        for log in (False, True):
+            put(f"ehvi/case{case}/log={log}", EV._call(b, phi, X, grp, log=log, topk=8, want_score=True, want_stair=True))
+            if grp["C"] > 0:
+                put(f"ehvi/case{case}/log={log}/C=0", EV._call(b, phi, X, free, log=log, topk=8, want_score=True))
     torch.save(out, path)
     print("saved", len(out), "arrays to", path)
 
@@ -68,11 +80,14 @@ def compare(pa, pb):
     import torch
 
     a, b = torch.load(pa), torch.load(pb)
-    if a.keys() != b.keys():
-        print("different sets of arrays:", sorted(set(a) ^ set(b)))
+    both = [k for k in a if k in b]
+    if len(both) != len(a) or len(both) != len(b):   # calls one of the trees does not have: compared on the arrays both have
+        print("arrays in one file only:", len(set(a) ^ set(b)), "with prefixes", sorted({k.split("/")[0] for k in set(a) ^ set(b)}))
+    if not both:
+        print("no array in common")
         return 1
-    bad = [k for k in a if a[k].shape != b[k].shape or not torch.equal(a[k].contiguous().view(torch.uint8), b[k].contiguous().view(torch.uint8))]
-    print("arrays compared", len(a), "different", bad)
+    bad = [k for k in both if a[k].shape != b[k].shape or not torch.equal(a[k].contiguous().view(torch.uint8), b[k].contiguous().view(torch.uint8))]
+    print("arrays compared", len(both), "different", bad)
     return 1 if bad else 0
 
 
