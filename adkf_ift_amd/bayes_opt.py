@@ -187,6 +187,73 @@ def run_gp_ei_bo(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int,
     return record
 
 
+def _bo_start(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, init_from: int, rngs, dim=None):
+    """The start of a batched loop: ``y_all`` standardised (``dim=0``: each column), the pool as float32 and each replicate's initial
+    design, drawn from its own generator.  Returns ``(y_all, X, queried)``."""
+    y_all = (y_all - y_all.mean(dim)) / y_all.std(dim)
+    X = x_all.detach().float().contiguous()
+    queried = [rng.choice(np.arange(init_from, x_all.shape[0]), size=num_init_points, replace=False).tolist() for rng in rngs]
+    return y_all, X, queried
+
+
+def _fit_tasks(name: str, x_all: torch.Tensor, tasks, X: torch.Tensor, kernel_type: str, device, noise_init: float, noise_prior: bool,
+               ard: bool):
+    """ONE batch of the tasks ``(indices, target column)`` - initial parameters and priors as ``create_gp`` makes them for each, with
+    ``ard`` the lengthscale expanded to one per feature dimension - fitted by ONE ``gp_ops.fit``.  Returns ``(b, phi)``, the batch
+    flagged to reuse the fit's distances and inner quantities."""
+    sizes = [len(q) for q, _ in tasks]
+    ns = max(sizes)
+    Zs = torch.zeros(len(tasks), ns, X.shape[1], dtype=torch.float32, device=X.device)
+    ys = torch.zeros(len(tasks), ns, dtype=torch.float32, device=X.device)
+    pri, phi0 = [], []
+    for t, (q, y) in enumerate(tasks):
+        _, model, mll = create_gp(x_all[q], y[q], kernel_type, device, noise_init, noise_prior)
+        Zs[t, :sizes[t]] = model.train_inputs[0].detach().float()
+        ys[t, :sizes[t]] = model.train_targets.detach().float()
+        pri.append(mll.priors_row(X.device))
+        p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
+        phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
+    n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
+    b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
+    phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
+    gp_ops.check_info(info, f"{name} fit")
+    b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    return b, phi
+
+
+def _path_generators(rngs) -> List[torch.Generator]:
+    """One torch generator per replicate, seeded from the replicate's own generator."""
+    return [torch.Generator().manual_seed(int(rng.integers(0, 2 ** 62))) for rng in rngs]
+
+
+def _pathwise_draws(gens, S: int, n_features: int, queried, device):
+    """The prior weights ``w [R, S, m]`` and noise draws ``eps [R, S, ns]`` of a pathwise posterior draw, replicate r's from ``gens[r]``,
+    the noise draws at the replicate's own support size (zeros beyond it)."""
+    sizes = [len(q) for q in queried]
+    w = torch.empty(len(gens), S, n_features, dtype=torch.float32)
+    eps = torch.zeros(len(gens), S, max(sizes), dtype=torch.float32)
+    for r, g in enumerate(gens):
+        w[r] = torch.randn(S, n_features, generator=g)
+        eps[r, :, :sizes[r]] = torch.randn(S, sizes[r], generator=g)
+    return w.to(device), eps.to(device)
+
+
+def _take_picks(top_idx: torch.Tensor, usable: torch.Tensor, query_batch_size: int, rngs, queried, records, n: int,
+                reverse: bool = False) -> None:
+    """The end of an iteration of the batched loops: replicate r takes the usable prefix of its
+    candidates ``top_idx[r]`` (``usable[r]``: a prefix mask), fills a shortfall with random rows it has not queried, drawn from its own
+    generator ``rngs[r]``, and adds the picks to ``queried[r]`` and ``records[r]`` (both updated in place; ``reverse``: to the record in
+    reverse order, as ``run_gp_ei_bo`` appends them)."""
+    for r, rng in enumerate(rngs):
+        nonzero = int(usable[r].sum())
+        pick = top_idx[r, :nonzero].tolist()
+        if nonzero < query_batch_size:
+            taken = set(queried[r] + pick)
+            pick += rng.choice([i for i in range(n) if i not in taken], size=query_batch_size - nonzero, replace=False).tolist()
+        queried[r] = list(set(queried[r] + pick))
+        records[r].extend(pick[::-1] if reverse else pick)
+
+
 @torch.no_grad()
 def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
                          kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
@@ -208,37 +275,14 @@ def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
     log = _acquisition(acquisition)
     if batch not in ("topk", "believer"):
         raise ValueError(f"batch must be 'topk' or 'believer', got {batch!r}")
-    R, n = len(rngs), x_all.shape[0]
-    y_all = (y_all - y_all.mean()) / y_all.std()
-    X = x_all.detach().float().contiguous()
-    queried = [rng.choice(np.arange(init_from, n), size=num_init_points, replace=False).tolist() for rng in rngs]
+    n = x_all.shape[0]
+    y_all, X, queried = _bo_start(x_all, y_all, num_init_points, init_from, rngs)
     records = [[min(q)] for q in queried]
 
-    def free(taken):
-        taken = set(taken)
-        return [i for i in range(n) if i not in taken]
-
     for _ in range(num_bo_iters):
-        sizes = [len(q) for q in queried]
-        ns = max(sizes)
-        Zs = torch.zeros(R, ns, X.shape[1], dtype=torch.float32, device=X.device)
-        ys = torch.zeros(R, ns, dtype=torch.float32, device=X.device)
-        pri, phi0, best = [], [], []
-        for r, q in enumerate(queried):
-            xq, yq = x_all[q], y_all[q]
-            best.append(yq.min().item())
-            _, model, mll = create_gp(xq, yq, kernel_type, device, noise_init, noise_prior)
-            Zs[r, :sizes[r]] = model.train_inputs[0].detach().float()
-            ys[r, :sizes[r]] = model.train_targets.detach().float()
-            pri.append(mll.priors_row(X.device))
-            p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
-            phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
-        n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
-        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
-        phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
-        gp_ops.check_info(info, "run_gp_ei_bo_batched fit")
-        b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
-        best_f = torch.tensor(best, dtype=torch.float32, device=X.device)
+        b, phi = _fit_tasks("run_gp_ei_bo_batched", x_all, [(q, y_all) for q in queried], X, kernel_type, device, noise_init, noise_prior,
+                            ard)
+        best_f = torch.tensor([y_all[q].min().item() for q in queried], dtype=torch.float32, device=X.device)
         if batch == "believer":
             believe = gp_ops.believer_pool_ard if b.ard else gp_ops.believer_pool
             out = believe(b, phi, X, best_f=best_f, q=query_batch_size, maximize=False, log_ei=log, exclude=queried)
@@ -251,17 +295,7 @@ def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
         usable = (torch.isfinite(top_val) & (top_idx >= 0)) if log else top_val > 0   # (a prefix of each row: descending scores)
         if batch == "believer":   # a believer score can round above its predecessor: keep the prefix
             usable = usable.long().cumprod(1).bool()
-        for r, rng in enumerate(rngs):
-            nonzero = int(usable[r].sum())   # of the query_batch_size best: all that the branches below distinguish
-            if nonzero == 0:
-                pick = rng.choice(free(queried[r]), size=query_batch_size, replace=False).tolist()
-            elif nonzero < query_batch_size:
-                pick = top_idx[r, :nonzero].tolist()
-                pick += rng.choice(free(queried[r] + pick), size=query_batch_size - nonzero, replace=False).tolist()
-            else:
-                pick = top_idx[r].tolist()
-            queried[r] = list(set(queried[r] + pick))
-            records[r].extend(pick[::-1])
+        _take_picks(top_idx, usable, query_batch_size, rngs, queried, records, n, reverse=True)
     return records
 
 
@@ -281,46 +315,26 @@ def run_gp_ts_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
     ``ard``: one lengthscale per feature dimension (the reference's ``ard_num_dims``) - each replicate's ``create_gp`` start is
     expanded to ``[2 + d]``, every lengthscale at the median heuristic (as ARD ``adkf_init_params`` starts), under the same
     priors; the batch is an ARD batch and the draws come from ``gp_ops.thompson_pool_ard``."""
-    R, n = len(rngs), x_all.shape[0]
+    n = x_all.shape[0]
     if not 1 <= query_batch_size <= gp_ops._lib.TS_SAMPLES_MAX:
         raise ValueError(f"query_batch_size must be in [1, {gp_ops._lib.TS_SAMPLES_MAX}], got {query_batch_size}")
-    y_all = (y_all - y_all.mean()) / y_all.std()
-    X = x_all.detach().float().contiguous()
+    y_all, X, queried = _bo_start(x_all, y_all, num_init_points, init_from, rngs)
     S = min(gp_ops._lib.TS_SAMPLES_MAX, query_batch_size * max(1, int(oversample)))
     omega, phase = gp_ops.rff_basis(kernel_type, X.shape[1], n_features, generator=torch.Generator().manual_seed(int(feature_seed)),
                                     device=X.device)
-    queried = [rng.choice(np.arange(init_from, n), size=num_init_points, replace=False).tolist() for rng in rngs]
     records = [[min(q)] for q in queried]
-    gens = [torch.Generator().manual_seed(int(rng.integers(0, 2 ** 62))) for rng in rngs]
+    gens = _path_generators(rngs)
 
     def free(taken):
         taken = set(taken)
         return [i for i in range(n) if i not in taken]
 
     for _ in range(num_bo_iters):
-        sizes = [len(q) for q in queried]
-        ns = max(sizes)
-        Zs = torch.zeros(R, ns, X.shape[1], dtype=torch.float32, device=X.device)
-        ys = torch.zeros(R, ns, dtype=torch.float32, device=X.device)
-        w = torch.empty(R, S, n_features, dtype=torch.float32)
-        eps = torch.zeros(R, S, ns, dtype=torch.float32)
-        pri, phi0 = [], []
-        for r, q in enumerate(queried):
-            _, model, mll = create_gp(x_all[q], y_all[q], kernel_type, device, noise_init, noise_prior)
-            Zs[r, :sizes[r]] = model.train_inputs[0].detach().float()
-            ys[r, :sizes[r]] = model.train_targets.detach().float()
-            pri.append(mll.priors_row(X.device))
-            p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
-            phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
-            w[r] = torch.randn(S, n_features, generator=gens[r])
-            eps[r, :, :sizes[r]] = torch.randn(S, sizes[r], generator=gens[r])
-        n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
-        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
-        phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
-        gp_ops.check_info(info, "run_gp_ts_bo_batched fit")
-        b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+        b, phi = _fit_tasks("run_gp_ts_bo_batched", x_all, [(q, y_all) for q in queried], X, kernel_type, device, noise_init, noise_prior,
+                            ard)
+        w, eps = _pathwise_draws(gens, S, n_features, queried, X.device)
         draw = gp_ops.thompson_pool_ard if b.ard else gp_ops.thompson_pool
-        out = draw(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w.to(X.device), eps=eps.to(X.device), maximize=False, exclude=queried)
+        out = draw(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w, eps=eps, maximize=False, exclude=queried)
         gp_ops.check_info(out["info"], "BO posterior")
         sel = out["sel_idx"].cpu().tolist()
         for r, rng in enumerate(rngs):
@@ -335,20 +349,6 @@ def run_gp_ts_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
             queried[r] = list(set(queried[r] + pick))
             records[r].extend(pick)
     return records
-
-
-def _take_picks(top_idx: torch.Tensor, usable: torch.Tensor, query_batch_size: int, rngs, queried, records, n: int) -> None:
-    """The end of an iteration of ``run_gp_mes_bo_batched``, ``run_gp_kg_bo_batched`` and ``run_gp_jes_bo_batched``: replicate r takes the usable prefix of its
-    candidates ``top_idx[r]`` (``usable[r]``: a prefix mask), fills a shortfall with random rows it has not queried, drawn from its own
-    generator ``rngs[r]``, and adds the picks to ``queried[r]`` and ``records[r]`` (both updated in place)."""
-    for r, rng in enumerate(rngs):
-        nonzero = int(usable[r].sum())
-        pick = top_idx[r, :nonzero].tolist()
-        if nonzero < query_batch_size:
-            taken = set(queried[r] + pick)
-            pick += rng.choice([i for i in range(n) if i not in taken], size=query_batch_size - nonzero, replace=False).tolist()
-        queried[r] = list(set(queried[r] + pick))
-        records[r].extend(pick)
 
 
 @torch.no_grad()
@@ -378,7 +378,7 @@ def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
     which a pick lowers the score of the rows correlated with it - keeps the usable prefix of its picks (index not -1, value
     finite; later values may be negative) and fills a shortfall in the same way; the records are in pick order.  At
     ``query_batch_size = 1`` the two are DIFFERENT loops: GIBBON's single-point score ``a`` is not the MES score ``g``."""
-    R, n = len(rngs), x_all.shape[0]
+    n = x_all.shape[0]
     if max_value not in ("thompson", "gumbel"):
         raise ValueError(f"max_value must be 'thompson' or 'gumbel', got {max_value!r}")
     if batch not in ("topk", "gibbon"):
@@ -389,52 +389,25 @@ def run_gp_mes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
     S = int(n_max_samples)
     if not 1 <= S <= gp_ops._lib.TS_SAMPLES_MAX:
         raise ValueError(f"n_max_samples must be in [1, {gp_ops._lib.TS_SAMPLES_MAX}], got {n_max_samples}")
-    y_all = (y_all - y_all.mean()) / y_all.std()
-    X = x_all.detach().float().contiguous()
+    y_all, X, queried = _bo_start(x_all, y_all, num_init_points, init_from, rngs)
     if not gumbel:
         omega, phase = gp_ops.rff_basis(kernel_type, X.shape[1], n_features, generator=torch.Generator().manual_seed(int(feature_seed)),
                                         device=X.device)
-    queried = [rng.choice(np.arange(init_from, n), size=num_init_points, replace=False).tolist() for rng in rngs]
     records = [[min(q)] for q in queried]
-    gens = [torch.Generator().manual_seed(int(rng.integers(0, 2 ** 62))) for rng in rngs]
+    gens = _path_generators(rngs)
 
     for _ in range(num_bo_iters):
-        sizes = [len(q) for q in queried]
-        ns = max(sizes)
-        Zs = torch.zeros(R, ns, X.shape[1], dtype=torch.float32, device=X.device)
-        ys = torch.zeros(R, ns, dtype=torch.float32, device=X.device)
+        b, phi = _fit_tasks("run_gp_mes_bo_batched", x_all, [(q, y_all) for q in queried], X, kernel_type, device, noise_init, noise_prior,
+                            ard)
         if gumbel:
-            u = torch.empty(R, S, dtype=torch.float32)
-        else:
-            w = torch.empty(R, S, n_features, dtype=torch.float32)
-            eps = torch.zeros(R, S, ns, dtype=torch.float32)
-        pri, phi0, best = [], [], []
-        for r, q in enumerate(queried):
-            xq, yq = x_all[q], y_all[q]
-            best.append(yq.min().item())
-            _, model, mll = create_gp(xq, yq, kernel_type, device, noise_init, noise_prior)
-            Zs[r, :sizes[r]] = model.train_inputs[0].detach().float()
-            ys[r, :sizes[r]] = model.train_targets.detach().float()
-            pri.append(mll.priors_row(X.device))
-            p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
-            phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
-            if gumbel:
-                u[r] = torch.rand(S, generator=gens[r])
-            else:
-                w[r] = torch.randn(S, n_features, generator=gens[r])
-                eps[r, :, :sizes[r]] = torch.randn(S, sizes[r], generator=gens[r])
-        n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
-        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
-        phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
-        gp_ops.check_info(info, "run_gp_mes_bo_batched fit")
-        b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
-        if gumbel:
+            u = torch.stack([torch.rand(S, generator=g) for g in gens])
             mv = gp_ops.gumbel_pool(b, phi, X, u=u.to(X.device), maximize=False)
         else:
-            mv = gp_ops.max_value_samples(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w.to(X.device), eps=eps.to(X.device),
-                                          maximize=False)
+            w, eps = _pathwise_draws(gens, S, n_features, queried, X.device)
+            mv = gp_ops.max_value_samples(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w, eps=eps, maximize=False)
         gp_ops.check_info(mv["info"], "BO posterior")
         # the minimum of f is no worse than the best value seen
+        best = [y_all[q].min().item() for q in queried]
         ystar = torch.minimum(mv["ystar"], torch.tensor(best, dtype=torch.float32, device=X.device)[:, None])
         if batch == "gibbon":
             out = gp_ops.gibbon_pool(b, phi, X, ystar=ystar, q=query_batch_size, maximize=False, exclude=queried)
@@ -464,36 +437,18 @@ def run_gp_kg_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
     row; it prices the observation noise and needs no ``best_f``.  A returned candidate counts when its index is not -1 and its
     score is finite; a shortfall is filled with random free rows from the replicate's generator, as in ``run_gp_mes_bo_batched``.
     Nothing random enters the score: a replicate's record does not depend on which other replicates share the batch."""
-    R, n = len(rngs), x_all.shape[0]
+    n = x_all.shape[0]
     if not 1 <= query_batch_size <= gp_ops._lib.POOL_TOPK_MAX:
         raise ValueError(f"query_batch_size must be in [1, {gp_ops._lib.POOL_TOPK_MAX}], got {query_batch_size}")
     M = int(n_refs)
     if not 1 <= M <= gp_ops._lib.KG_REFS_MAX:
         raise ValueError(f"n_refs must be in [1, {gp_ops._lib.KG_REFS_MAX}], got {n_refs}")
-    y_all = (y_all - y_all.mean()) / y_all.std()
-    X = x_all.detach().float().contiguous()
-    queried = [rng.choice(np.arange(init_from, n), size=num_init_points, replace=False).tolist() for rng in rngs]
+    y_all, X, queried = _bo_start(x_all, y_all, num_init_points, init_from, rngs)
     records = [[min(q)] for q in queried]
 
     for _ in range(num_bo_iters):
-        sizes = [len(q) for q in queried]
-        ns = max(sizes)
-        Zs = torch.zeros(R, ns, X.shape[1], dtype=torch.float32, device=X.device)
-        ys = torch.zeros(R, ns, dtype=torch.float32, device=X.device)
-        pri, phi0 = [], []
-        for r, q in enumerate(queried):
-            xq, yq = x_all[q], y_all[q]
-            _, model, mll = create_gp(xq, yq, kernel_type, device, noise_init, noise_prior)
-            Zs[r, :sizes[r]] = model.train_inputs[0].detach().float()
-            ys[r, :sizes[r]] = model.train_targets.detach().float()
-            pri.append(mll.priors_row(X.device))
-            p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
-            phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
-        n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
-        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
-        phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
-        gp_ops.check_info(info, "run_gp_kg_bo_batched fit")
-        b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+        b, phi = _fit_tasks("run_gp_kg_bo_batched", x_all, [(q, y_all) for q in queried], X, kernel_type, device, noise_init, noise_prior,
+                            ard)
         refs = gp_ops.predict_pool(b, phi, X, maximize=False, topk=M, score="mean", want_mean=False, want_var=False, want_ei=False)
         gp_ops.check_info(refs["info"], "BO posterior")
         out = gp_ops.kg_pool(b, phi, X, ref_idx=refs["top_idx"], maximize=False, log=True, topk=query_batch_size, exclude=queried,
@@ -525,7 +480,7 @@ def run_gp_jes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
     the noise draws at the replicate's own support size: a replicate's record does not depend on which other replicates share the
     batch.  ``oversample`` is accepted for the signature of ``run_gp_ts_bo_batched`` and not used.  ``ard``: as
     ``run_gp_ts_bo_batched``; the same two calls serve ARD batches."""
-    R, n = len(rngs), x_all.shape[0]
+    n = x_all.shape[0]
     if not 1 <= query_batch_size <= gp_ops._lib.POOL_TOPK_MAX:
         raise ValueError(f"query_batch_size must be in [1, {gp_ops._lib.POOL_TOPK_MAX}], got {query_batch_size}")
     S = int(n_opt_samples)
@@ -533,39 +488,17 @@ def run_gp_jes_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poi
         raise ValueError(f"n_opt_samples must be in [1, {gp_ops._lib.TS_SAMPLES_MAX}], got {n_opt_samples}")
     if not 0.0 <= float(cond_noise) < float("inf"):
         raise ValueError(f"cond_noise must be finite and >= 0, got {cond_noise}")
-    y_all = (y_all - y_all.mean()) / y_all.std()
-    X = x_all.detach().float().contiguous()
+    y_all, X, queried = _bo_start(x_all, y_all, num_init_points, init_from, rngs)
     omega, phase = gp_ops.rff_basis(kernel_type, X.shape[1], n_features, generator=torch.Generator().manual_seed(int(feature_seed)),
                                     device=X.device)
-    queried = [rng.choice(np.arange(init_from, n), size=num_init_points, replace=False).tolist() for rng in rngs]
     records = [[min(q)] for q in queried]
-    gens = [torch.Generator().manual_seed(int(rng.integers(0, 2 ** 62))) for rng in rngs]
+    gens = _path_generators(rngs)
 
     for _ in range(num_bo_iters):
-        sizes = [len(q) for q in queried]
-        ns = max(sizes)
-        Zs = torch.zeros(R, ns, X.shape[1], dtype=torch.float32, device=X.device)
-        ys = torch.zeros(R, ns, dtype=torch.float32, device=X.device)
-        w = torch.empty(R, S, n_features, dtype=torch.float32)
-        eps = torch.zeros(R, S, ns, dtype=torch.float32)
-        pri, phi0 = [], []
-        for r, q in enumerate(queried):
-            xq, yq = x_all[q], y_all[q]
-            _, model, mll = create_gp(xq, yq, kernel_type, device, noise_init, noise_prior)
-            Zs[r, :sizes[r]] = model.train_inputs[0].detach().float()
-            ys[r, :sizes[r]] = model.train_targets.detach().float()
-            pri.append(mll.priors_row(X.device))
-            p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
-            phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
-            w[r] = torch.randn(S, n_features, generator=gens[r])
-            eps[r, :, :sizes[r]] = torch.randn(S, sizes[r], generator=gens[r])
-        n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
-        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
-        phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
-        gp_ops.check_info(info, "run_gp_jes_bo_batched fit")
-        b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
-        opt = gp_ops.optimum_samples(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w.to(X.device), eps=eps.to(X.device),
-                                     maximize=False)
+        b, phi = _fit_tasks("run_gp_jes_bo_batched", x_all, [(q, y_all) for q in queried], X, kernel_type, device, noise_init, noise_prior,
+                            ard)
+        w, eps = _pathwise_draws(gens, S, n_features, queried, X.device)
+        opt = gp_ops.optimum_samples(b, phi, X, omega=omega, phase=phase, n_samples=S, w=w, eps=eps, maximize=False)
         gp_ops.check_info(opt["info"], "BO posterior")
         out = gp_ops.jes_pool(b, phi, X, opt_idx=opt["opt_idx"], opt_val=opt["opt_val"], cond_noise=cond_noise, maximize=False,
                               topk=query_batch_size, exclude=queried, want_score=False)
@@ -624,29 +557,15 @@ def run_gp_ehvi_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_po
         raise ValueError(f"acquisition must be 'log_ehvi' or 'ehvi', got {acquisition!r}")
     log = acquisition == "log_ehvi"
     maximize = tuple(bool(m) for m in maximize)
-    y_all = (y_all - y_all.mean(0)) / y_all.std(0)
-    X = x_all.detach().float().contiguous()
-    queried = [rng.choice(np.arange(init_from, n), size=num_init_points, replace=False).tolist() for rng in rngs]
+    y_all, X, queried = _bo_start(x_all, y_all, num_init_points, init_from, rngs, dim=0)
     records = [list(q) for q in queried]
     history = [[list(q)] for q in queried]
     obj = torch.tensor([[2 * r, 2 * r + 1] for r in range(R)], dtype=torch.int32)
     obj_max = torch.tensor([[int(maximize[0]), int(maximize[1])]] * R, dtype=torch.int32)
 
     for _ in range(num_bo_iters):
-        sizes = [len(q) for q in queried for _ in range(2)]
-        ns = max(sizes)
-        Zs = torch.zeros(2 * R, ns, X.shape[1], dtype=torch.float32, device=X.device)
-        ys = torch.zeros(2 * R, ns, dtype=torch.float32, device=X.device)
-        pri, phi0, fronts, refs = [], [], [], []
+        fronts, refs = [], []
         for r, q in enumerate(queried):
-            for j in range(2):
-                t = 2 * r + j
-                _, model, mll = create_gp(x_all[q], y_all[q, j], kernel_type, device, noise_init, noise_prior)
-                Zs[t, :sizes[t]] = model.train_inputs[0].detach().float()
-                ys[t, :sizes[t]] = model.train_targets.detach().float()
-                pri.append(mll.priors_row(X.device))
-                p0 = torch.cat([p.detach().reshape(-1) for p in mll.raw_params()])
-                phi0.append((torch.cat([p0[:2], p0[2:3].expand(X.shape[1])]) if ard else p0)[None])
             Yq = y_all[q].float()
             refs.append(_ehvi_ref_point(Yq, maximize))
             fronts.append(gp_ops.pareto_front(Yq.cpu(), maximize))
@@ -658,11 +577,8 @@ def run_gp_ehvi_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_po
         for r, f in enumerate(fronts):
             front[r, :f.shape[0]] = f
         front_n = torch.tensor([f.shape[0] for f in fronts], dtype=torch.int32)
-        n_s = None if min(sizes) == ns else torch.tensor(sizes, dtype=torch.int32)
-        b = gp_ops.GPBatch(Zs, ys, torch.cat(pri), model.kernel_id, n_s=n_s, ard=ard or model.ard)
-        phi, _, _, _, info = gp_ops.fit(b, torch.cat(phi0))
-        gp_ops.check_info(info, "run_gp_ehvi_bo_batched fit")
-        b.flags |= gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+        b, phi = _fit_tasks("run_gp_ehvi_bo_batched", x_all, [(q, y_all[:, j]) for q in queried for j in range(2)], X, kernel_type, device,
+                            noise_init, noise_prior, ard)
         out = gp_ops.ehvi_pool(b, phi, X, obj=obj, ref=torch.stack(refs).cpu(), front=front, front_n=front_n, obj_maximize=obj_max, log=log,
                                topk=query_batch_size, exclude=queried, want_score=False)
         gp_ops.check_info(out["info"], "BO posterior")

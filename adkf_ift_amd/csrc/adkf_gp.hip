@@ -231,27 +231,8 @@ size_t adkf_predict_pool_scratch_bytes(int32_t T, int32_t k) {
 int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
                       const int64_t* excl_idx, const int64_t* excl_off, float* mean, float* var, float* ei, int32_t k, int64_t* top_idx,
                       float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
-    int rc = check_support_only(b, phi, info, ws, rows);
-    if (rc) return rc;
-    if (k < 0) return ADKF_E_BADARG;
-    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
-    const bool by_mean = (flags & ADKF_PM_SCORE_MEAN) != 0;
-    if ((flags & ADKF_PM_LOG_EI) && !ei && (k == 0 || by_mean)) return ADKF_E_BADARG;   // nothing would read it
-    if (rows > 0 && !X) return ADKF_E_BADARG;
-    if ((ei || (k > 0 && !by_mean)) && !best_f) return ADKF_E_BADARG;
-    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
-    if (!mean && !var && !ei && k == 0) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
-    if (k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
-    const PoolScratch l = pool_scratch(scratch, b->T, k);
-    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
-    PmCtx c;
-    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
-    if (rc) return rc;
-    PmPool pool = pm_pool(excl_idx, excl_off, k, b->T, l.cand_idx, l.cand_val, rows, c.st);
-    pool.score_mean = by_mean ? 1 : 0; pool.top_idx = top_idx; pool.top_val = top_val;
-    const PmCall io{flags & (ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI), X, nullptr, rows, best_f, mean, var, ei, info, &pool};
-    return c.ard ? pm_launch<true, true>(c, io) : pm_launch<false, true>(c, io);
+    return predict_pool(b, phi, flags, X, rows, best_f, excl_idx, excl_off, mean, var, ei, k, top_idx, top_val, info, ws, ws_bytes, scratch,
+                        scratch_bytes, stream);
 }
 
 size_t adkf_thompson_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t S, int32_t m) {

@@ -1,5 +1,6 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool and adkf_ehvi_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts and the launches.
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool and adkf_ehvi_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
+// pool calls share (pool_walks, pool_select, pool_greedy) and the body of every entry.
 #pragma once
 #include "host_ard.h"
 
@@ -202,41 +203,109 @@ int pm_launch_walk(const PmCtx& c, PmArgs& pa, PmPool* pool, const typename EPI:
     return 0;
 }
 
-// The streaming launches of a prepared call.
+// A float64 walk or a reference kernel of a pool call with the epilogue EPI: k_predict_marginal64, k_mes_walk64, k_kg_walk64, k_kg_refs ...
+template <bool ARD, class EPI>
+using PoolKernel = void (*)(PmArgsOf<ARD, true, EPI>);
+
+// The walks of a pool call over the whole pool with the epilogue EPI (arguments v): the plain tasks, the refined ones and, where
+// the caller has given the float64 walk a grid (pool.grid[2] > 0), the flagged ones with walk64.  No rows: nothing.
+template <bool ARD, class EPI>
+int pool_walks(const PmCtx& c, PmArgs& pa, PmPool& pool, const typename EPI::Args& v, PoolKernel<ARD, EPI> walk64 = nullptr) {
+    if (pa.rows <= 0) return 0;
+    const int T = c.b.T;
+    const int64_t tiles = ((pa.rows + PM_TM - 1) / PM_TM) * T;
+    int rc;
+    if ((rc = pm_launch_walk<false, ARD, true, EPI>(c, pa, &pool, v, tiles))) return rc;
+    if ((rc = pm_launch_walk<true, ARD, true, EPI>(c, pa, &pool, v, tiles))) return rc;
+    if (pool.grid[2] > 0) walk64<<<dim3(pool.grid[2], T), PM64_NT, 0, c.st>>>(pm_kargs<ARD, true, EPI>(c, pa, &pool, v));
+    return 0;
+}
+
+// the grid of the float64 walk of a pool call: 0 where none runs (run64: the call has a float64 region)
+inline int pool_grid64(const PmPool& pool, int64_t rows, bool run64) {
+    return (run64 && rows > 0) ? std::min(pm64_grid(rows), pool.chunks_max) : 0;
+}
+
+// "Score, then select" - adkf_predict_pool, adkf_mes_pool, adkf_kg_pool, adkf_jes_pool: (ARD) the 1 / l pass, the reference state
+// where the call has one (refs: n_refs workgroups per task, with or without rows), the walks and the merge of the lists.  The caller
+// has zeroed its outputs.
+template <bool ARD, class EPI>
+int pool_select(const PmCtx& c, PmArgs& pa, PmPool& pool, const typename EPI::Args& v, PoolKernel<ARD, EPI> walk64, bool run64,
+                PoolKernel<ARD, EPI> refs = nullptr, int n_refs = 0) {
+    const int T = c.b.T;
+    if constexpr (ARD) launch_ard_il(c);
+    if (refs) refs<<<dim3(n_refs, T), 256, 0, c.st>>>(pm_kargs<ARD, true, EPI>(c, pa, &pool, v));
+    pool.grid[2] = pool_grid64(pool, pa.rows, run64);
+    const int rc = pool_walks<ARD, EPI>(c, pa, pool, v, walk64);
+    if (rc) return rc;
+    if (pool.k > 0) k_pool_topk<<<T, 64, 0, c.st>>>(pm_kargs<false, true>(c, pa, &pool));
+    LAUNCH_OK();
+    return 0;
+}
+
+// "q greedy steps" - adkf_believer_pool(_ard) (v and bv are one) and adkf_gibbon_pool (bv = v.b): q chained steps, each the walks with
+// the epilogue EPI and the believer's one workgroup per task on the believer's arguments.
+template <bool ARD, class EPI>
+int pool_greedy(const PmCtx& c, PmArgs& pa, PmPool& pool, typename EPI::Args& v, BvArgs& bv, PoolKernel<ARD, EPI> walk64, bool have64) {
+    if constexpr (ARD) launch_ard_il(c);
+    pool.grid[2] = pool_grid64(pool, pa.rows, have64);
+    for (int j = 0; j < bv.q; ++j) {
+        bv.j = j;
+        const int rc = pool_walks<ARD, EPI>(c, pa, pool, v, walk64);
+        if (rc) return rc;
+        k_bv_step<ARD><<<c.b.T, 256, 0, c.st>>>(pm_kargs<ARD, true, BvEpilogue>(c, pa, &pool, bv));
+    }
+    LAUNCH_OK();
+    return 0;
+}
+
+// The streaming launches of a prepared prediction call.  POOL: pool_select with prediction's own epilogue.
 template <bool ARD, bool POOL = false>
 int pm_launch(const PmCtx& c, const PmCall& io) {
-    const Workspace& w = c.w;
     hipStream_t st = c.st;
-    PmPool* pool = io.pool;
     const int T = c.b.T;
     const int64_t rows = io.rows;
-    if constexpr (ARD) launch_ard_il(c);
     PmArgs pa = pm_args(c, io.flags, io.Zq, rows, io.info);
     pa.q_off = io.q_off; pa.best_f = io.best_f; pa.mean = io.mean; pa.var = io.var; pa.ei = io.ei;
-    // upper bound of the tile count (the true one depends on q_off, which lives on the device); POOL: the number of items
-    const int64_t tiles = POOL ? ((rows + PM_TM - 1) / PM_TM) * T : rows / PM_TM + T;
     // every output row starts at 0: rows outside every task's range and those of skipped tasks (n_s == 0, info != 0) stay so
     const size_t out_n = POOL ? (size_t)rows * T : (size_t)rows;
     if (io.mean && out_n) hipMemsetAsync(io.mean, 0, sizeof(float) * out_n, st);
     if (io.var && out_n) hipMemsetAsync(io.var, 0, sizeof(float) * out_n, st);
     if (io.ei && out_n) hipMemsetAsync(io.ei, 0, sizeof(float) * out_n, st);
-    int rc;
-    if (rows > 0) {
-        if ((rc = pm_launch_walk<false, ARD, POOL>(c, pa, pool, {}, tiles))) return rc;
-        if ((rc = pm_launch_walk<true, ARD, POOL>(c, pa, pool, {}, tiles))) return rc;
-    }
-    if (w.w64 && rows > 0) {
-        int gx = pm64_grid(rows);
-        if constexpr (POOL) {
-            gx = std::min(gx, pool->chunks_max);
-            pool->grid[2] = gx;
+    if constexpr (POOL) {
+        return pool_select<ARD, PmRowEpilogue>(c, pa, *io.pool, {}, k_predict_marginal64<ARD, true>, c.w.w64 != nullptr);
+    } else {
+        if constexpr (ARD) launch_ard_il(c);
+        // upper bound of the tile count (the true one depends on q_off, which lives on the device)
+        const int64_t tiles = rows / PM_TM + T;
+        int rc;
+        if (rows > 0) {
+            if ((rc = pm_launch_walk<false, ARD, false>(c, pa, nullptr, {}, tiles))) return rc;
+            if ((rc = pm_launch_walk<true, ARD, false>(c, pa, nullptr, {}, tiles))) return rc;
         }
-        k_predict_marginal64<ARD, POOL><<<dim3(gx, T), PM64_NT, 0, st>>>(pm_kargs<ARD, POOL>(c, pa, pool));
+        if (c.w.w64 && rows > 0) k_predict_marginal64<ARD, false><<<dim3(pm64_grid(rows), T), PM64_NT, 0, st>>>(pm_kargs<ARD, false>(c, pa, nullptr));
+        LAUNCH_OK();
+        return 0;
     }
-    if constexpr (POOL)
-        if (pool->k > 0) k_pool_topk<<<T, 64, 0, st>>>(pm_kargs<false, true>(c, pa, pool));
-    LAUNCH_OK();
-    return 0;
+}
+
+// What every pool entry asks after check_support_only: a pool where there are rows, and exclusion lists only with their offsets
+inline bool pool_args_ok(const float* X, int64_t rows, const int64_t* excl_idx, const int64_t* excl_off) {
+    return !(rows > 0 && !X) && !(excl_idx && !excl_off);
+}
+
+// the selection of k rows per task: k itself and the two outputs it needs
+inline int check_topk(int k, const int64_t* top_idx, const float* top_val) {
+    if (k < 0 || (k > 0 && (!top_idx || !top_val))) return ADKF_E_BADARG;
+    return k > ADKF_POOL_TOPK_MAX ? ADKF_E_SIZE : 0;
+}
+
+// Whether the call keeps float64 twins of its own state for flagged tasks: the workspace has a float64 region and the scratch, at this
+// shape, the twins.  Without them no task takes the float64 walk.
+inline bool pm_have64(const PmCtx& c, PmArgs& pa) {
+    const bool have64 = c.w.w64 && c.b.ns_max <= R64_MAXN;
+    if (!have64) pa.r64_thresh = INFINITY;
+    return have64;
 }
 
 // What adkf_predict_marginal, adkf_thompson_pool (with their ARD forms) and adkf_predict_pool ask of their batch and first arguments:
@@ -266,6 +335,23 @@ int predict_marginal(bool ard, const adkf_batch_t* b, const float* phi, int32_t 
     return ard ? pm_launch<true>(c, io) : pm_launch<false>(c, io);
 }
 
+// The candidate lists at the end of a scratch: n row indices (int64), then n scores
+struct CandLists { int64_t* idx; float* val; };
+inline CandLists carve_cand(Arena& ar, size_t n) {
+    int64_t* idx = ar.as<int64_t>(n);
+    return {idx, ar.floats(n)};
+}
+
+// The head of the believer's, the knowledge gradient's and joint entropy search's scratch, for n entries per task: w [T, n, ns], its
+// float64 twin where a workspace of this shape can have a float64 region, and the entries' feature rows [T, n, d]
+struct RefHead { float* W; double* W64; float* Xp; };
+inline RefHead carve_ref_head(Arena& ar, int T, int n, int ns, int d) {
+    const size_t e = (size_t)T * n * ns;
+    float* W = ar.floats(e);
+    double* W64 = ar.as<double>(ns <= R64_MAXN ? e : 0);
+    return {W, W64, ar.floats((size_t)T * n * d)};
+}
+
 // adkf_thompson_pool: the scratch is V [T, S, ns] (float32), the same in float64 for flagged tasks where the workspace of this
 // shape can have a float64 region, and one (row, score) pair per (task, chunk, sample)
 struct TsScratch { float* v; double* v64; int64_t* cand_idx; float* cand_val; size_t bytes; };
@@ -275,8 +361,8 @@ inline TsScratch ts_scratch(void* base, int T, int ns, int S) {
     const size_t e = (size_t)T * S * ns, c = (size_t)T * pm_pool_chunks_max(T) * S;
     float* v = ar.floats(e);
     double* v64 = ar.as<double>(ns <= R64_MAXN ? e : 0);
-    int64_t* cand_idx = ar.as<int64_t>(c);
-    return {v, v64, cand_idx, ar.floats(c), ar.off};
+    const CandLists cand = carve_cand(ar, c);
+    return {v, v64, cand.idx, cand.val, ar.off};
 }
 
 // adkf_predict_pool: the scratch is the candidate lists, cand_idx [T, chunks_max, k] (int64) directly followed by cand_val (float32)
@@ -323,9 +409,8 @@ int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
     if (rc) return rc;
     if (is_ard(b) != ard) return ADKF_E_BADARG;
     if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (!omega || !phase || !w || !eps || !sel_idx || !sel_val) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
     if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
     if (m < 64 || m > ADKF_TS_FEATURES_MAX || (m & 63)) return ADKF_E_SIZE;
     const TsScratch l = ts_scratch(scratch, b->T, b->ns_max, S);
@@ -334,7 +419,7 @@ int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
     rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
     hipStream_t st = c.st;
-    const int T = b->T, ns = b->ns_max;
+    const int T = b->T;
     TsArgs ta{};
     ta.p = pm_args(c, flags, X, rows, info);
     ta.s = pm_pool(excl_idx, excl_off, S, T, l.cand_idx, l.cand_val, rows, st);
@@ -342,8 +427,7 @@ int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
     ta.omega = omega; ta.phase = phase; ta.w = w; ta.eps = eps; ta.m = m; ta.S = S;
     ta.vec_om = ((b->d & 3) == 0 && aligned16(omega)) ? 1 : 0;
     ta.V = l.v;
-    ta.V64 = (c.w.w64 && ns <= R64_MAXN) ? l.v64 : nullptr;
-    if (!ta.V64) ta.p.r64_thresh = INFINITY;
+    ta.V64 = pm_have64(c, ta.p) ? l.v64 : nullptr;
     ta.paths = paths;
     // skipped tasks keep zeros in paths
     if (paths && rows > 0) hipMemsetAsync(paths, 0, sizeof(float) * (size_t)T * S * (size_t)rows, st);
@@ -353,45 +437,29 @@ int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
 // adkf_believer_pool: the scratch is w [T, q, ns] (and its float64 twin where a workspace of this shape can have a float64 region),
 // the picks' feature rows [T, q, d], G [T, q, q] (and its twin), the incumbent and the pick count per task, and one (row, score)
 // pair per (task, chunk)
-struct BvScratch { float* W; double* W64; float* Xp; float* G; double* G64; float* best; int32_t* cnt; int64_t* cand_idx; float* cand_val; size_t bytes; };
+struct BvScratch { RefHead h; float* G; double* G64; float* best; int32_t* cnt; CandLists cand; size_t bytes; };
 inline BvScratch bv_scratch(void* base, int T, int ns, int d, int q) {
     Arena ar{static_cast<char*>(base), 0};
-    const size_t e = (size_t)T * q * ns, g = (size_t)T * q * q, c = (size_t)T * pm_pool_chunks_max(T);
+    const size_t g = (size_t)T * q * q;
     BvScratch l{};
-    l.W = ar.floats(e);
-    l.W64 = ar.as<double>(ns <= R64_MAXN ? e : 0);
-    l.Xp = ar.floats((size_t)T * q * d);
+    l.h = carve_ref_head(ar, T, q, ns, d);
     l.G = ar.floats(g);
     l.G64 = ar.as<double>(ns <= R64_MAXN ? g : 0);
     l.best = ar.floats((size_t)T);
     l.cnt = ar.as<int32_t>((size_t)T);
-    l.cand_idx = ar.as<int64_t>(c);
-    l.cand_val = ar.floats(c);
+    l.cand = carve_cand(ar, (size_t)T * pm_pool_chunks_max(T));
     l.bytes = ar.off;
     return l;
 }
 
-// The steps of a prepared believer call: q chained steps, each the walks of prediction with the believer's epilogue and one workgroup
-// per task.  ARD: c.r names the query scaling, whose 1 / l goes into ArdWs::c first (as pm_launch).
-template <bool ARD>
-int bv_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, BvArgs& v, int64_t rows, bool have64) {
-    hipStream_t st = c.st;
-    const int T = c.b.T;
-    if constexpr (ARD) launch_ard_il(c);
-    const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
-    pool.grid[2] = (have64 && rows > 0) ? std::min(pm64_grid(rows), pool.chunks_max) : 0;
-    int rc;
-    for (int j = 0; j < v.q; ++j) {
-        v.j = j;
-        if (rows > 0) {
-            if ((rc = pm_launch_walk<false, ARD, true, BvEpilogue>(c, pa, &pool, v, tiles))) return rc;
-            if ((rc = pm_launch_walk<true, ARD, true, BvEpilogue>(c, pa, &pool, v, tiles))) return rc;
-            if (have64) k_bv_walk64<ARD><<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(pm_kargs<ARD, true, BvEpilogue>(c, pa, &pool, v));
-        }
-        k_bv_step<ARD><<<T, 256, 0, st>>>(pm_kargs<ARD, true, BvEpilogue>(c, pa, &pool, v));
-    }
-    LAUNCH_OK();
-    return 0;
+// The believer's arguments on its scratch
+BvArgs bv_args(const BvScratch& l, bool have64, int q, float* trace, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var) {
+    BvArgs v{};
+    v.q = q;
+    v.W = l.h.W; v.W64 = have64 ? l.h.W64 : nullptr; v.Xp = l.h.Xp; v.G = l.G; v.G64 = have64 ? l.G64 : nullptr;
+    v.best = l.best; v.cnt = l.cnt; v.trace = trace;
+    v.sel_idx = sel_idx; v.sel_val = sel_val; v.sel_mean = sel_mean; v.sel_var = sel_var;
+    return v;
 }
 
 // adkf_believer_pool and adkf_believer_pool_ard: the same call on a batch that is (ard) or is not an ARD batch
@@ -402,9 +470,8 @@ int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
     if (rc) return rc;
     if (is_ard(b) != ard) return ADKF_E_BADARG;
     if (flags & ~(ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (!best_f || !sel_idx || !sel_val) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
     if (q < 1) return ADKF_E_BADARG;
     if (q > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
     const BvScratch l = bv_scratch(scratch, b->T, b->ns_max, b->d, q);
@@ -413,45 +480,41 @@ int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
     rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
     hipStream_t st = c.st;
-    const int T = b->T, ns = b->ns_max;
+    const int T = b->T;
     PmArgs pa = pm_args(c, flags, X, rows, info);
     pa.best_f = best_f;
-    const bool have64 = c.w.w64 && ns <= R64_MAXN;
-    if (!have64) pa.r64_thresh = INFINITY;
-    PmPool pool = pm_pool(excl_idx, excl_off, 1, T, l.cand_idx, l.cand_val, rows, st);
-    BvArgs v{};
-    v.q = q;
-    v.W = l.W; v.W64 = have64 ? l.W64 : nullptr; v.Xp = l.Xp; v.G = l.G; v.G64 = have64 ? l.G64 : nullptr;
-    v.best = l.best; v.cnt = l.cnt; v.trace = trace;
-    v.sel_idx = sel_idx; v.sel_val = sel_val; v.sel_mean = sel_mean; v.sel_var = sel_var;
+    const bool have64 = pm_have64(c, pa);
+    PmPool pool = pm_pool(excl_idx, excl_off, 1, T, l.cand.idx, l.cand.val, rows, st);
+    BvArgs v = bv_args(l, have64, q, trace, sel_idx, sel_val, sel_mean, sel_var);
     // skipped tasks keep zeros in trace
     if (trace && rows > 0) hipMemsetAsync(trace, 0, sizeof(float) * (size_t)T * q * (size_t)rows, st);
     k_bv_init<<<ceil_div(T, 256), 256, 0, st>>>(v, best_f, T);
-    return ard ? bv_launch<true>(c, pa, pool, v, rows, have64) : bv_launch<false>(c, pa, pool, v, rows, have64);
+    return ard ? pool_greedy<true, BvEpilogue>(c, pa, pool, v, v, k_bv_walk64<true>, have64)
+               : pool_greedy<false, BvEpilogue>(c, pa, pool, v, v, k_bv_walk64<false>, have64);
 }
 
-// The launches of a prepared max-value entropy search call, as pm_launch<ARD, true>: the walks of prediction with MesEpilogue, the
-// float64 walk where the workspace has a float64 region, then prediction's merge of the lists.
-template <bool ARD>
-int mes_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, const MesArgs& v, int64_t rows) {
-    hipStream_t st = c.st;
-    const int T = c.b.T;
-    if constexpr (ARD) launch_ard_il(c);
-    const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
-    // every score starts at 0: the rows of skipped tasks (n_s == 0, info != 0) stay so
-    if (v.score && rows > 0) hipMemsetAsync(v.score, 0, sizeof(float) * (size_t)rows * T, st);
-    int rc;
-    if (rows > 0) {
-        if ((rc = pm_launch_walk<false, ARD, true, MesEpilogue>(c, pa, &pool, v, tiles))) return rc;
-        if ((rc = pm_launch_walk<true, ARD, true, MesEpilogue>(c, pa, &pool, v, tiles))) return rc;
-    }
-    if (c.w.w64 && rows > 0) {
-        pool.grid[2] = std::min(pm64_grid(rows), pool.chunks_max);
-        k_mes_walk64<ARD><<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(pm_kargs<ARD, true, MesEpilogue>(c, pa, &pool, v));
-    }
-    if (pool.k > 0) k_pool_topk<<<T, 64, 0, st>>>(pm_kargs<false, true>(c, pa, &pool));
-    LAUNCH_OK();
-    return 0;
+// adkf_predict_pool: isotropic and ARD batches alike
+int predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
+                 const int64_t* excl_idx, const int64_t* excl_off, float* mean, float* var, float* ei, int32_t k, int64_t* top_idx,
+                 float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    const bool by_mean = (flags & ADKF_PM_SCORE_MEAN) != 0;
+    if ((flags & ADKF_PM_LOG_EI) && !ei && (k == 0 || by_mean)) return ADKF_E_BADARG;   // nothing would read it
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
+    if ((ei || (k > 0 && !by_mean)) && !best_f) return ADKF_E_BADARG;
+    if (!mean && !var && !ei && k == 0) return ADKF_E_BADARG;
+    if ((rc = check_topk(k, top_idx, top_val))) return rc;
+    const PoolScratch l = pool_scratch(scratch, b->T, k);
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    PmPool pool = pm_pool(excl_idx, excl_off, k, b->T, l.cand_idx, l.cand_val, rows, c.st);
+    pool.score_mean = by_mean ? 1 : 0; pool.top_idx = top_idx; pool.top_val = top_val;
+    const PmCall io{flags & (ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI), X, nullptr, rows, best_f, mean, var, ei, info, &pool};
+    return c.ard ? pm_launch<true, true>(c, io) : pm_launch<false, true>(c, io);
 }
 
 // adkf_mes_pool: isotropic and ARD batches alike (as adkf_predict_pool); the scratch is adkf_predict_pool's candidate lists
@@ -462,13 +525,10 @@ int mes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float
     if (rc) return rc;
     if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
     if (!ystar) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
-    if (k < 0) return ADKF_E_BADARG;
-    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (k == 0 && !score) return ADKF_E_BADARG;
+    if ((rc = check_topk(k, top_idx, top_val))) return rc;
     if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
-    if (k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
     const PoolScratch l = pool_scratch(scratch, b->T, k);
     if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
     PmCtx c;
@@ -478,30 +538,11 @@ int mes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float
     pool.top_idx = top_idx; pool.top_val = top_val;
     PmArgs pa = pm_args(c, flags, X, rows, info);
     const MesArgs v{ystar, S, score};
-    return c.ard ? mes_launch<true>(c, pa, pool, v, rows) : mes_launch<false>(c, pa, pool, v, rows);
-}
-
-// The steps of a prepared GIBBON call, as bv_launch: q chained steps, each the walks of prediction with GibbonEpilogue, the float64
-// walk, and the believer's own k_bv_step on the believer's part of the arguments.
-template <bool ARD>
-int gibbon_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, GibbonArgs& v, int64_t rows, bool have64) {
-    hipStream_t st = c.st;
-    const int T = c.b.T;
-    if constexpr (ARD) launch_ard_il(c);
-    const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
-    pool.grid[2] = (have64 && rows > 0) ? std::min(pm64_grid(rows), pool.chunks_max) : 0;
-    int rc;
-    for (int j = 0; j < v.b.q; ++j) {
-        v.b.j = j;
-        if (rows > 0) {
-            if ((rc = pm_launch_walk<false, ARD, true, GibbonEpilogue>(c, pa, &pool, v, tiles))) return rc;
-            if ((rc = pm_launch_walk<true, ARD, true, GibbonEpilogue>(c, pa, &pool, v, tiles))) return rc;
-            if (have64) k_gb_walk64<ARD><<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(pm_kargs<ARD, true, GibbonEpilogue>(c, pa, &pool, v));
-        }
-        k_bv_step<ARD><<<T, 256, 0, st>>>(pm_kargs<ARD, true, BvEpilogue>(c, pa, &pool, v.b));
-    }
-    LAUNCH_OK();
-    return 0;
+    // every score starts at 0: the rows of skipped tasks (n_s == 0, info != 0) stay so
+    if (score && rows > 0) hipMemsetAsync(score, 0, sizeof(float) * (size_t)rows * b->T, c.st);
+    // (no scratch twin: the float64 walk runs wherever the workspace has a float64 region)
+    return c.ard ? pool_select<true, MesEpilogue>(c, pa, pool, v, k_mes_walk64<true>, c.w.w64 != nullptr)
+                 : pool_select<false, MesEpilogue>(c, pa, pool, v, k_mes_walk64<false>, c.w.w64 != nullptr);
 }
 
 // adkf_gibbon_pool: isotropic and ARD batches alike (as adkf_mes_pool); the scratch is the believer's, with the believer's layout
@@ -511,9 +552,8 @@ int gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const fl
     int rc = check_support_only(b, phi, info, ws, rows);
     if (rc) return rc;
     if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (!ystar || !sel_idx || !sel_val) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
     if (q < 1 || S < 1) return ADKF_E_BADARG;
     if (q > ADKF_POOL_TOPK_MAX || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
     const BvScratch l = bv_scratch(scratch, b->T, b->ns_max, b->d, q);
@@ -522,67 +562,34 @@ int gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const fl
     rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
     hipStream_t st = c.st;
-    const int T = b->T, ns = b->ns_max;
+    const int T = b->T;
     PmArgs pa = pm_args(c, flags, X, rows, info);
-    const bool have64 = c.w.w64 && ns <= R64_MAXN;
-    if (!have64) pa.r64_thresh = INFINITY;
-    PmPool pool = pm_pool(excl_idx, excl_off, 1, T, l.cand_idx, l.cand_val, rows, st);
+    const bool have64 = pm_have64(c, pa);
+    PmPool pool = pm_pool(excl_idx, excl_off, 1, T, l.cand.idx, l.cand.val, rows, st);
     GibbonArgs v{};
-    v.b.q = q;
-    v.b.W = l.W; v.b.W64 = have64 ? l.W64 : nullptr; v.b.Xp = l.Xp; v.b.G = l.G; v.b.G64 = have64 ? l.G64 : nullptr;
-    v.b.best = l.best; v.b.cnt = l.cnt; v.b.trace = trace;
-    v.b.sel_idx = sel_idx; v.b.sel_val = sel_val; v.b.sel_mean = sel_mean; v.b.sel_var = sel_var;
+    v.b = bv_args(l, have64, q, trace, sel_idx, sel_val, sel_mean, sel_var);
     v.ystar = ystar; v.S = S;
     // skipped tasks keep zeros in trace
     if (trace && rows > 0) hipMemsetAsync(trace, 0, sizeof(float) * (size_t)T * q * (size_t)rows, st);
     // there is no incumbent: the believer's slot [T] is filled from the first T floats of ystar (S >= 1) and never read by a score
     k_bv_init<<<ceil_div(T, 256), 256, 0, st>>>(v.b, ystar, T);
-    return c.ard ? gibbon_launch<true>(c, pa, pool, v, rows, have64) : gibbon_launch<false>(c, pa, pool, v, rows, have64);
+    return c.ard ? pool_greedy<true, GibbonEpilogue>(c, pa, pool, v, v.b, k_gb_walk64<true>, have64)
+                 : pool_greedy<false, GibbonEpilogue>(c, pa, pool, v, v.b, k_gb_walk64<false>, have64);
 }
 
 // adkf_kg_pool: the scratch is the reference state - w [T, M, ns] (and its float64 twin where a workspace of this shape can have a
 // float64 region), the entries' feature rows [T, M, d], their means [T, M] and their pool rows [T, M] (-1: a skipped entry) - and
 // prediction's candidate lists [T, chunks_max, k].  It does not depend on rows.
-struct KgScratch { float* W; double* W64; float* Xp; float* am; int64_t* ridx; int64_t* cand_idx; float* cand_val; size_t bytes; };
+struct KgScratch { RefHead h; float* am; int64_t* ridx; CandLists cand; size_t bytes; };
 inline KgScratch kg_scratch(void* base, int T, int ns, int d, int M, int k) {
     Arena ar{static_cast<char*>(base), 0};
-    const size_t e = (size_t)T * M * ns, c = (size_t)T * pm_pool_chunks_max(T) * k;
     KgScratch l{};
-    l.W = ar.floats(e);
-    l.W64 = ar.as<double>(ns <= R64_MAXN ? e : 0);
-    l.Xp = ar.floats((size_t)T * M * d);
+    l.h = carve_ref_head(ar, T, M, ns, d);
     l.am = ar.floats((size_t)T * M);
     l.ridx = ar.as<int64_t>((size_t)T * M);
-    l.cand_idx = ar.as<int64_t>(c);
-    l.cand_val = ar.floats(c);
+    l.cand = carve_cand(ar, (size_t)T * pm_pool_chunks_max(T) * k);
     l.bytes = ar.off;
     return l;
-}
-
-// The launches of a prepared knowledge-gradient call: the reference state (one workgroup per entry and task), then as mes_launch - the
-// walks of prediction with KgEpilogue, the float64 walk, prediction's merge of the lists.
-template <bool ARD>
-int kg_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, const KgArgs& v, int64_t rows, bool have64) {
-    hipStream_t st = c.st;
-    const int T = c.b.T;
-    if constexpr (ARD) launch_ard_il(c);
-    const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
-    // every output starts at 0: the rows of skipped tasks (n_s == 0, info != 0) stay so
-    if (v.score && rows > 0) hipMemsetAsync(v.score, 0, sizeof(float) * (size_t)rows * T, st);
-    if (v.cov && rows > 0) hipMemsetAsync(v.cov, 0, sizeof(float) * (size_t)rows * T * v.M, st);
-    k_kg_refs<ARD><<<dim3(v.M, T), 256, 0, st>>>(pm_kargs<ARD, true, KgEpilogue>(c, pa, &pool, v));
-    int rc;
-    if (rows > 0) {
-        if ((rc = pm_launch_walk<false, ARD, true, KgEpilogue>(c, pa, &pool, v, tiles))) return rc;
-        if ((rc = pm_launch_walk<true, ARD, true, KgEpilogue>(c, pa, &pool, v, tiles))) return rc;
-    }
-    if (have64 && rows > 0) {
-        pool.grid[2] = std::min(pm64_grid(rows), pool.chunks_max);
-        k_kg_walk64<ARD><<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(pm_kargs<ARD, true, KgEpilogue>(c, pa, &pool, v));
-    }
-    if (pool.k > 0) k_pool_topk<<<T, 64, 0, st>>>(pm_kargs<false, true>(c, pa, &pool));
-    LAUNCH_OK();
-    return 0;
 }
 
 // adkf_kg_pool: isotropic and ARD batches alike (as adkf_mes_pool)
@@ -593,76 +600,48 @@ int kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float*
     if (rc) return rc;
     if (flags & ~(ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
     if (!ref_idx) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
-    if (k < 0) return ADKF_E_BADARG;
-    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (k == 0 && !score && !cov && !ref_mean) return ADKF_E_BADARG;
-    if (M < 1 || M > ADKF_KG_REFS_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    if ((rc = check_topk(k, top_idx, top_val))) return rc;
+    if (M < 1 || M > ADKF_KG_REFS_MAX) return ADKF_E_SIZE;
     const KgScratch l = kg_scratch(scratch, b->T, b->ns_max, b->d, M, k);
     if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
     PmCtx c;
     rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
-    PmPool pool = pm_pool(excl_idx, excl_off, k, b->T, l.cand_idx, l.cand_val, rows, c.st);
+    PmPool pool = pm_pool(excl_idx, excl_off, k, b->T, l.cand.idx, l.cand.val, rows, c.st);
     pool.top_idx = top_idx; pool.top_val = top_val;
     PmArgs pa = pm_args(c, flags, X, rows, info);
-    const bool have64 = c.w.w64 && b->ns_max <= R64_MAXN;
-    if (!have64) pa.r64_thresh = INFINITY;
+    const bool have64 = pm_have64(c, pa);
     KgArgs v{};
     v.M = M; v.ref_idx = ref_idx;
-    v.W = l.W; v.W64 = have64 ? l.W64 : nullptr; v.Xp = l.Xp; v.am = l.am; v.ridx = l.ridx;
+    v.W = l.h.W; v.W64 = have64 ? l.h.W64 : nullptr; v.Xp = l.h.Xp; v.am = l.am; v.ridx = l.ridx;
     v.score = score; v.cov = cov; v.ref_mean = ref_mean;
-    return c.ard ? kg_launch<true>(c, pa, pool, v, rows, have64) : kg_launch<false>(c, pa, pool, v, rows, have64);
+    // every output starts at 0: the rows of skipped tasks (n_s == 0, info != 0) stay so
+    if (score && rows > 0) hipMemsetAsync(score, 0, sizeof(float) * (size_t)rows * b->T, c.st);
+    if (cov && rows > 0) hipMemsetAsync(cov, 0, sizeof(float) * (size_t)rows * b->T * M, c.st);
+    return c.ard ? pool_select<true, KgEpilogue>(c, pa, pool, v, k_kg_walk64<true>, have64, k_kg_refs<true>, M)
+                 : pool_select<false, KgEpilogue>(c, pa, pool, v, k_kg_walk64<false>, have64, k_kg_refs<false>, M);
 }
 
 // adkf_jes_pool: the scratch is the knowledge gradient's reference state for M = S - w [T, S, ns] (and its float64 twin where a
 // workspace of this shape can have a float64 region), the entries' feature rows [T, S, d], their means and pool rows [T, S] - then the
 // entries' latent variance, 1 / d_s and gain [T, S] each, the task's scale [T], and prediction's candidate lists [T, chunks_max, k].
 // It does not depend on rows.
-struct JesScratch { float* W; double* W64; float* Xp; float *am, *ov, *invd, *gain, *scale; int64_t* ridx; int64_t* cand_idx; float* cand_val; size_t bytes; };
+struct JesScratch { RefHead h; float *am, *ov, *invd, *gain, *scale; int64_t* ridx; CandLists cand; size_t bytes; };
 inline JesScratch jes_scratch(void* base, int T, int ns, int d, int S, int k) {
     Arena ar{static_cast<char*>(base), 0};
-    const size_t e = (size_t)T * S * ns, c = (size_t)T * pm_pool_chunks_max(T) * k;
     JesScratch l{};
-    l.W = ar.floats(e);
-    l.W64 = ar.as<double>(ns <= R64_MAXN ? e : 0);
-    l.Xp = ar.floats((size_t)T * S * d);
+    l.h = carve_ref_head(ar, T, S, ns, d);
     l.am = ar.floats((size_t)T * S);
     l.ridx = ar.as<int64_t>((size_t)T * S);
     l.ov = ar.floats((size_t)T * S);
     l.invd = ar.floats((size_t)T * S);
     l.gain = ar.floats((size_t)T * S);
     l.scale = ar.floats((size_t)T);
-    l.cand_idx = ar.as<int64_t>(c);
-    l.cand_val = ar.floats(c);
+    l.cand = carve_cand(ar, (size_t)T * pm_pool_chunks_max(T) * k);
     l.bytes = ar.off;
     return l;
-}
-
-// The launches of a prepared joint-entropy-search call, as kg_launch: the reference state (one workgroup per sample and task), the
-// walks of prediction with JesEpilogue, the float64 walk, prediction's merge of the lists.
-template <bool ARD>
-int jes_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, const JesArgs& v, int64_t rows, bool have64) {
-    hipStream_t st = c.st;
-    const int T = c.b.T;
-    if constexpr (ARD) launch_ard_il(c);
-    const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
-    // every score starts at 0: the rows of skipped tasks (n_s == 0, info != 0) stay so
-    if (v.score && rows > 0) hipMemsetAsync(v.score, 0, sizeof(float) * (size_t)rows * T, st);
-    k_jes_refs<ARD><<<dim3(v.S, T), 256, 0, st>>>(pm_kargs<ARD, true, JesEpilogue>(c, pa, &pool, v));
-    int rc;
-    if (rows > 0) {
-        if ((rc = pm_launch_walk<false, ARD, true, JesEpilogue>(c, pa, &pool, v, tiles))) return rc;
-        if ((rc = pm_launch_walk<true, ARD, true, JesEpilogue>(c, pa, &pool, v, tiles))) return rc;
-    }
-    if (have64 && rows > 0) {
-        pool.grid[2] = std::min(pm64_grid(rows), pool.chunks_max);
-        k_jes_walk64<ARD><<<dim3(pool.grid[2], T), PM64_NT, 0, st>>>(pm_kargs<ARD, true, JesEpilogue>(c, pa, &pool, v));
-    }
-    if (pool.k > 0) k_pool_topk<<<T, 64, 0, st>>>(pm_kargs<false, true>(c, pa, &pool));
-    LAUNCH_OK();
-    return 0;
 }
 
 // adkf_jes_pool: isotropic and ARD batches alike (as adkf_kg_pool)
@@ -675,28 +654,28 @@ int jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float
     if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
     if (!opt_idx || !opt_val) return ADKF_E_BADARG;
     if (!(cond_noise >= 0.f && cond_noise < INFINITY)) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
-    if (k < 0) return ADKF_E_BADARG;
-    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (k == 0 && !score && !opt_mean && !opt_var) return ADKF_E_BADARG;
-    if (S < 1 || S > ADKF_TS_SAMPLES_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    if ((rc = check_topk(k, top_idx, top_val))) return rc;
+    if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
     const JesScratch l = jes_scratch(scratch, b->T, b->ns_max, b->d, S, k);
     if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
     PmCtx c;
     rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
     if (rc) return rc;
-    PmPool pool = pm_pool(excl_idx, excl_off, k, b->T, l.cand_idx, l.cand_val, rows, c.st);
+    PmPool pool = pm_pool(excl_idx, excl_off, k, b->T, l.cand.idx, l.cand.val, rows, c.st);
     pool.top_idx = top_idx; pool.top_val = top_val;
     PmArgs pa = pm_args(c, flags, X, rows, info);
-    const bool have64 = c.w.w64 && b->ns_max <= R64_MAXN;
-    if (!have64) pa.r64_thresh = INFINITY;
+    const bool have64 = pm_have64(c, pa);
     JesArgs v{};
     v.S = S; v.opt_idx = opt_idx; v.opt_val = opt_val; v.cond_noise = cond_noise;
-    v.W = l.W; v.W64 = have64 ? l.W64 : nullptr; v.Xp = l.Xp; v.am = l.am; v.ov = l.ov; v.invd = l.invd; v.gain = l.gain; v.ridx = l.ridx;
+    v.W = l.h.W; v.W64 = have64 ? l.h.W64 : nullptr; v.Xp = l.h.Xp; v.am = l.am; v.ov = l.ov; v.invd = l.invd; v.gain = l.gain; v.ridx = l.ridx;
     v.scale = l.scale;
     v.score = score; v.opt_mean = opt_mean; v.opt_var = opt_var;
-    return c.ard ? jes_launch<true>(c, pa, pool, v, rows, have64) : jes_launch<false>(c, pa, pool, v, rows, have64);
+    // every score starts at 0: the rows of skipped tasks (n_s == 0, info != 0) stay so
+    if (score && rows > 0) hipMemsetAsync(score, 0, sizeof(float) * (size_t)rows * b->T, c.st);
+    return c.ard ? pool_select<true, JesEpilogue>(c, pa, pool, v, k_jes_walk64<true>, have64, k_jes_refs<true>, S)
+                 : pool_select<false, JesEpilogue>(c, pa, pool, v, k_jes_walk64<false>, have64, k_jes_refs<false>, S);
 }
 
 // adkf_gumbel_pool: the scratch is the fixed-point sums [T, 64] (uint64), the probes [T, 64] (float32) and the images of the two
@@ -731,12 +710,11 @@ int gb_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, GumbelArgs v, int64_t ro
     const int T = c.b.T;
     if (rows > 0) {
         if constexpr (ARD) launch_ard_il(c);
-        const int64_t tiles = ((rows + PM_TM - 1) / PM_TM) * T;
         for (int walk = 0; walk < 3; ++walk) {
             v.bracket = walk == 0 ? 1 : 0;
-            int rc;
-            if ((rc = pm_launch_walk<false, ARD, true, GumbelEpilogue>(c, pa, &pool, v, tiles))) return rc;
-            if ((rc = pm_launch_walk<true, ARD, true, GumbelEpilogue>(c, pa, &pool, v, tiles))) return rc;
+            const int rc = pool_walks<ARD, GumbelEpilogue>(c, pa, pool, v);
+            if (rc) return rc;
+            // (on the whole of pm64_grid: there are no lists, so pool.grid[2] stays 0 and pool_walks launches no float64 walk)
             if (c.w.w64) k_gumbel_walk64<ARD><<<dim3(pm64_grid(rows), T), PM64_NT, 0, st>>>(pm_kargs<ARD, true, GumbelEpilogue>(c, pa, &pool, v));
             if (walk < 2) k_gumbel_window<<<T, 64, 0, st>>>(v, walk);
         }
@@ -754,7 +732,7 @@ int gumbel_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const fl
     if (rc) return rc;
     if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
     if (!u || !ystar) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, nullptr, nullptr)) return ADKF_E_BADARG;
     if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
     if (rows > GB_ROWS_MAX) return ADKF_E_SIZE;
     const GbScratch l = gb_scratch(scratch, b->T);
@@ -776,7 +754,7 @@ int gumbel_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const fl
 // adkf_ehvi_pool: the scratch is stage A's mean and latent variance of one chunk of the pool, [T, EHVI_CHUNK_ROWS] each, the groups'
 // state [G] and the candidate lists, one per (group, walker), at most max(PM_POOL_LISTS, G) of k entries.  It depends on neither rows,
 // ns nor d, and it does not shrink when T, G or k grow.
-struct EhviScratch { float *m, *v; EhviGroup* grp; int64_t* cand_idx; float* cand_val; size_t bytes; };
+struct EhviScratch { float *m, *v; EhviGroup* grp; CandLists cand; size_t bytes; };
 inline EhviScratch ehvi_scratch(void* base, int T, int G, int k) {
     Arena ar{static_cast<char*>(base), 0};
     const size_t mv = (size_t)T * EHVI_CHUNK_ROWS, c = (size_t)std::max(PM_POOL_LISTS, G) * k;
@@ -784,8 +762,7 @@ inline EhviScratch ehvi_scratch(void* base, int T, int G, int k) {
     l.m = ar.floats(mv);
     l.v = ar.floats(mv);
     l.grp = ar.as<EhviGroup>((size_t)G);
-    l.cand_idx = ar.as<int64_t>(c);
-    l.cand_val = ar.floats(c);
+    l.cand = carve_cand(ar, c);
     l.bytes = ar.off;
     return l;
 }
@@ -838,8 +815,7 @@ int ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const floa
     if (!obj || !ref || !front_n) return ADKF_E_BADARG;
     if (P > 0 && !front) return ADKF_E_BADARG;
     if (C > 0 && (!con || !con_thr || !con_geq)) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
     if (k == 0 && !score && !stair && !stair_n) return ADKF_E_BADARG;
     const EhviScratch l = ehvi_scratch(scratch, b->T, G, k);
@@ -856,7 +832,7 @@ int ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const floa
     e.rows = rows; e.score = score;
     e.s.excl_idx = excl_off ? excl_idx : nullptr; e.s.excl_off = excl_off;
     e.s.k = k; e.s.chunks_max = pm_pool_chunks_max(G);
-    e.s.cand_idx = l.cand_idx; e.s.cand_val = l.cand_val;
+    e.s.cand_idx = l.cand.idx; e.s.cand_val = l.cand.val;
     e.s.top_idx = top_idx; e.s.top_val = top_val;
     return c.ard ? ehvi_launch<true>(c, e, X, rows, info) : ehvi_launch<false>(c, e, X, rows, info);
 }

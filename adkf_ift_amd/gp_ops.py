@@ -359,6 +359,62 @@ def pack_exclude(exclude, T: int, rows: int, device=None) -> Tuple[torch.Tensor,
     return idx.contiguous(), off
 
 
+def _support_only(b, name: str) -> None:
+    if b.nq != 0:
+        raise ValueError(f"{name} takes a support-only batch (no Z_q / y_q): the pool comes in X")
+
+
+def _in_range(value, lo: int, hi: int, what: str) -> int:
+    value = int(value)
+    if value < lo or value > hi:
+        raise ValueError(f"{what} must be in [{lo}, {hi}], got {value}")
+    return value
+
+
+def _phi_and_pool(b, phi, X):
+    """``phi`` as the batch takes it and the pool ``X`` as float32 ``[rows, d]``."""
+    phi = b.check_phi(phi)
+    X = _f32(X, "X")
+    if X.dim() != 2 or X.shape[1] != b.d:
+        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    return phi, X
+
+
+def _on_device(b, **tensors) -> None:
+    for name, t in tensors.items():
+        if t is not None and t.device != b.device:
+            raise ValueError(f"{name} lives on {t.device}, the batch on {b.device}")
+
+
+def _sample_table(b, t, name: str, what: str) -> int:
+    """S of a table of samples ``[T, S]``, S at most 64 (``what``: what the S entries are)."""
+    if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] != b.T:
+        raise ValueError(f"{name} must be a tensor [T, S] = [{b.T}, S], got {tuple(t.shape) if torch.is_tensor(t) else t!r}")
+    return _in_range(t.shape[1], 1, _lib.TS_SAMPLES_MAX, what)
+
+
+def _exclusion(b, exclude, n: int, rows: int):
+    """``(excl_idx, excl_off)`` of ``n`` lists on the batch's device, ``(None, None)`` without ``exclude``."""
+    return (None, None) if exclude is None else pack_exclude(exclude, n, rows, b.device)
+
+
+def _selection(b, n: int, topk: int):
+    """The outputs of a selection of ``topk`` rows for each of ``n`` lists: ``(top_idx, top_val, info)``."""
+    top_idx = _new(b, n, topk, dtype=torch.int64) if topk > 0 else None
+    top_val = _new(b, n, topk) if topk > 0 else None
+    return top_idx, top_val, _new(b, b.T, dtype=torch.int32)
+
+
+def _pool_call(lib, entry: str, b, phi, flags: int, X, args, info, scratch_bytes: int) -> None:
+    """One pool entry of the library: ``args`` are the entry's own, between ``rows`` and ``info``."""
+    sb = int(scratch_bytes)
+    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device) if sb else None
+    ws, nb = b.workspace()
+    cb = b.c_struct()
+    _lib.check(getattr(lib, entry)(C.byref(cb), ptr(phi), flags, ptr(X), X.shape[0], *args, ptr(info), ptr(ws), nb, ptr(scratch), sb,
+                                   stream(b.device)), entry)
+
+
 def predict_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, latent: bool = False, best_f: Optional[torch.Tensor] = None,
                  maximize: bool = False, score: str = "ei", want_mean: bool = True, want_var: bool = True,
                  want_ei: Optional[bool] = None, topk: int = 0, exclude=None, log_ei: bool = False):
@@ -372,17 +428,11 @@ def predict_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, latent: bool
     ``exclude``: rows a task may not select (``pack_exclude``).  With no per-row output and ``topk > 0`` nothing of size
     T x rows is allocated or written."""
     lib = _lib.load()
-    if b.nq != 0:
-        raise ValueError("predict_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    _support_only(b, "predict_pool")
     if score not in ("ei", "mean"):
         raise ValueError(f"score must be 'ei' or 'mean', got {score!r}")
-    topk = int(topk)
-    if topk < 0 or topk > _lib.POOL_TOPK_MAX:
-        raise ValueError(f"topk must be in [0, {_lib.POOL_TOPK_MAX}], got {topk}")
-    phi = b.check_phi(phi)
-    X = _f32(X, "X")
-    if X.dim() != 2 or X.shape[1] != b.d:
-        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    topk = _in_range(topk, 0, _lib.POOL_TOPK_MAX, "topk")
+    phi, X = _phi_and_pool(b, phi, X)
     if best_f is not None:
         best_f = _f32(best_f, "best_f").reshape(-1)
         if best_f.numel() != b.T:
@@ -396,27 +446,16 @@ def predict_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, latent: bool
     if log_ei and not (want_ei or (topk > 0 and score == "ei")):
         raise ValueError("log_ei without want_ei or a selection ranked by ei: nothing would read it")
     rows = X.shape[0]
-    excl_idx = excl_off = None
-    if exclude is not None and topk > 0:
-        excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
-    for name, t in (("X", X), ("best_f", best_f)):
-        if t is not None and t.device != b.device:
-            raise ValueError(f"{name} lives on {t.device}, the batch on {b.device}")
+    excl_idx, excl_off = _exclusion(b, exclude if topk > 0 else None, b.T, rows)
+    _on_device(b, X=X, best_f=best_f)
     mean = _new(b, b.T, rows) if want_mean else None
     var = _new(b, b.T, rows) if want_var else None
     ei = _new(b, b.T, rows) if want_ei else None
-    top_idx = _new(b, b.T, topk, dtype=torch.int64) if topk > 0 else None
-    top_val = _new(b, b.T, topk) if topk > 0 else None
-    info = _new(b, b.T, dtype=torch.int32)
-    sb = int(lib.adkf_predict_pool_scratch_bytes(b.T, topk))
-    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device) if sb else None
+    top_idx, top_val, info = _selection(b, b.T, topk)
     flags = (_lib.PM_LATENT if latent else 0) | (_lib.PM_MAXIMIZE if maximize else 0) | (_lib.PM_SCORE_MEAN if score == "mean" else 0)
     flags |= _lib.PM_LOG_EI if log_ei else 0
-    ws, nb = b.workspace()
-    cb = b.c_struct()
-    _lib.check(lib.adkf_predict_pool(C.byref(cb), ptr(phi), flags, ptr(X), rows, ptr(best_f), ptr(excl_idx), ptr(excl_off),
-                                     ptr(mean), ptr(var), ptr(ei), topk, ptr(top_idx), ptr(top_val), ptr(info), ptr(ws), nb,
-                                     ptr(scratch), sb, stream(b.device)), "adkf_predict_pool")
+    args = (ptr(best_f), ptr(excl_idx), ptr(excl_off), ptr(mean), ptr(var), ptr(ei), topk, ptr(top_idx), ptr(top_val))
+    _pool_call(lib, "adkf_predict_pool", b, phi, flags, X, args, info, lib.adkf_predict_pool_scratch_bytes(b.T, topk))
     return dict(mean=mean, var=var, ei=ei, top_idx=top_idx, top_val=top_val, info=info)
 
 
@@ -424,44 +463,27 @@ def _believer_pool(name: str, b: GPBatch, phi, X, best_f, q, maximize, log_ei, e
     """The body of ``believer_pool`` (``name = "believer_pool"``, isotropic batches) and ``believer_pool_ard`` (ARD batches)."""
     lib = _lib.load()
     ard = name == "believer_pool_ard"
-    if b.nq != 0:
-        raise ValueError(f"{name} takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    _support_only(b, name)
     if b.ard and not ard:
         raise ValueError("believer_pool does not support ARD batches: use believer_pool_ard")
     if ard and not b.ard:
         raise ValueError("believer_pool_ard takes an ARD batch (GPBatch(..., ard=True)): use believer_pool")
-    q = int(q)
-    if q < 1 or q > _lib.POOL_TOPK_MAX:
-        raise ValueError(f"q must be in [1, {_lib.POOL_TOPK_MAX}], got {q}")
-    phi = b.check_phi(phi)
-    X = _f32(X, "X")
-    if X.dim() != 2 or X.shape[1] != b.d:
-        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    q = _in_range(q, 1, _lib.POOL_TOPK_MAX, "q")
+    phi, X = _phi_and_pool(b, phi, X)
     if best_f is None:
         raise ValueError(f"{name} needs best_f [T]")
     best_f = _f32(best_f, "best_f").reshape(-1)
     if best_f.numel() != b.T:
         raise ValueError(f"best_f must have T = {b.T} entries")
     rows = X.shape[0]
-    for arg, t in (("X", X), ("best_f", best_f)):
-        if t.device != b.device:
-            raise ValueError(f"{arg} lives on {t.device}, the batch on {b.device}")
-    excl_idx = excl_off = None
-    if exclude is not None:
-        excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
-    sel_idx = _new(b, b.T, q, dtype=torch.int64)
-    sel_val, sel_mean, sel_var = _new(b, b.T, q), _new(b, b.T, q), _new(b, b.T, q)
+    _on_device(b, X=X, best_f=best_f)
+    excl_idx, excl_off = _exclusion(b, exclude, b.T, rows)
+    sel_idx, sel_val, info = _selection(b, b.T, q)
+    sel_mean, sel_var = _new(b, b.T, q), _new(b, b.T, q)
     trace = _new(b, b.T, q, rows) if want_trace else None
-    info = _new(b, b.T, dtype=torch.int32)
-    sb = int(lib.adkf_believer_pool_scratch_bytes(b.T, b.ns, b.d, q))
-    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device)
     flags = (_lib.PM_MAXIMIZE if maximize else 0) | (_lib.PM_LOG_EI if log_ei else 0)
-    ws, nb = b.workspace()
-    cb = b.c_struct()
-    entry = "adkf_" + name
-    _lib.check(getattr(lib, entry)(C.byref(cb), ptr(phi), flags, ptr(X), rows, ptr(best_f), ptr(excl_idx), ptr(excl_off), q,
-                                   ptr(trace), ptr(sel_idx), ptr(sel_val), ptr(sel_mean), ptr(sel_var), ptr(info), ptr(ws), nb,
-                                   ptr(scratch), sb, stream(b.device)), entry)
+    args = (ptr(best_f), ptr(excl_idx), ptr(excl_off), q, ptr(trace), ptr(sel_idx), ptr(sel_val), ptr(sel_mean), ptr(sel_var))
+    _pool_call(lib, "adkf_" + name, b, phi, flags, X, args, info, lib.adkf_believer_pool_scratch_bytes(b.T, b.ns, b.d, q))
     return dict(sel_idx=sel_idx, sel_val=sel_val, sel_mean=sel_mean, sel_var=sel_var, trace=trace, info=info)
 
 
@@ -515,19 +537,13 @@ def _thompson_pool(name: str, b: GPBatch, phi, X, omega, phase, n_samples, gener
     """The body of ``thompson_pool`` (``name = "thompson_pool"``, isotropic batches) and ``thompson_pool_ard`` (ARD batches)."""
     lib = _lib.load()
     ard = name == "thompson_pool_ard"
-    if b.nq != 0:
-        raise ValueError(f"{name} takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    _support_only(b, name)
     if b.ard and not ard:
         raise ValueError("thompson_pool does not support ARD batches: use thompson_pool_ard")
     if ard and not b.ard:
         raise ValueError("thompson_pool_ard takes an ARD batch (GPBatch(..., ard=True)): use thompson_pool")
-    S = int(n_samples)
-    if S < 1 or S > _lib.TS_SAMPLES_MAX:
-        raise ValueError(f"n_samples must be in [1, {_lib.TS_SAMPLES_MAX}], got {S}")
-    phi = b.check_phi(phi)
-    X = _f32(X, "X")
-    if X.dim() != 2 or X.shape[1] != b.d:
-        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    S = _in_range(n_samples, 1, _lib.TS_SAMPLES_MAX, "n_samples")
+    phi, X = _phi_and_pool(b, phi, X)
     omega, phase = _f32(omega, "omega"), _f32(phase, "phase")
     if omega.dim() != 2 or omega.shape[1] != b.d:
         raise ValueError(f"omega must be [m, d] = [m, {b.d}], got {tuple(omega.shape)}")
@@ -549,23 +565,13 @@ def _thompson_pool(name: str, b: GPBatch, phi, X, omega, phase, n_samples, gener
     w = draw(w, (b.T, S, m), "w")
     eps = draw(eps, (b.T, S, b.ns), "eps")
     rows = X.shape[0]
-    excl_idx = excl_off = None
-    if exclude is not None:
-        excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
-    for arg, t in (("X", X), ("omega", omega), ("phase", phase), ("w", w), ("eps", eps)):
-        if t.device != b.device:
-            raise ValueError(f"{arg} lives on {t.device}, the batch on {b.device}")
+    excl_idx, excl_off = _exclusion(b, exclude, b.T, rows)
+    _on_device(b, X=X, omega=omega, phase=phase, w=w, eps=eps)
     paths = _new(b, b.T, S, rows) if want_paths else None
-    sel_idx, sel_val = _new(b, b.T, S, dtype=torch.int64), _new(b, b.T, S)
-    info = _new(b, b.T, dtype=torch.int32)
-    sb = int(lib.adkf_thompson_pool_scratch_bytes(b.T, b.ns, S, m))
-    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device)
-    ws, nb = b.workspace()
-    cb = b.c_struct()
-    entry = "adkf_" + name
-    _lib.check(getattr(lib, entry)(C.byref(cb), ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, ptr(X), rows, ptr(omega), ptr(phase),
-                                   m, ptr(w), ptr(eps), S, ptr(excl_idx), ptr(excl_off), ptr(paths), ptr(sel_idx), ptr(sel_val),
-                                   ptr(info), ptr(ws), nb, ptr(scratch), sb, stream(b.device)), entry)
+    sel_idx, sel_val, info = _selection(b, b.T, S)
+    args = (ptr(omega), ptr(phase), m, ptr(w), ptr(eps), S, ptr(excl_idx), ptr(excl_off), ptr(paths), ptr(sel_idx), ptr(sel_val))
+    _pool_call(lib, "adkf_" + name, b, phi, _lib.PM_MAXIMIZE if maximize else 0, X, args, info,
+               lib.adkf_thompson_pool_scratch_bytes(b.T, b.ns, S, m))
     return dict(sel_idx=sel_idx, sel_val=sel_val, paths=paths, info=info, w=w, eps=eps)
 
 
@@ -604,43 +610,22 @@ def mes_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, ystar: torch.Ten
     ``info [T]``.  A NaN or infinite ``ystar[t, s]`` makes the scores of task t NaN, which are never selected.  ``exclude``: rows a
     task may not select (``pack_exclude``).  With ``want_score=False`` nothing of size T x rows is allocated or written."""
     lib = _lib.load()
-    if b.nq != 0:
-        raise ValueError("mes_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
-    topk = int(topk)
-    if topk < 0 or topk > _lib.POOL_TOPK_MAX:
-        raise ValueError(f"topk must be in [0, {_lib.POOL_TOPK_MAX}], got {topk}")
+    _support_only(b, "mes_pool")
+    topk = _in_range(topk, 0, _lib.POOL_TOPK_MAX, "topk")
     if want_score is None:
         want_score = topk == 0
     if not (want_score or topk > 0):
         raise ValueError("no output asked for")
-    if not torch.is_tensor(ystar) or ystar.dim() != 2 or ystar.shape[0] != b.T:
-        raise ValueError(f"ystar must be a tensor [T, S] = [{b.T}, S], got {tuple(ystar.shape) if torch.is_tensor(ystar) else ystar!r}")
-    S = ystar.shape[1]
-    if S < 1 or S > _lib.TS_SAMPLES_MAX:
-        raise ValueError(f"the number of max-value samples must be in [1, {_lib.TS_SAMPLES_MAX}], got {S}")
+    S = _sample_table(b, ystar, "ystar", "the number of max-value samples")
     ystar = _f32(ystar, "ystar")
-    phi = b.check_phi(phi)
-    X = _f32(X, "X")
-    if X.dim() != 2 or X.shape[1] != b.d:
-        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    phi, X = _phi_and_pool(b, phi, X)
     rows = X.shape[0]
-    for arg, t in (("X", X), ("ystar", ystar)):
-        if t.device != b.device:
-            raise ValueError(f"{arg} lives on {t.device}, the batch on {b.device}")
-    excl_idx = excl_off = None
-    if exclude is not None and topk > 0:
-        excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
+    _on_device(b, X=X, ystar=ystar)
+    excl_idx, excl_off = _exclusion(b, exclude if topk > 0 else None, b.T, rows)
     score = _new(b, b.T, rows) if want_score else None
-    top_idx = _new(b, b.T, topk, dtype=torch.int64) if topk > 0 else None
-    top_val = _new(b, b.T, topk) if topk > 0 else None
-    info = _new(b, b.T, dtype=torch.int32)
-    sb = int(lib.adkf_predict_pool_scratch_bytes(b.T, topk))
-    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device) if sb else None
-    ws, nb = b.workspace()
-    cb = b.c_struct()
-    _lib.check(lib.adkf_mes_pool(C.byref(cb), ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, ptr(X), rows, ptr(ystar), S, ptr(excl_idx),
-                                 ptr(excl_off), ptr(score), topk, ptr(top_idx), ptr(top_val), ptr(info), ptr(ws), nb, ptr(scratch), sb,
-                                 stream(b.device)), "adkf_mes_pool")
+    top_idx, top_val, info = _selection(b, b.T, topk)
+    args = (ptr(ystar), S, ptr(excl_idx), ptr(excl_off), ptr(score), topk, ptr(top_idx), ptr(top_val))
+    _pool_call(lib, "adkf_mes_pool", b, phi, _lib.PM_MAXIMIZE if maximize else 0, X, args, info, lib.adkf_predict_pool_scratch_bytes(b.T, topk))
     return dict(score=score, top_idx=top_idx, top_val=top_val, info=info)
 
 
@@ -660,39 +645,20 @@ def gibbon_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, ystar: torch.
     ``trace [T, q, rows]`` (``want_trace``, else None) the score of every row at every step; ``info [T]``.  A NaN or infinite
     ``ystar[t, s]`` makes the scores of task t NaN: no pick.  ``exclude``: rows a task may not select (``pack_exclude``)."""
     lib = _lib.load()
-    if b.nq != 0:
-        raise ValueError("gibbon_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
-    q = int(q)
-    if q < 1 or q > _lib.POOL_TOPK_MAX:
-        raise ValueError(f"q must be in [1, {_lib.POOL_TOPK_MAX}], got {q}")
-    if not torch.is_tensor(ystar) or ystar.dim() != 2 or ystar.shape[0] != b.T:
-        raise ValueError(f"ystar must be a tensor [T, S] = [{b.T}, S], got {tuple(ystar.shape) if torch.is_tensor(ystar) else ystar!r}")
-    S = ystar.shape[1]
-    if S < 1 or S > _lib.TS_SAMPLES_MAX:
-        raise ValueError(f"the number of max-value samples S must be in [1, {_lib.TS_SAMPLES_MAX}], got {S}")
+    _support_only(b, "gibbon_pool")
+    q = _in_range(q, 1, _lib.POOL_TOPK_MAX, "q")
+    S = _sample_table(b, ystar, "ystar", "the number of max-value samples S")
     ystar = _f32(ystar, "ystar")
-    phi = b.check_phi(phi)
-    X = _f32(X, "X")
-    if X.dim() != 2 or X.shape[1] != b.d:
-        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    phi, X = _phi_and_pool(b, phi, X)
     rows = X.shape[0]
-    for arg, t in (("X", X), ("ystar", ystar)):
-        if t.device != b.device:
-            raise ValueError(f"{arg} lives on {t.device}, the batch on {b.device}")
-    excl_idx = excl_off = None
-    if exclude is not None:
-        excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
-    sel_idx = _new(b, b.T, q, dtype=torch.int64)
-    sel_val, sel_mean, sel_var = _new(b, b.T, q), _new(b, b.T, q), _new(b, b.T, q)
+    _on_device(b, X=X, ystar=ystar)
+    excl_idx, excl_off = _exclusion(b, exclude, b.T, rows)
+    sel_idx, sel_val, info = _selection(b, b.T, q)
+    sel_mean, sel_var = _new(b, b.T, q), _new(b, b.T, q)
     trace = _new(b, b.T, q, rows) if want_trace else None
-    info = _new(b, b.T, dtype=torch.int32)
-    sb = int(lib.adkf_believer_pool_scratch_bytes(b.T, b.ns, b.d, q))
-    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device)
-    ws, nb = b.workspace()
-    cb = b.c_struct()
-    _lib.check(lib.adkf_gibbon_pool(C.byref(cb), ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, ptr(X), rows, ptr(ystar), S, ptr(excl_idx),
-                                    ptr(excl_off), q, ptr(trace), ptr(sel_idx), ptr(sel_val), ptr(sel_mean), ptr(sel_var), ptr(info),
-                                    ptr(ws), nb, ptr(scratch), sb, stream(b.device)), "adkf_gibbon_pool")
+    args = (ptr(ystar), S, ptr(excl_idx), ptr(excl_off), q, ptr(trace), ptr(sel_idx), ptr(sel_val), ptr(sel_mean), ptr(sel_var))
+    _pool_call(lib, "adkf_gibbon_pool", b, phi, _lib.PM_MAXIMIZE if maximize else 0, X, args, info,
+               lib.adkf_believer_pool_scratch_bytes(b.T, b.ns, b.d, q))
     return dict(sel_idx=sel_idx, sel_val=sel_val, sel_mean=sel_mean, sel_var=sel_var, trace=trace, info=info)
 
 
@@ -712,51 +678,31 @@ def kg_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, ref_idx: Optional
     ``top_val`` as ``predict_pool`` returns them (None with ``topk == 0``) and ``info [T]``.  ``exclude``: rows a task may not
     select (``pack_exclude``); they are still scored."""
     lib = _lib.load()
-    if b.nq != 0:
-        raise ValueError("kg_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
-    topk = int(topk)
-    if topk < 0 or topk > _lib.POOL_TOPK_MAX:
-        raise ValueError(f"topk must be in [0, {_lib.POOL_TOPK_MAX}], got {topk}")
+    _support_only(b, "kg_pool")
+    topk = _in_range(topk, 0, _lib.POOL_TOPK_MAX, "topk")
     if ref_idx is None:
-        n_refs = int(n_refs)
-        if n_refs < 1 or n_refs > _lib.KG_REFS_MAX:
-            raise ValueError(f"n_refs must be in [1, {_lib.KG_REFS_MAX}], got {n_refs}")
+        n_refs = _in_range(n_refs, 1, _lib.KG_REFS_MAX, "n_refs")
     else:
         if not torch.is_tensor(ref_idx) or ref_idx.dtype != torch.int64 or ref_idx.dim() != 2 or ref_idx.shape[0] != b.T:
             raise ValueError(f"ref_idx must be an int64 tensor [T, M] = [{b.T}, M], got "
                              f"{(tuple(ref_idx.shape), ref_idx.dtype) if torch.is_tensor(ref_idx) else ref_idx!r}")
-        if ref_idx.shape[1] < 1 or ref_idx.shape[1] > _lib.KG_REFS_MAX:
-            raise ValueError(f"the number of reference rows M must be in [1, {_lib.KG_REFS_MAX}], got {ref_idx.shape[1]}")
-    phi = b.check_phi(phi)
-    X = _f32(X, "X")
-    if X.dim() != 2 or X.shape[1] != b.d:
-        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+        _in_range(ref_idx.shape[1], 1, _lib.KG_REFS_MAX, "the number of reference rows M")
+    phi, X = _phi_and_pool(b, phi, X)
     rows = X.shape[0]
-    if X.device != b.device:
-        raise ValueError(f"X lives on {X.device}, the batch on {b.device}")
+    _on_device(b, X=X)
     if ref_idx is None:
         ref_idx = predict_pool(b, phi, X, maximize=maximize, topk=n_refs, score="mean", want_mean=False, want_var=False, want_ei=False)["top_idx"]
-    elif ref_idx.device != b.device:
-        raise ValueError(f"ref_idx lives on {ref_idx.device}, the batch on {b.device}")
+    _on_device(b, ref_idx=ref_idx)
     ref_idx = ref_idx.contiguous()
     M = ref_idx.shape[1]
-    excl_idx = excl_off = None
-    if exclude is not None and topk > 0:
-        excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
+    excl_idx, excl_off = _exclusion(b, exclude if topk > 0 else None, b.T, rows)
     score = _new(b, b.T, rows) if want_score else None
     cov = _new(b, b.T, rows, M) if want_cov else None
     ref_mean = _new(b, b.T, M)
-    top_idx = _new(b, b.T, topk, dtype=torch.int64) if topk > 0 else None
-    top_val = _new(b, b.T, topk) if topk > 0 else None
-    info = _new(b, b.T, dtype=torch.int32)
-    sb = int(lib.adkf_kg_pool_scratch_bytes(b.T, b.ns, b.d, M, topk))
-    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device)
+    top_idx, top_val, info = _selection(b, b.T, topk)
     flags = (_lib.PM_MAXIMIZE if maximize else 0) | (_lib.PM_LOG_EI if log else 0)
-    ws, nb = b.workspace()
-    cb = b.c_struct()
-    _lib.check(lib.adkf_kg_pool(C.byref(cb), ptr(phi), flags, ptr(X), rows, ptr(ref_idx), M, ptr(excl_idx), ptr(excl_off), ptr(score),
-                                ptr(cov), ptr(ref_mean), topk, ptr(top_idx), ptr(top_val), ptr(info), ptr(ws), nb, ptr(scratch), sb,
-                                stream(b.device)), "adkf_kg_pool")
+    args = (ptr(ref_idx), M, ptr(excl_idx), ptr(excl_off), ptr(score), ptr(cov), ptr(ref_mean), topk, ptr(top_idx), ptr(top_val))
+    _pool_call(lib, "adkf_kg_pool", b, phi, flags, X, args, info, lib.adkf_kg_pool_scratch_bytes(b.T, b.ns, b.d, M, topk))
     return dict(score=score, cov=cov, ref_mean=ref_mean, ref_idx=ref_idx, top_idx=top_idx, top_val=top_val, info=info)
 
 
@@ -805,19 +751,14 @@ def jes_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, opt_idx: torch.T
     ``top_val [T, topk]`` as ``predict_pool`` returns them (None with ``topk == 0``) and ``info [T]``.  ``exclude``: rows a task may
     not select (``pack_exclude``); they are still scored."""
     lib = _lib.load()
-    if b.nq != 0:
-        raise ValueError("jes_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
-    topk = int(topk)
-    if topk < 0 or topk > _lib.POOL_TOPK_MAX:
-        raise ValueError(f"topk must be in [0, {_lib.POOL_TOPK_MAX}], got {topk}")
+    _support_only(b, "jes_pool")
+    topk = _in_range(topk, 0, _lib.POOL_TOPK_MAX, "topk")
     if want_score is None:
         want_score = topk == 0
     if not torch.is_tensor(opt_idx) or opt_idx.dtype != torch.int64 or opt_idx.dim() != 2 or opt_idx.shape[0] != b.T:
         raise ValueError(f"opt_idx must be an int64 tensor [T, S] = [{b.T}, S], got "
                          f"{(tuple(opt_idx.shape), opt_idx.dtype) if torch.is_tensor(opt_idx) else opt_idx!r}")
-    S = opt_idx.shape[1]
-    if S < 1 or S > _lib.TS_SAMPLES_MAX:
-        raise ValueError(f"the number of optimum samples S must be in [1, {_lib.TS_SAMPLES_MAX}], got {S}")
+    S = _in_range(opt_idx.shape[1], 1, _lib.TS_SAMPLES_MAX, "the number of optimum samples S")
     if not torch.is_tensor(opt_val) or tuple(opt_val.shape) != (b.T, S):
         raise ValueError(f"opt_val must be a tensor [T, S] = [{b.T}, {S}], got {tuple(opt_val.shape) if torch.is_tensor(opt_val) else opt_val!r}")
     cond_noise = float(cond_noise)
@@ -825,29 +766,17 @@ def jes_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, opt_idx: torch.T
         raise ValueError(f"cond_noise must be finite and >= 0, got {cond_noise}")
     opt_val = _f32(opt_val, "opt_val")
     opt_idx = opt_idx.contiguous()
-    phi = b.check_phi(phi)
-    X = _f32(X, "X")
-    if X.dim() != 2 or X.shape[1] != b.d:
-        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    phi, X = _phi_and_pool(b, phi, X)
     rows = X.shape[0]
-    for arg, t in (("X", X), ("opt_idx", opt_idx), ("opt_val", opt_val)):
-        if t.device != b.device:
-            raise ValueError(f"{arg} lives on {t.device}, the batch on {b.device}")
-    excl_idx = excl_off = None
-    if exclude is not None and topk > 0:
-        excl_idx, excl_off = pack_exclude(exclude, b.T, rows, b.device)
+    _on_device(b, X=X, opt_idx=opt_idx, opt_val=opt_val)
+    excl_idx, excl_off = _exclusion(b, exclude if topk > 0 else None, b.T, rows)
     score = _new(b, b.T, rows) if want_score else None
     opt_mean, opt_var = _new(b, b.T, S), _new(b, b.T, S)
-    top_idx = _new(b, b.T, topk, dtype=torch.int64) if topk > 0 else None
-    top_val = _new(b, b.T, topk) if topk > 0 else None
-    info = _new(b, b.T, dtype=torch.int32)
-    sb = int(lib.adkf_jes_pool_scratch_bytes(b.T, b.ns, b.d, S, topk))
-    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device)
-    ws, nb = b.workspace()
-    cb = b.c_struct()
-    _lib.check(lib.adkf_jes_pool(C.byref(cb), ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, ptr(X), rows, ptr(opt_idx), ptr(opt_val), S,
-                                 cond_noise, ptr(excl_idx), ptr(excl_off), ptr(score), ptr(opt_mean), ptr(opt_var), topk, ptr(top_idx),
-                                 ptr(top_val), ptr(info), ptr(ws), nb, ptr(scratch), sb, stream(b.device)), "adkf_jes_pool")
+    top_idx, top_val, info = _selection(b, b.T, topk)
+    args = (ptr(opt_idx), ptr(opt_val), S, cond_noise, ptr(excl_idx), ptr(excl_off), ptr(score), ptr(opt_mean), ptr(opt_var), topk,
+            ptr(top_idx), ptr(top_val))
+    _pool_call(lib, "adkf_jes_pool", b, phi, _lib.PM_MAXIMIZE if maximize else 0, X, args, info,
+               lib.adkf_jes_pool_scratch_bytes(b.T, b.ns, b.d, S, topk))
     return dict(score=score, opt_mean=opt_mean, opt_var=opt_var, top_idx=top_idx, top_val=top_val, info=info)
 
 
@@ -906,11 +835,8 @@ def ehvi_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, obj, ref, front
     ``topk == 0``), ``stair [G, P, 2]`` / ``stair_n [G]`` (int32) the cleaned staircase per group (``want_stair``; else None) and
     ``info [T]``.  ``exclude``: rows a GROUP may not select (``pack_exclude`` over G lists); they are still scored."""
     lib = _lib.load()
-    if b.nq != 0:
-        raise ValueError("ehvi_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
-    topk = int(topk)
-    if topk < 0 or topk > _lib.POOL_TOPK_MAX:
-        raise ValueError(f"topk must be in [0, {_lib.POOL_TOPK_MAX}], got {topk}")
+    _support_only(b, "ehvi_pool")
+    topk = _in_range(topk, 0, _lib.POOL_TOPK_MAX, "topk")
     if want_score is None:
         want_score = topk == 0
     obj = _int_table(obj, "obj", None, 2, "an integer table [G, 2] of task indices (-1 in the second column: one objective)")
@@ -927,9 +853,7 @@ def ehvi_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, obj, ref, front
         front = torch.as_tensor(front, dtype=torch.float32) if not torch.is_tensor(front) else front.float()
         if front.dim() != 3 or front.shape[0] != G or front.shape[2] != 2:
             raise ValueError(f"front must be [G, P, 2] = [{G}, P, 2], got {tuple(front.shape)}")
-        P = front.shape[1]
-        if P > _lib.EHVI_FRONT_MAX:
-            raise ValueError(f"the number of front points P must be in [0, {_lib.EHVI_FRONT_MAX}], got {P}")
+        P = _in_range(front.shape[1], 0, _lib.EHVI_FRONT_MAX, "the number of front points P")
         if P == 0:
             front = None
     if front_n is None:
@@ -941,9 +865,7 @@ def ehvi_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, obj, ref, front
     Cn = 0
     if con is not None:
         con = _int_table(con, "con", G, None, f"an integer table [G, C] = [{G}, C] of task indices (-1: unused)")
-        Cn = con.shape[1]
-        if Cn > _lib.EHVI_CONS_MAX:
-            raise ValueError(f"the number of constraints C must be in [0, {_lib.EHVI_CONS_MAX}], got {Cn}")
+        Cn = _in_range(con.shape[1], 0, _lib.EHVI_CONS_MAX, "the number of constraints C")
         if Cn == 0:
             con = None
     if Cn > 0:
@@ -958,31 +880,19 @@ def ehvi_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, obj, ref, front
         con_thr = con_geq = None
     if topk == 0 and not want_score and not want_stair:
         raise ValueError("no output requested: topk == 0, want_score and want_stair are all off")
-    phi = b.check_phi(phi)
-    X = _f32(X, "X")
-    if X.dim() != 2 or X.shape[1] != b.d:
-        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    phi, X = _phi_and_pool(b, phi, X)
     rows = X.shape[0]
     dev = b.device
     put = lambda t: None if t is None else t.to(dev).contiguous()
     obj, obj_maximize, ref, front, front_n, con, con_thr, con_geq = (put(t) for t in (obj, obj_maximize, ref, front, front_n, con, con_thr, con_geq))
-    excl_idx = excl_off = None
-    if exclude is not None and topk > 0:
-        excl_idx, excl_off = pack_exclude(exclude, G, rows, dev)
+    excl_idx, excl_off = _exclusion(b, exclude if topk > 0 else None, G, rows)
     score = _new(b, G, rows) if want_score else None
     stair = _new(b, G, P, 2) if want_stair else None
     stair_n = _new(b, G, dtype=torch.int32) if want_stair else None
-    top_idx = _new(b, G, topk, dtype=torch.int64) if topk > 0 else None
-    top_val = _new(b, G, topk) if topk > 0 else None
-    info = _new(b, b.T, dtype=torch.int32)
-    sb = int(lib.adkf_ehvi_pool_scratch_bytes(b.T, G, topk))
-    scratch = torch.empty(sb, dtype=torch.uint8, device=dev)
-    ws, nb = b.workspace()
-    cb = b.c_struct()
-    _lib.check(lib.adkf_ehvi_pool(C.byref(cb), ptr(phi), _lib.PM_LOG_EI if log else 0, ptr(X), rows, G, ptr(obj), ptr(obj_maximize), ptr(ref),
-                                  ptr(front), ptr(front_n), P, ptr(con), ptr(con_thr), ptr(con_geq), Cn, ptr(excl_idx), ptr(excl_off),
-                                  ptr(score), ptr(stair) if P > 0 else None, ptr(stair_n), topk, ptr(top_idx), ptr(top_val), ptr(info),
-                                  ptr(ws), nb, ptr(scratch), sb, stream(dev)), "adkf_ehvi_pool")
+    top_idx, top_val, info = _selection(b, G, topk)
+    args = (G, ptr(obj), ptr(obj_maximize), ptr(ref), ptr(front), ptr(front_n), P, ptr(con), ptr(con_thr), ptr(con_geq), Cn, ptr(excl_idx),
+            ptr(excl_off), ptr(score), ptr(stair) if P > 0 else None, ptr(stair_n), topk, ptr(top_idx), ptr(top_val))
+    _pool_call(lib, "adkf_ehvi_pool", b, phi, _lib.PM_LOG_EI if log else 0, X, args, info, lib.adkf_ehvi_pool_scratch_bytes(b.T, G, topk))
     return dict(score=score, top_idx=top_idx, top_val=top_val, stair=stair, stair_n=stair_n, info=info)
 
 
@@ -999,44 +909,26 @@ def gumbel_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, n_samples: Op
     and returned.  Skipped tasks and an empty pool give -inf in ``quant`` and ``gumbel`` and -inf / +inf in ``ystar``.  A task's
     result is the same bits alone or in a batch, and under any permutation of the pool's rows."""
     lib = _lib.load()
-    if b.nq != 0:
-        raise ValueError("gumbel_pool takes a support-only batch (no Z_q / y_q): the pool comes in X")
+    _support_only(b, "gumbel_pool")
     if u is None:
         if n_samples is None:
             raise ValueError("gumbel_pool needs n_samples or u")
-        S = int(n_samples)
-        if S < 1 or S > _lib.TS_SAMPLES_MAX:
-            raise ValueError(f"n_samples must be in [1, {_lib.TS_SAMPLES_MAX}], got {S}")
+        S = _in_range(n_samples, 1, _lib.TS_SAMPLES_MAX, "n_samples")
     else:
-        if not torch.is_tensor(u) or u.dim() != 2 or u.shape[0] != b.T:
-            raise ValueError(f"u must be a tensor [T, S] = [{b.T}, S], got {tuple(u.shape) if torch.is_tensor(u) else u!r}")
-        S = u.shape[1]
-        if S < 1 or S > _lib.TS_SAMPLES_MAX:
-            raise ValueError(f"the number of samples must be in [1, {_lib.TS_SAMPLES_MAX}], got {S}")
+        S = _sample_table(b, u, "u", "the number of samples")
         if n_samples is not None and int(n_samples) != S:
             raise ValueError(f"n_samples = {n_samples} does not match u [T, {S}]")
-    phi = b.check_phi(phi)
-    X = _f32(X, "X")
-    if X.dim() != 2 or X.shape[1] != b.d:
-        raise ValueError(f"X must be [rows, d] = [rows, {b.d}], got {tuple(X.shape)}")
+    phi, X = _phi_and_pool(b, phi, X)
     if u is None:
         gdev = generator.device if generator is not None else b.device
         u = torch.rand(b.T, S, dtype=torch.float32, generator=generator, device=gdev).to(b.device).contiguous()
     else:
         u = _f32(u, "u")
-    rows = X.shape[0]
-    for arg, t in (("X", X), ("u", u)):
-        if t.device != b.device:
-            raise ValueError(f"{arg} lives on {t.device}, the batch on {b.device}")
+    _on_device(b, X=X, u=u)
     ystar, quant, gumbel = _new(b, b.T, S), _new(b, b.T, 3), _new(b, b.T, 2)
     info = _new(b, b.T, dtype=torch.int32)
-    sb = int(lib.adkf_gumbel_pool_scratch_bytes(b.T))
-    scratch = torch.empty(sb, dtype=torch.uint8, device=b.device)
-    ws, nb = b.workspace()
-    cb = b.c_struct()
-    _lib.check(lib.adkf_gumbel_pool(C.byref(cb), ptr(phi), _lib.PM_MAXIMIZE if maximize else 0, ptr(X), rows, ptr(u), S, ptr(ystar),
-                                    ptr(quant), ptr(gumbel), ptr(info), ptr(ws), nb, ptr(scratch), sb, stream(b.device)),
-               "adkf_gumbel_pool")
+    args = (ptr(u), S, ptr(ystar), ptr(quant), ptr(gumbel))
+    _pool_call(lib, "adkf_gumbel_pool", b, phi, _lib.PM_MAXIMIZE if maximize else 0, X, args, info, lib.adkf_gumbel_pool_scratch_bytes(b.T))
     return dict(ystar=ystar, quant=quant, gumbel=gumbel, u=u, info=info)
 
 

@@ -8,9 +8,14 @@ at 1024; the ARD problem of tests/test_gpu_believer_pool_ard; tests/test_gpu_pre
 float64 walks): believer_pool with EI and with log EI and gibbon_pool, each with trace, predict_pool(log EI, k = 8), believer_pool_ard,
 kg_pool with KG and with log KG (score, cov, ref_mean and the selection; M = 16 reference rows of lowest posterior mean, a -1 and a
 repetition among them), and ehvi_pool on the problems of tests/test_gpu_ehvi_pool.py's score test (score, staircase and selection, linear
-and log, with and without the constraints) - and saves every returned tensor.  compare looks at the arrays both files have, so a
-tree can be held against one from before a call existed.  All lists are full (pools of 130 to 333 rows), so the arrays do not depend on how a short list is
-merged."""
+and log, with and without the constraints); on each of the five problems also mes_pool and jes_pool (score and k = 8; the optima of
+jes_pool at the first eight reference rows of kg_pool, their -1 and their repetition included), gumbel_pool on fixed uniforms and
+thompson_pool / thompson_pool_ard (m = 64 features and four paths from seeded generators, with the paths) - and saves every returned
+tensor.  Then the records of the six batched BO loops of adkf_ift_amd.bayes_opt, as int64 tensors under records/: a generated pool of
+400 rows in 6 dimensions, 4 initial points, batches of 2, 2 iterations, 3 replicates, 64 features, fixed seeds; the EI loop also with
+batch="believer" and with ard=True, the MES loop also with max_value="gumbel" and with batch="gibbon".  compare looks at the arrays both
+files have, so a tree can be held against one from before a call existed.  All lists are full (pools of 130 to 333 rows), so the
+arrays do not depend on how a short list is merged."""
 import os
 import sys
 
@@ -41,6 +46,16 @@ def dump(path):
         refs[:, 5] = refs[:, 0]
         return refs
 
+    def sampled(tag, b, phi, X, ystar, refs):
+        """mes_pool, jes_pool, gumbel_pool and the batch's kind of thompson_pool on one problem"""
+        put(f"mes/{tag}", gp_ops.mes_pool(b, phi, X, ystar=ystar, topk=8, want_score=True))
+        wide = (ystar[:, :1] - torch.linspace(0.0, 0.7, 8, device=dev)[None]).contiguous()
+        put(f"jes/{tag}", gp_ops.jes_pool(b, phi, X, opt_idx=refs[:, :8].contiguous(), opt_val=wide, topk=8, want_score=True))
+        put(f"gumbel/{tag}", gp_ops.gumbel_pool(b, phi, X, u=torch.linspace(0.05, 0.95, 5, device=dev).repeat(b.T, 1)))
+        omega, phase = gp_ops.rff_basis(b.kernel, b.d, 64, generator=torch.Generator().manual_seed(11), device=dev)
+        draw = gp_ops.thompson_pool_ard if b.ard else gp_ops.thompson_pool
+        put(f"thompson/{tag}", draw(b, phi, X, omega=omega, phase=phase, n_samples=4, generator=torch.Generator().manual_seed(12), want_paths=True))
+
     for kernel, n_s, d, rows, q in (("matern", [48, 45, 31], 16, 300, 8), ("rbf", [200, 197, 133], 64, 333, 8), ("matern", [1024, 700], 12, 130, 4)):
         b, phi, Zs, ys, n_s, X, best = BV._explicit(dev, kernel, n_s, d, rows, 500 + max(n_s))
         ystar = (ys.min(1).values[:, None] - torch.linspace(0.1, 1.0, 5)[None]).to(dev).contiguous()
@@ -51,9 +66,11 @@ def dump(path):
         refs = kg_refs(b, phi, X)
         for log in (False, True):
             put(f"kg/{kernel}{max(n_s)}/log={log}", gp_ops.kg_pool(b, phi, X, ref_idx=refs, log=log, topk=8, want_cov=True))
+        sampled(f"{kernel}{max(n_s)}", b, phi, X, ystar, refs)
     b, phi, Zs, ys, n_s, X, best = BVA._explicit(dev, "matern", [48, 45, 31], 12, 300, 548)
     put("believer_ard", gp_ops.believer_pool_ard(b, phi, X, best_f=best.to(dev), q=8, want_trace=True))
     put("kg_ard", gp_ops.kg_pool(b, phi, X, ref_idx=kg_refs(b, phi, X), log=True, topk=8, want_cov=True))
+    sampled("ard", b, phi, X, (ys.min(1).values[:, None] - torch.linspace(0.1, 1.0, 5)[None]).to(dev).contiguous(), kg_refs(b, phi, X))
     b, phi, Zs, ys, n_s, _ = P._ill_batch(dev)
     b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
     X = torch.cat([P._pool(300, 2, 3), b.Z_s[1, :5].cpu()]).to(dev)
@@ -62,6 +79,7 @@ def dump(path):
     for log in (False, True):
         put(f"float64/kg/log={log}", gp_ops.kg_pool(b, phi, X, ref_idx=kg_refs(b, phi, X), log=log, topk=8, want_cov=True))
     put("float64/gibbon", gp_ops.gibbon_pool(b, phi, X, ystar=(best[:, None] - torch.tensor([[1.0, 2.0]], device=dev)).contiguous(), q=6, want_trace=True))
+    sampled("float64", b, phi, X, (best[:, None] - torch.tensor([[1.0, 2.0]], device=dev)).contiguous(), kg_refs(b, phi, X))
     import test_gpu_ehvi_pool as EV
     from test_ehvi_pool_cpu import GPU_CASES
 
@@ -72,6 +90,27 @@ def dump(path):
             put(f"ehvi/case{case}/log={log}", EV._call(b, phi, X, grp, log=log, topk=8, want_score=True, want_stair=True))
             if grp["C"] > 0:
                 put(f"ehvi/case{case}/log={log}/C=0", EV._call(b, phi, X, free, log=log, topk=8, want_score=True))
+    import numpy as np
+
+    from adkf_ift_amd import bayes_opt as BO
+
+    g = torch.Generator().manual_seed(3)
+    Xb = torch.randn(400, 6, generator=g)
+    yb = torch.stack([((Xb - 0.3) ** 2).sum(1), ((Xb + 0.4) ** 2).sum(1)], 1)
+    order = torch.argsort(yb[:, 0])
+    Xb, yb = Xb[order].to(dev), yb[order].to(dev)
+    args = (4, 2, 2, "matern", dev, 200, 0.01, True)
+    rngs = lambda: [np.random.default_rng(40 + r) for r in range(3)]
+    runs = {"ei": (BO.run_gp_ei_bo_batched, {}), "ei_believer": (BO.run_gp_ei_bo_batched, dict(batch="believer")),
+            "ei_ard": (BO.run_gp_ei_bo_batched, dict(ard=True, acquisition="log_ei")), "ts": (BO.run_gp_ts_bo_batched, dict(n_features=64)),
+            "mes": (BO.run_gp_mes_bo_batched, dict(n_features=64)), "mes_gumbel": (BO.run_gp_mes_bo_batched, dict(max_value="gumbel")),
+            "mes_gibbon": (BO.run_gp_mes_bo_batched, dict(n_features=64, batch="gibbon")), "kg": (BO.run_gp_kg_bo_batched, {}),
+            "jes": (BO.run_gp_jes_bo_batched, dict(n_features=64))}
+    for tag, (loop, kw) in runs.items():
+        out[f"records/{tag}"] = torch.tensor(loop(Xb, yb[:, 0].contiguous(), *args, rngs=rngs(), **kw), dtype=torch.int64)
+    rec, hv = BO.run_gp_ehvi_bo_batched(Xb, yb, *args, rngs=rngs(), maximize=(False, False))
+    out["records/ehvi"] = torch.tensor(rec, dtype=torch.int64)
+    out["records/ehvi_hypervolume"] = torch.tensor(hv, dtype=torch.float64)
     torch.save(out, path)
     print("saved", len(out), "arrays to", path)
 
