@@ -16,12 +16,11 @@
 //             feature rows as its "support"); c0 = Kxp - F goes into pm_mm's two staging buffers, which are adjacent and free by then
 //             (a [64, 65] panel in 2 * 64 * 34 floats), so the instance needs NO LDS beyond prediction's: its row tiles move to the
 //             global slots at prediction's sizes (host_stream.h derives both from the same expression).  Thread i < 64 then runs the
-//             substitution of row i against G (uniform loads), takes v_j and the score, and the first wave merges the scores into the
-//             walk's one-entry list; the exclusion test also scans the picks made so far.  At c = 0 none of this runs and the row's
-//             score is prediction's, bit for bit.
-//   float64   tasks (refine64.h) take k_bv_walk64, k_predict_marginal64's wave-per-row loop (pm64_task, pm64_posterior_row,
-//             pm64_finish_walk) with float64 w and G: lane i forms c0(x, i), the substitution runs over the lanes (row i of G against
-//             the ell broadcast so far).
+//             substitution of row i against G (uniform loads), takes v_j and the score, and the shared tail (pm_tile_tail) offers the
+//             scores to the walk's one-entry list; the exclusion test also scans the picks made so far (bv_excl).  At c = 0 none of
+//             this runs and the row's score is prediction's, bit for bit.
+//   float64   tasks (refine64.h) take k_bv_walk64, the float64 pool walk (pm64_pool_walk, predict_stream.h) with float64 w and G: lane
+//             i forms c0(x, i), the substitution runs over the lanes (row i of G against the ell broadcast so far).
 //   k_bv_step merges the chunks' pairs under pm_beats (pm_merge_task_lists, k_pool_topk's merge at width 1), writes sel_*, forms
 //             k(Z_s, x_p) from the features in float64 (refine64.h's float64 kappa0, as the float64 walk), solves w = A^-1 k (float32
 //             tasks: pm_solve_refined, k_ts_solve's product and ONE refinement step with A regenerated from D2ss; flagged tasks:
@@ -41,7 +40,8 @@
 // The c0 panel, the substitution of one row and the float64 downdate are functions (bv_c0_panel, bv_downdate, bv64_downdate) because
 // adkf_gibbon_pool (gibbon_stream.h) downdates the same variance with the same state, k_bv_init and k_bv_step, under another score.
 // The float64 c0 of a lane (bv64_c0) and the first parts of k_bv_step - the stored row, k(Z_s, x) and w = A^-1 k (bv_store_row,
-// bv_kernel_col, bv_solve_w) - are functions because adkf_kg_pool (kg_stream.h) builds the same state for a fixed reference set.
+// bv_kernel_col, bv_solve_w) - are functions because adkf_kg_pool and adkf_jes_pool (kg_stream.h, jes_stream.h) build the same state
+// for a fixed reference set, one (entry, task) workgroup each: bv_ref_entry.
 #pragma once
 #include "thompson_stream.h"
 
@@ -67,6 +67,10 @@ __device__ __forceinline__ bool bv_picked(const BvArgs& v, int t, int c, long lo
     for (int i = 0; i < c; ++i)
         if (v.sel_idx[(size_t)t * v.q + i] == r) return true;
     return false;
+}
+// what task t may not select with c picks made: its exclusion list and the picks
+__device__ __forceinline__ auto bv_excl(const PmPool& s, const BvArgs& v, int t, int c) {
+    return [&s, &v, t, c](long long r) { return pm_excluded(s, t, r) || bv_picked(v, t, c, r); };
 }
 __device__ __forceinline__ float bv_score(const PmArgs& a, const BvArgs& v, int t, float mean, float vl) {
     return a.log_ei ? pm_log_ei(mean, vl, v.best[t], a.maximize) : pm_ei(mean, vl, v.best[t], a.maximize);
@@ -134,15 +138,11 @@ struct BvEpilogue {
         if (c > 0) bv_c0_panel<ARD>(a, v, tl, acc, c);
         float score = 0.f;
         if (tid < tl.m) {
-            float vl = tl.os - (tl.red[0][1][tid] + tl.red[1][1][tid]);
-            const float mean = tl.red[0][0][tid] + tl.red[1][0][tid];
+            float vl = tl.var(tid);
             if (c > 0) vl -= bv_downdate(v, t, c, C0 + tid * BV_LDC);
-            score = bv_score(a, v, t, mean, vl);
-            if (v.trace) v.trace[((size_t)t * q + v.j) * (size_t)a.rows + (size_t)(tl.r0 + tid)] = score;
+            score = bv_score(a, v, t, tl.mean(tid), vl);
         }
-        if ((tid >> 6) == 0)
-            pm_list_merge(walk.lv, walk.li, 1, score, (long long)(tl.r0 + tid), tid < tl.m,
-                          [&](long long r) { return pm_excluded(args.s, t, r) || bv_picked(v, t, c, r); });
+        pm_tile_tail(args, tl, walk, score, v.trace, (size_t)t * q + v.j, 1, bv_excl(args.s, v, t, c));
     }
 };
 
@@ -182,14 +182,12 @@ __device__ __forceinline__ double bv64_downdate(const PmArgs& a, const Pm64Task&
     return ss;
 }
 
-// ---- flagged tasks: k_predict_marginal64's loop (grid (chunks, T), one wave per pool row) with the downdate in float64
+// ---- flagged tasks: the float64 pool walk (pm64_pool_walk) with the downdate in float64
 template <bool ARD>
 __global__ __launch_bounds__(PM64_NT) void k_bv_walk64(BvKargs<ARD> args) {
     const PmArgs& a = args.p;
     const BvArgs& v = args.v;
     __shared__ double kr[PM64_WAVES][R64_MAXN];
-    float lv = -INFINITY;
-    long long li = -1;
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, q = v.q;
     Pm64Task tk;
     if (!pm64_task<ARD>(args, t, tk)) return;   // (uniform)
@@ -197,11 +195,7 @@ __global__ __launch_bounds__(PM64_NT) void k_bv_walk64(BvKargs<ARD> args) {
     const double* Wt = v.W64 + (size_t)t * q * tk.ld;
     const double* G = v.G64 + (size_t)t * q * q;
     const float* Xp = v.Xp + (size_t)t * q * a.d;
-    double* k = kr[wv];
-    for (int64_t r = (int64_t)blockIdx.x * PM64_WAVES + wv; r < a.rows; r += (int64_t)gridDim.x * PM64_WAVES) {
-        const float* zq = a.Zq + (size_t)r * a.d;
-        double s1, s2;
-        pm64_posterior_row<ARD>(a, tk, zq, k, s1, s2);
+    pm64_pool_walk<ARD>(args, tk, kr[wv], 1, bv_excl(args.s, v, t, c), [&](int64_t r, const float* zq, const double* k, double s1, double s2) {
         double vl = tk.os - s2;
         if (c > 0) vl -= bv64_downdate<ARD>(a, tk, zq, k, Wt, G, Xp, c, q, lane);
         float score = 0.f;
@@ -209,11 +203,8 @@ __global__ __launch_bounds__(PM64_NT) void k_bv_walk64(BvKargs<ARD> args) {
             score = bv_score(a, v, t, (float)s1, (float)vl);
             if (v.trace) v.trace[((size_t)t * q + v.j) * (size_t)a.rows + (size_t)r] = score;
         }
-        pm_list_merge(lv, li, 1, score, (long long)r, lane == 0, [&](long long x) { return pm_excluded(args.s, t, x) || bv_picked(v, t, c, x); });
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
-    pm64_finish_walk(args.s, t, 1, lv, li, [&](float x, long long i) { pm_list_merge(lv, li, 1, x, i, i >= 0, [](long long) { return false; }); });
+        return score;
+    });
 }
 
 // the per-task state before step 0
@@ -285,6 +276,37 @@ __device__ __forceinline__ void bv_solve_w(const PmArgs& a, int t, int n, bool f
         for (int i = tid; i < n; i += 256) Wn[i] = vs[i];
     }
     __syncthreads();
+}
+
+// ---- one (entry, task) workgroup of a reference kernel (k_kg_refs, k_jes_refs): the pool row idx as a fixed "pick" of task t, with
+// the caller's verdict ok (uniform) and the entry's slots Xj [d], Wj [ns_ld] and W64j [ns_ld] (null without a float64 region).
+// A skipped entry gets zero rows - nothing of it is read but by the c0 panel, whose column is ignored - and the answer 0.  Otherwise
+// the row goes into Xj (bv_store_row), k(Z_s, x) and w = A^-1 k into fb as bv_kernel_col and bv_solve_w leave them (float32 tasks:
+// k in fb, w at fb + TS_NS_MAX; flagged: doubles, k in fb, w behind it at R64_MAXN), w into its slot, zero beyond n, and the entry's
+// posterior mean w . y comes back, summed in float64 in a fixed order.  fb: 3 * TS_NS_MAX floats, 16-byte aligned; red: 256 doubles.
+template <bool ARD, class ARGS>
+__device__ __forceinline__ double bv_ref_entry(const ARGS& args, int t, bool ok, long long idx, float* Xj, float* Wj, double* W64j, float* fb, double* red) {
+    const PmArgs& a = args.p;
+    const int tid = threadIdx.x, ld = a.ns_ld, d = a.d;
+    if (!ok) {
+        for (int e = tid; e < d; e += 256) Xj[e] = 0.f;
+        for (int i = tid; i < ld; i += 256) { Wj[i] = 0.f; if (W64j) W64j[i] = 0.0; }
+        return 0.0;
+    }
+    const bool f64 = pm_kind_of(a, t) == 2;
+    const int n = pm_ns(a, t);
+    const float* sc = a.scal + (size_t)t * NSCAL;
+    const double os = sc[S_OS], il2 = 1.0 / ((double)sc[S_LS] * (double)sc[S_LS]);
+    const float* ys = a.y_s + (size_t)t * ld;
+    const float* xp = bv_store_row<ARD>(args, t, f64, a.Zq + (size_t)idx * d, Xj);
+    const float* vs = fb + TS_NS_MAX;
+    const double* w64 = reinterpret_cast<double*>(fb) + R64_MAXN;
+    bv_kernel_col(a, a.Zs + (size_t)t * ld * d, xp, n, os, il2, f64, reinterpret_cast<double*>(fb), fb);
+    bv_solve_w(a, t, n, f64, fb, Wj, W64j);
+    for (int i = n + tid; i < ld; i += 256) { Wj[i] = 0.f; if (W64j) W64j[i] = 0.0; }
+    double pm = 0.0;
+    for (int i = tid; i < n; i += 256) pm += (f64 ? w64[i] : (double)vs[i]) * (double)ys[i];
+    return bv_block_sum(pm, red);
 }
 
 // ---- the end of step j: one workgroup per task (see the top of the file)

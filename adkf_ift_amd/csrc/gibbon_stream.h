@@ -15,11 +15,11 @@
 // ignored.  Per step j: the walks of each task kind, then k_bv_step.
 //   the walk  is k_predict_marginal's tile with GibbonEpilogue: with c picks made the believer's c0 panel (bv_c0_panel) and thread
 //             i < 64's substitution (bv_downdate) give v_j, which that thread keeps in ONE register; behind a barrier - the panel is
-//             dead - all 256 threads sum the S terms of a(x) as MesEpilogue does (thread tid the row tid & 63 and the samples
-//             tid >> 6, + 4, ...), the four partial sums of a row meet in the staging buffers where the panel was and thread i < 64
-//             adds them in the order 0, 1, 2, 3.  No LDS beyond prediction's.  At c = 0 nothing of the downdate runs.
-//   float64   tasks take k_gb_walk64: k_bv_walk64's lane-per-pick downdate in float64 (bv64_downdate), the mean and the two variances
-//             rounded to float32, then k_mes_walk64's lane-per-sample sum with its fixed butterfly.
+//             dead - the four-wave sum of the S terms of a(x) where the panel was (pm_sum4, predict_stream.h), then the shared tail
+//             (pm_tile_tail).  No LDS beyond prediction's.  At c = 0 nothing of the downdate runs.
+//   float64   tasks take k_gb_walk64, the float64 pool walk (pm64_pool_walk): k_bv_walk64's lane-per-pick downdate in float64
+//             (bv64_downdate), the mean and the two variances rounded to float32, then k_mes_walk64's lane-per-sample sum with its
+//             fixed butterfly.
 // trace[j] <= trace[0] bit for bit: a(x) comes out of the same instructions at every step, v_j <= v_0 in float32 (the downdate only
 // subtracts a sum of squares; the float64 walk rounds monotonically), a quotient of x <= y is at most 1, its logarithm at most 0,
 // and adding a number <= 0 cannot round upwards.
@@ -90,12 +90,12 @@ struct GibbonEpilogue {
         float vj = 0.f;
         if (c > 0) {
             bv_c0_panel<ARD>(a, v, tl, acc, c);
-            if (tid < tl.m) vj = (tl.os - (tl.red[0][1][tid] + tl.red[1][1][tid])) - bv_downdate(v, t, c, ps + tid * BV_LDC);
+            if (tid < tl.m) vj = tl.var(tid) - bv_downdate(v, t, c, ps + tid * BV_LDC);
             __syncthreads();   // the panel is dead: the partial sums may overwrite it
         }
         if (row < tl.m) {
-            const float v0 = fmaxf(tl.os - (tl.red[0][1][row] + tl.red[1][1][row]), 1e-12f);
-            const float mean = tl.red[0][0][row] + tl.red[1][0][row];
+            const float v0 = fmaxf(tl.var(row), 1e-12f);
+            const float mean = tl.mean(row);
             const float sigma = sqrtf(v0), rho2 = v0 / (v0 + tl.noise);
             const float* ys = args.v.ystar + (size_t)t * S;
             float sum = 0.f;
@@ -104,25 +104,17 @@ struct GibbonEpilogue {
         }
         __syncthreads();
         float score = 0.f;
-        if (tid < tl.m) {
-            const float v0 = tl.os - (tl.red[0][1][tid] + tl.red[1][1][tid]);
-            score = gb_score(((ps[tid] + ps[PM_TM + tid]) + ps[2 * PM_TM + tid]) + ps[3 * PM_TM + tid], S, v0, vj, tl.noise, c);
-            if (v.trace) v.trace[((size_t)t * q + v.j) * (size_t)a.rows + (size_t)(tl.r0 + tid)] = score;
-        }
-        if ((tid >> 6) == 0)
-            pm_list_merge(walk.lv, walk.li, 1, score, (long long)(tl.r0 + tid), tid < tl.m,
-                          [&](long long r) { return pm_excluded(args.s, t, r) || bv_picked(v, t, c, r); });
+        if (tid < tl.m) score = gb_score(pm_sum4(ps, tid), S, tl.var(tid), vj, tl.noise, c);
+        pm_tile_tail(args, tl, walk, score, v.trace, (size_t)t * q + v.j, 1, bv_excl(args.s, v, t, c));
     }
 };
 
-// ---- flagged tasks: k_bv_walk64's loop and downdate (grid (chunks, T), one wave per pool row), then lane s the term of sample s
+// ---- flagged tasks: the float64 pool walk with k_bv_walk64's downdate, then lane s the term of sample s
 template <bool ARD>
 __global__ __launch_bounds__(PM64_NT) void k_gb_walk64(GibbonKargs<ARD> args) {
     const PmArgs& a = args.p;
     const BvArgs& v = args.v.b;
     __shared__ double kr[PM64_WAVES][R64_MAXN];
-    float lv = -INFINITY;
-    long long li = -1;
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, q = v.q, S = args.v.S;
     Pm64Task tk;
     if (!pm64_task<ARD>(args, t, tk)) return;   // (uniform)
@@ -132,11 +124,7 @@ __global__ __launch_bounds__(PM64_NT) void k_gb_walk64(GibbonKargs<ARD> args) {
     const float* Xp = v.Xp + (size_t)t * q * a.d;
     const float noise = (float)tk.noise;
     const float ys = lane < S ? args.v.ystar[(size_t)t * S + lane] : 0.f;
-    double* k = kr[wv];
-    for (int64_t r = (int64_t)blockIdx.x * PM64_WAVES + wv; r < a.rows; r += (int64_t)gridDim.x * PM64_WAVES) {
-        const float* zq = a.Zq + (size_t)r * a.d;
-        double s1, s2;
-        pm64_posterior_row<ARD>(a, tk, zq, k, s1, s2);
+    pm64_pool_walk<ARD>(args, tk, kr[wv], 1, bv_excl(args.s, v, t, c), [&](int64_t r, const float* zq, const double* k, double s1, double s2) {
         const double vl = tk.os - s2;
         const float mean = (float)s1, v0 = (float)vl;
         const float vj = c > 0 ? (float)(vl - bv64_downdate<ARD>(a, tk, zq, k, Wt, G, Xp, c, q, lane)) : v0;
@@ -145,11 +133,8 @@ __global__ __launch_bounds__(PM64_NT) void k_gb_walk64(GibbonKargs<ARD> args) {
         for (int o = 32; o > 0; o >>= 1) g += __shfl_xor(g, o);
         const float score = gb_score(g, S, v0, vj, noise, c);
         if (lane == 0 && v.trace) v.trace[((size_t)t * q + v.j) * (size_t)a.rows + (size_t)r] = score;
-        pm_list_merge(lv, li, 1, score, (long long)r, lane == 0, [&](long long x) { return pm_excluded(args.s, t, x) || bv_picked(v, t, c, x); });
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
-    pm64_finish_walk(args.s, t, 1, lv, li, [&](float x, long long i) { pm_list_merge(lv, li, 1, x, i, i >= 0, [](long long) { return false; }); });
+        return score;
+    });
 }
 
 }  // namespace adkf

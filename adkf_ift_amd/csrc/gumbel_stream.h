@@ -14,7 +14,7 @@
 //             linearly in z (the left end where the cell is flat or empty), fits b = (q75 - q25) / (log log 4 - log log(4 / 3)),
 //             a = q50 + b log log 2, and draws ystar_h = a - b log(-log u).
 // A walk is k_predict_marginal's tile with GumbelEpilogue in the place of prediction's epilogue (m and v are prediction's, bit for
-// bit), and k_gumbel_walk64 for float64 tasks (k_mes_walk64's loop).
+// bit), and k_gumbel_walk64 for float64 tasks (the float64 row loop, pm64_rows of predict_stream.h).
 //
 // Independent of the grid.  A float sum over a walk's chunk would depend on how many chunks a task has, which depends on the grid
 // and on the other tasks.  Every term -log Phi is therefore turned into an unsigned 64-bit fixed-point number and added with
@@ -92,9 +92,8 @@ struct GumbelEpilogue {
         const bool in = row < tl.m;
         float mu = 0.f, sigma = 1.f;
         if (in) {
-            const float vl = tl.os - (tl.red[0][1][row] + tl.red[1][1][row]);
-            const float mean = tl.red[0][0][row] + tl.red[1][0][row];
-            sigma = sqrtf(fmaxf(vl, 1e-12f));
+            const float mean = tl.mean(row);
+            sigma = sqrtf(fmaxf(tl.var(row), 1e-12f));
             mu = a.maximize ? mean : -mean;
         }
         if (v.bracket) {
@@ -120,8 +119,8 @@ struct GumbelEpilogue {
     }
 };
 
-// ---- flagged tasks: k_mes_walk64's loop (grid (chunks, T), one wave per pool row); lane g owns probe g and keeps its own integer sum
-// over the wave's rows, one atomicAdd per lane at the end.  Bracket mode: the wave's two maxima.
+// ---- flagged tasks: the float64 row loop over the whole pool (pm64_rows: grid (chunks, T), no list); lane g owns probe g and keeps its
+// own integer sum over the wave's rows, one atomicAdd per lane at the end.  Bracket mode: the wave's two maxima.
 template <bool ARD>
 __global__ __launch_bounds__(PM64_NT) void k_gumbel_walk64(GumbelKargs<ARD> args) {
     const PmArgs& a = args.p;
@@ -133,9 +132,7 @@ __global__ __launch_bounds__(PM64_NT) void k_gumbel_walk64(GumbelKargs<ARD> args
     const float z = v.bracket ? 0.f : v.probes[(size_t)t * GB_PROBES + lane];
     unsigned long long acc = 0;
     float lo = -INFINITY, hi = -INFINITY;
-    for (int64_t r = (int64_t)blockIdx.x * PM64_WAVES + wv; r < a.rows; r += (int64_t)gridDim.x * PM64_WAVES) {
-        double s1, s2;
-        pm64_posterior_row<ARD>(a, tk, a.Zq + (size_t)r * a.d, kr[wv], s1, s2);
+    pm64_rows<ARD>(a, tk, 0, a.rows, kr[wv], [&](int64_t, const float*, const double*, double s1, double s2) {
         const float mean = (float)s1, vl = (float)(tk.os - s2);
         const float sigma = sqrtf(fmaxf(vl, 1e-12f));
         const float mu = a.maximize ? mean : -mean;
@@ -145,9 +142,7 @@ __global__ __launch_bounds__(PM64_NT) void k_gumbel_walk64(GumbelKargs<ARD> args
         } else {
             acc += gb_fixed(pm_neg_log_cdf((z - mu) / sigma));
         }
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
+    });
     if (v.bracket) {
         if (lane == 0) {
             atomicMax(v.mx + 2 * (size_t)t, gb_image(lo));

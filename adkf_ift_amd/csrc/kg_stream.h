@@ -17,9 +17,9 @@
 // lo_j < hi_j; its successor is the active line of the next larger slope, and the crossing of the sum is recomputed from that pair - so
 // a line whose interval is empty up to rounding changes the sum by rounding only, kept or dropped (kg_clip, kg_term).  O(M^2) a row.
 //
-//   k_kg_refs grid (M, T), before the walks: entry j of task t - validity and the first occurrence, the row into Xp (ARD: scaled as the
-//             walk of the task's kind scales it), k(Z_s, x_r) from the features in float64, w = A^-1 k and a_j = w . y: the first parts
-//             of k_bv_step (bv_store_row, bv_kernel_col, bv_solve_w).  Skipped entries get zero rows, mean 0 and the index -1.
+//   k_kg_refs grid (M, T), before the walks: entry j of task t - validity and the first occurrence, then the reference entry of
+//             believer_stream.h (bv_ref_entry: the row into Xp, w = A^-1 k(Z_s, x_r) and a_j = w . y).  Skipped entries get zero rows,
+//             mean 0 and the index -1.
 //   the walk  is k_predict_marginal's tile with KgEpilogue: the believer's c0 panel (bv_c0_panel) with the reference state in the
 //             place of the picks is cov(x, r_j) for the tile's 64 rows; it is stored if asked, the absent lines of a row become NaN
 //             and vc goes into the panel's pad column 64.  The slopes are never divided out: the envelope is found on the numerators
@@ -27,11 +27,11 @@
 //             two float32 inputs, which rounds once.  All 256 threads share the envelope, thread tid the row tid & 63
 //             and the lines tid >> 6, + 4, ...: the active flags (a bit mask in a register), behind a barrier NaN over the inactive
 //             lines, behind another the successor and the term of each active line; the four partial sums of a row meet where the
-//             panel was, as MesEpilogue's, and thread i < 64 adds them in the order 0, 1, 2, 3 (log: four (max, sum) pairs).  No LDS
-//             beyond prediction's.
-//   float64   tasks take k_kg_walk64, k_bv_walk64's wave-per-row loop: lane i forms c0(x, i) in float64 (bv64_c0), the mean, variance
-//             and covariances are rounded to float32 as the tile holds them, the envelope runs across the lanes with the own line as
-//             uniform data, and the terms are added in a fixed butterfly.  A task takes one kind of walk.
+//             panel was (pm_sum4, predict_stream.h; log: four (max, sum) pairs, combined here), then the shared tail (pm_tile_tail).
+//             No LDS beyond prediction's.
+//   float64   tasks take k_kg_walk64, the float64 pool walk (pm64_pool_walk): lane i forms c0(x, i) in float64 (bv64_c0), the mean,
+//             variance and covariances are rounded to float32 as the tile holds them, the envelope runs across the lanes with the
+//             own line as uniform data, and the terms are added in a fixed butterfly.  A task takes one kind of walk.
 //   selection k_pool_topk, unchanged: the candidate lists are prediction's.
 //
 // NaN is the mark of an absent line in the panel, so a covariance that IS NaN (a reference row with NaN or infinite features: its w
@@ -92,35 +92,13 @@ __global__ __launch_bounds__(256) void k_kg_refs(KgKargs<ARD> args) {
     const KgArgs& v = args.v;
     __shared__ __attribute__((aligned(16))) float fb[3 * TS_NS_MAX];
     __shared__ double red[256];
-    const int j = blockIdx.x, t = blockIdx.y, tid = threadIdx.x, M = v.M, ld = a.ns_ld, d = a.d;
+    const int j = blockIdx.x, t = blockIdx.y, M = v.M, ld = a.ns_ld;
     const size_t o = (size_t)t * M + j;
-    const int kind = pm_kind_of(a, t);
     const long long idx = v.ref_idx[o];
-    bool ok = kind >= 0 && idx >= 0 && idx < a.rows;
+    bool ok = pm_kind_of(a, t) >= 0 && idx >= 0 && idx < a.rows;
     for (int i = 0; ok && i < j; ++i) ok = v.ref_idx[(size_t)t * M + i] != idx;   // (uniform) the first occurrence counts
-    const bool f64 = kind == 2;
-    float* Xj = v.Xp + o * d;
-    float* Wj = v.W + o * ld;
-    if (!ok) {   // (uniform) a skipped entry: nothing of it is read but by the panel, whose column is ignored
-        for (int e = tid; e < d; e += 256) Xj[e] = 0.f;
-        for (int i = tid; i < ld; i += 256) { Wj[i] = 0.f; if (v.W64) v.W64[o * ld + i] = 0.0; }
-        if (tid == 0) { v.ridx[o] = -1; v.am[o] = 0.f; if (v.ref_mean) v.ref_mean[o] = 0.f; }
-        return;
-    }
-    const int n = pm_ns(a, t);
-    const float* sc = a.scal + (size_t)t * NSCAL;
-    const double os = sc[S_OS], il2 = 1.0 / ((double)sc[S_LS] * (double)sc[S_LS]);
-    const float* ys = a.y_s + (size_t)t * ld;
-    const float* xp = bv_store_row<ARD>(args, t, f64, a.Zq + (size_t)idx * d, Xj);
-    const float* vs = fb + TS_NS_MAX;
-    const double* w64 = reinterpret_cast<double*>(fb) + R64_MAXN;
-    bv_kernel_col(a, a.Zs + (size_t)t * ld * d, xp, n, os, il2, f64, reinterpret_cast<double*>(fb), fb);
-    bv_solve_w(a, t, n, f64, fb, Wj, f64 ? v.W64 + o * ld : nullptr);
-    for (int i = n + tid; i < ld; i += 256) { Wj[i] = 0.f; if (v.W64) v.W64[o * ld + i] = 0.0; }
-    double pm = 0.0;
-    for (int i = tid; i < n; i += 256) pm += (f64 ? w64[i] : (double)vs[i]) * (double)ys[i];
-    const float mean = (float)bv_block_sum(pm, red);
-    if (tid == 0) { v.ridx[o] = idx; v.am[o] = mean; if (v.ref_mean) v.ref_mean[o] = mean; }
+    const float mean = (float)bv_ref_entry<ARD>(args, t, ok, idx, v.Xp + o * a.d, v.W + o * ld, v.W64 ? v.W64 + o * ld : nullptr, fb, red);
+    if (threadIdx.x == 0) { v.ridx[o] = ok ? idx : -1; v.am[o] = mean; if (v.ref_mean) v.ref_mean[o] = mean; }
 }
 
 struct KgEpilogue {
@@ -152,10 +130,10 @@ struct KgEpilogue {
         float* Cr = C0 + row * BV_LDC;
         float ax = 0.f, s = 1.f;
         if (row < tl.m) {   // the numerators of the row's slopes, in place: NaN for an absent line, vc for the own one
-            const float vc = fmaxf(tl.os - (tl.red[0][1][row] + tl.red[1][1][row]), 1e-12f);
+            const float vc = fmaxf(tl.var(row), 1e-12f);
             const long long r = tl.r0 + row;
             s = sqrtf(vc + tl.noise);
-            ax = sgn * (tl.red[0][0][row] + tl.red[1][0][row]);
+            ax = sgn * tl.mean(row);
             for (int j = part; j < M; j += PM_NT / 64) {
                 const long long rj = ridx[j];
                 if (rj < 0 || rj == r) Cr[j] = NAN;
@@ -222,27 +200,22 @@ struct KgEpilogue {
                 }
                 score = m4 == -INFINITY ? -INFINITY : m4 + logf(tot);
             } else {
-                score = ((ps[tid] + ps[PM_TM + tid]) + ps[2 * PM_TM + tid]) + ps[3 * PM_TM + tid];
+                score = pm_sum4(ps, tid);
             }
-            const float mean = tl.red[0][0][tid] + tl.red[1][0][tid], vl = tl.red[0][1][tid] + tl.red[1][1][tid];
-            if (mean != mean || vl != vl) score = NAN;   // a NaN mean or variance: NaN, never selected (fmaxf would hide it)
-            if (v.score) v.score[(size_t)t * (size_t)a.rows + (size_t)(tl.r0 + tid)] = score;
+            if (tl.is_nan(tid)) score = NAN;   // a NaN mean or variance: NaN, never selected (fmaxf would hide it)
         }
-        if (args.s.k > 0 && (tid >> 6) == 0)
-            pm_list_merge(walk.lv, walk.li, args.s.k, score, (long long)(tl.r0 + tid), tid < tl.m, [&](long long r) { return pm_excluded(args.s, t, r); });
+        pm_tile_tail(args, tl, walk, score, v.score, t, args.s.k, pm_excl(args.s, t));
     }
 };
 static_assert(PM_NT == 4 * 64 && 8 * PM_TM <= 2 * PM_TM * LD_MN && PM_TM * BV_LDC <= 2 * PM_TM * LD_MN,
               "KgEpilogue: the panel with its pad column, then eight partial values per row, in pm_mm's staging buffers");
 
-// ---- flagged tasks: k_bv_walk64's loop (grid (chunks, T), one wave per pool row), lane i the reference line i
+// ---- flagged tasks: the float64 pool walk (pm64_pool_walk), lane i the reference line i
 template <bool ARD>
 __global__ __launch_bounds__(PM64_NT) void k_kg_walk64(KgKargs<ARD> args) {
     const PmArgs& a = args.p;
     const KgArgs& v = args.v;
     __shared__ double kr[PM64_WAVES][R64_MAXN];
-    float lv = -INFINITY;
-    long long li = -1;
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, M = v.M, log = a.log_ei;
     constexpr int OWN = 64;
     Pm64Task tk;
@@ -252,11 +225,7 @@ __global__ __launch_bounds__(PM64_NT) void k_kg_walk64(KgKargs<ARD> args) {
     const float noise = (float)tk.noise, sgn = a.maximize ? 1.f : -1.f;
     const long long rj = lane < M ? (long long)v.ridx[(size_t)t * M + lane] : -1;
     const float aj = lane < M ? sgn * v.am[(size_t)t * M + lane] : 0.f;
-    double* k = kr[wv];
-    for (int64_t r = (int64_t)blockIdx.x * PM64_WAVES + wv; r < a.rows; r += (int64_t)gridDim.x * PM64_WAVES) {
-        const float* zq = a.Zq + (size_t)r * a.d;
-        double s1, s2;
-        pm64_posterior_row<ARD>(a, tk, zq, k, s1, s2);
+    pm64_pool_walk<ARD>(args, tk, kr[wv], args.s.k, pm_excl(args.s, t), [&](int64_t r, const float* zq, const double* k, double s1, double s2) {
         const float vc = fmaxf((float)(tk.os - s2), 1e-12f), s = sqrtf(vc + noise);
         const float c0 = (float)bv64_c0<ARD>(a, tk, zq, k, Wt, Xp, M, lane);
         if (v.cov && lane < M) v.cov[((size_t)t * (size_t)a.rows + (size_t)r) * M + lane] = rj >= 0 ? c0 : 0.f;
@@ -297,12 +266,8 @@ __global__ __launch_bounds__(PM64_NT) void k_kg_walk64(KgKargs<ARD> args) {
         }
         if (s1 != s1 || s2 != s2) score = NAN;   // as the tile: a NaN mean or variance scores NaN
         if (lane == 0 && v.score) v.score[(size_t)t * (size_t)a.rows + (size_t)r] = score;
-        if (args.s.k > 0) pm_list_merge(lv, li, args.s.k, score, (long long)r, lane == 0, [&](long long q) { return pm_excluded(args.s, t, q); });
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
-    if (args.s.k <= 0) return;   // (uniform)
-    pm64_finish_walk(args.s, t, args.s.k, lv, li, [&](float x, long long i) { pm_list_merge(lv, li, args.s.k, x, i, i >= 0, [](long long) { return false; }); });
+        return score;
+    });
 }
 
 }  // namespace adkf

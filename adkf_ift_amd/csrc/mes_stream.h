@@ -7,15 +7,12 @@
 //     score(x) = (1 / S) sum_s g(gamma_s)
 // g > 0 and strictly decreasing; no incumbent enters.  pm_mes_term forms g without its two hazards (see there).
 //
-//   the walk  is k_predict_marginal's tile itself with MesEpilogue in the place of prediction's epilogue: all 256 threads score, thread
-//             tid the row tid & 63 and the samples (tid >> 6), (tid >> 6) + 4, ...; the four partial sums of a row meet in pm_mm's
-//             staging buffers (free by then, as the believer uses them), and thread i < 64 adds them in the order 0, 1, 2, 3, scales by
-//             1 / S, writes the score if asked and offers it to the walk's list as prediction's epilogue does.  m and v are
-//             prediction's, bit for bit.  No LDS beyond prediction's.
-//   float64   tasks (refine64.h) take k_mes_walk64, k_predict_marginal64's wave-per-row loop (pm64_task, pm64_posterior_row,
-//             pm64_finish_walk): the row's float64 mean and variance rounded to float32 as that kernel hands them to pm_row_out, lane
-//             s < S evaluates sample s, and the wave adds the lanes in a fixed butterfly.  A task takes one kind of walk, so the two
-//             orders of summation never meet in one task.
+//   the walk  is k_predict_marginal's tile itself with MesEpilogue in the place of prediction's epilogue: the four-wave sum over the
+//             samples (pm_sum4, predict_stream.h), scaled by 1 / S, and the shared tail (pm_tile_tail).  m and v are prediction's,
+//             bit for bit.  No LDS beyond prediction's.
+//   float64   tasks (refine64.h) take k_mes_walk64, the float64 pool walk (pm64_pool_walk): the row's float64 mean and variance
+//             rounded to float32 as k_predict_marginal64 hands them to pm_row_out, lane s < S evaluates sample s, and the wave adds
+//             the lanes in a fixed butterfly.  A task takes one kind of walk, so the two orders of summation never meet in one task.
 //   selection k_pool_topk, unchanged: the candidate lists are prediction's.
 //
 // Deterministic: no atomics, every sum has a fixed order.  A NaN or infinite ystar[t, s] makes every score of task t NaN (never selected).
@@ -77,9 +74,7 @@ struct MesEpilogue {
         const int tid = threadIdx.x, row = tid & 63, part = tid >> 6, S = v.S;
         float* ps = tl.As;   // [4][64]: the partial sums (pm_mm's staging buffers are free here)
         if (row < tl.m) {
-            const float vl = tl.os - (tl.red[0][1][row] + tl.red[1][1][row]);
-            const float mean = tl.red[0][0][row] + tl.red[1][0][row];
-            const float sigma = sqrtf(fmaxf(vl, 1e-12f));
+            const float mean = tl.mean(row), sigma = sqrtf(fmaxf(tl.var(row), 1e-12f));
             const float* ys = v.ystar + (size_t)tl.t * S;
             float sum = 0.f;
             for (int s = part; s < S; s += PM_NT / 64) sum += pm_mes_term(mes_gamma(a.maximize, ys[s], mean, sigma));
@@ -87,43 +82,30 @@ struct MesEpilogue {
         }
         __syncthreads();
         float score = 0.f;
-        if (tid < tl.m) {
-            score = (((ps[tid] + ps[PM_TM + tid]) + ps[2 * PM_TM + tid]) + ps[3 * PM_TM + tid]) * (1.f / (float)S);
-            if (v.score) v.score[(size_t)tl.t * (size_t)a.rows + (size_t)(tl.r0 + tid)] = score;
-        }
-        if (args.s.k > 0 && (tid >> 6) == 0)
-            pm_list_merge(walk.lv, walk.li, args.s.k, score, (long long)(tl.r0 + tid), tid < tl.m, [&](long long r) { return pm_excluded(args.s, tl.t, r); });
+        if (tid < tl.m) score = pm_sum4(ps, tid) * (1.f / (float)S);
+        pm_tile_tail(args, tl, walk, score, v.score, tl.t, args.s.k, pm_excl(args.s, tl.t));
     }
 };
-static_assert(PM_NT == 4 * 64 && 4 * PM_TM <= 2 * PM_TM * LD_MN, "MesEpilogue: four partial sums per row, in pm_mm's staging buffers");
 
-// ---- flagged tasks: k_predict_marginal64's loop (grid (chunks, T), one wave per pool row), lane s the term of sample s
+// ---- flagged tasks: the float64 pool walk (pm64_pool_walk), lane s the term of sample s
 template <bool ARD>
 __global__ __launch_bounds__(PM64_NT) void k_mes_walk64(MesKargs<ARD> args) {
     const PmArgs& a = args.p;
     const MesArgs& v = args.v;
     __shared__ double kr[PM64_WAVES][R64_MAXN];
-    float lv = -INFINITY;
-    long long li = -1;
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, S = v.S;
     Pm64Task tk;
     if (!pm64_task<ARD>(args, t, tk)) return;   // (uniform)
     const float ys = lane < S ? v.ystar[(size_t)t * S + lane] : 0.f;
-    for (int64_t r = (int64_t)blockIdx.x * PM64_WAVES + wv; r < a.rows; r += (int64_t)gridDim.x * PM64_WAVES) {
-        double s1, s2;
-        pm64_posterior_row<ARD>(a, tk, a.Zq + (size_t)r * a.d, kr[wv], s1, s2);
+    pm64_pool_walk<ARD>(args, tk, kr[wv], args.s.k, pm_excl(args.s, t), [&](int64_t r, const float*, const double*, double s1, double s2) {
         const float mean = (float)s1, vl = (float)(tk.os - s2);
         const float sigma = sqrtf(fmaxf(vl, 1e-12f));
         float g = lane < S ? pm_mes_term(mes_gamma(a.maximize, ys, mean, sigma)) : 0.f;
         for (int o = 32; o > 0; o >>= 1) g += __shfl_xor(g, o);
         const float score = g * (1.f / (float)S);
         if (lane == 0 && v.score) v.score[(size_t)t * (size_t)a.rows + (size_t)r] = score;
-        if (args.s.k > 0) pm_list_merge(lv, li, args.s.k, score, (long long)r, lane == 0, [&](long long q) { return pm_excluded(args.s, t, q); });
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
-    if (args.s.k <= 0) return;   // (uniform)
-    pm64_finish_walk(args.s, t, args.s.k, lv, li, [&](float x, long long i) { pm_list_merge(lv, li, args.s.k, x, i, i >= 0, [](long long) { return false; }); });
+        return score;
+    });
 }
 
 }  // namespace adkf

@@ -68,6 +68,11 @@
 // BvEpilogue downdates the variance with the picks made so far before it scores; MesEpilogue (mes_stream.h) scores every row against
 // max-value samples with all four waves; GumbelEpilogue (gumbel_stream.h) reduces the tile's rows to two maxima or 64 fixed-point sums
 // per task; GibbonEpilogue (gibbon_stream.h) runs the believer's downdate and then MES's four-wave sum of the GIBBON terms.  The instances of the default are the kernels as they were, arithmetic and order.
+//
+// Shared by every pool acquisition (believer, MES, GIBBON, KG, JES, Gumbel), each described once, where it is defined: the head and
+// tail of a tile epilogue (PmTile::mean / ck / var / is_nan, pm_sum4, pm_excl, pm_tile_tail, next to PmTile) and the float64 walk
+// (pm64_rows, pm64_pool_walk, next to pm64_finish_walk).  Thompson's float64 kernel stays apart: it merges S lists, and
+// Pm64Task::il2 says why its kernel row is not this one's.
 #pragma once
 #include <type_traits>
 
@@ -463,9 +468,34 @@ struct PmTile {
     float *As, *Bs;                         // pm_mm's staging buffers, ADJACENT (2 * PM_TM * LD_MN floats from As) and free
     float (*rowsq)[2][PM_TM];
     float (*red)[2][PM_TM];                 // red[wc][0 | 1][row]: the halves of sum_j C_ij y_j and sum_j C_ij K_ij
+    // a row's posterior: the mean C . y, the sum C . K alone (NaN exactly when the variance is) and the latent variance os - C . K
+    __device__ __forceinline__ float mean(int row) const { return red[0][0][row] + red[1][0][row]; }
+    __device__ __forceinline__ float ck(int row) const { return red[0][1][row] + red[1][1][row]; }
+    __device__ __forceinline__ float var(int row) const { return os - ck(row); }
+    // the row's own mean or variance is NaN: what an epilogue that clamps with fmaxf has to ask, or the row gets a finite score
+    __device__ __forceinline__ bool is_nan(int row) const { const float m = mean(row), c = ck(row); return m != m || c != c; }
 };
 
-// the epilogue of prediction: the first 64 threads write the outputs of their row; POOL: the first wave merges the scores into the walk's list
+// ---- the head and the tail that the epilogues share.  An epilogue is entered by all 256 threads.  Those that score with every wave
+// (MES, GIBBON, KG, JES) give thread tid the row tid & 63 and the terms tid >> 6, + 4, ... of that row; the four partial values of
+// a row meet in pm_mm's staging buffers as ps[part * PM_TM + row] (free by then; behind a barrier where a c0 panel was there), and
+// thread i < 64 adds them in the order 0, 1, 2, 3:
+static_assert(PM_NT == 4 * 64 && 4 * PM_TM <= 2 * PM_TM * LD_MN, "four partial sums per row, in pm_mm's staging buffers");
+__device__ __forceinline__ float pm_sum4(const float* ps, int row) { return ((ps[row] + ps[PM_TM + row]) + ps[2 * PM_TM + row]) + ps[3 * PM_TM + row]; }
+
+// task t's exclusion list as the predicate of pm_list_merge
+__device__ __forceinline__ auto pm_excl(const PmPool& s, int t) { return [&s, t](long long r) { return pm_excluded(s, t, r); }; }
+
+// The tail of a pool epilogue: thread i < tl.m, which holds the score of row i, writes it to out[plane, r0 + i] (out: nullable,
+// [planes, rows]), then the first wave offers the tile's scores to the walk's list of `width` entries, but for the rows excl(r) holds for.
+template <class ARGS, class WALK, class EX>
+__device__ __forceinline__ void pm_tile_tail(const ARGS& args, const PmTile& tl, WALK& walk, float score, float* out, size_t plane, int width, EX excl) {
+    const int tid = threadIdx.x;
+    if (out && tid < tl.m) out[plane * (size_t)args.p.rows + (size_t)(tl.r0 + tid)] = score;
+    if (width > 0 && (tid >> 6) == 0) pm_list_merge(walk.lv, walk.li, width, score, (long long)(tl.r0 + tid), tid < tl.m, excl);
+}
+
+// the epilogue of prediction: the first 64 threads write the outputs of their row (pm_row_out); POOL: the tail, with nothing more to store
 struct PmRowEpilogue {
     using Args = PmNoEpilogueArgs;
     template <bool ARD, bool POOL, class ARGS, class WALK>
@@ -473,12 +503,10 @@ struct PmRowEpilogue {
         const int tid = threadIdx.x;
         [[maybe_unused]] float score = 0.f;
         if (tid < tl.m) {
-            const float vl = tl.os - (tl.red[0][1][tid] + tl.red[1][1][tid]);
-            score = pm_row_out<POOL>(args, tl.t, tl.r0 + tid, tl.red[0][0][tid] + tl.red[1][0][tid], vl, vl + tl.noise);
+            const float vl = tl.var(tid);
+            score = pm_row_out<POOL>(args, tl.t, tl.r0 + tid, tl.mean(tid), vl, vl + tl.noise);
         }
-        if constexpr (POOL)
-            if (args.s.k > 0 && (tid >> 6) == 0)
-                pm_list_merge(walk.lv, walk.li, args.s.k, score, (long long)(tl.r0 + tid), tid < tl.m, [&](long long r) { return pm_excluded(args.s, tl.t, r); });
+        if constexpr (POOL) pm_tile_tail(args, tl, walk, score, nullptr, 0, args.s.k, pm_excl(args.s, tl.t));
     }
 };
 
@@ -714,32 +742,60 @@ __device__ __forceinline__ void pm64_finish_walk(const PmPool& s, int t, int wid
     }
 }
 
-// POOL: grid (chunks, T); workgroup (c, t) walks the pool rows c * 4 + wave, stride chunks * 4, and writes the list of (t, c)
+// ---- the float64 walk.  Every float64 kernel of a pool call but Thompson's (k_predict_marginal64, k_bv_walk64, k_mes_walk64,
+// k_gb_walk64, k_kg_walk64, k_jes_walk64, k_gumbel_walk64) has this shape: kr[PM64_WAVES][R64_MAXN] doubles of LDS, pm64_task
+// with a uniform return for a task it does not own, then one of the two functions below with what it does to a row.
+//
+// The rows of one wave: lo + blockIdx.x * 4 + wave, stride gridDim.x * 4, below hi.  Per row the float64 posterior
+// (pm64_posterior_row, the kernel row into k - this wave's row of kr), then row(r, zq, k, s1, s2), entered by the whole wave.
+template <bool ARD, class F>
+__device__ __forceinline__ void pm64_rows(const PmArgs& a, const Pm64Task& tk, int64_t lo, int64_t hi, double* k, F row) {
+    const int wv = threadIdx.x >> 6;
+    for (int64_t r = lo + (int64_t)blockIdx.x * PM64_WAVES + wv; r < hi; r += (int64_t)gridDim.x * PM64_WAVES) {
+        const float* zq = a.Zq + (size_t)r * a.d;
+        double s1, s2;
+        pm64_posterior_row<ARD>(a, tk, zq, k, s1, s2);
+        row(r, zq, k, s1, s2);
+        // the next row overwrites k, which lanes of this wave may still be reading (the products of row(): bv64_c0's k . w); a wave
+        // is not lockstep for the compiler, so the barrier keeps the instructions apart and the fence orders the LDS traffic
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    }
+}
+
+// The walk of workgroup (c, t) of a grid (chunks, T) over the whole pool, keeping a list: every wave offers the score that row()
+// returns in lane 0 (row() also does the acquisition's own stores) to its list of `width` entries, but for the rows excl(r) holds for;
+// at the end the four lists become that of (t, c) (pm64_finish_walk).  width <= 0 (uniform): no list, the rows are only evaluated.
+template <bool ARD, class ARGS, class EX, class F>
+__device__ __forceinline__ void pm64_pool_walk(const ARGS& args, const Pm64Task& tk, double* k, int width, EX excl, F row) {
+    const int t = blockIdx.y, lane = threadIdx.x & 63;
+    float lv = -INFINITY;
+    long long li = -1;
+    pm64_rows<ARD>(args.p, tk, 0, args.p.rows, k, [&](int64_t r, const float* zq, const double* kq, double s1, double s2) {
+        const float score = row(r, zq, kq, s1, s2);
+        if (width > 0) pm_list_merge(lv, li, width, score, (long long)r, lane == 0, excl);
+    });
+    if (width <= 0) return;   // (uniform)
+    pm64_finish_walk(args.s, t, width, lv, li, [&](float v, long long i) { pm_list_merge(lv, li, width, v, i, i >= 0, [](long long) { return false; }); });
+}
+
+// prediction's own: the rows of the task's range, or (POOL) the pool walk with the score of pm_row_out
 template <bool ARD = false, bool POOL = false>
 __global__ __launch_bounds__(PM64_NT) void k_predict_marginal64(PmArgsOf<ARD, POOL> args) {
     const PmArgs& a = args.p;
     __shared__ double kr[PM64_WAVES][R64_MAXN];
-    [[maybe_unused]] float lv = -INFINITY;   // POOL: every wave keeps a list of the rows it evaluates; merged at the end
-    [[maybe_unused]] long long li = -1;
     const int t = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     Pm64Task tk;
     if (!pm64_task<ARD>(args, t, tk)) return;   // (uniform)
-    int64_t lo, hi;
-    if constexpr (POOL) { lo = 0; hi = a.rows; }
-    else pm_range(a, t, lo, hi);
-    for (int64_t r = lo + (int64_t)blockIdx.x * PM64_WAVES + wv; r < hi; r += (int64_t)gridDim.x * PM64_WAVES) {
-        double s1, s2;
-        pm64_posterior_row<ARD>(a, tk, a.Zq + (size_t)r * a.d, kr[wv], s1, s2);
-        [[maybe_unused]] float score = 0.f;
-        if (lane == 0) score = pm_row_out<POOL>(args, t, r, (float)s1, (float)(tk.os - s2), (float)(tk.os - s2 + tk.noise));
-        if constexpr (POOL)
-            if (args.s.k > 0) pm_list_merge(lv, li, args.s.k, score, (long long)r, lane == 0, [&](long long q) { return pm_excluded(args.s, t, q); });
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
+    auto out = [&](int64_t r, const float*, const double*, double s1, double s2) {
+        return lane == 0 ? pm_row_out<POOL>(args, t, r, (float)s1, (float)(tk.os - s2), (float)(tk.os - s2 + tk.noise)) : 0.f;
+    };
     if constexpr (POOL) {
-        if (args.s.k <= 0) return;   // (uniform)
-        pm64_finish_walk(args.s, t, args.s.k, lv, li, [&](float v, long long i) { pm_list_merge(lv, li, args.s.k, v, i, i >= 0, [](long long) { return false; }); });
+        pm64_pool_walk<ARD>(args, tk, kr[wv], args.s.k, pm_excl(args.s, t), out);
+    } else {
+        int64_t lo, hi;
+        pm_range(a, t, lo, hi);
+        pm64_rows<ARD>(a, tk, lo, hi, kr[wv], out);
     }
 }
 

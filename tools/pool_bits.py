@@ -5,10 +5,11 @@
 
 dump runs, on the problems of the GPU tests (tests/test_gpu_believer_pool._explicit: plain at 48 points, refined at 200, global slots
 at 1024; the ARD problem of tests/test_gpu_believer_pool_ard; tests/test_gpu_predict_pool._ill_batch, whose flagged tasks take the
-float64 walks): believer_pool with EI and with log EI and gibbon_pool, each with trace, predict_pool(log EI, k = 8), believer_pool_ard,
-kg_pool with KG and with log KG (score, cov, ref_mean and the selection; M = 16 reference rows of lowest posterior mean, a -1 and a
-repetition among them), and ehvi_pool on the problems of tests/test_gpu_ehvi_pool.py's score test (score, staircase and selection, linear
-and log, with and without the constraints); on each of the five problems also mes_pool and jes_pool (score and k = 8; the optima of
+float64 walks; tests/test_gpu_believer_pool_ard._f64_batch, an ARD batch whose tasks are all flagged, under float64_ard - the ARD
+instances of the float64 walks): believer_pool with EI and with log EI and gibbon_pool, each with trace, predict_pool(log EI, k = 8),
+believer_pool_ard, kg_pool with KG and with log KG (score, cov, ref_mean and the selection; M = 16 reference rows of lowest posterior
+mean, a -1 and a repetition among them), and ehvi_pool on the problems of tests/test_gpu_ehvi_pool.py's score test (score, staircase
+and selection, linear and log, with and without the constraints); on each of the six problems also mes_pool and jes_pool (score and k = 8; the optima of
 jes_pool at the first eight reference rows of kg_pool, their -1 and their repetition included), gumbel_pool on fixed uniforms and
 thompson_pool / thompson_pool_ard (m = 64 features and four paths from seeded generators, with the paths) - and saves every returned
 tensor.  Then the records of the six batched BO loops of adkf_ift_amd.bayes_opt, as int64 tensors under records/: a generated pool of
@@ -80,6 +81,14 @@ def dump(path):
         put(f"float64/kg/log={log}", gp_ops.kg_pool(b, phi, X, ref_idx=kg_refs(b, phi, X), log=log, topk=8, want_cov=True))
     put("float64/gibbon", gp_ops.gibbon_pool(b, phi, X, ystar=(best[:, None] - torch.tensor([[1.0, 2.0]], device=dev)).contiguous(), q=6, want_trace=True))
     sampled("float64", b, phi, X, (best[:, None] - torch.tensor([[1.0, 2.0]], device=dev)).contiguous(), kg_refs(b, phi, X))
+    b, phi, Zs, ys, n_s, X, best = BVA._f64_batch(dev)   # ARD, every task flagged: the <true> instances of the float64 walks
+    best = best.to(dev)
+    ystar = (best[:, None] - torch.tensor([[1.0, 2.0]], device=dev)).contiguous()
+    put("float64_ard/believer", gp_ops.believer_pool_ard(b, phi, X, best_f=best, q=6, want_trace=True))
+    for log in (False, True):
+        put(f"float64_ard/kg/log={log}", gp_ops.kg_pool(b, phi, X, ref_idx=kg_refs(b, phi, X), log=log, topk=8, want_cov=True))
+    put("float64_ard/gibbon", gp_ops.gibbon_pool(b, phi, X, ystar=ystar, q=6, want_trace=True))
+    sampled("float64_ard", b, phi, X, ystar, kg_refs(b, phi, X))
     import test_gpu_ehvi_pool as EV
     from test_ehvi_pool_cpu import GPU_CASES
 
