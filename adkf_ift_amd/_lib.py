@@ -24,6 +24,9 @@ KG_REFS_MAX = 64         # adkf_kg_pool: reference rows per task
 EHVI_FRONT_MAX = 64      # adkf_ehvi_pool: front points per group
 EHVI_CONS_MAX = 4        # ... constraint tasks per group
 EHVI_CHUNK_ROWS = 16384  # ... pool rows per chunk of its walk
+PM_SCORE_BALD = 32       # adkf_mix_pool: rank by the disagreement of the members
+MIX_MEMBERS_MAX = 64     # ... member tasks per group
+MIX_CHUNK_ROWS = 16384   # ... pool rows per chunk of its walk
 TS_SAMPLES_MAX = 64      # adkf_thompson_pool: posterior draws per task
 TS_FEATURES_MAX = 4096   # ... random Fourier features (a multiple of 64, at least 64)
 
@@ -111,6 +114,10 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adkf_mix_pool_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "adkf_mix_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_outer_nll_value_grad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_ift_hypergrad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -258,7 +258,7 @@ def _take_picks(top_idx: torch.Tensor, usable: torch.Tensor, query_batch_size: i
 def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
                          kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
                          rngs: List[np.random.Generator], acquisition: str = "ei", batch: str = "topk",
-                         ard: bool = False) -> List[List[int]]:
+                         ard: bool = False, marginalize: int = 0) -> List[List[int]]:
     """``len(rngs)`` replicates of ``run_gp_ei_bo`` over the same pool at once; returns their records.  Per iteration the
     replicates' queried sets form ONE batch (initial parameters and priors as ``create_gp`` makes them for each), fitted by ONE
     ``gp_ops.fit`` with ``fit_gpytorch_scipy``'s options and scored by ONE ``gp_ops.predict_pool`` call that excludes each
@@ -271,13 +271,26 @@ def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
     ``query_batch_size = 1`` the two are the same loop.
     ``ard``: one lengthscale per feature dimension (the reference's ``ard_num_dims``) - each replicate's ``create_gp`` start is
     expanded to ``[2 + d]`` as ``run_gp_ts_bo_batched(ard=True)`` expands it; the batch is an ARD batch, which ``predict_pool``
-    takes as it is and for which ``"believer"`` calls ``gp_ops.believer_pool_ard``."""
+    takes as it is and for which ``"believer"`` calls ``gp_ops.believer_pool_ard``.
+    ``marginalize``: 0 scores at the MAP point of the fit.  ``M >= 2`` (at most 64, ``batch="topk"``, isotropic) integrates the
+    acquisition over the hyperparameters (Snoek et al. 2012): after the fit each replicate draws ``M - 1`` Laplace samples of its
+    ``phi`` from a torch generator of its own (``gp_ops.phi_laplace_samples``; member 0 is the MAP point), the batch is replicated M
+    times (``gp_ops.replicate_batch``) and ONE ``gp_ops.mix_pool`` call ranks the pool by the members' average EI (or by its
+    logarithm) per replicate, under the same exclusions and the same rule for what counts."""
     log = _acquisition(acquisition)
     if batch not in ("topk", "believer"):
         raise ValueError(f"batch must be 'topk' or 'believer', got {batch!r}")
+    marginalize = int(marginalize)
+    if marginalize == 1 or not 0 <= marginalize <= 64:
+        raise ValueError(f"marginalize must be 0 or in [2, 64], got {marginalize}")
+    if marginalize and batch != "topk":
+        raise ValueError("marginalize needs batch='topk': the believer's greedy steps condition one model, not a mixture")
+    if marginalize and ard:
+        raise ValueError("marginalize needs ard=False: the Laplace samples cover isotropic batches only")
     n = x_all.shape[0]
     y_all, X, queried = _bo_start(x_all, y_all, num_init_points, init_from, rngs)
     records = [[min(q)] for q in queried]
+    gens = _path_generators(rngs) if marginalize else None
 
     for _ in range(num_bo_iters):
         b, phi = _fit_tasks("run_gp_ei_bo_batched", x_all, [(q, y_all) for q in queried], X, kernel_type, device, noise_init, noise_prior,
@@ -287,6 +300,16 @@ def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
             believe = gp_ops.believer_pool_ard if b.ard else gp_ops.believer_pool
             out = believe(b, phi, X, best_f=best_f, q=query_batch_size, maximize=False, log_ei=log, exclude=queried)
             top_idx, top_val = out["sel_idx"].cpu(), out["sel_val"].cpu()
+        elif marginalize:
+            M = marginalize
+            b.flags &= ~gp_ops.REUSE_INNER   # the sampler evaluates the gradient away from the fit's phi
+            eps = torch.stack([torch.randn(M, 3, dtype=torch.float64, generator=g) for g in gens])
+            phis = gp_ops.phi_laplace_samples(b, phi, M, eps=eps)
+            bm, members = gp_ops.replicate_batch(b, M)
+            out = gp_ops.mix_pool(bm, phis.reshape(-1, 3), X, members=members, best_f=best_f.repeat_interleave(M),
+                                  score="log_ei" if log else "ei", latent=True, maximize=False, want_mean=False, want_var=False,
+                                  want_score=False, topk=query_batch_size, exclude=queried)
+            top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
         else:
             out = gp_ops.predict_pool(b, phi, X, latent=True, best_f=best_f, maximize=False, want_mean=False, want_var=False,
                                       want_ei=False, topk=query_batch_size, exclude=queried, log_ei=log)

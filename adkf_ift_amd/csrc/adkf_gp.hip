@@ -32,6 +32,7 @@
 #include "kg_stream.h"
 #include "jes_stream.h"
 #include "ehvi_stream.h"
+#include "mix_stream.h"
 
 #include "host_common.h"
 #include "host_gp.h"
@@ -341,6 +342,19 @@ int adkf_ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const
                    void* scratch, size_t scratch_bytes, void* stream) {
     return ehvi_pool(b, phi, flags, X, rows, G, obj, obj_max, ref, front, front_n, P, con, con_thr, con_geq, C, excl_idx, excl_off, score,
                      stair, stair_n, k, top_idx, top_val, info, ws, ws_bytes, scratch, scratch_bytes, stream);
+}
+
+size_t adkf_mix_pool_scratch_bytes(int32_t T, int32_t G, int32_t k) {
+    if (T <= 0 || G < 1 || k < 0 || k > ADKF_POOL_TOPK_MAX) return 0;
+    return mix_scratch(nullptr, T, G, k).bytes;
+}
+
+int adkf_mix_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, int32_t G, const int32_t* mem,
+                  const float* w, int32_t M, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, float* mean,
+                  float* var, float* score, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes,
+                  void* scratch, size_t scratch_bytes, void* stream) {
+    return mix_pool(b, phi, flags, X, rows, G, mem, w, M, best_f, excl_idx, excl_off, mean, var, score, k, top_idx, top_val, info, ws,
+                    ws_bytes, scratch, scratch_bytes, stream);
 }
 
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

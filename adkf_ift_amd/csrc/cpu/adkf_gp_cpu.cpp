@@ -1516,6 +1516,110 @@ int adkf_ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const
     return 0;
 }
 
+size_t adkf_mix_pool_scratch_bytes(int32_t, int32_t, int32_t) { return 0; }
+
+// Hyperparameter-marginalised prediction and acquisition over a shared pool (include/adkf_gp.h): the members' mean, variance and EI
+// (log EI) of every task at every pool row first - adkf_predict_pool's float32 values, which is what the header defines the
+// mixture on - then per group the mixture in float64, rounded to float32 at the boundary; the selection ranks those float32 values
+// under adkf_predict_pool's total order.
+int adkf_mix_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, int32_t G, const int32_t* mem,
+                  const float* w, int32_t M, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, float* mean,
+                  float* var, float* score, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void*, size_t, void*, size_t,
+                  void*) {
+    if (int rc = check(b, false, true)) return rc;
+    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN | ADKF_PM_LOG_EI | ADKF_PM_SCORE_BALD)) return ADKF_E_BADARG;
+    const bool by_mean = (flags & ADKF_PM_SCORE_MEAN) != 0, by_bald = (flags & ADKF_PM_SCORE_BALD) != 0, lg = (flags & ADKF_PM_LOG_EI) != 0;
+    if ((by_mean && by_bald) || (lg && (by_mean || by_bald))) return ADKF_E_BADARG;
+    if (G < 1 || M < 1 || !mem || k < 0) return ADKF_E_BADARG;
+    if (M > ADKF_MIX_MEMBERS_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    const bool want_score = score || k > 0, want_e = want_score && !by_mean && !by_bald;
+    if (want_e && !best_f) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (k == 0 && !mean && !var && !score) return ADKF_E_BADARG;
+    const int T = b->T;
+    const size_t R = (size_t)rows;
+    const float ninf = -std::numeric_limits<float>::infinity(), fnan = std::numeric_limits<float>::quiet_NaN();
+    const double dinf = std::numeric_limits<double>::infinity();
+    const int pm_flags = flags & (ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI);
+    std::vector<float> mu((size_t)T * R), vr((size_t)T * R), ei(want_e ? (size_t)T * R : 0);
+    std::vector<char> done(T, 0);
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < T; ++t)
+        done[t] = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
+            float e1 = 0.f;
+            pm_row(in, b->kernel, D, b->y_s + (size_t)t * b->ns_max, pm_flags, best_f, t, 0, &mu[(size_t)t * R + r], &vr[(size_t)t * R + r],
+                   want_e ? &e1 : nullptr);
+            if (want_e) ei[(size_t)t * R + r] = e1;
+        }) ? 1 : 0;
+#pragma omp parallel for schedule(dynamic)
+    for (int g = 0; g < G; ++g) {
+        // the used entries in entry order, W their float32 sum in that order
+        std::vector<int> ts;
+        std::vector<float> ws;
+        bool bad = false;
+        float W = -0.f;
+        for (int j = 0; j < M; ++j) {
+            const int t = mem[(size_t)g * M + j];
+            if (t == -1) continue;
+            const float wj = w ? w[(size_t)g * M + j] : 1.f;
+            if (t < 0 || t >= T || !(wj >= 0.f) || std::isinf(wj)) { bad = true; continue; }
+            if (!(wj > 0.f)) continue;
+            if (!done[t]) bad = true;
+            ts.push_back(t); ws.push_back(wj); W += wj;
+        }
+        bad = bad || ts.empty() || !std::isfinite(W);
+        const int n = (int)ts.size();
+        std::vector<double> wt(n);
+        for (int i = 0; i < n; ++i) wt[i] = (double)(ws[i] / W);
+        for (int q = 0; q < k; ++q) { top_idx[(size_t)g * k + q] = -1; top_val[(size_t)g * k + q] = ninf; }
+        std::vector<float> sc(R, fnan);
+        for (size_t r = 0; r < R; ++r) {
+            const size_t o = (size_t)g * R + r;
+            if (bad) {
+                if (mean) mean[o] = fnan;
+                if (var) var[o] = fnan;
+                continue;
+            }
+            double m1 = 0.0, within = 0.0, between = 0.0, wc = 0.0, sl = 0.0, se = 0.0, mx = -dinf;
+            for (int i = 0; i < n; ++i) m1 += wt[i] * (double)mu[(size_t)ts[i] * R + r];
+            for (int i = 0; i < n; ++i) {
+                const size_t q = (size_t)ts[i] * R + r;
+                const double vi = vr[q], dev = (double)mu[q] - m1, vc = vi < 1e-12 ? 1e-12 : vi;
+                within += wt[i] * vi; between += wt[i] * dev * dev;
+                wc += wt[i] * vc; sl += wt[i] * std::log(vc);
+                if (want_e) { const double e1 = ei[q]; if (lg) { if (e1 == e1) mx = std::max(mx, e1); } else se += wt[i] * e1; }
+            }
+            if (mean) mean[o] = (float)m1;
+            if (var) var[o] = (float)(within + between);
+            if (!want_score) continue;
+            double val;
+            if (by_mean) val = (flags & ADKF_PM_MAXIMIZE) ? m1 : -m1;
+            else if (by_bald) val = 0.5 * (std::log(wc + between) - sl);
+            else if (!lg) val = se;
+            else {
+                double sum = 0.0;
+                for (int i = 0; i < n; ++i) { const double e1 = ei[(size_t)ts[i] * R + r]; if (e1 != -dinf) sum += wt[i] * std::exp(e1 - mx); }
+                val = sum == 0.0 ? -dinf : mx + std::log(sum);
+            }
+            sc[r] = (float)val;
+        }
+        if (score) std::copy(sc.begin(), sc.end(), score + (size_t)g * R);
+        if (bad || k <= 0) continue;
+        std::vector<int64_t> cand;
+        const int64_t *xb = excl_idx ? excl_idx + excl_off[g] : nullptr, *xe = excl_idx ? excl_idx + excl_off[g + 1] : nullptr;
+        for (int64_t r = 0; r < rows; ++r)
+            if (sc[r] == sc[r] && !(xb && std::binary_search(xb, xe, r))) cand.push_back(r);
+        const size_t kk = std::min<size_t>(k, cand.size());
+        std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return sc[a] > sc[c] || (sc[a] == sc[c] && a < c); });
+        for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)g * k + q] = cand[q]; top_val[(size_t)g * k + q] = sc[cand[q]]; }
+    }
+    return 0;
+}
+
 static int outer_common(const adkf_batch_t* b, const float* phi, int flags, bool with_hessian, float* f_out, float* g_phi, float* dZ_s, float* dZ_q,
                         float* v_out, float* H_out, int32_t* info) {
     const int d = b->d;

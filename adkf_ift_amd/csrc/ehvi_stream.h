@@ -270,19 +270,7 @@ __global__ __launch_bounds__(EHVI_NT) void k_ehvi_score(EhviArgs e) {
 
 // ---- one wave per group: the group's lists merged under the total order, top_idx / top_val [G, k] (nothing listed: -1 / -inf)
 __global__ __launch_bounds__(64) void k_ehvi_topk(EhviArgs e) {
-    const int g = blockIdx.x, lane = threadIdx.x, k = e.s.k;
-    const int total = (e.rows > 0 ? e.cpg : 0) * k;
-    const size_t base = (size_t)g * e.s.chunks_max * k;
-    float lv = -INFINITY;
-    long long li = -1;
-    for (int e0 = 0; e0 < total; e0 += 64) {
-        const int q = e0 + lane;
-        const bool in = q < total;
-        const long long r = in ? (long long)e.s.cand_idx[base + q] : -1;
-        const float v = in ? e.s.cand_val[base + q] : 0.f;
-        pm_list_merge(lv, li, k, v, r, r >= 0, [](long long) { return false; });
-    }
-    if (lane < k) { e.s.top_idx[(size_t)g * k + lane] = li; e.s.top_val[(size_t)g * k + lane] = li >= 0 ? lv : -INFINITY; }
+    pm_group_topk(e.s, blockIdx.x, e.rows > 0 ? e.cpg : 0);
 }
 
 }  // namespace adkf

@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool and adkf_ehvi_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ehvi_pool and adkf_mix_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
 // pool calls share (pool_walks, pool_select, pool_greedy) and the body of every entry.
 #pragma once
 #include "host_ard.h"
@@ -835,6 +835,97 @@ int ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const floa
     e.s.cand_idx = l.cand.idx; e.s.cand_val = l.cand.val;
     e.s.top_idx = top_idx; e.s.top_val = top_val;
     return c.ard ? ehvi_launch<true>(c, e, X, rows, info) : ehvi_launch<false>(c, e, X, rows, info);
+}
+
+// adkf_mix_pool: the scratch is stage A's mean, variance and EI (or log EI) of one chunk of the pool, [T, MIX_CHUNK_ROWS] each, the
+// groups' state [G] and the candidate lists, one per (group, walker), at most max(PM_POOL_LISTS, G) of k entries.  It depends on
+// neither rows, ns, d nor M, and it does not shrink when T, G or k grow.
+struct MixScratch { float *m, *v, *e; MixGroup* grp; CandLists cand; size_t bytes; };
+inline MixScratch mix_scratch(void* base, int T, int G, int k) {
+    Arena ar{static_cast<char*>(base), 0};
+    const size_t mv = (size_t)T * MIX_CHUNK_ROWS, c = (size_t)std::max(PM_POOL_LISTS, G) * k;
+    MixScratch l{};
+    l.m = ar.floats(mv);
+    l.v = ar.floats(mv);
+    l.e = ar.floats(mv);
+    l.grp = ar.as<MixGroup>((size_t)G);
+    l.cand = carve_cand(ar, c);
+    l.bytes = ar.off;
+    return l;
+}
+static_assert(MIX_MEMBERS_MAX == ADKF_MIX_MEMBERS_MAX && MIX_CHUNK_ROWS == ADKF_MIX_CHUNK_ROWS && MIX_CHUNK_ROWS % PM_TM == 0,
+              "mix_stream.h limits");
+
+// The launches of a prepared mixture call: the groups' state, then per chunk of the pool prediction's own pool launch (the members'
+// mean and, where something reads them, variance and EI into the scratch, no selection) and the outputs of that chunk; at the end one
+// wave per group merges the group's lists.  pm_flags: the caller's LATENT, MAXIMIZE and LOG_EI.
+template <bool ARD>
+int mix_launch(const PmCtx& c, MixArgs& e, int32_t pm_flags, const float* best_f, const float* X, int64_t rows, int32_t* info) {
+    hipStream_t st = c.st;
+    const int T = c.b.T, G = e.G, k = e.s.k;
+    if (k > 0) hipMemsetAsync(e.s.cand_idx, 0xff, sizeof(int64_t) * (size_t)G * e.s.chunks_max * k, st);
+    // the groups' "cannot be evaluated" flags read info and n_s here, once: pm_prepare has written info, and nothing below writes it
+    // again (prediction's walks only read it), so the flags hold for every chunk
+    k_mix_groups<<<G, 64, 0, st>>>(pm_args(c, 0, X, rows, info), e);
+    // one grid for every chunk, so that a list has the same walker throughout
+    const int64_t items = (int64_t)G * ((std::min<int64_t>(rows, MIX_CHUNK_ROWS) + PM_TM - 1) / PM_TM);
+    const int grid = pm_persistent_grid(k_mix_score, MIX_NT, 0, std::max<int64_t>(items, 1));
+    e.cpg = std::max(1, std::min(grid / G, e.s.chunks_max));
+    float* m = const_cast<float*>(e.m);
+    float* v = const_cast<float*>(e.v);
+    float* ei = const_cast<float*>(e.e);
+    for (int64_t c0 = 0; c0 < rows; c0 += MIX_CHUNK_ROWS) {
+        const int64_t L = std::min<int64_t>(MIX_CHUNK_ROWS, rows - c0);
+        PmPool none = pm_pool(nullptr, nullptr, 0, T, nullptr, nullptr, L, st);
+        const PmCall io{pm_flags, X + (size_t)c0 * c.b.d, nullptr, L, best_f, m, v, ei, info, &none};
+        // the whole of prediction's sequence per chunk, as ehvi_launch runs it and for its reason
+        const int rc = pm_launch<ARD, true>(c, io);
+        if (rc) return rc;
+        e.c0 = c0; e.L = L;
+        k_mix_score<<<grid, MIX_NT, 0, st>>>(e);
+    }
+    if (k > 0) k_mix_topk<<<G, 64, 0, st>>>(e);
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_mix_pool: isotropic and ARD batches alike (as adkf_mes_pool)
+int mix_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, int32_t G, const int32_t* mem,
+             const float* w, int32_t M, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, float* mean, float* var,
+             float* score, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch,
+             size_t scratch_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN | ADKF_PM_LOG_EI | ADKF_PM_SCORE_BALD)) return ADKF_E_BADARG;
+    const bool by_mean = flags & ADKF_PM_SCORE_MEAN, by_bald = flags & ADKF_PM_SCORE_BALD, lg = flags & ADKF_PM_LOG_EI;
+    if ((by_mean && by_bald) || (lg && (by_mean || by_bald))) return ADKF_E_BADARG;
+    if (G < 1 || M < 1 || !mem || k < 0) return ADKF_E_BADARG;
+    if (M > ADKF_MIX_MEMBERS_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    const bool want_score = score || k > 0, want_ei = want_score && !by_mean && !by_bald;
+    if (want_ei && !best_f) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (k == 0 && !mean && !var && !score) return ADKF_E_BADARG;
+    const MixScratch l = mix_scratch(scratch, b->T, G, k);
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    MixArgs e{};
+    e.G = G; e.M = M; e.maximize = (flags & ADKF_PM_MAXIMIZE) ? 1 : 0;
+    e.kind = by_mean ? MIX_MEAN : by_bald ? MIX_BALD : lg ? MIX_LOG_EI : MIX_EI;
+    e.mem = mem; e.w = w;
+    e.grp = l.grp; e.m = l.m;
+    e.v = (var || (by_bald && want_score)) ? l.v : nullptr;   // stage A writes the planes that something reads
+    e.e = want_ei ? l.e : nullptr;
+    e.rows = rows; e.mean = mean; e.var = var; e.score = score;
+    e.s.excl_idx = excl_off ? excl_idx : nullptr; e.s.excl_off = excl_off;
+    e.s.k = k; e.s.chunks_max = pm_pool_chunks_max(G);
+    e.s.cand_idx = l.cand.idx; e.s.cand_val = l.cand.val;
+    e.s.top_idx = top_idx; e.s.top_val = top_val;
+    // prediction's flags: without an EI plane LOG_EI has no reader there (and prediction refuses nothing here: pm_launch checks no flag)
+    const int32_t pm_flags = flags & (ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | (want_ei ? ADKF_PM_LOG_EI : 0));
+    return c.ard ? mix_launch<true>(c, e, pm_flags, best_f, X, rows, info) : mix_launch<false>(c, e, pm_flags, best_f, X, rows, info);
 }
 
 }  // namespace

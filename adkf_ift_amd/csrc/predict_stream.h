@@ -317,12 +317,11 @@ __device__ __forceinline__ void pm_list_store(const PmPool& s, int t, int chunk,
     }
 }
 
-// one wave: the lists of task t that the walks of prediction wrote, `width` entries each, merged under the total order into (lv, li),
-// entry `lane` in each lane (a skipped task, and every task when no walk ran, has no list: -inf / -1)
-__device__ __forceinline__ void pm_merge_task_lists(const PmArgs& a, const PmPool& s, int t, int width, float& lv, long long& li) {
+// one wave: the `total` scratch entries from `base` on - whole lists of `width` entries - merged under the total order into (lv, li),
+// entry `lane` in each lane (nothing listed: -inf / -1).  pm_merge_task_lists: the lists of task t that the walks of prediction wrote
+// (a skipped task, and every task when no walk ran, has none)
+__device__ __forceinline__ void pm_merge_lists(const PmPool& s, size_t base, int total, int width, float& lv, long long& li) {
     const int lane = threadIdx.x & 63;
-    const int total = pm_task_chunks(a, s, t, true) * width;
-    const size_t base = (size_t)t * s.chunks_max * width;
     lv = -INFINITY; li = -1;
     for (int e0 = 0; e0 < total; e0 += 64) {
         const int e = e0 + lane;
@@ -331,6 +330,18 @@ __device__ __forceinline__ void pm_merge_task_lists(const PmArgs& a, const PmPoo
         const float v = in ? s.cand_val[base + e] : 0.f;
         pm_list_merge(lv, li, width, v, r, r >= 0, [](long long) { return false; });
     }
+}
+__device__ __forceinline__ void pm_merge_task_lists(const PmArgs& a, const PmPool& s, int t, int width, float& lv, long long& li) {
+    pm_merge_lists(s, (size_t)t * s.chunks_max * width, pm_task_chunks(a, s, t, true) * width, width, lv, li);
+}
+// one wave per GROUP of a call that combines tasks (k_ehvi_topk, k_mix_topk): the `lists` lists of k entries that the group's walkers
+// wrote (none without rows) merged into top_idx / top_val [G, k] (nothing listed: -1 / -inf)
+__device__ __forceinline__ void pm_group_topk(const PmPool& s, int g, int lists) {
+    const int lane = threadIdx.x & 63, k = s.k;
+    float lv;
+    long long li;
+    pm_merge_lists(s, (size_t)g * s.chunks_max * k, lists * k, k, lv, li);
+    if (lane < k) { s.top_idx[(size_t)g * k + lane] = li; s.top_val[(size_t)g * k + lane] = li >= 0 ? lv : -INFINITY; }
 }
 
 // The walk of one workgroup over a shared pool (see the top of the file): a (task, chunk, tile) cursor that only moves forward,

@@ -896,6 +896,150 @@ def ehvi_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, obj, ref, front
     return dict(score=score, top_idx=top_idx, top_val=top_val, stair=stair, stair_n=stair_n, info=info)
 
 
+_MIX_SCORES = {"ei": 0, "log_ei": _lib.PM_LOG_EI, "mean": _lib.PM_SCORE_MEAN, "bald": _lib.PM_SCORE_BALD}
+
+
+def mix_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, members, weights=None, best_f: Optional[torch.Tensor] = None,
+             score: str = "ei", latent: bool = False, maximize: bool = False, want_mean: bool = True, want_var: bool = True,
+             want_score: Optional[bool] = None, topk: int = 0, exclude=None):
+    """Hyperparameter-marginalised prediction and acquisition (the integrated acquisition of Snoek et al. 2012; BoTorch's average
+    over the MCMC batch of a fully Bayesian model) over the shared pool ``X [rows, d]`` in one ``adkf_mix_pool`` call, for isotropic
+    and ARD batches alike.  The T tasks are models of the same rows - ``replicate_batch`` makes M copies of every task, which then
+    take M samples of ``phi`` (``phi_laplace_samples``).  Group g averages its member tasks ``members[g]`` ``[G, M]`` (M at most
+    64; -1: unused) with ``weights[g]`` (default: equal; normalised by the library; a zero weight leaves the entry unused).  A task
+    may serve in several groups.  Returns ``dict(mean, var, score, top_idx, top_val, info)``: ``mean [G, rows]`` the mixture mean,
+    ``var`` its total variance (mean of the members' variances, with their noise unless ``latent``, plus the variance of their
+    means), ``score`` (``want_score``, which defaults to ``topk == 0``) and the selection by it as ``predict_pool`` returns one
+    per task.  ``score``: ``"ei"`` the integrated EI, ``"log_ei"`` its logarithm formed without EI (both need ``best_f [T]``, per
+    member task), ``"mean"`` (+mean with ``maximize``, -mean without) or ``"bald"``, the disagreement of the members
+    ``(log var - sum_i wt_i log v_i) / 2`` (Riis et al. 2022; BoTorch's ``qBayesianActiveLearningByDisagreement``): an
+    active-learning score.  A group that cannot be evaluated - an index out of range, a negative or non-finite weight, no used
+    entry, a used member that is empty or failed - is NaN and selects nothing.  A group with one member has ``predict_pool``'s bits.
+    ``exclude``: rows a GROUP may not select (``pack_exclude`` over G lists)."""
+    lib = _lib.load()
+    _support_only(b, "mix_pool")
+    if score not in _MIX_SCORES:
+        raise ValueError(f"score must be 'ei', 'log_ei', 'mean' or 'bald', got {score!r}")
+    topk = _in_range(topk, 0, _lib.POOL_TOPK_MAX, "topk")
+    if want_score is None:
+        want_score = topk == 0
+    members = _int_table(members, "members", None, None, "an integer table [G, M] of task indices (-1: unused)")
+    G = members.shape[0]
+    if G < 1:
+        raise ValueError("members must be an integer table [G, M] with at least one group")
+    M = _in_range(members.shape[1], 1, _lib.MIX_MEMBERS_MAX, "the number of members M")
+    if weights is not None:
+        weights = torch.as_tensor(weights, dtype=torch.float32) if not torch.is_tensor(weights) else weights.float()
+        if tuple(weights.shape) != (G, M):
+            raise ValueError(f"weights must be [G, M] = [{G}, {M}], got {tuple(weights.shape)}")
+    reads_ei = score in ("ei", "log_ei") and (want_score or topk > 0)
+    if best_f is not None:
+        best_f = best_f.float().reshape(-1)
+        if best_f.numel() != b.T:
+            raise ValueError(f"best_f must have T = {b.T} entries")
+    if reads_ei and best_f is None:
+        raise ValueError("the ei and log_ei scores need best_f [T]")
+    if not (want_mean or want_var or want_score or topk > 0):
+        raise ValueError("no output requested: topk == 0, want_mean, want_var and want_score are all off")
+    phi, X = _phi_and_pool(b, phi, X)
+    rows = X.shape[0]
+    dev = b.device
+    members = members.to(dev).contiguous()
+    weights = None if weights is None else weights.to(dev).contiguous()
+    best_f = None if best_f is None else _f32(best_f.to(dev), "best_f")
+    excl_idx, excl_off = _exclusion(b, exclude if topk > 0 else None, G, rows)
+    mean = _new(b, G, rows) if want_mean else None
+    var = _new(b, G, rows) if want_var else None
+    sc = _new(b, G, rows) if want_score else None
+    top_idx, top_val, info = _selection(b, G, topk)
+    flags = (_lib.PM_LATENT if latent else 0) | (_lib.PM_MAXIMIZE if maximize else 0) | _MIX_SCORES[score]
+    args = (G, ptr(members), ptr(weights), M, ptr(best_f), ptr(excl_idx), ptr(excl_off), ptr(mean), ptr(var), ptr(sc), topk, ptr(top_idx),
+            ptr(top_val))
+    _pool_call(lib, "adkf_mix_pool", b, phi, flags, X, args, info, lib.adkf_mix_pool_scratch_bytes(b.T, G, topk))
+    return dict(mean=mean, var=var, score=sc, top_idx=top_idx, top_val=top_val, info=info)
+
+
+def replicate_batch(b: GPBatch, M: int):
+    """``(bm, members)``: a support-only batch in which task t of ``b`` occupies the tasks ``t * M .. t * M + M - 1`` - the same
+    data, ``n_s``, priors, kernel and ARD flag, no reuse flags (its workspace is its own) - and ``members = arange(T * M).view(T, M)``
+    (int32, on the host), the groups of ``mix_pool`` that average a task's M replicas."""
+    M = _in_range(M, 1, _lib.MIX_MEMBERS_MAX, "the number of replicas M")
+    rep = lambda t: None if t is None else t.repeat_interleave(M, dim=0)
+    bm = GPBatch(rep(b.Z_s), rep(b.y_s), rep(b.priors), b.kernel, n_s=rep(b.n_s), ard=b.ard)
+    return bm, torch.arange(b.T * M, dtype=torch.int32).view(b.T, M)
+
+
+def laplace_draws(H, n_s, eps, max_sd: float = 2.0):
+    """The offsets ``[T, S, h]`` (float64) of Laplace draws around a MAP point: ``Q diag(lambda^-1/2) eps_s`` with
+    ``n_s[t] H[t] = Q diag(lambda) Q^T`` the precision of task t - ``H [T, h, h]`` the Hessian of the per-point objective, which
+    is symmetrised here - and ``eps [T, S, h]`` standard normal.  Eigenvalues are floored at ``1 / max_sd^2``: where the posterior
+    is flat or H is indefinite a direction has standard deviation ``max_sd``.  Pure torch; runs on CPU tensors."""
+    H = torch.as_tensor(H, dtype=torch.float64)
+    eps = torch.as_tensor(eps, dtype=torch.float64)
+    if H.dim() != 3 or H.shape[1] != H.shape[2]:
+        raise ValueError(f"H must be [T, h, h], got {tuple(H.shape)}")
+    T, h = H.shape[0], H.shape[1]
+    if eps.dim() != 3 or eps.shape[0] != T or eps.shape[2] != h:
+        raise ValueError(f"eps must be [T, S, h] = [{T}, S, {h}], got {tuple(eps.shape)}")
+    n = torch.as_tensor(n_s, dtype=torch.float64).reshape(-1)
+    if n.numel() != T:
+        raise ValueError(f"n_s must have T = {T} entries, got {n.numel()}")
+    if not max_sd > 0:
+        raise ValueError(f"max_sd must be positive, got {max_sd}")
+    P = 0.5 * (H + H.transpose(1, 2)) * n.view(T, 1, 1)
+    lam, Q = torch.linalg.eigh(P)
+    lam = lam.clamp_min(1.0 / (max_sd * max_sd))
+    return torch.einsum("tij,tsj->tsi", Q, eps * lam.rsqrt().unsqueeze(1))
+
+
+def hessian_by_differences(grad, phi, step: float):
+    """``H [T, h, h]`` (float64, symmetrised) of a batch of objectives by central differences of their exact gradient:
+    ``grad(phi [T, h]) -> [T, h]`` is called 2 h times, all tasks at once; column j is ``(grad(phi + step e_j) - grad(phi -
+    step e_j)) / (2 step)``.  Pure torch; ``phi`` keeps its dtype and device for the calls."""
+    T, h = phi.shape
+    H = torch.empty(T, h, h, dtype=torch.float64)
+    for j in range(h):
+        e = torch.zeros(h, dtype=phi.dtype, device=phi.device)
+        e[j] = step
+        # the step that was taken, not the one asked for: phi + e rounds
+        gp, gm = grad(phi + e), grad(phi - e)
+        dx = ((phi + e) - (phi - e))[:, j].double().cpu()
+        H[:, :, j] = (gp.double().cpu() - gm.double().cpu()) / dx.unsqueeze(1)
+    return 0.5 * (H + H.transpose(1, 2))
+
+
+LAPLACE_STEP = 1e-2
+
+
+def phi_laplace_samples(b: GPBatch, phi: torch.Tensor, n_samples: int, *, generator: Optional[torch.Generator] = None, eps=None,
+                        step: float = LAPLACE_STEP, max_sd: float = 2.0, keep_map: bool = True) -> torch.Tensor:
+    """``phi [T, n_samples, 3]``: draws from the Laplace approximation of the posterior over the hyperparameters around the MAP
+    point ``phi [T, 3]`` of ``fit``, for isotropic batches.  The Hessian of the per-point objective comes from central differences
+    of ``mll_value_grad``'s exact gradient (6 evaluations, all tasks at once; ``hessian_by_differences``); the objective is divided
+    by the number of points after the priors are added, so the precision is ``n_s[t] H``.  The draws are made in float64 on the
+    host (``laplace_draws``: eigenvalues floored at ``1 / max_sd^2``) from ``eps [T, n_samples, 3]``, or from ``generator``.
+    ``keep_map``: draw 0 is ``phi`` itself.
+    ``step``: on the 31 golden ``gp_*`` fixtures the differenced Hessian of the CPU twin's ``adkf_mll_value_grad`` is within
+    ``max |H_d - H| / max |H|`` = 1.2e-5, 4.4e-6, 2.7e-5, 1.1e-4, 6.8e-4 and 2.7e-3 (worst fixture) of the ``H`` of its
+    ``adkf_ift_hypergrad`` at steps 1e-3, 3e-3, 1e-2, 2e-2, 5e-2 and 1e-1.  The twin's gradient is a float64 value rounded once; the
+    device's is float32 arithmetic, whose rounding error is divided by the step, so the default is 1e-2, one notch above the twin's
+    optimum: 2.7e-5 of truncation error, far below what the eigenvalue floor and the Laplace approximation itself leave."""
+    if b.ard:
+        raise ValueError("phi_laplace_samples covers isotropic batches only: the Laplace Hessian of an ARD batch (2 + d by 2 + d per "
+                         "task, 2 (2 + d) gradient evaluations) is not built")
+    n_samples = _in_range(n_samples, 1, _lib.MIX_MEMBERS_MAX, "n_samples")
+    phi = b.check_phi(phi)
+    T = b.T
+    if eps is None:
+        eps = torch.randn(T, n_samples, 3, dtype=torch.float64, generator=generator)
+    H = hessian_by_differences(lambda p: mll_value_grad(b, p)[1], phi, step)
+    n = torch.full((T,), b.ns) if b.n_s is None else b.n_s.cpu()
+    off = laplace_draws(H, n, eps, max_sd)
+    if keep_map:
+        off[:, 0] = 0.0
+    return (phi.double().cpu().unsqueeze(1) + off).float().to(b.device)
+
+
 def gumbel_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, n_samples: Optional[int] = None, u: Optional[torch.Tensor] = None,
                 generator: Optional[torch.Generator] = None, maximize: bool = False):
     """Gumbel max-value sampling (Wang & Jegelka 2017, section 3.1; BoTorch's ``_sample_max_value_Gumbel``) over the shared pool

@@ -617,6 +617,65 @@ int adkf_jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
 size_t adkf_ehvi_pool_scratch_bytes(int32_t T, int32_t G, int32_t k);
 int adkf_ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, int32_t G, const int32_t* obj, const int32_t* obj_max, const float* ref, const float* front, const int32_t* front_n, int32_t P, const int32_t* con, const float* con_thr, const int32_t* con_geq, int32_t C, const int64_t* excl_idx, const int64_t* excl_off, float* score, float* stair, int32_t* stair_n, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Hyperparameter-marginalised prediction and acquisition over a shared pool (csrc/mix_stream.h; the integrated acquisition of Snoek,
+ * Larochelle and Adams 2012, BoTorch's average over the MCMC batch of a fully Bayesian model; Riis et al. 2022 and BoTorch's
+ * qBayesianActiveLearningByDisagreement for ADKF_PM_SCORE_BALD).  It replaces a adkf_predict_pool call for mean, var and ei [T, rows]
+ * on M replicas of every task, combined and selected on the host.  The T tasks of the batch are MODELS of the SAME pool rows
+ * X [rows, d] - usually the same data under M samples of phi; a GROUP g names up to ADKF_MIX_MEMBERS_MAX member tasks mem[g, 0..M)
+ * (a task may serve in several groups; a task repeated inside a group counts each time) with weights w[g, 0..M) (NULL: all 1), and
+ * every pool row gets one mean, variance and score per group.
+ *   Used entries.  An entry is USED when mem != -1 and its weight is > 0 (the weight of an entry with mem == -1 is not read).  The
+ *          used entries are compacted in entry order into the slots 0 .. n - 1; W is the float32 sum of their weights in that
+ *          order and wt_i = w_i / W.
+ *   The quantities.  m_i, v_i, e_i: adkf_predict_pool's mean, var and ei of member i at the row under the caller's flags - var with
+ *          the member's own noise unless ADKF_PM_LATENT, ei on the latent variance with best_f[t_i] in the ADKF_PM_MAXIMIZE sense,
+ *          log EI with ADKF_PM_LOG_EI.
+ *              mean  = sum_i wt_i m_i
+ *              var   = sum_i wt_i v_i + sum_i wt_i (m_i - mean)^2     (total variance; the second term from the deviations, not
+ *                                                                      as E[m^2] - mean^2)
+ *              score = sum_i wt_i e_i                                 (default: the integrated EI)
+ *                    = log sum_i wt_i exp(le_i)                       (ADKF_PM_LOG_EI: its logarithm, as mx + log sum_i wt_i
+ *                                                                      exp(le_i - mx), mx = max_i le_i, in a fixed order; EI is
+ *                                                                      never formed, -inf terms are skipped, all -inf gives -inf)
+ *                    = +mean with ADKF_PM_MAXIMIZE, -mean without     (ADKF_PM_SCORE_MEAN)
+ *                    = (log var_c - sum_i wt_i log vc_i) / 2          (ADKF_PM_SCORE_BALD: vc_i = max(v_i, 1e-12), var_c the
+ *                                                                      variance above from the vc_i; not clamped at 0, it may round
+ *                                                                      a few ulp of the logarithms below 0)
+ *          Every sum is taken over four interleaved partials (slots p, p + 4, ..) that start from -0 and are joined in the order
+ *          0, 1, 2, 3.  ANCHORS: a group with one used member, and a group of two used entries that name the same task with equal
+ *          weights, have on every row the bits of adkf_predict_pool's mean, var and ei (log EI) of that task under the same flags,
+ *          and its selection; their BALD score is exactly 0.  A group's bits depend on the ORDER of its members, by rounding only.
+ *          A group cannot be evaluated when an index is outside [0, T) other than -1, a weight of an entry with mem != -1 is
+ *          negative, NaN or infinite, no entry is used, the weights do not sum to a finite number, or a used member has n_s == 0 or
+ *          info != 0: mean, var and score of the group are NaN on every row and it selects nothing (top_idx -1, top_val -inf); the
+ *          other groups keep their bits.  A pool row whose members are NaN is NaN, and never selected.
+ *   b      support-only, of either kind, as for adkf_mes_pool; REUSE_DIST / REUSE_INNER and info [T] as for adkf_predict_pool.  Every
+ *          task of the batch is predicted, whether a group names it or not.
+ *   flags  ADKF_PM_LATENT, ADKF_PM_MAXIMIZE, and at most one of ADKF_PM_SCORE_MEAN, ADKF_PM_LOG_EI, ADKF_PM_SCORE_BALD.
+ *   G, mem, w, M   G >= 1 groups; mem [G, M] (int32), w [G, M] nullable, 1 <= M <= ADKF_MIX_MEMBERS_MAX.
+ *   best_f [T], per member task: needed when the EI or log-EI score is read (score != NULL or k > 0).
+ *   excl_idx, excl_off   as for adkf_predict_pool, but per GROUP: excl_off is [G + 1].
+ *   mean, var, score   each nullable, [G, rows].
+ *   k, top_idx, top_val   the selection of adkf_predict_pool on the score, per group: [G, k], k <= ADKF_POOL_TOPK_MAX, its
+ *          eligibility, its unique order (score, then row index), its -1 / -inf tail; a NaN score is never selected.
+ *   scratch   adkf_mix_pool_scratch_bytes(T, G, k) bytes, 8-byte aligned and a multiple of 8: three planes [T, ADKF_MIX_CHUNK_ROWS]
+ *          (the pool is walked in such chunks, each through prediction's own launch, so m, v and e are adkf_predict_pool's bit for
+ *          bit), the groups' state and the candidate lists.  It depends on neither rows, ns_max, d nor M; the size function returns
+ *          0 for T < 1, G < 1, k < 0 or k > ADKF_POOL_TOPK_MAX.
+ * Asynchronous on `stream`, no allocation, no synchronisation, no atomics: reproducible to the bit, and a group's result depends on
+ * its own members, weights, best_f, exclusion list and the pool row only - not on the grid, on the other groups of the call or on
+ * where the chunk boundaries fall.
+ * Rejected before anything is launched, ADKF_E_BADARG unless noted: G < 1; M < 1; mem == NULL; k < 0; M > ADKF_MIX_MEMBERS_MAX or
+ * k > ADKF_POOL_TOPK_MAX (ADKF_E_SIZE); a flag bit other than the five above; ADKF_PM_SCORE_MEAN with ADKF_PM_SCORE_BALD;
+ * ADKF_PM_LOG_EI with either; the EI or log-EI score read without best_f; k > 0 without top_idx or top_val; no output at all (k == 0
+ * and mean, var and score all NULL); a batch with a query set; rows < 0; rows > 0 without X; excl_idx without excl_off; a scratch
+ * or a workspace that is too small (ADKF_E_WORKSPACE); a scratch that is not 8-byte aligned. */
+#define ADKF_PM_SCORE_BALD 32      /* adkf_mix_pool only: rank by the disagreement of the members */
+#define ADKF_MIX_MEMBERS_MAX 64
+#define ADKF_MIX_CHUNK_ROWS 16384  /* a multiple of 64: 192 KB of scratch per task */
+size_t adkf_mix_pool_scratch_bytes(int32_t T, int32_t G, int32_t k);
+int adkf_mix_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, int32_t G, const int32_t* mem, const float* w, int32_t M, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, float* mean, float* var, float* score, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,
