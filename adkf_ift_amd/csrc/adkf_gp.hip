@@ -23,6 +23,7 @@
 #include "gemm_x3.h"
 #include "dense_x3.h"
 #include "dist_task.h"
+#include "dz_task.h"
 #include "predict_stream.h"
 #include "thompson_stream.h"
 #include "believer_stream.h"
@@ -159,7 +160,7 @@ int adkf_mll_value_grad(const adkf_batch_t* b, const float* phi, float* f_in, fl
         k_win<<<grid_for(b->T, win_tiles), 256, 0, st>>>(wa);
         hipMemsetAsync(dZ_s, 0, (size_t)b->T * b->ns_max * b->d * sizeof(float), st);
         ProbDZ<false> pz; pz.tv = tv; pz.Wss = w.Wss; pz.Wqs = nullptr; pz.Wqq = nullptr; pz.Zs = b->Z_s; pz.Zq = nullptr; pz.dZ = dZ_s; pz.d = b->d;
-        launch_gemm(pz, b->T, b->ns_max, b->d, st, x3_for(b->d));
+        launch_gemm(pz, b->T, b->ns_max, b->d, st);   // (support only: the FP32 form, host_common.h)
         LAUNCH_OK();
     }
     return 0;

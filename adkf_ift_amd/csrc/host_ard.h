@@ -67,7 +67,7 @@ void ard_dz_support(ArdCtx& c, const float* W, float* out, const int32_t* n_over
     TaskView tv = make_tv(&c.bt, c.w, false);
     if (n_override) tv.n_s = n_override;
     ProbDZ<false> pz; pz.tv = tv; pz.Wss = W; pz.Wqs = nullptr; pz.Wqq = nullptr; pz.Zs = c.a.Zt_s; pz.Zq = nullptr; pz.dZ = out; pz.d = c.d;
-    launch_gemm(pz, c.T, c.ns, c.d, c.st, x3_for(c.d));
+    launch_gemm(pz, c.T, c.ns, c.d, c.st);   // (support only: the FP32 form, host_common.h)
 }
 
 // The inner quantities at x [T, h]: l, Zt_s, D2ss, Ainv, alpha and the scalars in the workspace (the first half of

@@ -37,10 +37,13 @@ int num_cus() {
 
 // Which problems run on the BF16 matrix pipe (gemm_x3.h: FP32 products out of three-way split operands).
 template <class P> struct use_x3 : std::false_type {};
-// (ProbDZ ran on it as well - every parity test green, MN-contiguous staging with a column per lane - at the same time as on the FP32
-// pipe, 62.5 + 54.4 against 61 + 56.5 us at C2: it is bound by its strided W_qs^T operand and the staging, not by the matrix pipe; left
-// on the FP32 form.)
 template <> struct use_x3<ProbDistMulti> : std::true_type {};
+// ProbDZ: as tiled launches the split form takes the same time as the FP32 form (62.5 + 54.4 against 61 + 56.5 us at C2: 64 x 64 tiles
+// wait for their operands, not for the matrix pipe).  It is on this list for its arithmetic: full batches of 128 + 128 points run
+// k_dz_task (dz_task.h), which writes what k_bgemm3<ProbDZ> writes, and every other batch of that padded size (ragged, misaligned,
+// other d, one cotangent only) has to round as they do.  The caller asks for it by a rule of ProbDZ's own (host_gp.h::outer_pipeline);
+// the support-only call sites never do.
+template <bool QUERY> struct use_x3<ProbDZ<QUERY>> : std::true_type {};
 // (The N^3 products of the multi-launch outer stage beyond 128 points - ProbP, ProbC, ProbS, ProbOC, ProbMA, ProbMixed - were tried on
 // it as well: the same 1.99 ms for the eleven products of a C5 step, profiles/r05_c5_x3_kernel_stats.csv - at 64 x 64 tiles and
 // K = 1024 they wait for their operands, 6.9 TB/s out of L2 / MALL, not for the matrix pipe.)

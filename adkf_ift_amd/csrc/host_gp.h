@@ -398,6 +398,16 @@ int inner_stage(const adkf_batch_t* b, const Workspace& w, const float* phi, int
     return 0;
 }
 
+// dL/dZ of a full batch in one launch (dz_task.h: one workgroup per task, bit-identical to the two tiled launches on the BF16 pipe):
+// use_dist_task's conditions on the shape - ns_max == nq_max == 128, no n_s and no n_q, d a multiple of the K chunk, 16-byte loads legal,
+// the LDS opt-in granted - with both cotangents requested in 16-byte aligned rows, and no ADKF_BATCH_DZ_TILED.
+bool dz_task_ok(const adkf_batch_t* b, const Workspace& w, const float* dZ_s, const float* dZ_q) {
+    static const bool optin = lds_optin(DT_LDS_BYTES, {kernel_ptr(&k_dz_task)});
+    // (d <= 2^22: a lane offset of 100 d bytes fits 32 bits)
+    return optin && dZ_s && dZ_q && !(b->flags & ADKF_BATCH_DZ_TILED) && b->ns_max == DT_N && b->nq_max == DT_N && !b->n_s && !b->n_q &&
+           (b->d % GK) == 0 && b->d <= (1 << 22) && vec_ok(b, w) && aligned16(dZ_s) && aligned16(dZ_q);
+}
+
 // Stage D..G shared by adkf_outer_nll_value_grad (with_hessian = false) and adkf_ift_hypergrad.
 int outer_pipeline(const adkf_batch_t* b, const Workspace& w, const float* phi, int flags, bool with_hessian, float* f_out,
                    float* dZ_s, float* dZ_q, float* g_phi_out, float* v_out, float* H_out, int32_t* info, hipStream_t st) {
@@ -472,11 +482,18 @@ int outer_pipeline(const adkf_batch_t* b, const Workspace& w, const float* phi, 
         if (dZ_q && b->n_q) hipMemsetAsync(dZ_q, 0, (size_t)T * nq * d * sizeof(float), st);
         ProbDZ<false> pzs; pzs.tv = tv; pzs.Wss = w.Wss; pzs.Wqs = w.Wqs; pzs.Wqq = w.Wqq; pzs.Zs = b->Z_s; pzs.Zq = b->Z_q; pzs.dZ = dZ_s; pzs.d = d;
         ProbDZ<true> pzq; pzq.tv = tv; pzq.Wss = w.Wss; pzq.Wqs = w.Wqs; pzq.Wqq = w.Wqq; pzq.Zs = b->Z_s; pzq.Zq = b->Z_q; pzq.dZ = dZ_q; pzq.d = d;
-        // (both cotangents in ONE launch through gemm.h's select() hook, with the two functors behind a run-time switch, was
-        // measured at 139.8 us against 62.6 + 56.4 for the two launches: dropped; so was one workgroup per task with both operands in
-        // LDS, k_dz in tools/variants/dz.h at 4c3bc9b: 135 us inside the step)
-        if (dZ_s) launch_gemm(pzs, T, ns, d, st, x3_for(d));
-        if (dZ_q) launch_gemm(pzq, T, nq, d, st, x3_for(d));
+        // Full batches: one launch, one workgroup per task (dz_task.h).  Measured at C2 (profiles/dz_task_bench.json: six alternating
+        // runs per library on one box): the step 0.8664 -> 0.8195 ms, ranges 8.4 and 5.9 us.  Earlier forms, measured and dropped: both
+        // cotangents in ONE tiled launch behind a run-time switch, 139.8 us against 62.6 + 56.4 for the two launches; one workgroup per
+        // task on the FP32 pipe with both operands in LDS and no pipeline (k_dz in tools/variants/dz.h at 4c3bc9b), 135 us.
+        if (dz_task_ok(b, w, dZ_s, dZ_q)) {
+            k_dz_task<<<grid_for(T, 1), DT_NT, DT_LDS_BYTES, st>>>(DzTaskArgs{w.Wss, w.Wqs, w.Wqq, b->Z_s, b->Z_q, dZ_s, dZ_q, d, T});
+        } else {
+            // the split form by a rule of this product's own: its contraction runs over the points, not over d
+            const bool x3 = ns == DT_N && nq == DT_N;
+            if (dZ_s) launch_gemm(pzs, T, ns, d, st, x3);
+            if (dZ_q) launch_gemm(pzq, T, nq, d, st, x3);
+        }
     }
     if (w.w64) {
         // flagged (ill-conditioned) tasks, ONE launch at the very end: the factorisation-type stages (A^-1, alpha, P, the Hessian, C,

@@ -70,6 +70,8 @@ extern "C" {
                                     (k_lg_diag, panel, update: csrc/large.h) instead of the update of step k and the diagonal sweep of
                                     step k + 1 in one launch (csrc/large_fused.h).  Both give bit-identical results. */
 #define ADKF_BATCH_LG_FUSED 32   /* ... and the fused form whatever the size (without either flag: fused from 512 points on, where it is faster) */
+#define ADKF_BATCH_DZ_TILED 64   /* A/B runs and tests: dL/dZ by the tiled launches whatever the shape (without it a full batch of 128 support
+                                    and 128 query points takes one launch, csrc/dz_task.h).  Both give bit-identical results. */
 
 /* ARD kernel (``use_ard``: fs_mol/models/adaptive_dkt.py:107-108 -> gpytorch ``ard_num_dims``): one lengthscale per
  * feature dimension.  With this flag EVERY phi / g_phi / v argument has h = 2 + d entries per task, laid out
