@@ -21,6 +21,7 @@ PM_SCORE_MEAN = 4  # adkf_predict_pool: rank by the posterior mean instead of ei
 PM_LOG_EI = 16    # ... ei, and the ei score of adkf_predict_pool, hold log EI (8 is not a flag)
 POOL_TOPK_MAX = 64
 KG_REFS_MAX = 64         # adkf_kg_pool: reference rows per task
+IPV_ENTRIES_MAX = 64     # adkf_ipv_pool: targets plus picks per task
 EHVI_FRONT_MAX = 64      # adkf_ehvi_pool: front points per group
 EHVI_CONS_MAX = 4        # ... constraint tasks per group
 EHVI_CHUNK_ROWS = 16384  # ... pool rows per chunk of its walk
@@ -109,6 +110,10 @@ SIGNATURES = {
     "adkf_jes_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                 C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adkf_ipv_pool_scratch_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "adkf_ipv_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_ehvi_pool_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
     "adkf_ehvi_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,

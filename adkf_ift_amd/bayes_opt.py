@@ -18,6 +18,8 @@ minima of pathwise posterior draws over the whole pool) and one ``adkf_mes_pool`
 for the reference rows and one ``adkf_kg_pool`` call (log KG) per iteration; it prices the observation noise and needs no ``best_f``.
 ``run_gp_jes_bo_batched`` is the loop under joint entropy search: one batched fit, one ``gp_ops.optimum_samples`` call (the minima of
 pathwise posterior draws over the whole pool, location and value) and one ``adkf_jes_pool`` call per iteration.
+``run_gp_ipv_al_batched`` is not an optimisation loop but the active-learning one: one batched fit and one ``adkf_ipv_pool`` call per
+round, which returns the batch of rows whose labels lower the posterior variance at given target rows the most.
 
 Only the Matern-5/2 branch exists here (the Tanimoto kernel of the reference's fingerprint baseline is not a
 distance-based kernel and is out of the library's scope).
@@ -480,6 +482,56 @@ def run_gp_kg_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
         top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
         usable = torch.isfinite(top_val) & (top_idx >= 0)   # (a prefix of each row: descending scores, the -1 / -inf tail last)
         _take_picks(top_idx, usable, query_batch_size, rngs, queried, records, n)
+    return records
+
+
+@torch.no_grad()
+def run_gp_ipv_al_batched(x_all: torch.Tensor, y_all: torch.Tensor, target_idx, num_init_points: int, query_batch_size: int,
+                          num_rounds: int, kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
+                          rngs: List[np.random.Generator], ard: bool = False, exclude_targets: bool = True) -> List[List[int]]:
+    """``len(rngs)`` replicates of a transductive active-learning loop over the same pool at once: which rows to label so that the
+    predictions at the rows ``target_idx`` (pool indices, shared by the replicates) get as good as possible.  Returns their records:
+    the rows each replicate labelled, in the order it chose them.  Per round the replicates' labelled sets are fitted by ONE
+    ``gp_ops.fit`` (as ``run_gp_ei_bo_batched``) and ONE ``gp_ops.ipv_pool(q=query_batch_size, exclude=labelled)`` call returns each
+    replicate's greedy batch: every pick lowers the posterior variance at the targets the most given the picks before it, and no
+    label is needed inside a batch.  ``exclude_targets``: the targets cannot be measured - they are excluded, and a target drawn
+    into an initial design is exchanged for a random free row.  ``query_batch_size`` plus the number of targets is at most 64.  A
+    returned candidate counts when its index is not -1 and its score is finite; a shortfall is filled with random free rows from the
+    replicate's generator, as in ``run_gp_mes_bo_batched``.  Nothing random enters the score."""
+    n = x_all.shape[0]
+    targets = torch.as_tensor(target_idx).reshape(-1)
+    if targets.is_floating_point() or targets.numel() < 1 or int(targets.min()) < 0 or int(targets.max()) >= n:
+        raise ValueError(f"target_idx must hold at least one integer pool index in [0, {n})")
+    tgt = sorted(set(int(i) for i in targets.tolist()))
+    M, cap = len(tgt), gp_ops._lib.IPV_ENTRIES_MAX
+    if M >= cap:
+        raise ValueError(f"at most {cap - 1} distinct targets, got {M}")
+    if not 1 <= query_batch_size <= cap - M:
+        raise ValueError(f"query_batch_size must be in [1, {cap - M}] with {M} targets, got {query_batch_size}")
+    if num_rounds < 0:
+        raise ValueError(f"num_rounds must not be negative, got {num_rounds}")
+    y_all, X, labelled = _bo_start(x_all, y_all, num_init_points, init_from, rngs)
+    if exclude_targets:
+        for r, rng in enumerate(rngs):
+            hit = [i for i in labelled[r] if i in tgt]
+            if hit:
+                free = [i for i in range(init_from, n) if i not in tgt and i not in labelled[r]]
+                labelled[r] = [i for i in labelled[r] if i not in tgt] + rng.choice(free, size=len(hit), replace=False).tolist()
+    # what a replicate may not pick: its labelled rows and, with exclude_targets, the targets.  _take_picks adds each round's picks
+    # to blocked[r] itself (it is the loop's `queried`), which is what keeps a later round from choosing them again
+    blocked = [rows_r + tgt if exclude_targets else list(rows_r) for rows_r in labelled]
+    records = [[] for _ in rngs]
+
+    for _ in range(num_rounds):
+        b, phi = _fit_tasks("run_gp_ipv_al_batched", x_all, [(rows_r, y_all) for rows_r in labelled], X, kernel_type, device,
+                            noise_init, noise_prior, ard)
+        out = gp_ops.ipv_pool(b, phi, X, targets=[tgt] * len(rngs), q=query_batch_size, exclude=blocked)
+        gp_ops.check_info(out["info"], "AL posterior")
+        sel_idx, sel_val = out["sel_idx"].cpu(), out["sel_val"].cpu()
+        usable = torch.isfinite(sel_val) & (sel_idx >= 0)   # (a prefix of each row: the -1 / -inf tail comes last)
+        _take_picks(sel_idx, usable, query_batch_size, rngs, blocked, records, n)
+        for r in range(len(rngs)):
+            labelled[r] = labelled[r] + records[r][-query_batch_size:]
     return records
 
 

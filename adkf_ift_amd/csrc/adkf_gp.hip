@@ -32,6 +32,7 @@
 #include "gibbon_stream.h"
 #include "kg_stream.h"
 #include "jes_stream.h"
+#include "ipv_stream.h"
 #include "ehvi_stream.h"
 #include "mix_stream.h"
 
@@ -329,6 +330,18 @@ int adkf_jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
                   void* scratch, size_t scratch_bytes, void* stream) {
     return jes_pool(b, phi, flags, X, rows, opt_idx, opt_val, S, cond_noise, excl_idx, excl_off, score, opt_mean, opt_var, k, top_idx, top_val,
                     info, ws, ws_bytes, scratch, scratch_bytes, stream);
+}
+
+size_t adkf_ipv_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t M, int32_t q) {
+    if (T <= 0 || ns_max <= 0 || ns_max > MAX_POINTS || d <= 0 || M < 1 || q < 1 || (int64_t)M + q > ADKF_IPV_ENTRIES_MAX) return 0;
+    return ipv_scratch(nullptr, T, ns_max, d, M, q).bytes;
+}
+
+int adkf_ipv_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* tgt_idx,
+                  const float* tgt_w, int32_t M, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx,
+                  float* sel_val, float* tvar, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    return ipv_pool(b, phi, flags, X, rows, tgt_idx, tgt_w, M, excl_idx, excl_off, q, trace, sel_idx, sel_val, tvar, info, ws, ws_bytes, scratch,
+                    scratch_bytes, stream);
 }
 
 size_t adkf_ehvi_pool_scratch_bytes(int32_t T, int32_t G, int32_t k) {

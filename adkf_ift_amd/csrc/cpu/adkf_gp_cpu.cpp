@@ -1253,6 +1253,127 @@ int adkf_kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const f
     return 0;
 }
 
+size_t adkf_ipv_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t, int32_t) { return 0; }
+
+// Target-variance batch selection over a shared pool (include/adkf_gp.h): the latent variance and K A^-1 of every pool row once, the
+// covariance of every row with every valid target from them, then per step the scores in float64, rounded to float32 at the
+// boundary and ranked under "larger score first, equal scores by ascending row", and one more column of ell for every row (the
+// believer's substitution, one row of G at a time); the targets' ell are the rows' own, read at the targets' indices.  ARD: pm_task
+// prepares the support set and the pool rows on z~ = (z - mu) / l, and the distances between pool rows are taken on x / l.
+int adkf_ipv_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* tgt_idx, const float* tgt_w,
+                  int32_t M, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
+                  float* tvar, int32_t* info, void*, size_t, void*, size_t, void*) {
+    if (int rc = check(b, false, true)) return rc;
+    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (flags) return ADKF_E_BADARG;
+    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (!tgt_idx || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (M < 1 || q < 1) return ADKF_E_BADARG;
+    if ((int64_t)M + q > ADKF_IPV_ENTRIES_MAX) return ADKF_E_SIZE;
+    const bool ard = (b->flags & ADKF_BATCH_ARD) != 0;
+    const int d = b->d;
+    const float ninf = -std::numeric_limits<float>::infinity();
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        for (int j = 0; j < q; ++j) { sel_idx[(size_t)t * q + j] = -1; sel_val[(size_t)t * q + j] = ninf; }
+        if (tvar) std::fill(tvar + (size_t)t * (q + 1), tvar + (size_t)(t + 1) * (q + 1), 0.f);
+        if (trace && rows > 0) std::fill(trace + (size_t)t * q * rows, trace + (size_t)(t + 1) * q * rows, 0.f);
+        const int n = std::min(ns_of(b, t), b->ns_max);
+        const size_t R = (size_t)rows;
+        Mat Kr(R * std::max(n, 0)), Cr(R * std::max(n, 0)), v(R), L(R * q);
+        double s = 0.0, noise = 0.0, il2 = 0.0;
+        const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
+            s = in.s; noise = in.noise; il2 = 1.0 / (in.l * in.l);
+            double* k = &Kr[(size_t)r * n];
+            double* c = &Cr[(size_t)r * n];
+            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); k[j] = in.s * k0; }
+            double qf = 0.0;
+            for (int j = 0; j < n; ++j) {
+                double cj = 0.0;
+                for (int i = 0; i < n; ++i) cj += k[i] * in.Ainv[(size_t)i * n + j];
+                c[j] = cj;
+                qf += cj * k[j];
+            }
+            v[r] = in.s - qf;
+        });
+        if (!done) continue;
+        Mat Xl(ard ? R * d : 0);   // ARD: the pool rows over l
+        if (ard) {
+            const float* x0 = phi + (size_t)t * (2 + d);
+            for (size_t r = 0; r < R; ++r) for (int c = 0; c < d; ++c) Xl[r * d + c] = (double)X[r * d + c] / softplus(x0[2 + c]);
+        }
+        // c0(x_r, x_p) for every row r
+        auto c0_col = [&](int64_t p, double* out) {
+            const Mat Dp = ard ? sqdist(Xl.data() + (size_t)p * d, 1, Xl.data(), (int)rows, d) : sqdist(X + (size_t)p * d, 1, X, (int)rows, d);
+            for (size_t r = 0; r < R; ++r) {
+                double k0, k1, k2;
+                kappa(b->kernel, Dp[r] * il2, k0, k1, k2);
+                double c0 = s * k0;
+                for (int i = 0; i < n; ++i) c0 -= Kr[r * n + i] * Cr[(size_t)p * n + i];
+                out[r] = c0;
+            }
+        };
+        // the valid targets: inside the pool, first occurrences, a weight > 0; Ct: cov_j(x_r, target), downdated with the rows
+        std::vector<int64_t> tg;
+        std::vector<double> wt;
+        for (int m = 0; m < M; ++m) {
+            const int64_t p = tgt_idx[(size_t)t * M + m];
+            const float w = tgt_w ? tgt_w[(size_t)t * M + m] : 1.f;
+            if (p < 0 || p >= rows || !(w > 0.f)) continue;
+            bool first = true;
+            for (int i = 0; i < m && first; ++i) first = tgt_idx[(size_t)t * M + i] != p;
+            if (first) { tg.push_back(p); wt.push_back(w); }
+        }
+        const size_t nt = tg.size();
+        if (nt == 0) continue;
+        Mat Ct(nt * R);
+        for (size_t m = 0; m < nt; ++m) c0_col(tg[m], &Ct[m * R]);
+        auto total = [&] { double x = 0.0; for (size_t m = 0; m < nt; ++m) x += wt[m] * v[tg[m]]; return x; };
+        if (tvar) tvar[(size_t)t * (q + 1)] = (float)total();
+        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
+        std::vector<char> taken(R, 0);
+        std::vector<float> score(R);
+        Mat G((size_t)q * q, 0.0), col(R);
+        int c = 0;   // picks made
+        for (int j = 0; j < q; ++j) {
+            int64_t p = -1;
+            for (int64_t r = 0; r < rows; ++r) {
+                double sum = 0.0;
+                for (size_t m = 0; m < nt; ++m) sum += wt[m] * Ct[m * R + r] * Ct[m * R + r];
+                score[r] = (float)(sum / (std::max(v[r], 1e-12) + noise));
+                if (trace) trace[((size_t)t * q + j) * R + r] = score[r];
+                if (score[r] != score[r] || taken[r] || (xb && std::binary_search(xb, xe, r))) continue;
+                if (p < 0 || score[r] > score[p]) p = r;   // (rows ascend: a tie keeps the lower index)
+            }
+            if (p < 0) {   // no eligible row: this step and all later ones keep -1 / -inf, the state stays
+                if (tvar) tvar[(size_t)t * (q + 1) + j + 1] = (float)total();
+                continue;
+            }
+            sel_idx[(size_t)t * q + j] = p; sel_val[(size_t)t * q + j] = score[p];
+            // the new row of G, then column c of ell and the downdates for every row (the picked one and the targets included)
+            for (int l = 0; l < c; ++l) G[(size_t)c * q + l] = L[(size_t)p * q + l];
+            G[(size_t)c * q + c] = std::sqrt(v[p] + noise);
+            c0_col(p, col.data());
+            for (size_t r = 0; r < R; ++r) {
+                double c0 = col[r];
+                for (int l = 0; l < c; ++l) c0 -= G[(size_t)c * q + l] * L[r * q + l];
+                L[r * q + c] = c0 / G[(size_t)c * q + c];
+            }
+            for (size_t m = 0; m < nt; ++m) {
+                const double em = L[(size_t)tg[m] * q + c];
+                for (size_t r = 0; r < R; ++r) Ct[m * R + r] -= L[r * q + c] * em;
+            }
+            for (size_t r = 0; r < R; ++r) v[r] -= L[r * q + c] * L[r * q + c];
+            taken[p] = 1;
+            ++c;
+            if (tvar) tvar[(size_t)t * (q + 1) + j + 1] = (float)total();
+        }
+    }
+    return 0;
+}
+
 size_t adkf_jes_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t, int32_t) { return 0; }
 
 // Joint entropy search over a shared pool (include/adkf_gp.h): the mean, the latent variance and K A^-1 of every pool row once, the

@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ehvi_pool and adkf_mix_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ipv_pool, adkf_ehvi_pool and adkf_mix_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
 // pool calls share (pool_walks, pool_select, pool_greedy) and the body of every entry.
 #pragma once
 #include "host_ard.h"
@@ -676,6 +676,82 @@ int jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float
     if (score && rows > 0) hipMemsetAsync(score, 0, sizeof(float) * (size_t)rows * b->T, c.st);
     return c.ard ? pool_select<true, JesEpilogue>(c, pa, pool, v, k_jes_walk64<true>, have64, k_jes_refs<true>, S)
                  : pool_select<false, JesEpilogue>(c, pa, pool, v, k_jes_walk64<false>, have64, k_jes_refs<false>, S);
+}
+
+// adkf_ipv_pool: the scratch is the entry state - w [T, M + q, ns] (and its float64 twin where a workspace of this shape can have a
+// float64 region) and the entries' feature rows [T, M + q, d], targets first - then G [T, q, q] and Lr [T, q, M] (and their twins),
+// the targets' effective weights and step-0 variances [T, M], tvar, the pick count and the number of valid targets per task, and one
+// (row, score) pair per (task, chunk).  It does not depend on rows.
+struct IpvScratch { RefHead h; float *G, *Lr, *wt; double *G64, *Lr64, *v0r, *tv; int32_t *cnt, *nv; CandLists cand; size_t bytes; };
+inline IpvScratch ipv_scratch(void* base, int T, int ns, int d, int M, int q) {
+    Arena ar{static_cast<char*>(base), 0};
+    const size_t g = (size_t)T * q * q, lr = (size_t)T * q * M;
+    const bool twin = ns <= R64_MAXN;
+    IpvScratch l{};
+    l.h = carve_ref_head(ar, T, M + q, ns, d);
+    l.G = ar.floats(g);
+    l.G64 = ar.as<double>(twin ? g : 0);
+    l.Lr = ar.floats(lr);
+    l.Lr64 = ar.as<double>(twin ? lr : 0);
+    l.wt = ar.floats((size_t)T * M);
+    l.v0r = ar.as<double>((size_t)T * M);
+    l.tv = ar.as<double>((size_t)T);
+    l.cnt = ar.as<int32_t>((size_t)T);
+    l.nv = ar.as<int32_t>((size_t)T);
+    l.cand = carve_cand(ar, (size_t)T * pm_pool_chunks_max(T));
+    l.bytes = ar.off;
+    return l;
+}
+
+// The launches of a prepared adkf_ipv_pool call: (ARD) the 1 / l pass, the target state, then q chained steps, each the walks with
+// IpvEpilogue and one workgroup per task (pool_greedy's shape with this entry's own step kernel)
+template <bool ARD>
+int ipv_launch(const PmCtx& c, PmArgs& pa, PmPool& pool, IpvArgs& v, bool have64) {
+    const int T = c.b.T;
+    if constexpr (ARD) launch_ard_il(c);
+    k_ipv_refs<ARD><<<dim3(v.M, T), 256, 0, c.st>>>(pm_kargs<ARD, true, IpvEpilogue>(c, pa, &pool, v));
+    k_ipv_init<<<ceil_div(T, 256), 256, 0, c.st>>>(v, T);
+    pool.grid[2] = pool_grid64(pool, pa.rows, have64);
+    for (int j = 0; j < v.q; ++j) {
+        v.j = j;
+        const int rc = pool_walks<ARD, IpvEpilogue>(c, pa, pool, v, k_ipv_walk64<ARD>);
+        if (rc) return rc;
+        k_ipv_step<ARD><<<T, 256, 0, c.st>>>(pm_kargs<ARD, true, IpvEpilogue>(c, pa, &pool, v));
+    }
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_ipv_pool: isotropic and ARD batches alike (as adkf_kg_pool)
+int ipv_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* tgt_idx, const float* tgt_w,
+             int32_t M, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* tvar,
+             int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
+    if (!tgt_idx || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (M < 1 || q < 1) return ADKF_E_BADARG;
+    if ((int64_t)M + q > ADKF_IPV_ENTRIES_MAX) return ADKF_E_SIZE;
+    const IpvScratch l = ipv_scratch(scratch, b->T, b->ns_max, b->d, M, q);
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    hipStream_t st = c.st;
+    const int T = b->T;
+    PmArgs pa = pm_args(c, flags, X, rows, info);
+    const bool have64 = pm_have64(c, pa);
+    PmPool pool = pm_pool(excl_idx, excl_off, 1, T, l.cand.idx, l.cand.val, rows, st);
+    IpvArgs v{};
+    v.M = M; v.q = q; v.tgt_idx = tgt_idx; v.tgt_w = tgt_w;
+    v.W = l.h.W; v.W64 = have64 ? l.h.W64 : nullptr; v.Xp = l.h.Xp;
+    v.G = l.G; v.G64 = have64 ? l.G64 : nullptr; v.Lr = l.Lr; v.Lr64 = have64 ? l.Lr64 : nullptr;
+    v.wt = l.wt; v.v0r = l.v0r; v.tv = l.tv; v.cnt = l.cnt; v.nv = l.nv;
+    v.trace = trace; v.sel_idx = sel_idx; v.sel_val = sel_val; v.tvar = tvar;
+    // skipped tasks keep zeros in trace
+    if (trace && rows > 0) hipMemsetAsync(trace, 0, sizeof(float) * (size_t)T * q * (size_t)rows, st);
+    return c.ard ? ipv_launch<true>(c, pa, pool, v, have64) : ipv_launch<false>(c, pa, pool, v, have64);
 }
 
 // adkf_gumbel_pool: the scratch is the fixed-point sums [T, 64] (uint64), the probes [T, 64] (float32) and the images of the two

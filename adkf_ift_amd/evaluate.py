@@ -204,6 +204,34 @@ def screen(model, mb: MetaBatch, X_features: torch.Tensor, k: int, maximize: boo
     return out["top_idx"], out["top_val"], phi
 
 
+def select_support(model, mb: MetaBatch, X_features: torch.Tensor, targets, q: int, exclude=None, max_evals: int = 200):
+    """Which rows to label next: every task of ``mb`` is fitted on its support set, then chooses ``q`` rows of the SAME library
+    ``X_features [rows, d]`` (rows in the model's feature space) whose labels would lower the posterior variance at its target rows
+    ``targets [T, M]`` (library indices; ``M + q`` at most 64) the most, in one ``gp_ops.ipv_pool`` call - ``screen``'s twin for the
+    question "what should I measure" instead of "what is best".  Returns (sel_idx [T, q] int64, sel_val [T, q], tvar [T, q + 1],
+    phi*): the picks in pick order, what each took off the summed target variance, and that variance before and after each pick.
+    ``exclude``: rows a task may not choose (``gp_ops.pack_exclude``) - the targets themselves, if they cannot be measured."""
+    from . import gp_ops
+
+    cfg = model.config
+    was_training = model.training
+    model.eval()
+    Z_s, _ = meta_features(model, mb)
+    y_s, _ = mb.labels(cfg.use_numeric_labels)
+    priors = torch.empty(mb.num_tasks, 4, dtype=torch.float32, device=Z_s.device)
+    b = gp_ops.GPBatch(Z_s.float().contiguous(), y_s.to(Z_s.device).float().contiguous(), priors, cfg.gp_kernel, n_s=mb.n_s, ard=cfg.use_ard)
+    phi0, _ = gp_ops.init_params_batch(b, cfg.use_numeric_labels, cfg.use_lengthscale_prior)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.DEFER_REFINE
+    phi, _, _, _, info = gp_ops.fit(b, phi0, max_evals)
+    gp_ops.check_info(info, "support selection inner fit")
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    out = gp_ops.ipv_pool(b, phi, X_features, targets=targets, q=q, exclude=exclude)
+    gp_ops.check_info(out["info"], "support selection")
+    if was_training:
+        model.train()
+    return out["sel_idx"], out["sel_val"], out["tvar"], phi
+
+
 def evaluate_tasks(model, tasks: Sequence[DKTBatch], names: Optional[Sequence[str]] = None, tasks_per_call: int = 64,
                    max_evals: int = 200, streaming: bool = False) -> Dict[str, object]:
     """``evaluate_adkt_model`` for tasks that are already in memory: per-task metric records, ``tasks_per_call`` tasks

@@ -707,6 +707,45 @@ def kg_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, ref_idx: Optional
     return dict(score=score, cov=cov, ref_mean=ref_mean, ref_idx=ref_idx, top_idx=top_idx, top_val=top_val, info=info)
 
 
+def ipv_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, targets, weights: Optional[torch.Tensor] = None, q: int, exclude=None,
+             want_trace: bool = False, want_tvar: bool = True):
+    """Target-variance batch selection (ALC, Cohn 1996; BoTorch's ``qNegIntegratedPosteriorVariance``; transductive active learning)
+    per task from the shared pool ``X [rows, d]`` in one ``adkf_ipv_pool`` call, for isotropic and ARD batches alike: ``q``
+    sequential-greedy picks, each the row whose noisy observation lowers the weighted latent posterior variance at the task's target
+    rows the most, given the picks before it.  No label is needed, so the whole batch is chosen before anything is measured.
+    ``targets [T, M]``: integer pool indices (a tensor or nested lists; ``M + q`` at most 64); ``weights [T, M]``: their weights
+    (None: 1).  An entry outside ``[0, rows)``, one whose index an earlier entry of its task has, and one whose weight is ``<= 0``
+    or NaN are skipped.  The targets themselves ARE eligible - observing a target is the best single pick; put them in ``exclude``
+    if they cannot be measured.  Returns ``dict(sel_idx, sel_val, tvar, trace, info)``: ``sel_idx [T, q]`` (int64) the picks in
+    pick order and ``sel_val`` the amount each took off the target variance, -1 / -inf from the step at which no eligible row was
+    left (and at every step of a task without a valid target); ``tvar [T, q + 1]`` (``want_tvar``, else None) the weighted target
+    variance before the first pick and after each; ``trace [T, q, rows]`` (``want_trace``, else None) the score of every row at
+    every step; ``info [T]``.  ``exclude``: rows a task may not select (``pack_exclude``).  A target row with non-finite features
+    makes every score of its task NaN: nothing is selected."""
+    lib = _lib.load()
+    _support_only(b, "ipv_pool")
+    q = _in_range(q, 1, _lib.IPV_ENTRIES_MAX - 1, "q")
+    M = _int_table(targets, "targets", b.T, None, f"an integer table [T, M] = [{b.T}, M]").shape[1]   # (the check; the indices stay int64)
+    _in_range(M, 1, _lib.IPV_ENTRIES_MAX - q, f"the number of target entries M (M + q at most {_lib.IPV_ENTRIES_MAX})")
+    if weights is not None:
+        weights = torch.as_tensor(weights)
+        if tuple(weights.shape) != (b.T, M):
+            raise ValueError(f"weights must be [T, M] = [{b.T}, {M}], got {tuple(weights.shape)}")
+    phi, X = _phi_and_pool(b, phi, X)
+    rows = X.shape[0]
+    _on_device(b, X=X)
+    if weights is not None:
+        weights = weights.to(device=b.device, dtype=torch.float32).contiguous()
+    targets = torch.as_tensor(targets).to(device=b.device, dtype=torch.int64).contiguous()
+    excl_idx, excl_off = _exclusion(b, exclude, b.T, rows)
+    sel_idx, sel_val, info = _selection(b, b.T, q)
+    tvar = _new(b, b.T, q + 1) if want_tvar else None
+    trace = _new(b, b.T, q, rows) if want_trace else None
+    args = (ptr(targets), ptr(weights), M, ptr(excl_idx), ptr(excl_off), q, ptr(trace), ptr(sel_idx), ptr(sel_val), ptr(tvar))
+    _pool_call(lib, "adkf_ipv_pool", b, phi, 0, X, args, info, lib.adkf_ipv_pool_scratch_bytes(b.T, b.ns, b.d, M, q))
+    return dict(sel_idx=sel_idx, sel_val=sel_val, tvar=tvar, trace=trace, info=info)
+
+
 def max_value_samples(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: torch.Tensor, phase: torch.Tensor, n_samples: int,
                       generator: Optional[torch.Generator] = None, w: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
                       maximize: bool = False):

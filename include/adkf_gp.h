@@ -563,6 +563,53 @@ int adkf_kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const f
 size_t adkf_jes_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t S, int32_t k);
 int adkf_jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* opt_idx, const float* opt_val, int32_t S, float cond_noise, const int64_t* excl_idx, const int64_t* excl_off, float* score, float* opt_mean, float* opt_var, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Target-variance batch selection over a shared pool (csrc/ipv_stream.h; Cohn 1996, "ALC"; Gramacy and Apley 2015; BoTorch's
+ * qNegIntegratedPosteriorVariance with the targets as its mc_points; Huebotter et al. 2024, "VTL"): transductive active learning.
+ * Per task, q rows of the SAME pool X [rows, d] are chosen, one after the other, so that noisy observations there lower the weighted
+ * posterior variance at the task's TARGET rows as far as possible.  The posterior variance of a GP does not depend on the labels,
+ * so the whole batch is chosen before anything is measured, and y_s enters only through the fit that gave phi.
+ *   The quantity.  v_0, cov_0(., .) the latent posterior of adkf_predict_pool, noise the task's, r_m = pool row tgt_idx[t, m] the
+ *          targets with weights wt_m = tgt_w[t, m] (tgt_w == NULL: 1), p_0 .. p_(j-1) the picks so far, w_e = A^-1 k(Z_s, x_e):
+ *              c0(x, e)     = k(x, x_e) - k(x, Z_s) . w_e                  e a target or a pick
+ *              G G^T        = [c0(x_(p_i), p_l)]_(i,l<j) + noise I         adkf_believer_pool's G
+ *              ell(x)       = G^-1 c0(x, picks)
+ *              v_j(x)       = v_0(x) - sum_(i<j) ell_i(x)^2
+ *              cov_j(x,r_m) = c0(x, r_m) - sum_(i<j) ell_i(x) ell_i(r_m)
+ *              score_j(x)   = sum_m wt_m cov_j(x, r_m)^2 / (max(v_j(x), 1e-12) + noise)      >= 0
+ *              tvar_j       = sum_m wt_m v_j(r_m)
+ *          score_j(x) is exactly what one noisy observation at x takes off tvar_j: tvar_j - tvar_(j+1) = score_j(p_j).  p_j is the
+ *          eligible row of largest score_j under adkf_predict_pool's total order (score, then ascending row); a row is eligible
+ *          unless it is in the task's exclusion list, is an earlier pick, or scores NaN.
+ *          A target entry is skipped if it lies outside [0, rows), if an earlier entry of the task's list has the same index (by
+ *          index alone, as adkf_kg_pool: the first occurrence is the one looked at), or if its weight is <= 0 or NaN.
+ *          THE TARGETS ARE ELIGIBLE unless the caller excludes them: observing a target is the best single pick.  A caller who cannot
+ *          measure the targets lists them in excl_idx.
+ *   b      support-only, of either kind, as for adkf_kg_pool; REUSE_DIST / REUSE_INNER and info as for adkf_predict_pool.
+ *   flags  0.
+ *   tgt_idx   [T, M] pool row indices; tgt_w nullable, [T, M].  M >= 1, q >= 1 and M + q <= ADKF_IPV_ENTRIES_MAX: targets and picks
+ *          share one 64-column covariance panel per row tile.  A form with two panels is not built.
+ *   trace  nullable, [T, q, rows]: score_j of every row at every step (as adkf_believer_pool's).
+ *   sel_idx, sel_val   [T, q], required: the picks in pick order and their scores at the step they were picked.  With no eligible
+ *          row at step j, that step and all later ones report -1 / -inf and the state stops changing.
+ *   tvar   nullable, [T, q + 1]: tvar_0 .. tvar_q (a step without a pick repeats the value before it).
+ *   Tasks with n_s == 0, info != 0 or no valid target entry: -1 / -inf at every step, zero slices of tvar and trace.
+ *   Non-finite data.  A target row with NaN or infinite features makes its own w and covariances NaN, and with them every score of
+ *          the task: nothing is selected.  Keep such rows out of tgt_idx.  A pool row whose own mean or variance is NaN scores NaN
+ *          and is never selected.
+ *   scratch   adkf_ipv_pool_scratch_bytes(T, ns_max, d, M, q) bytes, 8-byte aligned: w and the stored row of every entry [T, M + q,
+ *          ns_max] and [T, M + q, d] (w with a float64 copy where the workspace has a float64 region), G [T, q, q] and ell(r_m) [T, q,
+ *          M] with their copies, per-target and per-task scalars, and one candidate pair per (task, chunk).  A function of (T, ns_max,
+ *          d, M, q) only.
+ * Asynchronous on `stream` and capturable, no allocation, no synchronisation, no atomics, every sum in a fixed order: reproducible to
+ * the bit, and a task's result depends on that task's data, its targets, the pool and its exclusion list only - not on the grid or on
+ * the other tasks of the batch.  Rejected before anything is launched, ADKF_E_BADARG unless noted: M < 1; q < 1;
+ * M + q > ADKF_IPV_ENTRIES_MAX (ADKF_E_SIZE); tgt_idx, sel_idx, sel_val, info or ws NULL; a batch with a query set; any flag bit;
+ * rows < 0; rows > 0 without X; excl_idx without excl_off; a scratch or a workspace that is too small (ADKF_E_WORKSPACE); a scratch
+ * that is not 8-byte aligned. */
+#define ADKF_IPV_ENTRIES_MAX 64      /* M + q */
+size_t adkf_ipv_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t M, int32_t q);
+int adkf_ipv_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* tgt_idx, const float* tgt_w, int32_t M, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* tvar, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Constrained expected hypervolume improvement ACROSS tasks over a shared pool (csrc/ehvi_stream.h; Emmerich, Deutz and Klinkenberg
  * 2011 and Yang et al. 2019 for the exact two-objective form, BoTorch's analytic ExpectedHypervolumeImprovement; Schonlau 1998 and
  * Gardner et al. 2014 for the feasibility weight, BoTorch's ConstrainedExpectedImprovement; ADKF_PM_LOG_EI: their log forms).  It

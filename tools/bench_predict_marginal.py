@@ -64,6 +64,11 @@ alternately in this process (median of --reps single calls each) with adkf_kg_po
 reference panel followed by the envelope where JES makes S evaluations - with adkf_mes_pool(k = 8) on the same values - the same S
 evaluations without the panel - and with adkf_predict_pool(k = 8, log EI, nothing per row).  The line holds the times, the ratios, each
 series' spread (max - min) / median, the scratch bytes and the bit-equality of a repeated call.  No target.
+--ipv: target-variance batch selection (adkf_ipv_pool, q = 16, no trace) at T=64 ns=128 d=64, 100 000 rows, Matern, REUSE_INNER, with
+M = 16 and M = 48 random target rows per task, timed alternately in this process (median of --reps single calls each) with
+adkf_believer_pool(q = 16, log EI): the same sixteen walks, whose panel has j columns at step j where this entry's has M + j, without
+the j M multiply-adds a row.  The line holds the three times, the ratios, each series' spread (max - min) / median, the scratch
+bytes and the bit-equality of a repeated call.  No target.
 --ehvi: constrained EHVI across tasks (adkf_ehvi_pool, k = 8, nothing per row) on --mes's batch and pool: 8 two-objective groups
 (2 g, 2 g + 1) with mixed senses, fronts of P points drawn around the support labels, in log form at P = 16 and P = 64, in linear form
 at P = 16, and at P = 16 with C = 2 constraint tasks - random fronts, which clean down to a handful of steps - and on an anti-chain of
@@ -72,7 +77,7 @@ with C = 2, timed alternately in this process (median of --reps single calls eac
 adkf_predict_pool(latent, mean and var, no selection) - what its stage A runs per chunk - and adkf_predict_pool(k = 8, log EI,
 nothing per row).  The line holds the times, the ratios, the share of stage A, each series' spread, the scratch bytes, the staircase
 sizes and the bit-equality of a repeated call.  No target.
-Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--mes] [--gibbon] [--gumbel] [--kg] [--jes] [--ehvi] [--out FILE]"""
+Usage: python tools/bench_predict_marginal.py [--reps 5] [--skip-meta-test] [--ard] [--skip-large] [--pool] [--skip-bo] [--thompson [--ard]] [--believer [--ard]] [--mes] [--gibbon] [--gumbel] [--kg] [--jes] [--ipv] [--ehvi] [--out FILE]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -558,6 +563,58 @@ def shape_kg(T, ns, d, rows, k, Ms, reps, dev, out_path=None):
     return rec
 
 
+def shape_ipv(T, ns, d, rows, q, Ms, reps, dev, out_path=None):
+    g = torch.Generator(device=dev).manual_seed(0)
+    W = torch.randn(d, d, device=dev, generator=g) / d ** 0.5
+    Zs = torch.randn(T, ns, d, device=dev, generator=g) @ W
+    ys = torch.sin(Zs[..., :4].sum(-1))
+    b = gp_ops.GPBatch(Zs, ys, torch.empty(T, 4, device=dev), "matern")
+    phi0, _ = gp_ops.init_params_batch(b, True, True)
+    b.flags = gp_ops.REUSE_DIST
+    phi, _, _, _, info = gp_ops.fit(b, phi0, 200)
+    gp_ops.check_info(info)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    X = torch.empty(rows, d, device=dev)
+    for lo in range(0, rows, 1 << 16):
+        X[lo:lo + (1 << 16)] = torch.randn(min(1 << 16, rows - lo), d, device=dev, generator=g) @ W
+    best = ys.median(1).values.contiguous()
+    tg = {M: torch.stack([torch.randperm(rows, device=dev, generator=g)[:M] for _ in range(T)]) for M in Ms}
+    f_bv = lambda: gp_ops.believer_pool(b, phi, X, best_f=best, q=q, log_ei=True)
+    f_ipv = {M: (lambda M=M: gp_ops.ipv_pool(b, phi, X, targets=tg[M], q=q)) for M in Ms}
+    o1 = {M: f_ipv[M]() for M in Ms}
+    o2 = {M: f_ipv[M]() for M in Ms}
+    f_bv()
+    torch.cuda.synchronize()
+    for M in Ms:
+        gp_ops.check_info(o1[M]["info"])
+    ts = {"believer_log_ei": [], **{f"ipv_M{M}": [] for M in Ms}}
+    for _ in range(reps):
+        ts["believer_log_ei"].append(once(f_bv))
+        for M in Ms:
+            ts[f"ipv_M{M}"].append(once(f_ipv[M]))
+    med = {n: float(np.median(x)) for n, x in ts.items()}
+    lib = _lib.load()
+    rec = {"shape": f"ipv T={T} ns={ns} d={d} rows={rows} q={q} matern REUSE_INNER trace=NULL; believer q={q} log EI",
+           "refined_tasks": int(_refined(b).sum()), "float64_tasks": int((_scal(b)[:, 45] > 30.0).sum()),
+           "workspace_bytes": int(lib.adkf_workspace_bytes(T, ns, 0, d)),
+           "scratch_bytes": {str(M): int(lib.adkf_ipv_pool_scratch_bytes(T, ns, d, M, q)) for M in Ms},
+           "believer_log_ei_s": med["believer_log_ei"],
+           "ipv_s": {str(M): med[f"ipv_M{M}"] for M in Ms},
+           "ipv_over_believer": {str(M): med[f"ipv_M{M}"] / med["believer_log_ei"] for M in Ms},
+           "spread_max_minus_min_over_median": {n: (max(x) - min(x)) / float(np.median(x)) for n, x in ts.items()},
+           "repeat_is_bit_equal": bool(all(torch.equal(o1[M]["sel_idx"], o2[M]["sel_idx"]) and
+                                           torch.equal(o1[M]["sel_val"].view(torch.int32), o2[M]["sel_val"].view(torch.int32)) and
+                                           torch.equal(o1[M]["tvar"].view(torch.int32), o2[M]["tvar"].view(torch.int32)) for M in Ms)),
+           "all_selected": bool(all((o1[M]["sel_idx"] >= 0).all() and torch.isfinite(o1[M]["sel_val"]).all() for M in Ms)),
+           "all_s": ts}
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+    return rec
+
+
 def shape_ehvi(T, ns, d, rows, k, reps, dev, out_path=None):
     """T / 2 two-objective groups (2 g, 2 g + 1) with mixed senses, fronts from the support labels padded with jittered copies."""
     g = torch.Generator(device=dev).manual_seed(0)
@@ -875,8 +932,9 @@ def main():
     ap.add_argument("--gumbel", action="store_true", help="adkf_gumbel_pool against adkf_predict_pool(k, log EI) and max_value_samples(S = 16, m = 1024), timed alternately")
     ap.add_argument("--kg", action="store_true", help="adkf_kg_pool(log KG, k = 8) at M = 32 and 64 against adkf_predict_pool(k, log EI) and adkf_believer_pool(q = 8, log EI), timed alternately")
     ap.add_argument("--jes", action="store_true", help="adkf_jes_pool(k = 8) at S = 16 and 64 against adkf_kg_pool(log KG, k = 8) at M = S, adkf_mes_pool(k = 8) and adkf_predict_pool(k, log EI), timed alternately")
+    ap.add_argument("--ipv", action="store_true", help="adkf_ipv_pool(q = 16) at M = 16 and 48 targets against adkf_believer_pool(q = 16, log EI) at T = 64, ns = 128, d = 64, 100 000 rows, timed alternately")
     ap.add_argument("--ehvi", action="store_true", help="adkf_ehvi_pool(k = 8) over 8 two-objective groups - log form at P = 16 and 64, linear at P = 16, P = 16 with C = 2, and a 64-step anti-chain staircase (log, linear, log with C = 2) - against adkf_predict_pool(latent mean and var) and adkf_predict_pool(k, log EI), timed alternately")
-    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard), --mes, --gibbon, --gumbel, --kg, --jes, --ehvi: also write the JSON line to this file")
+    ap.add_argument("--out", default=None, help="--thompson, --believer (each with or without --ard), --mes, --gibbon, --gumbel, --kg, --jes, --ipv, --ehvi: also write the JSON line to this file")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.mes:
@@ -887,6 +945,9 @@ def main():
         return
     if a.jes:
         shape_jes(16, 128, 256, 100000, 8, (16, 64), 1024, a.reps, dev, a.out)
+        return
+    if a.ipv:
+        shape_ipv(64, 128, 64, 100000, 16, (16, 48), a.reps, dev, a.out)
         return
     if a.ehvi:
         shape_ehvi(16, 128, 256, 100000, 8, a.reps, dev, a.out)
