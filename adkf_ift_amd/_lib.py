@@ -27,6 +27,9 @@ EHVI_CONS_MAX = 4        # ... constraint tasks per group
 EHVI_CHUNK_ROWS = 16384  # ... pool rows per chunk of its walk
 PM_SCORE_BALD = 32       # adkf_mix_pool: rank by the disagreement of the members
 MIX_MEMBERS_MAX = 64     # ... member tasks per group
+PM_JK_SCALED = 64        # adkf_jackknife_pool: fold widths scaled by the leave-one-out predictive deviation
+JK_POINTS_MAX = 256      # ... support points per task
+JK_LEVELS_MAX = 8        # ... levels per call
 MIX_CHUNK_ROWS = 16384   # ... pool rows per chunk of its walk
 TS_SAMPLES_MAX = 64      # adkf_thompson_pool: posterior draws per task
 TS_FEATURES_MAX = 4096   # ... random Fourier features (a multiple of 64, at least 64)
@@ -114,6 +117,10 @@ SIGNATURES = {
     "adkf_ipv_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                 C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adkf_jackknife_pool_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "adkf_jackknife_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_ehvi_pool_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
     "adkf_ehvi_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,

@@ -33,6 +33,7 @@
 #include "kg_stream.h"
 #include "jes_stream.h"
 #include "ipv_stream.h"
+#include "jackknife_stream.h"
 #include "ehvi_stream.h"
 #include "mix_stream.h"
 
@@ -342,6 +343,19 @@ int adkf_ipv_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
                   float* sel_val, float* tvar, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
     return ipv_pool(b, phi, flags, X, rows, tgt_idx, tgt_w, M, excl_idx, excl_off, q, trace, sel_idx, sel_val, tvar, info, ws, ws_bytes, scratch,
                     scratch_bytes, stream);
+}
+
+size_t adkf_jackknife_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t L, int32_t k) {
+    if (T <= 0 || ns_max <= 0 || ns_max > ADKF_JK_POINTS_MAX || L < 1 || L > ADKF_JK_LEVELS_MAX || k < 0 || k > ADKF_POOL_TOPK_MAX) return 0;
+    return jk_scratch(nullptr, T, ns_max, k).bytes;
+}
+
+int adkf_jackknife_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* alpha, int32_t L,
+                        const int64_t* excl_idx, const int64_t* excl_off, float* lo, float* hi, float* loo_mean, float* loo_var, float* loo_lpd,
+                        int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch,
+                        size_t scratch_bytes, void* stream) {
+    return jackknife_pool(b, phi, flags, X, rows, alpha, L, excl_idx, excl_off, lo, hi, loo_mean, loo_var, loo_lpd, k, top_idx, top_val, info, ws,
+                          ws_bytes, scratch, scratch_bytes, stream);
 }
 
 size_t adkf_ehvi_pool_scratch_bytes(int32_t T, int32_t G, int32_t k) {

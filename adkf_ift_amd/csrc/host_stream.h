@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ipv_pool, adkf_ehvi_pool and adkf_mix_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ipv_pool, adkf_jackknife_pool, adkf_ehvi_pool and adkf_mix_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
 // pool calls share (pool_walks, pool_select, pool_greedy) and the body of every entry.
 #pragma once
 #include "host_ard.h"
@@ -208,15 +208,16 @@ template <bool ARD, class EPI>
 using PoolKernel = void (*)(PmArgsOf<ARD, true, EPI>);
 
 // The walks of a pool call over the whole pool with the epilogue EPI (arguments v): the plain tasks, the refined ones and, where
-// the caller has given the float64 walk a grid (pool.grid[2] > 0), the flagged ones with walk64.  No rows: nothing.
-template <bool ARD, class EPI>
+// the caller has given the float64 walk a grid (pool.grid[2] > 0), the flagged ones with walk64.  No rows: nothing.  EPI_LDS: the
+// static LDS of the epilogue itself (pm_launch_walk; JkEpilogue's row tile C - every other epilogue works in the staging buffers).
+template <bool ARD, class EPI, int EPI_LDS = 0>
 int pool_walks(const PmCtx& c, PmArgs& pa, PmPool& pool, const typename EPI::Args& v, PoolKernel<ARD, EPI> walk64 = nullptr) {
     if (pa.rows <= 0) return 0;
     const int T = c.b.T;
     const int64_t tiles = ((pa.rows + PM_TM - 1) / PM_TM) * T;
     int rc;
-    if ((rc = pm_launch_walk<false, ARD, true, EPI>(c, pa, &pool, v, tiles))) return rc;
-    if ((rc = pm_launch_walk<true, ARD, true, EPI>(c, pa, &pool, v, tiles))) return rc;
+    if ((rc = pm_launch_walk<false, ARD, true, EPI, EPI_LDS>(c, pa, &pool, v, tiles))) return rc;
+    if ((rc = pm_launch_walk<true, ARD, true, EPI, EPI_LDS>(c, pa, &pool, v, tiles))) return rc;
     if (pool.grid[2] > 0) walk64<<<dim3(pool.grid[2], T), PM64_NT, 0, c.st>>>(pm_kargs<ARD, true, EPI>(c, pa, &pool, v));
     return 0;
 }
@@ -228,15 +229,15 @@ inline int pool_grid64(const PmPool& pool, int64_t rows, bool run64) {
 
 // "Score, then select" - adkf_predict_pool, adkf_mes_pool, adkf_kg_pool, adkf_jes_pool: (ARD) the 1 / l pass, the reference state
 // where the call has one (refs: n_refs workgroups per task, with or without rows), the walks and the merge of the lists.  The caller
-// has zeroed its outputs.
-template <bool ARD, class EPI>
+// has zeroed its outputs.  EPI_LDS: the static LDS of the epilogue itself (pm_launch_walk).
+template <bool ARD, class EPI, int EPI_LDS = 0>
 int pool_select(const PmCtx& c, PmArgs& pa, PmPool& pool, const typename EPI::Args& v, PoolKernel<ARD, EPI> walk64, bool run64,
                 PoolKernel<ARD, EPI> refs = nullptr, int n_refs = 0) {
     const int T = c.b.T;
     if constexpr (ARD) launch_ard_il(c);
     if (refs) refs<<<dim3(n_refs, T), 256, 0, c.st>>>(pm_kargs<ARD, true, EPI>(c, pa, &pool, v));
     pool.grid[2] = pool_grid64(pool, pa.rows, run64);
-    const int rc = pool_walks<ARD, EPI>(c, pa, pool, v, walk64);
+    const int rc = pool_walks<ARD, EPI, EPI_LDS>(c, pa, pool, v, walk64);
     if (rc) return rc;
     if (pool.k > 0) k_pool_topk<<<T, 64, 0, c.st>>>(pm_kargs<false, true>(c, pa, &pool));
     LAUNCH_OK();
@@ -752,6 +753,61 @@ int ipv_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float
     // skipped tasks keep zeros in trace
     if (trace && rows > 0) hipMemsetAsync(trace, 0, sizeof(float) * (size_t)T * q * (size_t)rows, st);
     return c.ard ? ipv_launch<true>(c, pa, pool, v, have64) : ipv_launch<false>(c, pa, pool, v, have64);
+}
+
+// adkf_jackknife_pool: the scratch is the leave-one-out state - g, 1 / B_ii and the width factor [T, ns] each, with float64 twins
+// (ns <= ADKF_JK_POINTS_MAX, so a workspace of this shape can always have a float64 region), the ranks [T, ADKF_JK_LEVELS_MAX] - and
+// prediction's candidate lists [T, chunks_max, k].  It does not depend on rows (nor on L).
+struct JkScratch { float *g, *rv, *wd; double *g64, *rv64, *wd64; int32_t* rank; CandLists cand; size_t bytes; };
+inline JkScratch jk_scratch(void* base, int T, int ns, int k) {
+    Arena ar{static_cast<char*>(base), 0};
+    const size_t e = (size_t)T * ns;
+    JkScratch l{};
+    l.g = ar.floats(e); l.rv = ar.floats(e); l.wd = ar.floats(e);
+    l.g64 = ar.as<double>(e); l.rv64 = ar.as<double>(e); l.wd64 = ar.as<double>(e);
+    l.rank = ar.as<int32_t>((size_t)T * JK_LV_MAX);
+    l.cand = carve_cand(ar, (size_t)T * pm_pool_chunks_max(T) * k);
+    l.bytes = ar.off;
+    return l;
+}
+
+// adkf_jackknife_pool: isotropic and ARD batches alike (as adkf_kg_pool); rows == 0 is the plain leave-one-out diagnostic
+int jackknife_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* alpha, int32_t L,
+                   const int64_t* excl_idx, const int64_t* excl_off, float* lo, float* hi, float* loo_mean, float* loo_var, float* loo_lpd,
+                   int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes,
+                   void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags & ~(ADKF_PM_MAXIMIZE | ADKF_PM_JK_SCALED)) return ADKF_E_BADARG;
+    if (!alpha) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
+    if (k == 0 && !lo && !hi && !loo_mean && !loo_var && !loo_lpd) return ADKF_E_BADARG;
+    if ((rc = check_topk(k, top_idx, top_val))) return rc;
+    if (b->ns_max > ADKF_JK_POINTS_MAX || L < 1 || L > ADKF_JK_LEVELS_MAX) return ADKF_E_SIZE;
+    const JkScratch l = jk_scratch(scratch, b->T, b->ns_max, k);
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    hipStream_t st = c.st;
+    const size_t T = (size_t)b->T, ns = (size_t)b->ns_max;
+    PmPool pool = pm_pool(excl_idx, excl_off, k, b->T, l.cand.idx, l.cand.val, rows, st);
+    pool.top_idx = top_idx; pool.top_val = top_val;
+    PmArgs pa = pm_args(c, flags & ADKF_PM_MAXIMIZE, X, rows, info);
+    const bool have64 = pm_have64(c, pa);
+    JkArgs v{};
+    v.L = L; v.scaled = (flags & ADKF_PM_JK_SCALED) ? 1 : 0; v.alpha = alpha;
+    v.g = l.g; v.rv = l.rv; v.wd = l.wd; v.rank = l.rank;
+    if (have64) { v.g64 = l.g64; v.rv64 = l.rv64; v.wd64 = l.wd64; }
+    v.lo = lo; v.hi = hi; v.loo_mean = loo_mean; v.loo_var = loo_var; v.loo_lpd = loo_lpd;
+    // every output starts at 0: the slots beyond n_s and everything of skipped tasks (n_s == 0, info != 0) stay so
+    if (lo && rows > 0) hipMemsetAsync(lo, 0, sizeof(float) * T * L * (size_t)rows, st);
+    if (hi && rows > 0) hipMemsetAsync(hi, 0, sizeof(float) * T * L * (size_t)rows, st);
+    if (loo_mean) hipMemsetAsync(loo_mean, 0, sizeof(float) * T * ns, st);
+    if (loo_var) hipMemsetAsync(loo_var, 0, sizeof(float) * T * ns, st);
+    if (loo_lpd) hipMemsetAsync(loo_lpd, 0, sizeof(float) * T, st);
+    return c.ard ? pool_select<true, JkEpilogue, JK_EPI_LDS>(c, pa, pool, v, k_jk_walk64<true>, have64, k_jk_state<true>, 1)
+                 : pool_select<false, JkEpilogue, JK_EPI_LDS>(c, pa, pool, v, k_jk_walk64<false>, have64, k_jk_state<false>, 1);
 }
 
 // adkf_gumbel_pool: the scratch is the fixed-point sums [T, 64] (uint64), the probes [T, 64] (float32) and the images of the two

@@ -232,6 +232,61 @@ def select_support(model, mb: MetaBatch, X_features: torch.Tensor, targets, q: i
     return out["sel_idx"], out["sel_val"], out["tvar"], phi
 
 
+def _fitted_support(model, mb: MetaBatch, max_evals: int, what: str):
+    """The support-only batch of ``mb`` on the model's features, fitted as ``screen`` fits it: (b, phi*), b set to reuse the fit."""
+    from . import gp_ops
+
+    cfg = model.config
+    Z_s, _ = meta_features(model, mb)
+    y_s, _ = mb.labels(cfg.use_numeric_labels)
+    priors = torch.empty(mb.num_tasks, 4, dtype=torch.float32, device=Z_s.device)
+    b = gp_ops.GPBatch(Z_s.float().contiguous(), y_s.to(Z_s.device).float().contiguous(), priors, cfg.gp_kernel, n_s=mb.n_s, ard=cfg.use_ard)
+    phi0, _ = gp_ops.init_params_batch(b, cfg.use_numeric_labels, cfg.use_lengthscale_prior)
+    b.flags = gp_ops.REUSE_DIST | gp_ops.DEFER_REFINE
+    phi, _, _, _, info = gp_ops.fit(b, phi0, max_evals)
+    gp_ops.check_info(info, f"{what} inner fit")
+    b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
+    return b, phi
+
+
+def predict_intervals(model, mb: MetaBatch, X_features: torch.Tensor, alpha=0.1, scaled: bool = True, k: int = 0, maximize: bool = True,
+                      max_evals: int = 200):
+    """How far the predictions can be trusted: every task of ``mb`` is fitted on its support set, then gives every row of the SAME
+    library ``X_features [rows, d]`` (rows in the model's feature space) a jackknife+ prediction interval in one
+    ``gp_ops.jackknife_pool`` call - distribution-free, coverage at least ``1 - 2 alpha``, no label held out (at most 256 support
+    points per task).  ``alpha``: one level or up to 8.  The hyperparameters are those of the one fit, NOT refitted per fold, so
+    the coverage is a very good approximation rather than a theorem.  Returns (lo [T, L, rows], hi [T, L, rows], top_idx [T, k],
+    top_val [T, k], phi*): the selection ranks the rows by the bound one can rely on at the first level (``lo`` with ``maximize``,
+    ``-hi`` without); None, None with ``k == 0``."""
+    from . import gp_ops
+
+    was_training = model.training
+    model.eval()
+    b, phi = _fitted_support(model, mb, max_evals, "interval")
+    levels = (alpha,) if isinstance(alpha, (int, float)) else alpha
+    out = gp_ops.jackknife_pool(b, phi, X_features, alpha=levels, scaled=scaled, maximize=maximize, topk=k, want_loo=False)
+    gp_ops.check_info(out["info"], "interval prediction")
+    if was_training:
+        model.train()
+    return out["lo"], out["hi"], out["top_idx"], out["top_val"], phi
+
+
+def loo_check(model, mb: MetaBatch, max_evals: int = 200):
+    """Leave-one-out cross-validation of every task of ``mb`` at its fitted hyperparameters (not refitted per fold), at no extra
+    factorisation: (loo_mean [T, ns], loo_var [T, ns], loo_lpd [T], phi*) - each support point's prediction and observed variance
+    from the other points, and the summed log predictive density, a calibration check that needs no validation set."""
+    from . import gp_ops
+
+    was_training = model.training
+    model.eval()
+    b, phi = _fitted_support(model, mb, max_evals, "leave-one-out")
+    out = gp_ops.loo(b, phi)
+    gp_ops.check_info(out["info"], "leave-one-out check")
+    if was_training:
+        model.train()
+    return out["loo_mean"], out["loo_var"], out["loo_lpd"], phi
+
+
 def evaluate_tasks(model, tasks: Sequence[DKTBatch], names: Optional[Sequence[str]] = None, tasks_per_call: int = 64,
                    max_evals: int = 200, streaming: bool = False) -> Dict[str, object]:
     """``evaluate_adkt_model`` for tasks that are already in memory: per-task metric records, ``tasks_per_call`` tasks

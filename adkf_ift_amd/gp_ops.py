@@ -746,6 +746,56 @@ def ipv_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, targets, weights
     return dict(sel_idx=sel_idx, sel_val=sel_val, tvar=tvar, trace=trace, info=info)
 
 
+def jackknife_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, alpha=(0.1,), scaled: bool = False, maximize: bool = False,
+                   topk: int = 0, exclude=None, want_lo: bool = True, want_hi: bool = True, want_loo: bool = True):
+    """Leave-one-out checks (Rasmussen & Williams, section 5.4.2) and jackknife+ prediction intervals (Barber, Candes, Ramdas &
+    Tibshirani 2021) for every row of the shared pool ``X [rows, d]`` in one ``adkf_jackknife_pool`` call, for isotropic and ARD
+    batches alike (at most 256 support points per task).  Everything is at the ``phi`` passed - the hyperparameters are NOT refitted
+    per fold - and costs no extra factorisation: deleting point i is a rank-one update of the posterior.  ``alpha``: up to 8 levels
+    (floats, or a float32 tensor; rounded to float32, whose bits set the ranks); ``[lo[t, l], hi[t, l]]`` covers a new label with
+    probability at least ``1 - 2 alpha[l]`` whatever the data's distribution, for the fixed-``phi`` predictor (with ``phi`` fitted on
+    the same points: a very good approximation, not a theorem).  ``scaled``: fold widths scaled by the leave-one-out predictive
+    deviation at the row, so intervals widen away from the data.  Returns ``dict(lo, hi, loo_mean, loo_var, loo_lpd, top_idx,
+    top_val, info)``: ``lo`` / ``hi [T, L, rows]`` (``want_lo`` / ``want_hi``, else None; -inf / +inf where the task has too few
+    points for the level, ``floor(alpha (n + 1)) == 0``), ``loo_mean`` / ``loo_var [T, ns]`` the leave-one-out predictive mean and
+    observed variance of every support point and ``loo_lpd [T]`` their summed log predictive density (``want_loo``, else None),
+    ``top_idx [T, topk]`` / ``top_val`` as ``predict_pool`` returns them on the level-0 score - ``lo`` with ``maximize``, ``-hi``
+    without: screening by the bound one can rely on; rows without a finite bound are never selected - and ``info [T]``.
+    ``exclude``: rows a task may not select (``pack_exclude``).  With ``want_lo = want_hi = False`` nothing of size T x rows is
+    allocated or written."""
+    lib = _lib.load()
+    _support_only(b, "jackknife_pool")
+    topk = _in_range(topk, 0, _lib.POOL_TOPK_MAX, "topk")
+    _in_range(b.ns, 1, _lib.JK_POINTS_MAX, "the support size ns (with more labels use a held-out split)")
+    alpha = torch.as_tensor(alpha, dtype=torch.float32).reshape(-1)
+    L = _in_range(alpha.numel(), 1, _lib.JK_LEVELS_MAX, "the number of levels")
+    phi, X = _phi_and_pool(b, phi, X)
+    rows = X.shape[0]
+    _on_device(b, X=X)
+    if not (want_lo and rows > 0 or want_hi and rows > 0 or want_loo or topk > 0):
+        raise ValueError("no output asked for")
+    alpha = alpha.to(b.device).contiguous()
+    excl_idx, excl_off = _exclusion(b, exclude if topk > 0 else None, b.T, rows)
+    lo = _new(b, b.T, L, rows) if want_lo else None
+    hi = _new(b, b.T, L, rows) if want_hi else None
+    loo_mean = _new(b, b.T, b.ns) if want_loo else None
+    loo_var = _new(b, b.T, b.ns) if want_loo else None
+    loo_lpd = _new(b, b.T) if want_loo else None
+    top_idx, top_val, info = _selection(b, b.T, topk)
+    flags = (_lib.PM_MAXIMIZE if maximize else 0) | (_lib.PM_JK_SCALED if scaled else 0)
+    args = (ptr(alpha), L, ptr(excl_idx), ptr(excl_off), ptr(lo), ptr(hi), ptr(loo_mean), ptr(loo_var), ptr(loo_lpd), topk, ptr(top_idx),
+            ptr(top_val))
+    _pool_call(lib, "adkf_jackknife_pool", b, phi, flags, X, args, info, lib.adkf_jackknife_pool_scratch_bytes(b.T, b.ns, L, topk))
+    return dict(lo=lo, hi=hi, loo_mean=loo_mean, loo_var=loo_var, loo_lpd=loo_lpd, top_idx=top_idx, top_val=top_val, info=info)
+
+
+def loo(b: GPBatch, phi: torch.Tensor):
+    """Leave-one-out cross-validation of the fitted tasks at ``phi`` (not refitted per fold): the ``rows = 0`` form of
+    ``jackknife_pool``.  Returns ``dict(loo_mean [T, ns], loo_var [T, ns], loo_lpd [T], info [T])``."""
+    out = jackknife_pool(b, phi, torch.empty(0, b.d, device=b.device), want_lo=False, want_hi=False)
+    return {k: out[k] for k in ("loo_mean", "loo_var", "loo_lpd", "info")}
+
+
 def max_value_samples(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: torch.Tensor, phase: torch.Tensor, n_samples: int,
                       generator: Optional[torch.Generator] = None, w: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
                       maximize: bool = False):

@@ -610,6 +610,51 @@ int adkf_jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
 size_t adkf_ipv_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t M, int32_t q);
 int adkf_ipv_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* tgt_idx, const float* tgt_w, int32_t M, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* tvar, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Leave-one-out checks and jackknife+ prediction intervals over a shared pool (csrc/jackknife_stream.h; Rasmussen and Williams 2006,
+ * section 5.4.2, GPyTorch's LeaveOneOutPseudoLikelihood and BoTorch's batch_cross_validation for the leave-one-out forms; Barber,
+ * Candes, Ramdas and Tibshirani 2021, "Predictive inference with the jackknife+", for the intervals).  How far the predictions of a
+ * task with a handful of labels can be trusted, without holding any label out and without resting on the GP variance.
+ *   Fixed phi.  Everything below is at the phi passed: the hyperparameters are NOT refitted per fold.  The coverage theorem holds for
+ *          that fixed-phi predictor; with phi fitted on the same points it is a very good approximation, not a guarantee.
+ *   The quantities.  A = K_ss + noise I, B = A^-1, alpha = B y, os and noise exactly what adkf_predict_pool reads (zero prior mean);
+ *          m(x), v(x) its mean and latent variance of pool row x; c_i(x) = sum_j K(x, z_j) B_ji; n = n_s[t].  For i < n:
+ *              g_i           = alpha_i / B_ii                    (= y_i - mu_-i(z_i), the leave-one-out residual)
+ *              loo_mean[t,i] = y_i - g_i,    loo_var[t,i] = 1 / B_ii   (the observed variance, noise included)
+ *              loo_lpd[t]    = sum_i [ -log(2 pi / B_ii) / 2 - g_i^2 B_ii / 2 ]   (R&W eq. 5.10), summed by ascending i
+ *              mu_-i(x)      = m(x) - c_i(x) g_i,                v_-i(x) = v(x) + c_i(x)^2 / B_ii
+ *          (deleting point i is a rank-one update: no refactorisation).  Slots i >= n hold 0.  The fold values of a row:
+ *              plain         a_i = mu_-i(x) - |g_i|,             b_i = mu_-i(x) + |g_i|
+ *              scaled        a_i = mu_-i(x) - s_i sd_i(x),       b_i = mu_-i(x) + s_i sd_i(x)       (ADKF_PM_JK_SCALED: locally
+ *                            s_i = |g_i| sqrt(B_ii),             sd_i(x) = sqrt(max(v_-i(x), 1e-12) + noise)      adaptive widths)
+ *   alpha  [L] float32 on the device, shared by all tasks, 1 <= L <= ADKF_JK_LEVELS_MAX.  The rank of level l in task t is
+ *          k = floor((double)alpha[l] * (n + 1)) - exact in double, so a function of the bits passed; a level that is NaN, <= 0 or
+ *          >= 1 has k = 0.  lo[t, l, x] is the k-th smallest a_i, hi[t, l, x] the k-th largest b_i; k = 0 gives -inf / +inf: the
+ *          support set is too small for that level.  [lo, hi] covers a new label with probability >= 1 - 2 alpha[l].  Order
+ *          statistics are values: the answer is unique.
+ *   lo, hi   nullable, [T, L, rows].     loo_mean, loo_var, loo_lpd   nullable, [T, ns_max], [T, ns_max], [T].
+ *   k, top_idx, top_val   the selection of adkf_predict_pool ([T, k], its total order, exclusion lists and -1 / -inf tail) on the
+ *          level-0 score: lo with ADKF_PM_MAXIMIZE, -hi without - conservative screening, by the bound one can rely on.  A row
+ *          whose score is infinite or NaN is never selected.
+ *   b      support-only, of either kind, as for adkf_kg_pool, with ns_max <= ADKF_JK_POINTS_MAX (beyond: ADKF_E_SIZE; with that many
+ *          labels use a held-out split).  rows == 0 is valid: the plain leave-one-out diagnostic.
+ *   flags  ADKF_PM_MAXIMIZE | ADKF_PM_JK_SCALED.
+ *   Tasks with n_s == 0 or info != 0: zeros everywhere and -1 / -inf selections.  A pool row whose own mean or variance is NaN has
+ *          NaN bounds and is never selected.
+ *   scratch   adkf_jackknife_pool_scratch_bytes(T, ns_max, L, k) bytes, 8-byte aligned: g, 1 / B_ii and the width factor [T, ns_max]
+ *          (with float64 copies), the ranks and the candidate lists.  A function of (T, ns_max, k) only, 0 for arguments out of
+ *          range; nothing of size T x rows exists unless lo or hi is asked for.
+ * Asynchronous on `stream` and capturable, no allocation, no synchronisation, no atomics, every sum in a fixed order: reproducible to
+ * the bit, and a task's result depends on that task's data, the levels, the pool and its exclusion list only - not on the grid or on
+ * the other tasks of the batch.  Rejected before anything is launched, ADKF_E_BADARG unless noted: ns_max > ADKF_JK_POINTS_MAX, L < 1
+ * or L > ADKF_JK_LEVELS_MAX, k > ADKF_POOL_TOPK_MAX (ADKF_E_SIZE); alpha, info or ws NULL; a batch with a query set; a flag bit other
+ * than the two above; rows < 0; rows > 0 without X; excl_idx without excl_off; k < 0; k > 0 without top_idx or top_val; no output at
+ * all; a scratch or a workspace that is too small (ADKF_E_WORKSPACE); a scratch that is not 8-byte aligned. */
+#define ADKF_PM_JK_SCALED 64         /* adkf_jackknife_pool only: fold widths scaled by the leave-one-out predictive deviation */
+#define ADKF_JK_POINTS_MAX 256       /* FS-Mol's largest support size */
+#define ADKF_JK_LEVELS_MAX 8
+size_t adkf_jackknife_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t L, int32_t k);
+int adkf_jackknife_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* alpha, int32_t L, const int64_t* excl_idx, const int64_t* excl_off, float* lo, float* hi, float* loo_mean, float* loo_var, float* loo_lpd, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Constrained expected hypervolume improvement ACROSS tasks over a shared pool (csrc/ehvi_stream.h; Emmerich, Deutz and Klinkenberg
  * 2011 and Yang et al. 2019 for the exact two-objective form, BoTorch's analytic ExpectedHypervolumeImprovement; Schonlau 1998 and
  * Gardner et al. 2014 for the feasibility weight, BoTorch's ConstrainedExpectedImprovement; ADKF_PM_LOG_EI: their log forms).  It
