@@ -2,10 +2,14 @@
 // testing without a GPU"; section 8(d)(ii): the second CPU baseline, so that GPU-vs-CPU is not only GPU vs slow Python).
 //
 // Same C ABI, HOST pointers: adkf_batch_t, priors, phi layouts, info codes and flags exactly as in the header; `ws` /
-// `ws_bytes` / `stream` are accepted and ignored (adkf_workspace_bytes returns 0 here).  Non-ARD batches of any size; the
-// exceptions are adkf_predict_marginal_ard, which centres and scales the features by the per-dimension lengthscales and runs
-// the isotropic code at unit lengthscale (csrc/ard.h), and adkf_thompson_pool_ard and adkf_believer_pool_ard, which do the same for
-// Thompson sampling and Kriging-believer selection.  adkf_thompson_pool and adkf_believer_pool refuse ARD batches, as the library does.
+// `ws_bytes` / `stream` / `scratch` are accepted and ignored (adkf_workspace_bytes and every *_scratch_bytes return 0 here).  Batches
+// of any size.  The fit, prediction and hypergradient entries (adkf_median_lengthscale, adkf_init_params, adkf_mll_value_grad,
+// adkf_fit, adkf_predict, adkf_outer_nll_value_grad, adkf_ift_hypergrad) take non-ARD batches only.  The streaming entries on a
+// support-only batch take ARD batches too - they centre and scale the features by the per-dimension lengthscales and run the
+// isotropic code at unit lengthscale (csrc/ard.h, prepare_task below): adkf_predict_marginal_ard, adkf_thompson_pool_ard and
+// adkf_believer_pool_ard take ARD batches only and their plain namesakes refuse them, as the library does; adkf_predict_pool,
+// adkf_mes_pool, adkf_gumbel_pool, adkf_gibbon_pool, adkf_kg_pool, adkf_ipv_pool, adkf_jes_pool, adkf_jackknife_pool, adkf_ehvi_pool
+// and adkf_mix_pool take either kind.  What the pool entries share is the pool kit (after pm_task).
 // Plain loops, OpenMP over the tasks of a batch, float64 arithmetic inside and float32 at the boundary - a Cholesky-based
 // restatement of the same staged closed-form algebra the HIP kernels run (stage names as in DESIGN.md section 3 and
 // oracle/closed_form.py): kernel matrices from difference-form squared distances, A = L L^T, A^-1, the analytic 3 x 3 Hessian,
@@ -13,8 +17,11 @@
 // through D^2 to dL/dZ.  The inner fit is the same quasi-Newton state machine as csrc/inner.h (BFGS, Armijo backtracking
 // with safeguarded quadratic interpolation, the reference's gtol / ftol rules).
 //
-// Used ONLY by bench.py's cpu_baseline leg (entry "kind": "twin") and by tests/test_cpu_twin.py, which pins it to the golden
-// fixtures; the product package (adkf_ift_amd.gp_ops) never loads it and keeps refusing CPU tensors.
+// Test and baseline infrastructure only: bench.py's cpu_baseline leg (entry "kind": "twin") times it, tests/test_cpu_twin.py pins it
+// to the golden fixtures, every tests/test_*_pool_cpu.py, tests/test_predict_marginal*_cpu.py and tests/test_log_ei_cpu.py holds an
+// entry against its float64 reference, some GPU tests hold the library against it (tests/test_gpu_believer_pool*.py, test_gpu_gibbon_pool.py,
+// test_gpu_ipv_pool.py) and tools/twin_bits.py compares two builds of it bit for bit; the product package (adkf_ift_amd.gp_ops)
+// never loads it and keeps refusing CPU tensors.
 //   g++ -O3 -fopenmp -shared -fPIC -std=c++17 -I include adkf_ift_amd/csrc/cpu/adkf_gp_cpu.cpp -o adkf_ift_amd/libadkf_gp_cpu.so
 #include <algorithm>
 #include <functional>
@@ -373,60 +380,90 @@ float pm_ei(double mu, double vl, double bf, int flags) {
     return (float)(sg * (u * 0.5 * std::erfc(-u / std::sqrt(2.0)) + std::exp(-0.5 * u * u) / std::sqrt(2.0 * M_PI)));
 }
 
+// The posterior of one row from its squared distances D [n] to the support set of a task: k = s kappa(D / l^2) into kr [n] (row_k),
+// c = k A^-1 into c [n] unless it is null, mu = c . y and q = c . k (the latent variance is s - q).  The only place that forms them;
+// the variance clamp, ADKF_PM_LATENT and the noise stay with the callers.
+inline void row_k(const Inner& in, int kind, const double* D, double* kr) {
+    const double il2 = 1.0 / (in.l * in.l);
+    for (int j = 0; j < in.n; ++j) { double k0, k1, k2; kappa(kind, D[j] * il2, k0, k1, k2); kr[j] = in.s * k0; }
+}
+struct MuQ { double mu, q; };
+MuQ row_posterior(const Inner& in, int kind, const double* D, const float* y, double* kr, double* c) {
+    const int n = in.n;
+    row_k(in, kind, D, kr);
+    double mu = 0.0, q = 0.0;
+    for (int j = 0; j < n; ++j) {
+        double cj = 0.0;
+        for (int i = 0; i < n; ++i) cj += kr[i] * in.Ainv[(size_t)i * n + j];
+        if (c) c[j] = cj;
+        mu += cj * (double)y[j];
+        q += cj * kr[j];
+    }
+    return {mu, q};
+}
+
 // adkf_predict_marginal(_ard): mean, variance and EI (ADKF_PM_LOG_EI: log EI) of row r from its squared distances D [n] to the
 // support set of a task
 void pm_row(const Inner& in, int kind, const double* D, const float* y, int flags, const float* best_f, int t, int64_t r, float* mean,
             float* var, float* ei) {
-    const int n = in.n;
-    const double il2 = 1.0 / (in.l * in.l);
-    std::vector<double> k(n);
-    for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(kind, D[j] * il2, k0, k1, k2); k[j] = in.s * k0; }
-    double mu = 0.0, q = 0.0;
-    for (int j = 0; j < n; ++j) {
-        double cj = 0.0;
-        for (int i = 0; i < n; ++i) cj += k[i] * in.Ainv[(size_t)i * n + j];
-        mu += cj * (double)y[j];
-        q += cj * k[j];
-    }
-    const double vl = in.s - q;
-    mean[r] = (float)mu;
+    std::vector<double> k(in.n);
+    const MuQ p = row_posterior(in, kind, D, y, k.data(), nullptr);
+    const double vl = in.s - p.q;
+    mean[r] = (float)p.mu;
     if (var) var[r] = (float)((flags & ADKF_PM_LATENT) ? vl : vl + in.noise);
-    if (ei) ei[r] = pm_ei(mu, vl, best_f[t], flags);
+    if (ei) ei[r] = pm_ei(p.mu, vl, best_f[t], flags);
 }
 
-// One task of adkf_predict_marginal(_ard) and adkf_predict_pool: inner_stage on the support set, then row(r, in, D) for the rows
-// lo <= r < hi of Zq, D [n] the squared distances of row r to the support set.  ARD: on z~ = (z - mu) / l with mu the support column
+// What every streaming entry prepares of a task: inner_stage on the support set.  ARD: on z~ = (z - mu) / l with mu the support column
 // mean and l = softplus(raw_lengthscale) per dimension, at unit lengthscale (phi3 = (raw_noise, raw_outputscale, softplus^-1(1)),
-// no lengthscale prior), as csrc/ard.h does; otherwise mu = 0 and l = 1, which change no bit.  Sets info[t]; false when no row was
-// evaluated (n_s == 0 or info != 0).
-// state(in): called once per evaluated task before its rows (adkf_jackknife_pool: the leave-one-out state, with or without rows).
-template <class STATE, class ROW>
-bool pm_task_state(const adkf_batch_t* b, const float* phi, int t, const float* Zq, int64_t lo, int64_t hi, int32_t* info, STATE state, ROW row) {
+// no lengthscale prior), as csrc/ard.h does; otherwise mu = 0 and l = 1, which change no bit.  mean: the support column mean, for
+// ARD batches and where with_mean asks for it (Thompson centres its random features with it in both kinds); otherwise 0.
+struct TaskPrep {
+    int n = 0;
+    std::vector<double> mean, mu, l;   // mu, l: the centring and the scaling of the distance operands
+    Mat Zt;                            // the support rows, centred and scaled
+    Inner in;
+};
+// Sets info[t]; false when there is nothing to evaluate (n_s == 0 or info != 0).
+bool prepare_task(const adkf_batch_t* b, const float* phi, int t, bool with_mean, int32_t* info, TaskPrep& p) {
     const bool ard = (b->flags & ADKF_BATCH_ARD) != 0;
-    const int d = b->d, n = std::min(ns_of(b, t), b->ns_max);
+    const int d = b->d, n = p.n = std::min(ns_of(b, t), b->ns_max);
     info[t] = 0;
     if (n <= 0) return false;
     const float* Zs = b->Z_s + (size_t)t * b->ns_max * d;
     const float* x = phi + (size_t)t * (ard ? 2 + d : 3);
-    std::vector<double> mu(d, 0.0), l(d, 1.0);
-    if (ard) {
-        for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) mu[c] += Zs[(size_t)i * d + c];
-        for (int c = 0; c < d; ++c) { mu[c] /= n; l[c] = softplus(x[2 + c]); }
+    p.mean.assign(d, 0.0); p.l.assign(d, 1.0);
+    if (ard || with_mean) {
+        for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) p.mean[c] += Zs[(size_t)i * d + c];
+        for (int c = 0; c < d; ++c) p.mean[c] /= n;
     }
-    Mat Zt((size_t)n * d);
-    for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) Zt[(size_t)i * d + c] = ((double)Zs[(size_t)i * d + c] - mu[c]) / l[c];
-    const double p[3] = {x[0], x[1], ard ? std::log(std::expm1(1.0)) : (double)x[2]};
+    if (ard) for (int c = 0; c < d; ++c) p.l[c] = softplus(x[2 + c]);
+    p.mu = ard ? p.mean : std::vector<double>(d, 0.0);
+    p.Zt.resize((size_t)n * d);
+    for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) p.Zt[(size_t)i * d + c] = ((double)Zs[(size_t)i * d + c] - p.mu[c]) / p.l[c];
+    const double x3[3] = {x[0], x[1], ard ? std::log(std::expm1(1.0)) : (double)x[2]};
     const float pri[4] = {b->priors[t * 4], b->priors[t * 4 + 1], ard ? 0.f : b->priors[t * 4 + 2], ard ? -1.f : b->priors[t * 4 + 3]};
-    const Inner in = inner_stage(sqdist(Zt.data(), n, Zt.data(), n, d), b->y_s + (size_t)t * b->ns_max, n, p, pri, b->kernel, false, false);
-    info[t] = in.info;
-    if (in.info) return false;
-    state(in);
+    p.in = inner_stage(sqdist(p.Zt.data(), n, p.Zt.data(), n, d), b->y_s + (size_t)t * b->ns_max, n, x3, pri, b->kernel, false, false);
+    info[t] = p.in.info;
+    return p.in.info == 0;
+}
+// the squared distances [n] of the row x [d] to the prepared support set
+Mat task_row_dist(const TaskPrep& p, const float* x, int d) {
     std::vector<double> zt(d);
-    for (int64_t r = lo; r < hi; ++r) {
-        for (int c = 0; c < d; ++c) zt[c] = ((double)Zq[(size_t)r * d + c] - mu[c]) / l[c];
-        const Mat D = sqdist(zt.data(), 1, Zt.data(), n, d);
-        row(r, in, D.data());
-    }
+    for (int c = 0; c < d; ++c) zt[c] = ((double)x[c] - p.mu[c]) / p.l[c];
+    return sqdist(zt.data(), 1, p.Zt.data(), p.n, d);
+}
+
+// One task of adkf_predict_marginal(_ard) and of every pool entry but Thompson's: prepare_task, then row(r, in, D) for the rows
+// lo <= r < hi of Zq, D [n] the squared distances of row r to the support set.  Sets info[t]; false when no row was evaluated
+// (n_s == 0 or info != 0).
+// state(in): called once per evaluated task before its rows (adkf_jackknife_pool: the leave-one-out state, with or without rows).
+template <class STATE, class ROW>
+bool pm_task_state(const adkf_batch_t* b, const float* phi, int t, const float* Zq, int64_t lo, int64_t hi, int32_t* info, STATE state, ROW row) {
+    TaskPrep p;
+    if (!prepare_task(b, phi, t, false, info, p)) return false;
+    state(p.in);
+    for (int64_t r = lo; r < hi; ++r) row(r, p.in, task_row_dist(p, Zq + (size_t)r * b->d, b->d).data());
     return true;
 }
 template <class ROW>
@@ -434,11 +471,131 @@ bool pm_task(const adkf_batch_t* b, const float* phi, int t, const float* Zq, in
     return pm_task_state(b, phi, t, Zq, lo, hi, info, [](const Inner&) {}, row);
 }
 
+// ---- The pool kit: what the entries over a shared pool have in common.  An entry writes its own flags and arguments, its fills and its
+// arithmetic per row; the rest is here:
+//   check_support_only, pool_args_ok   every entry (named as in csrc/host_stream.h); check_topk: those with a top-k selection
+//   row_posterior (above)              pm_row (predict_marginal, predict_pool, gumbel, mix), mes, jackknife, ehvi, and pool_state
+//   PoolState, pool_state, c0_col      believer / gibbon, kg, ipv, jes: K, K A^-1, mean and latent variance of every row, c0(x_r, x_p)
+//   excl_range (Excl::has)             select_topk, greedy_pick and Thompson's per-row test
+//   init_topk, select_topk             predict_pool, mes, kg, jes, jackknife, ehvi and mix (per group); init_topk also the sel_* fills
+//   greedy_pick, append_pick           believer / gibbon (step j) and ipv (pick c)
+//   valid_entry                        kg (references) and ipv (targets)
+//   prepare_task, task_row_dist        pm_task_state and thompson_pool
+enum { ARD_EITHER = -1 };   // check_support_only's ard_mode; 0 / 1: the batch must not / must be an ARD batch
+int check_support_only(const adkf_batch_t* b, const float* phi, const int32_t* info, int64_t rows, int ard_mode) {
+    if (int rc = check(b, false, ard_mode != 0)) return rc;
+    const bool kind_ok = ard_mode == ARD_EITHER || ((b->flags & ADKF_BATCH_ARD) != 0) == (ard_mode != 0);
+    if (!kind_ok || b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
+    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    return 0;
+}
+// a pool where there are rows, and exclusion lists only with their offsets
+inline bool pool_args_ok(const float* X, int64_t rows, const int64_t* excl_idx, const int64_t* excl_off) {
+    return !(rows > 0 && !X) && !(excl_idx && !excl_off);
+}
+// the selection of k rows per task: k itself and the two outputs it needs
+inline int check_topk(int k, const int64_t* top_idx, const float* top_val) {
+    if (k < 0 || (k > 0 && (!top_idx || !top_val))) return ADKF_E_BADARG;
+    return k > ADKF_POOL_TOPK_MAX ? ADKF_E_SIZE : 0;
+}
+
+// the sorted exclusion list of task (group) t
+struct Excl {
+    const int64_t *lo = nullptr, *hi = nullptr;
+    bool has(int64_t r) const { return lo && std::binary_search(lo, hi, r); }
+};
+inline Excl excl_range(const int64_t* excl_idx, const int64_t* excl_off, int t) {
+    return excl_idx ? Excl{excl_idx + excl_off[t], excl_idx + excl_off[t + 1]} : Excl{};
+}
+// the k slots of task (group) t before anything is selected: -1 / -inf
+inline void init_topk(int64_t* top_idx, float* top_val, int t, int k) {
+    for (int q = 0; q < k; ++q) { top_idx[(size_t)t * k + q] = -1; top_val[(size_t)t * k + q] = -std::numeric_limits<float>::infinity(); }
+}
+// The selection of every pool entry: the k eligible rows (not NaN, not excluded) under the total order "larger score first, equal
+// scores by ascending row"; slots beyond the eligible rows keep what init_topk wrote.
+void select_topk(const std::vector<float>& sc, int64_t rows, int k, const Excl& excl, int64_t* top_idx, float* top_val) {
+    std::vector<int64_t> cand;
+    for (int64_t r = 0; r < rows; ++r)
+        if (sc[r] == sc[r] && !excl.has(r)) cand.push_back(r);
+    const size_t kk = std::min<size_t>(k, cand.size());
+    std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return sc[a] > sc[c] || (sc[a] == sc[c] && a < c); });
+    for (size_t q = 0; q < kk; ++q) { top_idx[q] = cand[q]; top_val[q] = sc[cand[q]]; }
+}
+// One step of a greedy batch: the row of largest score among those not NaN, not taken and not excluded, the lower index on a tie; -1
+// when there is none
+int64_t greedy_pick(const std::vector<float>& score, int64_t rows, const std::vector<char>& taken, const Excl& excl) {
+    int64_t p = -1;
+    for (int64_t r = 0; r < rows; ++r) {
+        if (score[r] != score[r] || taken[r] || excl.has(r)) continue;
+        if (p < 0 || score[r] > score[p]) p = r;   // (rows ascend: a tie keeps the lower index)
+    }
+    return p;
+}
+// entry j of idx when it is a row of the pool and its first occurrence, else -1
+int64_t valid_entry(const int64_t* idx, int j, int64_t rows) {
+    const int64_t p = idx[j];
+    if (p < 0 || p >= rows) return -1;
+    for (int i = 0; i < j; ++i) if (idx[i] == p) return -1;
+    return p;
+}
+
+// The state of a task over the whole pool: K [R, n], K A^-1 [R, n], the mean and the latent variance of every row, and for ARD batches
+// the pool rows over l (the distances between pool rows are taken on x / l: mu cancels).
+struct PoolState {
+    int n = 0;
+    size_t R = 0;
+    double s = 0.0, noise = 0.0, il2 = 0.0;
+    Mat Kr, Cr, mu, v, Xl;
+};
+// through pm_task; false when no row was evaluated
+bool pool_state(const adkf_batch_t* b, const float* phi, int t, const float* X, int64_t rows, int32_t* info, PoolState& st) {
+    const int n = st.n = std::min(ns_of(b, t), b->ns_max), d = b->d;
+    const size_t R = st.R = (size_t)rows;
+    st.Kr.resize(R * std::max(n, 0)); st.Cr.resize(R * std::max(n, 0)); st.mu.resize(R); st.v.resize(R);
+    const float* y = b->y_s + (size_t)t * b->ns_max;
+    const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
+        st.s = in.s; st.noise = in.noise; st.il2 = 1.0 / (in.l * in.l);
+        const MuQ p = row_posterior(in, b->kernel, D, y, &st.Kr[(size_t)r * n], &st.Cr[(size_t)r * n]);
+        st.mu[r] = p.mu; st.v[r] = in.s - p.q;
+    });
+    if (done && (b->flags & ADKF_BATCH_ARD)) {
+        const float* x0 = phi + (size_t)t * (2 + d);
+        st.Xl.resize(R * d);
+        for (size_t r = 0; r < R; ++r) for (int c = 0; c < d; ++c) st.Xl[r * d + c] = (double)X[r * d + c] / softplus(x0[2 + c]);
+    }
+    return done;
+}
+// c0(x_r, x_p), the posterior covariance of row p with every row r, into out [R]
+void c0_col(const PoolState& st, const adkf_batch_t* b, const float* X, int64_t p, double* out) {
+    const int n = st.n, d = b->d;
+    const Mat Dp = (b->flags & ADKF_BATCH_ARD) ? sqdist(st.Xl.data() + (size_t)p * d, 1, st.Xl.data(), (int)st.R, d) : sqdist(X + (size_t)p * d, 1, X, (int)st.R, d);
+    for (size_t r = 0; r < st.R; ++r) {
+        double k0, k1, k2;
+        kappa(b->kernel, Dp[r] * st.il2, k0, k1, k2);
+        double c0 = st.s * k0;
+        for (int i = 0; i < n; ++i) c0 -= st.Kr[r * n + i] * st.Cr[(size_t)p * n + i];
+        out[r] = c0;
+    }
+}
+// Row p joins a greedy batch as its entry c (of at most q): the new row of G, column c of ell for every row (the forward substitution
+// of the header, one row of G at a time; col [R] is scratch) and the downdate of every row's variance, the picked one included.
+void append_pick(PoolState& st, const adkf_batch_t* b, const float* X, int64_t p, int c, int q, Mat& G, Mat& L, Mat& col) {
+    for (int l = 0; l < c; ++l) G[(size_t)c * q + l] = L[(size_t)p * q + l];
+    G[(size_t)c * q + c] = std::sqrt(st.v[p] + st.noise);
+    c0_col(st, b, X, p, col.data());
+    for (size_t r = 0; r < st.R; ++r) {
+        double c0 = col[r];
+        for (int l = 0; l < c; ++l) c0 -= G[(size_t)c * q + l] * L[r * q + l];
+        const double e = c0 / G[(size_t)c * q + c];
+        L[r * q + c] = e;
+        st.v[r] -= e * e;
+    }
+}
+
 int predict_marginal(bool ard, const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
                      const float* best_f, float* mean, float* var, float* ei, int32_t* info) {
-    if (int rc = check(b, false, ard)) return rc;
-    if (((b->flags & ADKF_BATCH_ARD) != 0) != ard || b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !q_off || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (int rc = check_support_only(b, phi, info, rows, ard)) return rc;
+    if (!q_off) return ADKF_E_BADARG;
     if (rows > 0 && (!Zq || !mean)) return ADKF_E_BADARG;
     if (ei && !best_f) return ADKF_E_BADARG;
     if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
@@ -647,26 +804,21 @@ size_t adkf_predict_pool_scratch_bytes(int32_t, int32_t) { return 0; }
 int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
                       const int64_t* excl_idx, const int64_t* excl_off, float* mean, float* var, float* ei, int32_t k, int64_t* top_idx,
                       float* top_val, int32_t* info, void*, size_t, void*, size_t, void*) {
-    if (int rc = check(b, false, true)) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !info || !b->y_s || !b->priors || rows < 0 || k < 0) return ADKF_E_BADARG;
+    if (int rc = check_support_only(b, phi, info, rows, ARD_EITHER)) return rc;
     if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
     const bool by_mean = (flags & ADKF_PM_SCORE_MEAN) != 0, want_e = ei || (k > 0 && !by_mean);
     if ((flags & ADKF_PM_LOG_EI) && !want_e) return ADKF_E_BADARG;   // nothing would read it
-    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (want_e && !best_f) return ADKF_E_BADARG;
-    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
     if (!mean && !var && !ei && k == 0) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
-    if (k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
-    const float ninf = -std::numeric_limits<float>::infinity();
+    if (int rc = check_topk(k, top_idx, top_val)) return rc;
 #pragma omp parallel for schedule(dynamic)
     for (int t = 0; t < b->T; ++t) {
         const size_t o = (size_t)t * (size_t)rows;
         if (mean) std::fill(mean + o, mean + o + rows, 0.f);
         if (var) std::fill(var + o, var + o + rows, 0.f);
         if (ei) std::fill(ei + o, ei + o + rows, 0.f);
-        for (int q = 0; q < k; ++q) { top_idx[(size_t)t * k + q] = -1; top_val[(size_t)t * k + q] = ninf; }
+        init_topk(top_idx, top_val, t, k);
         std::vector<float> score(k > 0 ? (size_t)rows : 0);
         const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
             float m1, v1, e1 = 0.f;
@@ -676,14 +828,7 @@ int adkf_predict_pool(const adkf_batch_t* b, const float* phi, int32_t flags, co
             if (ei) ei[o + r] = e1;
             if (k > 0) score[r] = by_mean ? ((flags & ADKF_PM_MAXIMIZE) ? m1 : -m1) : e1;
         });
-        if (!done || k <= 0) continue;
-        std::vector<int64_t> cand;
-        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
-        for (int64_t r = 0; r < rows; ++r)
-            if (score[r] == score[r] && !(xb && std::binary_search(xb, xe, r))) cand.push_back(r);
-        const size_t kk = std::min<size_t>(k, cand.size());
-        std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return score[a] > score[c] || (score[a] == score[c] && a < c); });
-        for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)t * k + q] = cand[q]; top_val[(size_t)t * k + q] = score[cand[q]]; }
+        if (done && k > 0) select_topk(score, rows, k, excl_range(excl_idx, excl_off, t), top_idx + (size_t)t * k, top_val + (size_t)t * k);
     }
     return 0;
 }
@@ -720,56 +865,34 @@ static double mes_term(double g) {
 int adkf_mes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* ystar, int32_t S,
                   const int64_t* excl_idx, const int64_t* excl_off, float* score, int32_t k, int64_t* top_idx, float* top_val, int32_t* info,
                   void*, size_t, void*, size_t, void*) {
-    if (int rc = check(b, false, true)) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (int rc = check_support_only(b, phi, info, rows, ARD_EITHER)) return rc;
     if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
     if (!ystar) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
-    if (k < 0) return ADKF_E_BADARG;
-    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (k == 0 && !score) return ADKF_E_BADARG;
+    if (int rc = check_topk(k, top_idx, top_val)) return rc;
     if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
-    if (k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
-    const float ninf = -std::numeric_limits<float>::infinity();
     const bool maximize = (flags & ADKF_PM_MAXIMIZE) != 0;
 #pragma omp parallel for schedule(dynamic)
     for (int t = 0; t < b->T; ++t) {
         const size_t o = (size_t)t * (size_t)rows;
         if (score) std::fill(score + o, score + o + rows, 0.f);
-        for (int q = 0; q < k; ++q) { top_idx[(size_t)t * k + q] = -1; top_val[(size_t)t * k + q] = ninf; }
+        init_topk(top_idx, top_val, t, k);
         std::vector<float> sc((size_t)rows);
+        std::vector<double> kr(b->ns_max);
         const float* y = b->y_s + (size_t)t * b->ns_max;
         const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
-            const int n = in.n;
-            const double il2 = 1.0 / (in.l * in.l);
-            std::vector<double> kr(n);
-            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); kr[j] = in.s * k0; }
-            double mu = 0.0, q = 0.0;
-            for (int j = 0; j < n; ++j) {
-                double cj = 0.0;
-                for (int i = 0; i < n; ++i) cj += kr[i] * in.Ainv[(size_t)i * n + j];
-                mu += cj * (double)y[j];
-                q += cj * kr[j];
-            }
-            const double sg = std::sqrt(std::max(in.s - q, 1e-12));
+            const MuQ p = row_posterior(in, b->kernel, D, y, kr.data(), nullptr);
+            const double sg = std::sqrt(std::max(in.s - p.q, 1e-12));
             double sum = 0.0;
             for (int s = 0; s < S; ++s) {
                 const double ys = ystar[(size_t)t * S + s];
-                sum += mes_term((maximize ? (ys - mu) : (mu - ys)) / sg);
+                sum += mes_term((maximize ? (ys - p.mu) : (p.mu - ys)) / sg);
             }
             sc[r] = (float)(sum / S);
             if (score) score[o + r] = sc[r];
         });
-        if (!done || k <= 0) continue;
-        std::vector<int64_t> cand;
-        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
-        for (int64_t r = 0; r < rows; ++r)
-            if (sc[r] == sc[r] && !(xb && std::binary_search(xb, xe, r))) cand.push_back(r);
-        const size_t kk = std::min<size_t>(k, cand.size());
-        std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return sc[a] > sc[c] || (sc[a] == sc[c] && a < c); });
-        for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)t * k + q] = cand[q]; top_val[(size_t)t * k + q] = sc[cand[q]]; }
+        if (done && k > 0) select_topk(sc, rows, k, excl_range(excl_idx, excl_off, t), top_idx + (size_t)t * k, top_val + (size_t)t * k);
     }
     return 0;
 }
@@ -790,12 +913,10 @@ static double neg_log_cdf(double g) {
 // interpolation and the fit in float64, the draw in float32.
 int adkf_gumbel_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* u, int32_t S,
                      float* ystar, float* quant, float* gumbel, int32_t* info, void*, size_t, void*, size_t, void*) {
-    if (int rc = check(b, false, true)) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (int rc = check_support_only(b, phi, info, rows, ARD_EITHER)) return rc;
     if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
     if (!u || !ystar) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, nullptr, nullptr)) return ADKF_E_BADARG;
     if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
     if (rows > ((int64_t)1 << 27)) return ADKF_E_SIZE;
     constexpr int G = ADKF_GUMBEL_PROBES;
@@ -876,50 +997,36 @@ size_t adkf_thompson_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { re
 
 // Thompson sampling over a shared pool (include/adkf_gp.h): the pathwise posterior draws in float64, rounded to float32 at the
 // boundary; the selection ranks those float32 values under "larger score first, equal scores by ascending row".  ARD
-// (adkf_thompson_pool_ard): on z~ = (z - mu) / l at unit lengthscale, prepared as pm_task prepares it; otherwise the features are
-// centred with mu, the distances are taken from the rows as they are and l = 1, which changes no bit of the isotropic call.
+// (adkf_thompson_pool_ard): on z~ = (z - mu) / l at unit lengthscale, by prepare_task as for every entry; otherwise the features are
+// centred with the support column mean (prepare_task's with_mean), the distances are taken from the rows as they are and l = 1, which changes no bit of the isotropic call.
 static int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega,
                          const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const int64_t* excl_idx,
                          const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info) {
-    if (int rc = check(b, false, ard)) return rc;
-    if (((b->flags & ADKF_BATCH_ARD) != 0) != ard || b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (int rc = check_support_only(b, phi, info, rows, ard)) return rc;
     if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (!omega || !phase || !w || !eps || !sel_idx || !sel_val) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
     if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
     if (m < 64 || m > ADKF_TS_FEATURES_MAX || (m & 63)) return ADKF_E_SIZE;
     const int d = b->d, ld = b->ns_max;
     const float ninf = -std::numeric_limits<float>::infinity();
 #pragma omp parallel for schedule(dynamic)
     for (int t = 0; t < b->T; ++t) {
-        const int n = std::min(ns_of(b, t), ld);
-        info[t] = 0;
-        for (int q = 0; q < S; ++q) { sel_idx[(size_t)t * S + q] = -1; sel_val[(size_t)t * S + q] = ninf; }
+        init_topk(sel_idx, sel_val, t, S);
         if (paths && rows > 0) std::fill(paths + (size_t)t * S * rows, paths + (size_t)(t + 1) * S * rows, 0.f);
-        if (n <= 0) continue;
+        TaskPrep tp;
+        if (!prepare_task(b, phi, t, true, info, tp)) continue;
+        const Inner& in = tp.in;
+        const int n = tp.n;
         const float* Zs = b->Z_s + (size_t)t * ld * d;
         const float* ys = b->y_s + (size_t)t * ld;
-        const float* x0 = phi + (size_t)t * (ard ? 2 + d : 3);
-        std::vector<double> mu(d, 0.0), l(d, 1.0);
-        for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) mu[c] += Zs[(size_t)i * d + c];
-        for (int c = 0; c < d; ++c) { mu[c] /= n; if (ard) l[c] = softplus(x0[2 + c]); }
-        const std::vector<double> dmu = ard ? mu : std::vector<double>(d, 0.0);   // the centring of the distance operands
-        Mat Zt((size_t)n * d);
-        for (int i = 0; i < n; ++i) for (int c = 0; c < d; ++c) Zt[(size_t)i * d + c] = ((double)Zs[(size_t)i * d + c] - dmu[c]) / l[c];
-        const double p[3] = {x0[0], x0[1], ard ? std::log(std::expm1(1.0)) : (double)x0[2]};
-        const float pri[4] = {b->priors[t * 4], b->priors[t * 4 + 1], ard ? 0.f : b->priors[t * 4 + 2], ard ? -1.f : b->priors[t * 4 + 3]};
-        Inner in = inner_stage(sqdist(Zt.data(), n, Zt.data(), n, d), ys, n, p, pri, b->kernel, false, false);
-        info[t] = in.info;
-        if (in.info) continue;
-        const double amp = std::sqrt(2.0 * in.s / m), sigma = std::sqrt(in.noise), il2 = 1.0 / (in.l * in.l);
+        const double amp = std::sqrt(2.0 * in.s / m), sigma = std::sqrt(in.noise);
         std::vector<double> ft(m);
         auto features = [&](const float* x) {   // phi_j(x), j < m
             for (int j = 0; j < m; ++j) {
                 double a = 0.0;
                 const float* om = omega + (size_t)j * d;
-                for (int c = 0; c < d; ++c) a += (double)om[c] * (((double)x[c] - mu[c]) / l[c]);
+                for (int c = 0; c < d; ++c) a += (double)om[c] * (((double)x[c] - tp.mean[c]) / tp.l[c]);
                 ft[j] = amp * std::cos(a / in.l + (double)phase[j]);
             }
         };
@@ -938,15 +1045,13 @@ static int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int3
             }
         std::vector<float> bv(S, ninf);
         std::vector<int64_t> bi(S, -1);
-        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
-        std::vector<double> k(n), zt(d);
+        const Excl excl = excl_range(excl_idx, excl_off, t);
+        std::vector<double> k(n);
         for (int64_t r = 0; r < rows; ++r) {
             const float* x = X + (size_t)r * d;
             features(x);
-            for (int c = 0; c < d; ++c) zt[c] = ((double)x[c] - dmu[c]) / l[c];
-            const Mat D = sqdist(zt.data(), 1, Zt.data(), n, d);
-            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); k[j] = in.s * k0; }
-            const bool excluded = xb && std::binary_search(xb, xe, r);
+            row_k(in, b->kernel, task_row_dist(tp, x, d).data(), k.data());
+            const bool excluded = excl.has(r);
             for (int q = 0; q < S; ++q) {
                 double f = prior(q);
                 for (int j = 0; j < n; ++j) f += k[j] * V[(size_t)q * n + j];
@@ -1011,56 +1116,28 @@ static double gibbon_term(double g, double rho2) {
 static int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
                          const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
                          float* sel_mean, float* sel_var, int32_t* info, const float* ystar = nullptr, int32_t S = 0, bool gibbon = false) {
-    if (int rc = check(b, false, ard)) return rc;
-    if (((b->flags & ADKF_BATCH_ARD) != 0) != ard || b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (int rc = check_support_only(b, phi, info, rows, ard)) return rc;
     if (flags & ~(gibbon ? ADKF_PM_MAXIMIZE : (ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI))) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (!(gibbon ? ystar : best_f) || !sel_idx || !sel_val) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
     if (q < 1 || (gibbon && S < 1)) return ADKF_E_BADARG;
     if (q > ADKF_POOL_TOPK_MAX || (gibbon && S > ADKF_TS_SAMPLES_MAX)) return ADKF_E_SIZE;
-    const int d = b->d;
-    const float ninf = -std::numeric_limits<float>::infinity();
 #pragma omp parallel for schedule(dynamic)
     for (int t = 0; t < b->T; ++t) {
-        for (int j = 0; j < q; ++j) {
-            const size_t o = (size_t)t * q + j;
-            sel_idx[o] = -1; sel_val[o] = ninf;
-            if (sel_mean) sel_mean[o] = 0.f;
-            if (sel_var) sel_var[o] = 0.f;
-        }
+        init_topk(sel_idx, sel_val, t, q);
+        if (sel_mean) std::fill(sel_mean + (size_t)t * q, sel_mean + (size_t)(t + 1) * q, 0.f);
+        if (sel_var) std::fill(sel_var + (size_t)t * q, sel_var + (size_t)(t + 1) * q, 0.f);
         if (trace && rows > 0) std::fill(trace + (size_t)t * q * rows, trace + (size_t)(t + 1) * q * rows, 0.f);
-        const int n = std::min(ns_of(b, t), b->ns_max);
-        const size_t R = (size_t)rows;
-        Mat Kr(R * std::max(n, 0)), Cr(R * std::max(n, 0)), mu(R), v(R), L(R * q);
-        double s = 0.0, noise = 0.0, il2 = 0.0;
-        const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
-            s = in.s; noise = in.noise; il2 = 1.0 / (in.l * in.l);
-            const float* y = b->y_s + (size_t)t * b->ns_max;
-            double* k = &Kr[(size_t)r * n];
-            double* c = &Cr[(size_t)r * n];
-            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); k[j] = in.s * k0; }
-            double m1 = 0.0, qf = 0.0;
-            for (int j = 0; j < n; ++j) {
-                double cj = 0.0;
-                for (int i = 0; i < n; ++i) cj += k[i] * in.Ainv[(size_t)i * n + j];
-                c[j] = cj;
-                m1 += cj * (double)y[j];
-                qf += cj * k[j];
-            }
-            mu[r] = m1; v[r] = in.s - qf;
-        });
-        if (!done) continue;
-        Mat Xl(ard ? R * d : 0);   // ARD: the pool rows over l
-        if (ard) {
-            const float* x0 = phi + (size_t)t * (2 + d);
-            for (size_t r = 0; r < R; ++r) for (int c = 0; c < d; ++c) Xl[r * d + c] = (double)X[r * d + c] / softplus(x0[2 + c]);
-        }
-        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
+        PoolState st;
+        if (!pool_state(b, phi, t, X, rows, info, st)) continue;
+        const size_t R = st.R;
+        const Mat& mu = st.mu;
+        const Mat& v = st.v;   // (append_pick downdates it)
+        const double noise = st.noise;
+        const Excl excl = excl_range(excl_idx, excl_off, t);
         std::vector<char> taken(R, 0);
         std::vector<float> score(R);
-        Mat G((size_t)q * q, 0.0);
+        Mat G((size_t)q * q, 0.0), L(R * q), col(R);
         double best = gibbon ? 0.0 : best_f[t];
         Mat v0(gibbon ? v : Mat()), ax(gibbon ? R : 0);   // GIBBON: the step-0 variance and a(x)
         if (gibbon)
@@ -1074,33 +1151,18 @@ static int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int3
                 ax[r] = -0.5 * sum / S;
             }
         for (int j = 0; j < q; ++j) {
-            int64_t p = -1;
             for (int64_t r = 0; r < rows; ++r) {
                 score[r] = gibbon ? (float)(ax[r] + 0.5 * std::log((std::max(v[r], 1e-12) + noise) / (std::max(v0[r], 1e-12) + noise)))
                                   : pm_ei(mu[r], v[r], best, flags);
                 if (trace) trace[((size_t)t * q + j) * R + r] = score[r];
-                if (score[r] != score[r] || taken[r] || (xb && std::binary_search(xb, xe, r))) continue;
-                if (p < 0 || score[r] > score[p]) p = r;   // (rows ascend: a tie keeps the lower index)
             }
+            const int64_t p = greedy_pick(score, rows, taken, excl);
             if (p < 0) continue;   // no eligible row: this step and all later ones keep -1 / -inf, the state (hence trace) stays
             const size_t o = (size_t)t * q + j;
             sel_idx[o] = p; sel_val[o] = score[p];
             if (sel_mean) sel_mean[o] = (float)mu[p];
             if (sel_var) sel_var[o] = (float)v[p];
-            // the new row of G, then column j of ell and the downdate for every row (the picked one included)
-            for (int l = 0; l < j; ++l) G[(size_t)j * q + l] = L[(size_t)p * q + l];
-            G[(size_t)j * q + j] = std::sqrt(v[p] + noise);
-            const Mat Dp = ard ? sqdist(Xl.data() + (size_t)p * d, 1, Xl.data(), (int)rows, d) : sqdist(X + (size_t)p * d, 1, X, (int)rows, d);
-            for (int64_t r = 0; r < rows; ++r) {
-                double k0, k1, k2;
-                kappa(b->kernel, Dp[r] * il2, k0, k1, k2);
-                double c0 = s * k0;
-                for (int i = 0; i < n; ++i) c0 -= Kr[(size_t)r * n + i] * Cr[(size_t)p * n + i];
-                for (int l = 0; l < j; ++l) c0 -= G[(size_t)j * q + l] * L[(size_t)r * q + l];
-                const double e = c0 / G[(size_t)j * q + j];
-                L[(size_t)r * q + j] = e;
-                v[r] -= e * e;
-            }
+            append_pick(st, b, X, p, j, q, G, L, col);   // (a step without a pick ends the batch, so step j is entry j)
             taken[p] = 1;
             const double mp = (double)(float)mu[p];
             best = (flags & ADKF_PM_MAXIMIZE) ? std::max(best, mp) : std::min(best, mp);
@@ -1167,80 +1229,40 @@ static double kg_value(std::vector<std::pair<double, double>> ln, bool want_log)
 int adkf_kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* ref_idx, int32_t M,
                  const int64_t* excl_idx, const int64_t* excl_off, float* score, float* cov, float* ref_mean, int32_t k, int64_t* top_idx,
                  float* top_val, int32_t* info, void*, size_t, void*, size_t, void*) {
-    if (int rc = check(b, false, true)) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (int rc = check_support_only(b, phi, info, rows, ARD_EITHER)) return rc;
     if (flags & ~(ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
     if (!ref_idx) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
-    if (k < 0) return ADKF_E_BADARG;
-    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (k == 0 && !score && !cov && !ref_mean) return ADKF_E_BADARG;
-    if (M < 1 || M > ADKF_KG_REFS_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
-    const bool ard = (b->flags & ADKF_BATCH_ARD) != 0, want_log = (flags & ADKF_PM_LOG_EI) != 0;
+    if (int rc = check_topk(k, top_idx, top_val)) return rc;
+    if (M < 1 || M > ADKF_KG_REFS_MAX) return ADKF_E_SIZE;
+    const bool want_log = (flags & ADKF_PM_LOG_EI) != 0;
     const double sgn = (flags & ADKF_PM_MAXIMIZE) ? 1.0 : -1.0;
-    const int d = b->d;
-    const float ninf = -std::numeric_limits<float>::infinity();
 #pragma omp parallel for schedule(dynamic)
     for (int t = 0; t < b->T; ++t) {
         const size_t R = (size_t)rows, o = (size_t)t * R;
         if (score) std::fill(score + o, score + o + R, 0.f);
         if (cov) std::fill(cov + o * M, cov + (o + R) * M, 0.f);
         if (ref_mean) std::fill(ref_mean + (size_t)t * M, ref_mean + (size_t)(t + 1) * M, 0.f);
-        for (int q = 0; q < k; ++q) { top_idx[(size_t)t * k + q] = -1; top_val[(size_t)t * k + q] = ninf; }
-        const int n = std::min(ns_of(b, t), b->ns_max);
-        Mat Kr(R * std::max(n, 0)), Cr(R * std::max(n, 0)), mu(R), v(R);
-        double s = 0.0, noise = 0.0, il2 = 0.0;
-        const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
-            s = in.s; noise = in.noise; il2 = 1.0 / (in.l * in.l);
-            const float* y = b->y_s + (size_t)t * b->ns_max;
-            double* kr = &Kr[(size_t)r * n];
-            double* c = &Cr[(size_t)r * n];
-            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); kr[j] = in.s * k0; }
-            double m1 = 0.0, qf = 0.0;
-            for (int j = 0; j < n; ++j) {
-                double cj = 0.0;
-                for (int i = 0; i < n; ++i) cj += kr[i] * in.Ainv[(size_t)i * n + j];
-                c[j] = cj;
-                m1 += cj * (double)y[j];
-                qf += cj * kr[j];
-            }
-            mu[r] = m1; v[r] = in.s - qf;
-        });
-        if (!done) continue;
-        Mat Xl(ard ? R * d : 0);   // ARD: the pool rows over l
-        if (ard) {
-            const float* x0 = phi + (size_t)t * (2 + d);
-            for (size_t r = 0; r < R; ++r) for (int c = 0; c < d; ++c) Xl[r * d + c] = (double)X[r * d + c] / softplus(x0[2 + c]);
-        }
-        // the valid entries: inside the pool, first occurrences
-        std::vector<int64_t> ref(M, -1);
+        init_topk(top_idx, top_val, t, k);
+        PoolState st;
+        if (!pool_state(b, phi, t, X, rows, info, st)) continue;
+        const Mat &mu = st.mu, &v = st.v;
+        std::vector<int64_t> ref(M);   // the valid entries, -1 for the others
+        Mat C(R * M, 0.0), col(R);     // cov(x_r, entry j)
         for (int j = 0; j < M; ++j) {
-            const int64_t p = ref_idx[(size_t)t * M + j];
-            if (p < 0 || p >= rows) continue;
-            bool first = true;
-            for (int i = 0; i < j && first; ++i) first = ref_idx[(size_t)t * M + i] != p;
-            if (first) ref[j] = p;
-        }
-        Mat C(R * M, 0.0);   // cov(x_r, entry j)
-        for (int j = 0; j < M; ++j) {
-            const int64_t p = ref[j];
+            const int64_t p = ref[j] = valid_entry(ref_idx + (size_t)t * M, j, rows);
             if (p < 0) continue;
             if (ref_mean) ref_mean[(size_t)t * M + j] = (float)mu[p];
-            const Mat Dp = ard ? sqdist(Xl.data() + (size_t)p * d, 1, Xl.data(), (int)rows, d) : sqdist(X + (size_t)p * d, 1, X, (int)rows, d);
+            c0_col(st, b, X, p, col.data());
             for (size_t r = 0; r < R; ++r) {
-                double k0, k1, k2;
-                kappa(b->kernel, Dp[r] * il2, k0, k1, k2);
-                double c0 = s * k0;
-                for (int i = 0; i < n; ++i) c0 -= Kr[r * n + i] * Cr[(size_t)p * n + i];
-                C[r * M + j] = c0;
-                if (cov) cov[(o + r) * M + j] = (float)c0;
+                C[r * M + j] = col[r];
+                if (cov) cov[(o + r) * M + j] = (float)col[r];
             }
         }
         std::vector<float> sc(R);
         for (size_t r = 0; r < R; ++r) {
-            const double vc = std::max(v[r], 1e-12), sd = std::sqrt(vc + noise);
+            const double vc = std::max(v[r], 1e-12), sd = std::sqrt(vc + st.noise);
             std::vector<std::pair<double, double>> ln;
             for (int j = 0; j < M; ++j)
                 if (ref[j] >= 0 && ref[j] != (int64_t)r) ln.emplace_back(C[r * M + j] / sd, sgn * mu[ref[j]]);
@@ -1248,14 +1270,7 @@ int adkf_kg_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const f
             sc[r] = (mu[r] == mu[r] && v[r] == v[r]) ? (float)kg_value(ln, want_log) : std::numeric_limits<float>::quiet_NaN();   // a NaN row: NaN
             if (score) score[o + r] = sc[r];
         }
-        if (k <= 0) continue;
-        std::vector<int64_t> cand;
-        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
-        for (int64_t r = 0; r < rows; ++r)
-            if (sc[r] == sc[r] && !(xb && std::binary_search(xb, xe, r))) cand.push_back(r);
-        const size_t kk = std::min<size_t>(k, cand.size());
-        std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return sc[a] > sc[c] || (sc[a] == sc[c] && a < c); });
-        for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)t * k + q] = cand[q]; top_val[(size_t)t * k + q] = sc[cand[q]]; }
+        if (k > 0) select_topk(sc, rows, k, excl_range(excl_idx, excl_off, t), top_idx + (size_t)t * k, top_val + (size_t)t * k);
     }
     return 0;
 }
@@ -1270,111 +1285,58 @@ size_t adkf_ipv_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t, int32_t) 
 int adkf_ipv_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const int64_t* tgt_idx, const float* tgt_w,
                   int32_t M, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
                   float* tvar, int32_t* info, void*, size_t, void*, size_t, void*) {
-    if (int rc = check(b, false, true)) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (int rc = check_support_only(b, phi, info, rows, ARD_EITHER)) return rc;
     if (flags) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (!tgt_idx || !sel_idx || !sel_val) return ADKF_E_BADARG;
     if (M < 1 || q < 1) return ADKF_E_BADARG;
     if ((int64_t)M + q > ADKF_IPV_ENTRIES_MAX) return ADKF_E_SIZE;
-    const bool ard = (b->flags & ADKF_BATCH_ARD) != 0;
-    const int d = b->d;
-    const float ninf = -std::numeric_limits<float>::infinity();
 #pragma omp parallel for schedule(dynamic)
     for (int t = 0; t < b->T; ++t) {
-        for (int j = 0; j < q; ++j) { sel_idx[(size_t)t * q + j] = -1; sel_val[(size_t)t * q + j] = ninf; }
+        init_topk(sel_idx, sel_val, t, q);
         if (tvar) std::fill(tvar + (size_t)t * (q + 1), tvar + (size_t)(t + 1) * (q + 1), 0.f);
         if (trace && rows > 0) std::fill(trace + (size_t)t * q * rows, trace + (size_t)(t + 1) * q * rows, 0.f);
-        const int n = std::min(ns_of(b, t), b->ns_max);
-        const size_t R = (size_t)rows;
-        Mat Kr(R * std::max(n, 0)), Cr(R * std::max(n, 0)), v(R), L(R * q);
-        double s = 0.0, noise = 0.0, il2 = 0.0;
-        const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
-            s = in.s; noise = in.noise; il2 = 1.0 / (in.l * in.l);
-            double* k = &Kr[(size_t)r * n];
-            double* c = &Cr[(size_t)r * n];
-            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); k[j] = in.s * k0; }
-            double qf = 0.0;
-            for (int j = 0; j < n; ++j) {
-                double cj = 0.0;
-                for (int i = 0; i < n; ++i) cj += k[i] * in.Ainv[(size_t)i * n + j];
-                c[j] = cj;
-                qf += cj * k[j];
-            }
-            v[r] = in.s - qf;
-        });
-        if (!done) continue;
-        Mat Xl(ard ? R * d : 0);   // ARD: the pool rows over l
-        if (ard) {
-            const float* x0 = phi + (size_t)t * (2 + d);
-            for (size_t r = 0; r < R; ++r) for (int c = 0; c < d; ++c) Xl[r * d + c] = (double)X[r * d + c] / softplus(x0[2 + c]);
-        }
-        // c0(x_r, x_p) for every row r
-        auto c0_col = [&](int64_t p, double* out) {
-            const Mat Dp = ard ? sqdist(Xl.data() + (size_t)p * d, 1, Xl.data(), (int)rows, d) : sqdist(X + (size_t)p * d, 1, X, (int)rows, d);
-            for (size_t r = 0; r < R; ++r) {
-                double k0, k1, k2;
-                kappa(b->kernel, Dp[r] * il2, k0, k1, k2);
-                double c0 = s * k0;
-                for (int i = 0; i < n; ++i) c0 -= Kr[r * n + i] * Cr[(size_t)p * n + i];
-                out[r] = c0;
-            }
-        };
-        // the valid targets: inside the pool, first occurrences, a weight > 0; Ct: cov_j(x_r, target), downdated with the rows
+        PoolState st;
+        if (!pool_state(b, phi, t, X, rows, info, st)) continue;
+        const size_t R = st.R;
+        const Mat& v = st.v;   // (append_pick downdates it)
+        // the valid targets with a weight > 0; Ct: cov_j(x_r, target), downdated with the rows
         std::vector<int64_t> tg;
         std::vector<double> wt;
         for (int m = 0; m < M; ++m) {
-            const int64_t p = tgt_idx[(size_t)t * M + m];
+            const int64_t p = valid_entry(tgt_idx + (size_t)t * M, m, rows);
             const float w = tgt_w ? tgt_w[(size_t)t * M + m] : 1.f;
-            if (p < 0 || p >= rows || !(w > 0.f)) continue;
-            bool first = true;
-            for (int i = 0; i < m && first; ++i) first = tgt_idx[(size_t)t * M + i] != p;
-            if (first) { tg.push_back(p); wt.push_back(w); }
+            if (p >= 0 && w > 0.f) { tg.push_back(p); wt.push_back(w); }
         }
         const size_t nt = tg.size();
         if (nt == 0) continue;
         Mat Ct(nt * R);
-        for (size_t m = 0; m < nt; ++m) c0_col(tg[m], &Ct[m * R]);
+        for (size_t m = 0; m < nt; ++m) c0_col(st, b, X, tg[m], &Ct[m * R]);
         auto total = [&] { double x = 0.0; for (size_t m = 0; m < nt; ++m) x += wt[m] * v[tg[m]]; return x; };
         if (tvar) tvar[(size_t)t * (q + 1)] = (float)total();
-        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
+        const Excl excl = excl_range(excl_idx, excl_off, t);
         std::vector<char> taken(R, 0);
         std::vector<float> score(R);
-        Mat G((size_t)q * q, 0.0), col(R);
+        Mat G((size_t)q * q, 0.0), L(R * q), col(R);
         int c = 0;   // picks made
         for (int j = 0; j < q; ++j) {
-            int64_t p = -1;
             for (int64_t r = 0; r < rows; ++r) {
                 double sum = 0.0;
                 for (size_t m = 0; m < nt; ++m) sum += wt[m] * Ct[m * R + r] * Ct[m * R + r];
-                score[r] = (float)(sum / (std::max(v[r], 1e-12) + noise));
+                score[r] = (float)(sum / (std::max(v[r], 1e-12) + st.noise));
                 if (trace) trace[((size_t)t * q + j) * R + r] = score[r];
-                if (score[r] != score[r] || taken[r] || (xb && std::binary_search(xb, xe, r))) continue;
-                if (p < 0 || score[r] > score[p]) p = r;   // (rows ascend: a tie keeps the lower index)
             }
-            if (p < 0) {   // no eligible row: this step and all later ones keep -1 / -inf, the state stays
-                if (tvar) tvar[(size_t)t * (q + 1) + j + 1] = (float)total();
-                continue;
+            const int64_t p = greedy_pick(score, rows, taken, excl);
+            if (p >= 0) {   // (no eligible row: this step and all later ones keep -1 / -inf, the state stays)
+                sel_idx[(size_t)t * q + j] = p; sel_val[(size_t)t * q + j] = score[p];
+                append_pick(st, b, X, p, c, q, G, L, col);
+                for (size_t m = 0; m < nt; ++m) {   // the targets' ell are the rows' own
+                    const double em = L[(size_t)tg[m] * q + c];
+                    for (size_t r = 0; r < R; ++r) Ct[m * R + r] -= L[r * q + c] * em;
+                }
+                taken[p] = 1;
+                ++c;
             }
-            sel_idx[(size_t)t * q + j] = p; sel_val[(size_t)t * q + j] = score[p];
-            // the new row of G, then column c of ell and the downdates for every row (the picked one and the targets included)
-            for (int l = 0; l < c; ++l) G[(size_t)c * q + l] = L[(size_t)p * q + l];
-            G[(size_t)c * q + c] = std::sqrt(v[p] + noise);
-            c0_col(p, col.data());
-            for (size_t r = 0; r < R; ++r) {
-                double c0 = col[r];
-                for (int l = 0; l < c; ++l) c0 -= G[(size_t)c * q + l] * L[r * q + l];
-                L[r * q + c] = c0 / G[(size_t)c * q + c];
-            }
-            for (size_t m = 0; m < nt; ++m) {
-                const double em = L[(size_t)tg[m] * q + c];
-                for (size_t r = 0; r < R; ++r) Ct[m * R + r] -= L[r * q + c] * em;
-            }
-            for (size_t r = 0; r < R; ++r) v[r] -= L[r * q + c] * L[r * q + c];
-            taken[p] = 1;
-            ++c;
             if (tvar) tvar[(size_t)t * (q + 1) + j + 1] = (float)total();
         }
     }
@@ -1391,56 +1353,30 @@ int adkf_jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
                   const float* opt_val, int32_t S, float cond_noise, const int64_t* excl_idx, const int64_t* excl_off, float* score,
                   float* opt_mean, float* opt_var, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void*, size_t, void*, size_t,
                   void*) {
-    if (int rc = check(b, false, true)) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (int rc = check_support_only(b, phi, info, rows, ARD_EITHER)) return rc;
     if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
     if (!opt_idx || !opt_val) return ADKF_E_BADARG;
     if (!(cond_noise >= 0.f) || !std::isfinite(cond_noise)) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
-    if (k < 0) return ADKF_E_BADARG;
-    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (k == 0 && !score && !opt_mean && !opt_var) return ADKF_E_BADARG;
-    if (S < 1 || S > ADKF_TS_SAMPLES_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
-    const bool ard = (b->flags & ADKF_BATCH_ARD) != 0, maximize = (flags & ADKF_PM_MAXIMIZE) != 0;
-    const int d = b->d;
-    const float ninf = -std::numeric_limits<float>::infinity(), fnan = std::numeric_limits<float>::quiet_NaN();
+    if (int rc = check_topk(k, top_idx, top_val)) return rc;
+    if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
+    const bool maximize = (flags & ADKF_PM_MAXIMIZE) != 0;
+    const float fnan = std::numeric_limits<float>::quiet_NaN();
 #pragma omp parallel for schedule(dynamic)
     for (int t = 0; t < b->T; ++t) {
         const size_t R = (size_t)rows, o = (size_t)t * R;
         if (score) std::fill(score + o, score + o + R, 0.f);
         if (opt_mean) std::fill(opt_mean + (size_t)t * S, opt_mean + (size_t)(t + 1) * S, 0.f);
         if (opt_var) std::fill(opt_var + (size_t)t * S, opt_var + (size_t)(t + 1) * S, 0.f);
-        for (int q = 0; q < k; ++q) { top_idx[(size_t)t * k + q] = -1; top_val[(size_t)t * k + q] = ninf; }
-        const int n = std::min(ns_of(b, t), b->ns_max);
-        Mat Kr(R * std::max(n, 0)), Cr(R * std::max(n, 0)), mu(R), v(R);
-        double s = 0.0, noise = 0.0, il2 = 0.0;
-        const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
-            s = in.s; noise = in.noise; il2 = 1.0 / (in.l * in.l);
-            const float* y = b->y_s + (size_t)t * b->ns_max;
-            double* kr = &Kr[(size_t)r * n];
-            double* c = &Cr[(size_t)r * n];
-            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); kr[j] = in.s * k0; }
-            double m1 = 0.0, qf = 0.0;
-            for (int j = 0; j < n; ++j) {
-                double cj = 0.0;
-                for (int i = 0; i < n; ++i) cj += kr[i] * in.Ainv[(size_t)i * n + j];
-                c[j] = cj;
-                m1 += cj * (double)y[j];
-                qf += cj * kr[j];
-            }
-            mu[r] = m1; v[r] = in.s - qf;
-        });
-        if (!done) continue;
-        Mat Xl(ard ? R * d : 0);   // ARD: the pool rows over l
-        if (ard) {
-            const float* x0 = phi + (size_t)t * (2 + d);
-            for (size_t r = 0; r < R; ++r) for (int c = 0; c < d; ++c) Xl[r * d + c] = (double)X[r * d + c] / softplus(x0[2 + c]);
-        }
+        init_topk(top_idx, top_val, t, k);
+        PoolState st;
+        if (!pool_state(b, phi, t, X, rows, info, st)) continue;
+        const Mat &mu = st.mu, &v = st.v;
+        const double noise = st.noise;
         int s_eff = 0;
         bool bad = false;
-        Mat sum(R, 0.0);
+        Mat sum(R, 0.0), col(R);
         for (int j = 0; j < S; ++j) {
             const int64_t p = opt_idx[(size_t)t * S + j];
             if (p < 0 || p >= rows) continue;
@@ -1450,12 +1386,9 @@ int adkf_jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
             if (opt_mean) opt_mean[(size_t)t * S + j] = (float)mu[p];
             if (opt_var) opt_var[(size_t)t * S + j] = (float)v[p];
             const double dd = std::max(v[p], 1e-12) + (double)cond_noise, gain = (fs - mu[p]) / dd;
-            const Mat Dp = ard ? sqdist(Xl.data() + (size_t)p * d, 1, Xl.data(), (int)rows, d) : sqdist(X + (size_t)p * d, 1, X, (int)rows, d);
+            c0_col(st, b, X, p, col.data());
             for (size_t r = 0; r < R; ++r) {
-                double k0, k1, k2;
-                kappa(b->kernel, Dp[r] * il2, k0, k1, k2);
-                double c0 = s * k0;
-                for (int i = 0; i < n; ++i) c0 -= Kr[r * n + i] * Cr[(size_t)p * n + i];
+                const double c0 = col[r];
                 const double vc = std::max(v[r], 1e-12), vs = std::max(v[r] - c0 * c0 / dd, 1e-12), ms = mu[r] + c0 * gain;
                 const double g = (maximize ? (fs - ms) : (ms - fs)) / std::sqrt(vs);
                 sum[r] += std::log((vc + noise) / (vs + noise)) - gibbon_term(g, vs / (vs + noise));
@@ -1467,14 +1400,7 @@ int adkf_jes_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
             sc[r] = nan ? fnan : (float)(0.5 * sum[r] / s_eff);
             if (score) score[o + r] = sc[r];
         }
-        if (k <= 0) continue;
-        std::vector<int64_t> cand;
-        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
-        for (int64_t r = 0; r < rows; ++r)
-            if (sc[r] == sc[r] && !(xb && std::binary_search(xb, xe, r))) cand.push_back(r);
-        const size_t kk = std::min<size_t>(k, cand.size());
-        std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return sc[a] > sc[c] || (sc[a] == sc[c] && a < c); });
-        for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)t * k + q] = cand[q]; top_val[(size_t)t * k + q] = sc[cand[q]]; }
+        if (k > 0) select_topk(sc, rows, k, excl_range(excl_idx, excl_off, t), top_idx + (size_t)t * k, top_val + (size_t)t * k);
     }
     return 0;
 }
@@ -1487,16 +1413,12 @@ size_t adkf_jackknife_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { r
 int adkf_jackknife_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* alpha, int32_t L,
                         const int64_t* excl_idx, const int64_t* excl_off, float* lo, float* hi, float* loo_mean, float* loo_var, float* loo_lpd,
                         int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void*, size_t, void*, size_t, void*) {
-    if (int rc = check(b, false, true)) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (int rc = check_support_only(b, phi, info, rows, ARD_EITHER)) return rc;
     if (flags & ~(ADKF_PM_MAXIMIZE | ADKF_PM_JK_SCALED)) return ADKF_E_BADARG;
     if (!alpha) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (k == 0 && !lo && !hi && !loo_mean && !loo_var && !loo_lpd) return ADKF_E_BADARG;
-    if (k < 0 || (k > 0 && (!top_idx || !top_val))) return ADKF_E_BADARG;
-    if (k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    if (int rc = check_topk(k, top_idx, top_val)) return rc;
     if (b->ns_max > ADKF_JK_POINTS_MAX || L < 1 || L > ADKF_JK_LEVELS_MAX) return ADKF_E_SIZE;
     const float ninf = -std::numeric_limits<float>::infinity(), pinf = std::numeric_limits<float>::infinity();
     const bool maximize = (flags & ADKF_PM_MAXIMIZE) != 0, scaled = (flags & ADKF_PM_JK_SCALED) != 0;
@@ -1508,7 +1430,7 @@ int adkf_jackknife_pool(const adkf_batch_t* b, const float* phi, int32_t flags, 
         if (loo_mean) std::fill(loo_mean + t * ld, loo_mean + (t + 1) * ld, 0.f);
         if (loo_var) std::fill(loo_var + t * ld, loo_var + (t + 1) * ld, 0.f);
         if (loo_lpd) loo_lpd[t] = 0.f;
-        for (int q = 0; q < k; ++q) { top_idx[(size_t)t * k + q] = -1; top_val[(size_t)t * k + q] = ninf; }
+        init_topk(top_idx, top_val, t, k);
         const float* y = b->y_s + t * ld;
         std::vector<double> g, bii, wd, a, bb, kr, c;
         std::vector<int> rank(L, 0);
@@ -1534,17 +1456,8 @@ int adkf_jackknife_pool(const adkf_batch_t* b, const float* phi, int32_t flags, 
             },
             [&](int64_t r, const Inner& in, const double* D) {
                 const int n = in.n;
-                const double il2 = 1.0 / (in.l * in.l);
-                for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); kr[j] = in.s * k0; }
-                double mu = 0.0, qf = 0.0;
-                for (int j = 0; j < n; ++j) {
-                    double cj = 0.0;
-                    for (int i = 0; i < n; ++i) cj += kr[i] * in.Ainv[(size_t)i * n + j];
-                    c[j] = cj;
-                    mu += cj * (double)y[j];
-                    qf += cj * kr[j];
-                }
-                const double v = in.s - qf;
+                const MuQ p = row_posterior(in, b->kernel, D, y, kr.data(), c.data());
+                const double mu = p.mu, qf = p.q, v = in.s - qf;
                 for (int i = 0; i < n; ++i) {
                     const double mi = mu - c[i] * g[i];
                     const double w = scaled ? wd[i] * std::sqrt(std::max(v + c[i] * c[i] / bii[i], 1e-12) + in.noise) : wd[i];
@@ -1566,14 +1479,7 @@ int adkf_jackknife_pool(const adkf_batch_t* b, const float* phi, int32_t flags, 
                 }
                 sc[r] = std::isinf(s0) ? std::numeric_limits<float>::quiet_NaN() : s0;
             });
-        if (!done || k <= 0) continue;
-        std::vector<int64_t> cand;
-        const int64_t *xb = excl_idx ? excl_idx + excl_off[t] : nullptr, *xe = excl_idx ? excl_idx + excl_off[t + 1] : nullptr;
-        for (int64_t r = 0; r < rows; ++r)
-            if (sc[r] == sc[r] && !(xb && std::binary_search(xb, xe, r))) cand.push_back(r);
-        const size_t kk = std::min<size_t>(k, cand.size());
-        std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t p, int64_t q) { return sc[p] > sc[q] || (sc[p] == sc[q] && p < q); });
-        for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)t * k + q] = cand[q]; top_val[(size_t)t * k + q] = sc[cand[q]]; }
+        if (done && k > 0) select_topk(sc, rows, k, excl_range(excl_idx, excl_off, t), top_idx + (size_t)t * k, top_val + (size_t)t * k);
     }
     return 0;
 }
@@ -1600,42 +1506,30 @@ int adkf_ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const
                    const float* con_thr, const int32_t* con_geq, int32_t C, const int64_t* excl_idx, const int64_t* excl_off, float* score,
                    float* stair, int32_t* stair_n, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void*, size_t, void*, size_t,
                    void*) {
-    if (int rc = check(b, false, true)) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (int rc = check_support_only(b, phi, info, rows, ARD_EITHER)) return rc;
     if (flags & ~ADKF_PM_LOG_EI) return ADKF_E_BADARG;
     if (G < 1 || k < 0) return ADKF_E_BADARG;
     if (P < 0 || P > ADKF_EHVI_FRONT_MAX || C < 0 || C > ADKF_EHVI_CONS_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
     if (!obj || !ref || !front_n) return ADKF_E_BADARG;
     if (P > 0 && !front) return ADKF_E_BADARG;
     if (C > 0 && (!con || !con_thr || !con_geq)) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
-    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
+    if (int rc = check_topk(k, top_idx, top_val)) return rc;   // (the sizes come first here: only the two outputs are left to ask for)
     if (k == 0 && !score && !stair && !stair_n) return ADKF_E_BADARG;
     const bool want_log = (flags & ADKF_PM_LOG_EI) != 0;
     const int T = b->T;
     const size_t R = (size_t)rows;
-    const float ninf = -std::numeric_limits<float>::infinity(), fnan = std::numeric_limits<float>::quiet_NaN();
+    const float fnan = std::numeric_limits<float>::quiet_NaN();
     const double dinf = std::numeric_limits<double>::infinity();
     Mat mu((size_t)T * R), vl((size_t)T * R);
     std::vector<char> done(T, 0);
 #pragma omp parallel for schedule(dynamic)
     for (int t = 0; t < T; ++t) {
         const float* y = b->y_s + (size_t)t * b->ns_max;
+        std::vector<double> kr(b->ns_max);
         done[t] = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
-            const int n = in.n;
-            const double il2 = 1.0 / (in.l * in.l);
-            std::vector<double> kr(n);
-            for (int j = 0; j < n; ++j) { double k0, k1, k2; kappa(b->kernel, D[j] * il2, k0, k1, k2); kr[j] = in.s * k0; }
-            double m1 = 0.0, q = 0.0;
-            for (int j = 0; j < n; ++j) {
-                double cj = 0.0;
-                for (int i = 0; i < n; ++i) cj += kr[i] * in.Ainv[(size_t)i * n + j];
-                m1 += cj * (double)y[j];
-                q += cj * kr[j];
-            }
-            mu[(size_t)t * R + r] = m1; vl[(size_t)t * R + r] = in.s - q;
+            const MuQ p = row_posterior(in, b->kernel, D, y, kr.data(), nullptr);
+            mu[(size_t)t * R + r] = p.mu; vl[(size_t)t * R + r] = in.s - p.q;
         }) ? 1 : 0;
     }
     auto psi = [&](double m, double s, double c, bool lg) {
@@ -1684,7 +1578,7 @@ int adkf_ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const
                 stair[((size_t)g * P + i) * 2] = i < Pg ? sg1 * st[i].first : 0.f;
                 stair[((size_t)g * P + i) * 2 + 1] = i < Pg ? sg2 * st[i].second : 0.f;
             }
-        for (int q = 0; q < k; ++q) { top_idx[(size_t)g * k + q] = -1; top_val[(size_t)g * k + q] = ninf; }
+        init_topk(top_idx, top_val, g, k);
         std::vector<float> sc(R, fnan);
         if (!bad) {
             for (size_t r = 0; r < R; ++r) {
@@ -1731,14 +1625,7 @@ int adkf_ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const
             }
         }
         if (score) std::copy(sc.begin(), sc.end(), score + (size_t)g * R);
-        if (bad || k <= 0) continue;
-        std::vector<int64_t> cand;
-        const int64_t *xb = excl_idx ? excl_idx + excl_off[g] : nullptr, *xe = excl_idx ? excl_idx + excl_off[g + 1] : nullptr;
-        for (int64_t r = 0; r < rows; ++r)
-            if (sc[r] == sc[r] && !(xb && std::binary_search(xb, xe, r))) cand.push_back(r);
-        const size_t kk = std::min<size_t>(k, cand.size());
-        std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return sc[a] > sc[c] || (sc[a] == sc[c] && a < c); });
-        for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)g * k + q] = cand[q]; top_val[(size_t)g * k + q] = sc[cand[q]]; }
+        if (!bad && k > 0) select_topk(sc, rows, k, excl_range(excl_idx, excl_off, g), top_idx + (size_t)g * k, top_val + (size_t)g * k);
     }
     return 0;
 }
@@ -1753,9 +1640,7 @@ int adkf_mix_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
                   const float* w, int32_t M, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, float* mean,
                   float* var, float* score, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void*, size_t, void*, size_t,
                   void*) {
-    if (int rc = check(b, false, true)) return rc;
-    if (b->nq_max != 0 || b->Z_q || b->y_q) return ADKF_E_BADARG;
-    if (!phi || !info || !b->y_s || !b->priors || rows < 0) return ADKF_E_BADARG;
+    if (int rc = check_support_only(b, phi, info, rows, ARD_EITHER)) return rc;
     if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN | ADKF_PM_LOG_EI | ADKF_PM_SCORE_BALD)) return ADKF_E_BADARG;
     const bool by_mean = (flags & ADKF_PM_SCORE_MEAN) != 0, by_bald = (flags & ADKF_PM_SCORE_BALD) != 0, lg = (flags & ADKF_PM_LOG_EI) != 0;
     if ((by_mean && by_bald) || (lg && (by_mean || by_bald))) return ADKF_E_BADARG;
@@ -1763,13 +1648,12 @@ int adkf_mix_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
     if (M > ADKF_MIX_MEMBERS_MAX || k > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
     const bool want_score = score || k > 0, want_e = want_score && !by_mean && !by_bald;
     if (want_e && !best_f) return ADKF_E_BADARG;
-    if (rows > 0 && !X) return ADKF_E_BADARG;
-    if (excl_idx && !excl_off) return ADKF_E_BADARG;
-    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
+    if (int rc = check_topk(k, top_idx, top_val)) return rc;   // (the sizes come first here: only the two outputs are left to ask for)
     if (k == 0 && !mean && !var && !score) return ADKF_E_BADARG;
     const int T = b->T;
     const size_t R = (size_t)rows;
-    const float ninf = -std::numeric_limits<float>::infinity(), fnan = std::numeric_limits<float>::quiet_NaN();
+    const float fnan = std::numeric_limits<float>::quiet_NaN();
     const double dinf = std::numeric_limits<double>::infinity();
     const int pm_flags = flags & (ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI);
     std::vector<float> mu((size_t)T * R), vr((size_t)T * R), ei(want_e ? (size_t)T * R : 0);
@@ -1802,7 +1686,7 @@ int adkf_mix_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
         const int n = (int)ts.size();
         std::vector<double> wt(n);
         for (int i = 0; i < n; ++i) wt[i] = (double)(ws[i] / W);
-        for (int q = 0; q < k; ++q) { top_idx[(size_t)g * k + q] = -1; top_val[(size_t)g * k + q] = ninf; }
+        init_topk(top_idx, top_val, g, k);
         std::vector<float> sc(R, fnan);
         for (size_t r = 0; r < R; ++r) {
             const size_t o = (size_t)g * R + r;
@@ -1835,14 +1719,7 @@ int adkf_mix_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const 
             sc[r] = (float)val;
         }
         if (score) std::copy(sc.begin(), sc.end(), score + (size_t)g * R);
-        if (bad || k <= 0) continue;
-        std::vector<int64_t> cand;
-        const int64_t *xb = excl_idx ? excl_idx + excl_off[g] : nullptr, *xe = excl_idx ? excl_idx + excl_off[g + 1] : nullptr;
-        for (int64_t r = 0; r < rows; ++r)
-            if (sc[r] == sc[r] && !(xb && std::binary_search(xb, xe, r))) cand.push_back(r);
-        const size_t kk = std::min<size_t>(k, cand.size());
-        std::partial_sort(cand.begin(), cand.begin() + kk, cand.end(), [&](int64_t a, int64_t c) { return sc[a] > sc[c] || (sc[a] == sc[c] && a < c); });
-        for (size_t q = 0; q < kk; ++q) { top_idx[(size_t)g * k + q] = cand[q]; top_val[(size_t)g * k + q] = sc[cand[q]]; }
+        if (!bad && k > 0) select_topk(sc, rows, k, excl_range(excl_idx, excl_off, g), top_idx + (size_t)g * k, top_val + (size_t)g * k);
     }
     return 0;
 }

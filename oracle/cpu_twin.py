@@ -1,7 +1,10 @@
 """ctypes/numpy binding of libadkf_gp_cpu.so, the C++ CPU twin of the GP entry points of include/adkf_gp.h
 (adkf_ift_amd/csrc/cpu/adkf_gp_cpu.cpp).  TEST / BASELINE INFRASTRUCTURE ONLY (same import rule as gp_oracle.py): used by
-tests/test_cpu_twin.py and by bench.py's cpu_baseline leg ("kind": "twin").  The product package never imports this module
-and its operators keep refusing CPU tensors."""
+tests/test_cpu_twin.py (the wrappers below: fit, prediction, hypergradient), by bench.py's cpu_baseline leg ("kind": "twin",
+time_tasks), and through build() / load() / CpuBatch by the tests of the streaming and pool entries (tests/test_*_pool_cpu.py,
+tests/test_predict_marginal*_cpu.py, the GPU tests that hold the library against the twin) and by tools/twin_bits.py, which call
+those entries with the prototypes load() binds.  The product package never imports this module and its operators keep refusing
+CPU tensors."""
 from __future__ import annotations
 
 import ctypes as C

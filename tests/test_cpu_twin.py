@@ -1,6 +1,9 @@
-"""CPU: libadkf_gp_cpu.so - the C++ twin of the seven GP entry points of include/adkf_gp.h -
-exports them with the header's signatures and reproduces the golden vectors (float64 autograd oracle) through the same call
-sequence the GPU parity test uses.  It is float64 inside, so it is held to 1e-5 (phi and every output cross the boundary as float32)."""
+"""CPU: libadkf_gp_cpu.so - the C++ twin of the GP entry points of include/adkf_gp.h - exports its
+fit, prediction and hypergradient entries (adkf_median_lengthscale, adkf_init_params, adkf_mll_value_grad, adkf_fit, adkf_predict,
+adkf_outer_nll_value_grad, adkf_ift_hypergrad) with the header's signatures and reproduces the golden vectors (float64 autograd
+oracle) through the same call sequence the GPU parity test uses.  It is float64 inside, so it is held to 1e-5 (phi and every output
+cross the boundary as float32).  The twin's streaming entries (adkf_predict_marginal, its ARD form and the calls over a shared
+pool) are held against float64 references in tests/test_predict_marginal*_cpu.py and tests/test_*_pool_cpu.py."""
 import glob
 import os
 
