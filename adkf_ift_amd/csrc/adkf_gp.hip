@@ -73,9 +73,11 @@ size_t adkf_workspace_bytes_ard(int32_t T, int32_t ns_max, int32_t nq_max, int32
 
 // median heuristic (+ optionally a4 in the same launch); returns true through *fused when init was applied
 static int median_core(const adkf_batch_t* b, const Workspace& w, float* l0, const InitArgs& init, bool* fused, hipStream_t st) {
-    int rc = stage_dist(b, w, has_query(b), st);
+    bool selected = false;
+    int rc = stage_dist(b, w, has_query(b), st, 3, l0, &init, &selected);
     if (rc) return rc;
     *fused = b->ns_max <= 256;
+    if (selected) return 0;   // k_dist_task has written l0 (and phi / priors): no k_median
     if (b->ns_max <= 128) k_median<512, 16><<<grid_for(b->T, 1), 512, 0, st>>>(w.D2ss, b->n_s, b->ns_max, l0, b->T, init);
     else if (b->ns_max <= 256) k_median<1024, 32><<<grid_for(b->T, 1), 1024, 0, st>>>(w.D2ss, b->n_s, b->ns_max, l0, b->T, init);
     else {

@@ -19,9 +19,16 @@
 // also stored as their mirror image.  The MFMA takes the column operand first (d3_multiply's transposed 16 x 16 block: the same products in
 // the same order), so a lane holds four consecutive columns of one row: D2qs and the upper halves go out as 16-byte stores.
 // Waves (wr, wc) = (1, 0), (1, 1) hold the 64 x 64 quadrant below the diagonal of a symmetric block and issue no MFMA for it.
-// Measured and dropped (T = 256, d = 256, this kernel alone, back to back): k_median's 31-step select run on the D2ss values while they are
-// in registers, between the passes (32 held values per lane where k_median holds 16, the fifteen tiles of the busiest SIMD against eight):
-// 65.3 us against 46.6 us without it, i.e. 18.7 us for what k_median does in 19.0 us as a launch of its own.  k_median stays.
+// The median heuristic in the same launch (SELECT instance; adkf_median_lengthscale / adkf_init_params on a batch that takes this path):
+// between the passes, once pass 1's stores are issued, the entries above the diagonal of D2ss go - still in registers, 32 keys per lane,
+// none in the waves (1, 0) and (1, 1) - through median_select.h's histogram select; the histograms (26 368 bytes) lie in the staging
+// buffers, which are free there.  Lane 0 writes l0 and calls init_params_task, as k_median does, and such a step launches no k_median.
+// First tried with k_median's 31-step select on the same registers: 65.3 us against 46.6 us without it, i.e. 18.7 us inside the launch
+// for what k_median did in 19.0 us as a launch of its own - nothing.  Neither select is bound by its barriers: it is bound by its
+// instructions per held key (the 31 steps: four per key and step; the histogram form: a few dozen per key and digit, most of them the
+// tie handling), so four barriers instead of thirty-two bought less than their count suggests.  Measured (MI355X, C2, rocprofv3 trace
+// averages, profiles/dist_fused_kernel_stats{_parent,}.csv): 58.6 us against 43.5 + 19.1 us for k_dist_task and k_median as two
+// launches, i.e. the select costs 15.1 us inside the launch (4.0 us saved).  The C2 step: profiles/dist_fused_bench.json.
 #pragma once
 #include "kernels.h"
 #include "gemm_x3.h"
@@ -35,10 +42,15 @@ struct DistTaskArgs {
     const float *Zs, *Zq, *mean;      // [T, 128, d], [T, 128, d], [T, d] (k_colmean's); 16-byte aligned, d a multiple of 32
     float *D2ss, *D2qs, *D2qq;        // [T, 128, 128] each
     int d, T;
+    float* l0;                        // SELECT instance: [T], sqrt(median / 2) of the task's D2ss
+    InitArgs init;                    // SELECT instance: phi != null -> init_params_task with that l0
 };
+
+static_assert(MedianSelect<MEDIAN_W>::WORDS * (int)sizeof(uint32_t) <= DT_LDS_BYTES, "the select's histograms live in the staging buffers");
 
 extern __shared__ __attribute__((aligned(16))) unsigned short dt_lds[];
 
+template <bool SELECT>   // SELECT: the median heuristic (and a4) on the D2ss values between the passes; without it l0 and init are not read
 __global__ __launch_bounds__(DT_NT) void k_dist_task(DistTaskArgs a) {
     constexpr int MI = 4, MJ = 2, IH = 1;   // IH: row tiles whose fragments are held at once (block_terms)
     int t, tile;
@@ -164,10 +176,9 @@ __global__ __launch_bounds__(DT_NT) void k_dist_task(DistTaskArgs a) {
         v[2] = fmaxf(nx + ny.z - 2.f * acc[2], 0.f); v[3] = fmaxf(nx + ny.w - 2.f * acc[3], 0.f);
     };
     // a symmetric block's 16 x 16 tile (row tile rt, column tile ct): nothing below the diagonal, the diagonal 0, every entry above it
-    // and its mirror image
-    auto store_sym = [&](float* D, const f32x4& acc, const float* nrm, int rt, int ct) __attribute__((always_inline)) {
+    // and its mirror image; v: the lane's four values (those on or below the diagonal included)
+    auto store_sym = [&](float* D, const f32x4& acc, const float* nrm, int rt, int ct, float (&v)[4]) __attribute__((always_inline)) {
         const int gi = rt * 16 + fi, gj0 = ct * 16 + fk * 4;
-        float v[4];
         values(acc, nrm, nrm, gi, gj0, v);
         if (rt < ct) {   // (wave-uniform)
             *reinterpret_cast<float4*>(D + (size_t)gi * DT_N + gj0) = make_float4(v[0], v[1], v[2], v[3]);
@@ -217,6 +228,8 @@ __global__ __launch_bounds__(DT_NT) void k_dist_task(DistTaskArgs a) {
             if ((tid & 7) == 0) { rowsq[0][sr + ps * 64] = s; rowsq[1][sr + ps * 64] = q; }
         }
         __syncthreads();
+        // the select's keys: the entries above the diagonal of D2ss, as k_median takes them from memory (0: not a candidate)
+        uint32_t key[SELECT ? MI * MJ * 4 : 1];
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -225,8 +238,20 @@ __global__ __launch_bounds__(DT_NT) void k_dist_task(DistTaskArgs a) {
                 float v[4];
                 values(acc_q[i][j] + small_q[i][j], rowsq[1], rowsq[0], rt * 16 + fi, ct * 16 + fk * 4, v);
                 *reinterpret_cast<float4*>(Dqs + (size_t)(rt * 16 + fi) * DT_N + ct * 16 + fk * 4) = make_float4(v[0], v[1], v[2], v[3]);
-                if (rt <= ct) store_sym(Dss, acc_s[i][j] + small_s[i][j], rowsq[0], rt, ct);
+                if (rt <= ct) store_sym(Dss, acc_s[i][j] + small_s[i][j], rowsq[0], rt, ct, v);
+                if constexpr (SELECT) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        key[(i * MJ + j) * 4 + r] = (rt <= ct && rt * 16 + fi < ct * 16 + fk * 4 + r) ? __float_as_uint(v[r]) : 0u;
+                }
             }
+        // The staging buffers are free between the passes (every wave is past the barrier that follows its last multiply) and hold the
+        // histograms; the stores above drain under the select.  The barrier behind it keeps pass 2's staging off the last scan.
+        if constexpr (SELECT) {
+            const uint32_t bits = median_select<DT_NT, MI * MJ * 4, MEDIAN_W>(key, reinterpret_cast<uint32_t*>(dt_lds));
+            __syncthreads();
+            if (tid == 0) median_finish(a.init, t, a.l0, bits);   // (behind the barrier: the other waves do not wait for its logarithms)
+        }
     }
 
     // ---- pass 2: D2qq (Z_q alone, from L2) ----
@@ -246,7 +271,8 @@ __global__ __launch_bounds__(DT_NT) void k_dist_task(DistTaskArgs a) {
 #pragma unroll
             for (int j = 0; j < MJ; ++j) {
                 const int rt = wr * 4 + i, ct = wc * 2 + j;
-                if (rt <= ct) store_sym(Dqq, acc_g[i][j] + small_g[i][j], rowsq[1], rt, ct);
+                float v[4];
+                if (rt <= ct) store_sym(Dqq, acc_g[i][j] + small_g[i][j], rowsq[1], rt, ct, v);
             }
     }
 }

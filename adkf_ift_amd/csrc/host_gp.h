@@ -115,25 +115,33 @@ inline bool is_ard(const adkf_batch_t* b) { return (b->flags & ADKF_BATCH_ARD) !
 // 4 = the features are already centred and w.mean holds zeros (ARD: Z~ = (Z - mu) / l has zero column mean by construction).
 // (The squared row norms are summed inside the distance GEMM while it stages its operands: no separate pass.)
 //
-// Fast path (dist_task.h: one workgroup per task, every row loaded, centred and split once; bit-identical to the generic launch): a FULL
+// Fast path (dist_task.h: one workgroup per task, every row loaded, centred and split once; bit-identical to the generic launch; for
+// adkf_median_lengthscale / adkf_init_params the median select and the initialisation ride in the same launch): a FULL
 // batch of 128 support and 128 query points - parts == 3 with a query set, ns_max == nq_max == 128, no n_s and no n_q, d a multiple of
 // the K chunk (which implies x3_for(d)), 16-byte loads legal (vec_ok), the LDS opt-in granted, no REUSE_DIST.  Every other batch
 // (ragged, other sizes, support only, ARD's parts bits, other d, misaligned Z) keeps the generic launch.
 bool use_dist_task(const adkf_batch_t* b, const Workspace& w, bool with_query, int parts) {
-    static const bool optin = lds_optin(DT_LDS_BYTES, {kernel_ptr(&k_dist_task)});
+    static const bool optin = lds_optin(DT_LDS_BYTES, {kernel_ptr(&k_dist_task<false>), kernel_ptr(&k_dist_task<true>)});
     // (d <= 2^22: the kernel's 32-bit byte offsets inside a task's block of 64 rows)
     return optin && parts == 3 && with_query && b->ns_max == DT_N && b->nq_max == DT_N && !b->n_s && !b->n_q && (b->d % GK) == 0 &&
            b->d <= (1 << 22) && vec_ok(b, w);
 }
 
-int stage_dist(const adkf_batch_t* b, const Workspace& w, bool with_query, hipStream_t st, int parts = 3) {
+// l0 / init / selected (median_core): the median heuristic the caller wants next.  The fast path runs it inside its launch (l0[t], and
+// init_params_task when init->phi is set) and says so through *selected; every other way out leaves it to k_median.
+int stage_dist(const adkf_batch_t* b, const Workspace& w, bool with_query, hipStream_t st, int parts = 3, float* l0 = nullptr,
+               const InitArgs* init = nullptr, bool* selected = nullptr) {
+    if (selected) *selected = false;
     if (b->flags & ADKF_BATCH_REUSE_DIST) return 0;
     const int T = b->T, ns = b->ns_max, nq = with_query ? b->nq_max : 0, d = b->d;
     if (!(parts & 2)) with_query = false;
     if ((parts & 1) && !(parts & 4)) k_colmean<<<dim3(ceil_div(d, 64), T), 256, 0, st>>>(b->Z_s, b->n_s, ns, d, w.mean, T);
     if (use_dist_task(b, w, with_query, parts)) {
-        k_dist_task<<<grid_for(T, 1), DT_NT, DT_LDS_BYTES, st>>>(DistTaskArgs{b->Z_s, b->Z_q, w.mean, w.D2ss, w.D2qs, w.D2qq, d, T});
+        const DistTaskArgs a{b->Z_s, b->Z_q, w.mean, w.D2ss, w.D2qs, w.D2qq, d, T, l0, init ? *init : InitArgs{0, 0, nullptr, nullptr}};
+        if (l0 && selected) k_dist_task<true><<<grid_for(T, 1), DT_NT, DT_LDS_BYTES, st>>>(a);
+        else k_dist_task<false><<<grid_for(T, 1), DT_NT, DT_LDS_BYTES, st>>>(a);
         LAUNCH_OK();
+        if (l0 && selected) *selected = true;
         return 0;
     }
     ProbDist p;

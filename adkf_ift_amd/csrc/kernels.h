@@ -2,6 +2,7 @@
 #pragma once
 #include "problems.h"
 #include "inner.h"
+#include "median_select.h"
 
 namespace adkf {
 
@@ -165,28 +166,33 @@ __global__ void k_init_params(const float* l0, int T, InitArgs a) {
     if (t < T) init_params_task(a, t, l0[t]);
 }
 
-// ---- K10: median heuristic.  Exact lower median of the positive strict-upper-triangle entries by a
-// 31-step radix select on the float bit patterns (positive floats order like their bits). ---------------
-// One workgroup per task; the candidates are loaded ONCE into registers, every radix step is then one compare per held
-// value whose wave-wide count is the population count of the compare mask (a scalar instruction, no lane shuffles) and ONE
-// barrier for the cross-wave sum (partials alternate between two LDS rows).  Only the strict upper triangle is held:
+// ---- K10: median heuristic.  Exact lower median of the positive strict-upper-triangle entries by the histogram
+// radix select of median_select.h on the float bit patterns (positive floats order like their bits). ---------------
+// One workgroup per task; the candidates are loaded ONCE into registers.  Only the strict upper triangle is held:
 // rows i and n-1-i are folded into one row of n-1 candidates, so ceil(n/2) (n-1) slots cover all n (n-1) / 2 pairs.
+constexpr int MEDIAN_W = 11;   // digit width of the select: 11 + 11 + 9 bits at most
+
+// l0 = sqrt(median / 2) from the select's bit pattern (0: no positive candidate), and a4 in the same launch when asked for
+__device__ __forceinline__ void median_finish(const InitArgs& init, int t, float* l0, uint32_t bits) {
+    const float l = sqrtf(0.5f * __uint_as_float(bits));
+    l0[t] = l;
+    if (init.phi) init_params_task(init, t, l);
+}
+
 template <int NT, int EPT>  // NT * EPT >= ceil(ld / 2) * (ld - 1): <512, 16> up to 128 points, <1024, 32> up to 256
 __global__ __launch_bounds__(NT) void k_median(const float* D2ss, const int32_t* n_s, int ld, float* l0, int T, InitArgs init) {
-    constexpr int NW = NT / 64;
-    __shared__ int red[2][NW];
+    __shared__ __attribute__((aligned(16))) uint32_t sel[MedianSelect<MEDIAN_W>::WORDS];
     int t, tile;
     if (!task_tile(T, 1, t, tile)) return;
     const int n = n_s ? n_s[t] : ld;
     const uint32_t* D = reinterpret_cast<const uint32_t*>(D2ss + (size_t)t * ld * ld);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     if (n <= 1 || n > ld) {   // an empty, single-point (or corrupt) task: no candidates
-        if (tid == 0) { l0[t] = 0.f; if (init.phi) init_params_task(init, t, 0.f); }
+        if (tid == 0) median_finish(init, t, l0, 0u);
         return;
     }
     const int nm1 = n - 1, slots = ((n + 1) >> 1) * nm1;
     uint32_t v[EPT];
-    int nonzero = 0;   // wave-uniform
 #pragma unroll
     for (int r = 0; r < EPT; ++r) {
         const int e = r * NT + tid;
@@ -198,36 +204,9 @@ __global__ __launch_bounds__(NT) void k_median(const float* D2ss, const int32_t*
         uint32_t val = D[(size_t)i * ld + j];
         if (!(e < slots && (c < top || top != fr))) val = 0u;          // odd n: the middle row is folded onto itself
         v[r] = val;
-        nonzero += __popcll(__ballot(val != 0u));
     }
-    const int zeros = EPT * 64 - nonzero;
-    if (lane == 0) red[0][wv] = nonzero;
-    __syncthreads();
-    int total = 0;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) total += red[0][i];
-    if (total == 0) { if (tid == 0) { l0[t] = 0.f; if (init.phi) init_params_task(init, t, 0.f); } return; }
-    int rank = (total - 1) / 2;  // torch.median: lower median
-    uint32_t prefix = 0;
-    int buf = 1;
-    for (int bit = 30; bit >= 0; --bit, buf ^= 1) {
-        const uint32_t hi_mask = ~((1u << bit) - 1u);  // bits >= bit
-        int c0 = 0;
-#pragma unroll
-        for (int r = 0; r < EPT; ++r) c0 += __popcll(__ballot((v[r] & hi_mask) == prefix));  // prefix matches, this bit = 0
-        if (prefix == 0u) c0 -= zeros;   // the non-candidates match the all-zero prefix
-        if (lane == 0) red[buf][wv] = c0;
-        __syncthreads();   // one barrier per step: row `buf` was last read two steps ago, before the previous barrier
-        c0 = 0;
-#pragma unroll
-        for (int i = 0; i < NW; ++i) c0 += red[buf][i];
-        if (rank >= c0) { rank -= c0; prefix |= (1u << bit); }
-    }
-    if (tid == 0) {
-        const float l = sqrtf(0.5f * __uint_as_float(prefix));
-        l0[t] = l;
-        if (init.phi) init_params_task(init, t, l);   // a4 in the same launch
-    }
+    const uint32_t bits = median_select<NT, EPT, MEDIAN_W>(v, sel);
+    if (tid == 0) median_finish(init, t, l0, bits);
 }
 
 // ---- Stage C: beta = G alpha, gamma = Ainv alpha, delta = Ainv beta, traces, 3x3 Hessian ------------------
