@@ -626,7 +626,11 @@ __device__ __forceinline__ void refine64_task(const Refine64Args& a) {
                 for (int i = 0; i < 3; ++i)
                     for (int j = 0; j < 3; ++j) sc[S_H0 + i * 3 + j] = (float)((h[i][j] * d1[i] * d1[j] + (i == j ? gt[i] * d2[i] : 0.0)) / fn);
             }
-            if (badA && a.info[t] == 0) a.info[t] = badA;
+            // Everything the caller gets for a flagged task comes from this path, so its info[] is this path's verdict alone.  (The
+            // float32 sweeps of a matrix they cannot resolve may have met a non-positive pivot - seen beyond 128 support points at
+            // cond(A) ~ 1e4: pivot 132 of A, pivots 1 .. 13 of a Sigma_q built on the float32 A^-1 - and that code used to stay in
+            // info[] next to float64 results good to 1e-6; tests/test_gpu_float64_path.py.)  Sigma_q's verdict is added below.
+            a.info[t] = badA;
         }
     }
     __syncthreads();

@@ -31,7 +31,9 @@
  *   - return value: 0 = enqueued, < 0 = rejected argument (ADKF_E_*).  Numerical failure is reported
  *     per task in the device array info[T]: 0 = ok, k > 0 = the k-th pivot of a Cholesky factorisation was
  *     not positive (the reference's NotPSDError after jitter retries; this library never adds jitter),
- *     with ADKF_INFO_OUTER_BASE added when it was the N_q x N_q predictive covariance.
+ *     with ADKF_INFO_OUTER_BASE added when it was the N_q x N_q predictive covariance.  For a task the call
+ *     sent through the float64 path (ill-conditioned: DESIGN.md section 3.5) info[] is the verdict of the float64
+ *     factorisations, which produced everything the call returns for it - not of the float32 sweeps before them.
  *     adkf_check_info() synchronises and folds info[] into one status (index+1 of the first bad task).
  */
 #ifndef ADKF_GP_H
