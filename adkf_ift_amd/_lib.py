@@ -33,6 +33,8 @@ JK_LEVELS_MAX = 8        # ... levels per call
 MIX_CHUNK_ROWS = 16384   # ... pool rows per chunk of its walk
 TS_SAMPLES_MAX = 64      # adkf_thompson_pool: posterior draws per task
 TS_FEATURES_MAX = 4096   # ... random Fourier features (a multiple of 64, at least 64)
+QEI_SAMPLES_MAX = 256    # adkf_qei_pool: posterior draws per task
+QEI_PICKS_MAX = 64       # ... picks per task
 
 ERRORS = {-1: "bad argument", -2: "unsupported size (see adkf_max_points)", -3: "workspace too small",
           -4: "HIP launch failed"}
@@ -89,6 +91,10 @@ SIGNATURES = {
     "adkf_thompson_pool_ard": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adkf_qei_pool_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "adkf_qei_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_believer_pool_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
     "adkf_believer_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -12,6 +12,9 @@ batched fit and one ``adkf_predict_pool`` call per iteration, which returns each
 and each function picks its own best candidate - a diverse batch of ``query_batch_size > 1`` picks from one pass, with no
 ``best_f`` and nothing that can underflow.  Both EI loops take ``acquisition="log_ei"``: the same candidates ranked by log EI
 (``ADKF_PM_LOG_EI``), which stays finite where float32 EI is 0 on the whole pool and the ``"ei"`` loops fall back to random picks.
+``run_gp_qei_bo_batched`` is the loop under Monte-Carlo q-EI: one batched fit and one ``adkf_qei_pool`` call per iteration, which scores
+the ``query_batch_size`` picks jointly over pathwise posterior draws and, by default, against each draw's own best value at the
+queried points (noisy q-EI) instead of the best observed label.
 ``run_gp_mes_bo_batched`` is the loop under max-value entropy search: one batched fit, one ``gp_ops.max_value_samples`` call (the
 minima of pathwise posterior draws over the whole pool) and one ``adkf_mes_pool`` call per iteration, with no ``best_f`` in the score.
 ``run_gp_kg_bo_batched`` is the loop under the knowledge gradient for correlated beliefs: one batched fit, one mean top-``n_refs`` call
@@ -373,6 +376,46 @@ def run_gp_ts_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
                 pick += rng.choice(free(queried[r] + pick), size=query_batch_size - len(pick), replace=False).tolist()
             queried[r] = list(set(queried[r] + pick))
             records[r].extend(pick)
+    return records
+
+
+@torch.no_grad()
+def run_gp_qei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
+                          kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
+                          rngs: List[np.random.Generator], n_samples: int = 128, n_features: int = 1024, noisy: bool = True,
+                          feature_seed: int = 0, ard: bool = False) -> List[List[int]]:
+    """``len(rngs)`` replicates of a Monte-Carlo q-EI BO loop over the same pool at once (minimisation, as ``run_gp_ei_bo``); returns
+    their records: the best initial index, then the picks in pick order.  Per iteration the replicates' queried sets are fitted by ONE
+    ``gp_ops.fit`` (as ``run_gp_ei_bo_batched``) and ONE ``gp_ops.qei_pool`` call picks each replicate's ``query_batch_size`` (at most
+    64) rows jointly: sequential-greedy q-EI by a sample average over ``n_samples`` (at most 256) pathwise posterior draws on a
+    random-Fourier basis of ``n_features`` features (drawn once from ``feature_seed``), among the rows the replicate has not queried.
+    ``noisy`` (the default): noisy q-EI - the incumbent of every draw is its own best value over the replicate's queried points, so a
+    lucky measurement does not set the bar; otherwise the incumbent is the best observed label.  A pick counts while its score is
+    positive (a prefix: the scores of a call never increase); the rest are random free rows from the replicate's generator.  The
+    draws of replicate r come from a torch generator seeded from ``rngs[r]`` (``_pathwise_draws``): a replicate's record does not
+    depend on which other replicates share the batch.  ``ard``: as ``run_gp_ts_bo_batched``; the call is the same."""
+    n = x_all.shape[0]
+    if not 1 <= query_batch_size <= gp_ops._lib.QEI_PICKS_MAX:
+        raise ValueError(f"query_batch_size must be in [1, {gp_ops._lib.QEI_PICKS_MAX}], got {query_batch_size}")
+    if not 1 <= n_samples <= gp_ops._lib.QEI_SAMPLES_MAX:
+        raise ValueError(f"n_samples must be in [1, {gp_ops._lib.QEI_SAMPLES_MAX}], got {n_samples}")
+    y_all, X, queried = _bo_start(x_all, y_all, num_init_points, init_from, rngs)
+    omega, phase = gp_ops.rff_basis(kernel_type, X.shape[1], n_features, generator=torch.Generator().manual_seed(int(feature_seed)),
+                                    device=X.device)
+    records = [[min(q)] for q in queried]
+    gens = _path_generators(rngs)
+
+    for _ in range(num_bo_iters):
+        b, phi = _fit_tasks("run_gp_qei_bo_batched", x_all, [(q, y_all) for q in queried], X, kernel_type, device, noise_init, noise_prior,
+                            ard)
+        w, eps = _pathwise_draws(gens, n_samples, n_features, queried, X.device)
+        best_f = None if noisy else torch.tensor([y_all[q].min().item() for q in queried], dtype=torch.float32, device=X.device)
+        out = gp_ops.qei_pool(b, phi, X, omega=omega, phase=phase, n_samples=n_samples, q=query_batch_size, best_f=best_f, w=w, eps=eps,
+                              maximize=False, exclude=queried)
+        gp_ops.check_info(out["info"], "BO posterior")
+        top_idx, top_val = out["sel_idx"].cpu(), out["sel_val"].cpu()
+        usable = ((top_val > 0) & (top_idx >= 0)).long().cumprod(1).bool()
+        _take_picks(top_idx, usable, query_batch_size, rngs, queried, records, n)
     return records
 
 

@@ -36,6 +36,7 @@
 #include "jackknife_stream.h"
 #include "ehvi_stream.h"
 #include "mix_stream.h"
+#include "qei_stream.h"
 
 #include "host_common.h"
 #include "host_gp.h"
@@ -261,6 +262,20 @@ int adkf_thompson_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flag
                            void* scratch, size_t scratch_bytes, void* stream) {
     return thompson_pool(true, b, phi, flags, X, rows, omega, phase, m, w, eps, S, excl_idx, excl_off, paths, sel_idx, sel_val, info, ws,
                          ws_bytes, scratch, scratch_bytes, stream);
+}
+
+size_t adkf_qei_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t S, int32_t m) {
+    if (T <= 0 || ns_max <= 0 || ns_max > MAX_POINTS || S < 1 || S > ADKF_QEI_SAMPLES_MAX) return 0;
+    if (m < 64 || m > ADKF_TS_FEATURES_MAX || (m & 63)) return 0;
+    return qe_scratch(nullptr, T, ns_max, S).bytes;
+}
+
+int adkf_qei_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega, const float* phase,
+                  int32_t m, const float* w, const float* eps, int32_t S, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off,
+                  int32_t q, float* trace, float* inc, int64_t* sel_idx, float* sel_val, int32_t* info, void* ws, size_t ws_bytes,
+                  void* scratch, size_t scratch_bytes, void* stream) {
+    return qei_pool(b, phi, flags, X, rows, omega, phase, m, w, eps, S, best_f, excl_idx, excl_off, q, trace, inc, sel_idx, sel_val, info, ws,
+                    ws_bytes, scratch, scratch_bytes, stream);
 }
 
 size_t adkf_believer_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t q) {

@@ -480,7 +480,7 @@ bool pm_task(const adkf_batch_t* b, const float* phi, int t, const float* Zq, in
 //   init_topk, select_topk             predict_pool, mes, kg, jes, jackknife, ehvi and mix (per group); init_topk also the sel_* fills
 //   greedy_pick, append_pick           believer / gibbon (step j) and ipv (pick c)
 //   valid_entry                        kg (references) and ipv (targets)
-//   prepare_task, task_row_dist        pm_task_state and thompson_pool
+//   prepare_task, task_row_dist        pm_task_state and PathDraws (thompson_pool, qei_pool)
 enum { ARD_EITHER = -1 };   // check_support_only's ard_mode; 0 / 1: the batch must not / must be an ARD batch
 int check_support_only(const adkf_batch_t* b, const float* phi, const int32_t* info, int64_t rows, int ard_mode) {
     if (int rc = check(b, false, ard_mode != 0)) return rc;
@@ -993,6 +993,48 @@ int adkf_gumbel_pool(const adkf_batch_t* b, const float* phi, int32_t flags, con
     return 0;
 }
 
+// The pathwise posterior draws of a prepared task (prepare_task with_mean), for adkf_thompson_pool(_ard) and adkf_qei_pool: the features
+// phi_j(x) = sqrt(2 s / m) cos(omega_j . ((x - mean) / l_dim) / l + phase_j), the prior draws g_q = w_q . phi, r = y - g(Z_s) - sqrt(noise) eps
+// and v = A^-1 r (V [S, n]).  row(x) prepares the features and the kernel row of x; value(q) is then f_q(x) = g_q(x) + k(x, Z_s) . v_q.
+struct PathDraws {
+    const TaskPrep& tp;
+    const Inner& in;
+    const float *omega, *phase, *wt;
+    int kind, d, m, S, n;
+    double amp, sigma;
+    std::vector<double> ft, k;
+    Mat V;
+    PathDraws(const adkf_batch_t* b, int t, const TaskPrep& tp_, const float* omega_, const float* phase_, int m_, const float* w, const float* eps, int S_)
+        : tp(tp_), in(tp_.in), omega(omega_), phase(phase_), wt(w + (size_t)t * S_ * m_), kind(b->kernel), d(b->d), m(m_), S(S_), n(tp_.n),
+          amp(std::sqrt(2.0 * tp_.in.s / m_)), sigma(std::sqrt(tp_.in.noise)), ft(m_), k(tp_.n), V((size_t)S_ * tp_.n) {
+        const int ld = b->ns_max;
+        const float* Zs = b->Z_s + (size_t)t * ld * d;
+        const float* ys = b->y_s + (size_t)t * ld;
+        Mat R((size_t)S * n);
+        for (int i = 0; i < n; ++i) {
+            features(Zs + (size_t)i * d);
+            for (int q = 0; q < S; ++q) R[(size_t)q * n + i] = (double)ys[i] - prior(q) - sigma * (double)eps[((size_t)t * S + q) * ld + i];
+        }
+        for (int q = 0; q < S; ++q)
+            for (int i = 0; i < n; ++i) {
+                double v = 0.0;
+                for (int kk = 0; kk < n; ++kk) v += in.Ainv[(size_t)i * n + kk] * R[(size_t)q * n + kk];
+                V[(size_t)q * n + i] = v;
+            }
+    }
+    void features(const float* x) {   // phi_j(x), j < m
+        for (int j = 0; j < m; ++j) {
+            double a = 0.0;
+            const float* om = omega + (size_t)j * d;
+            for (int c = 0; c < d; ++c) a += (double)om[c] * (((double)x[c] - tp.mean[c]) / tp.l[c]);
+            ft[j] = amp * std::cos(a / in.l + (double)phase[j]);
+        }
+    }
+    double prior(int q) const { double g = 0.0; const float* wq = wt + (size_t)q * m; for (int j = 0; j < m; ++j) g += (double)wq[j] * ft[j]; return g; }
+    void row(const float* x) { features(x); row_k(in, kind, task_row_dist(tp, x, d).data(), k.data()); }
+    double value(int q) const { double f = prior(q); for (int j = 0; j < n; ++j) f += k[j] * V[(size_t)q * n + j]; return f; }
+};
+
 size_t adkf_thompson_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { return 0; }
 
 // Thompson sampling over a shared pool (include/adkf_gp.h): the pathwise posterior draws in float64, rounded to float32 at the
@@ -1008,7 +1050,7 @@ static int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int3
     if (!omega || !phase || !w || !eps || !sel_idx || !sel_val) return ADKF_E_BADARG;
     if (S < 1 || S > ADKF_TS_SAMPLES_MAX) return ADKF_E_SIZE;
     if (m < 64 || m > ADKF_TS_FEATURES_MAX || (m & 63)) return ADKF_E_SIZE;
-    const int d = b->d, ld = b->ns_max;
+    const int d = b->d;
     const float ninf = -std::numeric_limits<float>::infinity();
 #pragma omp parallel for schedule(dynamic)
     for (int t = 0; t < b->T; ++t) {
@@ -1016,46 +1058,15 @@ static int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int3
         if (paths && rows > 0) std::fill(paths + (size_t)t * S * rows, paths + (size_t)(t + 1) * S * rows, 0.f);
         TaskPrep tp;
         if (!prepare_task(b, phi, t, true, info, tp)) continue;
-        const Inner& in = tp.in;
-        const int n = tp.n;
-        const float* Zs = b->Z_s + (size_t)t * ld * d;
-        const float* ys = b->y_s + (size_t)t * ld;
-        const double amp = std::sqrt(2.0 * in.s / m), sigma = std::sqrt(in.noise);
-        std::vector<double> ft(m);
-        auto features = [&](const float* x) {   // phi_j(x), j < m
-            for (int j = 0; j < m; ++j) {
-                double a = 0.0;
-                const float* om = omega + (size_t)j * d;
-                for (int c = 0; c < d; ++c) a += (double)om[c] * (((double)x[c] - tp.mean[c]) / tp.l[c]);
-                ft[j] = amp * std::cos(a / in.l + (double)phase[j]);
-            }
-        };
-        auto prior = [&](int q) { double g = 0.0; const float* wq = w + ((size_t)t * S + q) * m; for (int j = 0; j < m; ++j) g += (double)wq[j] * ft[j]; return g; };
-        // r = y - g(Z_s) - sqrt(noise) eps, v = A^-1 r: V [S, n]
-        Mat R((size_t)S * n), V((size_t)S * n);
-        for (int i = 0; i < n; ++i) {
-            features(Zs + (size_t)i * d);
-            for (int q = 0; q < S; ++q) R[(size_t)q * n + i] = (double)ys[i] - prior(q) - sigma * (double)eps[((size_t)t * S + q) * ld + i];
-        }
-        for (int q = 0; q < S; ++q)
-            for (int i = 0; i < n; ++i) {
-                double v = 0.0;
-                for (int k = 0; k < n; ++k) v += in.Ainv[(size_t)i * n + k] * R[(size_t)q * n + k];
-                V[(size_t)q * n + i] = v;
-            }
+        PathDraws pd(b, t, tp, omega, phase, m, w, eps, S);
         std::vector<float> bv(S, ninf);
         std::vector<int64_t> bi(S, -1);
         const Excl excl = excl_range(excl_idx, excl_off, t);
-        std::vector<double> k(n);
         for (int64_t r = 0; r < rows; ++r) {
-            const float* x = X + (size_t)r * d;
-            features(x);
-            row_k(in, b->kernel, task_row_dist(tp, x, d).data(), k.data());
+            pd.row(X + (size_t)r * d);
             const bool excluded = excl.has(r);
             for (int q = 0; q < S; ++q) {
-                double f = prior(q);
-                for (int j = 0; j < n; ++j) f += k[j] * V[(size_t)q * n + j];
-                const float ff = (float)f, sc = (flags & ADKF_PM_MAXIMIZE) ? ff : -ff;
+                const float ff = (float)pd.value(q), sc = (flags & ADKF_PM_MAXIMIZE) ? ff : -ff;
                 if (paths) paths[((size_t)t * S + q) * rows + r] = ff;
                 if (sc == sc && !excluded && (bi[q] < 0 || sc > bv[q])) { bv[q] = sc; bi[q] = r; }   // (rows ascend: a tie keeps the lower index)
             }
@@ -1077,6 +1088,75 @@ int adkf_thompson_pool_ard(const adkf_batch_t* b, const float* phi, int32_t flag
                            const int64_t* excl_off, float* paths, int64_t* sel_idx, float* sel_val, int32_t* info, void*, size_t, void*, size_t,
                            void*) {
     return thompson_pool(true, b, phi, flags, X, rows, omega, phase, m, w, eps, S, excl_idx, excl_off, paths, sel_idx, sel_val, info);
+}
+
+size_t adkf_qei_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { return 0; }
+
+// Monte-Carlo (noisy) q-EI over a shared pool (include/adkf_gp.h), for either kind of batch: Thompson's paths (PathDraws) in float64,
+// rounded to float32 at the boundary as adkf_thompson_pool's paths are; the incumbents are float32 values; a row's score is the float64
+// sum of its clipped differences, divided by S and rounded once; the selection is greedy_pick's.  The noisy incumbent is taken as the
+// header states it: y_i - sqrt(noise) eps_(s,i) - noise v_(s,i).
+int adkf_qei_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega, const float* phase,
+                  int32_t m, const float* w, const float* eps, int32_t S, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off,
+                  int32_t q, float* trace, float* inc, int64_t* sel_idx, float* sel_val, int32_t* info, void*, size_t, void*, size_t, void*) {
+    if (int rc = check_support_only(b, phi, info, rows, ARD_EITHER)) return rc;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
+    if (!omega || !phase || !w || !eps || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (S < 1 || S > ADKF_QEI_SAMPLES_MAX) return ADKF_E_SIZE;
+    if (m < 64 || m > ADKF_TS_FEATURES_MAX || (m & 63)) return ADKF_E_SIZE;
+    if (q < 1 || q > ADKF_QEI_PICKS_MAX) return ADKF_E_SIZE;
+    const int d = b->d, ld = b->ns_max;
+    const bool mx = (flags & ADKF_PM_MAXIMIZE) != 0;
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        init_topk(sel_idx, sel_val, t, q);
+        if (trace && rows > 0) std::fill(trace + (size_t)t * q * rows, trace + (size_t)(t + 1) * q * rows, 0.f);
+        float* inct = inc ? inc + (size_t)t * (q + 1) * S : nullptr;
+        if (inct) std::fill(inct, inct + (size_t)(q + 1) * S, best_f ? best_f[t] : 0.f);
+        TaskPrep tp;
+        if (!prepare_task(b, phi, t, true, info, tp)) continue;
+        PathDraws pd(b, t, tp, omega, phase, m, w, eps, S);
+        const int n = tp.n;
+        const size_t R = (size_t)rows;
+        std::vector<float> F((size_t)S * R), bs(S), score(R);
+        for (size_t r = 0; r < R; ++r) {
+            pd.row(X + r * d);
+            for (int s = 0; s < S; ++s) F[(size_t)s * R + r] = (float)pd.value(s);
+        }
+        const float* ys = b->y_s + (size_t)t * ld;
+        for (int s = 0; s < S; ++s) {
+            if (best_f) { bs[s] = best_f[t]; continue; }
+            double best = 0.0;
+            for (int i = 0; i < n; ++i) {
+                const double f = (double)ys[i] - pd.sigma * (double)eps[((size_t)t * S + s) * ld + i] - tp.in.noise * pd.V[(size_t)s * n + i];
+                best = i == 0 ? f : (mx ? std::max(best, f) : std::min(best, f));
+            }
+            bs[s] = (float)best;
+        }
+        if (inct) std::copy(bs.begin(), bs.end(), inct);
+        const Excl excl = excl_range(excl_idx, excl_off, t);
+        std::vector<char> taken(R, 0);
+        for (int j = 0; j < q; ++j) {
+            for (size_t r = 0; r < R; ++r) {
+                double sum = 0.0;
+                for (int s = 0; s < S; ++s) {
+                    const double imp = mx ? (double)F[(size_t)s * R + r] - (double)bs[s] : (double)bs[s] - (double)F[(size_t)s * R + r];
+                    sum += imp < 0.0 ? 0.0 : imp;   // (NaN stays NaN)
+                }
+                score[r] = (float)(sum / S);
+                if (trace) trace[((size_t)t * q + j) * R + r] = score[r];
+            }
+            const int64_t p = greedy_pick(score, rows, taken, excl);
+            if (p >= 0) {   // (no eligible row: this step and all later ones keep -1 / -inf, the state stays)
+                sel_idx[(size_t)t * q + j] = p; sel_val[(size_t)t * q + j] = score[p];
+                taken[p] = 1;
+                for (int s = 0; s < S; ++s) bs[s] = mx ? std::max(bs[s], F[(size_t)s * R + p]) : std::min(bs[s], F[(size_t)s * R + p]);
+            }
+            if (inct) std::copy(bs.begin(), bs.end(), inct + (size_t)(j + 1) * S);
+        }
+    }
+    return 0;
 }
 
 size_t adkf_believer_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { return 0; }

@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ipv_pool, adkf_jackknife_pool, adkf_ehvi_pool and adkf_mix_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ipv_pool, adkf_jackknife_pool, adkf_ehvi_pool, adkf_mix_pool and adkf_qei_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
 // pool calls share (pool_walks, pool_select, pool_greedy) and the body of every entry.
 #pragma once
 #include "host_ard.h"
@@ -433,6 +433,96 @@ int thompson_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
     // skipped tasks keep zeros in paths
     if (paths && rows > 0) hipMemsetAsync(paths, 0, sizeof(float) * (size_t)T * S * (size_t)rows, st);
     return ard ? ts_launch<true>(c, ta, rows) : ts_launch<false>(c, ta, rows);
+}
+
+// adkf_qei_pool: the scratch is Thompson's V [T, S, ns] (and its float64 twin where the workspace of this shape can have a float64
+// region), the incumbents b [T, S], a pick count per task, one (row, score) pair per (task, chunk) and that candidate's S path values
+struct QeScratch { float* v; double* v64; float* b; int32_t* cnt; CandLists cand; float* slots; size_t bytes; };
+static_assert(QE_S_MAX == ADKF_QEI_SAMPLES_MAX && QE_Q_MAX == ADKF_QEI_PICKS_MAX && QE_NB_MAX == 4, "qei_stream.h limits");
+inline QeScratch qe_scratch(void* base, int T, int ns, int S) {
+    Arena ar{static_cast<char*>(base), 0};
+    const size_t e = (size_t)T * S * ns, c = (size_t)T * pm_pool_chunks_max(T);
+    QeScratch l{};
+    l.v = ar.floats(e);
+    l.v64 = ar.as<double>(ns <= R64_MAXN ? e : 0);
+    l.b = ar.floats((size_t)T * S);
+    l.cnt = ar.as<int32_t>((size_t)T);
+    l.cand = carve_cand(ar, c);
+    l.slots = ar.floats(c * S);
+    l.bytes = ar.off;
+    return l;
+}
+
+// The launches of a prepared q-EI call: Thompson's residual and solve once, the state, then q x (the walks, the step).  The walks are
+// Thompson's (one persistent walk over the plain and the refined tasks, the float64 kernel for the flagged ones), which is why the
+// loop is written here and is not pool_greedy's, whose walks are prediction's.
+template <bool ARD, int NB>
+int qe_launch(const PmCtx& c, QeArgs& v, int64_t rows) {
+    hipStream_t st = c.st;
+    const int T = c.b.T, ns = c.b.ns_max, S = v.S;
+    auto args = [&] {
+        QeArgsOf<ARD> k{};
+        static_cast<QeArgs&>(k) = v;
+        if constexpr (ARD) k.r = c.r;
+        return k;
+    };
+    // (with or without rows: the noisy incumbents, inc row 0, come out of v)
+    k_ts_resid<false, ARD><<<dim3(ns, T), 256, 0, st>>>(v);
+    if (v.V64) k_ts_resid<true, ARD><<<dim3(ns, T), 256, 0, st>>>(v);
+    k_ts_solve<false><<<dim3(S, T), 256, 0, st>>>(v);
+    if (v.V64) k_ts_solve<true><<<dim3(S, T), 256, 0, st>>>(v);
+    if (rows > 0) {
+        if constexpr (ARD) launch_ard_il(c);
+        v.s.grid[0] = pm_persistent_grid(k_qei_stream<ARD, NB>, PM_NT, 0, ((rows + PM_TM - 1) / PM_TM) * T);
+        v.s.grid[2] = v.V64 ? std::min(pm64_grid(rows), v.s.chunks_max) : 0;
+    }
+    k_qei_init<<<T, 256, 0, st>>>(v);
+    for (int j = 0; j < v.q; ++j) {
+        v.j = j;
+        if (rows > 0) {
+            k_qei_stream<ARD, NB><<<v.s.grid[0], PM_NT, 0, st>>>(args());
+            if (v.V64) k_qei_stream64<ARD><<<dim3(v.s.grid[2], T), PM64_NT, 0, st>>>(args());
+        }
+        k_qei_step<<<T, 256, 0, st>>>(v);
+    }
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_qei_pool: isotropic and ARD batches alike (as adkf_mes_pool)
+int qei_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega, const float* phase,
+             int32_t m, const float* w, const float* eps, int32_t S, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off,
+             int32_t q, float* trace, float* inc, int64_t* sel_idx, float* sel_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch,
+             size_t scratch_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
+    if (!omega || !phase || !w || !eps || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (S < 1 || S > ADKF_QEI_SAMPLES_MAX) return ADKF_E_SIZE;
+    if (m < 64 || m > ADKF_TS_FEATURES_MAX || (m & 63)) return ADKF_E_SIZE;
+    if (q < 1 || q > ADKF_QEI_PICKS_MAX) return ADKF_E_SIZE;
+    const QeScratch l = qe_scratch(scratch, b->T, b->ns_max, S);
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    hipStream_t st = c.st;
+    const int T = b->T;
+    QeArgs v{};
+    v.p = pm_args(c, flags, X, rows, info);
+    v.s = pm_pool(excl_idx, excl_off, 1, T, l.cand.idx, l.cand.val, rows, st);
+    v.omega = omega; v.phase = phase; v.w = w; v.eps = eps; v.m = m; v.S = S;
+    v.vec_om = ((b->d & 3) == 0 && aligned16(omega)) ? 1 : 0;
+    v.V = l.v;
+    v.V64 = pm_have64(c, v.p) ? l.v64 : nullptr;
+    v.q = q; v.b = l.b; v.cnt = l.cnt; v.slots = l.slots; v.best_f = best_f;
+    v.trace = trace; v.inc = inc; v.sel_idx = sel_idx; v.sel_val = sel_val;
+    // skipped tasks keep zeros in trace
+    if (trace && rows > 0) hipMemsetAsync(trace, 0, sizeof(float) * (size_t)T * q * (size_t)rows, st);
+    const int nb = S <= TS_S_MAX ? 1 : (S <= 2 * TS_S_MAX ? 2 : 4);
+    if (c.ard) return nb == 1 ? qe_launch<true, 1>(c, v, rows) : (nb == 2 ? qe_launch<true, 2>(c, v, rows) : qe_launch<true, 4>(c, v, rows));
+    return nb == 1 ? qe_launch<false, 1>(c, v, rows) : (nb == 2 ? qe_launch<false, 2>(c, v, rows) : qe_launch<false, 4>(c, v, rows));
 }
 
 // adkf_believer_pool: the scratch is w [T, q, ns] (and its float64 twin where a workspace of this shape can have a float64 region),

@@ -39,6 +39,8 @@
 // promoting to float64 (the rule of k_predict_marginal64<true>).  k_ts_solve and k_ts_merge are the isotropic instances: the scaled batch's
 // scalars and D2ss are those of the unit-lengthscale pipeline that built A^-1 (scal[S_LS] = softplus(RAW_ONE) = 1, ard.h).
 //
+// Shared with qei_stream.h (adkf_qei_pool): k_ts_resid, k_ts_solve and the tile itself (ts_tile, with NB sample blocks of 64; k_ts_stream is
+// its NB = 1 instance, bit for bit what it was before the tile was a function).
 // Shared with believer_stream.h: pm_solve_refined, the float32 solve with its refinement step (k_ts_solve<false> copies v to V, k_bv_step
 // to W and goes on with it).
 #pragma once
@@ -208,6 +210,103 @@ __device__ __forceinline__ void ts_stage(float* Bp, const float* src, size_t ld,
     }
 }
 
+// ---- the [64 rows, 64 NB samples] tile of draws of task t at the pool rows r0 .. r0 + mr, for k_ts_stream (NB = 1) and k_qei_stream
+// (qei_stream.h; NB sample blocks of 64): F[bk] is this wave's 32 x 32 quarter of block bk, samples 64 bk .. 64 bk + 63.  The feature
+// product, the cosine panel and the K panel are computed once per feature chunk / support panel; per block only the B panel (W, then
+// V) is staged and multiplied.  What a sample gets does not depend on S, NB or its block: block bk, column s is the tile of NB = 1 on
+// the draws of sample 64 bk + s alone, bit for bit.  ril (ARD): the task's 1 / l.  All 256 threads; the LDS arrays are the caller's
+// (As, Bs: pm_mm's staging buffers; Pp, Bp: [64, TS_LDP] panels), free when it returns (behind a barrier).  The tile comes back in Fout.
+template <bool ARD, int NB>
+__device__ __forceinline__ void ts_tile(const TsArgs& args, const float* ril, int t, int64_t r0, int mr, float* As, float* Bs, float* Pp, float* Bp,
+                                        float (&rowsq)[2][PM_TM], f32x4 (&Fout)[NB][2][2]) {
+    const PmArgs& a = args.p;
+    const int S = args.S;
+    const int64_t d = a.d;
+    const int n = pm_ns(a, t);
+    const float* sc = a.scal + (size_t)t * NSCAL;
+    const float os = sc[S_OS], il2 = 1.f / (sc[S_LS] * sc[S_LS]), amp = sqrtf(2.f * os / (float)args.m);
+    [[maybe_unused]] const float il = 1.f / sc[S_LS];   // (isotropic: the scaling of the cosine's argument)
+    const float* Zs = a.Zs + (size_t)t * a.ns_ld * d;
+    const float* mu = a.mean_s + (size_t)t * d;
+    const int np = (n + PM_TM - 1) / PM_TM;
+    // the accumulators are locals, handed over once at the end: accumulated through the reference, the tile is moved between the
+    // accumulator and the vector registers around every product
+    f32x4 acc[2][2], F[NB][2][2];
+#pragma unroll
+    for (int bk = 0; bk < NB; ++bk)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) F[bk][i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // the centred (ARD: and scaled) pool rows of the tile, for the feature part (by reference, once per tile: the functor
+    // itself held across the feature loop costs 22 VGPRs)
+    auto fx = [&](int i, int k, float (&v)[4]) { pm_query_rows<ARD>(a, mu, ril, r0, mr)(i, k, v); };
+    float dummy[2];
+    // ---- feature part: F = sqrt(2 s / m) cos((X - mu) Omega^T / l + phase) W^T (ARD: X~ Omega^T + phase)
+    for (int j0 = 0; j0 < args.m; j0 += PM_TM) {
+        pm_mm<false>(acc, a.d, As, Bs, fx,
+            [&](int j, int k, float (&v)[4]) { pm_ld4(args.omega + (size_t)(j0 + j) * d, k, a.d, args.vec_om, v); }, dummy, dummy);
+        ts_stage(Bp, args.w + (size_t)t * S * args.m, args.m, S, j0, args.m);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int jj = pm_col(j);
+            const float ph = args.phase[j0 + jj];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int ii = pm_row(i, r);
+                    float arg;
+                    if constexpr (ARD) arg = acc[i][j][r] + ph;
+                    else arg = fmaf(acc[i][j][r], il, ph);
+                    Pp[ii * TS_LDP + jj] = ii < mr ? amp * ts_cos(arg) : 0.f;
+                }
+        }
+        __syncthreads();
+        ts_mm(F[0], Pp, Bp, S);
+        __syncthreads();
+#pragma unroll
+        for (int bk = 1; bk < NB; ++bk)
+            if (bk * TS_S_MAX < S) {   // (uniform) the same cosine panel against the next block of W
+                ts_stage(Bp, args.w + ((size_t)t * S + bk * TS_S_MAX) * args.m, args.m, S - bk * TS_S_MAX, j0, args.m);
+                __syncthreads();
+                ts_mm(F[bk], Pp, Bp, S - bk * TS_S_MAX);
+                __syncthreads();
+            }
+    }
+    // ---- update part: F += K V^T; the V panel is staged while the norms of the K panel are on their way
+    for (int p = 0; p < np; ++p) {
+        const int j0 = p * PM_TM;
+        pm_k_panel<ARD>(a, Zs, mu, ril, r0, mr, n, j0, os, il2, As, Bs, rowsq, acc, Pp, TS_LDP,
+                          [&] { ts_stage(Bp, args.V + (size_t)t * S * a.ns_ld, a.ns_ld, S, j0, n); });
+        ts_mm(F[0], Pp, Bp, S);
+        __syncthreads();
+#pragma unroll
+        for (int bk = 1; bk < NB; ++bk)
+            if (bk * TS_S_MAX < S) {   // (uniform) the same K panel against the next block of V
+                ts_stage(Bp, args.V + ((size_t)t * S + bk * TS_S_MAX) * a.ns_ld, a.ns_ld, S - bk * TS_S_MAX, j0, n);
+                __syncthreads();
+                ts_mm(F[bk], Pp, Bp, S - bk * TS_S_MAX);
+                __syncthreads();
+            }
+    }
+#pragma unroll
+    for (int bk = 0; bk < NB; ++bk)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) Fout[bk][i][j] = F[bk][i][j];
+}
+// one block of the tile as [sample][row] into an LDS panel (the caller publishes it)
+__device__ __forceinline__ void ts_tile_to_lds(float* Pp, const f32x4 (&F)[2][2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Pp[pm_col(j) * TS_LDP + pm_row(i, r)] = F[i][j][r];
+}
+
 template <bool ARD = false>
 __global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgsOf<ARD> args) {
     const PmArgs& a = args.p;
@@ -216,7 +315,6 @@ __global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgsOf<ARD> args) {
     __shared__ float rowsq[2][PM_TM];
     const int tid = threadIdx.x, wv = tid >> 6;
     const int S = args.S;
-    const int64_t d = a.d;
     PmPoolWalk<TS_KINDS32> walk;   // first wave, lane q: (walk.lv, walk.li) is the best (score, row) of sample q in this walk
     if (!walk.start(a, args.s)) return;
     for (;;) {
@@ -224,63 +322,12 @@ __global__ __launch_bounds__(PM_NT) void k_ts_stream(TsArgsOf<ARD> args) {
         int64_t r0;
         if (!walk.next(a, args.s, S, t, r0)) return;
         const int mr = (int)(a.rows - r0 < PM_TM ? a.rows - r0 : PM_TM);
-        const int n = pm_ns(a, t);
-        const float* sc = a.scal + (size_t)t * NSCAL;
-        const float os = sc[S_OS], il2 = 1.f / (sc[S_LS] * sc[S_LS]), amp = sqrtf(2.f * os / (float)args.m);
-        [[maybe_unused]] const float il = 1.f / sc[S_LS];   // (isotropic: the scaling of the cosine's argument)
-        const float* Zs = a.Zs + (size_t)t * a.ns_ld * d;
-        const float* mu = a.mean_s + (size_t)t * d;
         const float* ril = nullptr;                         // ARD: 1 / l per dimension, applied while the pool rows are staged
-        if constexpr (ARD) ril = args.r.il + (size_t)t * d;
-        const int np = (n + PM_TM - 1) / PM_TM;
-        f32x4 acc[2][2], F[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) F[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // the centred (ARD: and scaled) pool rows of the tile, for the feature part (by reference, once per tile: the functor
-        // itself held across the feature loop costs 22 VGPRs)
-        auto fx = [&](int i, int k, float (&v)[4]) { pm_query_rows<ARD>(a, mu, ril, r0, mr)(i, k, v); };
-        float dummy[2];
-        // ---- feature part: F = sqrt(2 s / m) cos((X - mu) Omega^T / l + phase) W^T (ARD: X~ Omega^T + phase)
-        for (int j0 = 0; j0 < args.m; j0 += PM_TM) {
-            pm_mm<false>(acc, a.d, As, Bs, fx,
-                [&](int j, int k, float (&v)[4]) { pm_ld4(args.omega + (size_t)(j0 + j) * d, k, a.d, args.vec_om, v); }, dummy, dummy);
-            ts_stage(Bp, args.w + (size_t)t * S * args.m, args.m, S, j0, args.m);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int jj = pm_col(j);
-                const float ph = args.phase[j0 + jj];
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int ii = pm_row(i, r);
-                        float arg;
-                        if constexpr (ARD) arg = acc[i][j][r] + ph;
-                        else arg = fmaf(acc[i][j][r], il, ph);
-                        Pp[ii * TS_LDP + jj] = ii < mr ? amp * ts_cos(arg) : 0.f;
-                    }
-            }
-            __syncthreads();
-            ts_mm(F, Pp, Bp, S);
-            __syncthreads();
-        }
-        // ---- update part: F += K V^T; the V panel is staged while the norms of the K panel are on their way
-        for (int p = 0; p < np; ++p) {
-            const int j0 = p * PM_TM;
-            pm_k_panel<ARD>(a, Zs, mu, ril, r0, mr, n, j0, os, il2, As, Bs, rowsq, acc, Pp, TS_LDP,
-                              [&] { ts_stage(Bp, args.V + (size_t)t * S * a.ns_ld, a.ns_ld, S, j0, n); });
-            ts_mm(F, Pp, Bp, S);
-            __syncthreads();
-        }
+        if constexpr (ARD) ril = args.r.il + (size_t)t * a.d;
+        f32x4 F[1][2][2];
+        ts_tile<ARD, 1>(args, ril, t, r0, mr, As, Bs, Pp, Bp, rowsq, F);
         // ---- epilogue: the tile as [sample][row] through LDS
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) Pp[pm_col(j) * TS_LDP + pm_row(i, r)] = F[i][j][r];
+        ts_tile_to_lds(Pp, F[0]);
         __syncthreads();
         if (args.paths)
             for (int e = tid; e < S * PM_TM; e += PM_NT) {

@@ -534,17 +534,10 @@ def rff_basis(kernel, d: int, m: int, generator: Optional[torch.Generator] = Non
     return omega.contiguous(), phase.contiguous()
 
 
-def _thompson_pool(name: str, b: GPBatch, phi, X, omega, phase, n_samples, generator, w, eps, maximize, exclude, want_paths):
-    """The body of ``thompson_pool`` (``name = "thompson_pool"``, isotropic batches) and ``thompson_pool_ard`` (ARD batches)."""
-    lib = _lib.load()
-    ard = name == "thompson_pool_ard"
-    _support_only(b, name)
-    if b.ard and not ard:
-        raise ValueError("thompson_pool does not support ARD batches: use thompson_pool_ard")
-    if ard and not b.ard:
-        raise ValueError("thompson_pool_ard takes an ARD batch (GPBatch(..., ard=True)): use thompson_pool")
-    S = _in_range(n_samples, 1, _lib.TS_SAMPLES_MAX, "n_samples")
-    phi, X = _phi_and_pool(b, phi, X)
+def _basis_and_draws(b, omega, phase, S: int, generator, w, eps):
+    """The basis and the standard normal draws of the pathwise calls (``thompson_pool``, ``qei_pool``), checked:
+    ``(omega [m, d], phase [m], m, w [T, S, m], eps [T, S, ns])``; ``w`` / ``eps`` are drawn from ``generator`` (on its device) where
+    they are not given, ``w`` first."""
     omega, phase = _f32(omega, "omega"), _f32(phase, "phase")
     if omega.dim() != 2 or omega.shape[1] != b.d:
         raise ValueError(f"omega must be [m, d] = [m, {b.d}], got {tuple(omega.shape)}")
@@ -565,6 +558,21 @@ def _thompson_pool(name: str, b: GPBatch, phi, X, omega, phase, n_samples, gener
 
     w = draw(w, (b.T, S, m), "w")
     eps = draw(eps, (b.T, S, b.ns), "eps")
+    return omega, phase, m, w, eps
+
+
+def _thompson_pool(name: str, b: GPBatch, phi, X, omega, phase, n_samples, generator, w, eps, maximize, exclude, want_paths):
+    """The body of ``thompson_pool`` (``name = "thompson_pool"``, isotropic batches) and ``thompson_pool_ard`` (ARD batches)."""
+    lib = _lib.load()
+    ard = name == "thompson_pool_ard"
+    _support_only(b, name)
+    if b.ard and not ard:
+        raise ValueError("thompson_pool does not support ARD batches: use thompson_pool_ard")
+    if ard and not b.ard:
+        raise ValueError("thompson_pool_ard takes an ARD batch (GPBatch(..., ard=True)): use thompson_pool")
+    S = _in_range(n_samples, 1, _lib.TS_SAMPLES_MAX, "n_samples")
+    phi, X = _phi_and_pool(b, phi, X)
+    omega, phase, m, w, eps = _basis_and_draws(b, omega, phase, S, generator, w, eps)
     rows = X.shape[0]
     excl_idx, excl_off = _exclusion(b, exclude, b.T, rows)
     _on_device(b, X=X, omega=omega, phase=phase, w=w, eps=eps)
@@ -597,6 +605,43 @@ def thompson_pool_ard(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: 
     (``rff_basis``), shared by all tasks; arguments and the returned dict are those of ``thompson_pool``.  Raises ``ValueError``
     for a batch that is not an ARD batch."""
     return _thompson_pool("thompson_pool_ard", b, phi, X, omega, phase, n_samples, generator, w, eps, maximize, exclude, want_paths)
+
+
+def qei_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, omega: torch.Tensor, phase: torch.Tensor, n_samples: int, q: int,
+             best_f: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, w: Optional[torch.Tensor] = None,
+             eps: Optional[torch.Tensor] = None, maximize: bool = False, exclude=None, want_trace: bool = False, want_inc: bool = False):
+    """Monte-Carlo q-EI over the shared pool ``X [rows, d]`` in one ``adkf_qei_pool`` call, for isotropic and ARD batches alike: every
+    task of the support-only batch ``b`` draws ``n_samples`` (at most 256) pathwise posterior functions - ``thompson_pool``'s, on the
+    same basis ``(omega [m, d], phase [m])`` and draws - and picks ``q`` (at most 64) rows by sequential-greedy maximisation of the
+    sample average of the joint improvement ``max(0, incumbent_s - min_j f_s(x_j))`` (``maximize``: the mirror image).  Without
+    ``best_f`` the incumbent of path s is its own best value over the task's support rows (noisy q-EI, BoTorch's
+    ``qNoisyExpectedImprovement``); with ``best_f [T]`` it is that value for every path (``qExpectedImprovement``).  Returns
+    ``dict(sel_idx [T, q] int64, sel_val [T, q], trace [T, q, rows] or None, inc [T, q + 1, S] or None, info [T], w, eps)``:
+    ``sel_val`` the score of each pick at the step it was picked - their sum is the MC q-EI of the batch - and -1 / -inf from the step
+    at which no eligible row was left; ``trace`` (``want_trace``) every row's score at every step; ``inc`` (``want_inc``) the
+    incumbents before step 0 and after every step.  ``w`` / ``eps`` as in ``thompson_pool``; ``exclude``: rows a task may not select
+    (``pack_exclude``)."""
+    lib = _lib.load()
+    _support_only(b, "qei_pool")
+    S = _in_range(n_samples, 1, _lib.QEI_SAMPLES_MAX, "n_samples")
+    q = _in_range(q, 1, _lib.QEI_PICKS_MAX, "q")
+    phi, X = _phi_and_pool(b, phi, X)
+    omega, phase, m, w, eps = _basis_and_draws(b, omega, phase, S, generator, w, eps)
+    if best_f is not None:
+        best_f = _f32(best_f, "best_f").reshape(-1)
+        if best_f.numel() != b.T:
+            raise ValueError(f"best_f must have T = {b.T} entries")
+    rows = X.shape[0]
+    excl_idx, excl_off = _exclusion(b, exclude, b.T, rows)
+    _on_device(b, X=X, omega=omega, phase=phase, w=w, eps=eps, best_f=best_f)
+    sel_idx, sel_val, info = _selection(b, b.T, q)
+    trace = _new(b, b.T, q, rows) if want_trace else None
+    inc = _new(b, b.T, q + 1, S) if want_inc else None
+    args = (ptr(omega), ptr(phase), m, ptr(w), ptr(eps), S, ptr(best_f), ptr(excl_idx), ptr(excl_off), q, ptr(trace), ptr(inc),
+            ptr(sel_idx), ptr(sel_val))
+    _pool_call(lib, "adkf_qei_pool", b, phi, _lib.PM_MAXIMIZE if maximize else 0, X, args, info,
+               lib.adkf_qei_pool_scratch_bytes(b.T, b.ns, S, m))
+    return dict(sel_idx=sel_idx, sel_val=sel_val, trace=trace, inc=inc, info=info, w=w, eps=eps)
 
 
 def mes_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, ystar: torch.Tensor, maximize: bool = False, topk: int = 0,

@@ -772,6 +772,36 @@ int adkf_ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const
 size_t adkf_mix_pool_scratch_bytes(int32_t T, int32_t G, int32_t k);
 int adkf_mix_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, int32_t G, const int32_t* mem, const float* w, int32_t M, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, float* mean, float* var, float* score, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Monte-Carlo q-EI and noisy q-EI over a shared pool: a batch of q rows per task, chosen by sequential-greedy maximisation of the
+ * sample-average joint improvement over S pathwise posterior draws (Wilson, Hutter and Deisenroth 2018, "Maximizing acquisition
+ * functions for Bayesian optimization"; Balandat et al. 2020, BoTorch; the noisy incumbent of Letham et al. 2019, "Constrained
+ * Bayesian optimization with noisy experiments").  Replaces BoTorch's qNoisyExpectedImprovement (best_f NULL) or
+ * qExpectedImprovement (best_f given) under optimize_acqf_discrete's sequential greedy with fixed base samples.
+ *
+ * Isotropic and ARD batches alike (ADKF_BATCH_ARD, as adkf_mes_pool); the batch is support-only.  All per task t, with the
+ * paths f_s of adkf_thompson_pool on the same arguments (omega [m, d], phase [m], w [T, S, m], eps [T, S, ns_max]; m under
+ * Thompson's limits, 1 <= S <= ADKF_QEI_SAMPLES_MAX), so the call is a deterministic function of its arguments:
+ *     f_s(x) = g_s(x) + k(x, Z_s) v_s,  v_s = A^-1 r_s,  r_s = y - g_s(Z_s) - sqrt(noise) eps_s
+ * Minimisation by default: imp_s(x) = b_s - f_s(x) and incumbents move by min; ADKF_PM_MAXIMIZE (the only flag accepted) flips both.
+ *   incumbent   best_f NULL:  b_s^0 = min_(i < n_s[t]) f_s(z_i), the best value of path s over the task's own support rows, taken as
+ *               y_i - sqrt(noise) eps_(s,i) - noise v_(s,i) (A v = r and K_ss = A - noise I: no further product);
+ *               best_f [T]:   b_s^0 = best_f[t] for every s.
+ *   step j      score_j(x) = (1 / S) sum_s max(0, imp_s^j(x)); the pick p_j is the eligible row of largest score, equal scores by
+ *               the lower row index; eligible: not in the task's exclusion list (excl_idx / excl_off as adkf_predict_pool) and not an
+ *               earlier pick; NaN scores are never selected.  Then b_s^(j+1) = min(b_s^j, f_s(p_j)).  With no eligible row the step
+ *               reports -1 / -inf, leaves the state unchanged, and every later step does the same (adkf_believer_pool's rule).
+ * Hence score_(j+1)(x) <= score_j(x) for every row, and sum_j score_j(p_j) = (1 / S) sum_s (b_s^0 - b_s^q), the MC q-EI of the batch.
+ * Outputs: sel_idx, sel_val [T, q] (1 <= q <= ADKF_QEI_PICKS_MAX); inc [T, q + 1, S] (nullable): the incumbents b_s^j, row 0 the
+ * starting ones; trace [T, q, rows] (nullable): every row's score at every step (zeros for skipped tasks).  With trace and inc
+ * NULL nothing of size T x rows exists; the scratch does not depend on rows: V [T, S, ns_max] (and its float64 twin where the
+ * workspace of this shape can have a float64 region), the incumbents [T, S], a pick count per task, and per (task, chunk) one
+ * candidate: (row, score) and that row's S path values.  Flags other than ADKF_PM_MAXIMIZE: BADARG; S, m or q out of range: SIZE
+ * (adkf_qei_pool_scratch_bytes returns 0 for them); a short scratch: WORKSPACE; a misaligned one: BADARG. */
+#define ADKF_QEI_SAMPLES_MAX 256
+#define ADKF_QEI_PICKS_MAX 64
+size_t adkf_qei_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t S, int32_t m);
+int adkf_qei_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* omega, const float* phase, int32_t m, const float* w, const float* eps, int32_t S, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, float* inc, int64_t* sel_idx, float* sel_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* a8 (training branch) = f_outer (fs_mol/models/adaptive_dkt.py:183-191): joint predictive NLL of the query
  * set, with gradients: f_out [T], g_phi [T,3] (nullable), dZ_s, dZ_q (nullable). */
 int adkf_outer_nll_value_grad(const adkf_batch_t* b, const float* phi, float* f_out, float* g_phi, float* dZ_s,

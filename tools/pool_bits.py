@@ -1,6 +1,7 @@
 """Bitwise comparison of the pool calls between two builds of the library (a refactoring must return the other build's bits).
 
-    python tools/pool_bits.py dump OUT.pt        in each of the two trees (each with its own built library), on the GPU
+    python tools/pool_bits.py dump OUT.pt        in each of the two trees (each with its own built library), on the GPU; or twice in one
+                                                 tree, once with ADKF_LIB naming the other build of the library
     python tools/pool_bits.py compare A.pt B.pt  exit status 1 and the names of the arrays that differ, if any
 
 dump runs, on the problems of the GPU tests (tests/test_gpu_believer_pool._explicit: plain at 48 points, refined at 200, global slots
@@ -11,8 +12,9 @@ believer_pool_ard, kg_pool with KG and with log KG (score, cov, ref_mean and the
 mean, a -1 and a repetition among them), and ehvi_pool on the problems of tests/test_gpu_ehvi_pool.py's score test (score, staircase
 and selection, linear and log, with and without the constraints); on each of the six problems also mes_pool and jes_pool (score and k = 8; the optima of
 jes_pool at the first eight reference rows of kg_pool, their -1 and their repetition included), gumbel_pool on fixed uniforms and
-thompson_pool / thompson_pool_ard (m = 64 features and four paths from seeded generators, with the paths) - and saves every returned
-tensor.  Then the records of the six batched BO loops of adkf_ift_amd.bayes_opt, as int64 tensors under records/: a generated pool of
+thompson_pool / thompson_pool_ard (m = 64 features and four paths from seeded generators, with the paths; also 64 paths on 128 features and
+37 on 256, minimising and maximising) and qei_pool (the 64-feature basis, 80 paths in two sample blocks, four noisy picks, with trace
+and incumbents; skipped where ADKF_LIB names a build without the entry) - and saves every returned tensor.  Then the records of the six batched BO loops of adkf_ift_amd.bayes_opt, as int64 tensors under records/: a generated pool of
 400 rows in 6 dimensions, 4 initial points, batches of 2, 2 iterations, 3 replicates, 64 features, fixed seeds; the EI loop also with
 batch="believer" and with ard=True, the MES loop also with max_value="gumbel" and with batch="gibbon".  compare looks at the arrays both
 files have, so a tree can be held against one from before a call existed.  All lists are full (pools of 130 to 333 rows), so the
@@ -25,6 +27,21 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+def _bind_what_the_library_has(entry):
+    """ADKF_LIB may name a build of the library from before an entry existed (the way a refactoring is held against its parent commit
+    from one tree): the entries that build does not export leave the binding table before the library is loaded, and dump skips
+    their calls.  Returns whether `entry` is there."""
+    import ctypes
+
+    import torch  # noqa: F401  (before the library, as _lib.load has it)
+
+    from adkf_ift_amd import _lib
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in [n for n in _lib.SIGNATURES if not hasattr(lib, n)]:
+        del _lib.SIGNATURES[name]
+    return entry in _lib.SIGNATURES
+
+
 def dump(path):
     import torch
 
@@ -35,6 +52,7 @@ def dump(path):
 
     dev = torch.device("cuda:0")
     out = {}
+    have_qei = _bind_what_the_library_has("adkf_qei_pool")
 
     def put(tag, o):
         for k, v in o.items():
@@ -56,6 +74,14 @@ def dump(path):
         omega, phase = gp_ops.rff_basis(b.kernel, b.d, 64, generator=torch.Generator().manual_seed(11), device=dev)
         draw = gp_ops.thompson_pool_ard if b.ard else gp_ops.thompson_pool
         put(f"thompson/{tag}", draw(b, phi, X, omega=omega, phase=phase, n_samples=4, generator=torch.Generator().manual_seed(12), want_paths=True))
+        for S, m in ((64, 128), (37, 256)):   # a full and a partial sample block, more features, both senses
+            om, ph = gp_ops.rff_basis(b.kernel, b.d, m, generator=torch.Generator().manual_seed(11), device=dev)
+            for mx in (False, True):
+                put(f"thompson/{tag}/S={S}/m={m}/maximize={mx}", draw(b, phi, X, omega=om, phase=ph, n_samples=S, maximize=mx,
+                                                                  generator=torch.Generator().manual_seed(12), want_paths=True))
+        if have_qei:
+            put(f"qei/{tag}", gp_ops.qei_pool(b, phi, X, omega=omega, phase=phase, n_samples=80, q=4, generator=torch.Generator().manual_seed(13),
+                                              want_trace=True, want_inc=True))
 
     for kernel, n_s, d, rows, q in (("matern", [48, 45, 31], 16, 300, 8), ("rbf", [200, 197, 133], 64, 333, 8), ("matern", [1024, 700], 12, 130, 4)):
         b, phi, Zs, ys, n_s, X, best = BV._explicit(dev, kernel, n_s, d, rows, 500 + max(n_s))
@@ -136,6 +162,10 @@ def compare(pa, pb):
         return 1
     bad = [k for k in both if a[k].shape != b[k].shape or not torch.equal(a[k].contiguous().view(torch.uint8), b[k].contiguous().view(torch.uint8))]
     print("arrays compared", len(both), "different", bad)
+    by_call = {}
+    for k in both:
+        by_call[k.split("/")[0]] = by_call.get(k.split("/")[0], 0) + 1
+    print("per call:", ", ".join(f"{c} {n}" for c, n in sorted(by_call.items())))
     return 1 if bad else 0
 
 
