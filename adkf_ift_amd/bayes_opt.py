@@ -6,7 +6,9 @@ streaming marginal prediction (no size cap, workspace independent of the pool si
 gets EI straight from that one call.  ``run_gp_ei_bo_batched`` runs many replicates of that loop over the same pool at once: one
 batched fit and one ``adkf_predict_pool`` call per iteration, which returns each replicate's best candidates itself (or one
 ``adkf_believer_pool`` call for a Kriging-believer batch; with ``ard=True`` the batch is an ARD batch and that call is
-``adkf_believer_pool_ard``).
+``adkf_believer_pool_ard``; ``batch="liar"``: one ``adkf_liar_pool`` call for a constant-liar batch).  With ``refit_every=r`` it
+refits every ``r`` iterations and plays the iterations in between, at fixed hyperparameters, with one ``adkf_liar_pool`` call on the
+pool's label table.
 ``run_gp_ts_bo_batched`` is the same loop under Thompson sampling: one batched fit and one ``adkf_thompson_pool`` call (with
 ``ard=True``: ``adkf_thompson_pool_ard``) per iteration, in which every replicate draws posterior functions over the whole pool
 and each function picks its own best candidate - a diverse batch of ``query_batch_size > 1`` picks from one pass, with no
@@ -263,7 +265,7 @@ def _take_picks(top_idx: torch.Tensor, usable: torch.Tensor, query_batch_size: i
 def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
                          kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
                          rngs: List[np.random.Generator], acquisition: str = "ei", batch: str = "topk",
-                         ard: bool = False, marginalize: int = 0) -> List[List[int]]:
+                         ard: bool = False, marginalize: int = 0, lie="min", refit_every: int = 1) -> List[List[int]]:
     """``len(rngs)`` replicates of ``run_gp_ei_bo`` over the same pool at once; returns their records.  Per iteration the
     replicates' queried sets form ONE batch (initial parameters and priors as ``create_gp`` makes them for each), fitted by ONE
     ``gp_ops.fit`` with ``fit_gpytorch_scipy``'s options and scored by ONE ``gp_ops.predict_pool`` call that excludes each
@@ -281,10 +283,25 @@ def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
     acquisition over the hyperparameters (Snoek et al. 2012): after the fit each replicate draws ``M - 1`` Laplace samples of its
     ``phi`` from a torch generator of its own (``gp_ops.phi_laplace_samples``; member 0 is the MAP point), the batch is replicated M
     times (``gp_ops.replicate_batch``) and ONE ``gp_ops.mix_pool`` call ranks the pool by the members' average EI (or by its
-    logarithm) per replicate, under the same exclusions and the same rule for what counts."""
+    logarithm) per replicate, under the same exclusions and the same rule for what counts.
+    ``batch="liar"``: the constant-liar batch of ONE ``gp_ops.liar_pool`` call - the believer's loop with every pick conditioned on
+    ``lie`` (``"min"``, ``"max"``, ``"mean"`` of the replicate's own labels, or a tensor with one value per replicate) instead of on
+    its posterior mean, under the believer's rule for what counts.  With ``query_batch_size = 1`` it is the ``"topk"`` loop.
+    ``refit_every``: 1 refits the hyperparameters in every iteration.  ``r > 1`` (``query_batch_size = 1``, no ``marginalize``)
+    refits every ``r`` iterations: each fit is followed by ONE ``gp_ops.liar_pool`` call that plays ``min(r, iterations left)``
+    iterations at the fitted ``phi`` - each step picks by EI, reads the pick's true label from ``y_all``, updates mean, variance
+    and incumbent - and its picks extend the records as that many iterations would: the usable prefix counts, random free rows
+    fill the rest."""
     log = _acquisition(acquisition)
-    if batch not in ("topk", "believer"):
-        raise ValueError(f"batch must be 'topk' or 'believer', got {batch!r}")
+    if batch not in ("topk", "believer", "liar"):
+        raise ValueError(f"batch must be 'topk', 'believer' or 'liar', got {batch!r}")
+    refit_every = int(refit_every)
+    if refit_every < 1:
+        raise ValueError(f"refit_every must be at least 1, got {refit_every}")
+    if refit_every > 1 and query_batch_size != 1:
+        raise ValueError("refit_every > 1 needs query_batch_size = 1: the replay plays single-pick iterations")
+    if refit_every > 1 and marginalize:
+        raise ValueError("refit_every > 1 needs marginalize = 0: the replay conditions one model, not a mixture")
     marginalize = int(marginalize)
     if marginalize == 1 or not 0 <= marginalize <= 64:
         raise ValueError(f"marginalize must be 0 or in [2, 64], got {marginalize}")
@@ -297,11 +314,25 @@ def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
     records = [[min(q)] for q in queried]
     gens = _path_generators(rngs) if marginalize else None
 
-    for _ in range(num_bo_iters):
+    labels = y_all.detach().float().to(X.device).contiguous() if refit_every > 1 else None
+    done = 0
+    while done < num_bo_iters:
+        steps = min(refit_every, num_bo_iters - done) if refit_every > 1 else 1
+        done += steps
         b, phi = _fit_tasks("run_gp_ei_bo_batched", x_all, [(q, y_all) for q in queried], X, kernel_type, device, noise_init, noise_prior,
                             ard)
         best_f = torch.tensor([y_all[q].min().item() for q in queried], dtype=torch.float32, device=X.device)
-        if batch == "believer":
+        if refit_every > 1:
+            out = gp_ops.liar_pool(b, phi, X, best_f=best_f, q=steps, labels=labels, maximize=False, log_ei=log, exclude=queried)
+            gp_ops.check_info(out["info"], "BO posterior")
+            top_idx, top_val = out["sel_idx"].cpu(), out["sel_val"].cpu()
+            usable = (torch.isfinite(top_val) & (top_idx >= 0)) if log else top_val > 0
+            _take_picks(top_idx, usable.long().cumprod(1).bool(), steps, rngs, queried, records, n)
+            continue
+        if batch == "liar":
+            out = gp_ops.liar_pool(b, phi, X, best_f=best_f, q=query_batch_size, lie=lie, maximize=False, log_ei=log, exclude=queried)
+            top_idx, top_val = out["sel_idx"].cpu(), out["sel_val"].cpu()
+        elif batch == "believer":
             believe = gp_ops.believer_pool_ard if b.ard else gp_ops.believer_pool
             out = believe(b, phi, X, best_f=best_f, q=query_batch_size, maximize=False, log_ei=log, exclude=queried)
             top_idx, top_val = out["sel_idx"].cpu(), out["sel_val"].cpu()
@@ -321,7 +352,7 @@ def run_gp_ei_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
             top_idx, top_val = out["top_idx"].cpu(), out["top_val"].cpu()
         gp_ops.check_info(out["info"], "BO posterior")
         usable = (torch.isfinite(top_val) & (top_idx >= 0)) if log else top_val > 0   # (a prefix of each row: descending scores)
-        if batch == "believer":   # a believer score can round above its predecessor: keep the prefix
+        if batch in ("believer", "liar"):   # a believer score can round above its predecessor: keep the prefix
             usable = usable.long().cumprod(1).bool()
         _take_picks(top_idx, usable, query_batch_size, rngs, queried, records, n, reverse=True)
     return records

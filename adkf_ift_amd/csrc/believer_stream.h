@@ -41,7 +41,9 @@
 // adkf_gibbon_pool (gibbon_stream.h) downdates the same variance with the same state, k_bv_init and k_bv_step, under another score.
 // The float64 c0 of a lane (bv64_c0) and the first parts of k_bv_step - the stored row, k(Z_s, x) and w = A^-1 k (bv_store_row,
 // bv_kernel_col, bv_solve_w) - are functions because adkf_kg_pool and adkf_jes_pool (kg_stream.h, jes_stream.h) build the same state
-// for a fixed reference set, one (entry, task) workgroup each: bv_ref_entry.
+// for a fixed reference set, one (entry, task) workgroup each: bv_ref_entry.  k_bv_step's body is a function too (bv_step), with
+// what is believed about the pick as a parameter, because adkf_liar_pool (liar_stream.h) runs the same step with a supplied value;
+// bv64_downdate shows each ell_i to a functor for the same entry's mean shift.
 #pragma once
 #include "thompson_stream.h"
 
@@ -167,10 +169,11 @@ __device__ __forceinline__ double bv64_c0(const PmArgs& a, const Pm64Task& tk, c
 }
 
 // the float64 downdate of one pool row zq (kernel row k) with c > 0 picks made, over the lanes of a wave: lane i forms c0(x, i), the
-// substitution runs over the lanes (row i of G against the ell broadcast so far); returns |ell|^2 to every lane
-template <bool ARD>
+// substitution runs over the lanes (row i of G against the ell broadcast so far); returns |ell|^2 to every lane.  each(i, ell_i)
+// sees every entry as it is broadcast (adkf_liar_pool's mean shift, liar_stream.h).
+template <bool ARD, class EACH>
 __device__ __forceinline__ double bv64_downdate(const PmArgs& a, const Pm64Task& tk, const float* zq, const double* k, const double* Wt,
-                                                const double* G, const float* Xp, int c, int q, int lane) {
+                                                const double* G, const float* Xp, int c, int q, int lane, EACH each) {
     const double c0 = bv64_c0<ARD>(a, tk, zq, k, Wt, Xp, c, lane);   // lane i: c0(x, i)
     double part = 0.0, ss = 0.0;   // lane i: sum_(l < i) G[i, l] ell_l so far
     for (int i = 0; i < c; ++i) {
@@ -178,8 +181,14 @@ __device__ __forceinline__ double bv64_downdate(const PmArgs& a, const Pm64Task&
         e = __shfl(e, i);
         if (lane > i && lane < c) part += G[(size_t)lane * q + i] * e;
         ss += e * e;
+        each(i, e);
     }
     return ss;
+}
+template <bool ARD>
+__device__ __forceinline__ double bv64_downdate(const PmArgs& a, const Pm64Task& tk, const float* zq, const double* k, const double* Wt,
+                                                const double* G, const float* Xp, int c, int q, int lane) {
+    return bv64_downdate<ARD>(a, tk, zq, k, Wt, G, Xp, c, q, lane, [](int, double) {});
 }
 
 // ---- flagged tasks: the float64 pool walk (pm64_pool_walk) with the downdate in float64
@@ -309,12 +318,25 @@ __device__ __forceinline__ double bv_ref_entry(const ARGS& args, int t, bool ok,
     return bv_block_sum(pm, red);
 }
 
-// ---- the end of step j: one workgroup per task (see the top of the file)
-template <bool ARD>
-__global__ __launch_bounds__(256) void k_bv_step(BvKargs<ARD> args) {
+// What a greedy entry believes about a pick - the one part of the step its entries do not share.  The believer's and GIBBON's: the
+// pick's posterior mean, which never moves.  adkf_liar_pool's (liar_stream.h) supplies the value and moves the mean.
+//   none(o)                       no eligible row at output slot o (one thread)
+//   pick(o, p, m0, ell, c, gd)    row p is pick c: m0 its mean from the support set, ell [c] = G^-1 c0(x_p, .), gd = G[c, c]; returns
+//                                 the mean to report and the value believed, which moves the incumbent (one thread)
+struct BvPick { float mean, believed; };
+struct BvBelieveMean {
+    __device__ __forceinline__ void none(size_t) const {}
+    __device__ __forceinline__ BvPick pick(size_t, long long, double m0, const double*, int, double) const {
+        const float mf = (float)m0;
+        return {mf, mf};
+    }
+};
+
+// ---- the end of step j: one workgroup per task (see the top of the file), on the believer's arguments v with the entry's rule
+template <bool ARD, class ARGS, class BELIEVE>
+__device__ __forceinline__ void bv_step(const ARGS& args, const BvArgs& v, const BELIEVE& believe) {
     const PmArgs& a = args.p;
     const PmPool& s = args.s;
-    const BvArgs& v = args.v;
     __shared__ __attribute__((aligned(16))) float fb[3 * TS_NS_MAX];
     __shared__ double red[256];
     __shared__ double c0s[PM_TOPK_MAX];
@@ -335,6 +357,7 @@ __global__ __launch_bounds__(256) void k_bv_step(BvKargs<ARD> args) {
             v.sel_idx[o] = -1; v.sel_val[o] = -INFINITY;
             if (v.sel_mean) v.sel_mean[o] = 0.f;
             if (v.sel_var) v.sel_var[o] = 0.f;
+            believe.none(o);
         }
         return;
     }
@@ -384,13 +407,17 @@ __global__ __launch_bounds__(256) void k_bv_step(BvKargs<ARD> args) {
             const double g = i < c ? c0s[i] : gd;
             if (f64) v.G64[((size_t)t * q + c) * q + i] = g; else v.G[((size_t)t * q + c) * q + i] = (float)g;
         }
-        const float mf = (float)mean;
+        const BvPick b = believe.pick(o, p, mean, c0s, c, gd);
         v.sel_idx[o] = p; v.sel_val[o] = val_s;
-        if (v.sel_mean) v.sel_mean[o] = mf;
+        if (v.sel_mean) v.sel_mean[o] = b.mean;
         if (v.sel_var) v.sel_var[o] = (float)vj;
-        v.best[t] = a.maximize ? fmaxf(v.best[t], mf) : fminf(v.best[t], mf);
+        v.best[t] = a.maximize ? fmaxf(v.best[t], b.believed) : fminf(v.best[t], b.believed);
         v.cnt[t] = c + 1;
     }
+}
+template <bool ARD>
+__global__ __launch_bounds__(256) void k_bv_step(BvKargs<ARD> args) {
+    bv_step<ARD>(args, args.v, BvBelieveMean{});
 }
 
 }  // namespace adkf

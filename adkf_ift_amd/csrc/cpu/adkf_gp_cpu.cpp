@@ -8,7 +8,7 @@
 // support-only batch take ARD batches too - they centre and scale the features by the per-dimension lengthscales and run the
 // isotropic code at unit lengthscale (csrc/ard.h, prepare_task below): adkf_predict_marginal_ard, adkf_thompson_pool_ard and
 // adkf_believer_pool_ard take ARD batches only and their plain namesakes refuse them, as the library does; adkf_predict_pool,
-// adkf_mes_pool, adkf_gumbel_pool, adkf_gibbon_pool, adkf_kg_pool, adkf_ipv_pool, adkf_jes_pool, adkf_jackknife_pool, adkf_ehvi_pool
+// adkf_mes_pool, adkf_gumbel_pool, adkf_gibbon_pool, adkf_liar_pool, adkf_kg_pool, adkf_ipv_pool, adkf_jes_pool, adkf_jackknife_pool, adkf_ehvi_pool
 // and adkf_mix_pool take either kind.  What the pool entries share is the pool kit (after pm_task).
 // Plain loops, OpenMP over the tasks of a batch, float64 arithmetic inside and float32 at the boundary - a Cholesky-based
 // restatement of the same staged closed-form algebra the HIP kernels run (stage names as in DESIGN.md section 3 and
@@ -478,7 +478,7 @@ bool pm_task(const adkf_batch_t* b, const float* phi, int t, const float* Zq, in
 //   PoolState, pool_state, c0_col      believer / gibbon, kg, ipv, jes: K, K A^-1, mean and latent variance of every row, c0(x_r, x_p)
 //   excl_range (Excl::has)             select_topk, greedy_pick and Thompson's per-row test
 //   init_topk, select_topk             predict_pool, mes, kg, jes, jackknife, ehvi and mix (per group); init_topk also the sel_* fills
-//   greedy_pick, append_pick           believer / gibbon (step j) and ipv (pick c)
+//   greedy_pick, append_pick           believer / gibbon / liar (step j) and ipv (pick c)
 //   valid_entry                        kg (references) and ipv (targets)
 //   prepare_task, task_row_dist        pm_task_state and PathDraws (thompson_pool, qei_pool)
 enum { ARD_EITHER = -1 };   // check_support_only's ard_mode; 0 / 1: the batch must not / must be an ARD batch
@@ -1193,25 +1193,37 @@ static double gibbon_term(double g, double rho2) {
 // GIBBON (adkf_gibbon_pool: ystar given, S samples per task, no best_f): the same greedy loop and downdate with the score
 // a(x) + 1/2 log((max(v_j, 1e-12) + noise) / (max(v_0, 1e-12) + noise)), a(x) from gibbon_term, computed once per row; the mean and
 // the variances enter the score in float64 (the device rounds them to float32 first).
+// The constant liar and label replay (adkf_liar_pool: liar given): the pick is conditioned on y_j, the first finite of its label, the
+// task's lie and its own mean, so after append_pick - whose column of ell is the one the mean moves along - every row's mean gains
+// ell_j(x) z_j, z_j = (y_j - m_j(x_p)) / G[j, j]; the incumbent follows y_j.
+struct Liar {
+    const float *lie, *labels; int64_t stride;
+    float *sel_lie, *inc;
+};
 static int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
                          const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val,
-                         float* sel_mean, float* sel_var, int32_t* info, const float* ystar = nullptr, int32_t S = 0, bool gibbon = false) {
+                         float* sel_mean, float* sel_var, int32_t* info, const float* ystar = nullptr, int32_t S = 0, bool gibbon = false,
+                         const Liar* liar = nullptr) {
     if (int rc = check_support_only(b, phi, info, rows, ard)) return rc;
     if (flags & ~(gibbon ? ADKF_PM_MAXIMIZE : (ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI))) return ADKF_E_BADARG;
     if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
     if (!(gibbon ? ystar : best_f) || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (liar && !liar->lie && !liar->labels) return ADKF_E_BADARG;
+    if (liar && liar->stride != 0 && (liar->stride != rows || !liar->labels)) return ADKF_E_BADARG;
     if (q < 1 || (gibbon && S < 1)) return ADKF_E_BADARG;
     if (q > ADKF_POOL_TOPK_MAX || (gibbon && S > ADKF_TS_SAMPLES_MAX)) return ADKF_E_SIZE;
 #pragma omp parallel for schedule(dynamic)
     for (int t = 0; t < b->T; ++t) {
         init_topk(sel_idx, sel_val, t, q);
+        if (liar && liar->sel_lie) std::fill(liar->sel_lie + (size_t)t * q, liar->sel_lie + (size_t)(t + 1) * q, 0.f);
+        if (liar && liar->inc) std::fill(liar->inc + (size_t)t * (q + 1), liar->inc + (size_t)(t + 1) * (q + 1), best_f[t]);
         if (sel_mean) std::fill(sel_mean + (size_t)t * q, sel_mean + (size_t)(t + 1) * q, 0.f);
         if (sel_var) std::fill(sel_var + (size_t)t * q, sel_var + (size_t)(t + 1) * q, 0.f);
         if (trace && rows > 0) std::fill(trace + (size_t)t * q * rows, trace + (size_t)(t + 1) * q * rows, 0.f);
         PoolState st;
         if (!pool_state(b, phi, t, X, rows, info, st)) continue;
         const size_t R = st.R;
-        const Mat& mu = st.mu;
+        Mat& mu = st.mu;       // (the liar moves it)
         const Mat& v = st.v;   // (append_pick downdates it)
         const double noise = st.noise;
         const Excl excl = excl_range(excl_idx, excl_off, t);
@@ -1242,10 +1254,22 @@ static int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int3
             sel_idx[o] = p; sel_val[o] = score[p];
             if (sel_mean) sel_mean[o] = (float)mu[p];
             if (sel_var) sel_var[o] = (float)v[p];
+            const double mjp = mu[p];
             append_pick(st, b, X, p, j, q, G, L, col);   // (a step without a pick ends the batch, so step j is entry j)
             taken[p] = 1;
-            const double mp = (double)(float)mu[p];
+            double mp = (double)(float)mjp;
+            if (liar) {
+                float y = liar->labels ? liar->labels[(size_t)t * (size_t)liar->stride + (size_t)p] : std::numeric_limits<float>::quiet_NaN();
+                if (!std::isfinite(y) && liar->lie) y = liar->lie[t];
+                if (std::isfinite(y)) {
+                    mp = y;
+                    const double z = ((double)y - mjp) / G[(size_t)j * q + j];
+                    for (size_t r = 0; r < R; ++r) mu[r] += L[r * q + j] * z;
+                }
+                if (liar->sel_lie) liar->sel_lie[o] = (float)mp;
+            }
             best = (flags & ADKF_PM_MAXIMIZE) ? std::max(best, mp) : std::min(best, mp);
+            if (liar && liar->inc) std::fill(liar->inc + (size_t)t * (q + 1) + j + 1, liar->inc + (size_t)(t + 1) * (q + 1), (float)best);
         }
     }
     return 0;
@@ -1269,6 +1293,19 @@ int adkf_gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, con
                      float* sel_mean, float* sel_var, int32_t* info, void*, size_t, void*, size_t, void*) {
     const bool ard = b && (b->flags & ADKF_BATCH_ARD) != 0;
     return believer_pool(ard, b, phi, flags, X, rows, nullptr, excl_idx, excl_off, q, trace, sel_idx, sel_val, sel_mean, sel_var, info, ystar, S, true);
+}
+
+size_t adkf_liar_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { return 0; }
+
+// Constant-liar and label-replay batches (include/adkf_gp.h): believer_pool's loop with the believed value supplied, for either kind of batch
+int adkf_liar_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f, const float* lie,
+                   const float* labels, int64_t label_stride, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace,
+                   int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, float* sel_lie, float* inc, int32_t* info, void*, size_t,
+                   void*, size_t, void*) {
+    const bool ard = b && (b->flags & ADKF_BATCH_ARD) != 0;
+    const Liar liar{lie, labels, label_stride, sel_lie, inc};
+    return believer_pool(ard, b, phi, flags, X, rows, best_f, excl_idx, excl_off, q, trace, sel_idx, sel_val, sel_mean, sel_var, info, nullptr, 0,
+                         false, &liar);
 }
 
 size_t adkf_kg_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t, int32_t) { return 0; }

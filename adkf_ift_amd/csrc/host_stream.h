@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ipv_pool, adkf_jackknife_pool, adkf_ehvi_pool, adkf_mix_pool and adkf_qei_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_liar_pool, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ipv_pool, adkf_jackknife_pool, adkf_ehvi_pool, adkf_mix_pool and adkf_qei_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
 // pool calls share (pool_walks, pool_select, pool_greedy) and the body of every entry.
 #pragma once
 #include "host_ard.h"
@@ -245,19 +245,25 @@ int pool_select(const PmCtx& c, PmArgs& pa, PmPool& pool, const typename EPI::Ar
 }
 
 // "q greedy steps" - adkf_believer_pool(_ard) (v and bv are one) and adkf_gibbon_pool (bv = v.b): q chained steps, each the walks with
-// the epilogue EPI and the believer's one workgroup per task on the believer's arguments.
-template <bool ARD, class EPI>
-int pool_greedy(const PmCtx& c, PmArgs& pa, PmPool& pool, typename EPI::Args& v, BvArgs& bv, PoolKernel<ARD, EPI> walk64, bool have64) {
+// the epilogue EPI and the believer's one workgroup per task on the believer's arguments.  adkf_liar_pool (bv = v.b) names its own
+// step kernel and that kernel's arguments sv, which hold bv (so they follow the step).
+template <bool ARD, class EPI, class SEPI>
+int pool_greedy(const PmCtx& c, PmArgs& pa, PmPool& pool, typename EPI::Args& v, BvArgs& bv, PoolKernel<ARD, EPI> walk64, bool have64,
+                PoolKernel<ARD, SEPI> step, const typename SEPI::Args& sv) {
     if constexpr (ARD) launch_ard_il(c);
     pool.grid[2] = pool_grid64(pool, pa.rows, have64);
     for (int j = 0; j < bv.q; ++j) {
         bv.j = j;
         const int rc = pool_walks<ARD, EPI>(c, pa, pool, v, walk64);
         if (rc) return rc;
-        k_bv_step<ARD><<<c.b.T, 256, 0, c.st>>>(pm_kargs<ARD, true, BvEpilogue>(c, pa, &pool, bv));
+        step<<<c.b.T, 256, 0, c.st>>>(pm_kargs<ARD, true, SEPI>(c, pa, &pool, sv));
     }
     LAUNCH_OK();
     return 0;
+}
+template <bool ARD, class EPI>
+int pool_greedy(const PmCtx& c, PmArgs& pa, PmPool& pool, typename EPI::Args& v, BvArgs& bv, PoolKernel<ARD, EPI> walk64, bool have64) {
+    return pool_greedy<ARD, EPI, BvEpilogue>(c, pa, pool, v, bv, walk64, have64, k_bv_step<ARD>, bv);
 }
 
 // The streaming launches of a prepared prediction call.  POOL: pool_select with prediction's own epilogue.
@@ -582,6 +588,55 @@ int believer_pool(bool ard, const adkf_batch_t* b, const float* phi, int32_t fla
     k_bv_init<<<ceil_div(T, 256), 256, 0, st>>>(v, best_f, T);
     return ard ? pool_greedy<true, BvEpilogue>(c, pa, pool, v, v, k_bv_walk64<true>, have64)
                : pool_greedy<false, BvEpilogue>(c, pa, pool, v, v, k_bv_walk64<false>, have64);
+}
+
+// adkf_liar_pool: the scratch is the believer's (bv_scratch), then z [T, q] and its float64 twin
+struct LiarScratch { BvScratch b; float* z; double* z64; size_t bytes; };
+inline LiarScratch liar_scratch(void* base, int T, int ns, int d, int q) {
+    LiarScratch l{};
+    l.b = bv_scratch(base, T, ns, d, q);
+    Arena ar{static_cast<char*>(base), l.b.bytes};
+    l.z = ar.floats((size_t)T * q);
+    l.z64 = ar.as<double>(ns <= R64_MAXN ? (size_t)T * q : 0);
+    l.bytes = ar.off;
+    return l;
+}
+
+// adkf_liar_pool: isotropic and ARD batches alike (as adkf_gibbon_pool)
+int liar_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f, const float* lie,
+              const float* labels, int64_t label_stride, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace,
+              int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, float* sel_lie, float* inc, int32_t* info, void* ws,
+              size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags & ~(ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
+    if (!best_f || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (!lie && !labels) return ADKF_E_BADARG;   // (that call is adkf_believer_pool)
+    if (label_stride != 0 && (label_stride != rows || !labels)) return ADKF_E_BADARG;
+    if (q < 1) return ADKF_E_BADARG;
+    if (q > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    const LiarScratch l = liar_scratch(scratch, b->T, b->ns_max, b->d, q);
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    hipStream_t st = c.st;
+    const int T = b->T;
+    PmArgs pa = pm_args(c, flags, X, rows, info);
+    pa.best_f = best_f;
+    const bool have64 = pm_have64(c, pa);
+    PmPool pool = pm_pool(excl_idx, excl_off, 1, T, l.b.cand.idx, l.b.cand.val, rows, st);
+    LiarArgs v{};
+    v.b = bv_args(l.b, have64, q, trace, sel_idx, sel_val, sel_mean, sel_var);
+    v.lie = lie; v.labels = labels; v.stride = label_stride;
+    v.z = l.z; v.z64 = have64 ? l.z64 : nullptr; v.sel_lie = sel_lie; v.inc = inc;
+    // skipped tasks keep zeros in trace
+    if (trace && rows > 0) hipMemsetAsync(trace, 0, sizeof(float) * (size_t)T * q * (size_t)rows, st);
+    k_bv_init<<<ceil_div(T, 256), 256, 0, st>>>(v.b, best_f, T);
+    k_liar_init<<<ceil_div(T, 256), 256, 0, st>>>(v, best_f, T);
+    return c.ard ? pool_greedy<true, LiarEpilogue, LiarEpilogue>(c, pa, pool, v, v.b, k_liar_walk64<true>, have64, k_liar_step<true>, v)
+                 : pool_greedy<false, LiarEpilogue, LiarEpilogue>(c, pa, pool, v, v.b, k_liar_walk64<false>, have64, k_liar_step<false>, v);
 }
 
 // adkf_predict_pool: isotropic and ARD batches alike

@@ -510,6 +510,66 @@ def believer_pool_ard(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, best_f:
     return _believer_pool("believer_pool_ard", b, phi, X, best_f, q, maximize, log_ei, exclude, want_trace)
 
 
+def liar_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, best_f: torch.Tensor, q: int, lie=None, labels: Optional[torch.Tensor] = None,
+              maximize: bool = False, log_ei: bool = False, exclude=None, want_trace: bool = False):
+    """A constant-liar or label-replay batch per task from the shared pool ``X [rows, d]`` in one ``adkf_liar_pool`` call, for
+    isotropic and ARD batches alike: ``believer_pool`` with the believed value supplied.  ``q`` (at most 64) sequential-greedy EI
+    picks; each pick is conditioned as a noisy observation on the first finite value of its entry in ``labels`` (``[rows]``, one
+    table for all tasks, or ``[T, rows]``), the task's ``lie`` and its own posterior mean - so the posterior MEAN moves inside the
+    call, as well as the variance and the incumbent.  ``lie``: a tensor ``[T]``, or ``"min"`` / ``"max"`` / ``"mean"`` of each
+    task's own support labels (maximising, CL-min explores harder than the believer and CL-max stays on its peak; minimising swaps
+    the two: Ginsbourger et al. 2010).  With
+    ``labels`` the call plays ``q`` iterations of a replay at fixed ``phi`` (BoTorch's ``condition_on_observations``).  At least
+    one of ``lie`` and ``labels``.  Returns ``believer_pool``'s dict - ``sel_mean`` / ``sel_var`` the conditioned mean and latent
+    variance each pick had when it was picked - plus ``sel_lie [T, q]``, the value each pick was conditioned on (0 where there was
+    no pick), and ``inc [T, q + 1]``, the incumbent before step 0 and after every step."""
+    lib = _lib.load()
+    _support_only(b, "liar_pool")
+    q = _in_range(q, 1, _lib.POOL_TOPK_MAX, "q")
+    phi, X = _phi_and_pool(b, phi, X)
+    rows = X.shape[0]
+    if best_f is None:
+        raise ValueError("liar_pool needs best_f [T]")
+    best_f = _f32(best_f, "best_f").reshape(-1)
+    if best_f.numel() != b.T:
+        raise ValueError(f"best_f must have T = {b.T} entries")
+    if lie is None and labels is None:
+        raise ValueError("liar_pool needs lie or labels: without either it is believer_pool")
+    if isinstance(lie, str):
+        if lie not in ("min", "max", "mean"):
+            raise ValueError(f"lie must be a tensor [T] or one of 'min', 'max', 'mean', got {lie!r}")
+        n_s = b.n_s.to(torch.int64) if b.n_s is not None else torch.full((b.T,), b.ns, dtype=torch.int64, device=b.device)
+        live = torch.arange(b.ns, device=b.device)[None, :] < n_s[:, None]
+        y = b.y_s.to(torch.float32)
+        if lie == "mean":
+            lie = torch.where(live, y, torch.zeros_like(y)).sum(1) / n_s.clamp(min=1).to(torch.float32)
+        else:
+            pad = float("inf") if lie == "min" else float("-inf")
+            y = torch.where(live, y, torch.full_like(y, pad))
+            lie = y.min(1).values if lie == "min" else y.max(1).values
+    if lie is not None:
+        lie = _f32(lie, "lie").reshape(-1)
+        if lie.numel() != b.T:
+            raise ValueError(f"lie must have T = {b.T} entries")
+    stride = 0
+    if labels is not None:
+        labels = _f32(labels, "labels")
+        if tuple(labels.shape) == (b.T, rows):
+            stride = rows
+        elif tuple(labels.shape) != (rows,):
+            raise ValueError(f"labels must be [rows] = [{rows}] or [T, rows] = [{b.T}, {rows}], got {tuple(labels.shape)}")
+    _on_device(b, X=X, best_f=best_f, lie=lie, labels=labels)
+    excl_idx, excl_off = _exclusion(b, exclude, b.T, rows)
+    sel_idx, sel_val, info = _selection(b, b.T, q)
+    sel_mean, sel_var, sel_lie, inc = _new(b, b.T, q), _new(b, b.T, q), _new(b, b.T, q), _new(b, b.T, q + 1)
+    trace = _new(b, b.T, q, rows) if want_trace else None
+    flags = (_lib.PM_MAXIMIZE if maximize else 0) | (_lib.PM_LOG_EI if log_ei else 0)
+    args = (ptr(best_f), ptr(lie), ptr(labels), stride, ptr(excl_idx), ptr(excl_off), q, ptr(trace), ptr(sel_idx), ptr(sel_val),
+            ptr(sel_mean), ptr(sel_var), ptr(sel_lie), ptr(inc))
+    _pool_call(lib, "adkf_liar_pool", b, phi, flags, X, args, info, lib.adkf_liar_pool_scratch_bytes(b.T, b.ns, b.d, q))
+    return dict(sel_idx=sel_idx, sel_val=sel_val, sel_mean=sel_mean, sel_var=sel_var, sel_lie=sel_lie, inc=inc, trace=trace, info=info)
+
+
 def rff_basis(kernel, d: int, m: int, generator: Optional[torch.Generator] = None, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """A random-Fourier basis ``(omega [m, d], phase [m])`` of ``kernel`` AT UNIT LENGTHSCALE, as ``thompson_pool`` takes it:
     ``(1/m) sum_j 2 cos(omega_j.x + phase_j) cos(omega_j.y + phase_j)`` estimates ``kappa(|x - y|)``.  RBF: the rows of ``omega``

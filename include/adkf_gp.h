@@ -468,6 +468,47 @@ int adkf_gumbel_pool(const adkf_batch_t* b, const float* phi, int32_t flags, con
  * (ADKF_E_WORKSPACE); a scratch that is not 8-byte aligned. */
 int adkf_gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* ystar, int32_t S, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Constant-liar and label-replay batches over a shared pool (csrc/liar_stream.h; the constant liar of Ginsbourger, Le Riche and
+ * Carraro 2010, the sibling of the Kriging believer; conditioning on real labels without a refit is BoTorch's
+ * condition_on_observations): adkf_believer_pool with the believed value SUPPLIED.  Per task q sequential-greedy picks by EI (log EI
+ * with ADKF_PM_LOG_EI) from the SAME pool X [rows, d]; after pick p_j is chosen it is conditioned on y_j as a NOISY observation
+ * under the task's own noise, so the posterior mean moves inside the call.  y_j is the first finite value of
+ *              labels[t * label_stride + p_j]    if labels is given,
+ *              lie[t]                            if lie is given,
+ *              m_j(x_(p_j))                      the pick's own posterior mean, which is the believer's rule.
+ *          With A, w_i, c0, G and ell exactly as for adkf_believer_pool:
+ *              z_j      = (y_j - m_j(x_(p_j))) / G[j, j]          G[j, j] = sqrt(v_j(x_(p_j)) + noise)
+ *              m_j(x)   = m_0(x) + sum_(i<j) ell_i(x) z_i         v_j(x) = v_0(x) - sum_(i<j) ell_i(x)^2
+ *              score_j  = EI or log EI (m_j(x), v_j(x), best_j)   best_(j+1) = min(best_j, y_j)   (max with ADKF_PM_MAXIMIZE)
+ *          which is the posterior of the support set with the picks appended as labelled points at the same phi.  A constant lie
+ *          (CL-min, CL-max, CL-mean of the observed labels) is the dial on batch diversity the believer lacks; a label table plays
+ *          q iterations of a replay at fixed phi in one call.  Step 0 is adkf_predict_pool(k = 1) bit for bit; with every y_j from the
+ *          third rule (a lie of NaN) every output is adkf_believer_pool's bit for bit.
+ *          Eligibility, the total order and "no eligible row at step j: -1 / -inf from there on, the state stops changing" are
+ *          adkf_believer_pool's; such a step has 0 in sel_lie and repeats the incumbent in inc.
+ *   b      support-only, of either kind (as adkf_gibbon_pool): with ADKF_BATCH_ARD phi is [T, 2 + d] and ws an ARD workspace.
+ *   flags  ADKF_PM_MAXIMIZE, ADKF_PM_LOG_EI.
+ *   best_f [T], required: best_0.
+ *   lie    nullable [T].  labels  nullable; label_stride 0: one table [rows] shared by all tasks (replicates over one pool);
+ *          label_stride == rows: [T, rows].  At least one of lie and labels.
+ *   q      1 <= q <= ADKF_POOL_TOPK_MAX.
+ *   sel_idx, sel_val   [T, q], required: the pick of each step and its score.
+ *   sel_mean, sel_var  [T, q], each nullable: m_j and the latent v_j at the pick, before it is conditioned on.
+ *   sel_lie   [T, q], nullable: the y_j actually used.    inc  [T, q + 1], nullable: best_0 .. best_q.
+ *   trace  nullable, [T, q, rows] as for adkf_believer_pool.  With trace == NULL nothing of size T x rows is written or kept.
+ *   Tasks with n_s == 0 or info != 0: -1 / -inf in every step, zeros in sel_mean, sel_var, sel_lie and trace, best_f[t] in inc.
+ *   scratch   adkf_liar_pool_scratch_bytes(T, ns_max, d, q) bytes, 8-byte aligned, independent of rows: the believer's state with the
+ *          believer's layout, then z [T, q] and its float64 twin.
+ * Asynchronous on `stream`, no allocation, no synchronisation, no atomics: reproducible to the bit, and a task's result depends on
+ * that task's data, its lie, its labels, the pool and its exclusion list only.
+ * Rejected before anything is launched, ADKF_E_BADARG unless noted: a batch with a query set; any flag bit other than the two
+ * above; rows < 0; rows > 0 without X; a missing best_f, sel_idx, sel_val, info or ws; lie and labels both NULL (that call is
+ * adkf_believer_pool); a label_stride other than 0 and rows; a non-zero label_stride without labels; excl_idx without excl_off;
+ * q < 1; q > ADKF_POOL_TOPK_MAX (ADKF_E_SIZE); a workspace or a scratch that is too small (ADKF_E_WORKSPACE); a scratch that is not
+ * 8-byte aligned. */
+size_t adkf_liar_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t q);
+int adkf_liar_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f, const float* lie, const float* labels, int64_t label_stride, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, float* sel_lie, float* inc, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Knowledge-gradient selection over a shared pool (csrc/kg_stream.h; Frazier, Powell and Dayanik 2009; Scott, Frazier and Powell
  * 2011, "KGCP"; the single-step form of BoTorch's qKnowledgeGradient on a discrete set): every row of the SAME pool X [rows, d] is
  * scored, per task, by how much one noisy observation there is expected to raise the best posterior mean over the row itself and a

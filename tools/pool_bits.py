@@ -14,7 +14,9 @@ and selection, linear and log, with and without the constraints); on each of the
 jes_pool at the first eight reference rows of kg_pool, their -1 and their repetition included), gumbel_pool on fixed uniforms and
 thompson_pool / thompson_pool_ard (m = 64 features and four paths from seeded generators, with the paths; also 64 paths on 128 features and
 37 on 256, minimising and maximising) and qei_pool (the 64-feature basis, 80 paths in two sample blocks, four noisy picks, with trace
-and incumbents; skipped where ADKF_LIB names a build without the entry) - and saves every returned tensor.  Then the records of the six batched BO loops of adkf_ift_amd.bayes_opt, as int64 tensors under records/: a generated pool of
+and incumbents; skipped where ADKF_LIB names a build without the entry) and liar_pool (a constant lie at the tasks' smallest label with
+log EI, and a shared label table, each with trace; the isotropic, the ARD and both float64 problems; skipped likewise) - and saves every
+returned tensor.  Then the records of the six batched BO loops of adkf_ift_amd.bayes_opt, as int64 tensors under records/: a generated pool of
 400 rows in 6 dimensions, 4 initial points, batches of 2, 2 iterations, 3 replicates, 64 features, fixed seeds; the EI loop also with
 batch="believer" and with ard=True, the MES loop also with max_value="gumbel" and with batch="gibbon".  compare looks at the arrays both
 files have, so a tree can be held against one from before a call existed.  All lists are full (pools of 130 to 333 rows), so the
@@ -53,6 +55,7 @@ def dump(path):
     dev = torch.device("cuda:0")
     out = {}
     have_qei = _bind_what_the_library_has("adkf_qei_pool")
+    have_liar = _bind_what_the_library_has("adkf_liar_pool")
 
     def put(tag, o):
         for k, v in o.items():
@@ -64,6 +67,15 @@ def dump(path):
         refs[:, 4] = -1
         refs[:, 5] = refs[:, 0]
         return refs
+
+    def liar(tag, b, phi, X, best, q):
+        """liar_pool with a constant lie and with a shared label table on one problem"""
+        if not have_liar:
+            return
+        Xc = X.cpu()
+        labels = (torch.sin(Xc[:, : min(b.d, 4)].sum(-1)) + 0.1 * torch.randn(Xc.shape[0], generator=torch.Generator().manual_seed(9))).to(dev)
+        put(f"liar/{tag}/lie", gp_ops.liar_pool(b, phi, X, best_f=best, q=q, lie="min", log_ei=True, want_trace=True))
+        put(f"liar/{tag}/labels", gp_ops.liar_pool(b, phi, X, best_f=best, q=q, labels=labels, want_trace=True))
 
     def sampled(tag, b, phi, X, ystar, refs):
         """mes_pool, jes_pool, gumbel_pool and the batch's kind of thompson_pool on one problem"""
@@ -89,6 +101,7 @@ def dump(path):
         for log in (False, True):
             put(f"believer/{kernel}{max(n_s)}/log_ei={log}", gp_ops.believer_pool(b, phi, X, best_f=best.to(dev), q=q, log_ei=log, want_trace=True))
         put(f"gibbon/{kernel}{max(n_s)}", gp_ops.gibbon_pool(b, phi, X, ystar=ystar, q=q, want_trace=True))
+        liar(f"{kernel}{max(n_s)}", b, phi, X, best.to(dev), q)
         put(f"predict_pool/{kernel}{max(n_s)}", gp_ops.predict_pool(b, phi, X, best_f=best.to(dev), topk=8, log_ei=True))
         refs = kg_refs(b, phi, X)
         for log in (False, True):
@@ -96,6 +109,7 @@ def dump(path):
         sampled(f"{kernel}{max(n_s)}", b, phi, X, ystar, refs)
     b, phi, Zs, ys, n_s, X, best = BVA._explicit(dev, "matern", [48, 45, 31], 12, 300, 548)
     put("believer_ard", gp_ops.believer_pool_ard(b, phi, X, best_f=best.to(dev), q=8, want_trace=True))
+    liar("ard", b, phi, X, best.to(dev), 8)
     put("kg_ard", gp_ops.kg_pool(b, phi, X, ref_idx=kg_refs(b, phi, X), log=True, topk=8, want_cov=True))
     sampled("ard", b, phi, X, (ys.min(1).values[:, None] - torch.linspace(0.1, 1.0, 5)[None]).to(dev).contiguous(), kg_refs(b, phi, X))
     b, phi, Zs, ys, n_s, _ = P._ill_batch(dev)
@@ -103,6 +117,7 @@ def dump(path):
     X = torch.cat([P._pool(300, 2, 3), b.Z_s[1, :5].cpu()]).to(dev)
     best = torch.tensor([float(ys[t, :n_s[t]].median()) for t in range(len(n_s))], device=dev)
     put("float64/believer", gp_ops.believer_pool(b, phi, X, best_f=best, q=6, want_trace=True))
+    liar("float64", b, phi, X, best, 6)
     for log in (False, True):
         put(f"float64/kg/log={log}", gp_ops.kg_pool(b, phi, X, ref_idx=kg_refs(b, phi, X), log=log, topk=8, want_cov=True))
     put("float64/gibbon", gp_ops.gibbon_pool(b, phi, X, ystar=(best[:, None] - torch.tensor([[1.0, 2.0]], device=dev)).contiguous(), q=6, want_trace=True))
@@ -111,6 +126,7 @@ def dump(path):
     best = best.to(dev)
     ystar = (best[:, None] - torch.tensor([[1.0, 2.0]], device=dev)).contiguous()
     put("float64_ard/believer", gp_ops.believer_pool_ard(b, phi, X, best_f=best, q=6, want_trace=True))
+    liar("float64_ard", b, phi, X, best, 6)
     for log in (False, True):
         put(f"float64_ard/kg/log={log}", gp_ops.kg_pool(b, phi, X, ref_idx=kg_refs(b, phi, X), log=log, topk=8, want_cov=True))
     put("float64_ard/gibbon", gp_ops.gibbon_pool(b, phi, X, ystar=ystar, q=6, want_trace=True))
