@@ -33,6 +33,7 @@ JK_LEVELS_MAX = 8        # ... levels per call
 MIX_CHUNK_ROWS = 16384   # ... pool rows per chunk of its walk
 TS_SAMPLES_MAX = 64      # adkf_thompson_pool: posterior draws per task
 TS_FEATURES_MAX = 4096   # ... random Fourier features (a multiple of 64, at least 64)
+LS_STRADDLE, LS_PROB, LS_BOUND = 0, 1, 2   # adkf_levelset_pool: the score kinds
 QEI_SAMPLES_MAX = 256    # adkf_qei_pool: posterior draws per task
 QEI_PICKS_MAX = 64       # ... picks per task
 
@@ -115,6 +116,11 @@ SIGNATURES = {
     "adkf_liar_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adkf_levelset_pool_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "adkf_levelset_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
     "adkf_kg_pool_scratch_bytes": (C.c_size_t, [C.c_int32] * 5),
     "adkf_kg_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

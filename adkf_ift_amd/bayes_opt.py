@@ -559,6 +559,73 @@ def run_gp_kg_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_poin
     return records
 
 
+def _batch_size(query_batch_size: int) -> int:
+    if not 1 <= query_batch_size <= gp_ops._lib.POOL_TOPK_MAX:
+        raise ValueError(f"query_batch_size must be in [1, {gp_ops._lib.POOL_TOPK_MAX}], got {query_batch_size}")
+    return int(query_batch_size)
+
+
+@torch.no_grad()
+def run_gp_lse_al_batched(x_all: torch.Tensor, y_all: torch.Tensor, tau: float, num_init_points: int, query_batch_size: int, num_iters: int,
+                          kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
+                          rngs: List[np.random.Generator], beta: float = 1.96, maximize: bool = True, ard: bool = False,
+                          return_counts: bool = False):
+    """``len(rngs)`` replicates of a level-set active-learning loop (the straddle of Bryan et al. 2005 with the hallucinated batches of
+    Gotovos et al. 2013) over the same pool at once: which rows have ``y > tau`` (``y < tau`` without ``maximize``)?  ``tau`` is given
+    in the units of ``y_all`` and mapped through the loop's standardisation of the labels.  Per iteration the replicates' queried
+    sets are fitted by ONE ``gp_ops.fit`` (as ``run_gp_ei_bo_batched``) and ONE ``gp_ops.levelset_pool(score="straddle",
+    q=query_batch_size, exclude=queried)`` call returns each replicate's batch: the rows whose confidence band ``m +- beta sigma``
+    straddles tau the most, each pick shrinking the bands of its neighbours before the next is taken.  A pick counts when its index
+    is not -1 and its score is finite; random free rows from the replicate's generator fill the rest.  Returns the records (the
+    lowest initial index, then the picks in pick order); with ``return_counts`` also ``counts [iterations, R, 3]`` (int64), the
+    number of active, inactive and undecided pool rows each replicate saw BEFORE each iteration's batch.  Nothing random enters the
+    score: a replicate's record does not depend on which other replicates share the batch."""
+    n = x_all.shape[0]
+    q = _batch_size(query_batch_size)
+    mean, std = y_all.mean(), y_all.std()
+    y_all, X, queried = _bo_start(x_all, y_all, num_init_points, init_from, rngs)
+    tau_std = float((tau - mean) / std)
+    records = [[min(s)] for s in queried]
+    seen = []
+    for _ in range(num_iters):
+        b, phi = _fit_tasks("run_gp_lse_al_batched", x_all, [(s, y_all) for s in queried], X, kernel_type, device, noise_init, noise_prior,
+                            ard)
+        out = gp_ops.levelset_pool(b, phi, X, tau=tau_std, beta=beta, q=q, score="straddle", maximize=maximize, exclude=queried)
+        gp_ops.check_info(out["info"], "level-set posterior")
+        seen.append(out["counts"][:, 0].cpu())
+        top_idx, top_val = out["sel_idx"].cpu(), out["sel_val"].cpu()
+        usable = (torch.isfinite(top_val) & (top_idx >= 0)).long().cumprod(1).bool()
+        _take_picks(top_idx, usable, q, rngs, queried, records, n)
+    if return_counts:
+        return records, (torch.stack(seen) if seen else torch.zeros(0, len(rngs), 3, dtype=torch.int64))
+    return records
+
+
+@torch.no_grad()
+def run_gp_ucb_bo_batched(x_all: torch.Tensor, y_all: torch.Tensor, num_init_points: int, query_batch_size: int, num_bo_iters: int,
+                          kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,
+                          rngs: List[np.random.Generator], beta: float = 2.0, ard: bool = False) -> List[List[int]]:
+    """``len(rngs)`` replicates of a GP-BUCB loop (Desautels, Krause and Burdick 2014) over the same pool at once (minimisation, as
+    ``run_gp_ei_bo``); returns their records: the best initial index, then the picks in pick order.  Per iteration the replicates'
+    queried sets are fitted by ONE ``gp_ops.fit`` and ONE ``gp_ops.levelset_pool(score="bound", q=query_batch_size,
+    exclude=queried)`` call returns each replicate's batch: sequential-greedy picks of the lowest confidence bound ``m - beta
+    sigma_j``, the variance downdated by every pick (hallucinated at its mean, so the mean never moves) before the next is taken.
+    It needs no incumbent.  A pick counts when its index is not -1 and its score is finite; random free rows fill the rest."""
+    n = x_all.shape[0]
+    q = _batch_size(query_batch_size)
+    y_all, X, queried = _bo_start(x_all, y_all, num_init_points, init_from, rngs)
+    records = [[min(s)] for s in queried]
+    for _ in range(num_bo_iters):
+        b, phi = _fit_tasks("run_gp_ucb_bo_batched", x_all, [(s, y_all) for s in queried], X, kernel_type, device, noise_init, noise_prior,
+                            ard)
+        out = gp_ops.levelset_pool(b, phi, X, tau=0.0, beta=beta, q=q, score="bound", maximize=False, exclude=queried, want_counts=False)
+        gp_ops.check_info(out["info"], "BO posterior")
+        top_idx, top_val = out["sel_idx"].cpu(), out["sel_val"].cpu()
+        usable = (torch.isfinite(top_val) & (top_idx >= 0)).long().cumprod(1).bool()
+        _take_picks(top_idx, usable, q, rngs, queried, records, n)
+    return records
+
+
 @torch.no_grad()
 def run_gp_ipv_al_batched(x_all: torch.Tensor, y_all: torch.Tensor, target_idx, num_init_points: int, query_batch_size: int,
                           num_rounds: int, kernel_type: str, device, init_from: int, noise_init: float, noise_prior: bool,

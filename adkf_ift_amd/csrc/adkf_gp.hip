@@ -31,6 +31,7 @@
 #include "gumbel_stream.h"
 #include "gibbon_stream.h"
 #include "liar_stream.h"
+#include "levelset_stream.h"
 #include "kg_stream.h"
 #include "jes_stream.h"
 #include "ipv_stream.h"
@@ -324,6 +325,19 @@ int adkf_gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, con
                      void* stream) {
     return gibbon_pool(b, phi, flags, X, rows, ystar, S, excl_idx, excl_off, q, trace, sel_idx, sel_val, sel_mean, sel_var, info, ws, ws_bytes,
                        scratch, scratch_bytes, stream);
+}
+
+size_t adkf_levelset_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t q) {
+    if (T <= 0 || ns_max <= 0 || ns_max > MAX_POINTS || d <= 0 || q < 1 || q > ADKF_POOL_TOPK_MAX) return 0;
+    return ls_scratch(nullptr, T, ns_max, d, q).bytes;
+}
+
+int adkf_levelset_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* tau, const float* beta,
+                       int32_t score, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int8_t* cls, int64_t* counts,
+                       float* hits, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, int32_t* info, void* ws,
+                       size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    return levelset_pool(b, phi, flags, X, rows, tau, beta, score, excl_idx, excl_off, q, trace, cls, counts, hits, sel_idx, sel_val, sel_mean,
+                         sel_var, info, ws, ws_bytes, scratch, scratch_bytes, stream);
 }
 
 size_t adkf_liar_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t q) {

@@ -8,7 +8,7 @@
 // support-only batch take ARD batches too - they centre and scale the features by the per-dimension lengthscales and run the
 // isotropic code at unit lengthscale (csrc/ard.h, prepare_task below): adkf_predict_marginal_ard, adkf_thompson_pool_ard and
 // adkf_believer_pool_ard take ARD batches only and their plain namesakes refuse them, as the library does; adkf_predict_pool,
-// adkf_mes_pool, adkf_gumbel_pool, adkf_gibbon_pool, adkf_liar_pool, adkf_kg_pool, adkf_ipv_pool, adkf_jes_pool, adkf_jackknife_pool, adkf_ehvi_pool
+// adkf_mes_pool, adkf_gumbel_pool, adkf_gibbon_pool, adkf_liar_pool, adkf_levelset_pool, adkf_kg_pool, adkf_ipv_pool, adkf_jes_pool, adkf_jackknife_pool, adkf_ehvi_pool
 // and adkf_mix_pool take either kind.  What the pool entries share is the pool kit (after pm_task).
 // Plain loops, OpenMP over the tasks of a batch, float64 arithmetic inside and float32 at the boundary - a Cholesky-based
 // restatement of the same staged closed-form algebra the HIP kernels run (stage names as in DESIGN.md section 3 and
@@ -1306,6 +1306,79 @@ int adkf_liar_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const
     const Liar liar{lie, labels, label_stride, sel_lie, inc};
     return believer_pool(ard, b, phi, flags, X, rows, best_f, excl_idx, excl_off, q, trace, sel_idx, sel_val, sel_mean, sel_var, info, nullptr, 0,
                          false, &liar);
+}
+
+size_t adkf_levelset_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { return 0; }
+
+static double log_cdf(double z);
+
+// Level-set estimation and batch UCB (include/adkf_gp.h): believer_pool's greedy loop and downdate with the mean held fixed and no
+// incumbent.  The posterior, z and the scores are float64, rounded to float32 at the boundary; the class of a row is taken from the
+// float32-rounded straddle - the value a STRADDLE call stores in trace - so that the counts are comparable with the device's; hits
+// is the device's 2^-31 fixed-point sum of the float32-rounded Phi terms, integer adds only (csrc/levelset_stream.h).
+int adkf_levelset_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* tau, const float* beta,
+                       int32_t kind, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int8_t* cls, int64_t* counts,
+                       float* hits, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, int32_t* info, void*, size_t, void*,
+                       size_t, void*) {
+    if (int rc = check_support_only(b, phi, info, rows, ARD_EITHER)) return rc;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (kind < ADKF_LS_STRADDLE || kind > ADKF_LS_BOUND) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
+    if (!tau || !beta || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (q < 1) return ADKF_E_BADARG;
+    if (q > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    if ((counts || hits) && rows > ((int64_t)1 << 31)) return ADKF_E_SIZE;
+    const bool maximize = (flags & ADKF_PM_MAXIMIZE) != 0;
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        init_topk(sel_idx, sel_val, t, q);
+        if (sel_mean) std::fill(sel_mean + (size_t)t * q, sel_mean + (size_t)(t + 1) * q, 0.f);
+        if (sel_var) std::fill(sel_var + (size_t)t * q, sel_var + (size_t)(t + 1) * q, 0.f);
+        if (trace && rows > 0) std::fill(trace + (size_t)t * q * rows, trace + (size_t)(t + 1) * q * rows, 0.f);
+        if (cls && rows > 0) std::fill(cls + (size_t)t * rows, cls + (size_t)(t + 1) * rows, (int8_t)-1);
+        if (counts) std::fill(counts + (size_t)t * q * 3, counts + (size_t)(t + 1) * q * 3, (int64_t)0);
+        if (hits) std::fill(hits + (size_t)t * q, hits + (size_t)(t + 1) * q, 0.f);
+        PoolState st;
+        if (!pool_state(b, phi, t, X, rows, info, st)) continue;
+        const size_t R = st.R;
+        const Mat &mu = st.mu, &v = st.v;   // (append_pick downdates v)
+        const double tf = tau[t], bf = beta[t];
+        const bool ok = std::isfinite(tf) && std::isfinite(bf) && bf >= 0.0;
+        const Excl excl = excl_range(excl_idx, excl_off, t);
+        std::vector<char> taken(R, 0);
+        std::vector<float> score(R);
+        Mat G((size_t)q * q, 0.0), L(R * q), col(R);
+        for (int j = 0; j < q; ++j) {
+            const size_t o = (size_t)t * q + j;
+            uint64_t n[3] = {0, 0, 0}, fixed = 0;
+            for (size_t r = 0; r < R; ++r) {
+                int c = -1;
+                score[r] = nan;
+                if (ok && mu[r] == mu[r] && v[r] == v[r]) {
+                    const double sg = std::sqrt(std::max(v[r], 1e-12)), dm = mu[r] - tf, sd = maximize ? dm : -dm, z = sd / sg;
+                    const double straddle = bf * sg - std::fabs(dm);
+                    c = (float)straddle > 0.f ? 2 : (sd > 0.0 ? 0 : 1);
+                    const double Phi = z > 0.0 ? 1.0 - 0.5 * std::erfc(z / std::sqrt(2.0)) : 0.5 * std::erfc(-z / std::sqrt(2.0));
+                    fixed += (uint64_t)std::llrint((double)(float)Phi * 2147483648.0);
+                    ++n[c];
+                    score[r] = (float)(kind == ADKF_LS_STRADDLE ? straddle : (kind == ADKF_LS_PROB ? log_cdf(z) : (maximize ? mu[r] : -mu[r]) + bf * sg));
+                }
+                if (trace) trace[o * R + r] = score[r];
+                if (cls && j == 0) cls[(size_t)t * R + r] = (int8_t)c;
+            }
+            if (counts) for (int c = 0; c < 3; ++c) counts[o * 3 + c] = (int64_t)n[c];
+            if (hits) hits[o] = (float)((double)fixed / 2147483648.0);
+            const int64_t p = greedy_pick(score, rows, taken, excl);
+            if (p < 0) continue;   // no eligible row: this step and all later ones keep -1 / -inf, the state (hence the counts) stays
+            sel_idx[o] = p; sel_val[o] = score[p];
+            if (sel_mean) sel_mean[o] = (float)mu[p];
+            if (sel_var) sel_var[o] = (float)v[p];
+            append_pick(st, b, X, p, j, q, G, L, col);
+            taken[p] = 1;
+        }
+    }
+    return 0;
 }
 
 size_t adkf_kg_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t, int32_t) { return 0; }

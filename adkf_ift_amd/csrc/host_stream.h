@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_liar_pool, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ipv_pool, adkf_jackknife_pool, adkf_ehvi_pool, adkf_mix_pool and adkf_qei_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_liar_pool, adkf_levelset_pool, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ipv_pool, adkf_jackknife_pool, adkf_ehvi_pool, adkf_mix_pool and adkf_qei_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
 // pool calls share (pool_walks, pool_select, pool_greedy) and the body of every entry.
 #pragma once
 #include "host_ard.h"
@@ -245,8 +245,8 @@ int pool_select(const PmCtx& c, PmArgs& pa, PmPool& pool, const typename EPI::Ar
 }
 
 // "q greedy steps" - adkf_believer_pool(_ard) (v and bv are one) and adkf_gibbon_pool (bv = v.b): q chained steps, each the walks with
-// the epilogue EPI and the believer's one workgroup per task on the believer's arguments.  adkf_liar_pool (bv = v.b) names its own
-// step kernel and that kernel's arguments sv, which hold bv (so they follow the step).
+// the epilogue EPI and the believer's one workgroup per task on the believer's arguments.  adkf_liar_pool and adkf_levelset_pool
+// (bv = v.b) name their own step kernel and that kernel's arguments sv, which hold bv (so they follow the step).
 template <bool ARD, class EPI, class SEPI>
 int pool_greedy(const PmCtx& c, PmArgs& pa, PmPool& pool, typename EPI::Args& v, BvArgs& bv, PoolKernel<ARD, EPI> walk64, bool have64,
                 PoolKernel<ARD, SEPI> step, const typename SEPI::Args& sv) {
@@ -721,6 +721,55 @@ int gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const fl
     k_bv_init<<<ceil_div(T, 256), 256, 0, st>>>(v.b, ystar, T);
     return c.ard ? pool_greedy<true, GibbonEpilogue>(c, pa, pool, v, v.b, k_gb_walk64<true>, have64)
                  : pool_greedy<false, GibbonEpilogue>(c, pa, pool, v, v.b, k_gb_walk64<false>, have64);
+}
+
+// adkf_levelset_pool: the scratch is the believer's (bv_scratch), then four 64-bit accumulators per task
+struct LsScratch { BvScratch b; unsigned long long* acc; size_t bytes; };
+inline LsScratch ls_scratch(void* base, int T, int ns, int d, int q) {
+    LsScratch l{};
+    l.b = bv_scratch(base, T, ns, d, q);
+    Arena ar{static_cast<char*>(base), l.b.bytes};
+    l.acc = ar.as<unsigned long long>((size_t)T * 4);
+    l.bytes = ar.off;
+    return l;
+}
+
+// adkf_levelset_pool: isotropic and ARD batches alike (as adkf_gibbon_pool)
+int levelset_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* tau, const float* beta,
+                  int32_t score, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int8_t* cls, int64_t* counts,
+                  float* hits, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, int32_t* info, void* ws, size_t ws_bytes,
+                  void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags & ~ADKF_PM_MAXIMIZE) return ADKF_E_BADARG;
+    if (score < ADKF_LS_STRADDLE || score > ADKF_LS_BOUND) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
+    if (!tau || !beta || !sel_idx || !sel_val) return ADKF_E_BADARG;
+    if (q < 1) return ADKF_E_BADARG;
+    if (q > ADKF_POOL_TOPK_MAX) return ADKF_E_SIZE;
+    if ((counts || hits) && rows > ((int64_t)1 << 31)) return ADKF_E_SIZE;   // (below that the fixed-point sum cannot wrap)
+    const LsScratch l = ls_scratch(scratch, b->T, b->ns_max, b->d, q);
+    if ((rc = check_scratch(scratch, scratch_bytes, l.bytes))) return rc;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    hipStream_t st = c.st;
+    const int T = b->T;
+    PmArgs pa = pm_args(c, flags, X, rows, info);
+    const bool have64 = pm_have64(c, pa);
+    PmPool pool = pm_pool(excl_idx, excl_off, 1, T, l.b.cand.idx, l.b.cand.val, rows, st);
+    LsArgs v{};
+    v.b = bv_args(l.b, have64, q, trace, sel_idx, sel_val, sel_mean, sel_var);
+    v.tau = tau; v.beta = beta; v.kind = score; v.cls = cls;
+    v.acc = (counts || hits) ? l.acc : nullptr; v.counts = counts; v.hits = hits;
+    // skipped tasks keep zeros in trace, counts and hits, and "not evaluated" in cls
+    if (trace && rows > 0) hipMemsetAsync(trace, 0, sizeof(float) * (size_t)T * q * (size_t)rows, st);
+    if (cls && rows > 0) hipMemsetAsync(cls, 0xff, (size_t)T * (size_t)rows, st);
+    if (counts) hipMemsetAsync(counts, 0, sizeof(int64_t) * (size_t)T * q * 3, st);
+    if (hits) hipMemsetAsync(hits, 0, sizeof(float) * (size_t)T * q, st);
+    k_ls_init<<<ceil_div(T, 256), 256, 0, st>>>(v, T);
+    return c.ard ? pool_greedy<true, LsEpilogue, LsEpilogue>(c, pa, pool, v, v.b, k_ls_walk64<true>, have64, k_ls_step<true>, v)
+                 : pool_greedy<false, LsEpilogue, LsEpilogue>(c, pa, pool, v, v.b, k_ls_walk64<false>, have64, k_ls_step<false>, v);
 }
 
 // adkf_kg_pool: the scratch is the reference state - w [T, M, ns] (and its float64 twin where a workspace of this shape can have a

@@ -249,6 +249,33 @@ def _fitted_support(model, mb: MetaBatch, max_evals: int, what: str):
     return b, phi
 
 
+@torch.no_grad()
+def find_actives(model, mb: MetaBatch, X_features: torch.Tensor, tau, beta=1.96, q: int = 0, maximize: bool = True, exclude=None,
+                 max_evals: int = 200):
+    """Thresholded screening: every task of ``mb`` is fitted on its support set, then sorts the SAME library ``X_features [rows, d]``
+    (rows in the model's feature space) against the threshold ``tau`` (a scalar or ``[T]``) in one ``gp_ops.levelset_pool`` call -
+    ``screen``'s twin for "which rows are active, how many are there, and what must I measure to decide the rest".  A row is active
+    (0) or inactive (1) when its confidence band ``m +- beta sigma`` lies wholly on one side of tau (above it means active with
+    ``maximize``, below it without) and undecided (2) while the band holds tau.  Returns (cls [T, rows] int8, counts [T, 3] int64,
+    hits [T], sel_idx [T, q] int64, counts_after [T, 3], phi*): the class of every row (-1: not evaluated), the number of active,
+    inactive and undecided rows, the expected number of actives ``sum_r Phi(+-(m - tau) / sigma)``, the ``q`` (at most 63) rows whose
+    labels would settle the most - a straddle batch, each pick shrinking its neighbours' bands before the next is taken - and the
+    counts that batch would leave if every pick came back at its posterior mean (``counts`` itself with ``q = 0``).  ``exclude``:
+    rows a task may not pick (``gp_ops.pack_exclude``); they are classified and counted all the same."""
+    from . import gp_ops
+
+    q = gp_ops._in_range(q, 0, gp_ops._lib.POOL_TOPK_MAX - 1, "q")
+    was_training = model.training
+    model.eval()
+    b, phi = _fitted_support(model, mb, max_evals, "level-set")
+    out = gp_ops.levelset_pool(b, phi, X_features, tau=tau, beta=beta, q=q + 1, score="straddle", maximize=maximize, exclude=exclude,
+                               want_cls=True)
+    gp_ops.check_info(out["info"], "level-set estimation")
+    if was_training:
+        model.train()
+    return out["cls"], out["counts"][:, 0], out["hits"][:, 0], out["sel_idx"][:, :q], out["counts"][:, q], phi
+
+
 def predict_intervals(model, mb: MetaBatch, X_features: torch.Tensor, alpha=0.1, scaled: bool = True, k: int = 0, maximize: bool = True,
                       max_evals: int = 200):
     """How far the predictions can be trusted: every task of ``mb`` is fitted on its support set, then gives every row of the SAME

@@ -768,6 +768,65 @@ def gibbon_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, ystar: torch.
     return dict(sel_idx=sel_idx, sel_val=sel_val, sel_mean=sel_mean, sel_var=sel_var, trace=trace, info=info)
 
 
+_LS_SCORES = {"straddle": _lib.LS_STRADDLE, "prob": _lib.LS_PROB, "bound": _lib.LS_BOUND}
+
+
+def _per_task(b, value, name: str) -> torch.Tensor:
+    """A scalar or ``[T]`` values as float32 ``[T]`` on the batch's device."""
+    if torch.is_tensor(value):
+        t = value.detach().to(device=b.device, dtype=torch.float32).reshape(-1)
+    else:
+        t = torch.as_tensor(value, dtype=torch.float32).reshape(-1).to(b.device)
+    if t.numel() == 1:
+        t = t.expand(b.T)
+    if t.numel() != b.T:
+        raise ValueError(f"{name} must be a scalar or have T = {b.T} entries, got {t.numel()}")
+    return t.contiguous()
+
+
+def levelset_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, tau, beta=1.96, q: int, score: str = "straddle", maximize: bool = False,
+                  exclude=None, want_trace: bool = False, want_cls: bool = False, want_counts: bool = True):
+    """Level-set estimation and batch UCB per task over the shared pool ``X [rows, d]`` in one ``adkf_levelset_pool`` call, for
+    isotropic and ARD batches alike: which rows are on the active side of the threshold ``tau`` (``f > tau`` with ``maximize``,
+    ``f < tau`` without), how many actives the pool is expected to hold, and ``q`` (at most 64) sequential-greedy picks of what to
+    measure next.  ``tau`` and ``beta`` (the width of the confidence band, at least 0) are a scalar or ``[T]``.  With ``sigma_j`` the
+    latent deviation of a row given the picks made so far (each pick hallucinated at its mean, as ``believer_pool`` does: the mean
+    never moves) the score of a row at step j is, by ``score``:
+    ``"straddle"``  ``beta sigma_j - |m - tau|`` (Bryan et al. 2005), positive exactly when the band ``m +- beta sigma_j`` holds tau;
+    ``"prob"``      ``log Phi(+-(m - tau) / sigma_j)``, the log probability of being active - it does NOT diversify: the batch is the
+    rows most certainly active if the earlier picks land on their means;
+    ``"bound"``     ``+-m + beta sigma_j``: UCB with ``maximize``, minus LCB without (GP-BUCB; ``tau`` is not used by the score).
+    A row is *undecided* (2) while its straddle is positive, otherwise *active* (0) or *inactive* (1) by the side of tau its mean is on.
+    Returns ``dict(sel_idx, sel_val, sel_mean, sel_var, counts, hits, cls, trace, info)``: ``sel_*  [T, q]`` as ``believer_pool``
+    returns them; ``counts [T, q, 3]`` (int64) the number of active, inactive and undecided rows of the whole pool at each step and
+    ``hits [T, q]`` the expected number of actives ``sum_r Phi(z_j)`` (``want_counts``, else None; at steps j > 0 both are
+    hallucinated like the picks - ask for ``q + 1`` steps and drop the last pick to see the counts after a batch of q);
+    ``cls [T, rows]`` (int8, ``want_cls``) the class at step 0, -1 for a row that was not evaluated; ``trace [T, q, rows]``
+    (``want_trace``) every score; ``info [T]``.  A task whose ``tau`` is not finite or whose ``beta`` is negative or not finite
+    scores NaN everywhere: no pick, zero counts.  ``exclude``: rows a task may not select (``pack_exclude``); they are still counted."""
+    lib = _lib.load()
+    _support_only(b, "levelset_pool")
+    if score not in _LS_SCORES:
+        raise ValueError(f"score must be one of {sorted(_LS_SCORES)}, got {score!r}")
+    q = _in_range(q, 1, _lib.POOL_TOPK_MAX, "q")
+    tau, beta = _per_task(b, tau, "tau"), _per_task(b, beta, "beta")
+    phi, X = _phi_and_pool(b, phi, X)
+    rows = X.shape[0]
+    _on_device(b, X=X)
+    excl_idx, excl_off = _exclusion(b, exclude, b.T, rows)
+    sel_idx, sel_val, info = _selection(b, b.T, q)
+    sel_mean, sel_var = _new(b, b.T, q), _new(b, b.T, q)
+    trace = _new(b, b.T, q, rows) if want_trace else None
+    cls = _new(b, b.T, rows, dtype=torch.int8) if want_cls else None
+    counts = _new(b, b.T, q, 3, dtype=torch.int64) if want_counts else None
+    hits = _new(b, b.T, q) if want_counts else None
+    args = (ptr(tau), ptr(beta), _LS_SCORES[score], ptr(excl_idx), ptr(excl_off), q, ptr(trace), ptr(cls), ptr(counts), ptr(hits),
+            ptr(sel_idx), ptr(sel_val), ptr(sel_mean), ptr(sel_var))
+    _pool_call(lib, "adkf_levelset_pool", b, phi, _lib.PM_MAXIMIZE if maximize else 0, X, args, info,
+               lib.adkf_levelset_pool_scratch_bytes(b.T, b.ns, b.d, q))
+    return dict(sel_idx=sel_idx, sel_val=sel_val, sel_mean=sel_mean, sel_var=sel_var, counts=counts, hits=hits, cls=cls, trace=trace, info=info)
+
+
 def kg_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, ref_idx: Optional[torch.Tensor] = None, n_refs: int = 32,
             maximize: bool = False, log: bool = False, topk: int = 0, exclude=None, want_score: bool = True, want_cov: bool = False):
     """The knowledge gradient for correlated beliefs (Frazier, Powell & Dayanik 2009; Scott, Frazier & Powell 2011) over the shared

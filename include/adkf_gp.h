@@ -509,6 +509,67 @@ int adkf_gibbon_pool(const adkf_batch_t* b, const float* phi, int32_t flags, con
 size_t adkf_liar_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t q);
 int adkf_liar_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f, const float* lie, const float* labels, int64_t label_stride, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, float* sel_lie, float* inc, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Level-set estimation and batch UCB over a shared pool (csrc/levelset_stream.h; the straddle of Bryan et al. 2005, the classification
+ * of Gotovos et al. 2013, GP-BUCB of Desautels, Krause and Burdick 2014): per task, against a threshold tau[t] with a confidence band
+ * of width beta[t], which rows of the SAME pool X [rows, d] are on the active side of tau, how many actives the pool is expected to
+ * hold, and q sequential-greedy picks of what to measure next.  It also supplies the two acquisitions that take a parameter instead
+ * of an incumbent: probability of improvement over a threshold, and the upper / lower confidence bound.
+ *   The quantity.  m(x) and v_0(x) adkf_predict_pool's mean and latent variance; v_j(x) = v_0(x) - sum_(i<j) ell_i(x)^2 the downdated
+ *          latent variance of adkf_believer_pool after the picks p_0 .. p_(j-1) (w_i, c0, G and ell as there); sigma_j =
+ *          sqrt(max(v_j, 1e-12)) as everywhere; s = +1 with ADKF_PM_MAXIMIZE (active means f > tau) and -1 without (active means
+ *          f < tau, the minimisation default of every other entry); z_j(x) = s (m - tau) / sigma_j.
+ *              straddle_j(x) = beta sigma_j - |m - tau|         > 0 exactly when the band m +- beta sigma_j holds tau
+ *              ADKF_LS_STRADDLE   score_j = straddle_j
+ *              ADKF_LS_PROB       score_j = log Phi(z_j)        unclamped: the ranking survives where float32 Phi is 0, as log EI does
+ *              ADKF_LS_BOUND      score_j = s m + beta sigma_j  UCB with ADKF_PM_MAXIMIZE, -(LCB) without
+ *          The class of a row at step j, in this order: undecided if straddle_j > 0; otherwise active if s (m - tau) > 0; otherwise
+ *          inactive.  Whatever the score, the class is decided from the same float32 straddle_j that an ADKF_LS_STRADDLE call
+ *          stores in trace, formed as fmaf(beta, sigma_j, -|m - tau|) (tasks on the float64 path: from the float32-rounded mean and
+ *          variance by the same function).  hits_j = sum over the pool rows of Phi(z_j) is the expected number of actives.
+ *          A row whose mean or variance is NaN belongs to no class, adds nothing to hits and has score NaN.
+ *          The picks are hallucinated: a GP's variance does not depend on the labels, so the mean never moves and every pick only
+ *          downdates the variance.  Counts and hits at steps j > 0 are hallucinated in the same sense: "if the earlier picks land on
+ *          their means".  ADKF_LS_PROB does NOT diversify: for a row beyond tau the probability rises as its variance falls, so its
+ *          batch is the rows most certainly active given the earlier picks, not a spread over the pool.
+ *          p_j is the eligible row of largest score_j, equal scores going to the lowest row index (the total order of
+ *          adkf_predict_pool).  A row is eligible unless it is listed in excl_idx[excl_off[t] .. excl_off[t + 1]) (nullable), it is one
+ *          of p_0 .. p_(j-1), or its score is NaN.  With no eligible row at step j, that step and all later ones report -1 / -inf (0
+ *          in sel_mean / sel_var) and the state stops changing.  A pick counts when its index is not -1 and its value is finite.
+ *   b      support-only, of either kind (as adkf_gibbon_pool): with ADKF_BATCH_ARD in b->flags phi is [T, 2 + d] and ws has
+ *          adkf_workspace_bytes_ard(T, ns_max, 0, d) bytes; without it [T, 3] and adkf_workspace_bytes(T, ns_max, 0, d).  REUSE_DIST /
+ *          REUSE_INNER mean what they mean for adkf_predict_pool.
+ *   flags  ADKF_PM_MAXIMIZE only.  The variance is always the latent one: ADKF_PM_LATENT is refused like any other bit.
+ *   tau, beta   [T], required.  A tau[t] that is not finite, or a beta[t] that is NaN, infinite or negative, cannot be refused by the
+ *          host (the values live on the device): every score of task t is NaN, nothing is picked, its counts and hits are 0 and
+ *          its cls is -1.
+ *   score  ADKF_LS_STRADDLE, ADKF_LS_PROB or ADKF_LS_BOUND.
+ *   q      1 <= q <= ADKF_POOL_TOPK_MAX.  A caller who wants the counts AFTER a batch of q asks for q + 1 steps and drops the last pick.
+ *   trace  nullable, [T, q, rows] with element (t, j, r) at (t q + j) rows + r: score_j of every row, eligible or not.
+ *   cls    nullable, [T, rows] int8: the class at step 0.  0 = active, 1 = inactive, 2 = undecided, -1 = not evaluated (a NaN row, and
+ *          the whole slice of a skipped task).
+ *   counts nullable, [T, q, 3] int64: at step j the number of active, inactive and undecided pool rows given the picks before it.  It
+ *          covers ALL rows: excluded and picked rows are counted too.
+ *   hits   nullable, [T, q]: hits_j, the 2^-31 fixed-point sum (adkf_gumbel_pool's format) of the float32 Phi terms, integer adds
+ *          only, converted once at the end (u64 to double to float).  The rounding of the sum is at most rows 2^-32.
+ *   sel_idx, sel_val   [T, q], required: the pick of each step and its score.
+ *   sel_mean, sel_var  [T, q], each nullable: m(x_(p_j)), which never moves, and v_j(x_(p_j)).
+ *   Tasks with n_s == 0 or info != 0: -1 / -inf in every step, zeros in sel_mean, sel_var, trace, counts and hits, cls = -1.
+ *   scratch   adkf_levelset_pool_scratch_bytes(T, ns_max, d, q) bytes, 8-byte aligned, a function of (T, ns_max, d, q) only: the
+ *          believer's state with the believer's layout, then four 64-bit accumulators per task.
+ * Nothing of size T x rows exists unless trace or cls is given.  Asynchronous on `stream`, no allocation, no synchronisation,
+ * capturable.  The class counts and the Phi sum are accumulated with integer adds and integer atomics only - no floating-point
+ * atomics - so the call is reproducible to the bit, and a task's counts and hits are the same bits alone or in a batch, on any grid,
+ * and under any permutation of the pool's rows.
+ * Rejected before anything is launched, ADKF_E_BADARG unless noted: a batch with a query set; any flag bit other than
+ * ADKF_PM_MAXIMIZE; score outside 0 .. 2; rows < 0; rows > 0 without X; a missing tau, beta, sel_idx, sel_val, info or ws; excl_idx
+ * without excl_off; q < 1; q > ADKF_POOL_TOPK_MAX (ADKF_E_SIZE); rows > 2^31 with counts or hits (ADKF_E_SIZE: below that the
+ * fixed-point sum cannot wrap); a workspace or a scratch that is too small (ADKF_E_WORKSPACE); a scratch that is not 8-byte aligned. */
+#define ADKF_LS_STRADDLE 0
+#define ADKF_LS_PROB 1
+#define ADKF_LS_BOUND 2
+size_t adkf_levelset_pool_scratch_bytes(int32_t T, int32_t ns_max, int32_t d, int32_t q);
+int adkf_levelset_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* tau, const float* beta, int32_t score, const int64_t* excl_idx, const int64_t* excl_off, int32_t q, float* trace, int8_t* cls, int64_t* counts, float* hits, int64_t* sel_idx, float* sel_val, float* sel_mean, float* sel_var, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Knowledge-gradient selection over a shared pool (csrc/kg_stream.h; Frazier, Powell and Dayanik 2009; Scott, Frazier and Powell
  * 2011, "KGCP"; the single-step form of BoTorch's qKnowledgeGradient on a discrete set): every row of the SAME pool X [rows, d] is
  * scored, per task, by how much one noisy observation there is expected to raise the best posterior mean over the row itself and a
