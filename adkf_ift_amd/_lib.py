@@ -36,6 +36,9 @@ TS_FEATURES_MAX = 4096   # ... random Fourier features (a multiple of 64, at lea
 LS_STRADDLE, LS_PROB, LS_BOUND = 0, 1, 2   # adkf_levelset_pool: the score kinds
 QEI_SAMPLES_MAX = 256    # adkf_qei_pool: posterior draws per task
 QEI_PICKS_MAX = 64       # ... picks per task
+RANK_K_MAX = 65536       # adkf_rank_pool: rows listed per task
+RANK_REFS_MAX = 1024     # ... rows ranked per task
+RANK_CHUNK_ROWS = 16384  # ... pool rows per chunk of its walk
 
 ERRORS = {-1: "bad argument", -2: "unsupported size (see adkf_max_points)", -3: "workspace too small",
           -4: "HIP launch failed"}
@@ -146,6 +149,10 @@ SIGNATURES = {
     "adkf_mix_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adkf_rank_pool_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "adkf_rank_pool": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_outer_nll_value_grad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adkf_ift_hypergrad": (C.c_int, [C.POINTER(Batch), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -38,6 +38,7 @@
 #include "jackknife_stream.h"
 #include "ehvi_stream.h"
 #include "mix_stream.h"
+#include "rank_stream.h"
 #include "qei_stream.h"
 
 #include "host_common.h"
@@ -415,6 +416,19 @@ int adkf_ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const
                    void* scratch, size_t scratch_bytes, void* stream) {
     return ehvi_pool(b, phi, flags, X, rows, G, obj, obj_max, ref, front, front_n, P, con, con_thr, con_geq, C, excl_idx, excl_off, score,
                      stair, stair_n, k, top_idx, top_val, info, ws, ws_bytes, scratch, scratch_bytes, stream);
+}
+
+size_t adkf_rank_pool_scratch_bytes(int32_t T, int32_t k, int32_t M, int32_t d) {
+    if (T <= 0 || k < 0 || k > ADKF_RANK_K_MAX || M < 0 || M > ADKF_RANK_REFS_MAX || d <= 0) return 0;
+    return rank_scratch(nullptr, T, k, M, d).bytes;
+}
+
+int adkf_rank_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
+                   const int64_t* excl_idx, const int64_t* excl_off, int32_t k, int64_t* top_idx, float* top_val, const int64_t* ref_idx,
+                   int32_t M, int64_t* ref_rank, float* ref_val, int64_t* n_ranked, int32_t* info, void* ws, size_t ws_bytes, void* scratch,
+                   size_t scratch_bytes, void* stream) {
+    return rank_pool(b, phi, flags, X, rows, best_f, excl_idx, excl_off, k, top_idx, top_val, ref_idx, M, ref_rank, ref_val, n_ranked, info,
+                     ws, ws_bytes, scratch, scratch_bytes, stream);
 }
 
 size_t adkf_mix_pool_scratch_bytes(int32_t T, int32_t G, int32_t k) {

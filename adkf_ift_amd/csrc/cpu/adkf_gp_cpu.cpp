@@ -477,7 +477,7 @@ bool pm_task(const adkf_batch_t* b, const float* phi, int t, const float* Zq, in
 //   row_posterior (above)              pm_row (predict_marginal, predict_pool, gumbel, mix), mes, jackknife, ehvi, and pool_state
 //   PoolState, pool_state, c0_col      believer / gibbon, kg, ipv, jes: K, K A^-1, mean and latent variance of every row, c0(x_r, x_p)
 //   excl_range (Excl::has)             select_topk, greedy_pick and Thompson's per-row test
-//   init_topk, select_topk             predict_pool, mes, kg, jes, jackknife, ehvi and mix (per group); init_topk also the sel_* fills
+//   init_topk, select_topk             predict_pool, mes, kg, jes, jackknife, ehvi and mix (per group), rank (alone without check_topk's cap); init_topk also the sel_* fills
 //   greedy_pick, append_pick           believer / gibbon / liar (step j) and ipv (pick c)
 //   valid_entry                        kg (references) and ipv (targets)
 //   prepare_task, task_row_dist        pm_task_state and PathDraws (thompson_pool, qei_pool)
@@ -1816,6 +1816,53 @@ int adkf_ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const
         }
         if (score) std::copy(sc.begin(), sc.end(), score + (size_t)g * R);
         if (!bad && k > 0) select_topk(sc, rows, k, excl_range(excl_idx, excl_off, g), top_idx + (size_t)g * k, top_val + (size_t)g * k);
+    }
+    return 0;
+}
+
+size_t adkf_rank_pool_scratch_bytes(int32_t, int32_t, int32_t, int32_t) { return 0; }
+
+// Large-k selection and row ranks (include/adkf_gp.h): adkf_predict_pool's score on every row, select_topk without the cap of 64, and
+// for a named row the number of eligible rows that come before it in select_topk's order.
+int adkf_rank_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f,
+                   const int64_t* excl_idx, const int64_t* excl_off, int32_t k, int64_t* top_idx, float* top_val, const int64_t* ref_idx,
+                   int32_t M, int64_t* ref_rank, float* ref_val, int64_t* n_ranked, int32_t* info, void*, size_t, void*, size_t, void*) {
+    if (int rc = check_support_only(b, phi, info, rows, ARD_EITHER)) return rc;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    const bool by_mean = (flags & ADKF_PM_SCORE_MEAN) != 0;
+    if (by_mean && (flags & ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    if (k < 0 || M < 0) return ADKF_E_BADARG;
+    if (k > ADKF_RANK_K_MAX || M > ADKF_RANK_REFS_MAX) return ADKF_E_SIZE;
+    if (!by_mean && !best_f) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (M > 0 && (!ref_idx || !ref_rank || !ref_val)) return ADKF_E_BADARG;
+    if (k == 0 && M == 0 && !n_ranked) return ADKF_E_BADARG;
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        init_topk(top_idx, top_val, t, k);
+        for (int j = 0; j < M; ++j) { ref_rank[(size_t)t * M + j] = -1; ref_val[(size_t)t * M + j] = std::numeric_limits<float>::quiet_NaN(); }
+        if (n_ranked) n_ranked[t] = 0;
+        std::vector<float> sc((size_t)rows);
+        const bool done = pm_task(b, phi, t, X, 0, rows, info, [&](int64_t r, const Inner& in, const double* D) {
+            float m1, e1 = 0.f;
+            pm_row(in, b->kernel, D, b->y_s + (size_t)t * b->ns_max, flags, best_f, t, 0, &m1, nullptr, by_mean ? nullptr : &e1);
+            sc[r] = by_mean ? ((flags & ADKF_PM_MAXIMIZE) ? m1 : -m1) : e1;
+        });
+        if (!done) continue;
+        const Excl excl = excl_range(excl_idx, excl_off, t);
+        if (k > 0) select_topk(sc, rows, k, excl, top_idx + (size_t)t * k, top_val + (size_t)t * k);
+        std::vector<char> ok((size_t)rows);
+        int64_t n = 0;
+        for (int64_t r = 0; r < rows; ++r) n += (ok[r] = sc[r] == sc[r] && !excl.has(r));
+        if (n_ranked) n_ranked[t] = n;
+        for (int j = 0; j < M; ++j) {
+            const int64_t p = ref_idx[(size_t)t * M + j];
+            if (p < 0 || p >= rows || sc[p] != sc[p]) continue;
+            int64_t c = 0;
+            for (int64_t r = 0; r < rows; ++r) c += ok[r] && (sc[r] > sc[p] || (sc[r] == sc[p] && r < p));
+            ref_rank[(size_t)t * M + j] = c; ref_val[(size_t)t * M + j] = sc[p];
+        }
     }
     return 0;
 }

@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_liar_pool, adkf_levelset_pool, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ipv_pool, adkf_jackknife_pool, adkf_ehvi_pool, adkf_mix_pool and adkf_qei_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_liar_pool, adkf_levelset_pool, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ipv_pool, adkf_jackknife_pool, adkf_ehvi_pool, adkf_mix_pool, adkf_rank_pool and adkf_qei_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
 // pool calls share (pool_walks, pool_select, pool_greedy) and the body of every entry.
 #pragma once
 #include "host_ard.h"
@@ -1252,6 +1252,101 @@ int mix_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float
     // prediction's flags: without an EI plane LOG_EI has no reader there (and prediction refuses nothing here: pm_launch checks no flag)
     const int32_t pm_flags = flags & (ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | (want_ei ? ADKF_PM_LOG_EI : 0));
     return c.ard ? mix_launch<true>(c, e, pm_flags, best_f, X, rows, info) : mix_launch<false>(c, e, pm_flags, best_f, X, rows, info);
+}
+
+// adkf_rank_pool: the scratch is the score plane of one chunk of the pool [T, RANK_CHUNK_ROWS], two sorted lists per task ([2, T, k]
+// rows, then [2, T, k] scores) with the tasks' marks (which list is current, and its length: int32 [2, T]), the refs' rows as a packed
+// query set [T * M, d] with prediction's mean and EI of them ([T * M] each) and its offsets [T + 1].  The ranks are counted in
+// ref_rank and n_ranked themselves.  Every part is rounded up to 256 bytes; nothing depends on rows or ns.
+struct RankScratch { float* plane; int64_t* list_idx; float* list_val; int32_t* mark; float *Xg, *gmean, *gei; int64_t* q_off; size_t bytes; };
+inline RankScratch rank_scratch(void* base, int T, int k, int M, int d) {
+    Arena ar{static_cast<char*>(base), 0};
+    const size_t tm = (size_t)T * M;
+    RankScratch l{};
+    l.plane = ar.floats((size_t)T * RANK_CHUNK_ROWS);
+    l.list_idx = ar.as<int64_t>((size_t)2 * T * k);
+    l.list_val = ar.floats((size_t)2 * T * k);
+    l.mark = ar.as<int32_t>((size_t)2 * T);
+    l.Xg = ar.floats(tm * d);
+    l.gmean = ar.floats(tm);
+    l.gei = ar.floats(tm);
+    l.q_off = ar.as<int64_t>((size_t)T + 1);
+    l.bytes = ar.off;
+    return l;
+}
+static_assert(RANK_K_MAX == ADKF_RANK_K_MAX && RANK_REFS_MAX == ADKF_RANK_REFS_MAX && RANK_CHUNK_ROWS == ADKF_RANK_CHUNK_ROWS &&
+              RANK_CHUNK_ROWS % PM_TM == 0, "rank_stream.h limits");
+
+// The launches of a prepared ranking call: the refs' rows through prediction's packed launch (M > 0), the tasks' state, then per chunk
+// of the pool prediction's own pool launch (the plane the score reads into the scratch, no selection) and k_rank_chunk; at the end
+// the lists go to top_*.  pm_flags: the caller's LATENT, MAXIMIZE and LOG_EI; by_mean: the score is +-mean.
+template <bool ARD>
+int rank_launch(const PmCtx& c, RankArgs& e, int32_t pm_flags, bool by_mean, const float* best_f, int32_t* info) {
+    hipStream_t st = c.st;
+    const int T = c.b.T;
+    const int64_t rows = e.rows;
+    if (e.M > 0) {
+        k_rank_gather<<<(unsigned)((size_t)T * e.M), 64, 0, st>>>(e);
+        const PmCall io{pm_flags, e.Xg, e.q_off, (int64_t)T * e.M, by_mean ? nullptr : best_f, e.gmean, nullptr, by_mean ? nullptr : e.gei, info, nullptr};
+        const int rc = pm_launch<ARD, false>(c, io);
+        if (rc) return rc;
+    }
+    // (info and n_s are read here and in every chunk: pm_prepare has written info, and nothing below writes it again)
+    const PmArgs pa = pm_args(c, 0, e.X, rows, info);
+    k_rank_refs<<<T, RANK_NT, 0, st>>>(pa, e);
+    float* plane = const_cast<float*>(e.plane);
+    for (int64_t c0 = 0; c0 < rows; c0 += RANK_CHUNK_ROWS) {
+        const int64_t L = std::min<int64_t>(RANK_CHUNK_ROWS, rows - c0);
+        PmPool none = pm_pool(nullptr, nullptr, 0, T, nullptr, nullptr, L, st);
+        const PmCall io{pm_flags, e.X + (size_t)c0 * c.b.d, nullptr, L, by_mean ? nullptr : best_f, by_mean ? plane : nullptr, nullptr,
+                        by_mean ? nullptr : plane, info, &none};
+        // the whole of prediction's sequence per chunk, as ehvi_launch runs it and for its reason
+        const int rc = pm_launch<ARD, true>(c, io);
+        if (rc) return rc;
+        e.c0 = c0; e.L = L;
+        k_rank_chunk<<<T, RANK_NT, 0, st>>>(pa, e);
+    }
+    if (e.k > 0) k_rank_finish<<<T, RANK_NT, 0, st>>>(e);
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_rank_pool: isotropic and ARD batches alike (as adkf_mix_pool)
+int rank_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f, const int64_t* excl_idx,
+              const int64_t* excl_off, int32_t k, int64_t* top_idx, float* top_val, const int64_t* ref_idx, int32_t M, int64_t* ref_rank,
+              float* ref_val, int64_t* n_ranked, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_SCORE_MEAN | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    const bool by_mean = flags & ADKF_PM_SCORE_MEAN;
+    if (by_mean && (flags & ADKF_PM_LOG_EI)) return ADKF_E_BADARG;   // nothing would read it
+    if (k < 0 || M < 0) return ADKF_E_BADARG;
+    if (k > ADKF_RANK_K_MAX || M > ADKF_RANK_REFS_MAX) return ADKF_E_SIZE;
+    if (!by_mean && !best_f) return ADKF_E_BADARG;
+    if (!pool_args_ok(X, rows, excl_idx, excl_off)) return ADKF_E_BADARG;
+    if (k > 0 && (!top_idx || !top_val)) return ADKF_E_BADARG;
+    if (M > 0 && (!ref_idx || !ref_rank || !ref_val)) return ADKF_E_BADARG;
+    if (k == 0 && M == 0 && !n_ranked) return ADKF_E_BADARG;
+    const RankScratch l = rank_scratch(scratch, b->T, k, M, b->d);
+    if (!scratch) return ADKF_E_BADARG;
+    // (a misaligned scratch is a short one here: its aligned part does not hold the bytes)
+    if (scratch_bytes < l.bytes || (reinterpret_cast<uintptr_t>(scratch) & 7u)) return ADKF_E_WORKSPACE;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    RankArgs e{};
+    e.T = b->T; e.k = k; e.M = M;
+    e.neg = (by_mean && !(flags & ADKF_PM_MAXIMIZE)) ? 1 : 0;
+    e.count = (M > 0 || n_ranked) ? 1 : 0;
+    e.plane = l.plane; e.rows = rows;
+    e.excl_idx = excl_off ? excl_idx : nullptr; e.excl_off = excl_off;
+    e.list_idx = l.list_idx; e.list_val = l.list_val; e.cur = l.mark; e.cnt = l.mark + b->T;
+    e.ref_idx = ref_idx; e.ref_rank = ref_rank; e.ref_val = ref_val; e.n_ranked = n_ranked;
+    e.top_idx = top_idx; e.top_val = top_val;
+    e.X = X; e.d = b->d; e.Xg = l.Xg; e.gmean = l.gmean; e.gei = by_mean ? nullptr : l.gei; e.q_off = l.q_off;
+    // prediction's flags: the mean score reads no EI plane (and prediction refuses nothing here: pm_launch checks no flag)
+    const int32_t pm_flags = flags & (ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI);
+    return c.ard ? rank_launch<true>(c, e, pm_flags, by_mean, best_f, info) : rank_launch<false>(c, e, pm_flags, by_mean, best_f, info);
 }
 
 }  // namespace

@@ -180,9 +180,10 @@ def meta_test(model, mb: MetaBatch, max_evals: int = 200, gtol: float = 1e-5, ft
 @torch.no_grad()
 def screen(model, mb: MetaBatch, X_features: torch.Tensor, k: int, maximize: bool = True, max_evals: int = 200):
     """Virtual screening: every task of ``mb`` is fitted on its support set, then ranks the SAME library ``X_features [rows, d]``
-    (rows in the model's feature space) by posterior mean in one ``gp_ops.predict_pool`` call.  Returns (top_idx [T, k] int64,
-    top_val [T, k], phi*): each task's ``k`` (at most 64) best rows, best first (largest mean with ``maximize``, smallest
-    without; ``top_val`` is +mean / -mean accordingly).  Nothing of size T x rows is allocated."""
+    (rows in the model's feature space) by posterior mean in one ``gp_ops.predict_pool`` call, or beyond 64 rows per task in one
+    ``gp_ops.rank_pool`` call.  Returns (top_idx [T, k] int64, top_val [T, k], phi*): each task's ``k`` (at most 65536) best rows,
+    best first (largest mean with ``maximize``, smallest without; ``top_val`` is +mean / -mean accordingly).  Nothing of size
+    T x rows is allocated."""
     from . import gp_ops
 
     cfg = model.config
@@ -197,7 +198,10 @@ def screen(model, mb: MetaBatch, X_features: torch.Tensor, k: int, maximize: boo
     phi, _, _, _, info = gp_ops.fit(b, phi0, max_evals)
     gp_ops.check_info(info, "screening inner fit")
     b.flags = gp_ops.REUSE_DIST | gp_ops.REUSE_INNER
-    out = gp_ops.predict_pool(b, phi, X_features, maximize=maximize, score="mean", want_mean=False, want_var=False, topk=k)
+    if int(k) <= gp_ops._lib.POOL_TOPK_MAX:
+        out = gp_ops.predict_pool(b, phi, X_features, maximize=maximize, score="mean", want_mean=False, want_var=False, topk=k)
+    else:
+        out = gp_ops.rank_pool(b, phi, X_features, maximize=maximize, score="mean", topk=k)
     gp_ops.check_info(out["info"], "screening prediction")
     if was_training:
         model.train()
@@ -274,6 +278,50 @@ def find_actives(model, mb: MetaBatch, X_features: torch.Tensor, tau, beta=1.96,
     if was_training:
         model.train()
     return out["cls"], out["counts"][:, 0], out["hits"][:, 0], out["sel_idx"][:, :q], out["counts"][:, q], phi
+
+
+def enrichment_from_ranks(ranks: torch.Tensor, n_ranked: torch.Tensor, fractions=(0.01, 0.05)) -> torch.Tensor:
+    """Enrichment factors from ranks (CPU tensors, pure torch): ``ranks [T, M]`` the 0-based ranks of each task's actives (-1: not
+    ranked), ``n_ranked [T]`` the rows each task ranked.  ``ef[t, f]`` is the share of task t's ranked actives with
+    ``rank < ceil(f * n_ranked[t])``, divided by ``f``: 1 for a random order, ``1 / f`` at most.  NaN for a task without ranked
+    actives.  Returns float64 ``[T, len(fractions)]``."""
+    ranks, n_ranked = torch.as_tensor(ranks).to(torch.int64), torch.as_tensor(n_ranked).to(torch.int64).reshape(-1)
+    if ranks.dim() != 2 or ranks.shape[0] != n_ranked.numel():
+        raise ValueError(f"ranks must be [T, M] with n_ranked [T], got {tuple(ranks.shape)} and {tuple(n_ranked.shape)}")
+    fractions = [float(f) for f in fractions]
+    if not fractions or any(not (0.0 < f <= 1.0) for f in fractions):
+        raise ValueError(f"fractions must lie in (0, 1], got {fractions}")
+    ranked = ranks >= 0
+    n_act = ranked.sum(1).double()
+    ef = torch.empty(ranks.shape[0], len(fractions), dtype=torch.float64)
+    for i, f in enumerate(fractions):
+        cut = torch.ceil(f * n_ranked.double()).to(torch.int64)
+        hits = (ranked & (ranks < cut[:, None])).sum(1).double()
+        ef[:, i] = hits / n_act / f   # (0 / 0: NaN)
+    return ef
+
+
+@torch.no_grad()
+def enrichment(model, mb: MetaBatch, X_features: torch.Tensor, actives, fractions=(0.01, 0.05), maximize: bool = True, exclude=None,
+               max_evals: int = 200):
+    """Retrospective screening: every task of ``mb`` is fitted on its support set as ``screen`` fits it, ranks the SAME library
+    ``X_features [rows, d]`` by posterior mean and reports where its known actives ``actives`` (``[T, M]`` int64 library indices or
+    T index lists, at most 1024 per task, -1: unused) come in that ranking, in one ``gp_ops.rank_pool`` call.  Returns (ranks [T, M]
+    int64, n_ranked [T] int64, ef [T, len(fractions)] float64 on the CPU, phi*): the 0-based rank of every active (-1: not ranked),
+    the rows each task ranked and the enrichment factors of ``enrichment_from_ranks``.  ``exclude``: rows a task leaves out of its
+    ranking (``gp_ops.pack_exclude``) - its own support rows, usually."""
+    from . import gp_ops
+
+    was_training = model.training
+    model.eval()
+    b, phi = _fitted_support(model, mb, max_evals, "enrichment")
+    out = gp_ops.rank_pool(b, phi, X_features, maximize=maximize, score="mean", rank_rows=actives, exclude=exclude)
+    gp_ops.check_info(out["info"], "enrichment ranking")
+    if was_training:
+        model.train()
+    ranks = out["ref_rank"] if out["ref_rank"] is not None else torch.empty(b.T, 0, dtype=torch.int64, device=b.device)
+    ef = enrichment_from_ranks(ranks.cpu(), out["n_ranked"].cpu(), fractions)
+    return ranks, out["n_ranked"], ef, phi
 
 
 def predict_intervals(model, mb: MetaBatch, X_features: torch.Tensor, alpha=0.1, scaled: bool = True, k: int = 0, maximize: bool = True,

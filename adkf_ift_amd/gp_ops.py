@@ -1213,6 +1213,63 @@ def mix_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, members, weights
     return dict(mean=mean, var=var, score=sc, top_idx=top_idx, top_val=top_val, info=info)
 
 
+def rank_pool(b: GPBatch, phi: torch.Tensor, X: torch.Tensor, *, best_f: Optional[torch.Tensor] = None, maximize: bool = False,
+              score: str = "ei", log_ei: bool = False, latent: bool = False, topk: int = 0, rank_rows=None, exclude=None):
+    """Large selections and row ranks over the shared pool ``X [rows, d]`` in one ``adkf_rank_pool`` call, for isotropic and ARD
+    batches alike: what a virtual screen asks beyond a BO batch.  The score, the eligibility and the order are ``predict_pool``'s
+    (``score``: ``"ei"``, which needs ``best_f [T]`` and is log EI with ``log_ei``, or ``"mean"``), but ``topk`` goes up to 65536
+    instead of 64, and ``rank_rows`` - a ``[T, M]`` int64 tensor, or a list of T index lists (padded with -1), M at most 1024 - names
+    rows whose place in each task's ranking is wanted: known actives, for enrichment factors.  Returns ``dict(top_idx, top_val,
+    ref_rank, ref_val, n_ranked, info)``: ``top_idx [T, topk]`` / ``top_val`` as ``predict_pool`` returns them (None with
+    ``topk == 0``), ``ref_rank [T, M]`` (int64) the number of eligible rows that come strictly before the named row - 0-based, so an
+    eligible row with ``ref_rank < topk`` is ``top_idx[t, ref_rank]``; an excluded row gets the place it would take; -1 for an entry
+    outside the pool or a NaN score - with ``ref_val`` that row's score (None, None without ``rank_rows``), ``n_ranked [T]`` (int64)
+    the rows a task ranked (neither excluded nor NaN), and ``info [T]``.  ``exclude``: rows a task may not list
+    (``pack_exclude``).  Nothing of size T x rows is allocated."""
+    lib = _lib.load()
+    _support_only(b, "rank_pool")
+    if score not in ("ei", "mean"):
+        raise ValueError(f"score must be 'ei' or 'mean', got {score!r}")
+    if log_ei and score != "ei":
+        raise ValueError("log_ei with score='mean': nothing would read it")
+    topk = _in_range(topk, 0, _lib.RANK_K_MAX, "topk")
+    if rank_rows is not None:
+        if not torch.is_tensor(rank_rows):
+            lists = [[int(i) for i in (l if l is not None else [])] for l in rank_rows]
+            width = max([len(l) for l in lists], default=0)
+            rank_rows = torch.tensor([l + [-1] * (width - len(l)) for l in lists], dtype=torch.int64).reshape(len(lists), width)
+        if rank_rows.dtype != torch.int64 or rank_rows.dim() != 2 or rank_rows.shape[0] != b.T:
+            raise ValueError(f"rank_rows must be an int64 tensor [T, M] = [{b.T}, M] or T index lists, got "
+                             f"{(tuple(rank_rows.shape), rank_rows.dtype)}")
+        _in_range(rank_rows.shape[1], 0, _lib.RANK_REFS_MAX, "the number of ranked rows M")
+        if rank_rows.shape[1] == 0:
+            rank_rows = None
+    if best_f is not None:
+        best_f = torch.as_tensor(best_f).float().reshape(-1)
+        if best_f.numel() != b.T:
+            raise ValueError(f"best_f must have T = {b.T} entries")
+    if score == "ei" and best_f is None:
+        raise ValueError("ranking by ei needs best_f [T]")
+    phi, X = _phi_and_pool(b, phi, X)
+    rows = X.shape[0]
+    dev = b.device
+    best_f = None if best_f is None else _f32(best_f.to(dev), "best_f")
+    _on_device(b, X=X)
+    M = 0 if rank_rows is None else rank_rows.shape[1]
+    ref_idx = None if rank_rows is None else rank_rows.to(dev).contiguous()
+    ref_rank = _new(b, b.T, M, dtype=torch.int64) if M else None
+    ref_val = _new(b, b.T, M) if M else None
+    n_ranked = _new(b, b.T, dtype=torch.int64)
+    excl_idx, excl_off = _exclusion(b, exclude, b.T, rows)
+    top_idx, top_val, info = _selection(b, b.T, topk)
+    flags = (_lib.PM_LATENT if latent else 0) | (_lib.PM_MAXIMIZE if maximize else 0) | (_lib.PM_SCORE_MEAN if score == "mean" else 0)
+    flags |= _lib.PM_LOG_EI if log_ei else 0
+    args = (ptr(best_f), ptr(excl_idx), ptr(excl_off), topk, ptr(top_idx), ptr(top_val), ptr(ref_idx), M, ptr(ref_rank), ptr(ref_val),
+            ptr(n_ranked))
+    _pool_call(lib, "adkf_rank_pool", b, phi, flags, X, args, info, lib.adkf_rank_pool_scratch_bytes(b.T, topk, M, b.d))
+    return dict(top_idx=top_idx, top_val=top_val, ref_rank=ref_rank, ref_val=ref_val, n_ranked=n_ranked, info=info)
+
+
 def replicate_batch(b: GPBatch, M: int):
     """``(bm, members)``: a support-only batch in which task t of ``b`` occupies the tasks ``t * M .. t * M + M - 1`` - the same
     data, ``n_s``, priors, kernel and ARD flag, no reuse flags (its workspace is its own) - and ``members = arange(T * M).view(T, M)``

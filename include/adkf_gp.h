@@ -874,6 +874,51 @@ int adkf_ehvi_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const
 size_t adkf_mix_pool_scratch_bytes(int32_t T, int32_t G, int32_t k);
 int adkf_mix_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, int32_t G, const int32_t* mem, const float* w, int32_t M, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, float* mean, float* var, float* score, int32_t k, int64_t* top_idx, float* top_val, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Large-k selection and row ranks over a shared pool (csrc/rank_stream.h): what a virtual screen asks beyond a BO batch.  Every task
+ * ranks the SAME pool X [rows, d] by adkf_predict_pool's score and returns its first k rows, k up to ADKF_RANK_K_MAX instead of
+ * ADKF_POOL_TOPK_MAX, the rank of up to ADKF_RANK_REFS_MAX named rows (known actives: enrichment factors and every retrospective
+ * screening metric) and the number of rows ranked.  Nothing of size T x rows exists.
+ *   score  adkf_predict_pool's, bit for bit: EI on the latent variance against best_f[t] in the ADKF_PM_MAXIMIZE sense, log EI with
+ *          ADKF_PM_LOG_EI, +mean (ADKF_PM_MAXIMIZE) or -mean with ADKF_PM_SCORE_MEAN.  A row is ELIGIBLE when its score is not NaN and
+ *          it is not in the task's exclusion list (excl_idx / excl_off as adkf_predict_pool).  THE ORDER: larger score first, equal
+ *          scores by ascending row; -0 and +0 tie; a score of -inf is eligible and comes last.
+ *   flags  ADKF_PM_LATENT (accepted, no score reads it), ADKF_PM_MAXIMIZE, ADKF_PM_SCORE_MEAN, ADKF_PM_LOG_EI (not with SCORE_MEAN);
+ *          any other bit is ADKF_E_BADARG.  best_f [T] is required unless the score is the mean.
+ *   k, top_idx, top_val   [T, k], 0 <= k <= ADKF_RANK_K_MAX: the first k eligible rows in the order, -1 / -inf where fewer are
+ *          eligible.  top_val has the score's own bits, the sign of a zero included.  The first min(k, 64) entries are
+ *          adkf_predict_pool's selection.  k == 0 needs M > 0 or n_ranked.
+ *   ref_idx, M, ref_rank, ref_val   [T, M], 0 <= M <= ADKF_RANK_REFS_MAX (ref_idx nullable with M == 0): ref_rank[t, j] is the number
+ *          of eligible pool rows that come strictly before row ref_idx[t, j] in the order - 0-based, counted whether or not the row
+ *          itself is excluded (an excluded row gets the position it would take) - and ref_val[t, j] that row's score.  An eligible
+ *          row with ref_rank < k is top_idx[t, ref_rank].  An entry outside [0, rows) or a row with a NaN score gives -1 / NaN;
+ *          repeated entries are independent.
+ *   n_ranked   [T], nullable: the eligible rows of the task, the denominator of every percentile.
+ *   b, ws  support-only, of either kind (ADKF_BATCH_ARD or not), plain, refined and float64 tasks, as for adkf_mix_pool; REUSE_DIST /
+ *          REUSE_INNER and info [T] as for adkf_predict_pool.  Tasks with n_s == 0 or info != 0: top_idx -1, top_val -inf,
+ *          ref_rank -1, ref_val NaN, n_ranked 0.
+ *   scratch   adkf_rank_pool_scratch_bytes(T, k, M, d) bytes, 8-byte aligned.  With r(x) = x rounded up to a multiple of 256:
+ *              r(4 T ADKF_RANK_CHUNK_ROWS)                 the score plane of one chunk (the pool is walked in such chunks, each
+ *                                                          through prediction's own launch, so the scores are adkf_predict_pool's)
+ *            + r(16 T k) + r(8 T k) + r(8 T)               two sorted lists per task, rows and scores, and which one is current
+ *            + r(4 T M d) + 2 r(4 T M) + r(8 (T + 1))      the refs' rows as a packed query set, prediction's outputs on them and
+ *                                                          its offsets (the refs' scores are known before the walk: prediction's
+ *                                                          packed launch on T M rows, which has the pool launch's bits)
+ *          It depends on neither rows nor ns_max; the size function returns 0 for T < 1, d < 1, k or M out of range.  The ranks are
+ *          counted in ref_rank and n_ranked themselves.
+ * Asynchronous on `stream`, no allocation, no synchronisation, no device-to-host read, no floating-point atomics: capturable, and
+ * reproducible to the bit; a task's result depends on its own data, best_f, exclusion list, refs and the pool only - not on the grid,
+ * on the other tasks or on where the chunk boundaries fall.
+ * Rejected before anything is launched, ADKF_E_BADARG unless noted: a batch with a query set; rows < 0; rows > 0 without X; a flag
+ * bit other than the four above; ADKF_PM_LOG_EI with ADKF_PM_SCORE_MEAN; k < 0; M < 0; k > ADKF_RANK_K_MAX or M > ADKF_RANK_REFS_MAX
+ * (ADKF_E_SIZE); the EI or log-EI score without best_f; excl_idx without excl_off; k > 0 without top_idx or top_val; M > 0 without
+ * ref_idx, ref_rank or ref_val; nothing asked for (k == 0, M == 0 and n_ranked NULL); scratch NULL; a scratch that is too small or
+ * not 8-byte aligned, or a workspace that is too small (ADKF_E_WORKSPACE). */
+#define ADKF_RANK_K_MAX 65536
+#define ADKF_RANK_REFS_MAX 1024
+#define ADKF_RANK_CHUNK_ROWS 16384 /* as ADKF_EHVI_CHUNK_ROWS / ADKF_MIX_CHUNK_ROWS: 64 KB of scratch per task */
+size_t adkf_rank_pool_scratch_bytes(int32_t T, int32_t k, int32_t M, int32_t d);
+int adkf_rank_pool(const adkf_batch_t* b, const float* phi, int32_t flags, const float* X, int64_t rows, const float* best_f, const int64_t* excl_idx, const int64_t* excl_off, int32_t k, int64_t* top_idx, float* top_val, const int64_t* ref_idx, int32_t M, int64_t* ref_rank, float* ref_val, int64_t* n_ranked, int32_t* info, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Monte-Carlo q-EI and noisy q-EI over a shared pool: a batch of q rows per task, chosen by sequential-greedy maximisation of the
  * sample-average joint improvement over S pathwise posterior draws (Wilson, Hutter and Deisenroth 2018, "Maximizing acquisition
  * functions for Bayesian optimization"; Balandat et al. 2020, BoTorch; the noisy incumbent of Letham et al. 2019, "Constrained
