@@ -40,6 +40,7 @@
 #include "mix_stream.h"
 #include "rank_stream.h"
 #include "qei_stream.h"
+#include "grad_stream.h"
 
 #include "host_common.h"
 #include "host_gp.h"
@@ -231,6 +232,12 @@ int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags
 int adkf_predict_marginal_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
                               const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
     return predict_marginal(true, b, phi, flags, Zq, q_off, rows, best_f, mean, var, ei, info, ws, ws_bytes, stream);
+}
+
+int adkf_predict_grad(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
+                      const float* best_f, const float* g_mean, const float* g_var, const float* g_ei, float* dZq, int32_t* info,
+                      void* ws, size_t ws_bytes, void* stream) {
+    return predict_grad(b, phi, flags, Zq, q_off, rows, best_f, g_mean, g_var, g_ei, dZq, info, ws, ws_bytes, stream);
 }
 
 size_t adkf_predict_pool_scratch_bytes(int32_t T, int32_t k) {

@@ -615,6 +615,92 @@ int predict_marginal(bool ard, const adkf_batch_t* b, const float* phi, int32_t 
     }
     return 0;
 }
+// Phi(u) / h(u) and phi(u) / h(u), h(u) = phi(u) + u Phi(u): the two ratios behind the derivatives of log EI.  Directly while
+// h keeps its digits in float64 (u > -20: the cancellation costs a^2 eps); below, with a = -u, h = phi b(a) and Phi = phi (1 - b) / a
+// from the series of log_h.
+void ei_ratios(double u, double& cdf_h, double& pdf_h) {
+    if (u > -20.0) {
+        const double cdf = 0.5 * std::erfc(-u / std::sqrt(2.0)), pdf = std::exp(-0.5 * u * u) / std::sqrt(2.0 * M_PI);
+        const double h = pdf + u * cdf;
+        cdf_h = cdf / h; pdf_h = pdf / h;
+        return;
+    }
+    const double a = -u, w = 1.0 / (a * a);
+    double sum = 1.0, term = 1.0;
+    for (int k = 1; k < 64; ++k) {
+        const double next = -term * (2 * k + 1) * w;
+        if (std::fabs(next) >= std::fabs(term)) break;
+        sum += term = next;
+    }
+    const double bb = w * sum;
+    pdf_h = 1.0 / bb; cdf_h = (1.0 - bb) / (a * bb);
+}
+
+// adkf_predict_grad: the coefficients a_m = d(sum of cotangent x output) / d mean and a_v = the same by the latent variance of a row
+// (include/adkf_gp.h).  Where the variance clamp is active the derivative through sigma is 0.
+struct GradCoef { double am, av; };
+GradCoef grad_coef(double mu, double vl, double bf, int flags, double gm, double gv, double ge, bool with_ei) {
+    GradCoef c{gm, gv};
+    if (!with_ei) return c;
+    const bool live = vl > 1e-12;
+    const double sg = std::sqrt(std::max(vl, 1e-12)), sgn = (flags & ADKF_PM_MAXIMIZE) ? 1.0 : -1.0;
+    const double u = sgn * (mu - bf) / sg;
+    if (flags & ADKF_PM_LOG_EI) {
+        double ch, ph;
+        ei_ratios(u, ch, ph);
+        c.am += ge * sgn * ch / sg;
+        if (live) c.av += ge * ph / (2.0 * vl);
+    } else {
+        c.am += ge * sgn * 0.5 * std::erfc(-u / std::sqrt(2.0));
+        if (live) c.av += ge * std::exp(-0.5 * u * u) / std::sqrt(2.0 * M_PI) / (2.0 * sg);
+    }
+    return c;
+}
+
+// adkf_predict_grad: dZq [rows, d] = the vector-Jacobian product of streaming prediction by the packed rows, in float64 on the scaled
+// features of prepare_task, rounded once.
+int predict_grad(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
+                 const float* best_f, const float* g_mean, const float* g_var, const float* g_ei, float* dZq, int32_t* info) {
+    if (int rc = check_support_only(b, phi, info, rows, ARD_EITHER)) return rc;
+    if (!q_off) return ADKF_E_BADARG;
+    if (rows > 0 && (!Zq || !dZq)) return ADKF_E_BADARG;
+    if (!g_mean && !g_var && !g_ei) return ADKF_E_BADARG;
+    if (g_ei && !best_f) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    if ((flags & ADKF_PM_LOG_EI) && !g_ei) return ADKF_E_BADARG;
+    const int d = b->d;
+    if (rows > 0) std::fill(dZq, dZq + (size_t)rows * d, 0.f);
+#pragma omp parallel for schedule(dynamic)
+    for (int t = 0; t < b->T; ++t) {
+        const int64_t lo = std::min(std::max<int64_t>(q_off[t], 0), rows), hi = std::min(std::max<int64_t>(q_off[t + 1], lo), rows);
+        TaskPrep p;
+        if (!prepare_task(b, phi, t, false, info, p)) continue;
+        const Inner& in = p.in;
+        const int n = in.n;
+        const float* y = b->y_s + (size_t)t * b->ns_max;
+        const double il2 = 1.0 / (in.l * in.l);
+        std::vector<double> kr(n), c(n), zt(d), W(n);
+        for (int64_t r = lo; r < hi; ++r) {
+            const float* x = Zq + (size_t)r * d;
+            for (int q = 0; q < d; ++q) zt[q] = ((double)x[q] - p.mu[q]) / p.l[q];
+            const Mat D = sqdist(zt.data(), 1, p.Zt.data(), n, d);
+            const MuQ pq = row_posterior(in, b->kernel, D.data(), y, kr.data(), c.data());
+            const GradCoef gc = grad_coef(pq.mu, in.s - pq.q, g_ei ? best_f[t] : 0.0, flags, g_mean ? g_mean[r] : 0.0, g_var ? g_var[r] : 0.0,
+                                          g_ei ? g_ei[r] : 0.0, g_ei != nullptr);
+            for (int i = 0; i < n; ++i) {
+                double k0, k1, k2;
+                kappa(b->kernel, D[i] * il2, k0, k1, k2);
+                W[i] = in.s * k1 * (gc.am * in.alpha[i] - 2.0 * gc.av * c[i]);
+            }
+            for (int q = 0; q < d; ++q) {
+                double s = 0.0;
+                for (int i = 0; i < n; ++i) s += W[i] * (zt[q] - p.Zt[(size_t)i * d + q]);
+                dZq[(size_t)r * d + q] = (float)(2.0 * il2 * s / p.l[q]);
+            }
+        }
+    }
+    return 0;
+}
 inline int nq_of(const adkf_batch_t* b, int t) { return b->n_q ? b->n_q[t] : b->nq_max; }
 
 // The quasi-Newton driver of csrc/inner.h (Bfgs + fit_advance), in float64.
@@ -790,6 +876,11 @@ int adkf_predict(const adkf_batch_t* b, const float* phi, float* mean, float* va
 int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
                           const float* best_f, float* mean, float* var, float* ei, int32_t* info, void*, size_t, void*) {
     return predict_marginal(false, b, phi, flags, Zq, q_off, rows, best_f, mean, var, ei, info);
+}
+
+int adkf_predict_grad(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,
+                      const float* best_f, const float* g_mean, const float* g_var, const float* g_ei, float* dZq, int32_t* info, void*, size_t, void*) {
+    return predict_grad(b, phi, flags, Zq, q_off, rows, best_f, g_mean, g_var, g_ei, dZq, info);
 }
 
 int adkf_predict_marginal_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows,

@@ -1,5 +1,5 @@
 // Host side of streaming prediction on a support-only batch (adkf_predict_marginal, adkf_predict_pool, adkf_thompson_pool, their
-// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_liar_pool, adkf_levelset_pool, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ipv_pool, adkf_jackknife_pool, adkf_ehvi_pool, adkf_mix_pool, adkf_rank_pool and adkf_qei_pool): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
+// ARD forms, adkf_believer_pool, adkf_believer_pool_ard, adkf_liar_pool, adkf_levelset_pool, adkf_mes_pool, adkf_gibbon_pool, adkf_gumbel_pool, adkf_kg_pool, adkf_jes_pool, adkf_ipv_pool, adkf_jackknife_pool, adkf_ehvi_pool, adkf_mix_pool, adkf_rank_pool, adkf_qei_pool and adkf_predict_grad): the inner quantities into the workspace, the row-tile slots borrowed from it, the scratch layouts, the launch drivers the
 // pool calls share (pool_walks, pool_select, pool_greedy) and the body of every entry.
 #pragma once
 #include "host_ard.h"
@@ -340,6 +340,57 @@ int predict_marginal(bool ard, const adkf_batch_t* b, const float* phi, int32_t 
     if (rows == 0) return 0;
     const PmCall io{flags, Zq, q_off, rows, best_f, mean, var, ei, info, nullptr};
     return ard ? pm_launch<true>(c, io) : pm_launch<false>(c, io);
+}
+
+// The launches of a prepared adkf_predict_grad call (grad_stream.h): the tile kernel for the plain tasks where its three row tiles fit
+// in LDS (up to 128 points; otherwise the row kernel takes them too), the row kernel for the rest.
+template <bool ARD>
+int pg_launch(const PmCtx& c, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows, const float* best_f, PgArgs g, const int32_t* info) {
+    hipStream_t st = c.st;
+    const int T = c.b.T, ns = c.b.ns_max;
+    PmArgs pa = pm_args(c, flags, Zq, rows, info);
+    pa.q_off = q_off; pa.best_f = best_f;
+    hipMemsetAsync(g.dZq, 0, sizeof(float) * (size_t)rows * c.b.d, st);   // rows of no task's range and of skipped tasks stay 0
+    if constexpr (ARD) launch_ard_il(c);
+    PgArgsOf<ARD> k{};
+    k.p = pa;
+    if constexpr (ARD) k.r = c.r;
+    k.g = g;
+    constexpr int static_lds = (2 * PM_TM * LD_MN + 2 * PM_TM + 4 * PM_TM + 3 * PM_TM) * (int)sizeof(float);
+    constexpr int dyn_max = PM_LDS_BYTES - static_lds;
+    static const bool optin = lds_optin(dyn_max, {kernel_ptr(&k_predict_grad_tile<ARD>)});
+    const size_t dyn = ((size_t)3 * PM_TM * pa.buf_ld + (pa.buf_ld - 4)) * sizeof(float);
+    const bool tile = optin && ns <= 128 && dyn <= (size_t)dyn_max;
+    k.g.row_kinds = tile ? 6 : 7;
+    if (tile) {
+        const int64_t tiles = rows / PM_TM + T;   // upper bound (the true count depends on q_off, which lives on the device)
+        const int grid = pm_persistent_grid(k_predict_grad_tile<ARD>, PM_NT, dyn, tiles);
+        k_predict_grad_tile<ARD><<<grid, PM_NT, dyn, st>>>(k);
+    }
+    const size_t dyn_row = pg_row_lds(ns, c.w.w64 != nullptr);
+    static const bool optin_row = lds_optin(pg_row_lds(MAX_POINTS, false), {kernel_ptr(&k_predict_grad_row<ARD>)});
+    if (dyn_row > 64 * 1024 && !optin_row) return ADKF_E_LAUNCH;
+    k_predict_grad_row<ARD><<<dim3((unsigned)std::min<int64_t>(rows, 64), T), PG_NT, dyn_row, st>>>(k);
+    LAUNCH_OK();
+    return 0;
+}
+
+// adkf_predict_grad: one entry for isotropic and ARD batches
+int predict_grad(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows, const float* best_f,
+                 const float* g_mean, const float* g_var, const float* g_ei, float* dZq, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
+    int rc = check_support_only(b, phi, info, ws, rows);
+    if (rc) return rc;
+    if (!q_off || (rows > 0 && (!Zq || !dZq))) return ADKF_E_BADARG;
+    if (!g_mean && !g_var && !g_ei) return ADKF_E_BADARG;
+    if (g_ei && !best_f) return ADKF_E_BADARG;
+    if (flags & ~(ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI)) return ADKF_E_BADARG;
+    if ((flags & ADKF_PM_LOG_EI) && !g_ei) return ADKF_E_BADARG;
+    PmCtx c;
+    rc = pm_prepare(b, phi, info, ws, ws_bytes, stream, c);
+    if (rc) return rc;
+    if (rows == 0) return 0;
+    const PgArgs g{g_mean, g_var, g_ei, dZq, 0};
+    return c.ard ? pg_launch<true>(c, flags, Zq, q_off, rows, best_f, g, info) : pg_launch<false>(c, flags, Zq, q_off, rows, best_f, g, info);
 }
 
 // The candidate lists at the end of a scratch: n row indices (int64), then n scores

@@ -362,6 +362,50 @@ def loo_check(model, mb: MetaBatch, max_evals: int = 200):
     return out["loo_mean"], out["loo_var"], out["loo_lpd"], phi
 
 
+@torch.no_grad()
+def explain_hits(model, mb: MetaBatch, X_features: torch.Tensor, idx: torch.Tensor, of: str = "mean", maximize: bool = True,
+                 max_evals: int = 200) -> torch.Tensor:
+    """Why these rows: every task of ``mb`` is fitted on its support set as ``screen`` fits it, then returns the gradient of its
+    prediction at its chosen rows of the library ``X_features [rows, d]`` with respect to the rows' features - ``[T, k, d]``, the
+    saliency at the feature layer, ready to be pushed back through the extractor.  ``idx [T, k]`` (int64 library indices, typically
+    ``screen``'s ``top_idx``; -1 or out of range: a zero row).  ``of``: "mean", "var", or the acquisition "ei" / "log_ei" against each
+    task's best support label (largest with ``maximize``).  The chosen rows are gathered into ONE packed ``gp_ops.predict_grad`` call:
+    nothing of size T x rows is allocated."""
+    from . import gp_ops
+
+    if of not in ("mean", "var", "ei", "log_ei"):
+        raise ValueError(f'of must be "mean", "var", "ei" or "log_ei", got {of!r}')
+    was_training = model.training
+    model.eval()
+    b, phi = _fitted_support(model, mb, max_evals, "explanation")
+    dev = b.device
+    idx = torch.as_tensor(idx).to(device=dev, dtype=torch.int64)
+    if idx.dim() != 2 or idx.shape[0] != b.T:
+        raise ValueError(f"idx must be [T, k] = [{b.T}, k], got {tuple(idx.shape)}")
+    T, k = idx.shape
+    X = X_features.to(dev).float()
+    valid = (idx >= 0) & (idx < X.shape[0])
+    Zq = X[idx[valid]].contiguous()   # task-major: the valid rows of task 0, then those of task 1, ...
+    q_off = torch.zeros(T + 1, dtype=torch.int64, device=dev)
+    q_off[1:] = torch.cumsum(valid.sum(1), 0)
+    out = torch.zeros(T, k, b.d, dtype=torch.float32, device=dev)
+    if Zq.shape[0] > 0:
+        ones = torch.ones(Zq.shape[0], dtype=torch.float32, device=dev)
+        kw = {}
+        if of in ("ei", "log_ei"):
+            n_s = b.n_s if b.n_s is not None else torch.full((T,), b.ns, dtype=torch.int32, device=dev)
+            y = b.y_s.masked_fill(torch.arange(b.ns, device=dev)[None, :] >= n_s[:, None], float("-inf") if maximize else float("inf"))
+            kw = dict(g_ei=ones, best_f=(y.max(1).values if maximize else y.min(1).values), maximize=maximize, log_ei=of == "log_ei")
+        else:
+            kw = {"g_" + of: ones}
+        dZq, info = gp_ops.predict_grad(b, phi, Zq, q_off, **kw)
+        gp_ops.check_info(info, "explanation")
+        out[valid] = dZq
+    if was_training:
+        model.train()
+    return out
+
+
 def evaluate_tasks(model, tasks: Sequence[DKTBatch], names: Optional[Sequence[str]] = None, tasks_per_call: int = 64,
                    max_evals: int = 200, streaming: bool = False) -> Dict[str, object]:
     """``evaluate_adkt_model`` for tasks that are already in memory: per-task metric records, ``tasks_per_call`` tasks

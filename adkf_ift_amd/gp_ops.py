@@ -333,6 +333,58 @@ def predict_marginal(b: GPBatch, phi: torch.Tensor, Zq: torch.Tensor, q_off: tor
     return mean, var, ei, info
 
 
+def predict_grad(b: GPBatch, phi: torch.Tensor, Zq: torch.Tensor, q_off: torch.Tensor, *, g_mean: Optional[torch.Tensor] = None,
+                 g_var: Optional[torch.Tensor] = None, g_ei: Optional[torch.Tensor] = None, best_f: Optional[torch.Tensor] = None,
+                 maximize: bool = False, log_ei: bool = False):
+    """The vector-Jacobian product of ``predict_marginal`` with respect to the packed query rows, in one ``adkf_predict_grad`` call:
+    returns (dZq [rows, d], info [T]) with ``dZq[r] = d/dZq[r] (g_mean[r] mean[r] + g_var[r] var[r] + g_ei[r] ei[r])``.  The
+    cotangents are ``[rows]`` each and at least one must be given; ``g_ei`` needs ``best_f [T]`` and is the cotangent of log EI with
+    ``log_ei`` (``maximize`` as in ``predict_marginal``; the noise is a constant, so ``latent`` would change nothing and is not an
+    argument).  The support set and ``phi`` are constants of the call.  Rows of no task's range, and rows of tasks with no support
+    points or ``info != 0``, get 0.  Autograd-free, like the rest of this module (``models.predict_marginal_diff`` is the bridge).
+    Isotropic and ARD batches alike."""
+    lib = _lib.load()
+    if g_mean is None and g_var is None and g_ei is None:
+        raise ValueError("predict_grad needs at least one of g_mean, g_var, g_ei")
+    if g_ei is not None and best_f is None:
+        raise ValueError("g_ei needs best_f [T]")
+    if log_ei and g_ei is None:
+        raise ValueError("log_ei needs g_ei (the cotangent of log EI)")
+    if b.nq != 0:
+        raise ValueError("predict_grad takes a support-only batch (no Z_q / y_q): the query rows come packed in Zq")
+    phi = b.check_phi(phi)
+    Zq = _f32(Zq, "Zq")
+    if Zq.dim() != 2 or Zq.shape[1] != b.d:
+        raise ValueError(f"Zq must be [rows, d] = [rows, {b.d}], got {tuple(Zq.shape)}")
+    if not q_off.is_cuda or q_off.dtype != torch.int64 or q_off.numel() != b.T + 1:
+        raise ValueError(f"q_off must be int64 [T + 1] = [{b.T + 1}] on the GPU")
+    q_off = q_off.contiguous()
+    rows = Zq.shape[0]
+    cot = {}
+    for name, t in (("g_mean", g_mean), ("g_var", g_var), ("g_ei", g_ei)):
+        if t is not None:
+            t = _f32(t, name).reshape(-1)
+            if t.numel() != rows:
+                raise ValueError(f"{name} must have rows = {rows} entries, got {t.numel()}")
+        cot[name] = t
+    if best_f is not None:
+        best_f = _f32(best_f, "best_f").reshape(-1)
+        if best_f.numel() != b.T:
+            raise ValueError(f"best_f must have T = {b.T} entries")
+    for name, t in (("Zq", Zq), ("q_off", q_off), ("best_f", best_f), *cot.items()):
+        if t is not None and t.device != b.device:
+            raise ValueError(f"{name} lives on {t.device}, the batch on {b.device}")
+    dZq = _new(b, rows, b.d)
+    info = _new(b, b.T, dtype=torch.int32)
+    flags = (_lib.PM_MAXIMIZE if maximize else 0) | (_lib.PM_LOG_EI if log_ei else 0)
+    ws, nb = b.workspace()
+    cb = b.c_struct()
+    _lib.check(lib.adkf_predict_grad(C.byref(cb), ptr(phi), flags, ptr(Zq), ptr(q_off), rows, ptr(best_f), ptr(cot["g_mean"]),
+                                     ptr(cot["g_var"]), ptr(cot["g_ei"]), ptr(dZq), ptr(info), ptr(ws), nb, stream(b.device)),
+               "adkf_predict_grad")
+    return dZq, info
+
+
 def pack_exclude(exclude, T: int, rows: int, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The exclusion lists of ``predict_pool`` in the library's layout: ``(excl_idx, excl_off)``, both int64, task t's rows in
     ``excl_idx[excl_off[t]:excl_off[t + 1]]`` sorted ascending, without duplicates or entries outside ``[0, rows)``.

@@ -211,6 +211,43 @@ class _OuterNLLFunction(torch.autograd.Function):
         return grad_out * dZs, None, grad_out * dZq, None, grad_out * g, None, None, None
 
 
+class _PredictMarginalFunction(torch.autograd.Function):
+    """Streaming prediction of packed query rows (``gp_ops.predict_marginal``), differentiable in ``Zq`` ONLY: ``phi`` and the
+    support set are constants of the fitted state (their gradients are None).  The backward is one ``gp_ops.predict_grad`` call
+    with the three incoming cotangents.  Without ``best_f`` the third output is a tensor of zeros that nothing depends on."""
+
+    @staticmethod
+    def forward(ctx, Zq, b, phi, q_off, best_f, latent, maximize, log_ei):
+        Zq_d = Zq.detach().float().contiguous()
+        mean, var, ei, info = gp_ops.predict_marginal(b, phi.detach(), Zq_d, q_off, latent=latent, best_f=best_f, maximize=maximize,
+                                                      log_ei=log_ei)
+        gp_ops.check_info(info, "streaming prediction")
+        ctx.save_for_backward(Zq_d, phi.detach(), q_off)
+        ctx.b, ctx.best_f, ctx.maximize, ctx.log_ei = b, best_f, maximize, log_ei
+        if ei is None:
+            ei = torch.zeros_like(mean)
+            ctx.mark_non_differentiable(ei)
+        return mean, var, ei
+
+    @staticmethod
+    def backward(ctx, g_mean, g_var, g_ei):
+        Zq, phi, q_off = ctx.saved_tensors
+        with_ei = ctx.best_f is not None
+        dZq, info = gp_ops.predict_grad(ctx.b, phi, Zq, q_off, g_mean=g_mean, g_var=g_var, g_ei=g_ei if with_ei else None,
+                                        best_f=ctx.best_f, maximize=ctx.maximize, log_ei=ctx.log_ei and with_ei)
+        gp_ops.check_info(info, "streaming prediction gradient")
+        return dZq, None, None, None, None, None, None, None
+
+
+def predict_marginal_diff(b: "gp_ops.GPBatch", phi: torch.Tensor, Zq: torch.Tensor, q_off: torch.Tensor, *, latent: bool = False,
+                          best_f: Optional[torch.Tensor] = None, maximize: bool = False, log_ei: bool = False):
+    """``gp_ops.predict_marginal`` under autograd: (mean [rows], var [rows], ei [rows]) of the packed rows ``Zq [rows, d]`` against
+    the fitted support-only batch ``b``, differentiable in ``Zq`` - a loss on the predictive moments of a query set backpropagates
+    into whatever produced the rows (a feature head, the rows themselves in feature-space ascent of an acquisition).  ``phi`` and
+    the support set are constants: no gradient reaches them.  ``ei`` is log EI with ``log_ei``, and zeros without ``best_f``."""
+    return _PredictMarginalFunction.apply(Zq, b, phi, q_off, best_f, bool(latent), bool(maximize), bool(log_ei))
+
+
 def fit_gpytorch_scipy(mll: ExactMarginalLogLikelihood, max_evals: int = 200, gtol: float = 1e-5, ftol: float = gp_ops.FTOL_DEFAULT):
     """Drop-in for ``botorch.optim.fit.fit_gpytorch_scipy(model.mll)``: minimises -mll over the raw GP parameters on the
     GPU (in-kernel BFGS for the three-parameter kernel, device L-BFGS for ARD) and writes the optimum back into the

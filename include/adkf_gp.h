@@ -212,6 +212,32 @@ int adkf_predict_marginal(const adkf_batch_t* b, const float* phi, int32_t flags
  * Outputs, zeroed rows and info as adkf_predict_marginal; info as ARD adkf_predict reports it. */
 int adkf_predict_marginal_ard(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows, const float* best_f, float* mean, float* var, float* ei, int32_t* info, void* ws, size_t ws_bytes, void* stream);
 
+/* Feature gradients of streaming prediction: the vector-Jacobian product of adkf_predict_marginal(_ard) with respect to the packed
+ * query rows (csrc/grad_stream.h),
+ *     dZq[r, :] = d/dZq[r, :] ( g_mean[r] mean[r] + g_var[r] var[r] + g_ei[r] ei[r] ),
+ * for saliency at the feature layer, losses on the predictive moments of a query set, and ascent of an acquisition in feature space.
+ *   b      support-only as for adkf_predict_marginal; with ADKF_BATCH_ARD in b->flags the call behaves as
+ *          adkf_predict_marginal_ard (phi [T, 2 + d], ws of adkf_workspace_bytes_ard(T, ns_max, 0, d) bytes), without it as
+ *          adkf_predict_marginal (adkf_workspace_bytes(T, ns_max, 0, d)).  REUSE_DIST / REUSE_INNER mean what they mean there.
+ *          The workspace does not depend on rows; every size the library accepts is served.
+ *   Zq, q_off, rows, best_f   as adkf_predict_marginal;
+ *   flags  ADKF_PM_LATENT | ADKF_PM_MAXIMIZE | ADKF_PM_LOG_EI, as there.  The noise is a constant of the row, so ADKF_PM_LATENT changes no
+ *          gradient; with ADKF_PM_LOG_EI g_ei is the cotangent of log EI;
+ *   g_mean, g_var, g_ei   [rows] each, nullable (a missing one is a cotangent of 0);
+ *   dZq    [rows, d], overwritten: the gradient with respect to the RAW row (ARD: the 1 / l of the scaling included).  Rows that
+ *          belong to no task's range, and the rows of tasks with n_s == 0 or info != 0, are 0.  A row whose three cotangents are 0 is
+ *          exactly 0; a NaN in a row's features or cotangents stays in that row.  With k_i = os kappa(u_i), u_i = |x - z_i|^2 / l^2,
+ *          c = k A^-1, alpha = A^-1 y, sigma = sqrt(max(var_latent, 1e-12)):
+ *              a_m = g_mean + g_ei dE/dmean,   a_v = g_var + g_ei dE/dvar,   W_i = os kappa'(u_i) (a_m alpha_i - 2 a_v c_i),
+ *              dZq[r, :] = (2 / l^2) ( (sum_i W_i) x - sum_i W_i z_i ),
+ *          dEI/dmean = -+Phi(u), dEI/dvar = phi(u) / (2 sigma); d log EI/dmean = -+Phi / (sigma h), d log EI/dvar = (phi / h) / (2 var),
+ *          the ratios Phi / h and phi / h formed without cancellation for u << 0.  Where the clamp of sigma is active
+ *          (var_latent <= 1e-12) the derivative through sigma is 0.
+ * ADKF_E_BADARG, before anything is launched: a batch with a query set, rows < 0, rows > 0 without Zq or dZq, no cotangent at all,
+ * g_ei without best_f, ADKF_PM_LOG_EI without g_ei, any other flag bit.  A short workspace is ADKF_E_WORKSPACE.
+ * Asynchronous, no allocation, capturable, no atomics; a row's result depends on its task and its own features only. */
+int adkf_predict_grad(const adkf_batch_t* b, const float* phi, int32_t flags, const float* Zq, const int64_t* q_off, int64_t rows, const float* best_f, const float* g_mean, const float* g_var, const float* g_ei, float* dZq, int32_t* info, void* ws, size_t ws_bytes, void* stream);
+
 /* Shared-pool prediction: every task of the batch scores the SAME rows X [rows, d], and the call can return each task's best k
  * rows itself, so that nothing of size T x rows has to exist unless the caller asks for it (Bayesian-optimisation replicates
  * over one candidate pool, virtual screening).
